@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the TDNet per-frame hot path on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model td4|td2|psp] [--size HxW]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model td4|td2|psp] [--size HxW] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times EXACTLY K steps, writes the last timed step's outputs if --dump-outputs is given, and prints the
+line: `value` (frames/s) and `ms_per_step` come from those K steps alone.  Everything else the line can carry (the objects below,
+the N-rank rank check and solo scaling run, the host launch cost) is measured only with --full.
+
+--dump-outputs DIR  after the timed steps: what the last step returned to its caller (logits, float32) as DIR/<name>.npy, one file per
+                    returned array (`logits`, or `logits_<i>` when a step returns several; `rank<r>_` in front at N > 1).  An array is
+                    written whole when it fits the 56 MB budget of the run, else as a fixed seeded sample of its flattened elements
+                    (`<name>_sample.npy`: one element at a seeded offset in each of k equal strides).  Weights and frames are seeded,
+                    so the same arguments give the same inputs in every run and two builds can be compared file for file.
 
 A "step" is one frame of one synthetic video clip through model(image, pos_id) (Testing/test.py:53): sub-network
 forward + attention propagation from the cached frames + head + x8 upsample to full-resolution logits.  Frames are
@@ -14,7 +24,7 @@ N ranks: under `python -m torch.distributed.run ...` (WORLD_SIZE set) this proce
 node has fewer than N GPUs: `python bench.py --gpus 8` never quietly measures one GPU.  Every line carries
 `world_size_seen` (an all-reduce of ones), `rccl_bcast_ms` and the per-rank frames/s.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel: achieved = executed FLOP per launch / average launch duration (HIP events on the forward's
                 stream during a profiled replay right after the timed region); peak = 157.3 TFLOP/s fp32 MFMA
                 (MI355X_MICROARCH.md); traffic = HBM-side bytes per launch of that kernel SYMBOL, measured in this run by two
@@ -66,8 +76,15 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-frames", type=int, default=5, help="steady-state frames timed on the CPU oracle (SURVEY 8d: >= 5)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short legs for BASELINE configs[1] (td2-psp18 1024x2048 fp32) and configs[4] (td2-psp34 720x960 fp16, the "
-                         "stand-in for the BiSeNet-34 the reference does not contain) that the default N = 1 run appends as `other_configs`")
-    ap.add_argument("--quick", action="store_true", help="= --no-cpu-baseline --no-pmc --no-direct-line --no-other-configs, no `sustained` window (A/B and profiler runs)")
+                         "stand-in for the BiSeNet-34 the reference does not contain) that a --full N = 1 run appends as `other_configs`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: sustained window, host launch cost, roofline / breakdown "
+                         "(profiled replay), latency_ms_synced, all-direct line, PMC traffic passes, hipgraph, CPU baseline + parity, "
+                         "other_configs, numerics_stress; at N > 1 the solo scaling run and the rank check.  The --no-* options and "
+                         "--quick switch parts of it off.  Off by default: a plain run times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (logits, float32; a seeded sample beyond the 56 MB budget) as DIR/<name>.npy")
+    ap.add_argument("--quick", action="store_true", help="with --full: = --no-cpu-baseline --no-pmc --no-direct-line --no-other-configs, no `sustained` window (A/B and profiler runs)")
     ap.add_argument("--perturb-rank", type=int, default=-1,
                     help="TEST ONLY: this rank scales one weight tensor by 1.001 after the broadcast; the N-rank line must then say "
                          "ranks_agree false and the run must exit non-zero (tests/test_bench_launch.py)")
@@ -92,7 +109,7 @@ def parse_args(argv=None):
                          "parallel.FramePipelinedStream; a step = one round of two frames; throughput mode for maps that leave CUs idle)")
     ap.add_argument("--graph", action="store_true",
                     help="the timed loop replays ONE hipGraph per pos_id cycle (P frame calls captured on a stream in steady state: tdnet_amd/graph.py) "
-                         "instead of enqueueing every frame's launches; a step is then one cycle of P frames.  The default run reports the same comparison "
+                         "instead of enqueueing every frame's launches; a step is then one cycle of P frames.  A --full run reports the same comparison "
                          "as the `hipgraph` object of the line without changing `value`")
     ap.add_argument("--no-numerics-stress", action="store_true", help="skip the un-calibrated-init numerics leg (`numerics_stress`: fp64 oracle on 4 frames at 769x1537)")
     ap.add_argument("--dry-run", action="store_true",
@@ -247,6 +264,40 @@ def logits_digest(out, torch):
     v = out.contiguous().view(torch.int32).flatten().to(torch.int64)
     idx = (torch.arange(v.numel(), device=v.device, dtype=torch.int64) % 65521) + 1
     return [int(v.sum().item()), int((v * idx).sum().item())]
+
+
+DUMP_BUDGET_ELEMS = 14 * 2 ** 20                  # float32 elements over all files of a run (56 MB)
+
+
+def dump_outputs(outs, d, rank, world, torch, np):
+    """--dump-outputs: the arrays one step returned to its caller as DIR/<name>.npy, float32.  An array over its share of the budget is
+    written as a sample: k equal strides of the flattened array, one element per stride at an offset drawn from a generator seeded by
+    (k, numel), so two runs of the same arguments sample the same elements.  Returns {file name: what it holds} for the line."""
+    outs = [o for o in outs if torch.is_tensor(o)]
+    if not outs:
+        return {}
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET_ELEMS // (len(outs) * world)
+    files = {}
+    for i, o in enumerate(outs):
+        name = ("rank%d_" % rank if world > 1 else "") + ("logits" if len(outs) == 1 else "logits_%d" % i)
+        flat = o.detach().reshape(-1)
+        n = flat.numel()
+        if n <= share:
+            arr = o.detach().float().cpu().numpy()
+            what = {"shape": list(o.shape), "elements": "all"}
+        else:
+            stride = -(-n // share)
+            k = n // stride
+            off = np.random.default_rng([k, n]).integers(0, stride, k)
+            idx = torch.from_numpy(np.arange(k, dtype=np.int64) * stride + off).to(flat.device)
+            arr = flat[idx].float().cpu().numpy()
+            name += "_sample"
+            what = {"shape": list(o.shape), "elements": "sample of %d: flat index i * %d + offset_i, offsets ~ U[0, %d) from default_rng([%d, %d])"
+                                                        % (k, stride, stride, k, n)}
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        files[name + ".npy"] = what
+    return files
 
 
 def profile_dominant(eng, step_one, nprof, sync, torch):
@@ -647,19 +698,22 @@ def main():
     if args.mode == "frame-pipelined" and not args.dry_run:
         fpl = parallel.FramePipelinedStream(models[:2], P, dev, (H, W))
         C = 1
-        # the line says "bit-identical outputs": hold the two-lane path to ONE handle on a replay from an empty FIFO, in this run
-        with torch.no_grad():
-            nchk_ = P + 4
-            one = [models[0](clip[t % NF], pos_id=t % P).clone() for t in range(nchk_)]
-            models[0].reset()
-            two = fpl.process([clip[t % NF] for t in range(nchk_)])
-            fpl_same = all(torch.equal(x, y) for x, y in zip(one, two))
-            del one, two
-            fpl.reset()
+        # --full: the line says "bit-identical outputs": hold the two-lane path to ONE handle on a replay from an empty FIFO, in this run
+        if args.full:
+            with torch.no_grad():
+                nchk_ = P + 4
+                one = [models[0](clip[t % NF], pos_id=t % P).clone() for t in range(nchk_)]
+                models[0].reset()
+                two = fpl.process([clip[t % NF] for t in range(nchk_)])
+                fpl_same = all(torch.equal(x, y) for x, y in zip(one, two))
+                del one, two
+                fpl.reset()
     gclip = {"g": None}
     if args.graph and (C != 1 or fpl is not None or pp is not None or args.dry_run):
         raise SystemExit("bench.py --graph: one clip per GPU in the default mode only")
     FR = C * (2 if fpl is not None else 1) * (P if args.graph else 1)   # frames per step and rank (--graph: a step = one cycle of P frames)
+
+    keep_outs = args.dump_outputs is not None                         # --dump-outputs: state["outs"] = what the last step of the run returned
 
     def step(ms=None, n_clips=None):
         ms = models if ms is None else ms
@@ -667,10 +721,14 @@ def main():
         if fpl is not None and ms is models:                          # one round: frames t, t + 1 of the clip, no join between rounds
             out = fpl.process([clip[t % NF], clip[(t + 1) % NF]], first_frame=t, join=False)
             state["t"] = t + 2
+            if keep_outs:
+                state["outs"] = list(out)
             return out[0]
         if gclip["g"] is not None and ms is models:                   # --graph: one replay = P frames (t is a multiple of P here)
             out = gclip["g"].replay([clip[(t + j) % NF] for j in range(P)])
             state["t"] = t + P
+            if keep_outs:
+                state["outs"] = list(out)
             return out[0]
         if args.dry_run:
             clip[t % NF].add_(1.0)
@@ -680,13 +738,19 @@ def main():
             # PathParallelStream.process keeps pos_id = t mod P only if rounds start at multiples of lcm(world, P): NF = 8 does
             out = pp.process([clip[(t + j) % NF] for j in range(world)], first_frame=t)
             state["t"] = t + world
+            if keep_outs:
+                state["outs"] = [out[i] for i in sorted(out)]
             return out
         out = None
+        outs = []
         for c in range(len(ms) if n_clips is None else n_clips):
             with torch.cuda.stream(streams[c]):
                 o = ms[c](clips[c][t % NF], pos_id=t % P)
             out = o if out is None else out
+            outs.append(o)
         state["t"] = t + 1
+        if keep_outs and ms is models:
+            state["outs"] = outs
         return out
 
     def timed(nsteps, ms=None):
@@ -715,7 +779,7 @@ def main():
         # host cost of ENQUEUEING a frame (all of its launches, events and stream waits), measured on an empty queue so that the host
         # never waits for the device: when this approaches ms_per_step the rank is CPU-bound, which an 8-rank node can be with 8
         # launcher processes on one socket
-        nh = 0 if args.pmc_child else 4                               # (a counter pass counts bytes per frame: no extra frames there)
+        nh = 4 if args.full and not args.pmc_child else 0            # (a counter pass counts bytes per frame: no extra frames there)
         parallel.barrier()
         th0 = time.perf_counter()
         for _ in range(nh):
@@ -725,7 +789,7 @@ def main():
         # N > 1: the SAME process's 1-rank figure, in the same invocation -- rank 0 runs the K steps alone while the others wait at a barrier -- so
         # that the line carries its own scaling efficiency (N-rank per-GPU frames/s / this) instead of leaning on another run of another box
         solo_dt = None
-        if world > 1 and pp is None and not args.pmc_child:
+        if world > 1 and pp is None and not args.pmc_child and args.full:
             parallel.barrier()
             if rank == 0:
                 sync()
@@ -735,11 +799,15 @@ def main():
                 sync()
                 solo_dt = time.perf_counter() - ts0
             parallel.barrier()
+        state.pop("outs", None)
         dt = timed(args.steps)
+        dumped = None
+        if keep_outs and not args.pmc_child:                          # the last timed step's outputs, before anything runs again
+            dumped = dump_outputs(state.get("outs", []), args.dump_outputs, rank, world, torch, np)
         # `value` stays the contract's EXACTLY K steps; a window under 0.5 s (K = 20 at 275 frames/s is 73 ms) is re-measured over as
         # many frames as fill 0.5 s -- the same number on every rank (derived from the all-reduced K-step time) -- and printed beside it
         sustained = None
-        if not args.pmc_child and not args.dry_run and not args.quick and args.steps > 0:
+        if args.full and not args.pmc_child and not args.dry_run and not args.quick and args.steps > 0:
             dt_all = parallel.allreduce_max(torch.tensor([dt], dtype=torch.float64, device=dev)).item()
             if dt_all < 0.5:
                 n_long = int(min(20000, max(args.steps + 1, round(0.6 * args.steps / max(dt_all, 1e-6)))))
@@ -777,14 +845,14 @@ def main():
            "bcast_bytes": 4 * nparam if world > 1 else 0, "per_rank_fps": [round(v, 3) for v in per_rank],
            "per_rank_fps_min_max_spread": [round(min(per_rank), 3), round(max(per_rank), 3), round((max(per_rank) - min(per_rank)) / max(max(per_rank), 1e-9), 4)],
            "init_s_per_rank": [round(v, 2) for v in init_rank],
-           "host_launch_us_per_frame": [round(v, 1) for v in host_rank],
+           "host_launch_us_per_frame": [round(v, 1) for v in host_rank] if nh else None,
            "cpu_affinity": aff_rank if aff_rank is not None else "not pinned (N = 1: the whole host, %d CPUs allowed)" % (len(allowed0) if allowed0 else os.cpu_count() or 1),
            "omp_num_threads": (aff or {}).get("omp_num_threads", torch.get_num_threads()),
            "hw_queues": __import__("tdnet_amd").hw_queue_note(),
            "config": {"workload": "%s, %dx%d Cityscapes-shaped synthetic stream, %d-frame feature cache, %d clip%s per GPU"
                                   % (mname, H, W, spec.fifo, C, "" if C == 1 else "s (concurrent HIP streams)"),
                       "parallelism": ("clip-parallel x%d, RCCL weight broadcast only; each clip with TWO FRAMES IN FLIGHT (two handles sharing one weight block on two "
-                                      "HIP streams, cache entries handed over between encode and propagate; outputs held bit for bit to one handle in this run: "
+                                      "HIP streams, cache entries handed over between encode and propagate; outputs held bit for bit to one handle in a --full run: "
                                       "see two_lanes_bit_identical_to_one_handle)" % world) if fpl is not None else
                                      ("clip-parallel x%d, RCCL weight broadcast only" % world) if pp is None else
                                      ("path-parallel x%d: one stream, one all-gather of %d cache entries per round" % (world, world)),
@@ -802,20 +870,23 @@ def main():
                              "what": "ONE broadcast of the flat weight blob at start (timed between two barriers, so it includes the slowest rank's readiness); "
                                      "end-of-run all-reduces of timing / digests / confusion matrix; no per-frame collective",
                              "hw_queues_per_rank": hwq_rank}
-        if solo_dt is not None or rank != 0:
+        if args.full and (solo_dt is not None or rank != 0):
             solo_fps = None if solo_dt is None else FR * args.steps / solo_dt
             res["scaling_check"] = {"solo_fps_rank0": None if (solo_fps is None or args.dry_run) else round(solo_fps, 3),
                                     "per_gpu_fps": None if args.dry_run else round(fps / world, 3),
                                     "scaling_efficiency": None if (solo_fps is None or args.dry_run) else round(fps / world / solo_fps, 4),
                                     "what": "rank 0 alone ran the same K steps in this invocation (the other ranks waiting at a barrier) right before the N-rank timed "
                                             "loop: efficiency = N-rank frames/s per GPU / that.  No curve has been measured by the builder (no multi-GPU box)"}
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped, "dtype": "float32",
+                               "what": "what the last of the --steps timed steps returned to its caller"}
     if sustained is not None:
         res["sustained"] = {"steps_timed": sustained[0], "seconds": round(sustained[1], 4),
                             "value": round(world * FR * sustained[0] / sustained[1], 3),
                             "unit": "frames/s", "ms_per_step": round(1e3 * sustained[1] / sustained[0], 4),
                             "note": "the same timed loop (barrier + synchronize on both sides, max over ranks) over >= 0.5 s, because --steps %d "
                                     "is a %.0f-ms window; `value` above is exactly --steps frames" % (args.steps, 1e3 * tmax)}
-    if fpl is not None:
+    if fpl is not None and fpl_same is not None:
         res["two_lanes_bit_identical_to_one_handle"] = bool(fpl_same)
         if not fpl_same:
             res["FAILED"] = "frame-pipelined outputs differ from the single handle's"
@@ -829,13 +900,13 @@ def main():
         res["dry_run"] = True
         res["metric"] = "DRY RUN (launch plumbing only, no model): " + res["metric"]
 
-    exit_code = 5 if (fpl is not None and not fpl_same) else 0
+    exit_code = 5 if (fpl is not None and fpl_same is False) else 0
     # ---- N > 1: the line must be able to FAIL.  Every rank replays RANK 0's clip for P + 2 frames and contributes a 64-bit digest of each
     # frame's logits bits plus its label histogram; MIN and MAX all-reduces must coincide (every rank bit-identical to rank 0, whose
     # output is held to the CPU oracle below), and the 19x19 confusion matrices (each rank's labels vs the oracle's) are
     # summed over the ranks into the line.  --dry-run does the same over the broadcast weight bytes (there is no model on the CPU).
     ref_labels = None
-    if world > 1 and pp is None:
+    if world > 1 and pp is None and args.full:
         nchk = P + 2
         my_labels = []
         if args.dry_run:
@@ -897,11 +968,12 @@ def main():
         dist.all_reduce(code, op=dist.ReduceOp.MAX)                            # every rank leaves with the same verdict
         exit_code = int(code.item())
     if rank == 0 and not args.dry_run:
+        res["config"]["kernel_opts"] = model.engine.opts()
+    if rank == 0 and not args.dry_run and args.full:
         eng = model.engine
         opts = eng.opts()
         gflop = eng.flops_per_frame() / 1e9
         peak = PEAK_FP16_MFMA_TFLOPS if opts["precision"] == 1 else PEAK_BF16X3_TFLOPS if opts["precision"] == 2 else PEAK_FP32_MFMA_TFLOPS
-        res["config"]["kernel_opts"] = opts
         # ---- roofline of the dominant kernel: profiled replay (HIP events around every launch, same stream) ----------
         nprof = 2 * P
         if world > 1 and pp is None:
@@ -1044,7 +1116,7 @@ def main():
                 exit_code = 3
             del ref
 
-        # ---- the other single-GPU configs of BASELINE.json on the same line (default N = 1 run only) --------------------------
+        # ---- the other single-GPU configs of BASELINE.json on the same line (--full N = 1 run only) ---------------------------
         default_workload = args.model == "td4" and args.backbone == "resnet18" and (H, W) == (1024, 2048) and args.precision == "fp32" and C == 1
         if world == 1 and pp is None and default_workload and not args.no_other_configs:
             ncpu = 0 if args.no_cpu_baseline else 5                       # >= 5 steady-state frames on the CPU

@@ -26,7 +26,7 @@ def _last_json(out):
 
 
 def test_self_spawn_two_ranks_over_gloo():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run"], env=_env(), cwd=ROOT,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full"], env=_env(), cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0, out[-3000:]
@@ -45,7 +45,7 @@ def test_self_spawn_two_ranks_over_gloo():
 def test_a_rank_with_different_weights_fails_the_run():
     """--perturb-rank (TEST ONLY) makes rank 1 hold a slightly different weight tensor after the broadcast: the line must carry
     ranks_agree false and EVERY rank must exit non-zero -- an 8-GPU scaling run cannot pass with one rank computing something else."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--perturb-rank", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full", "--perturb-rank", "1"],
                        env=_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = r.stdout.decode(errors="replace")
     assert r.returncode != 0, out[-2000:]
@@ -89,7 +89,7 @@ def test_single_rank_line_and_no_gpu_refusal():
 def test_eight_ranks_the_size_of_the_scaling_run():
     """the first time this code meets 8 ranks must not be the driver's RCCL run.  The same dry run at world_size 8
     (the line carries every rank's CPU placement and host launch cost), and a perturbed LAST rank must fail all eight."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run"], env=_env(), cwd=ROOT,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--full"], env=_env(), cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0, out[-3000:]
@@ -101,7 +101,7 @@ def test_eight_ranks_the_size_of_the_scaling_run():
     assert line["omp_num_threads"] >= 1
     assert line["rank_check"]["ranks_agree"] is True
     assert sum(1 for l in out.splitlines() if l.startswith("{")) == 1
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--perturb-rank", "7"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--full", "--perturb-rank", "7"],
                        env=_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors="replace")
     assert r.returncode != 0, out[-2000:]
@@ -112,7 +112,7 @@ def test_eight_rank_dry_run_line_schema():
     """The WHOLE `bench.py --gpus 8` self-spawn path (launcher, rendezvous, pinning plan, weight broadcast, the solo reference run of rank 0, the
     8-rank timed loop, reductions, rank check) over gloo on the CPU, and the schema of the line the driver's scaling run will read: the
     collective block (backend, bytes, GB/s, hardware queues per rank), per-rank frames/s with min / max / spread, and the scaling check."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run"], env=_env(), cwd=ROOT,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run", "--full"], env=_env(), cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0, out[-3000:]
@@ -129,3 +129,52 @@ def test_eight_rank_dry_run_line_schema():
     assert line["rank_check"]["ranks_agree"] is True
     assert line["warmup"] >= line["warmup_requested"] == 1
     assert isinstance(line["cpu_affinity"], list) and len(line["cpu_affinity"]) == 8
+
+
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the line is the headline alone: the K timed steps and the fields that describe them.  The N-rank checks (solo
+    run, rank digests), the host launch frames and everything else beside the headline come only with --full (tests above)."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"], env=_env(), cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, out[-3000:]
+    line = _last_json(out)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "world_size_seen"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["world_size_seen"] == 2
+    for k in ("rank_check", "scaling_check", "sustained", "roofline", "cpu_baseline", "parity", "other_configs", "hipgraph"):
+        assert k not in line, k
+    assert line["host_launch_us_per_frame"] is None                  # not measured: no frames beyond warm-up and the K steps
+
+
+def test_dump_outputs_writes_float32_files_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs (bench.dump_outputs): one .npy per returned array, float32, whole when it fits the budget, else the documented
+    seeded stride sample -- the same elements in every run -- and never more than the budget over all files."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_ELEMS", 1000)
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn(1, 19, 3, 5, generator=g)
+    files = bench.dump_outputs([small], str(tmp_path / "a"), 0, 1, torch, np)
+    assert list(files) == ["logits.npy"]
+    a = np.load(str(tmp_path / "a" / "logits.npy"))
+    assert a.dtype == np.float32 and a.shape == (1, 19, 3, 5) and np.array_equal(a, small.numpy())
+    big = [torch.randn(1, 19, 33, 65, generator=g) for _ in range(2)]
+    for d in ("b", "c"):
+        files = bench.dump_outputs(big, str(tmp_path / d), 0, 1, torch, np)
+        assert sorted(files) == ["logits_0_sample.npy", "logits_1_sample.npy"]
+    total = 0
+    for i, o in enumerate(big):
+        b = np.load(str(tmp_path / "b" / ("logits_%d_sample.npy" % i)))
+        c = np.load(str(tmp_path / "c" / ("logits_%d_sample.npy" % i)))
+        assert b.dtype == np.float32 and np.array_equal(b, c)
+        n = o.numel()
+        stride = -(-n // 500)
+        k = n // stride
+        idx = np.arange(k) * stride + np.random.default_rng([k, n]).integers(0, stride, k)
+        assert np.array_equal(b, o.reshape(-1).numpy()[idx])
+        total += b.size
+    assert total <= 1000
+    files = bench.dump_outputs([small], str(tmp_path / "r"), 1, 2, torch, np)   # N ranks: every rank its own file
+    assert list(files) == ["rank1_logits.npy"]

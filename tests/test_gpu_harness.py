@@ -82,7 +82,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "6", "--warmup", "6",
-                        "--size", "257x513"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+                        "--size", "257x513", "--full"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0, out[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
@@ -104,7 +104,7 @@ def test_bench_four_ranks_one_perturbed_rank_fails():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--share-gpu", "--steps", "4", "--warmup", "6",
-                        "--size", "129x257", "--perturb-rank", "3", "--no-cpu-baseline"], env=env, cwd=root, stdout=subprocess.PIPE,
+                        "--size", "129x257", "--perturb-rank", "3", "--no-cpu-baseline", "--full"], env=env, cwd=root, stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode(errors="replace")
     assert r.returncode != 0, out[-3000:]
@@ -112,6 +112,45 @@ def test_bench_four_ranks_one_perturbed_rank_fails():
     assert line["rank_check"]["ranks_agree"] is False and line["rank_check"]["FAILED"] is True
     assert line["n_gpus"] == 4 and line["world_size_seen"] == 4 and len(line["per_rank_fps"]) == 4 and min(line["per_rank_fps"]) > 0
     assert len(line["cpu_affinity"]) == 4 and len(line["host_launch_us_per_frame"]) == 4 and min(line["host_launch_us_per_frame"]) > 0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` line: exactly --steps timed steps and the headline fields, nothing measured beside them.  --dump-outputs writes
+    what the last timed step returned: at 129x257 the whole logits tensor, held to the CPU oracle on the same frame (the run's weights,
+    clip and frame count restated here); at 1024x2048 the seeded sample, the same in two runs of the same arguments."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(d, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "4", "--dump-outputs", str(d)] + list(extra),
+                           env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        out = r.stdout.decode(errors="replace")
+        assert r.returncode == 0, out[-3000:]
+        return json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+
+    H, W = 129, 257
+    line = run(tmp_path / "a", "--size", "%dx%d" % (H, W))
+    assert line["steps"] == 5 and line["warmup"] == 4 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1.0       # one frame per step
+    for k in ("roofline", "frame", "latency_ms_synced", "sustained", "hipgraph", "cpu_baseline", "parity", "other_configs", "numerics_stress"):
+        assert k not in line, k
+    got = np.load(str(tmp_path / "a" / "logits.npy"))
+    assert got.dtype == np.float32 and got.shape == (1, 19, H, W)
+    spec = arch.model_spec("td4", 19, "resnet18")
+    ref = tdnet_ref.TDNetRef(spec, weights.synth_state_dict(spec, arch.feat_size(H), arch.feat_size(W), 0))
+    clip = weights.synth_video(H, W, 8, seed=100)
+    for t in range(4 + 5):                                        # warm-up + timed frames; the last one is what the file holds
+        exp = ref.forward(torch.from_numpy(clip[t % 8]), t % 4)
+    err = float(np.abs(got - exp.numpy()).max())
+    assert err <= 1e-3, err
+    a = run(tmp_path / "b1")
+    b = run(tmp_path / "b2")
+    assert list(a["dump_outputs"]["files"]) == ["logits_sample.npy"]
+    s1 = np.load(str(tmp_path / "b1" / "logits_sample.npy"))
+    s2 = np.load(str(tmp_path / "b2" / "logits_sample.npy"))
+    assert s1.dtype == np.float32 and s1.nbytes <= 64 * 2 ** 20 and s1.size > 10 ** 6 and np.isfinite(s1).all()
+    assert np.array_equal(s1, s2), float(np.abs(s1 - s2).max())
+    assert b["steps"] == 5 and b["ms_per_step"] > 0
 
 
 def test_a_handle_created_behind_an_rccl_communicator_runs_at_full_rate():
@@ -187,7 +226,7 @@ def test_bench_line_carries_measured_hbm_traffic_of_the_dominant_kernel():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     for extra in ([], ["--precision", "fp16"]):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "6", "--size", "513x1025", "--no-cpu-baseline",
-                            "--no-direct-line", "--no-other-configs"] + extra, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+                            "--no-direct-line", "--no-other-configs", "--full"] + extra, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
         out = r.stdout.decode(errors="replace")
         assert r.returncode == 0, out[-3000:]
         line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])

@@ -4,8 +4,8 @@
 # steps (executed in order, each under its own timeout):
 #   tests[:<pytest -k expression>]   the `-m gpu` suite (or the selected part)            -> gpu_tests.log
 #   smoke                            __graft_entry__.smoke()                              -> smoke.log
-#   bench[:<bench.py args>]          the default line with all legs + live PMC passes     -> bench_<n>.log / lines.jsonl
-#   quick[:<bench.py args>]          bench.py --quick --steps 60 <args>                   -> lines.jsonl + summary.txt
+#   bench[:<bench.py args>]          bench.py --full: all legs + live PMC passes          -> bench_<n>.log / lines.jsonl
+#   quick[:<bench.py args>]          bench.py --full --quick --steps 60 <args>            -> lines.jsonl + summary.txt
 #   ab:<ab_opts.py args>             same-process A/B of tdnet_opts variants (tools/ab_opts.py) -> ab.txt
 #   prof:<name>[:<bench.py args>]    rocprofv3 --kernel-trace --stats of a short quick run -> kernel_stats_<name>.csv, timeline_<name>.txt
 #   (counter passes: `cmd:tools/gpu_pmc.sh <tag2> <bench args>` -- one counter set per rocprofv3 pass, never with other trace domains)
@@ -28,9 +28,9 @@ for step in "$@"; do
     tests) if [ -n "$rest" ]; then timeout 1500 python -m pytest tests -q -m gpu -s --durations=8 -k "$rest" > $R/gpu_tests_$n.log 2>&1; tail -n 6 $R/gpu_tests_$n.log
            else timeout 1700 python -m pytest tests -q -m gpu -s --durations=12 > $R/gpu_tests.log 2>&1; tail -n 16 $R/gpu_tests.log; fi ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $R/smoke.log 2>&1; tail -n 2 $R/smoke.log ;;
-    bench) ( time timeout 900 python bench.py $rest ) > $R/bench_$n.log 2>&1; grep '^{' $R/bench_$n.log | tail -1 >> $R/lines.jsonl
+    bench) ( time timeout 900 python bench.py --full $rest ) > $R/bench_$n.log 2>&1; grep '^{' $R/bench_$n.log | tail -1 >> $R/lines.jsonl
            echo "[bench $rest] $(grep '^{' $R/bench_$n.log | tail -1 | line)" | tee -a $R/summary.txt ;;
-    quick) timeout 300 python bench.py --steps 60 --quick $rest > $R/quick_$n.log 2>&1; grep '^{' $R/quick_$n.log | tail -1 >> $R/lines.jsonl
+    quick) timeout 300 python bench.py --steps 60 --full --quick $rest > $R/quick_$n.log 2>&1; grep '^{' $R/quick_$n.log | tail -1 >> $R/lines.jsonl
            echo "[quick $rest] $(grep '^{' $R/quick_$n.log | tail -1 | line)" | tee -a $R/summary.txt ;;
     ab)    eval "timeout 900 python tools/ab_opts.py --json $R/ab.jsonl $rest" 2>&1 | grep -v "amdgpu.ids" | tee -a $R/ab.txt ;;
     prof)  name=${rest%%:*}; args=""; [ "$name" != "$rest" ] && args=${rest#*:}
