@@ -37,8 +37,9 @@ typedef struct tdnet_cfg {
     int32_t model;      /* 4 = td4 (Testing/model/pspnet/td4_psp18.py:29-120), 2 = td2 (td2_psp50.py:29-96),
                            1 = pspnet, the stateless comparison model (pspnet.py:31-115)                             */
     int32_t backbone;   /* 18 / 34 (BasicBlock, resnet.py:218-236), 50 / 101 (Bottleneck + deep stem, :62-111,122-131)     */
-    int32_t nclass;     /* 19 for Cityscapes (test.py:26)                                                            */
-    int32_t height;     /* input H; the LayerNorm affine is [ceil(H/8), ceil(W/8)] (td4_psp18.py:107-110)            */
+    int32_t nclass;     /* 1..256: 19 for Cityscapes (test.py:26), 40 for NYUD-v2                                    */
+    int32_t height;     /* input H; the LayerNorm affine is the feature map's [h, w] (td4_psp18.py:107-110): [ceil(H/8), ceil(W/8)]
+                           with the dilated backbone, five halvings n -> (n-1)/2+1 with dilated = 0 (tdnet_feature_dims)   */
     int32_t width;      /* input W                                                                                   */
     int32_t device;     /* HIP device ordinal                                                                        */
 } tdnet_cfg;
@@ -97,10 +98,27 @@ typedef struct tdnet_opts {
 #define TDNET_OVERLAP_MASK 0x3f    /* the bits of tdnet_opts.overlap that exist: 1 | 2 | 4 | 8 | 16 | 32 */
 void tdnet_opts_default(tdnet_opts* o);
 
+/* Backbone layout: the `dilated` / `multi_grid` arguments of the reference constructors (resnet.py:138-158).  Every field is 0 or 1. */
+typedef struct tdnet_arch {
+    int32_t dilated;      /* 1 (default) = layers 3-4 at stride 1, dilation 2 / 4: output stride 8 (resnet.py:140-149);
+                             0 = layers 3-4 at stride 2, dilation 1: output stride 32 (resnet.py:150-158)                        */
+    int32_t multi_grid;   /* with dilated = 1: 1 (default) = layer-4 conv1 dilations 4, 8, 16 (resnet.py:181,196), 0 = 2, 4, 4
+                             (BasicBlock conv2 and every later block: 4; resnet.py:188,199).  Ignored with dilated = 0.          */
+    int32_t reserved[6];  /* must be 0                                                                                           */
+} tdnet_arch;
+void tdnet_arch_default(tdnet_arch* a);                                                  /* {1, 1}: the backbone the reference ships */
+
 /* ---- lifecycle: replaces the nn.Module constructor + load_state_dict (td4_psp18.py:32-120, :232-240) ---------- */
 int  tdnet_create(const tdnet_cfg* cfg, tdnet_t** out);                                  /* default options */
 int  tdnet_create_opts(const tdnet_cfg* cfg, const tdnet_opts* opts /* NULL = defaults */, tdnet_t** out);
+/* Any backbone layout.  tdnet_create_opts(cfg, opts) is this with arch {1, 1}, except that it keeps refusing the single-frame
+ * PSPNet (model 1) on the BasicBlock backbones 18 / 34, which only this entry accepts (pspnet.py:50-57: 7x7 stem, PSPHead(512)).  */
+int  tdnet_create_arch(const tdnet_cfg* cfg, const tdnet_arch* arch /* NULL = {1, 1} */, const tdnet_opts* opts /* NULL = defaults */,
+                       tdnet_t** out);
 int  tdnet_get_opts(const tdnet_t* h, tdnet_opts* out);
+int  tdnet_get_arch(const tdnet_t* h, tdnet_arch* out);
+/* Size of the backbone's output map (and of the LayerNorm affine, the attention's query grid and the low-resolution logits). */
+int  tdnet_feature_dims(const tdnet_t* h, int* height, int* width);
 void tdnet_destroy(tdnet_t* h);
 
 /* One call per state_dict entry, reference key names ("pretrained1.layer4.1.conv2.weight", ...), host fp32
@@ -113,7 +131,7 @@ int  tdnet_finalize_weights(tdnet_t* h);
 /* A further handle on the SAME weight block as `weights_of` (which must be finalized): own workspace, own K/Q/V FIFO, own
  * streams -- another video stream on this GPU, the samples 1..N-1 of a batch (the reference's batch shares one nn.Module's
  * parameters: td4_psp18.py:216-229), or the second lane of a frame-pipelined clip -- without a second copy of the packed weights
- * and without folding / packing / uploading them again.  `opts` must be NULL (inherit) or equal to the block's options: the
+ * and without folding / packing / uploading them again; the backbone layout (tdnet_arch) is the block's too.  `opts` must be NULL (inherit) or equal to the block's options: the
  * packing depends on them.  The block is reference-counted (atomically): handles may be destroyed in any order, the weights go with the
  * last.  Threading: a HANDLE is single-threaded (one host thread at a time), but tdnet_create_shared / tdnet_destroy of DIFFERENT handles
  * on one block may run concurrently on different host threads (a garbage collector's finaliser thread, say).                    */

@@ -53,6 +53,9 @@ int tdnet_op_layernorm_hw(const float* x_dev, int HW, int C, const float* g_dev,
 /* PPM (td4_psp18.py:271-284): c4 NHWC [h,w,512] -> z NHWC [h,w,512]; w_host: 4 folded [128,512] matrices, b_host 4x[128] */
 int tdnet_op_ppm(const float* c4_dev, int h, int w, const float* w_host, const float* b_host, int path_num, int pid,
                  float* z_dev, void* stream);
+/* 1x1 classifier conv (+bias): x NHWC [HW,C] dev, w [NC,C] dev, b [NC] dev -> planar out [NC,HW] dev; the frame's routing by NC
+ * (<= 32: k_classifier, 33 .. 256: the class-tiled k_classifier_ct, C <= 512)                                    */
+int tdnet_op_classifier(const float* x_dev, int HW, int C, const float* w_dev, const float* b_dev, int NC, float* out_dev, void* stream);
 /* bilinear align_corners=True (td4_psp18.py:227): planar [C,h,w] -> [C,H,W]                                       */
 int tdnet_op_upsample(const float* in_dev, int C, int h, int w, int H, int W, float* out_dev, void* stream);
 

@@ -30,6 +30,14 @@ class TdnetOpts(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class TdnetArch(ctypes.Structure):
+    """include/tdnet.h tdnet_arch: the backbone layout (the reference constructors' dilated / multi_grid)."""
+    _fields_ = [("dilated", ctypes.c_int32), ("multi_grid", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+    def as_dict(self):
+        return {"dilated": self.dilated, "multi_grid": self.multi_grid}
+
+
 class TdnetError(RuntimeError):
     pass
 
@@ -37,12 +45,17 @@ class TdnetError(RuntimeError):
 # name -> (restype, argtypes); every symbol include/tdnet.h declares
 WINOGRAD_DEFAULT = 3          # include/tdnet.h TDNET_WINOGRAD_DEFAULT: F(4x4,3x3) for the wide stride-1 3x3 convs
 c_opts_p = ctypes.POINTER(TdnetOpts)
+c_arch_p = ctypes.POINTER(TdnetArch)
 
 SYMBOLS = {
     "tdnet_opts_default": (None, [c_opts_p]),
+    "tdnet_arch_default": (None, [c_arch_p]),
     "tdnet_create": (ctypes.c_int, [ctypes.POINTER(TdnetCfg), ctypes.POINTER(c_void_p)]),
     "tdnet_create_opts": (ctypes.c_int, [ctypes.POINTER(TdnetCfg), c_opts_p, ctypes.POINTER(c_void_p)]),
+    "tdnet_create_arch": (ctypes.c_int, [ctypes.POINTER(TdnetCfg), c_arch_p, c_opts_p, ctypes.POINTER(c_void_p)]),
     "tdnet_get_opts": (ctypes.c_int, [c_void_p, c_opts_p]),
+    "tdnet_get_arch": (ctypes.c_int, [c_void_p, c_arch_p]),
+    "tdnet_feature_dims": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tdnet_destroy": (None, [c_void_p]),
     "tdnet_set_weight": (ctypes.c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "tdnet_finalize_weights": (ctypes.c_int, [c_void_p]),
@@ -91,6 +104,7 @@ TEST_SYMBOLS = {
                                     c_void_p, c_void_p]),
     "tdnet_op_upsample": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          c_void_p, c_void_p]),
+    "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
 }
 
 
@@ -125,6 +139,13 @@ class Lib:
             if v is not None:
                 setattr(o, k, int(v))
         return o
+
+    def arch(self, dilated=True, multi_grid=True):
+        """tdnet_arch from the reference constructors' booleans."""
+        a = TdnetArch()
+        self.tdnet_arch_default(ctypes.byref(a))
+        a.dilated, a.multi_grid = int(bool(dilated)), int(bool(multi_grid))
+        return a
 
     def check(self, rc):
         if rc is not None and rc < 0:

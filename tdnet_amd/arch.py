@@ -27,9 +27,10 @@ def expansion(backbone):
     return 4 if is_bottleneck(backbone) else 1
 
 
-def feat_size(n):
-    """Spatial size after the three stride-2 stages (stem conv, max-pool, layer2): n -> ((n-1)//2+1) x3."""
-    for _ in range(3):
+def feat_size(n, dilated=True):
+    """Spatial size after the stride-2 stages: stem conv, max-pool, layer2 (n -> ((n-1)//2+1) x3, output stride 8), and with
+    dilated=False layer3 and layer4 as well (x5, output stride 32; resnet.py:150-158)."""
+    for _ in range(3 if dilated else 5):
         n = (n - 1) // 2 + 1
     return n
 
@@ -39,12 +40,14 @@ def key_size(n):
     return (n - 1) // 4 + 1
 
 
-def backbone_blocks(backbone):
-    """BasicBlock list of the dilated, multi-grid ResNet used by TDNet (output stride 8).
+def backbone_blocks(backbone, dilated=True, multi_grid=True):
+    """Block list of the ResNet the reference constructors build (resnet.py:138-158).
 
-    resnet.py:138-149 -> layer1 (64, s1, d1), layer2 (128, s2, d1), layer3 (256, s1, dilation=2),
-    layer4 (512, s1, dilation=4, multi_grid -> block dilations 4, 8, 16); conv1 of a block uses `dilation`,
+    dilated=True (output stride 8): layer1 (64, s1, d1), layer2 (128, s2, d1), layer3 (256, s1, dilation=2), layer4 (512, s1,
+    dilation=4; multi_grid -> block dilations 4, 8, 16, otherwise 2, 4, 4 -- resnet.py:181-199); conv1 of a block uses `dilation`,
     conv2 uses `previous_dilation` (resnet.py:32-37); the first block of layer3 uses dilation 1 (resnet.py:183-185).
+    dilated=False (output stride 32, resnet.py:150-158; `for_seg` is never passed): layer3 and layer4 at stride 2, dilation 1;
+    multi_grid is then ignored.
     """
     if backbone not in _LAYERS:
         raise ValueError("backbone must be resnet18/34/50/101; got %r" % (backbone,))
@@ -53,9 +56,13 @@ def backbone_blocks(backbone):
     exp = 4 if bott else 1
     blocks = []
     inpl = 128 if bott else 64                      # deep_base stem ends in 128 channels (resnet.py:117,122-131)
+    if dilated:
+        l34 = [(256, nb[2], 1, 2, False), (512, nb[3], 1, 4, bool(multi_grid))]
+    else:
+        l34 = [(256, nb[2], 2, 1, False), (512, nb[3], 2, 1, False)]
     # (planes, blocks, stride, dilation, multi_grid)
     for li, (planes, n, stride, dil, mg) in enumerate(
-            [(64, nb[0], 1, 1, False), (128, nb[1], 2, 1, False), (256, nb[2], 1, 2, False), (512, nb[3], 1, 4, True)], 1):
+            [(64, nb[0], 1, 1, False), (128, nb[1], 2, 1, False)] + l34, 1):
         for b in range(n):
             first = b == 0
             if mg:
@@ -71,11 +78,28 @@ def backbone_blocks(backbone):
     return blocks
 
 
-ModelSpec = namedtuple("ModelSpec", "name path_num backbone d_model d_k d_v psp_path_num pids head_mid nclass fifo atn_names")
+# dilated / multi_grid: the reference constructors' arguments of the same names (trailing, defaulted: the shipped layout)
+ModelSpec = namedtuple("ModelSpec", "name path_num backbone d_model d_k d_v psp_path_num pids head_mid nclass fifo atn_names dilated multi_grid",
+                       defaults=(True, True))
 
 
-def model_spec(name, nclass=19, backbone=None):
-    """name: 'td4' (td4_psp18.py) or 'td2' (td2_psp50.py with a BasicBlock backbone)."""
+def spec_blocks(spec):
+    """The block list of a model spec's backbone."""
+    return backbone_blocks(spec.backbone, spec.dilated, spec.multi_grid)
+
+
+def spec_feat_size(spec, n):
+    """Feature size of an input axis for a model spec (output stride 8, or 32 when not dilated)."""
+    return feat_size(n, spec.dilated)
+
+
+def model_spec(name, nclass=19, backbone=None, dilated=True, multi_grid=True):
+    """name: 'td4' (td4_psp18.py), 'td2' (td2_psp50.py) or 'psp' (pspnet.py); dilated / multi_grid as the constructors take them."""
+    s = _model_spec(name, nclass, backbone)
+    return s._replace(dilated=bool(dilated), multi_grid=bool(multi_grid))
+
+
+def _model_spec(name, nclass, backbone):
     if name == "td4":
         bb = backbone or "resnet18"
         if bb == "resnet101":
@@ -93,11 +117,13 @@ def model_spec(name, nclass=19, backbone=None):
         atn = {0: ("atn1",), 1: ("atn2",)}
         return ModelSpec("td2", 2, bb, 512 * e, 64, 128 * e, 2, (0, 1), 128 * e // 2, nclass, 1, atn)
     if name == "psp":
-        # pspnet.py:31-70: single-frame PSPNet (the comparison model of test.py:34-38); full pyramid pooling, no attention
+        # pspnet.py:31-70: single-frame PSPNet (the comparison model of test.py:34-38); full pyramid pooling, no attention.
+        # :50-57: ResNet-18 / 34 with the 7x7 stem and PSPHead(512): pyramid 512 -> 4 x 128, conv3x3 1024 -> 128, classifier
         bb = backbone or "resnet101"
-        if not is_bottleneck(bb):
-            raise ValueError("psp is shipped with resnet101 (pspnet.py:36); only Bottleneck backbones are implemented for it")
-        return ModelSpec("psp", 1, bb, 2048, 0, 0, 1, (0,), 512, nclass, 0, {})
+        if bb not in _LAYERS:
+            raise ValueError("unknown backbone: %r" % (bb,))
+        dm = 512 * expansion(bb)
+        return ModelSpec("psp", 1, bb, dm, 0, 0, 1, (0,), dm // 4, nclass, 0, {})
     raise ValueError(name)
 
 
@@ -130,7 +156,7 @@ def state_dict_shapes(spec, h, w):
         else:
             out[pre + ".conv1.weight"] = (64, 3, 7, 7)
             bn(pre + ".bn1", 64)
-        for b in backbone_blocks(spec.backbone):
+        for b in spec_blocks(spec):
             bp = "%s.%s" % (pre, b.name)
             if b.kind == "basic":
                 out[bp + ".conv1.weight"] = (b.cout, b.cin, 3, 3)

@@ -77,18 +77,22 @@ struct DevGuard {
 // bott: conv1x1(cin->planes) conv3x3(planes->planes, stride, dil1) conv1x1(planes->cout); Bottleneck ignores dil2 (resnet.py:62-111)
 struct BlockSpec { std::string name; int cin, cout, stride, dil1, dil2; bool ds; bool bott; int planes; };
 
-static std::vector<BlockSpec> backbone_blocks(int backbone) {
+// dilated (tdnet_arch.dilated): layers 3-4 at stride 1 with dilation 2 / 4 (output stride 8, resnet.py:140-149); otherwise at stride 2 with
+// dilation 1 (output stride 32, resnet.py:150-158; `for_seg` is never passed by the Testing constructors).  multi_grid: layer 4's conv1
+// dilations 4, 8, 16 (resnet.py:181,196); without it 2, 4, 4 (:188,199).  Ignored when not dilated.
+static std::vector<BlockSpec> backbone_blocks(int backbone, bool dilated = true, bool multi_grid = true) {
     const int nb18[4] = {2, 2, 2, 2}, nb34[4] = {3, 4, 6, 3};
     const int nb101[4] = {3, 4, 23, 3};
     const int* nb = backbone == 18 ? nb18 : backbone == 101 ? nb101 : nb34;   // ResNet-50 has the ResNet-34 block counts
     const bool bott = backbone == 50 || backbone == 101;
     const int exp = bott ? 4 : 1;
-    const int planes[4] = {64, 128, 256, 512}, strides[4] = {1, 2, 1, 1}, dils[4] = {1, 1, 2, 4};
+    const int planes[4] = {64, 128, 256, 512};
+    const int strides[4] = {1, 2, dilated ? 1 : 2, dilated ? 1 : 2}, dils[4] = {1, 1, dilated ? 2 : 1, dilated ? 4 : 1};
     std::vector<BlockSpec> out;
     int inpl = bott ? 128 : 64;                                      // deep_base stem ends in 128 channels (resnet.py:117)
     for (int li = 0; li < 4; ++li) {
         for (int b = 0; b < nb[li]; ++b) {
-            const bool first = b == 0, mg = li == 3;
+            const bool first = b == 0, mg = li == 3 && dilated && multi_grid;
             int d1;
             if (mg) d1 = b == 0 ? 4 : b == 1 ? 8 : 16;            // multi-grid (4,8,16): resnet.py:181,196-198
             else if (first) d1 = (dils[li] == 1 || dils[li] == 2) ? 1 : 2;
@@ -111,9 +115,16 @@ static std::vector<BlockSpec> backbone_blocks(int backbone) {
     }
     return out;
 }
-static int feat_size(int n) { for (int i = 0; i < 3; ++i) n = (n - 1) / 2 + 1; return n; }
 static int key_size(int n) { return (n - 1) / 4 + 1; }
 static int out_size(int n, int KS, int stride, int dil, int pad) { return (n + 2 * pad - dil * (KS - 1) - 1) / stride + 1; }
+// Feature size of an input axis from the strides themselves: the stem conv (stride 2, "same" padding), the 3x3 stride-2 max-pool, then every
+// block's strided conv (3x3 with padding = dilation; the 1x1 downsample beside it gives the same size).  Output stride 8 or 32 follows from the list.
+static int feature_size(int n, const std::vector<BlockSpec>& blocks) {
+    n = (n - 1) / 2 + 1;
+    n = (n - 1) / 2 + 1;
+    for (const BlockSpec& s : blocks) n = out_size(n, 3, s.stride, s.dil1, s.dil1);
+    return n;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // device conv layer
@@ -187,6 +198,7 @@ struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };  
 struct TdWeights {
     std::atomic<int> refs{1};                                          // handles on this block; tdnet_create_shared / tdnet_destroy may run on different host threads
     int device = 0;
+    tdnet_arch arch = {1, 1, {0, 0, 0, 0, 0, 0}};                     // the backbone's layout (tdnet_create_arch); bspec is built from it
     std::vector<BlockSpec> bspec;
     std::map<std::string, std::vector<float>> sd;                      // host state_dict until finalize
     std::map<std::string, size_t> expected;                            // name -> element count

@@ -301,7 +301,11 @@ static int run_classifier(tdnet* n, const float* x, int HW, int C, int NC, const
     prof_begin(n, 2, false, 0, s);
     const int grid = (HW + 63) / 64, lds = (NC * C + 4 * NC * 64) * 4;
     if (NC <= 19) TD_LAUNCH((k_classifier<19>), dim3(grid), dim3(256), lds, s, x, wgt, bias, out, HW, C, NC);
-    else TD_LAUNCH((k_classifier<32>), dim3(grid), dim3(256), lds, s, x, wgt, bias, out, HW, C, NC);
+    else if (NC <= 32) TD_LAUNCH((k_classifier<32>), dim3(grid), dim3(256), lds, s, x, wgt, bias, out, HW, C, NC);
+    else {                                                             // 33 .. 256 classes: 32-class tiles, each tile's weights in LDS
+        if (!classifier_ct_supports(C)) { prof_end(n, s); return td_fail("classifier: C=%d is above the class-tiled kernel's 512 channels", C); }
+        TD_LAUNCH(k_classifier_ct, dim3((NC + 31) / 32, grid), dim3(256), classifier_ct_lds(C), s, x, wgt, bias, out, HW, C, NC);
+    }
     prof_end(n, s);
     return 0;
 }

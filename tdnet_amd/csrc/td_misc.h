@@ -422,6 +422,55 @@ TD_KERNEL void k_classifier(const float* __restrict__ x, const float* __restrict
     }
 }
 
+// ---- classifier for NC > 32 (NYUD-v2: 40, ADE20K: 150, COCO-Stuff: 171 / 182; up to 256) --------------------------------------------
+// grid = (32-class tiles, 64-pixel blocks): a workgroup is k_classifier<32> for the classes k0 .. k0 + 31 of its tile.  The tile's [32][C]
+// weights sit in LDS (C <= 512: <= 64 KiB, plus the 32 KiB reduction -- within the 160 KiB of a CU), a lane's four channel quarters are
+// four sequential fma chains added in k_classifier's fixed order: every logit is the sum k_classifier forms for that class.  The class tiles
+// of one pixel block are adjacent in the grid, so the block's C-channel rows are read from HBM once and from L2 by the other tiles.
+constexpr int TD_CLS_TILE = 32;
+static inline bool classifier_ct_supports(int C) { return C % 16 == 0 && C >= 16 && C <= 512; }
+static inline int classifier_ct_lds(int C) { return (TD_CLS_TILE * C + 4 * TD_CLS_TILE * 64) * 4; }
+TD_KERNEL void k_classifier_ct(const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
+                               float* __restrict__ out, int HW, int C, int NC) {
+    TD_DYN_LDS(smem);
+    const int k0 = blockIdx.x * TD_CLS_TILE, nc = NC - k0 < TD_CLS_TILE ? NC - k0 : TD_CLS_TILE;
+    float* ws = reinterpret_cast<float*>(smem);                // [nc][C]
+    float* red = ws + TD_CLS_TILE * C;                         // [4][nc][64]
+    const float* wt = wgt + (size_t)k0 * C;
+    for (int i = threadIdx.x; i < nc * C; i += blockDim.x) ws[i] = wt[i];
+    __syncthreads();
+    const int lp = threadIdx.x & 63, q = threadIdx.x >> 6, CQ = C >> 2;
+    const int p = blockIdx.y * 64 + lp;
+    float acc[TD_CLS_TILE];
+#pragma unroll
+    for (int k = 0; k < TD_CLS_TILE; ++k) acc[k] = 0.f;
+    if (p < HW) {
+        const float* xp = x + (size_t)p * C + q * CQ;
+#pragma unroll 4
+        for (int c = 0; c < CQ; c += 4) {
+            const f32x4 v = td_ld4(xp + c);
+#pragma unroll
+            for (int k = 0; k < TD_CLS_TILE; ++k) {
+                if (k < nc) {
+                    const float* wr = ws + k * C + q * CQ + c;
+                    acc[k] = fmaf(v[0], wr[0], acc[k]); acc[k] = fmaf(v[1], wr[1], acc[k]);
+                    acc[k] = fmaf(v[2], wr[2], acc[k]); acc[k] = fmaf(v[3], wr[3], acc[k]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < TD_CLS_TILE; ++k)
+        if (k < nc) red[(q * nc + k) * 64 + lp] = acc[k];
+    __syncthreads();
+    for (int v = threadIdx.x; v < nc * 64; v += blockDim.x) {
+        const int k = v >> 6, pl = v & 63, pp = blockIdx.y * 64 + pl;
+        if (pp >= HW) continue;
+        const float sum = ((red[(0 * nc + k) * 64 + pl] + red[(1 * nc + k) * 64 + pl]) + red[(2 * nc + k) * 64 + pl]) + red[(3 * nc + k) * 64 + pl];
+        out[(size_t)(k0 + k) * HW + pp] = sum + bias[k0 + k];
+    }
+}
+
 // ---- bilinear, align_corners=True (td4_psp18.py:227): planar [C][h][w] -> [C][H][W] ------------------------------
 struct UpCoef { int i0, i1; float l; };
 TD_DEV UpCoef td_up_coef(int d, float scale, int n_in) {

@@ -28,9 +28,15 @@ extern "C" void tdnet_opts_default(tdnet_opts* o) {
     o->fusion = TDNET_FUSION_DEFAULT;
     o->overlap = TDNET_OVERLAP_DEFAULT;
 }
+extern "C" void tdnet_arch_default(tdnet_arch* a) {
+    if (!a) return;
+    memset(a, 0, sizeof(*a));
+    a->dilated = 1;                         // output stride 8 (resnet.py:140-149)
+    a->multi_grid = 1;                      // layer-4 dilations 4, 8, 16
+}
 extern "C" int tdnet_create(const tdnet_cfg* cfg, tdnet_t** out) { return tdnet_create_opts(cfg, nullptr, out); }
 
-// geometry of a handle from its configuration (the same for every handle of a weight block)
+// geometry of a handle from its configuration and block list (the same for every handle of a weight block)
 static void set_geometry(tdnet* n, const tdnet_cfg* cfg) {
     n->cfg = *cfg;
     n->P = cfg->model;
@@ -45,20 +51,29 @@ static void set_geometry(tdnet* n, const tdnet_cfg* cfg) {
     n->H = cfg->height; n->W = cfg->width;
     n->H1 = (n->H - 1) / 2 + 1; n->W1 = (n->W - 1) / 2 + 1;
     n->H2 = (n->H1 - 1) / 2 + 1; n->W2 = (n->W1 - 1) / 2 + 1;
-    n->h = feat_size(n->H); n->w = feat_size(n->W);
+    n->h = feature_size(n->H, n->bspec); n->w = feature_size(n->W, n->bspec);   // output stride 8 or 32, from the block list
     n->hk = key_size(n->h); n->wk = key_size(n->w);
     n->Lq = n->h * n->w; n->Lk = n->hk * n->wk;
 }
 
-extern "C" int tdnet_create_opts(const tdnet_cfg* cfg, const tdnet_opts* opts, tdnet_t** out) {
+extern "C" int tdnet_create_arch(const tdnet_cfg* cfg, const tdnet_arch* arch, const tdnet_opts* opts, tdnet_t** out) {
     if (!cfg || !out) return td_fail("tdnet_create: null argument");
+    tdnet_arch a;
+    tdnet_arch_default(&a);
+    if (arch) {
+        if ((arch->dilated != 0 && arch->dilated != 1) || (arch->multi_grid != 0 && arch->multi_grid != 1))
+            return td_fail("tdnet_create: tdnet_arch.dilated / multi_grid must be 0 or 1, got %d / %d", arch->dilated, arch->multi_grid);
+        for (int r : arch->reserved)
+            if (r != 0) return td_fail("tdnet_create: tdnet_arch.reserved must be 0");
+        a = *arch;
+    }
     if (cfg->model != 4 && cfg->model != 2 && cfg->model != 1)
         return td_fail("tdnet_create: model must be 4 (td4), 2 (td2) or 1 (single-frame PSPNet), got %d", cfg->model);
     if (cfg->backbone != 18 && cfg->backbone != 34 && cfg->backbone != 50 && cfg->backbone != 101)
         return td_fail("tdnet_create: backbone must be 18, 34, 50 or 101, got %d", cfg->backbone);
-    if ((cfg->backbone == 101) != (cfg->model == 1) && !(cfg->model == 1 && cfg->backbone == 50))
-        return td_fail("tdnet_create: resnet101 is the PSPNet baseline's backbone (pspnet.py:36); psp accepts 50 or 101");
-    if (cfg->nclass < 1 || cfg->nclass > 32) return td_fail("tdnet_create: nclass must be in 1..32");
+    if (cfg->backbone == 101 && cfg->model != 1)
+        return td_fail("tdnet_create: resnet101 is the PSPNet baseline's backbone (pspnet.py:36); td4 / td2 accept 18, 34 or 50");
+    if (cfg->nclass < 1 || cfg->nclass > 256) return td_fail("tdnet_create: nclass must be in 1..256, got %d", cfg->nclass);
     if (cfg->height < 9 || cfg->width < 9) return td_fail("tdnet_create: input too small");
     {
         int ndev = 0;
@@ -67,12 +82,31 @@ extern "C" int tdnet_create_opts(const tdnet_cfg* cfg, const tdnet_opts* opts, t
     }
     TdWeights* wt = new TdWeights();
     wt->device = cfg->device;
+    wt->arch = a;
     tdnet* n = new tdnet(wt);
+    n->bspec = backbone_blocks(cfg->backbone, a.dilated != 0, a.multi_grid != 0);
     set_geometry(n, cfg);
     n->opts = opts_or_default(opts);
-    n->bspec = backbone_blocks(cfg->backbone);
     build_expected(n);
     *out = n;
+    return 0;
+}
+
+extern "C" int tdnet_create_opts(const tdnet_cfg* cfg, const tdnet_opts* opts, tdnet_t** out) {
+    if (cfg && cfg->model == 1 && (cfg->backbone == 18 || cfg->backbone == 34))
+        return td_fail("tdnet_create: pspnet on resnet%d is created with tdnet_create_arch; tdnet_create_opts keeps accepting 50 or 101 only", cfg->backbone);
+    return tdnet_create_arch(cfg, nullptr, opts, out);
+}
+
+extern "C" int tdnet_get_arch(const tdnet_t* n, tdnet_arch* out) {
+    if (!n || !out) return td_fail("tdnet_get_arch: null argument");
+    *out = n->wt->arch;
+    return 0;
+}
+extern "C" int tdnet_feature_dims(const tdnet_t* n, int* height, int* width) {
+    if (!n) return td_fail("tdnet_feature_dims: null handle");
+    if (height) *height = n->h;
+    if (width) *width = n->w;
     return 0;
 }
 

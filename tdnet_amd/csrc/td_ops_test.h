@@ -166,6 +166,13 @@ extern "C" int tdnet_op_ppm(const float* c4, int h, int w, const float* w_host, 
     for (float* q : {dw, db, rowpart, pooled, ppmfeat}) hipFree(q);
     return 0;
 }
+extern "C" int tdnet_op_classifier(const float* x, int HW, int C, const float* w, const float* b, int NC, float* out, void* stream) {
+    if (NC < 1 || NC > 256) return td_fail("tdnet_op_classifier: NC must be in 1..256");
+    TD_TRY(run_classifier(nullptr, x, HW, C, NC, w, b, out, (hipStream_t)stream));
+    TD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
 extern "C" int tdnet_op_upsample(const float* in, int C, int h, int w, int H, int W, float* out, void* stream) {
     launch_upsample(in, C, h, w, H, W, out, (hipStream_t)stream);
     TD_HIP(hipStreamSynchronize((hipStream_t)stream));

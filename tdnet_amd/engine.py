@@ -20,8 +20,10 @@ def _ptr(a):
 
 
 class Engine:
-    def __init__(self, model, backbone, nclass, height, width, device=0, lib=None, opts=None, _shared_from=None):
-        """opts: None (library defaults) or a dict of tdnet_opts fields (winograd=, precision=, pipeline=, ...): per handle."""
+    def __init__(self, model, backbone, nclass, height, width, device=0, lib=None, opts=None, _shared_from=None, arch=None):
+        """opts: None (library defaults) or a dict of tdnet_opts fields (winograd=, precision=, pipeline=, ...): per handle.
+        arch: None (tdnet_create_opts: the shipped dilated, multi-grid backbone) or a dict {dilated:, multi_grid:} of booleans
+        (tdnet_create_arch: any layout the reference constructors accept, and pspnet on ResNet-18 / 34)."""
         self.lib = lib or _capi.lib()
         self.cfg = _capi.TdnetCfg(model, backbone, nclass, height, width, device)
         h = ctypes.c_void_p()
@@ -31,7 +33,11 @@ class Engine:
             self.finalized = True
             return
         o = self.lib.opts(**(opts or {}))
-        self.lib.check(self.lib.tdnet_create_opts(ctypes.byref(self.cfg), ctypes.byref(o), ctypes.byref(h)))
+        if arch is None:
+            self.lib.check(self.lib.tdnet_create_opts(ctypes.byref(self.cfg), ctypes.byref(o), ctypes.byref(h)))
+        else:
+            a = arch if isinstance(arch, _capi.TdnetArch) else self.lib.arch(**arch)
+            self.lib.check(self.lib.tdnet_create_arch(ctypes.byref(self.cfg), ctypes.byref(a), ctypes.byref(o), ctypes.byref(h)))
         self.h = h
         self.finalized = False
 
@@ -125,6 +131,17 @@ class Engine:
         o = _capi.TdnetOpts()
         self.lib.check(self.lib.tdnet_get_opts(self.h, ctypes.byref(o)))
         return o.as_dict()
+
+    def arch(self):
+        a = _capi.TdnetArch()
+        self.lib.check(self.lib.tdnet_get_arch(self.h, ctypes.byref(a)))
+        return a.as_dict()
+
+    def feature_dims(self):
+        """(h, w) of the backbone's output map: the library's stride rule, not restated here."""
+        h, w = ctypes.c_int(), ctypes.c_int()
+        self.lib.check(self.lib.tdnet_feature_dims(self.h, ctypes.byref(h), ctypes.byref(w)))
+        return h.value, w.value
 
     def flops_per_frame(self):
         return self.lib.tdnet_flops_per_frame(self.h)

@@ -20,6 +20,10 @@ Differences from the reference, on purpose:
     and is an error at the first frame otherwise;
   * td4 accepts all three backbones the reference's constructor accepts (td4_psp18.py:52-66), including the never-shipped
     resnet50 (d_model = d_v = 2048): its attention runs as four 512-channel launches.
+
+Constructor arguments taken as the reference takes them: `dilated` / `multi_grid` select the backbone layout (resnet.py:138-158;
+dilated=False is output stride 32: the feature map, the LayerNorm plane and the logits before the x32 upsample are five halvings of the
+input), `nclass` is 1..256 (NYUD-v2: 40).  `norm_layer` and `aux` are accepted and ignored.
 """
 import os
 
@@ -43,16 +47,15 @@ class _TDNetBase(nn.Module):
         super().__init__()
         assert backbone == "resnet50" or backbone == "resnet34" or backbone == "resnet18"
         assert path_num == self._model_id
-        if not (dilated and multi_grid):
-            raise NotImplementedError("only the dilated, multi-grid backbone the reference ships is implemented")
         self.psp_path = model_path
         self.path_num = path_num
         self.nclass = nclass
         self.backbone = backbone
+        self.dilated, self.multi_grid = bool(dilated), bool(multi_grid)
         self.synthetic_seed = synthetic_seed
         self.kernel_opts = dict(kernel_opts or {})
         self._pending_shape = None
-        self.spec = arch.model_spec(self._spec_name, nclass, backbone)
+        self.spec = arch.model_spec(self._spec_name, nclass, backbone, self.dilated, self.multi_grid)
         self._state = None
         self._engine = None
         self._engine_key = None
@@ -151,7 +154,7 @@ class _TDNetBase(nn.Module):
         return self._engine
 
     def _build_engine(self, H, W, dev, n=1):
-        h, w = arch.feat_size(H), arch.feat_size(W)
+        h, w = arch.spec_feat_size(self.spec, H), arch.spec_feat_size(self.spec, W)
         sd = self._state
         if sd is None:
             if self.synthetic_seed is None:
@@ -173,7 +176,10 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("Given normalized_shape=%s, expected input with shape [*, %d, %d], but got input of size"
                                "[%d, %d, %d, %d]" % (list(ln.shape), ln.shape[0], ln.shape[1], n, self.spec.d_v, h, w))
         try:
-            eng = Engine(self._model_id, int(self.backbone[6:]), self.nclass, H, W, dev, opts=self.kernel_opts)
+            eng = Engine(self._model_id, int(self.backbone[6:]), self.nclass, H, W, dev, opts=self.kernel_opts,
+                         arch={"dilated": self.dilated, "multi_grid": self.multi_grid})
+            if eng.feature_dims() != (h, w):
+                raise TdnetError("internal: feature size %s (library) != %s (arch.py)" % (eng.feature_dims(), (h, w)))
             eng.load_state_dict(sd)
         except TdnetError as e:
             raise RuntimeError("Error(s) in loading state_dict for %s:\n\t%s" % (type(self).__name__, e))
@@ -309,7 +315,7 @@ class _TDNetBase(nn.Module):
 
     def cache_entry_numel_for(self, H, W):
         """The same from the input size alone (arch): lets every rank of a path-parallel group size its buffers before any frame."""
-        lk = arch.key_size(arch.feat_size(H)) * arch.key_size(arch.feat_size(W))
+        lk = arch.key_size(arch.spec_feat_size(self.spec, H)) * arch.key_size(arch.spec_feat_size(self.spec, W))
         return lk * self.spec.d_k, lk * self.spec.d_k, lk * self.spec.d_v
 
     def cache_export(self, q, k, v):

@@ -3,7 +3,9 @@
 Mirror of Testing/model/pspnet/pspnet.py:31-115: the stateless single-frame PSPNet the reference uses as its comparison
 model (ResNet-101 dilated multi-grid backbone + PSPHead = full pyramid pooling, conv3x3 4096->512, classifier).  It reuses
 the TDNet kernels (Bottleneck convs, pyramid pooling, head, upsample); `pos_id` is accepted and ignored like in the
-reference (pspnet.py:73)."""
+reference (pspnet.py:73).  Every backbone the constructor accepts runs (pspnet.py:50-67): ResNet-18 / 34 with the 7x7 stem and
+PSPHead(512) (pyramid 512 -> 4 x 128, conv3x3 1024 -> 128), ResNet-50 / 101 with the deep stem and PSPHead(2048); `dilated` /
+`multi_grid` as for the TDNet classes."""
 import torch
 
 from ._base import _TDNetBase
@@ -16,19 +18,18 @@ class pspnet(_TDNetBase):
 
     def __init__(self, nclass=21, norm_layer=None, backbone="resnet101", dilated=True, aux=True, multi_grid=True,
                  model_path=None, synthetic_seed=None, kernel_opts=None):
-        if backbone not in ("resnet50", "resnet101"):
-            if backbone in ("resnet18", "resnet34"):
-                raise NotImplementedError("PSPNet with a BasicBlock backbone is not a configuration the reference ships")
+        if backbone not in ("resnet18", "resnet34", "resnet50", "resnet101"):
             raise RuntimeError("unknown backbone: {}".format(backbone))             # pspnet.py:65-66
         torch.nn.Module.__init__(self)
         self.psp_path = model_path
         self.path_num = 1
         self.nclass = nclass
         self.backbone = backbone
+        self.dilated, self.multi_grid = bool(dilated), bool(multi_grid)
         self.synthetic_seed = synthetic_seed
         self.kernel_opts = dict(kernel_opts or {})
         self._pending_shape = None
-        self.spec = arch.model_spec("psp", nclass, backbone)
+        self.spec = arch.model_spec("psp", nclass, backbone, self.dilated, self.multi_grid)
         self._state = None
         self._engine = None
         self._engine_key = None

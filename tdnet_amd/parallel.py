@@ -305,7 +305,8 @@ class FramePipelinedStream:
         model.ensure_engine(H, Wd, device)
         stages = [model]
         for _ in range(lanes - 1):
-            kw = dict(nclass=model.nclass, model_path=None, backbone=model.backbone, kernel_opts=model.kernel_opts, synthetic_seed=model.synthetic_seed)
+            kw = dict(nclass=model.nclass, model_path=None, backbone=model.backbone, kernel_opts=model.kernel_opts, synthetic_seed=model.synthetic_seed,
+                      dilated=getattr(model, "dilated", True), multi_grid=getattr(model, "multi_grid", True))
             if getattr(model, "_model_id", None) != 1:
                 kw["path_num"] = model.path_num
             stages.append(type(model)(**kw).eval().share_weights_with(model))

@@ -88,7 +88,7 @@ def synth_state_dict(spec, h, w, seed=0, init="calibrated"):
     variance to the trunk, so an un-normalised 16-block ResNet-34 ends ~2x hotter than the 8-block ResNet-18, the
     attention scores grow with it and fp32 evaluations of the same graph drift apart (see QK_GAIN above).  The factor
     is 1 for ResNet-18."""
-    nblocks = len(arch.backbone_blocks(spec.backbone))
+    nblocks = len(arch.spec_blocks(spec))
     # measured with the CPU oracle: these factors keep c4 rms of ResNet-34 / ResNet-50 at the ResNet-18 level (~9 at full size)
     g2 = np.float32(BOTTLENECK_GAIN * (16.0 / nblocks) ** BOTTLENECK_DEPTH_EXP if arch.is_bottleneck(spec.backbone) else (8.0 / nblocks) ** 0.77)
     if init == "reference":

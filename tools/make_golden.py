@@ -6,6 +6,7 @@ to the reference objects is the one SURVEY.md §8c documents: `layer_normN` is r
 size of the input, because the shipped modules hard-code LayerNorm([97,193]) (td4_psp18.py:107-110).
 
     python tools/make_golden.py            # writes tests/golden/
+    python tools/make_golden.py --arch     # only the backbone-layout / class-count fixtures (ARCH_CASES) + the pspnet inventory
 """
 import hashlib
 import os
@@ -27,14 +28,14 @@ THREADS = 8
 OUT = os.path.join(ROOT, "tests", "golden")
 
 
-def build_reference(name, backbone, H, W, seed):
-    spec = arch.model_spec(name, 19, backbone)
-    h, w = arch.feat_size(H), arch.feat_size(W)
+def build_reference(name, backbone, H, W, seed, nclass=19, dilated=True, multi_grid=True):
+    spec = arch.model_spec(name, nclass, backbone, dilated, multi_grid)
+    h, w = arch.feat_size(H, dilated), arch.feat_size(W, dilated)
     if name == "td4":
-        m = ref_td4.td4_psp18(nclass=19, path_num=4, model_path=None, backbone=backbone)
+        m = ref_td4.td4_psp18(nclass=nclass, path_num=4, model_path=None, backbone=backbone, dilated=dilated, multi_grid=multi_grid)
         LN = ref_td4.Layer_Norm
     else:
-        m = ref_td2.td2_psp50(nclass=19, path_num=2, model_path=None, backbone=backbone)
+        m = ref_td2.td2_psp50(nclass=nclass, path_num=2, model_path=None, backbone=backbone, dilated=dilated, multi_grid=multi_grid)
         LN = ref_td2.Layer_Norm
     for i in range(1, spec.path_num + 1):
         setattr(m, "layer_norm%d" % i, LN([h, w]))
@@ -113,10 +114,73 @@ def psp_goldens(meta, digests):
             print(tag, digests[tag + "_stats"])
 
 
+# Backbone layouts and class counts beyond the shipped ones (the constructors' dilated / multi_grid / nclass; pspnet on ResNet-18 / 34).
+# (name, backbone, H, W, T, nclass, dilated, multi_grid, kept frames): every frame's low-resolution logits; the full logits and c4 / z of the
+# kept frames only (z only where d_model <= 512), so that each fixture stays under 1 MiB.
+ARCH_CASES = [("td4", "resnet18", 33, 65, 8, 19, True, False, (0, 3, 7)),     # every path in steady state (t = 3..7 -> paths 3,0,1,2,3)
+              ("td2", "resnet50", 33, 65, 4, 19, True, False, (3,)),
+              ("td2", "resnet18", 65, 129, 4, 19, False, True, (3,)),         # output stride 32: 3 x 5 features
+              ("td2", "resnet18", 33, 65, 3, 40, True, True, (2,)),           # NYUD-v2's 40 classes
+              ("psp", "resnet18", 33, 65, 1, 19, True, True, (0,)),
+              ("psp", "resnet34", 65, 129, 1, 19, False, True, (0,))]
+
+
+def arch_tag(name, bb, H, W, nclass, dilated, multi_grid):
+    return "%s_%s_%dx%d%s%s%s" % (name, bb, H, W, "" if dilated else "_nodil", "" if (multi_grid or not dilated) else "_nomg",
+                                  "" if nclass == 19 else "_nc%d" % nclass)
+
+
+def arch_goldens(meta, only=()):
+    for name, bb, H, W, T, nc, dil, mg, keep in ARCH_CASES:
+        tag = arch_tag(name, bb, H, W, nc, dil, mg)
+        if only and tag not in only:
+            continue
+        frames = weights.synth_video(H, W, T, seed=1)
+        arrs = {}
+        if name == "psp":
+            spec = arch.model_spec("psp", nc, bb, dil, mg)
+            sd = weights.synth_state_dict(spec, arch.feat_size(H, dil), arch.feat_size(W, dil), 0)
+            m = ref_psp.pspnet(nclass=nc, model_path=None, backbone=bb, dilated=dil, multi_grid=mg).eval()
+            m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+            cur = {}
+            hs = [m.pretrained.layer4.register_forward_hook(lambda mod, i, o: cur.__setitem__("c4", o)),
+                  m.head.conv5[0].register_forward_hook(lambda mod, i, o: cur.__setitem__("z", o)),
+                  m.head.register_forward_hook(lambda mod, i, o: cur.__setitem__("lowres", o))]
+            with torch.no_grad():
+                out = m(torch.from_numpy(frames[0]), pos_id=0)
+            for h_ in hs:
+                h_.remove()
+            arrs.update({"f0_%s" % k: v.numpy().astype(np.float32) for k, v in cur.items()})
+            arrs["f0_logits"] = out.numpy().astype(np.float32)
+        else:
+            spec, m = build_reference(name, bb, H, W, 0, nc, dil, mg)
+            for t, r in enumerate(run_traced(spec, m, frames)):
+                kept = ("logits", "c4") + (("z",) if spec.d_model <= 512 else ()) if t in keep else ()
+                for k in ("lowres",) + kept:
+                    arrs["f%d_%s" % (t, k)] = r[k].astype(np.float32)
+        fn = os.path.join(OUT, tag + ".npz")
+        np.savez_compressed(fn, __meta__=np.array(meta), **arrs)
+        print("wrote", fn, "%.2f MB" % (os.path.getsize(fn) / 1e6))
+    if not only or "psp_state_dict_inventory" in only:
+        # name -> shape of the REAL pspnet state dicts on the BasicBlock backbones (the inventory arch.state_dict_shapes must reproduce)
+        import json
+        inv = {}
+        for bb in ("resnet18", "resnet34"):
+            m = ref_psp.pspnet(nclass=19, model_path=None, backbone=bb)
+            inv[bb] = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+        fn = os.path.join(OUT, "psp_state_dict_inventory.json")
+        with open(fn, "w") as f:
+            json.dump(inv, f, indent=0)
+        print("wrote", fn)
+
+
 def main():
     torch.set_num_threads(THREADS)
     os.makedirs(OUT, exist_ok=True)
     meta = "torch %s, threads %d" % (torch.__version__, THREADS)
+    if "--arch" in sys.argv:                                        # `make_golden.py --arch [tag ...]`: the backbone-layout / class-count fixtures only
+        arch_goldens(meta, [a for a in sys.argv[1:] if not a.startswith("-")])
+        return
 
     # ---- small, fully traced cases (every stage boundary) -------------------------------------------------
     # T: every path in steady state at least twice (td4: warm-up = frames 0..2, so T = 11 gives paths 3,0,1,2 | 3,0,1,2 at t = 3..10;
@@ -177,6 +241,7 @@ def main():
     fn = os.path.join(OUT, "fullsize_digests.npz")
     np.savez_compressed(fn, __meta__=np.array(meta), **digests)
     print("wrote", fn)
+    arch_goldens(meta)
 
 
 if __name__ == "__main__":
