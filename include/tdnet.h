@@ -48,9 +48,31 @@ typedef struct tdnet_cfg {
  * tdnet_opts_default() fills the defaults; fields left 0 by a caller that memset()s the struct select the plain variants. */
 #define TDNET_WINOGRAD_DEFAULT 3
 #define TDNET_ATTENTION_DEFAULT 2
-#define TDNET_FUSION_DEFAULT 2072614  /* 2 | 4 | 32 | 8192 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 (measurements: DESIGN.md 5, DESIGN_experiments.md) */
-#define TDNET_FUSION_MASK 2072614     /* the bits of tdnet_opts.fusion that exist (= the default); the others are cleared and ignored */
-#define TDNET_OVERLAP_DEFAULT 41   /* row-parity chains with 4 channels per lane (+2 %) on the LDS-DMA-fed GEMM (+0.9 %): profiles/r03a_*, r03m_* */
+/* The live bits of tdnet_opts.fusion and tdnet_opts.overlap by name (what each does: the field comments below, which cite them by value). */
+#define TDNET_FUSION_LN_STATS 2            /* LayerNorm strip statistics from the attention epilogue */
+#define TDNET_FUSION_LN_IN_HEAD 4          /* LayerNorm inside the head's Winograd input transform */
+#define TDNET_FUSION_A_DIRECT 32           /* Cout <= 64 convs: A operand straight from global memory */
+#define TDNET_FUSION_DMA_LOADERS 8192      /* precision 1: LDS-DMA conv tiles with dedicated loader waves */
+#define TDNET_FUSION_DMA_NARROW 32768      /* precision 1: narrow LDS-DMA conv tiles on small maps and ResNet layer1 */
+#define TDNET_FUSION_STEM_ROWS 65536       /* the 7x7 stem on a packed-row image */
+#define TDNET_FUSION_CONV_GROUPS 131072    /* precision 1: convs that share a kernel form in one launch */
+#define TDNET_FUSION_CLS_IN_HEAD 262144    /* the classifier inside the head conv's Winograd output transform */
+#define TDNET_FUSION_SPLIT_NARROW 524288   /* precision 2: the narrow direct convs and the packed-row stem on the split bf16 MFMA */
+#define TDNET_FUSION_LATE_CHAIN 1048576    /* the cache-only attention chain forks in front of the first dilated block */
+#define TDNET_OVERLAP_CHAINS 1             /* row-parity chains on two streams */
+#define TDNET_OVERLAP_LOWREG_TRANSFORMS 2  /* the low-register F(4x4) transform kernels everywhere */
+#define TDNET_OVERLAP_CHAINS_ANY_SIZE 4    /* the chains at any map size */
+#define TDNET_OVERLAP_GEMM_DMA 8           /* the Winograd GEMMs on the LDS-DMA-fed kernel */
+#define TDNET_OVERLAP_VW_SHIFT 4           /* bits 4-5: log2 of the channels per lane of the chunked transform kernels */
+#define TDNET_OVERLAP_VW_MASK 0x30
+/* 2072614: the measured default (measurements: DESIGN.md 5, DESIGN_experiments.md) */
+#define TDNET_FUSION_DEFAULT (TDNET_FUSION_LN_STATS | TDNET_FUSION_LN_IN_HEAD | TDNET_FUSION_A_DIRECT | TDNET_FUSION_DMA_LOADERS | TDNET_FUSION_DMA_NARROW | \
+                              TDNET_FUSION_STEM_ROWS | TDNET_FUSION_CONV_GROUPS | TDNET_FUSION_CLS_IN_HEAD | TDNET_FUSION_SPLIT_NARROW | TDNET_FUSION_LATE_CHAIN)
+#define TDNET_FUSION_MASK TDNET_FUSION_DEFAULT   /* the bits of tdnet_opts.fusion that exist (= the default); the others are cleared and ignored */
+/* 41: row-parity chains with 4 channels per lane (+2 %) on the LDS-DMA-fed GEMM (+0.9 %): profiles/r03a_*, r03m_* */
+#define TDNET_OVERLAP_DEFAULT (TDNET_OVERLAP_CHAINS | TDNET_OVERLAP_GEMM_DMA | (2 << TDNET_OVERLAP_VW_SHIFT))
+/* 0x3f: the bits of tdnet_opts.overlap that exist: 1 | 2 | 4 | 8 | 16 | 32 */
+#define TDNET_OVERLAP_MASK (TDNET_OVERLAP_CHAINS | TDNET_OVERLAP_LOWREG_TRANSFORMS | TDNET_OVERLAP_CHAINS_ANY_SIZE | TDNET_OVERLAP_GEMM_DMA | TDNET_OVERLAP_VW_MASK)
 typedef struct tdnet_opts {
     int32_t winograd;        /* conv algorithm: 0 = direct implicit GEMM everywhere, 3 (default) = Winograd F(4x4,3x3) for the stride-1 3x3
                                 convs with Cin, Cout >= 128 (ResNet layers 2-4 + FCN head), 4 = F(4x4,3x3) for every stride-1 3x3 (test
@@ -95,7 +117,6 @@ typedef struct tdnet_opts {
                                 Retired, ignored: 64, 128 (DESIGN_experiments.md 4.1d, 9.2, 10.10).                                   */
     int32_t reserved[8];     /* must be 0 (round 4: cu_reserve / cu_mode, the CU-mask-partitioned pipeline, -2.5x, removed)        */
 } tdnet_opts;
-#define TDNET_OVERLAP_MASK 0x3f    /* the bits of tdnet_opts.overlap that exist: 1 | 2 | 4 | 8 | 16 | 32 */
 void tdnet_opts_default(tdnet_opts* o);
 
 /* Backbone layout: the `dilated` / `multi_grid` arguments of the reference constructors (resnet.py:138-158).  Every field is 0 or 1. */

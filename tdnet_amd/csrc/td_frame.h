@@ -66,16 +66,14 @@ static int launch_chain_now(tdnet* n, PathLayers& L, hipStream_t s) {
 // The 1x1 stride-1 downsample conv (resnet.py:172-177) on the image rows y = ny * i + cy only: a batched GEMM, batch = row, M = W pixels,
 // row pitch ny * W pixels, one weight set (td_gemm.h GemmArgs.wshare).
 static int run_ds_rows(tdnet* n, const ConvLayer& L, const float* in, int H, int W, float* out, int ny, int cy, hipStream_t s) {
-    if (L.KS != 1 || L.stride != 1 || L.h16 || !L.pers || !gemm_supports(L.Cin)) return td_fail("internal: downsample conv cannot run on image rows");
+    if (L.route != CR_GEMM1X1) return td_fail("internal: downsample conv cannot run on image rows");
     const int rows = (H - cy + ny - 1) / ny;
     if (rows <= 0) return 0;
-    GemmArgs ga;
-    ga.a = in + (size_t)cy * W * L.Cin; ga.wp = L.d_wp; ga.bias = L.d_bias; ga.resid = nullptr; ga.out = out + (size_t)cy * W * L.Cout;
-    ga.M = W; ga.N = L.Cout; ga.NPad = L.CoutPad; ga.K = L.Cin; ga.nbatch = rows; ga.act = L.act; ga.tiles_m = ga.tiles_n = 0; ga.MP = ny * W;
+    GemmArgs ga = gemm_args(L, in + (size_t)cy * W * L.Cin, W, rows, L.d_bias, nullptr, out + (size_t)cy * W * L.Cout, L.act);
+    ga.MP = ny * W;
     ga.wshare = 1;
     prof_begin(n, 0, 0, 2.0 * rows * W * (double)L.Cin * L.Cout, s);
-    if (L.b3) gemm_b3_launch(ga, L.pers > 1 ? L.pers : 0, s);
-    else gemm_launch(ga, L.tile, L.pers > 1 ? L.pers : 0, s);
+    launch_gemm(L, ga, 0, s);
     prof_end(n, s);
     return 0;
 }
@@ -117,7 +115,7 @@ static int launch_chain_now(tdnet* n, PathLayers& L, hipStream_t s);
 static int encode_frame(tdnet* n, PathLayers& L, const float* img, hipStream_t s, int chain_at = -1) {   // chain_at >= 0: fork the cache-only chain in front of that backbone block
     const int DV = n->DV;
     // backbone (resnet.py:204-215)
-    run_stem_pre(n, img, n->H, n->W, n->img4, s, L.stem.stem_rows);
+    run_stem_pre(n, img, n->H, n->W, n->img4, s, L.stem.stem_rows());
     if (n->deep) {                                                     // resnet.py:122-131
         TD_TRY(run_conv(n, L.stem, n->img4, n->H, n->W, nullptr, n->s1b, s));
         TD_TRY(run_conv(n, L.stem2, n->s1b, n->H1, n->W1, nullptr, n->s1, s));
@@ -192,21 +190,21 @@ static int finish_frame(tdnet* n, PathLayers& L, bool steady, hipStream_t s) {
         TD_HIP(hipStreamWaitEvent(s, n->ev_join, 0));                   // join: v' of the newest cached frame is ready
         const CacheSlot& ck = n->slots[n->fifo[n->FIFO - 1]];
         const AtnLayer& A = L.atn[n->P == 4 ? 2 : 0];                   // td4_psp18.py:147 / td2_psp50.py:120
-        stats_nstr = (n->opts.fusion & 2) ? attn_strips(n->Lq, DV) : 0;                                         // LayerNorm strip statistics from the epilogue
+        stats_nstr = (n->opts.fusion & TDNET_FUSION_LN_STATS) ? attn_strips(n->Lq, DV) : 0;                                         // LayerNorm strip statistics from the epilogue
         if (run_attention(n, n->q_cur, ck.k, n->vp, A.d_bias, n->v_cur, n->Lq, n->Lk, DV, n->feat, s, n->opts.attention,
                           stats_nstr ? n->ln_part : nullptr, nullptr, false, /*vt_ready=*/n->vt16 != nullptr, /*b3=*/n->opts.precision >= 2)) return -1;       // v4 + v_cur
         feat = n->feat;
     }
     // (warm-up, td4_psp18.py:142-143: feat = v_cur -- read in place; rounds 1-4 copied it into n->feat, a device copy per warm-up frame)
     // fusion bit 4: the normalised map is never written -- the head's Winograd input transform normalises while it reads `feat`
-    const bool ln_in_head = (n->opts.fusion & 4) && L.head3.wino;
+    const bool ln_in_head = (n->opts.fusion & TDNET_FUSION_LN_IN_HEAD) && L.head3.wino;
     const bool ln16 = L.head3.in16;                                     // fp16 mode: n->ln holds the map as fp16; the fp32 stage is made on request
     run_layernorm(n, feat, n->Lq, DV, L.d_ln_g, L.d_ln_b, n->ln_part, n->ln_mean, n->ln_rstd, ln_in_head ? nullptr : n->ln, s, stats_nstr, ln16);
     n->ln_pending = ln_in_head || ln16;
     n->ln_path = (int)(&L - &n->paths[0]);
     // fusion bit 262144 (round 6): the 1x1 classifier inside the head conv's Winograd output transform (k_wino4_out_cls): the hidden map is never
     // written, one launch fewer, low-resolution logits bit-identical to the two-kernel form
-    const bool cls_in_head = (n->opts.fusion & 262144) && L.head3.wino && L.head3.chunks == 1 && wino_out_cls_supports(n->MID, n->cfg.nclass);
+    const bool cls_in_head = (n->opts.fusion & TDNET_FUSION_CLS_IN_HEAD) && L.head3.wino && L.head3.chunks == 1 && wino_out_cls_supports(n->MID, n->cfg.nclass);
     const ClsArgs ca = {L.d_cls_w, L.d_cls_b, n->lowres, n->cfg.nclass};
     if (ln_in_head) {
         const LnFuse lf = {n->ln_mean, n->ln_rstd, L.d_ln_g, L.d_ln_b};
@@ -313,7 +311,7 @@ static int forward_lowres_impl(tdnet* n, const float* img, int pos_id, hipStream
     // results bit for bit.  Forking in front of layer1's second block or of layer2: -1.0 % / -0.7 % with precision 2; one / two / three blocks INSIDE the row-parity run
     // (layer3's second block, layer4's blocks): 278.1 -> 275.5 / 275.3 / 273.7 fp32 (experiments TDNET_CHAIN_AT / TDNET_CHAIN_SHIFT, visits r6ak, r6am).
     int chain_at = -1;
-    if (steady && (n->opts.fusion & 1048576) && n->opts.precision != 1)
+    if (steady && (n->opts.fusion & TDNET_FUSION_LATE_CHAIN) && n->opts.precision != 1)
         for (size_t b = 0; b < n->bspec.size() && b < L.blocks.size(); ++b)
             if (n->bspec[b].dil1 > 1 || n->bspec[b].dil2 > 1) { chain_at = (int)b; break; }
     if (steady && chain_at < 0 && launch_chain_now(n, L, s)) return -1;

@@ -3,8 +3,10 @@
 //
 // Split of the former td_model.hip monolith (round 5):
 //   td_handle.h    this file
-//   td_weights.h   strict state_dict inventory, BN folding (fp64), packing, upload, the row-parity plan, workspace allocation
-//   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier / upsample)
+//   td_weights.h   strict state_dict inventory, BN folding (fp64), plan_conv (which kernel each conv runs on, decided once), packing, upload,
+//                  the row-parity plan, workspace allocation
+//   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier / upsample):
+//                  a switch on the layer's planned route
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
@@ -129,31 +131,51 @@ static int feature_size(int n, const std::vector<BlockSpec>& blocks) {
 // ---------------------------------------------------------------------------------------------------------------
 // device conv layer
 // ---------------------------------------------------------------------------------------------------------------
+// The launch path of a conv layer and, where that path is a GEMM, its kernel.  plan_conv (td_weights.h) fixes both; nothing changes them
+// afterwards, and the launch helpers (td_launch.h) switch on them without looking at the options again.
+enum ConvRoute {
+    CR_IGEMM,                                                          // fp32 implicit GEMM (td_conv.h conv_launch)
+    CR_ADIRECT,                                                        // fp32, Cout <= 64: A operand straight from global (td_conv_ad.h, fusion bit 32); stem: NHWC4 taps
+    CR_ADIRECT_ROWS,                                                   // ... the 7x7 stem on the packed-row image (td_conv_ad.h STEM = 2; fusion bit 65536)
+    CR_ADIRECT_B3,                                                     // precision 2: the narrow direct convs on the split bf16 MFMA (td_conv_ad_b3.h; fusion bit 524288)
+    CR_ADIRECT_ROWS_B3,                                                // ... the packed-row stem (td_conv_ad_b3.h STEM = 2)
+    CR_GEMM1X1,                                                        // a stride-1 1x1 conv as one persistent GEMM (`gemm`: GK_PERSISTENT or GK_B3)
+    CR_STEM_H,                                                         // precision 1: the 7x7 stem on the fp16 MFMA (td_conv_h.h)
+    CR_CONV_H,                                                         // precision 1: fp16-MFMA operands, register-staged (td_conv_h.h)
+    CR_CONV_DMA,                                                       // precision 1, fp16 map in: the LDS-DMA kernel, tile form `rh` (td_conv_hd.h)
+    CR_WINO                                                            // Winograd F(4x4,3x3): d_wp = 36 packed 1x1 weight sets, `gemm` runs them (td_wino.h)
+};
+enum GemmKernel {
+    GK_CONV,                                                           // one tile per workgroup on the conv kernel (gemm_persistent = 0, or K % 64 != 0)
+    GK_PERSISTENT,                                                     // k_gemm_persistent (td_gemm.h)
+    GK_DMA,                                                            // the LDS-DMA-fed kernel (td_gemm_dma.h; tdnet_opts.overlap bit 8)
+    GK_B3                                                              // k_gemm_b3: d_wp holds the three bf16 parts of the weights (td_gemm_b3.h gemm_b3_pack; tdnet_opts.precision = 2)
+};
 struct ConvLayer {
     int Cin = 0, Cout = 0, KS = 1, stride = 1, dil = 1, pad = 0, act = 0;
     bool stem = false;
-    bool stem_rows = false;                                            // the 7x7 fp32 stem on the packed-row image (td_conv_ad.h STEM = 2; tdnet_opts.fusion bit 65536)
-    bool h16 = false;                                                  // fp16-MFMA operands (td_conv_h.h)
-    bool adirect = false;                                              // Cout <= 64: A operand straight from global (td_conv_ad.h, fusion bit 32)
-    bool in16 = false, out16 = false;                                  // h16 only: the input (+ residual) / output map is stored as fp16 in HBM
-    int rh = 0;                                                        // h16 + in16: != 0 -> the LDS-DMA kernel with 64 rh rows per tile (td_conv_hd.h); M_out: its output pixels
-    long M_out = 0;
+    ConvRoute route = CR_IGEMM;
+    GemmKernel gemm = GK_CONV;                                         // CR_WINO, CR_GEMM1X1 only
+    bool in16 = false, out16 = false;                                  // fp16 routes only: the input (+ residual) / output map is stored as fp16 in HBM
+    int rh = 0;                                                        // CR_CONV_DMA: the ConvDmaCode of its tile (64 rh rows for the plain forms; td_conv_hd.h)
     bool rowimg_off = false;                                           // test hook (tdnet_op_conv2d_f16io tile + 32): keep the tap-by-tap LDS-DMA kernel
-    int pers = 1;                                                      // tdnet_opts.gemm_persistent of the owning handle
+    int pers = 1;                                                      // tdnet_opts.gemm_persistent of the owning handle (> 1: the forced grid of the persistent GEMMs)
     int chunks = 1;                                                    // > 1: run as that many row-parity chunks (tdnet_opts.overlap bit 1); the GEMM tile is picked for T / chunks rows
-    int b3 = 0;                                                        // != 0: d_wp holds the three bf16 parts of the weights (td_gemm_b3.h gemm_b3_pack; tdnet_opts.precision = 2) and the GEMM runs on k_gemm_b3
-    bool gdma = false;                                                 // the Winograd GEMMs on the LDS-DMA-fed kernel (td_gemm_dma.h; tdnet_opts.overlap bit 8)
     int vw = 0;                                                        // != 0: the low-register F(4x4) transform kernels with vw channels per lane (td_wino.h k_wino4_*_c)
-    int wino = 0;                                                      // Winograd output tile edge m (0 = direct, 4 = F(4x4,3x3)): d_wp = 36 packed 1x1 weight sets (td_wino.h)
+    int wino = 0;                                                      // CR_WINO: the output tile edge m = 4, otherwise 0
     float* d_zero = nullptr;                                           // zero bias for the batched GEMM pass
     ConvTile tile = CT_128x128;
     int CoutPad = 0, nsteps = 0;
     float* d_wp = nullptr;
     float* d_bias = nullptr;
+    bool h16() const { return route == CR_STEM_H || route == CR_CONV_H || route == CR_CONV_DMA; }   // fp16-MFMA operands
+    bool stem_rows() const { return route == CR_ADIRECT_ROWS || route == CR_ADIRECT_ROWS_B3; }      // reads the packed-row image
     double flops_per_pixel() const { return 2.0 * Cout * (stem ? 3.0 * KS * KS : (double)Cin * KS * KS); }
 };
 
 // Per-handle kernel configuration (include/tdnet.h tdnet_opts); nothing here is process-wide: two handles in one process may differ.
+static_assert(TDNET_FUSION_DEFAULT == 2072614 && TDNET_FUSION_MASK == 2072614 && TDNET_OVERLAP_DEFAULT == 41 && TDNET_OVERLAP_MASK == 0x3f,
+              "the named option bits of include/tdnet.h must add up to the documented values");
 static tdnet_opts opts_or_default(const tdnet_opts* o) {
     tdnet_opts d;
     tdnet_opts_default(&d);
@@ -166,7 +188,7 @@ static tdnet_opts opts_or_default(const tdnet_opts* o) {
     d.attention = d.attention < 0 ? 0 : d.attention > 2 ? 2 : d.attention;
     d.fusion &= TDNET_FUSION_MASK;                                    // retired bits are ignored: opts report only what is in effect
     d.overlap = d.overlap < 0 ? 0 : d.overlap & TDNET_OVERLAP_MASK;
-    if (((d.overlap >> 4) & 3) == 3) d.overlap &= ~0x30;
+    if ((d.overlap & TDNET_OVERLAP_VW_MASK) == TDNET_OVERLAP_VW_MASK) d.overlap &= ~TDNET_OVERLAP_VW_MASK;
     d.reserved0 = 0;
     for (int& r : d.reserved) r = 0;
     return d;

@@ -53,6 +53,30 @@ static void launch_wino4_c(bool out_side, const WinoArgs& wa, hipStream_t s) {
     else TD_LAUNCH((k_wino4_in_c<VW>), dim3(wino_chunk_grid(wa.Tc, wa.C, VW)), dim3(256), 0, s, wa);
 }
 
+// The launch arguments of layer L on an H x W input map / as one GEMM of `nbatch` x M rows
+static ConvArgs conv_args(const ConvLayer& L, const float* in, int H, int W, const float* resid, float* out) {
+    const int Ho = out_size(H, L.KS, L.stride, L.dil, L.pad), Wo = out_size(W, L.KS, L.stride, L.dil, L.pad);
+    return ConvArgs{in, L.d_wp, L.d_bias, resid, out, H, W, L.Cin, Wo, L.Cout, L.CoutPad, L.stride, L.dil, L.pad, Ho * Wo, L.nsteps, L.act, 0, 1};
+}
+static GemmArgs gemm_args(const ConvLayer& L, const float* a, int M, int nbatch, const float* bias, const float* resid, float* out, int act) {
+    GemmArgs ga;
+    ga.a = a; ga.wp = L.d_wp; ga.bias = bias; ga.resid = resid; ga.out = out;
+    ga.M = M; ga.N = L.Cout; ga.NPad = L.CoutPad; ga.K = L.Cin; ga.nbatch = nbatch; ga.act = act; ga.tiles_m = ga.tiles_n = 0; ga.MP = M;
+    return ga;
+}
+// The GEMM(s) of a CR_WINO / CR_GEMM1X1 layer on the kernel it was planned for.  b3_grid: the split kernel's grid where the options force none (0: its own)
+static void launch_gemm(const ConvLayer& L, const GemmArgs& ga, int b3_grid, hipStream_t s) {
+    const int forced_grid = L.pers > 1 ? L.pers : 0;
+    switch (L.gemm) {
+    case GK_B3: gemm_b3_launch(ga, forced_grid ? forced_grid : b3_grid, s); break;
+    case GK_DMA: gemm_dma_launch(ga, forced_grid, s); break;
+    case GK_PERSISTENT: gemm_launch(ga, L.tile, forced_grid, s); break;
+    case GK_CONV:                                                      // the same GEMMs as batched 1x1 convs over a 1 x M map, one tile per workgroup
+        conv_launch(ConvArgs{ga.a, ga.wp, ga.bias, ga.resid, ga.out, 1, ga.M, ga.K, ga.M, ga.N, ga.NPad, 1, 1, 0, ga.M, L.nsteps, ga.act, 0, ga.nbatch}, L.tile, 1, false, s);
+        break;
+    }
+}
+
 // Winograd F(4x4) conv (or one chunk of it): input transform -> 36 batched GEMMs -> output transform, all on stream s.
 // V / Mb: workspaces for THIS call ([nb][Tc + pad][C]); nullptr = the handle's (n->wino_v / wino_m) or, without a handle, temporary ones.
 // cls != nullptr: the conv is the FCN head's 3x3 and its output transform also applies the 1x1 classifier (k_wino4_out_cls): `out` is not written
@@ -96,25 +120,11 @@ static int run_wino(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
     };
     transform(false);
     prof_begin(n, 0, 2, 2.0 * nb * Tc * (double)L.Cin * L.Cout, s);
-    if (n && (probe_skip() & 8)) { /* timing probe: no GEMMs */ }
-    else if (L.pers && gemm_supports(L.Cin)) {
-        GemmArgs ga;
-        ga.a = V; ga.wp = L.d_wp; ga.bias = L.d_zero; ga.resid = nullptr; ga.out = Mb;
-        ga.M = (int)Tc; ga.N = L.Cout; ga.NPad = L.CoutPad; ga.K = L.Cin; ga.nbatch = nb; ga.act = 0; ga.tiles_m = ga.tiles_n = 0; ga.MP = (int)Tc;
-        // the split GEMM's persistent grid: 512 workgroups (two per CU); a row-parity CHUNK's GEMM -- two of them are in flight, one per chain -- takes 320: of
-        // layer 4's 576 tiles 256 workgroups then walk two and the sibling's first workgroups find a free slot at once.  Frame with precision 2 at 1024x2048, by grid of the
-        // chunks' GEMMs (profiles/r06ao_*): 512: 339.4, 288: 338.6, 320: 346.0, 352: 344.7, 384: 344.5, 448: 342.1 frames/s.
-        if (L.b3) gemm_b3_launch(ga, L.pers > 1 ? L.pers : chunked ? 320 : 0, s);
-        // (the fp32 kernel keeps its 768 workgroups for the chunks too: 448 / 512 / 576 / 640 / 1024 gave 273.1 / 273.4 / 271.8 / 275.5 / 274.3 against 278.9 frames/s)
-        else if (L.gdma && gemm_dma_supports(L.Cin, L.Cout, L.tile)) gemm_dma_launch(ga, L.pers > 1 ? L.pers : 0, s);
-        else gemm_launch(ga, L.tile, L.pers > 1 ? L.pers : 0, s);
-    } else {
-        ConvArgs g;
-        g.in = V; g.wp = L.d_wp; g.bias = L.d_zero; g.resid = nullptr; g.out = Mb;
-        g.H = 1; g.W = (int)Tc; g.Cin = L.Cin; g.Wo = (int)Tc; g.Cout = L.Cout; g.CoutPad = L.CoutPad;
-        g.stride = 1; g.dil = 1; g.pad = 0; g.M = (int)Tc; g.nsteps = L.nsteps; g.act = 0; g.tiles_n = 0; g.nbatch = nb;
-        conv_launch(g, L.tile, 1, false, s);
-    }
+    // the split GEMM's persistent grid: 512 workgroups (two per CU); a row-parity CHUNK's GEMM -- two of them are in flight, one per chain -- takes 320: of
+    // layer 4's 576 tiles 256 workgroups then walk two and the sibling's first workgroups find a free slot at once.  Frame with precision 2 at 1024x2048, by grid of the
+    // chunks' GEMMs (profiles/r06ao_*): 512: 339.4, 288: 338.6, 320: 346.0, 352: 344.7, 384: 344.5, 448: 342.1 frames/s.
+    // (the fp32 kernel keeps its 768 workgroups for the chunks too: 448 / 512 / 576 / 640 / 1024 gave 273.1 / 273.4 / 271.8 / 275.5 / 274.3 against 278.9 frames/s)
+    if (!(n && (probe_skip() & 8))) launch_gemm(L, gemm_args(L, V, (int)Tc, nb, L.d_zero, nullptr, Mb, 0), chunked ? 320 : 0, s);   // (timing probe: no GEMMs)
     prof_end(n, s);
     transform(true);
     if (own) { TD_HIP(hipStreamSynchronize(s)); hipFree(V); hipFree(Mb); }
@@ -157,31 +167,28 @@ static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
         }
         return run_wino(n, L, in, H, W, resid, out, s, lnf, WinoChunk(), nullptr, nullptr, cls);
     }
-    ConvArgs a;
-    a.in = in; a.wp = L.d_wp; a.bias = L.d_bias; a.resid = resid; a.out = out;
-    a.H = H; a.W = W; a.Cin = L.Cin; a.Wo = Wo; a.Cout = L.Cout; a.CoutPad = L.CoutPad;
-    a.stride = L.stride; a.dil = L.dil; a.pad = L.pad; a.M = Ho * Wo; a.nsteps = L.nsteps; a.act = L.act; a.tiles_n = 0; a.nbatch = 1;
+    const ConvArgs a = conv_args(L, in, H, W, resid, out);
     // dominant: bits 0-1 = 1 for the 128x128-tile / LDS-DMA 3x3 convs (the kernel set of rounds 3-4), bit 2 = EVERY 3x3 conv that reads an fp16 map
     // (the fixed set of the fp16 mode's roofline since round 5: routing a layer to another kernel does not change it)
-    prof_begin(n, 0, (((L.tile == CT_128x128 || L.tile == CT_128x128_DEEP || L.rh) && L.KS == 3 && !L.stem) ? 1 : 0) | ((L.h16 && L.in16 && L.KS == 3 && !L.stem) ? 4 : 0), L.flops_per_pixel() * a.M, s);
-    if (L.h16 && L.stem) conv_launch_stem_h(a, L.out16, s);
-    else if (L.h16 && L.rh) launch_conv_dma_forms(L, a, s);
-    else if (L.h16) conv_launch_h(a, L.tile, L.KS, L.in16, L.out16, s);
-    else if (L.adirect && L.b3 && !L.stem_rows) conv_launch_adirect_b3(a, L.KS, 0, s);   // precision 2, narrow convs (incl. the stride-1 1x1 ones kept off the GEMM route)
-    else if (L.pers && L.KS == 1 && L.stride == 1 && !L.stem && gemm_supports(L.Cin)) {
-        GemmArgs ga;
-        ga.a = in; ga.wp = L.d_wp; ga.bias = L.d_bias; ga.resid = resid; ga.out = out;
-        ga.M = a.M; ga.N = L.Cout; ga.NPad = L.CoutPad; ga.K = L.Cin; ga.nbatch = 1; ga.act = L.act; ga.tiles_m = ga.tiles_n = 0; ga.MP = a.M;
-        if (L.b3) gemm_b3_launch(ga, L.pers > 1 ? L.pers : 0, s);
-        else gemm_launch(ga, L.tile, L.pers > 1 ? L.pers : 0, s);
-    } else if (L.adirect && L.stem_rows) {                              // the image is padded already: its own geometry, 3 channels, no padding taps
+    prof_begin(n, 0, (((L.tile == CT_128x128 || L.tile == CT_128x128_DEEP || L.rh) && L.KS == 3 && !L.stem) ? 1 : 0) | ((L.h16() && L.in16 && L.KS == 3 && !L.stem) ? 4 : 0), L.flops_per_pixel() * a.M, s);
+    switch (L.route) {
+    case CR_STEM_H: conv_launch_stem_h(a, L.out16, s); break;
+    case CR_CONV_DMA: launch_conv_dma_forms(L, a, s); break;
+    case CR_CONV_H: conv_launch_h(a, L.tile, L.KS, L.in16, L.out16, s); break;
+    case CR_ADIRECT_B3: conv_launch_adirect_b3(a, L.KS, 0, s); break;   // precision 2, narrow convs (incl. the stride-1 1x1 ones kept off the GEMM route)
+    case CR_GEMM1X1: launch_gemm(L, gemm_args(L, in, a.M, 1, L.d_bias, resid, out, L.act), 0, s); break;
+    case CR_ADIRECT_ROWS:
+    case CR_ADIRECT_ROWS_B3: {                                         // the image is padded already: its own geometry, 3 channels, no padding taps
         ConvArgs r = a;
         r.H = stem_rows_hp(H); r.W = stem_rows_wp(W); r.Cin = 3; r.pad = 0;
-        if (L.b3) conv_launch_adirect_b3(r, L.KS, 2, s);
+        if (L.route == CR_ADIRECT_ROWS_B3) conv_launch_adirect_b3(r, L.KS, 2, s);
         else conv_launch_adirect(r, L.KS, 2, s);
+        break;
     }
-    else if (L.adirect) conv_launch_adirect(a, L.KS, L.stem ? 1 : 0, s);
-    else conv_launch(a, L.tile, L.KS, L.stem, s);
+    case CR_ADIRECT: conv_launch_adirect(a, L.KS, L.stem ? 1 : 0, s); break;
+    case CR_IGEMM: conv_launch(a, L.tile, L.KS, L.stem, s); break;
+    case CR_WINO: break;                                               // (ran above)
+    }
     prof_end(n, s);
     if (Ho_out) *Ho_out = Ho;
     if (Wo_out) *Wo_out = Wo;
@@ -192,11 +199,11 @@ struct ConvCall { const ConvLayer* L; const float* in; int H, W; float* out; };
 // Up to three independent convs in one launch when they share a kernel form (fp16 mode: the register-staged k_conv_igemm_h on the same tile,
 // kernel size and storage types; `fusion` bit 131072); otherwise one launch each, in order.
 static int run_conv_group(tdnet* n, const ConvCall* c, int ng, hipStream_t s, int* Ho_out = nullptr, int* Wo_out = nullptr) {   // Ho / Wo: of c[0]
-    bool same = n && (n->opts.fusion & 131072) && ng >= 2 && ng <= 3;
+    bool same = n && (n->opts.fusion & TDNET_FUSION_CONV_GROUPS) && ng >= 2 && ng <= 3;
     for (int g = 0; same && g < ng; ++g) {
         const ConvLayer& L = *c[g].L;
         const ConvLayer& L0 = *c[0].L;
-        same = L.h16 && !L.stem && !L.rh && !L.wino && L.in16 == L.out16 && L.in16 == L0.in16 && (g == 0 ? (L.KS == 1 || L.KS == 3) : L.KS == 1) &&
+        same = L.route == CR_CONV_H && L.in16 == L.out16 && L.in16 == L0.in16 && (g == 0 ? (L.KS == 1 || L.KS == 3) : L.KS == 1) &&
                conv_tile_dims(L.tile).BM == conv_tile_dims(L0.tile).BM && conv_tile_dims(L.tile).BN == conv_tile_dims(L0.tile).BN;
     }
     if (!same) {
@@ -207,13 +214,10 @@ static int run_conv_group(tdnet* n, const ConvCall* c, int ng, hipStream_t s, in
     double flops = 0.0;
     for (int g = 0; g < ng; ++g) {
         const ConvLayer& L = *c[g].L;
-        const int Ho = out_size(c[g].H, L.KS, L.stride, L.dil, L.pad), Wo = out_size(c[g].W, L.KS, L.stride, L.dil, L.pad);
-        a[g].in = c[g].in; a[g].wp = L.d_wp; a[g].bias = L.d_bias; a[g].resid = nullptr; a[g].out = c[g].out;
-        a[g].H = c[g].H; a[g].W = c[g].W; a[g].Cin = L.Cin; a[g].Wo = Wo; a[g].Cout = L.Cout; a[g].CoutPad = L.CoutPad;
-        a[g].stride = L.stride; a[g].dil = L.dil; a[g].pad = L.pad; a[g].M = Ho * Wo; a[g].nsteps = L.nsteps; a[g].act = L.act; a[g].tiles_n = 0; a[g].nbatch = 1;
+        a[g] = conv_args(L, c[g].in, c[g].H, c[g].W, nullptr, c[g].out);
         flops += L.flops_per_pixel() * a[g].M;
-        if (g == 0 && Ho_out) *Ho_out = Ho;
-        if (g == 0 && Wo_out) *Wo_out = Wo;
+        if (g == 0 && Ho_out) *Ho_out = out_size(c[0].H, L.KS, L.stride, L.dil, L.pad);
+        if (g == 0 && Wo_out) *Wo_out = a[0].Wo;
     }
     // a 3x3 conv on an fp16 map stays in the fp16 roofline's fixed layer set: the record carries ITS FLOP only (the launch's time includes the 1x1 beside it)
     const bool dom = c[0].L->in16 && c[0].L->KS == 3;
@@ -276,7 +280,7 @@ static void run_ppm(tdnet* n, const float* c4, int h, int w, int C, int XS, int 
     prof_end(n, s);
 }
 
-// rows: the packed-row image of the 7x7 stem (ConvLayer.stem_rows; img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
+// rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
 static void run_stem_pre(tdnet* n, const float* img, int H, int W, float* img4, hipStream_t s, bool rows = false) {
     prof_begin(n, 2, false, 0, s);
     if (rows)

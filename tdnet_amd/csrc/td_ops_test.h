@@ -21,7 +21,7 @@ extern "C" int tdnet_op_conv2d(const float* in, int H, int W, int Cin, const flo
     const int pad = dil * (KS / 2);
     const long M = (long)out_size(H, KS, stride, dil, pad) * out_size(W, KS, stride, dil, pad);
     // tdnet_opts.overlap bit 1: an even-dilation Winograd conv runs as its two row-parity chunks (here one after the other)
-    if (make_conv_layer(L, w, b, Cout, Cin, KS, stride, dil, act, false, M, o, tile < 0 ? -1 : tile, (o.overlap & 1) ? 2 : 1)) return -1;
+    if (plan_conv(L, Cout, Cin, KS, stride, dil, act, false, M, o, tile < 0 ? -1 : tile, (o.overlap & TDNET_OVERLAP_CHAINS) ? 2 : 1) || upload_conv(L, w, b)) return -1;
     int rc = run_conv(nullptr, L, in, H, W, resid, out, (hipStream_t)stream);
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_conv2d: device error");
     free_conv_layer(L);
@@ -56,16 +56,11 @@ extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, con
     if (bias_host) b.assign(bias_host, bias_host + Cout);
     const int pad = dil * (KS / 2);
     const int Ho = out_size(H, KS, stride, dil, pad), Wo = out_size(W, KS, stride, dil, pad);
-    if (make_conv_layer(L, w, b, Cout, Cin, KS, stride, dil, act, false, (long)Ho * Wo, o, tile < 0 ? -1 : tile)) return -1;
-    L.in16 = L.out16 = true;
-    L.rowimg_off = no_rowimg;
-    if (force_rh == CD_256x256 && L.CoutPad % 256) { free_conv_layer(L); return td_fail("tdnet_op_conv2d_f16io: the 256 x 256 tile needs Cout padded to a multiple of 256"); }
-    if (force_rh && !conv_dma_supports(Cin, Cout, KS, L.tile)) {
-        free_conv_layer(L);
-        return td_fail("tdnet_op_conv2d_f16io: this shape cannot run on the LDS-DMA kernel");
-    }
-    if (force_rh) L.rh = force_rh;
-    else if (tile < 0 && Cout >= 128 && conv_dma_supports(Cin, Cout, KS, L.tile)) L.rh = conv_dma_pick_rh((long)Ho * Wo, Cout, L.CoutPad % 256 == 0);
+    // fp16 maps in and out; the LDS-DMA form: the forced one, or for tile -1 by the map's size alone (RH_BY_SIZE -- not the frame's rule), else none
+    if (plan_conv(L, Cout, Cin, KS, stride, dil, act, false, (long)Ho * Wo, o, tile < 0 ? -1 : tile, 1, true, true, force_rh ? force_rh : tile < 0 ? RH_BY_SIZE : CD_NONE, no_rowimg)) return -1;
+    if (force_rh == CD_256x256 && L.CoutPad % 256) return td_fail("tdnet_op_conv2d_f16io: the 256 x 256 tile needs Cout padded to a multiple of 256");
+    if (force_rh && !conv_dma_supports(Cin, Cout, KS, L.tile)) return td_fail("tdnet_op_conv2d_f16io: this shape cannot run on the LDS-DMA kernel");
+    if (upload_conv(L, w, b)) return -1;
     _Float16 *hin = nullptr, *hres = nullptr, *hout = nullptr;
     const long nin = (long)H * W * Cin, nout = (long)Ho * Wo * Cout;
     auto cleanup = [&]() {                                             // one release path, also for the error returns
@@ -89,12 +84,12 @@ extern "C" int tdnet_op_stem(const float* img, int H, int W, const float* w_host
     ConvLayer L;
     std::vector<float> w(w_host, w_host + 64 * 3 * 49), b;
     if (bias_host) b.assign(bias_host, bias_host + 64);
-    if (make_conv_layer(L, w, b, 64, 3, 7, 2, 1, 1, true, (long)H1 * W1, o)) return -1;
+    if (plan_conv(L, 64, 3, 7, 2, 1, 1, true, (long)H1 * W1, o) || upload_conv(L, w, b)) return -1;
     float *img4 = nullptr, *s1 = nullptr;
     const size_t img_floats = std::max((size_t)H * W * 4, (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4);
     if (dev_alloc(&img4, img_floats) || dev_alloc(&s1, (size_t)H1 * W1 * 64)) return -1;
-    if (L.stem_rows) TD_HIP(hipMemsetAsync(img4, 0, img_floats * sizeof(float), s));   // the packed-row image's zero border
-    run_stem_pre(nullptr, img, H, W, img4, s, L.stem_rows);
+    if (L.stem_rows()) TD_HIP(hipMemsetAsync(img4, 0, img_floats * sizeof(float), s));   // the packed-row image's zero border
+    run_stem_pre(nullptr, img, H, W, img4, s, L.stem_rows());
     run_conv(nullptr, L, img4, H, W, nullptr, s1, s);
     run_maxpool(nullptr, s1, H1, W1, 64, out, s);
     TD_HIP(hipStreamSynchronize(s));
@@ -235,7 +230,7 @@ extern "C" double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int 
     const int pad_ = dil * (KS / 2);
     const long M_ = (long)out_size(H, KS, stride, dil, pad_) * out_size(W, KS, stride, dil, pad_);
     // tile -1: the heuristic's choice for this M; overlap bit 1: the conv as its 2 row classes one after the other on the stream
-    if (make_conv_layer(L, w, b, Cout, Cin, KS, stride, dil, 1, false, M_, o, tile, (o.overlap & 1) ? 2 : 1)) return -1.0;
+    if (plan_conv(L, Cout, Cin, KS, stride, dil, 1, false, M_, o, tile, (o.overlap & TDNET_OVERLAP_CHAINS) ? 2 : 1) || upload_conv(L, w, b)) return -1.0;
     float *din = nullptr, *dout = nullptr;
     if (upload(&din, x)) return -1.0;
     const int Ho = out_size(H, KS, stride, dil, L.pad), Wo = out_size(W, KS, stride, dil, L.pad);

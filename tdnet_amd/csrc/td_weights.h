@@ -3,131 +3,147 @@
 #pragma once
 #include "td_handle.h"
 
-// Upload a BN-folded OIHW weight + bias as a ConvLayer for an output of M pixels.
-static int make_conv_layer(ConvLayer& L, const std::vector<float>& w, const std::vector<float>& b, int Cout, int Cin, int KS,
-                           int stride, int dil, int act, bool stem, long M, const tdnet_opts& o, int forced_tile = -1, int chunks = 1) {
+// plan_conv's `rh` argument -- how the tile form of the fp16 LDS-DMA kernel is chosen for a layer that reads an fp16 map: a ConvDmaCode forces
+// that form (CD_NONE: stay on the register-staged kernel), or one of the two rules
+constexpr int RH_FRAME = -1;                                           // the frame's: plan_dma_form
+constexpr int RH_BY_SIZE = -2;                                         // tdnet_op_conv2d_f16io's for tile -1: conv_dma_pick_rh from 128 output channels, no narrow-tile or loader-wave promotion
+
+// The frame's rule: the LDS-DMA tile form of the planned fp16 layer c (fp16 map in, M output pixels), CD_NONE = it stays register-staged.
+static int plan_dma_form(const ConvLayer& c, long M, const tdnet_opts& o) {
+    const bool narrow = (o.fusion & TDNET_FUSION_DMA_NARROW) != 0, same3 = c.KS == 3 && c.stride == 1 && c.pad == c.dil;
+    if (!conv_dma_supports(c.Cin, c.Cout, c.KS, c.tile)) return CD_NONE;
+    // ResNet layer1 (64 -> 64 channels, 3x3): one narrow tile column of the 128-wide packing (plan_conv chose that tile).  Isolated
+    // 11.9 -> 9.8 us at 180x240, 22.0 -> 18.5 us at 256x512 against k_conv_igemm_h<128,64,..>, bit-identical (profiles/r04z_fp16_layer1_*; shipped in round 5)
+    if (c.Cout == 64 && c.CoutPad == 128 && same3 && narrow) return CD_128_N;
+    if (c.Cout < 128) return CD_NONE;                                  // Cout >= 128: the LDS-DMA kernel (td_conv_hd.h)
+    const int rh = conv_dma_pick_rh(M, c.Cout, c.CoutPad % 256 == 0);
+    // Small maps (720x960: 10800 output pixels): a 3x3 "same" conv with <= 256 output channels on NARROW tiles (rows x 64
+    // channels, k_conv_dma_h3n) -- half the weight bytes per K step and CU, the term that dominates there: 128 channels
+    // 13.8 -> 10.3 us, 256 channels 20.6 -> 19.8 us isolated (profiles/r04u_*).  No gain at 32768 pixels.
+    // (256 channels on 128 x 64 tiles as well: 2.1 % instead of 2.6 % in the frame; 512 channels, 64- and 96-row tiles: slower, profiles/r05c_*)
+    if (narrow && same3 && M <= 16384 && c.Cout <= 256) return c.Cout <= 128 ? CD_128_N : CD_192_N;
+    // the 128- and 192-row tiles with four dedicated loader waves (k_conv_dma_h3p): isolated 22.5 -> 21.0 / 57.8 -> 56.7 us; 256 rows: no gain (profiles/r04d_*).
+    // (192 rows with TWELVE matrix waves of 32 x 64 -- three per SIMD instead of two SIMDs with twice the MFMAs -- is 3-5 % faster alone and 0.6 % SLOWER in the frame: profiles/r04z_*.)
+    if (o.fusion & TDNET_FUSION_DMA_LOADERS) return rh == CD_128 ? CD_128_P : rh == CD_192 ? CD_192_P : rh;
+    return rh;
+}
+
+// Which kernel a conv layer with an output of M pixels runs on: route, GEMM kernel, tile, CoutPad, nsteps, rh -- and with them the format upload_conv packs
+// the weights in.  Decided here once, from the geometry and the options alone: pure host arithmetic, no HIP call, no allocation.
+// in16 / out16: the layer's maps are stored as fp16 (they hold for the fp16 routes only); rh: see RH_FRAME; rowimg_off: ConvLayer.
+static int plan_conv(ConvLayer& L, int Cout, int Cin, int KS, int stride, int dil, int act, bool stem, long M, const tdnet_opts& o,
+                     int forced_tile = -1, int chunks = 1, bool in16 = false, bool out16 = false, int rh = RH_FRAME, bool rowimg_off = false) {
+    L = ConvLayer();
     L.Cin = stem ? 4 : Cin; L.Cout = Cout; L.KS = KS; L.stride = stride; L.dil = dil; L.act = act; L.stem = stem;
     L.pad = stem ? KS / 2 : dil * (KS / 2);
-    L.M_out = M;
     L.pers = o.gemm_persistent;
-    const bool deep = o.pipeline != 0;
+    L.rowimg_off = rowimg_off;
     if (!stem && Cin % 32 != 0) return td_fail("conv: Cin=%d is not a multiple of 32", Cin);
-    const bool wino_ok = o.winograd && o.precision != 1 && !stem && KS == 3 && stride == 1 && Cin % 32 == 0 && Cout % 4 == 0 &&
-                         (o.winograd == 4 || (Cin >= 128 && Cout >= 128));
-    L.wino = wino_ok ? 4 : 0;
-    if (L.wino) {
-        L.chunks = (chunks > 1 && dil % chunks == 0 && o.gemm_persistent && gemm_supports(Cin)) ? chunks : 1;
-        chunks = L.chunks;
-        L.vw = (L.chunks > 1 || (o.overlap & 2)) ? (1 << ((o.overlap >> 4) & 3)) : 0;
-        L.gdma = (o.overlap & 8) != 0;
+    const bool deep = o.pipeline != 0, forced = forced_tile >= 0;       // a forced tile (tests, probes): no size rule below moves the layer to another kernel
+    const bool pers_gemm = o.gemm_persistent && gemm_supports(Cin);     // a GEMM over this K runs on the persistent kernels
+    const bool split = o.precision >= 2;                                // the fp32-accurate kernels on the bf16 MFMA
+    const bool split_narrow = split && (o.fusion & TDNET_FUSION_A_DIRECT) && (o.fusion & TDNET_FUSION_SPLIT_NARROW);
+    if (o.winograd && o.precision != 1 && !stem && KS == 3 && stride == 1 && Cin % 32 == 0 && Cout % 4 == 0 && (o.winograd == 4 || (Cin >= 128 && Cout >= 128))) {
+        L.route = CR_WINO;
+        L.wino = 4;
+        L.chunks = (chunks > 1 && dil % chunks == 0 && pers_gemm) ? chunks : 1;
+        L.vw = (L.chunks > 1 || (o.overlap & TDNET_OVERLAP_LOWREG_TRANSFORMS)) ? (1 << ((o.overlap & TDNET_OVERLAP_VW_MASK) >> TDNET_OVERLAP_VW_SHIFT)) : 0;
         // nb = (m+2)^2 batched [T x Cin] x [Cin x Cout] GEMMs, T = M / m^2 tiles: nb * T rows in total -> pick the tile for that many workgroups
         const int nb = (L.wino + 2) * (L.wino + 2);
-        const bool pers = o.gemm_persistent && gemm_supports(Cin);
-        L.tile = forced_tile >= 0 ? (ConvTile)forced_tile
-               : pers ? gemm_pick_tile(wino_tiles_estimate(M, dil, L.wino) / chunks, nb, Cout, deep)
-                      : conv_pick_tile((int)std::min<long>(nb * M / (L.wino * L.wino), 1 << 30), Cout, deep);
-        L.CoutPad = conv_cout_pad(Cout, L.tile);
+        const long rows = wino_tiles_estimate(M, dil, L.wino) / L.chunks;
+        L.tile = forced ? (ConvTile)forced_tile : pers_gemm ? gemm_pick_tile(rows, nb, Cout, deep)
+                                                            : conv_pick_tile((int)std::min<long>(nb * M / (L.wino * L.wino), 1 << 30), Cout, deep);
         L.nsteps = conv_nsteps(Cin, 1, 0);
-        std::vector<std::vector<float>> U;
-        wino_transform_weights(w.data(), Cout, Cin, L.wino, U);
-        const int b3 = !(o.precision >= 2 && pers && gemm_b3_supports(Cin, Cout)) ? 0
-                     : (forced_tile >= 0 || o.precision == 3) ? 1 : gemm_b3_pick(wino_tiles_estimate(M, dil, L.wino) / chunks, nb, Cout);   // a forced tile (tests, probes): always the split kernel
-        if (b3) {
-            // the 36 GEMMs on the bf16 MFMA, fp32-accurate (td_gemm_b3.h): the Winograd-domain weights as three bf16 parts, split here once
-            L.b3 = b3;
-            L.CoutPad = gemm_b3_npad(Cout);
-            const size_t per = gemm_b3_packed_bytes(Cin, Cout) / 2;
-            std::vector<unsigned short> packed(nb * per);
-            for (int bi = 0; bi < nb; ++bi) gemm_b3_pack(U[bi].data(), Cout, Cin, packed.data() + bi * per);
-            TD_TRY(dev_alloc((unsigned short**)&L.d_wp, packed.size()));
-            TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-        } else {
-        const size_t per = (size_t)L.nsteps * 8 * L.CoutPad * 4;
-        std::vector<float> packed(nb * per);
-        for (int bi = 0; bi < nb; ++bi) conv_pack_weights(U[bi].data(), Cout, Cin, 1, 0, L.tile, packed.data() + bi * per);
-        TD_TRY(dev_alloc(&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        std::vector<float> bb(Cout, 0.f), zz(Cout, 0.f);
-        if (!b.empty()) bb = b;
-        TD_TRY(dev_alloc(&L.d_bias, (size_t)Cout));
-        TD_HIP(hipMemcpy(L.d_bias, bb.data(), Cout * sizeof(float), hipMemcpyHostToDevice));
-        TD_TRY(dev_alloc(&L.d_zero, (size_t)Cout));
-        TD_HIP(hipMemcpy(L.d_zero, zz.data(), Cout * sizeof(float), hipMemcpyHostToDevice));
+        // the 36 GEMMs on the bf16 MFMA, fp32-accurate (td_gemm_b3.h); a forced tile: always the split kernel
+        const bool b3 = split && pers_gemm && gemm_b3_supports(Cin, Cout) && (forced || o.precision == 3 || gemm_b3_pick(rows, nb, Cout));
+        L.gemm = !pers_gemm ? GK_CONV : b3 ? GK_B3 : ((o.overlap & TDNET_OVERLAP_GEMM_DMA) && gemm_dma_supports(Cin, Cout, L.tile)) ? GK_DMA : GK_PERSISTENT;
+        L.CoutPad = b3 ? gemm_b3_npad(Cout) : conv_cout_pad(Cout, L.tile);
         return 0;
     }
-    L.h16 = o.precision == 1 && !stem && Cin % 64 == 0;
+    const bool h16 = o.precision == 1 && !stem && Cin % 64 == 0;
     const bool stem16 = o.precision == 1 && stem && KS == 7 && stride == 2 && Cout <= 64;    // fp16-MFMA stem (td_conv_h.h)
-    bool gemm1x1 = !L.h16 && !stem && KS == 1 && stride == 1 && o.gemm_persistent && gemm_supports(Cin);   // run_conv's persistent-GEMM route
+    const bool is1x1 = !h16 && !stem && KS == 1 && stride == 1 && pers_gemm;                   // a candidate for the persistent-GEMM route
     // precision 2: a stride-1 1x1 conv to <= 128 channels on a large map (a Bottleneck's conv1 in layers 1-2) is too narrow for the split GEMM's 128-column tiles
     // and would stay on the fp32 GEMM: it runs on the split DIRECT kernel instead (td_conv_ad_b3.h with KS = 1: a lane's A row is contiguous)
     // (td2-psp50 769x1537 169.2 -> 170.9 frames/s, td4-psp18 unchanged: profiles/r06ah_*)
-    if (gemm1x1 && forced_tile < 0 && o.precision >= 2 && (o.fusion & 32) && (o.fusion & 524288) && Cout <= 128 && M >= 8192 && gemm_b3_supports(Cin, Cout) &&
-        !gemm_b3_pick(M, 1, Cout, Cin) && conv_adirect_b3_supports(CT_128x64, Cin, KS, stem)) gemm1x1 = false;
-    L.tile = forced_tile >= 0 ? (ConvTile)forced_tile : gemm1x1 ? gemm_pick_tile(M, 1, Cout, deep) : conv_pick_tile((int)M, Cout, deep);
+    const bool narrow1x1 = is1x1 && !forced && split_narrow && Cout <= 128 && M >= 8192 && gemm_b3_supports(Cin, Cout) && !gemm_b3_pick(M, 1, Cout, Cin) &&
+                           conv_adirect_b3_supports(CT_128x64, Cin, KS, stem);
+    const bool gemm1x1 = is1x1 && !narrow1x1;
+    L.tile = forced ? (ConvTile)forced_tile : gemm1x1 ? gemm_pick_tile(M, 1, Cout, deep) : conv_pick_tile((int)M, Cout, deep);
     // precision 2: a direct conv of up to 128 output channels (a strided 3x3 / 1x1 of layer2.0, a deep stem's 64 -> 128 conv) runs as two 64-column tiles of the
     // split direct kernel (td_conv_ad_b3.h; A is loaded once per column tile) instead of the fp32 128-column kernel
     // (td2-psp50 769x1537 164.4 -> 168.0 frames/s, td4-psp18 1024x2048 351.1 -> 352.5, two processes each way on one box: profiles/r06ah_*)
-    if (forced_tile < 0 && o.precision >= 2 && (o.fusion & 32) && (o.fusion & 524288) && !L.h16 && !stem && !gemm1x1 && Cout <= 128 &&
-        conv_adirect_b3_supports(CT_128x64, Cin, KS, stem)) L.tile = CT_128x64;
+    if (!forced && split_narrow && !h16 && !stem && !gemm1x1 && Cout <= 128 && conv_adirect_b3_supports(CT_128x64, Cin, KS, stem)) L.tile = CT_128x64;
     // fp16 mode, ResNet layer1 (64 -> 64, 3x3 stride 1): packed for the 128-wide two-wave-column tile, of which the narrow LDS-DMA kernel
-    // runs the first 64-channel column (finalize_block's dma(); the second column is all padding and is never launched)
-    if (L.h16 && forced_tile < 0 && !stem16 && (o.fusion & 32768) && KS == 3 && stride == 1 && Cout == 64 && Cin % 64 == 0)
-        L.tile = CT_128x128_DEEP;
+    // runs the first 64-channel column (plan_dma_form; the second column is all padding and is never launched)
+    if (h16 && !forced && (o.fusion & TDNET_FUSION_DMA_NARROW) && KS == 3 && stride == 1 && Cout == 64) L.tile = CT_128x128_DEEP;
     L.CoutPad = conv_cout_pad(Cout, L.tile);
+    L.nsteps = conv_nsteps(Cin, KS, stem ? 1 : 0);
     if (stem16 && conv_stem_h_supports(L.tile)) {
-        L.h16 = true;
+        L.route = CR_STEM_H;
         L.nsteps = conv_nsteps_stem_h();
-        std::vector<_Float16> packed((size_t)L.nsteps * 8 * L.CoutPad * 8);
-        conv_pack_weights_stem_h(w.data(), Cout, L.tile, packed.data());
-        TD_TRY(dev_alloc((_Float16**)&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    } else if (L.h16) {
+    } else if (h16) {
+        L.route = CR_CONV_H;
         L.nsteps = conv_nsteps_h(Cin, KS);
-        std::vector<_Float16> packed((size_t)L.nsteps * 8 * L.CoutPad * 8);
-        conv_pack_weights_h(w.data(), Cout, Cin, KS, L.tile, packed.data());
-        TD_TRY(dev_alloc((_Float16**)&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    } else if (o.precision >= 2 && gemm1x1 && gemm_b3_supports(Cin, Cout) && (forced_tile >= 0 || o.precision == 3 || gemm_b3_pick(M, 1, Cout, Cin))) {
+    } else if (gemm1x1) {
         // precision 2: a large stride-1 1x1 conv is one GEMM on the bf16 MFMA with its weights as three bf16 parts (td_gemm_b3.h)
-        L.b3 = 1;
-        L.CoutPad = gemm_b3_npad(Cout);
-        L.nsteps = Cin / 16;
-        std::vector<unsigned short> packed(gemm_b3_packed_bytes(Cin, Cout) / 2);
-        gemm_b3_pack(w.data(), Cout, Cin, packed.data());
-        TD_TRY(dev_alloc((unsigned short**)&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    } else if (o.precision >= 2 && (o.fusion & 32) && (o.fusion & 524288) && !gemm1x1 && conv_adirect_b3_supports(L.tile, Cin, KS, stem)) {
-        // precision 2: the Cout <= 64 convs (ResNet layer1) on the bf16 MFMA, A straight from global memory (td_conv_ad_b3.h)
-        L.b3 = 1;
-        L.nsteps = conv_nsteps(Cin, KS, 0);
-        std::vector<unsigned short> packed(conv_adb3_packed_bytes(Cout, Cin, KS) / 2);
-        conv_pack_weights_adb3(w.data(), Cout, Cin, KS, packed.data());
-        TD_TRY(dev_alloc((unsigned short**)&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    } else {
-        // the 7x7 stem with its A operand straight from global memory can read a packed-row image instead of NHWC4 taps: K = 168 instead of 224
-        L.stem_rows = stem && KS == 7 && stride == 2 && (o.fusion & 65536) && (o.fusion & 32) && conv_adirect_supports(L.tile, 1);
-        const int stem_kind = L.stem_rows ? 2 : stem ? 1 : 0;
-        L.nsteps = conv_nsteps(Cin, KS, stem_kind);
-        if (L.stem_rows && o.precision >= 2 && (o.fusion & 524288)) {   // precision 2: the packed-row stem on the bf16 MFMA (td_conv_ad_b3.h STEM = 2)
-            L.b3 = 1;
-            std::vector<unsigned short> packed(conv_adb3_packed_bytes(Cout, Cin, KS, 2) / 2);
-            conv_pack_weights_adb3(w.data(), Cout, Cin, KS, packed.data(), 2);
-            TD_TRY(dev_alloc((unsigned short**)&L.d_wp, packed.size()));
-            TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-        } else {
-        std::vector<float> packed((size_t)L.nsteps * 8 * L.CoutPad * 4);
-        conv_pack_weights(w.data(), Cout, Cin, KS, stem_kind, L.tile, packed.data());
-        TD_TRY(dev_alloc(&L.d_wp, packed.size()));
-        TD_HIP(hipMemcpy(L.d_wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+        const bool b3 = split && gemm_b3_supports(Cin, Cout) && (forced || o.precision == 3 || gemm_b3_pick(M, 1, Cout, Cin));
+        L.route = CR_GEMM1X1;
+        L.gemm = b3 ? GK_B3 : GK_PERSISTENT;
+        if (b3) { L.CoutPad = gemm_b3_npad(Cout); L.nsteps = Cin / 16; }
+    } else if (split_narrow && conv_adirect_b3_supports(L.tile, Cin, KS, stem)) {
+        L.route = CR_ADIRECT_B3;                                       // precision 2: the Cout <= 64 convs (ResNet layer1) on the bf16 MFMA, A straight from global memory (td_conv_ad_b3.h)
+    } else if ((o.fusion & TDNET_FUSION_A_DIRECT) && conv_adirect_supports(L.tile, 1)) {
+        // the 7x7 stem with its A operand straight from global memory can read a packed-row image instead of NHWC4 taps: K = 168 instead of 224;
+        // precision 2: the packed-row stem on the bf16 MFMA (td_conv_ad_b3.h STEM = 2)
+        const bool rows = stem && KS == 7 && stride == 2 && (o.fusion & TDNET_FUSION_STEM_ROWS);
+        L.route = !rows ? CR_ADIRECT : split_narrow ? CR_ADIRECT_ROWS_B3 : CR_ADIRECT_ROWS;
+        if (rows) L.nsteps = conv_nsteps(Cin, KS, 2);
     }
-    L.adirect = (o.fusion & 32) && !L.h16 && !gemm1x1 && conv_adirect_supports(L.tile, 1);
-    std::vector<float> bb(Cout, 0.f);
-    if (!b.empty()) bb = b;
-    TD_TRY(dev_alloc(&L.d_bias, (size_t)Cout));
-    TD_HIP(hipMemcpy(L.d_bias, bb.data(), Cout * sizeof(float), hipMemcpyHostToDevice));
+    if (L.h16()) { L.in16 = in16; L.out16 = out16; }
+    if (L.route == CR_CONV_H && L.in16) {
+        L.rh = rh == RH_FRAME ? plan_dma_form(L, M, o)
+             : rh == RH_BY_SIZE ? (Cout >= 128 && conv_dma_supports(Cin, Cout, KS, L.tile) ? conv_dma_pick_rh(M, Cout, L.CoutPad % 256 == 0) : CD_NONE) : rh;
+        if (L.rh) L.route = CR_CONV_DMA;
+    }
+    return 0;
+}
+
+// pack `count` elements of T on the host, allocate, copy: the device image of a layer's weights
+template <typename T, typename Pack>
+static int upload_packed(float** d, size_t count, Pack pack) {
+    std::vector<T> packed(count);
+    pack(packed.data());
+    TD_TRY(dev_alloc((T**)d, count));
+    TD_HIP(hipMemcpy(*d, packed.data(), count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+// Packs a BN-folded OIHW weight in the format the planned layer's kernel reads and uploads it with the bias.  Four formats: the fp32 tile image
+// (td_conv.h), the fp16 tile image and its stem variant (td_conv_h.h), three bf16 parts for the split GEMM (td_gemm_b3.h) and for the split direct
+// conv with its packed-row stem variant (td_conv_ad_b3.h); a Winograd layer holds 36 fp32 or split-GEMM images of its transformed weights.
+static int upload_conv(ConvLayer& L, const std::vector<float>& w, const std::vector<float>& b) {
+    typedef unsigned short bf16;
+    const int Cout = L.Cout, Cin = L.Cin, KS = L.KS, stem_kind = L.stem_rows() ? 2 : L.stem ? 1 : 0;
+    const size_t tile_image = (size_t)L.nsteps * 8 * L.CoutPad * 4;    // floats of the fp32 tile image [nsteps][8][CoutPad][4]; the fp16 one is [nsteps][8][CoutPad][8]
+    if (L.route == CR_WINO) {
+        const int nb = (L.wino + 2) * (L.wino + 2);
+        std::vector<std::vector<float>> U;
+        wino_transform_weights(w.data(), Cout, Cin, L.wino, U);
+        const size_t per = L.gemm == GK_B3 ? gemm_b3_packed_bytes(Cin, Cout) / 2 : tile_image;
+        if (L.gemm == GK_B3) TD_TRY(upload_packed<bf16>(&L.d_wp, nb * per, [&](bf16* p) { for (int bi = 0; bi < nb; ++bi) gemm_b3_pack(U[bi].data(), Cout, Cin, p + bi * per); }));
+        else TD_TRY(upload_packed<float>(&L.d_wp, nb * per, [&](float* p) { for (int bi = 0; bi < nb; ++bi) conv_pack_weights(U[bi].data(), Cout, Cin, 1, 0, L.tile, p + bi * per); }));
+    } else if (L.route == CR_STEM_H)
+        TD_TRY(upload_packed<_Float16>(&L.d_wp, 2 * tile_image, [&](_Float16* p) { conv_pack_weights_stem_h(w.data(), Cout, L.tile, p); }));
+    else if (L.h16())
+        TD_TRY(upload_packed<_Float16>(&L.d_wp, 2 * tile_image, [&](_Float16* p) { conv_pack_weights_h(w.data(), Cout, Cin, KS, L.tile, p); }));
+    else if (L.route == CR_GEMM1X1 && L.gemm == GK_B3)
+        TD_TRY(upload_packed<bf16>(&L.d_wp, gemm_b3_packed_bytes(Cin, Cout) / 2, [&](bf16* p) { gemm_b3_pack(w.data(), Cout, Cin, p); }));
+    else if (L.route == CR_ADIRECT_B3 || L.route == CR_ADIRECT_ROWS_B3)
+        TD_TRY(upload_packed<bf16>(&L.d_wp, conv_adb3_packed_bytes(Cout, Cin, KS, stem_kind) / 2, [&](bf16* p) { conv_pack_weights_adb3(w.data(), Cout, Cin, KS, p, stem_kind); }));
+    else
+        TD_TRY(upload_packed<float>(&L.d_wp, tile_image, [&](float* p) { conv_pack_weights(w.data(), Cout, Cin, KS, stem_kind, L.tile, p); }));
+    TD_TRY(upload(&L.d_bias, b.empty() ? std::vector<float>(Cout, 0.f) : b));
+    if (L.wino) TD_TRY(upload(&L.d_zero, std::vector<float>(Cout, 0.f)));
     return 0;
 }
 static void free_conv_layer(ConvLayer& L) {
@@ -258,12 +274,12 @@ static bool conv_chainable(int cin, int cout, int stride, int dil) {
 static void plan_chains(tdnet* n) {
     n->seg_block = -1; n->seg_conv = 0;
     const tdnet_opts& o = n->opts;
-    if (!(o.overlap & 1) || o.winograd < 3 || o.precision == 1 || !o.gemm_persistent || n->deep) return;
+    if (!(o.overlap & TDNET_OVERLAP_CHAINS) || o.winograd < 3 || o.precision == 1 || !o.gemm_persistent || n->deep) return;
     // The chains pay on LARGE maps only: td4-psp18, frames/s with / without them (profiles/r05g_*): 512x1024 (8192 feature pixels) 805 / 822,
     // 640x1280 (12800) 565 / 575, 769x1537 (18721) 384.5 / 391.9, 896x1792 (25088) 324.1 / 321.7, 1024x2048 (32768) 273.8 / 269.1 -- two
     // half-size GEMMs fill the chip less well than one, and below ~23 k pixels that costs more than the hidden transforms return.
     // overlap bit 4 forces them at any size (tests, A/B).
-    if (n->Lq < TD_CHAIN_MIN_PIXELS && !(o.overlap & 4)) return;
+    if (n->Lq < TD_CHAIN_MIN_PIXELS && !(o.overlap & TDNET_OVERLAP_CHAINS_ANY_SIZE)) return;
     int sb = -1, sc = 0;
     for (int b = (int)n->bspec.size() - 1; b >= 0; --b) {
         const BlockSpec& S = n->bspec[b];
@@ -294,7 +310,7 @@ static int alloc_workspace(tdnet* n) {
         }
     }
     {   // the stem's input image: NHWC4, or the packed-row image with its zero border (written once, here)
-        const bool rows = !n->paths.empty() && n->paths[0].stem.stem_rows;
+        const bool rows = !n->paths.empty() && n->paths[0].stem.stem_rows();
         const size_t img_floats = std::max((size_t)n->H * n->W * 4, rows ? (size_t)stem_rows_hp(n->H) * stem_rows_wp(n->W) * 3 + 4 : (size_t)0);
         if (dev_alloc(&n->img4, img_floats)) return -1;
         if (rows) TD_HIP(hipMemset(n->img4, 0, img_floats * sizeof(float)));
@@ -354,8 +370,119 @@ static int alloc_workspace(tdnet* n) {
 }
 static double frame_flops(const tdnet* n);
 
-// Builds the weight block from the host state_dict: strict inventory check, BN folding, packing, upload.  Called once per block, under
-// the handle that owns the state_dict; handles created with tdnet_create_shared find the block finished.
+// One walk over the layers of every path.  up = false: the layers are PLANNED (plan_conv) -- nothing is folded, allocated or copied; up = true: planned
+// again, with the chain plan and act16 as finalize_block settled them on the first walk, and folded, packed and uploaded.
+static int build_paths(tdnet* n, bool up) {
+    const int C = n->C, DV = n->DV, FS = C / (2 * 4);
+    char b[160];
+    // precision = 1: every map between two convs of the backbone is stored as fp16 (half the conv input / output bytes; td_conv_h.h).
+    // The rim: the 7x7 stem runs on the fp16 MFMA from the fp32 image and writes an fp16 map (the 3x3 deep stem's first conv stays an
+    // fp32 kernel with an fp32 map), and c4 -- the LAST conv of the backbone -- writes fp32 for the pyramid, Encoding and head
+    // kernels, which keep fp32 storage.
+    const bool a16 = n->act16;
+    auto conv = [&](ConvLayer& L, const std::string& wkey, const std::string& bkey, const std::string& bn, int Cout, int Cin, int KS, int stride, int dil,
+                    int act, bool stem, long M, int tile = -1, int chunks = 1, bool in16 = false, bool out16 = false) -> int {
+        TD_TRY(plan_conv(L, Cout, Cin, KS, stride, dil, act, stem, M, n->opts, tile, chunks, in16, out16));
+        if (!up) return 0;
+        const Folded f = fold(n, wkey, bkey, bn, Cout);
+        return upload_conv(L, f.w, f.b);
+    };
+    n->paths.clear();
+    n->paths.resize(n->P);
+    for (int p = 0; p < n->P; ++p) {
+        PathLayers& L = n->paths[p];
+        L.pid = p & 1;                                                 // td4_psp18.py:80-83 / td2_psp50.py:76-77
+        snprintf(b, sizeof(b), "pretrained%d", p + 1);
+        const std::string pre = n->cfg.model == 1 ? std::string("pretrained") : std::string(b);
+        const long M1 = (long)n->H1 * n->W1;
+        if (n->deep) {                                                 // conv3x3 s2 3->64, conv3x3 64->64, conv3x3 64->128 (+bn1)
+            TD_TRY(conv(L.stem, pre + ".conv1.0.weight", "", pre + ".conv1.1", 64, 3, 3, 2, 1, 1, true, M1));
+            TD_TRY(conv(L.stem2, pre + ".conv1.3.weight", "", pre + ".conv1.4", 64, 64, 3, 1, 1, 1, false, M1, -1, 1, false, a16));
+            TD_TRY(conv(L.stem3, pre + ".conv1.6.weight", "", pre + ".bn1", 128, 64, 3, 1, 1, 1, false, M1, -1, 1, a16, a16));
+        } else                                                         // the fp16-MFMA 7x7 stem: its map is fp16 too (max-pool reads fp16)
+            TD_TRY(conv(L.stem, pre + ".conv1.weight", "", pre + ".bn1", 64, 3, 7, 2, 1, 1, true, M1, -1, 1, false, a16));
+        int ch = n->H2, cw = n->W2;
+        for (size_t bsi = 0; bsi < n->bspec.size(); ++bsi) {
+            const BlockSpec& s = n->bspec[bsi];
+            const int k1 = in_chain(n, (int)bsi, 0) ? 2 : 1, k2 = in_chain(n, (int)bsi, 1) ? 2 : 1;   // row-parity chunks of conv1 / conv2
+            const bool o16 = a16 && bsi + 1 < n->bspec.size();          // the last conv of the backbone writes fp32
+            BlockLayers B;
+            const std::string bp = pre + "." + s.name;
+            const int oh = out_size(ch, 3, s.stride, s.dil1, s.dil1), ow = out_size(cw, 3, s.stride, s.dil1, s.dil1);
+            const long M = (long)oh * ow;
+            B.bott = s.bott;
+            if (s.bott) {
+                TD_TRY(conv(B.c1, bp + ".conv1.weight", "", bp + ".bn1", s.planes, s.cin, 1, 1, 1, 1, false, (long)ch * cw, -1, 1, a16, a16));
+                TD_TRY(conv(B.c2, bp + ".conv2.weight", "", bp + ".bn2", s.planes, s.planes, 3, s.stride, s.dil1, 1, false, M, -1, 1, a16, a16));
+                TD_TRY(conv(B.c3, bp + ".conv3.weight", "", bp + ".bn3", s.cout, s.planes, 1, 1, 1, 1, false, M, -1, 1, a16, o16));   // ReLU after the residual add
+            } else {
+                TD_TRY(conv(B.c1, bp + ".conv1.weight", "", bp + ".bn1", s.cout, s.cin, 3, s.stride, s.dil1, 1, false, M, -1, k1, a16, a16));
+                TD_TRY(conv(B.c2, bp + ".conv2.weight", "", bp + ".bn2", s.cout, s.cout, 3, 1, s.dil2, 1, false, M, -1, k2, a16, o16));
+            }
+            B.has_ds = s.ds;
+            if (s.ds) TD_TRY(conv(B.ds, bp + ".downsample.0.weight", "", bp + ".downsample.1", s.cout, s.cin, 1, s.stride, 1, 0, false, M, -1, 1, a16, a16));
+            L.blocks.push_back(B);
+            ch = oh; cw = ow;
+        }
+        if (ch != n->h || cw != n->w) return td_fail("internal: feature size mismatch %dx%d vs %dx%d", ch, cw, n->h, n->w);
+        if (n->cfg.model == 1) {                                       // PSPHead (pspnet.py:102-115): full pyramid, conv3x3, classifier
+            const int F4 = C / 4;
+            std::vector<float> pw((size_t)4 * F4 * C), pb((size_t)4 * F4);
+            for (int j = 0; up && j < 4; ++j) {
+                snprintf(b, sizeof(b), "head.conv5.0.conv%d", j + 1);
+                Folded f = fold(n, std::string(b) + ".0.weight", "", std::string(b) + ".1", F4);
+                for (int o = 0; o < F4; ++o) {
+                    for (int c = 0; c < C; ++c) pw[((size_t)j * C + c) * F4 + o] = f.w[(size_t)o * C + c];
+                    pb[j * F4 + o] = f.b[o];
+                }
+            }
+            if (up && (upload(&L.d_ppm_w, pw) || upload(&L.d_ppm_b, pb))) return -1;
+            TD_TRY(conv(L.head3, "head.conv5.1.weight", "", "head.conv5.2", n->MID, 2 * C, 3, 1, 1, 1, false, n->Lq));
+            if (up && (upload(&L.d_cls_w, T(n, "head.conv5.5.weight")) || upload(&L.d_cls_b, T(n, "head.conv5.5.bias")))) return -1;
+            continue;
+        }
+        // pyramid convs: keep only the FS output channels this path's slice uses (td4_psp18.py:279-282)
+        std::vector<float> pw((size_t)4 * FS * C), pb((size_t)4 * FS);
+        for (int j = 0; up && j < 4; ++j) {
+            snprintf(b, sizeof(b), "psp%d.conv%d", p + 1, j + 1);
+            Folded f = fold(n, std::string(b) + ".0.weight", "", std::string(b) + ".1", C / 4);
+            for (int o = 0; o < FS; ++o) {
+                for (int c = 0; c < C; ++c) pw[((size_t)j * C + c) * FS + o] = f.w[(size_t)(L.pid * FS + o) * C + c];   // [lvl][c][f]
+                pb[j * FS + o] = f.b[L.pid * FS + o];
+            }
+        }
+        if (up && (upload(&L.d_ppm_w, pw) || upload(&L.d_ppm_b, pb))) return -1;
+        snprintf(b, sizeof(b), "enc%d", p + 1);
+        const std::string ep = b;
+        // fp16 mode with grouped launches: the value conv on the 64-channel tile of the query / key convs it shares a launch with
+        const int vtile = (n->opts.precision == 1 && (n->opts.fusion & TDNET_FUSION_CONV_GROUPS)) ? (int)conv_pick_tile((int)n->Lq, 64, n->opts.pipeline != 0) : -1;
+        TD_TRY(conv(L.enc_v, ep + ".w_vs.0.conv.weight", ep + ".w_vs.0.conv.bias", "", DV, C, 1, 1, 1, 0, false, n->Lq, vtile));
+        TD_TRY(conv(L.enc_q0, ep + ".w_qs.0.conv.weight", ep + ".w_qs.0.conv.bias", ep + ".w_qs.0.bn", 64, C, 1, 1, 1, 2, false, n->Lq));
+        TD_TRY(conv(L.enc_q1, ep + ".w_qs.1.conv.weight", ep + ".w_qs.1.conv.bias", "", 64, 64, 1, 1, 1, 0, false, n->Lq));
+        TD_TRY(conv(L.enc_k0, ep + ".w_ks.0.conv.weight", ep + ".w_ks.0.conv.bias", ep + ".w_ks.0.bn", 64, C, 1, 4, 1, 2, false, n->Lk));   // stride 4 = the key sub-sampling
+        TD_TRY(conv(L.enc_k1, ep + ".w_ks.1.conv.weight", ep + ".w_ks.1.conv.bias", "", 64, 64, 1, 1, 1, 0, false, n->Lk));
+        for (auto& an : atn_order(n->cfg.model, p)) {
+            AtnLayer A;
+            TD_TRY(conv(A.fc, an + ".fc.0.conv.weight", "", "", DV, DV, 1, 1, 1, 0, false, n->Lk));   // the bias is added after P V'
+            if (up && upload(&A.d_bias, T(n, an + ".fc.0.conv.bias"))) return -1;
+            L.atn.push_back(A);
+        }
+        snprintf(b, sizeof(b), "layer_norm%d.ln", p + 1);
+        if (up && (upload(&L.d_ln_g, T(n, std::string(b) + ".weight")) || upload(&L.d_ln_b, T(n, std::string(b) + ".bias")))) return -1;
+        snprintf(b, sizeof(b), "head%d.conv5", p + 1);
+        const std::string hp = b;
+        // The head's 3x3 conv (d_v -> d_v / 4 channels; >= 128 for td4): where it can run on the LDS-DMA kernel, LayerNorm writes its map as fp16 -- the
+        // rounding the conv applied to the fp32 map while staging it (1024x2048: 77 -> 46 us); otherwise it keeps reading the fp32 map.
+        ConvLayer h16in;
+        const bool head16 = a16 && plan_conv(h16in, n->MID, DV, 3, 1, 1, 1, false, n->Lq, n->opts, -1, 1, true) == 0 && h16in.route == CR_CONV_DMA;
+        TD_TRY(conv(L.head3, hp + ".0.weight", "", hp + ".1", n->MID, DV, 3, 1, 1, 1, false, n->Lq, -1, 1, head16));
+        if (up && (upload(&L.d_cls_w, T(n, hp + ".4.weight")) || upload(&L.d_cls_b, T(n, hp + ".4.bias")))) return -1;
+    }
+    return 0;
+}
+
+// Builds the weight block from the host state_dict: strict inventory check, then every layer is planned, and only then BN folding, packing, upload.
+// Called once per block, under the handle that owns the state_dict; handles created with tdnet_create_shared find the block finished.
 static int finalize_block(tdnet* n) {
     AllocScope count_(&n->wt->device_bytes);
     for (auto& kv : n->expected) {
@@ -364,191 +491,26 @@ static int finalize_block(tdnet* n) {
         if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) continue;
         if (!n->sd.count(k)) return td_fail("Missing key in state_dict: \"%s\"", k.c_str());
     }
-    const int C = n->C, DV = n->DV, FS = C / (2 * 4), NC = n->cfg.nclass;
     plan_chains(n);
-    char b[160];
-    // The row-parity plan (plan_chains / conv_chainable) and the per-layer decision (make_conv_layer: Winograd F(4x4) + chunkable) are two
-    // predicates over the same facts.  Should they ever disagree, the chains are a schedule, not a requirement: the layers are rebuilt
-    // unchained (attempt 1) instead of failing the load.
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    bool plan_mismatch = false;
-    n->wt->device_bytes = 0;
-    for (auto& pl : n->paths) free_path(pl);
-    n->paths.clear();
-    n->paths.resize(n->P);
-    for (int p = 0; p < n->P && !plan_mismatch; ++p) {
-        PathLayers& L = n->paths[p];
-        L.pid = p & 1;                                                 // td4_psp18.py:80-83 / td2_psp50.py:76-77
-        snprintf(b, sizeof(b), "pretrained%d", p + 1);
-        const std::string pre = n->cfg.model == 1 ? std::string("pretrained") : std::string(b);
-        if (n->deep) {                                                 // conv3x3 s2 3->64, conv3x3 64->64, conv3x3 64->128 (+bn1)
-            Folded f0 = fold(n, pre + ".conv1.0.weight", "", pre + ".conv1.1", 64);
-            if (make_conv_layer(L.stem, f0.w, f0.b, 64, 3, 3, 2, 1, 1, true, (long)n->H1 * n->W1, n->opts)) return -1;
-            Folded f1 = fold(n, pre + ".conv1.3.weight", "", pre + ".conv1.4", 64);
-            if (make_conv_layer(L.stem2, f1.w, f1.b, 64, 64, 3, 1, 1, 1, false, (long)n->H1 * n->W1, n->opts)) return -1;
-            Folded f2 = fold(n, pre + ".conv1.6.weight", "", pre + ".bn1", 128);
-            if (make_conv_layer(L.stem3, f2.w, f2.b, 128, 64, 3, 1, 1, 1, false, (long)n->H1 * n->W1, n->opts)) return -1;
-        } else {
-            Folded f = fold(n, pre + ".conv1.weight", "", pre + ".bn1", 64);
-            if (make_conv_layer(L.stem, f.w, f.b, 64, 3, 7, 2, 1, 1, true, (long)n->H1 * n->W1, n->opts)) return -1;
+    n->act16 = false;
+    TD_TRY(build_paths(n, false));
+    // The row-parity plan (plan_chains / conv_chainable) and the per-layer decision (plan_conv: Winograd F(4x4) + chunkable) are two predicates over
+    // the same facts.  Should they ever disagree, the chains are a schedule, not a requirement: the layers run unchained instead of failing the load.
+    for (auto& L : n->paths)
+        for (size_t bi = 0; bi < L.blocks.size(); ++bi) {
+            const BlockLayers& B = L.blocks[bi];
+            if ((in_chain(n, (int)bi, 0) && B.c1.chunks != 2) || (in_chain(n, (int)bi, 1) && B.c2.chunks != 2)) { n->seg_block = -1; n->seg_conv = 0; }
         }
-        int ch = n->H2, cw = n->W2;
-        for (size_t bsi = 0; bsi < n->bspec.size(); ++bsi) {
-            const BlockSpec& s = n->bspec[bsi];
-            const int k1 = in_chain(n, (int)bsi, 0) ? 2 : 1, k2 = in_chain(n, (int)bsi, 1) ? 2 : 1;   // row-parity chunks of conv1 / conv2
-            BlockLayers B;
-            const std::string bp = pre + "." + s.name;
-            const int oh = out_size(ch, 3, s.stride, s.dil1, s.dil1), ow = out_size(cw, 3, s.stride, s.dil1, s.dil1);
-            const long M = (long)oh * ow;
-            B.bott = s.bott;
-            if (s.bott) {
-                Folded f1 = fold(n, bp + ".conv1.weight", "", bp + ".bn1", s.planes);
-                if (make_conv_layer(B.c1, f1.w, f1.b, s.planes, s.cin, 1, 1, 1, 1, false, (long)ch * cw, n->opts)) return -1;
-                Folded f2 = fold(n, bp + ".conv2.weight", "", bp + ".bn2", s.planes);
-                if (make_conv_layer(B.c2, f2.w, f2.b, s.planes, s.planes, 3, s.stride, s.dil1, 1, false, M, n->opts)) return -1;
-                Folded f3 = fold(n, bp + ".conv3.weight", "", bp + ".bn3", s.cout);
-                if (make_conv_layer(B.c3, f3.w, f3.b, s.cout, s.planes, 1, 1, 1, 1, false, M, n->opts)) return -1;   // ReLU after the residual add
-            } else {
-                Folded f1 = fold(n, bp + ".conv1.weight", "", bp + ".bn1", s.cout);
-                if (make_conv_layer(B.c1, f1.w, f1.b, s.cout, s.cin, 3, s.stride, s.dil1, 1, false, M, n->opts, -1, k1)) return -1;
-                Folded f2 = fold(n, bp + ".conv2.weight", "", bp + ".bn2", s.cout);
-                if (make_conv_layer(B.c2, f2.w, f2.b, s.cout, s.cout, 3, 1, s.dil2, 1, false, M, n->opts, -1, k2)) return -1;
-                if ((k1 > 1 && B.c1.chunks != k1) || (k2 > 1 && B.c2.chunks != k2)) plan_mismatch = true;
-            }
-            B.has_ds = s.ds;
-            if (s.ds) {
-                Folded fd = fold(n, bp + ".downsample.0.weight", "", bp + ".downsample.1", s.cout);
-                if (make_conv_layer(B.ds, fd.w, fd.b, s.cout, s.cin, 1, s.stride, 1, 0, false, M, n->opts)) return -1;
-            }
-            L.blocks.push_back(B);
-            ch = oh; cw = ow;
-            if (plan_mismatch) break;
-        }
-        if (plan_mismatch) break;
-        if (ch != n->h || cw != n->w) return td_fail("internal: feature size mismatch %dx%d vs %dx%d", ch, cw, n->h, n->w);
-        if (n->cfg.model == 1) {                                       // PSPHead (pspnet.py:102-115): full pyramid, conv3x3, classifier
-            const int F4 = C / 4;
-            std::vector<float> pw((size_t)4 * F4 * C), pb((size_t)4 * F4);
-            for (int j = 0; j < 4; ++j) {
-                snprintf(b, sizeof(b), "head.conv5.0.conv%d", j + 1);
-                Folded f = fold(n, std::string(b) + ".0.weight", "", std::string(b) + ".1", F4);
-                for (int o = 0; o < F4; ++o) {
-                    for (int c = 0; c < C; ++c) pw[((size_t)j * C + c) * F4 + o] = f.w[(size_t)o * C + c];
-                    pb[j * F4 + o] = f.b[o];
-                }
-            }
-            if (upload(&L.d_ppm_w, pw) || upload(&L.d_ppm_b, pb)) return -1;
-            Folded fh = fold(n, "head.conv5.1.weight", "", "head.conv5.2", n->MID);
-            if (make_conv_layer(L.head3, fh.w, fh.b, n->MID, 2 * C, 3, 1, 1, 1, false, n->Lq, n->opts)) return -1;
-            if (upload(&L.d_cls_w, T(n, "head.conv5.5.weight")) || upload(&L.d_cls_b, T(n, "head.conv5.5.bias"))) return -1;
-            continue;
-        }
-        // pyramid convs: keep only the FS output channels this path's slice uses (td4_psp18.py:279-282)
-        std::vector<float> pw((size_t)4 * FS * C), pb((size_t)4 * FS);
-        for (int j = 0; j < 4; ++j) {
-            snprintf(b, sizeof(b), "psp%d.conv%d", p + 1, j + 1);
-            Folded f = fold(n, std::string(b) + ".0.weight", "", std::string(b) + ".1", C / 4);
-            for (int o = 0; o < FS; ++o) {
-                for (int c = 0; c < C; ++c) pw[((size_t)j * C + c) * FS + o] = f.w[(size_t)(L.pid * FS + o) * C + c];   // [lvl][c][f]
-                pb[j * FS + o] = f.b[L.pid * FS + o];
-            }
-        }
-        if (upload(&L.d_ppm_w, pw) || upload(&L.d_ppm_b, pb)) return -1;
-        snprintf(b, sizeof(b), "enc%d", p + 1);
-        const std::string ep = b;
-        {
-            Folded fv = fold(n, ep + ".w_vs.0.conv.weight", ep + ".w_vs.0.conv.bias", "", DV);
-            // fp16 mode with grouped launches: the value conv on the 64-channel tile of the query / key convs it shares a launch with
-            const int vtile = (n->opts.precision == 1 && (n->opts.fusion & 131072)) ? (int)conv_pick_tile((int)n->Lq, 64, n->opts.pipeline != 0) : -1;
-            if (make_conv_layer(L.enc_v, fv.w, fv.b, DV, C, 1, 1, 1, 0, false, n->Lq, n->opts, vtile)) return -1;
-            Folded q0 = fold(n, ep + ".w_qs.0.conv.weight", ep + ".w_qs.0.conv.bias", ep + ".w_qs.0.bn", 64);
-            if (make_conv_layer(L.enc_q0, q0.w, q0.b, 64, C, 1, 1, 1, 2, false, n->Lq, n->opts)) return -1;
-            Folded q1 = fold(n, ep + ".w_qs.1.conv.weight", ep + ".w_qs.1.conv.bias", "", 64);
-            if (make_conv_layer(L.enc_q1, q1.w, q1.b, 64, 64, 1, 1, 1, 0, false, n->Lq, n->opts)) return -1;
-            Folded k0 = fold(n, ep + ".w_ks.0.conv.weight", ep + ".w_ks.0.conv.bias", ep + ".w_ks.0.bn", 64);
-            if (make_conv_layer(L.enc_k0, k0.w, k0.b, 64, C, 1, 4, 1, 2, false, n->Lk, n->opts)) return -1;   // stride 4 = the key sub-sampling
-            Folded k1 = fold(n, ep + ".w_ks.1.conv.weight", ep + ".w_ks.1.conv.bias", "", 64);
-            if (make_conv_layer(L.enc_k1, k1.w, k1.b, 64, 64, 1, 1, 1, 0, false, n->Lk, n->opts)) return -1;
-        }
-        for (auto& an : atn_order(n->cfg.model, p)) {
-            AtnLayer A;
-            std::vector<float> nob;
-            if (make_conv_layer(A.fc, T(n, an + ".fc.0.conv.weight"), nob, DV, DV, 1, 1, 1, 0, false, n->Lk, n->opts)) return -1;
-            if (upload(&A.d_bias, T(n, an + ".fc.0.conv.bias"))) return -1;
-            L.atn.push_back(A);
-        }
-        snprintf(b, sizeof(b), "layer_norm%d.ln", p + 1);
-        if (upload(&L.d_ln_g, T(n, std::string(b) + ".weight")) || upload(&L.d_ln_b, T(n, std::string(b) + ".bias"))) return -1;
-        snprintf(b, sizeof(b), "head%d.conv5", p + 1);
-        const std::string hp = b;
-        Folded fh = fold(n, hp + ".0.weight", "", hp + ".1", n->MID);
-        if (make_conv_layer(L.head3, fh.w, fh.b, n->MID, DV, 3, 1, 1, 1, false, n->Lq, n->opts)) return -1;
-        if (upload(&L.d_cls_w, T(n, hp + ".4.weight")) || upload(&L.d_cls_b, T(n, hp + ".4.bias"))) return -1;
-        (void)NC;
-    }
-    if (plan_mismatch) {
-        if (attempt == 1) return td_fail("internal: conv layers ask for row-parity chunks without a chain plan");
-        n->seg_block = -1; n->seg_conv = 0;                             // rebuild every layer with chunks = 1
-        continue;
-    }
-    // precision = 1: every map between two convs of the backbone is stored as fp16 (half the conv input / output bytes; td_conv_h.h).
-    // The rim: the 7x7 stem runs on the fp16 MFMA from the fp32 image and writes an fp16 map (the 3x3 deep stem's first conv stays an
-    // fp32 kernel with an fp32 map), and c4 -- the LAST conv of the backbone -- writes fp32 for the pyramid, Encoding and head
-    // kernels, which keep fp32 storage.
+    // fp16 maps between the backbone's convs (build_paths): only when every one of them runs on the fp16 MFMA and the last block has no downsample
     n->act16 = n->opts.precision == 1;
-    if (n->act16)
-        for (auto& L : n->paths) {
-            bool all16 = true;
-            for (auto& B : L.blocks) all16 = all16 && B.c1.h16 && B.c2.h16 && (!B.bott || B.c3.h16) && (!B.has_ds || B.ds.h16);
-            if (n->deep) all16 = all16 && L.stem2.h16 && L.stem3.h16;
-            all16 = all16 && !L.blocks.empty() && !L.blocks.back().has_ds;
-            if (!all16) { n->act16 = false; break; }
-        }
-    if (n->act16)
-        for (auto& L : n->paths) {
-            if (n->deep) { L.stem2.out16 = true; L.stem3.in16 = L.stem3.out16 = true; }
-            else if (L.stem.h16) L.stem.out16 = true;                  // fp16-MFMA 7x7 stem: its map is fp16 too (max-pool reads fp16)
-            for (size_t bi = 0; bi < L.blocks.size(); ++bi) {
-                BlockLayers& B = L.blocks[bi];
-                const bool last = bi + 1 == L.blocks.size();
-                B.c1.in16 = B.c1.out16 = true;
-                B.c2.in16 = true;
-                if (B.bott) { B.c2.out16 = true; B.c3.in16 = true; B.c3.out16 = !last; }
-                else B.c2.out16 = !last;
-                if (B.has_ds) B.ds.in16 = B.ds.out16 = true;
-            }
-            // fp16 maps in, Cout >= 128: the LDS-DMA kernel (td_conv_hd.h)
-            auto dma = [&](ConvLayer& c) {
-                if (!c.h16 || !c.in16 || c.stem) return;
-                // ResNet layer1 (64 -> 64 channels, 3x3): one narrow tile column of the 128-wide packing (make_conv_layer packed it that way).  Isolated
-                // 11.9 -> 9.8 us at 180x240, 22.0 -> 18.5 us at 256x512 against k_conv_igemm_h<128,64,..>, bit-identical (profiles/r04z_fp16_layer1_*; shipped in round 5)
-                if (c.Cout == 64 && c.CoutPad == 128 && c.KS == 3 && c.stride == 1 && c.pad == c.dil && (n->opts.fusion & 32768) && conv_dma_supports(c.Cin, c.Cout, c.KS, c.tile)) {
-                    c.rh = CD_128_N;
-                    return;
-                }
-                if (c.Cout >= 128 && conv_dma_supports(c.Cin, c.Cout, c.KS, c.tile)) {
-                    c.rh = conv_dma_pick_rh(c.M_out, c.Cout, c.CoutPad % 256 == 0);
-                    // Small maps (720x960: 10800 output pixels): a 3x3 "same" conv with <= 256 output channels on NARROW tiles (rows x 64
-                    // channels, k_conv_dma_h3n) -- half the weight bytes per K step and CU, the term that dominates there: 128 channels
-                    // 13.8 -> 10.3 us, 256 channels 20.6 -> 19.8 us isolated (profiles/r04u_*).  No gain at 32768 pixels.
-                    const bool same3 = c.KS == 3 && c.stride == 1 && c.pad == c.dil;
-                    if ((n->opts.fusion & 32768) && same3 && c.M_out <= 16384 && c.Cout <= 256)
-                        c.rh = c.Cout <= 128 ? CD_128_N : CD_192_N;       // (256 channels on 128 x 64 tiles as well: 2.1 % instead of 2.6 % in the frame;
-                                                                          //  512 channels, 64- and 96-row tiles: slower, profiles/r05c_*)
-                    else if (n->opts.fusion & 8192)                     // the 128- and 192-row tiles with four dedicated loader waves (k_conv_dma_h3p):
-                        c.rh = c.rh == CD_128 ? CD_128_P : c.rh == CD_192 ? CD_192_P : c.rh;
-                        // isolated 22.5 -> 21.0 / 57.8 -> 56.7 us; 256 rows: no gain (profiles/r04d_*).  (192 rows with TWELVE matrix waves of 32 x 64 -- three
-                        // per SIMD instead of two SIMDs with twice the MFMAs -- is 3-5 % faster alone and 0.6 % SLOWER in the frame: profiles/r04z_*.)
-                }
-            };
-            if (n->deep) dma(L.stem3);
-            for (auto& B : L.blocks) { dma(B.c1); dma(B.c2); if (B.bott) dma(B.c3); if (B.has_ds) dma(B.ds); }
-            // The head's 3x3 conv (d_v -> d_v / 4 channels; >= 128 for td4): LayerNorm writes its map as fp16 -- the rounding the conv
-            // applied to the fp32 map while staging it -- and the conv runs on the LDS-DMA kernel (1024x2048: 77 -> 46 us).
-            if (n->cfg.model != 1 && L.head3.h16 && !L.head3.wino) { L.head3.in16 = true; dma(L.head3); if (!L.head3.rh) L.head3.in16 = false; }
-        }
-    break;
+    for (auto& L : n->paths) {
+        bool all16 = !L.blocks.empty() && !L.blocks.back().has_ds;
+        for (auto& B : L.blocks) all16 = all16 && B.c1.h16() && B.c2.h16() && (!B.bott || B.c3.h16()) && (!B.has_ds || B.ds.h16());
+        if (n->deep) all16 = all16 && L.stem2.h16() && L.stem3.h16();
+        n->act16 = n->act16 && all16;
     }
+    n->wt->device_bytes = 0;
+    TD_TRY(build_paths(n, true));
     n->sd.clear();
     n->finalized = true;
     n->flops_frame = frame_flops(n);
