@@ -48,8 +48,10 @@ struct LnFuse { const float *mean, *rstd, *g, *b; };
 struct WinoChunk { int ny = 1, cy = 0, nx = 1, cx = 0; };
 
 template <int VW>
-static void launch_wino4_c(bool out_side, const WinoArgs& wa, hipStream_t s) {
-    if (out_side) TD_LAUNCH((k_wino4_out_c<VW>), dim3(wino_chunk_grid(wa.Tc, wa.Cout, VW)), dim3(256), 0, s, wa);
+static void launch_wino4_c(bool out_side, WinoArgs wa, hipStream_t s) {
+    wa.mg_sl = wino_magic(((out_side ? wa.Cout : wa.C) + 64 * VW - 1) / (64 * VW));
+    if (out_side && wino_act_general(wa.act)) TD_LAUNCH((k_wino4_out_c<VW, true>), dim3(wino_chunk_grid(wa.Tc, wa.Cout, VW)), dim3(256), 0, s, wa);
+    else if (out_side) TD_LAUNCH((k_wino4_out_c<VW, false>), dim3(wino_chunk_grid(wa.Tc, wa.Cout, VW)), dim3(256), 0, s, wa);
     else TD_LAUNCH((k_wino4_in_c<VW>), dim3(wino_chunk_grid(wa.Tc, wa.C, VW)), dim3(256), 0, s, wa);
 }
 
@@ -101,6 +103,12 @@ static int run_wino(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
     wa.H = H; wa.W = W; wa.C = L.Cin; wa.Cout = L.Cout; wa.dil = L.dil; wa.TY = TY; wa.TX = TX; wa.T = (int)T; wa.act = L.act; wa.TP = (int)Tc;
     wa.ln_mean = lnf ? lnf->mean : nullptr; wa.ln_rstd = lnf ? lnf->rstd : nullptr; wa.ln_g = lnf ? lnf->g : nullptr; wa.ln_b = lnf ? lnf->b : nullptr;
     wa.Tc = (int)Tc; wa.ny = ck.ny; wa.cy = ck.cy; wa.nx = ck.nx; wa.cx = ck.cx;
+    // the transforms address with 32-bit byte offsets below TD_BUF_OOB, and the wave-per-tile ones decode a tile with wino_magic() reciprocals
+    const long cmax = L.Cin > L.Cout ? L.Cin : L.Cout;
+    if ((long)nb * Tc * cmax * 4 >= (1l << 31) || (long)H * W * cmax * 4 >= (1l << 31) ||
+        (L.vw && !(wino_magic_ok(Tc * ((cmax + 63) / 64), TX) && wino_magic_ok(0, TY) && wino_magic_ok(0, L.dil))))
+        return td_fail("internal: this conv is too large for the Winograd transforms");
+    wa.mg_sl = wino_magic(1); wa.mg_tx = wino_magic(TX); wa.mg_ty = wino_magic(TY); wa.pw = L.dil / ck.nx; wa.mg_pw = wino_magic(wa.pw);
     auto transform = [&](bool out_side) {
         if (n && (probe_skip() & 1)) return;
         prof_begin(n, 2, false, 0, s);
@@ -114,7 +122,8 @@ static int run_wino(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
         else if (L.vw == 2 && C % 2 == 0) launch_wino4_c<2>(out_side, wa, s);
         else if (L.vw == 4 && C % 4 == 0) launch_wino4_c<4>(out_side, wa, s);
         else if (L.vw) launch_wino4_c<1>(out_side, wa, s);
-        else if (out_side) TD_LAUNCH(k_wino4_out, dim3(td_grid_for(T * (L.Cout / 4), 256, 256 * 16)), dim3(256), 0, s, wa);
+        else if (out_side && wino_act_general(wa.act)) TD_LAUNCH((k_wino4_out<true>), dim3(td_grid_for(T * (L.Cout / 4), 256, 256 * 16)), dim3(256), 0, s, wa);
+        else if (out_side) TD_LAUNCH((k_wino4_out<false>), dim3(td_grid_for(T * (L.Cout / 4), 256, 256 * 16)), dim3(256), 0, s, wa);
         else TD_LAUNCH(k_wino4_in, dim3(td_grid_for(T * (L.Cin / 4), 256, 256 * 16)), dim3(256), 0, s, wa);
         prof_end(n, s);
     };
@@ -153,7 +162,7 @@ static void launch_conv_dma_forms(const ConvLayer& L, const ConvArgs& a, hipStre
 static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W, const float* resid, float* out, hipStream_t s,
                     int* Ho_out = nullptr, int* Wo_out = nullptr, const LnFuse* lnf = nullptr, const ClsArgs* cls = nullptr) {
     if (lnf && !L.wino) return td_fail("internal: LayerNorm fusion needs a Winograd input transform");
-    if (cls && (!L.wino || L.chunks > 1 || resid)) return td_fail("internal: the classifier rides in a whole Winograd conv's output transform");
+    if (cls && (!L.wino || L.chunks > 1 || resid || wino_act_general(L.act))) return td_fail("internal: the classifier rides in a whole Winograd conv's output transform");
     const int Ho = out_size(H, L.KS, L.stride, L.dil, L.pad), Wo = out_size(W, L.KS, L.stride, L.dil, L.pad);
     if (L.wino) {
         if (Ho_out) *Ho_out = H;
