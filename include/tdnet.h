@@ -19,7 +19,9 @@
  *     (skipped while the stream is being captured into a hipGraph).  Every caller stream is checked ONCE per handle (the handle remembers
  *     the streams it has seen; alternating between two streams does not repeat the check), for at most 8 distinct streams.  tdnet_finalize_weights, tdnet_create_shared, tdnet_get_stage
  *     synchronise (as do the test library's tdnet_op_* / tdnet_bench_* entries, include/tdnet_test.h).
- *   - all tensors are fp32.  Image in / logits out are NCHW like the reference; internal layout is NHWC.
+ *   - tensors are fp32 unless an entry says otherwise: image in / logits out are NCHW like the reference, labels int32 [H,W]; internal
+ *     layout is NHWC.  The *_u8 entries are the byte ends of the same frame: the image as uint8 HWC RGB at its SOURCE size (resized and
+ *     normalised on the device exactly as tdnet_amd/dataloader.py does on the host), labels as uint8 [H,W] (nclass <= 256 always).
  */
 #ifndef TDNET_H
 #define TDNET_H
@@ -172,6 +174,24 @@ int  tdnet_forward(tdnet_t* h, const float* img_nchw_dev, int pos_id, float* log
 int  tdnet_argmax(tdnet_t* h, const float* logits_nchw_dev, int32_t* labels_dev, void* stream);
 /* forward + argmax without materialising the full-resolution logits (labels identical to the two calls above).  */
 int  tdnet_forward_labels(tdnet_t* h, const float* img_nchw_dev, int pos_id, int32_t* labels_dev, void* stream);
+/* ---- uint8 frames in, uint8 labels out ---------------------------------------------------------------------------
+ * What every caller of the fp32 entries does on the host per frame -- cv2.resize to the network size, (x / 255 - mean) / std in float64,
+ * HWC -> CHW, fp32 (Testing/dataloader.py:64-71; tdnet_amd/dataloader.py resize_linear_u8 + cityscapesLoader.normalise) -- done by the
+ * frame's first kernel instead, BIT-IDENTICALLY: the resize is integer arithmetic on coefficient tables built like the loader builds them,
+ * the normalisation a 3 x 256 table evaluated in double and rounded once.  A frame given as bytes computes what the same frame given as the
+ * loader's fp32 tensor computes, and takes the same number of launches.
+ * tdnet_set_input_u8: configuration (not a frame call: it may synchronise; idempotent for equal arguments).  Frames will arrive as
+ * [src_height][src_width][3] bytes; mean / std: 3 doubles each, NULL = {.485, .456, .406} / {.229, .224, .225} (dataloader.py:52-53).
+ * Builds the tables on the host and uploads them into memory the handle owns (a tdnet_create_shared handle has its own configuration).
+ * Fails on a handle that is not finalized, sizes below 1, a zero or non-finite std, and a column downscale beyond about 20x.           */
+int  tdnet_set_input_u8(tdnet_t* h, int src_height, int src_width, const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
+/* tdnet_forward / tdnet_forward_labels / tdnet_encode with the image as device bytes [src_height][src_width][3], RGB, contiguous, at ANY
+ * byte address (no alignment assumed).  Without a prior tdnet_set_input_u8 they fail.  Like the fp32 entries they only enqueue.  fp32 and
+ * uint8 entries may be mixed frame by frame on one handle: the FIFO does not care how the image arrived.                                */
+int  tdnet_forward_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, float* logits_nchw_dev, void* stream);
+int  tdnet_forward_u8_labels(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* [H,W] */, void* stream);
+/* tdnet_argmax with uint8 labels [H,W] (the same labels, one byte each).                                            */
+int  tdnet_argmax_u8(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -188,6 +208,9 @@ int  tdnet_encode(tdnet_t* h, const float* img_nchw_dev, int pos_id, void* strea
 /* attention propagation + LayerNorm + head + x8 upsample of the pending frame (td4_psp18.py:142-152), then FIFO push */
 int  tdnet_propagate(tdnet_t* h, float* logits_nchw_dev, void* stream);
 int  tdnet_propagate_labels(tdnet_t* h, int32_t* labels_dev, void* stream);
+/* the byte forms (see "uint8 frames in, uint8 labels out")                                                        */
+int  tdnet_encode_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, void* stream);
+int  tdnet_propagate_labels_u8(tdnet_t* h, uint8_t* labels_dev, void* stream);
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

@@ -58,6 +58,15 @@ int tdnet_op_ppm(const float* c4_dev, int h, int w, const float* w_host, const f
 int tdnet_op_classifier(const float* x_dev, int HW, int C, const float* w_dev, const float* b_dev, int NC, float* out_dev, void* stream);
 /* bilinear align_corners=True (td4_psp18.py:227): planar [C,h,w] -> [C,H,W]                                       */
 int tdnet_op_upsample(const float* in_dev, int C, int h, int w, int H, int W, float* out_dev, void* stream);
+/* The stem's image buffer -- allocated and zeroed as a handle's workspace does -- filled from an fp32 NCHW image [3,H,W] (img_f32_dev) or from
+ * uint8 bytes [Hs,Ws,3] at any byte address (src_u8_dev; mean / std as tdnet_set_input_u8; Hs, Ws are ignored with img_f32_dev): exactly one
+ * of the two.  rows != 0: the packed-row image of the 7x7 stem [H+7][Wp][3], else NHWC4.  The COMPLETE buffer, border included, is copied to
+ * out_dev.  Returns its float count (out_dev == NULL: nothing else happens), <0 on error.                              */
+long tdnet_op_stem_image(const float* img_f32_dev, const uint8_t* src_u8_dev, int Hs, int Ws, int H, int W, const double* mean, const double* std,
+                         int rows, float* out_dev, size_t capacity, void* stream);
+/* low-resolution logits [C,h,w] -> labels [H,W] (bilinear align_corners=True, first maximum): int32 through the kernel of tdnet_forward_labels
+ * (labels_i32_dev != NULL) and / or uint8 (labels_u8_dev != NULL) through the kernel of its uint8 form.  C in 1..256. */
+int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, int W, int32_t* labels_i32_dev, uint8_t* labels_u8_dev, void* stream);
 
 #ifdef __cplusplus
 }

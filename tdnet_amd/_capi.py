@@ -67,6 +67,12 @@ SYMBOLS = {
     "tdnet_forward": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_argmax": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_forward_labels": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_set_input_u8": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "tdnet_forward_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_forward_u8_labels": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_argmax_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_encode_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
+    "tdnet_propagate_labels_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -104,6 +110,9 @@ TEST_SYMBOLS = {
                                     c_void_p, c_void_p]),
     "tdnet_op_upsample": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          c_void_p, c_void_p]),
+    "tdnet_op_stem_image": (ctypes.c_long, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
 }
 

@@ -112,7 +112,7 @@ static int run_parity_chains(tdnet* n, PathLayers& L, int h, int w, hipStream_t 
 }
 
 static int launch_chain_now(tdnet* n, PathLayers& L, hipStream_t s);
-static int encode_frame(tdnet* n, PathLayers& L, const float* img, hipStream_t s, int chain_at = -1) {   // chain_at >= 0: fork the cache-only chain in front of that backbone block
+static int encode_frame(tdnet* n, PathLayers& L, const FrameInput& img, hipStream_t s, int chain_at = -1) {   // chain_at >= 0: fork the cache-only chain in front of that backbone block
     const int DV = n->DV;
     // backbone (resnet.py:204-215)
     run_stem_pre(n, img, n->H, n->W, n->img4, s, L.stem.stem_rows());
@@ -223,8 +223,9 @@ static int finish_frame(tdnet* n, PathLayers& L, bool steady, hipStream_t s) {
     return 0;
 }
 
-static int frame_checks(tdnet* n, int pos_id, const char* who) {
+static int frame_checks(tdnet* n, int pos_id, const char* who, const FrameInput* in = nullptr) {
     if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized (the HIP path never runs on random init)", who);
+    if (in && in->kind == TD_IMG_U8 && !n->u8.set) return td_fail("%s: the uint8 input is not configured (call tdnet_set_input_u8 first)", who);
     if (pos_id < 0 || pos_id >= n->P) return td_fail("%s: pos_id %d out of range 0..%d", who, pos_id, n->P - 1);
     return 0;
 }
@@ -285,19 +286,19 @@ static int place_chain_stream(tdnet* n, hipStream_t s, bool explicit_call = fals
 }
 
 // started: set once the frame's own work has begun (past the argument checks) -- only then does a failure drop state
-static int forward_lowres_impl(tdnet* n, const float* img, int pos_id, hipStream_t s, bool* started);
-static int forward_lowres(tdnet* n, const float* img, int pos_id, hipStream_t s) {
+static int forward_lowres_impl(tdnet* n, const FrameInput& img, int pos_id, hipStream_t s, bool* started, const char* who);
+static int forward_lowres(tdnet* n, const FrameInput& img, int pos_id, hipStream_t s, const char* who = "tdnet_forward") {
     bool started = false;
-    const int rc = forward_lowres_impl(n, img, pos_id, s, &started);
+    const int rc = forward_lowres_impl(n, img, pos_id, s, &started, who);
     // A frame that failed after it started is dropped: it never reaches the FIFO, and whatever the internal streams were given is joined
     // back into the caller's.  A call rejected by the checks (bad pos_id, a frame waiting for tdnet_propagate) changes nothing: the
     // pending entry of a tdnet_encode stays valid.
     if (rc && started) { rejoin_streams(n, s); n->pending_slot = n->pending_pos = -1; }
     return rc;
 }
-static int forward_lowres_impl(tdnet* n, const float* img, int pos_id, hipStream_t s, bool* started) {
-    if (frame_checks(n, pos_id, "tdnet_forward")) return -1;
-    if (n->pending_slot >= 0) return td_fail("tdnet_forward: a frame encoded with tdnet_encode is waiting for tdnet_propagate");
+static int forward_lowres_impl(tdnet* n, const FrameInput& img, int pos_id, hipStream_t s, bool* started, const char* who) {
+    if (frame_checks(n, pos_id, who, &img)) return -1;
+    if (n->pending_slot >= 0) return td_fail("%s: a frame encoded with tdnet_encode is waiting for tdnet_propagate", who);
     PathLayers& L = n->paths[pos_id];
     n->nrec = 0;
     n->failed = false;

@@ -8,6 +8,7 @@
 //   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier / upsample):
 //                  a switch on the layer's planned route
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
+//   td_ingest.h    (kernels) uint8 image in, uint8 labels out; the host side of its tables is at the end of this file
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -26,6 +27,7 @@
 #include "td_attn_h.h"
 #include "td_attn_b3.h"
 #include "td_misc.h"
+#include "td_ingest.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -211,6 +213,19 @@ struct PathLayers {
     int pid = 0;
 };
 struct CacheSlot { float* q = nullptr; float* k = nullptr; float* v = nullptr; };
+// The uint8 image input of a handle (tdnet_set_input_u8): source size, normalisation and the device tables k_ingest_u8 reads.  Per handle:
+// tdnet_create_shared handles configure their own.
+struct U8Input {
+    bool set = false;
+    int Hs = 0, Ws = 0, H = 0, W = 0, Wt = 0;                          // Wt: W rounded up to a multiple of 4 (the x tables' row length)
+    double mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
+    bool resize = false;                                               // false: source size == network size, lookup only
+    int span = 0, threads = 256;                                       // LDS bytes per staged source row; workgroup size (a strip = 4 * threads columns)
+    float* lut = nullptr;                                              // [3][256]
+    int* xt = nullptr;                                                 // [4][Wt]
+    int* yt = nullptr;                                                 // [H][4]
+    size_t bytes = 0;                                                  // HBM held by the three tables
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -290,6 +305,7 @@ struct tdnet {
     bool prof = false;
     std::vector<ProfRec> recs;
     size_t nrec = 0;
+    U8Input u8;                                                        // tdnet_set_input_u8
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
     explicit tdnet(TdWeights* w)
@@ -317,3 +333,89 @@ struct AllocScope {                                                   // RAII: a
     explicit AllocScope(size_t* counter) : prev(g_alloc_counter) { g_alloc_counter = counter; }
     ~AllocScope() { g_alloc_counter = prev; }
 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// uint8 image input: the host side of td_ingest.h
+// ---------------------------------------------------------------------------------------------------------------
+// tdnet_amd/dataloader.py _linear_coeffs (OpenCV's INTER_LINEAR tables) with the same operations in the same types: a double scale,
+// fx = (float)((d + 0.5) * scale - 0.5), s = floor(fx), fx -= s in float, clamped at both borders, weights = rint to even of (1 - fx, fx) * 2048
+// in float.  (The library is built with -ffp-contract=off: no product here is fused into a later sum.)
+static void u8_linear_coeffs(int n_src, int n_dst, std::vector<int>& s0, std::vector<int>& s1, std::vector<int>& w0, std::vector<int>& w1) {
+    const double scale = (double)n_src / (double)n_dst;
+    s0.resize(n_dst); s1.resize(n_dst); w0.resize(n_dst); w1.resize(n_dst);
+    for (int d = 0; d < n_dst; ++d) {
+        float fx = (float)(((double)d + 0.5) * scale - 0.5);
+        long s = (long)floorf(fx);
+        fx = fx - (float)s;
+        if (s < 0) { fx = 0.f; s = 0; }
+        if (s >= n_src - 1) { fx = 0.f; s = n_src - 1; }
+        const float f1 = fx * 2048.0f, om = 1.0f - fx, f0 = om * 2048.0f;
+        w1[d] = (int)nearbyintf(f1);
+        w0[d] = (int)nearbyintf(f0);
+        s0[d] = (int)s;
+        s1[d] = (int)std::min<long>(s + 1, n_src - 1);
+    }
+}
+static void u8_free(U8Input& u) {
+    if (u.lut) hipFree(u.lut);
+    if (u.xt) hipFree(u.xt);
+    if (u.yt) hipFree(u.yt);
+    u = U8Input();
+}
+constexpr int TD_INGEST_LDS_MAX = 64 * 1024;
+// Validate, build the tables on the host and upload them into memory `u` owns.  NULL mean / std: the loader's (dataloader.py:52-53).
+static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who) {
+    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};
+    if (!mean) mean = mean0;
+    if (!std_) std_ = std0;
+    if (Hs < 1 || Ws < 1) return td_fail("%s: source size %d x %d must be at least 1 x 1", who, Hs, Ws);
+    if (H < 1 || W < 1 || H > 65535) return td_fail("%s: network size %d x %d out of range", who, H, W);
+    if ((double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(mean[c])) return td_fail("%s: mean[%d] is not finite", who, c);
+        if (!std::isfinite(std_[c]) || std_[c] == 0.0) return td_fail("%s: std[%d] must be finite and non-zero", who, c);
+    }
+    U8Input v;
+    v.Hs = Hs; v.Ws = Ws; v.H = H; v.W = W; v.Wt = (W + 3) / 4 * 4;
+    for (int c = 0; c < 3; ++c) { v.mean[c] = mean[c]; v.std[c] = std_[c]; }
+    v.resize = !(Hs == H && Ws == W);
+    std::vector<float> lut(768);
+    for (int c = 0; c < 3; ++c)
+        for (int b = 0; b < 256; ++b) lut[c * 256 + b] = (float)(((double)b / 255.0 - mean[c]) / std_[c]);
+    std::vector<int> xt, yt, x0, x1, a0, a1;
+    if (v.resize) {
+        std::vector<int> y0, y1, b0, b1;
+        u8_linear_coeffs(Ws, W, x0, x1, a0, a1);
+        u8_linear_coeffs(Hs, H, y0, y1, b0, b1);
+        xt.resize((size_t)4 * v.Wt);
+        for (int x = 0; x < v.Wt; ++x) {
+            const int k = x < W ? x : W - 1;                           // the padding repeats the last column: every table entry indexes the staged span
+            xt[x] = x0[k]; xt[v.Wt + x] = x1[k]; xt[2 * v.Wt + x] = a0[k]; xt[3 * v.Wt + x] = a1[k];
+        }
+        yt.resize((size_t)4 * H);
+        for (int y = 0; y < H; ++y) { yt[4 * y] = y0[y]; yt[4 * y + 1] = y1[y]; yt[4 * y + 2] = b0[y]; yt[4 * y + 3] = b1[y]; }
+    }
+    // the workgroup size: the largest whose two staged spans (+ up to 15 bytes in front of the first, rounded to 16) fit beside the table
+    bool fits = false;
+    for (int threads = 256; threads >= 64 && !fits; threads >>= 1) {
+        long span = 0;
+        for (int xs = 0; xs < W; xs += 4 * threads) {
+            const int xe = std::min(xs + 4 * threads, W);
+            const long cols = v.resize ? (long)x1[xe - 1] - x0[xs] + 1 : xe - xs;
+            span = std::max(span, (cols * 3 + 15 + 15) / 16 * 16);
+        }
+        if (TD_INGEST_LUT_BYTES + 2 * span <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; }
+    }
+    if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about 20x)", who, Ws, W);
+    if (upload(&v.lut, lut)) return -1;
+    if (v.resize) {
+        if (dev_alloc(&v.xt, xt.size()) || dev_alloc(&v.yt, yt.size())) { u8_free(v); return -1; }
+        if (hipMemcpy(v.xt, xt.data(), xt.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(v.yt, yt.data(), yt.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { u8_free(v); return td_fail("%s: table upload failed", who); }
+    }
+    v.bytes = lut.size() * sizeof(float) + (xt.size() + yt.size()) * sizeof(int);
+    v.set = true;
+    u8_free(u);
+    u = v;
+    return 0;
+}

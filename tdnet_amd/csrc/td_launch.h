@@ -289,13 +289,29 @@ static void run_ppm(tdnet* n, const float* c4, int h, int w, int C, int XS, int 
     prof_end(n, s);
 }
 
+// The image of a frame as the caller handed it over: fp32 NCHW [3][H][W] at the network size, or uint8 HWC [Hs][Ws][3] at the source size the
+// handle was configured for (tdnet_set_input_u8; `u8` = that configuration).  Everything behind the stem's image buffer is the same frame.
+enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };
+struct FrameInput { const void* p; int kind; const U8Input* u8; };
+static inline FrameInput frame_input_f32(const float* img) { return FrameInput{img, TD_IMG_F32, nullptr}; }
 // rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
-static void run_stem_pre(tdnet* n, const float* img, int H, int W, float* img4, hipStream_t s, bool rows = false) {
+static void run_stem_pre(tdnet* n, const FrameInput& in, int H, int W, float* img4, hipStream_t s, bool rows = false) {
     prof_begin(n, 2, false, 0, s);
-    if (rows)
-        TD_LAUNCH(k_nchw3_to_rgbpad, dim3(td_grid_for((long)H * ((W + 3) / 4))), dim3(256), 0, s, img, img4, H, W, stem_rows_wp(W));
-    else
-        TD_LAUNCH(k_nchw3_to_nhwc4, dim3(td_grid_for((long)H * W)), dim3(256), 0, s, img, img4, H * W);
+    switch (in.kind) {
+    case TD_IMG_U8: {                                                  // resize + normalise + layout in the same one launch (td_ingest.h)
+        const U8Input& u = *in.u8;
+        const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0, u.span};
+        TD_LAUNCH(k_ingest_u8, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span, s, a);
+        break;
+    }
+    default: {
+        const float* img = (const float*)in.p;
+        if (rows)
+            TD_LAUNCH(k_nchw3_to_rgbpad, dim3(td_grid_for((long)H * ((W + 3) / 4))), dim3(256), 0, s, img, img4, H, W, stem_rows_wp(W));
+        else
+            TD_LAUNCH(k_nchw3_to_nhwc4, dim3(td_grid_for((long)H * W)), dim3(256), 0, s, img, img4, H * W);
+    }
+    }
     prof_end(n, s);
 }
 // pool16: 0 = fp32 in / fp32 out; the fp16-activation mode's first map: 1 = fp32 in (the stem's output) / fp16 out, 2 = fp16 in (deep stem) / fp16 out
@@ -327,4 +343,13 @@ static void launch_upsample(const float* in, int C, int h, int w, int H, int W, 
     if (W % 4 == 0 && ((size_t)out & 15) == 0 && H <= 65535 && C <= 65535) TD_LAUNCH(k_upsample_x4, dim3((W / 4 + 255) / 256, H, C), dim3(256), 0, s, in, out, C, h, w, H, W);
     else if (H <= 65535 && C <= 65535) TD_LAUNCH(k_upsample_row, dim3((W / 4 + 2 + 255) / 256, H, C), dim3(256), 0, s, in, out, C, h, w, H, W);
     else TD_LAUNCH(k_upsample, dim3(td_grid_for((long)C * H * W, 256, 256 * 16)), dim3(256), 0, s, in, out, C, h, w, H, W);
+}
+// uint8 labels (nclass <= 256): the fused upsample + argmax, and the argmax of full-resolution logits (td_ingest.h)
+static int launch_upsample_argmax_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, hipStream_t s) {
+    if (H > 65535) return td_fail("uint8 labels: H = %d is above the grid's 65535 rows", H);
+    TD_LAUNCH(k_upsample_argmax_u8, dim3((W / 4 + 2 + 255) / 256, H), dim3(256), 0, s, in, labels, C, h, w, H, W);
+    return 0;
+}
+static void launch_argmax_u8(const float* logits, int C, long HW, unsigned char* labels, hipStream_t s) {
+    TD_LAUNCH(k_argmax_u8, dim3((unsigned)((HW / 4 + 2 + 255) / 256)), dim3(256), 0, s, logits, labels, C, HW);
 }

@@ -141,6 +141,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     for (auto& s : n->slots) { if (s.q) hipFree(s.q); if (s.k) hipFree(s.k); if (s.v) hipFree(s.v); }
     for (auto& r : n->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     if (n->vt16) hipFree(n->vt16);
+    u8_free(n->u8);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -215,17 +216,26 @@ struct LaunchCount {
     explicit LaunchCount(tdnet* n_) : n(n_), l0(td_launch_count) {}
     ~LaunchCount() { n->launches = (int)(td_launch_count - l0); }
 };
-extern "C" int tdnet_forward(tdnet_t* n, const float* img, int pos_id, float* logits, void* stream) {
-    if (!n || !img || !logits) return td_fail("tdnet_forward: null argument");
+// The frame entries differ in how the image arrives (FrameInput: fp32 NCHW, or uint8 HWC through tdnet_set_input_u8) and in what leaves
+// (logits, int32 labels, uint8 labels); everything between is one frame.  fp32 and uint8 entries may be mixed frame by frame on one handle.
+static int forward_logits(tdnet* n, const FrameInput& in, int pos_id, float* logits, void* stream, const char* who) {
     TD_ON_DEVICE(n, -1);
     LaunchCount count_(n);
     hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, img, pos_id, s)) return -1;
+    if (forward_lowres(n, in, pos_id, s, who)) return -1;
     prof_begin(n, 2, false, 0, s);
     launch_upsample(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, logits, s);
     prof_end(n, s);
     TD_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int tdnet_forward(tdnet_t* n, const float* img, int pos_id, float* logits, void* stream) {
+    if (!n || !img || !logits) return td_fail("tdnet_forward: null argument");
+    return forward_logits(n, frame_input_f32(img), pos_id, logits, stream, "tdnet_forward");
+}
+extern "C" int tdnet_forward_u8(tdnet_t* n, const uint8_t* img, int pos_id, float* logits, void* stream) {
+    if (!n || !img || !logits) return td_fail("tdnet_forward_u8: null argument");
+    return forward_logits(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, logits, stream, "tdnet_forward_u8");
 }
 extern "C" int tdnet_argmax(tdnet_t* n, const float* logits, int32_t* labels, void* stream) {
     if (!n || !logits || !labels) return td_fail("tdnet_argmax: null argument");
@@ -234,12 +244,19 @@ extern "C" int tdnet_argmax(tdnet_t* n, const float* logits, int32_t* labels, vo
     TD_HIP(hipGetLastError());
     return 0;
 }
+extern "C" int tdnet_argmax_u8(tdnet_t* n, const float* logits, uint8_t* labels, void* stream) {
+    if (!n || !logits || !labels) return td_fail("tdnet_argmax_u8: null argument");
+    TD_ON_DEVICE(n, -1);
+    launch_argmax_u8(logits, n->cfg.nclass, (long)n->H * n->W, labels, (hipStream_t)stream);
+    TD_HIP(hipGetLastError());
+    return 0;
+}
 extern "C" int tdnet_forward_labels(tdnet_t* n, const float* img, int pos_id, int32_t* labels, void* stream) {
     if (!n || !img || !labels) return td_fail("tdnet_forward_labels: null argument");
     TD_ON_DEVICE(n, -1);
     LaunchCount count_(n);
     hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, img, pos_id, s)) return -1;
+    if (forward_lowres(n, frame_input_f32(img), pos_id, s)) return -1;
     prof_begin(n, 2, false, 0, s);
     TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)n->H * n->W)), dim3(256), 0, s, (const float*)n->lowres, labels, n->cfg.nclass,
               n->h, n->w, n->H, n->W);
@@ -247,16 +264,44 @@ extern "C" int tdnet_forward_labels(tdnet_t* n, const float* img, int pos_id, in
     TD_HIP(hipGetLastError());
     return 0;
 }
+extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, void* stream) {
+    if (!n || !img || !labels) return td_fail("tdnet_forward_u8_labels: null argument");
+    TD_ON_DEVICE(n, -1);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (forward_lowres(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, s, "tdnet_forward_u8_labels")) return -1;
+    prof_begin(n, 2, false, 0, s);
+    const int rc = launch_upsample_argmax_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, s);
+    prof_end(n, s);
+    TD_HIP(hipGetLastError());
+    return rc;
+}
+// Configuration of the uint8 image input (not a frame call: it may synchronise; idempotent for equal arguments).  The tables live in memory this
+// handle owns; a tdnet_create_shared handle has its own configuration.
+extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, const double* mean, const double* std_) {
+    if (!n) return td_fail("tdnet_set_input_u8: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_u8: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};   // dataloader.py:52-53
+    const double* m = mean ? mean : mean0;
+    const double* sd = std_ ? std_ : std0;
+    const U8Input& u = n->u8;
+    if (u.set && u.Hs == src_height && u.Ws == src_width && memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
+    if (u.set) TD_HIP(hipDeviceSynchronize());                        // a frame in flight may still read the tables that are about to go
+    const size_t before = n->u8.bytes;
+    TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_u8"));
+    n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
+    return 0;
+}
 // ---- split frame + cache transport (path-parallel single stream) ------------------------------------
 // Rank g of a path-parallel group serves the frames t = g (mod W): it encodes its frame as soon as the image is there, publishes
 // the resulting cache entry, receives the entries of the frames in between from its peers (in frame order) and only then
 // propagates.  The FIFO of every rank therefore holds exactly what the sequential td4_psp18.py:123-154 would hold.
-extern "C" int tdnet_encode(tdnet_t* n, const float* img, int pos_id, void* stream) {
-    if (!n || !img) return td_fail("tdnet_encode: null argument");
+static int encode_impl(tdnet* n, const FrameInput& img, int pos_id, void* stream, const char* who) {
     TD_ON_DEVICE(n, -1);
-    if (frame_checks(n, pos_id, "tdnet_encode")) return -1;
-    if (n->cfg.model == 1) return td_fail("tdnet_encode: pspnet has no temporal state; use tdnet_forward");
-    if (n->pending_slot >= 0) return td_fail("tdnet_encode: the previous encoded frame has not been propagated");
+    if (frame_checks(n, pos_id, who, &img)) return -1;
+    if (n->cfg.model == 1) return td_fail("%s: pspnet has no temporal state; use tdnet_forward", who);
+    if (n->pending_slot >= 0) return td_fail("%s: the previous encoded frame has not been propagated", who);
     n->nrec = 0;
     n->failed = false;
     TD_TRY(place_chain_stream(n, (hipStream_t)stream));
@@ -269,6 +314,14 @@ extern "C" int tdnet_encode(tdnet_t* n, const float* img, int pos_id, void* stre
     n->pending_pos = pos_id;
     TD_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int tdnet_encode(tdnet_t* n, const float* img, int pos_id, void* stream) {
+    if (!n || !img) return td_fail("tdnet_encode: null argument");
+    return encode_impl(n, frame_input_f32(img), pos_id, stream, "tdnet_encode");
+}
+extern "C" int tdnet_encode_u8(tdnet_t* n, const uint8_t* img, int pos_id, void* stream) {
+    if (!n || !img) return td_fail("tdnet_encode_u8: null argument");
+    return encode_impl(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, stream, "tdnet_encode_u8");
 }
 static int propagate_lowres(tdnet* n, hipStream_t s) {
     if (n->pending_slot < 0) return td_fail("tdnet_propagate: no encoded frame (call tdnet_encode first)");
@@ -295,6 +348,16 @@ extern "C" int tdnet_propagate_labels(tdnet_t* n, int32_t* labels, void* stream)
     if (propagate_lowres(n, s)) return -1;
     TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)n->H * n->W)), dim3(256), 0, s, (const float*)n->lowres, labels, n->cfg.nclass,
               n->h, n->w, n->H, n->W);
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_propagate_labels_u8(tdnet_t* n, uint8_t* labels, void* stream) {
+    if (!n || !labels) return td_fail("tdnet_propagate_labels_u8: null argument");
+    TD_ON_DEVICE(n, -1);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (propagate_lowres(n, s)) return -1;
+    TD_TRY(launch_upsample_argmax_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, s));
     TD_HIP(hipGetLastError());
     return 0;
 }

@@ -89,7 +89,7 @@ extern "C" int tdnet_op_stem(const float* img, int H, int W, const float* w_host
     const size_t img_floats = std::max((size_t)H * W * 4, (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4);
     if (dev_alloc(&img4, img_floats) || dev_alloc(&s1, (size_t)H1 * W1 * 64)) return -1;
     if (L.stem_rows()) TD_HIP(hipMemsetAsync(img4, 0, img_floats * sizeof(float), s));   // the packed-row image's zero border
-    run_stem_pre(nullptr, img, H, W, img4, s, L.stem_rows());
+    run_stem_pre(nullptr, frame_input_f32(img), H, W, img4, s, L.stem_rows());
     run_conv(nullptr, L, img4, H, W, nullptr, s1, s);
     run_maxpool(nullptr, s1, H1, W1, 64, out, s);
     TD_HIP(hipStreamSynchronize(s));
@@ -171,6 +171,43 @@ extern "C" int tdnet_op_classifier(const float* x, int HW, int C, const float* w
 extern "C" int tdnet_op_upsample(const float* in, int C, int h, int w, int H, int W, float* out, void* stream) {
     launch_upsample(in, C, h, w, H, W, out, (hipStream_t)stream);
     TD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// The stem's image buffer, allocated and zeroed as the workspace does (td_weights.h alloc_workspace), filled from an fp32 NCHW image (img_f32 != NULL:
+// run_stem_pre's fp32 kernels) or from a uint8 source (src_u8: the ingest kernel with the tables tdnet_set_input_u8 would build), then copied
+// WHOLE -- border included -- to out_dev.  rows: the packed-row layout, else NHWC4.  Returns the buffer's float count (out_dev == NULL: only that).
+extern "C" long tdnet_op_stem_image(const float* img_f32, const uint8_t* src_u8, int Hs, int Ws, int H, int W, const double* mean, const double* std_,
+                                    int rows, float* out, size_t capacity, void* stream) {
+    if (H < 1 || W < 1) return td_fail("tdnet_op_stem_image: empty image");
+    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
+    if (!out) return (long)img_floats;
+    if ((img_f32 != nullptr) == (src_u8 != nullptr)) return td_fail("tdnet_op_stem_image: give exactly one of img_f32 and src_u8");
+    if (capacity < img_floats) return td_fail("tdnet_op_stem_image: capacity %zu < %zu", capacity, img_floats);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    if (src_u8 && u8_build(u, Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image")) return -1;
+    float* img4 = nullptr;
+    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
+    long rc = (long)img_floats;
+    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("tdnet_op_stem_image: memset failed");
+    if (rc >= 0) {
+        run_stem_pre(nullptr, src_u8 ? FrameInput{src_u8, TD_IMG_U8, &u} : frame_input_f32(img_f32), H, W, img4, s, rows != 0);
+        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("tdnet_op_stem_image: copy failed");
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_image: device error");
+    hipFree(img4);
+    u8_free(u);
+    return rc;
+}
+// low-resolution logits [C][h][w] -> labels [H][W]: int32 through k_upsample_argmax (labels_i32 != NULL) and / or uint8 through
+// k_upsample_argmax_u8 (labels_u8 != NULL)
+extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, int H, int W, int32_t* labels_i32, uint8_t* labels_u8, void* stream) {
+    if (C < 1 || C > 256) return td_fail("tdnet_op_upsample_argmax: C must be in 1..256");
+    hipStream_t s = (hipStream_t)stream;
+    if (labels_i32) TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)H * W)), dim3(256), 0, s, in, labels_i32, C, h, w, H, W);
+    if (labels_u8) TD_TRY(launch_upsample_argmax_u8(in, C, h, w, H, W, labels_u8, s));
+    TD_HIP(hipStreamSynchronize(s));
     TD_HIP(hipGetLastError());
     return 0;
 }

@@ -60,8 +60,9 @@ class cityscapesLoader():
               [255, 0, 0], [0, 0, 142], [0, 0, 70], [0, 60, 100], [0, 80, 100], [0, 0, 230], [119, 11, 32]]
     label_colours = dict(zip(range(19), colors))
 
-    def __init__(self, img_path, in_size, pin_memory=False):
+    def __init__(self, img_path, in_size, pin_memory=False, as_uint8=False):
         self.img_path = img_path
+        self.as_uint8 = bool(as_uint8)                   # not in the reference: frames stay the decoded bytes [1, Hs, Ws, 3] (model.forward_u8 / forward_labels_u8 resize and normalise on the device, bit-identically)
         self.pin_memory = bool(pin_memory)               # not in the reference: frames land in page-locked memory (DevicePrefetcher uploads them without a bounce copy)
         self.n_classes = 19
         self.files = sorted(recursive_glob(rootdir=self.img_path, suffix=".png"))
@@ -85,7 +86,12 @@ class cityscapesLoader():
             path = path.rstrip()
             img_name = path.split('/')[-1]
             folder = path.split('/')[-2]
-            im = resize_linear_u8(np.asarray(Image.open(path).convert("RGB")), self.size)      # = cv2.resize(img, self.size), dataloader.py:64
+            im = np.asarray(Image.open(path).convert("RGB"))
+            if self.as_uint8:                                          # no resize, no normalisation: a quarter of the fp32 frame's bytes (at equal size)
+                t = torch.from_numpy(np.ascontiguousarray(im)[np.newaxis])
+                self.data.append([t.pin_memory() if self.pin_memory else t, img_name, folder, self.size])
+                continue
+            im = resize_linear_u8(im, self.size)                       # = cv2.resize(img, self.size), dataloader.py:64
             self.data.append([self.normalise(im), img_name, folder, self.size])
 
     def decode_segmap(self, temp):
@@ -99,7 +105,8 @@ class cityscapesLoader():
 
 
 class DevicePrefetcher:
-    """Iterate `loader.data` items ([img [1,3,H,W] fp32 CPU, name, folder, size], dataloader.py:73) with the image ALREADY ON THE DEVICE:
+    """Iterate `loader.data` items ([img [1,3,H,W] fp32 CPU -- or [1,Hs,Ws,3] uint8 from cityscapesLoader(as_uint8=True): the device buffers
+    take the items' dtype --, name, folder, size], dataloader.py:73) with the image ALREADY ON THE DEVICE:
     the host->device copy of item i + 1 runs on a copy stream while the caller's stream computes item i.  Page-locked frames
     (cityscapesLoader(..., pin_memory=True)) upload asynchronously; a pageable frame is staged by the HIP runtime while the host waits (still
     under the device's previous frame; an own bounce copy into pinned memory was measured SLOWER than that: 106 against 149 frames/s).
@@ -128,7 +135,7 @@ class DevicePrefetcher:
         return len(self.items)
 
     def _device_buffer(self, shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
+        return torch.empty(shape, dtype=getattr(self.items[0][0], "dtype", torch.float32), device=self.device)
 
     def __iter__(self):
         if not self.items:
@@ -164,7 +171,7 @@ class DevicePrefetcher:
 
 
 class LabelDownloader:
-    """Device int32 label maps -> host numpy arrays through pinned memory, asynchronously: submit(labels, tag) enqueues the copy on a side
+    """Device int32 (or uint8: forward_labels_u8) label maps -> host numpy arrays through pinned memory, asynchronously: submit(labels, tag) enqueues the copy on a side
     stream and returns the results that have ARRIVED meanwhile as [(tag, array)], in order; drain() waits for the rest.  The arrays are
     VIEWS of the pinned buffers, valid until the next submit() / drain() call (copy what must live longer).  Replaces the
     synchronous `output.max(1)[1].cpu().numpy()` of test.py:61 (a 16.8 MB int64 round trip per 1024x2048 frame) in a loop that wants the

@@ -90,6 +90,37 @@ class Engine:
     def forward_labels(self, img_ptr, pos_id, labels_ptr, stream=None):
         self.lib.check(self.lib.tdnet_forward_labels(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), stream))
 
+    # ---- uint8 frames in, uint8 labels out (include/tdnet.h) ----
+    def set_input_u8(self, src_height, src_width, mean=None, std=None):
+        """Frames will arrive as uint8 [src_height, src_width, 3]; mean / std: three numbers each, None = the loader's.  A configuration
+        call (it may synchronise); repeating it with equal arguments does nothing."""
+        key = (int(src_height), int(src_width), None if mean is None else tuple(float(v) for v in mean),
+               None if std is None else tuple(float(v) for v in std))
+        if getattr(self, "_u8_key", None) == key:
+            return
+        for v in key[2:]:
+            if v is not None and len(v) != 3:
+                raise _capi.TdnetError("set_input_u8: mean and std are three numbers each")
+        m = None if key[2] is None else (ctypes.c_double * 3)(*key[2])
+        sd = None if key[3] is None else (ctypes.c_double * 3)(*key[3])
+        self.lib.check(self.lib.tdnet_set_input_u8(self.h, key[0], key[1], m, sd))
+        self._u8_key = key
+
+    def forward_u8(self, img_ptr, pos_id, logits_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8(self.h, _ptr(img_ptr), int(pos_id), _ptr(logits_ptr), stream))
+
+    def forward_u8_labels(self, img_ptr, pos_id, labels_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_labels(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), stream))
+
+    def encode_u8(self, img_ptr, pos_id, stream=None):
+        self.lib.check(self.lib.tdnet_encode_u8(self.h, _ptr(img_ptr), int(pos_id), stream))
+
+    def propagate_labels_u8(self, labels_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_labels_u8(self.h, _ptr(labels_ptr), stream))
+
+    def argmax_u8(self, logits_ptr, labels_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_argmax_u8(self.h, _ptr(logits_ptr), _ptr(labels_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

@@ -119,9 +119,11 @@ class _TDNetBase(nn.Module):
         n, c, H, W = img.shape
         return self._engine_for(H, W, img.device.index or 0, n)
 
-    def _engines_for_batch(self, img):
-        """One handle per batch sample: sample 0 on the model's own handle, sample i > 0 on its own (same weights, own FIFO)."""
-        n, c, H, W = img.shape
+    def _engines_for_batch(self, img, size=None):
+        """One handle per batch sample: sample 0 on the model's own handle, sample i > 0 on its own (same weights, own FIFO).
+        size: the network's (H, W) where the tensor does not carry it (uint8 frames at their source size)."""
+        n = img.shape[0]
+        H, W = size if size is not None else img.shape[2:]
         first = self._engine_for(H, W, img.device.index or 0, n)
         if self._batch is not None and n != self._batch and first.fifo_len() > 0:
             # the reference's queues hold [N, Lk, .] tensors: a frame with another N fails in torch.bmm (transformer.py:133)
@@ -209,11 +211,11 @@ class _TDNetBase(nn.Module):
         if pos_id not in range(self.path_num):
             raise RuntimeError("pos_id must be t mod %d" % self.path_num)
 
-    def _for_each_sample(self, img, call):
+    def _for_each_sample(self, img, call, size=None):
         """call(i, engine, raw_stream) for every batch sample: even samples on the caller's stream, odd ones on a second stream, which
         waits for the caller's (the input is ready) and is joined again before this returns -- so the caller's stream stays the only
         one the caller has to order against, as with a single handle.  N = 1 (test.py:46-53): one handle, one call, no events."""
-        engines = self._engines_for_batch(img)
+        engines = self._engines_for_batch(img) if size is None else self._engines_for_batch(img, size)
         cur = torch.cuda.current_stream(img.device)
         if len(engines) == 1:
             call(0, engines[0], cur.cuda_stream)
@@ -280,6 +282,74 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, lambda i, eng, s: eng.forward_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s))
         return out
 
+    # ---- uint8 frames in, uint8 labels out (not in the reference; include/tdnet.h "uint8 frames in") ---------------------------------
+    # img_u8: torch.uint8 CUDA tensor [N, Hs, Ws, 3] -- the decoded frames as they are (RGB, HWC, any source size).  The library resizes to
+    # the network size and normalises on the device, bit-identically to cityscapesLoader (resize_linear_u8 + normalise), so
+    # forward_u8(frame_bytes) == forward(loader_tensor).  The NETWORK size is the one the handle was built for: by ensure_engine(H, W, device)
+    # or an earlier frame; a model without a handle takes it from in_size=(H, W) (as cityscapesLoader does).
+    def _check_frame_u8(self, img, pos_id, in_size):
+        if not torch.is_tensor(img) or img.dtype != torch.uint8:
+            raise RuntimeError("expected a torch.uint8 image tensor [N,Hs,Ws,3], got %s" % (img.dtype if torch.is_tensor(img) else type(img).__name__))
+        if img.dim() != 4 or img.shape[3] != 3:
+            raise RuntimeError("expected a uint8 image tensor [N,Hs,Ws,3] (HWC, RGB), got shape %s" % (tuple(img.shape),))
+        if img.device.type != "cuda":
+            raise TdnetError("tdnet_amd runs on MI355X only: got a %s tensor (no CPU fallback)" % img.device.type)
+        if img.shape[0] < 1 or img.shape[1] < 1 or img.shape[2] < 1:
+            raise RuntimeError("expected a uint8 image tensor [N,Hs,Ws,3] with N, Hs, Ws >= 1")
+        if pos_id not in range(self.path_num):
+            raise RuntimeError("pos_id must be t mod %d" % self.path_num)
+        if in_size is not None:
+            return int(in_size[0]), int(in_size[1])
+        if self._engine_key is None:
+            raise RuntimeError("the network size is not known yet: pass in_size=(H, W), or call ensure_engine(H, W, device) first")
+        return self._engine_key[0], self._engine_key[1]
+
+    def _u8_call(self, img, size, call, mean, std):
+        Hs, Ws = int(img.shape[1]), int(img.shape[2])
+
+        def one(i, eng, s):
+            eng.set_input_u8(Hs, Ws, mean, std)                        # (re)configured when the source size changes; a no-op otherwise
+            call(i, eng, s)
+        self._for_each_sample(img, one, size)
+
+    def forward_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+        """forward() on the decoded bytes: logits [N, nclass, H, W] at the network size."""
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        out = torch.empty((img.shape[0], self.nclass, H, W), device=img.device, dtype=torch.float32)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std)
+        return out
+
+    def forward_labels_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+        """forward_labels() on the decoded bytes, labels as uint8 [N, H, W] (the same labels: nclass <= 256)."""
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std)
+        return out
+
+    def encode_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+        """encode() on the decoded bytes."""
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        if img_u8.shape[0] != 1:
+            raise RuntimeError("encode_u8(): the split frame serves ONE stream (batch size 1)")
+        img = img_u8.contiguous()
+        eng = self._engine_for(H, W, img.device.index or 0, 1)
+        eng.set_input_u8(int(img.shape[1]), int(img.shape[2]), mean, std)
+        self._pending_shape = (H, W, img.device)
+        eng.encode_u8(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
+
+    def argmax_u8(self, logits):
+        """logits [N, nclass, H, W] (fp32, CUDA) of this model -> uint8 labels [N, H, W] = logits.max(1)[1]."""
+        if self._engine is None:
+            raise RuntimeError("argmax_u8(): no handle yet")
+        logits = logits.contiguous().float()
+        out = torch.empty((logits.shape[0],) + tuple(logits.shape[2:]), device=logits.device, dtype=torch.uint8)
+        s = torch.cuda.current_stream(logits.device).cuda_stream
+        for i in range(logits.shape[0]):
+            self._engine.argmax_u8(logits[i].data_ptr(), out[i].data_ptr(), s)
+        return out
+
     # ---- split frame + cache transport (path-parallel single stream: parallel.PathParallelStream) ------------------
     def encode(self, img, pos_id=0):
         """First half of forward(): backbone + pyramid slice + Encoding; the frame's cache entry is left pending."""
@@ -292,13 +362,19 @@ class _TDNetBase(nn.Module):
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
     def propagate(self, labels=False):
-        """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits (or int32 labels)."""
+        """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True) or
+        uint8 labels (labels="u8")."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
         H, W, dev = self._pending_shape
         self._pending_shape = None
         s = torch.cuda.current_stream(dev).cuda_stream
-        if labels:
+        if isinstance(labels, str):
+            if labels != "u8":
+                raise RuntimeError("propagate(): labels must be False, True or \"u8\"")
+            out = torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+            self._engine.propagate_labels_u8(out.data_ptr(), s)
+        elif labels:
             out = torch.empty((1, H, W), device=dev, dtype=torch.int32)
             self._engine.propagate_labels(out.data_ptr(), s)
         else:

@@ -41,3 +41,9 @@ class pspnet(_TDNetBase):
 
     def forward_labels(self, x, pos_id=None):
         return super().forward_labels(x[-1:], 0)
+
+    def forward_u8(self, x, pos_id=None, **kw):
+        return super().forward_u8(x[-1:], 0, **kw)
+
+    def forward_labels_u8(self, x, pos_id=None, **kw):
+        return super().forward_labels_u8(x[-1:], 0, **kw)

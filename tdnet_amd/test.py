@@ -8,7 +8,9 @@ Same loop as Testing/test.py:45-81: pos_id = i % path_num, forward timed between
 i > 5 averaged, argmax = output.max(1)[1], quarter-resolution colour PNG per frame.  Differences: PNG I/O through PIL
 (imageio / cv2 are not in this image, so no on-screen display); `--gpu` sets HIP_VISIBLE_DEVICES as well;
 `--synthetic_seed N` runs on seeded synthetic weights when no checkpoint is available; `--in_size HxW` (default 769x1537,
-test.py:24) must match the checkpoint's LayerNorm shape exactly as in the reference.
+test.py:24) must match the checkpoint's LayerNorm shape exactly as in the reference; `--u8` keeps the frames as the decoded bytes (the
+library resizes and normalises them on the device, bit-identically to the loader) and, with `--prefetch`, is the all-bytes loop: uint8
+upload, forward_labels_u8, uint8 label download.
 """
 import argparse
 import os
@@ -25,7 +27,8 @@ def test(args):
     from tdnet_amd.model import td2_psp50, td4_psp18
     device = torch.device("cuda")
     H, W = (int(v) for v in args.in_size.lower().split("x"))
-    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False))
+    u8 = bool(getattr(args, "u8", False))
+    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8)
     vid_seq.load_frames()
     if args.model == "td4-psp18":
         path_num = 4
@@ -65,7 +68,7 @@ def test(args):
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
             for i, (image, img_name, folder, ori_size) in enumerate(DevicePrefetcher(vid_seq.data, device)):
-                labels = model.forward_labels(image, pos_id=i % path_num)
+                labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
                     save(pred, *tag)
             for tag, pred in down.drain():
@@ -82,7 +85,7 @@ def test(args):
             image = image.to(device)
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
-            output = model(image, pos_id=i % path_num)
+            output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
             torch.cuda.synchronize()
             elapsed_time = timeit.default_timer() - start_time
             if i > 5:
@@ -108,4 +111,5 @@ if __name__ == "__main__":
     parser.add_argument("--in_size", nargs="?", type=str, default="769x1537", help="HxW fed to the network (test.py:24)")
     parser.add_argument("--synthetic_seed", nargs="?", type=int, default=None, help="run on seeded synthetic weights")
     parser.add_argument("--prefetch", action="store_true", help="throughput loop: upload of the next frame under the current one, asynchronous label download")
+    parser.add_argument("--u8", action="store_true", help="frames stay uint8 HWC at their source size: resize + normalisation on the device (bit-identical); with --prefetch uint8 labels too")
     test(parser.parse_args())
