@@ -192,6 +192,23 @@ int  tdnet_forward_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, float*
 int  tdnet_forward_u8_labels(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* [H,W] */, void* stream);
 /* tdnet_argmax with uint8 labels [H,W] (the same labels, one byte each).                                            */
 int  tdnet_argmax_u8(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev, void* stream);
+/* ---- colour map out ------------------------------------------------------------------------------------------------
+ * What the reference's loop does on the host behind the labels (Testing/test.py:61-71): the label map resized with nearest sampling and
+ * decode_segmap -- done by the frame's LAST kernel instead.  It evaluates the x8 upsample only at the sampled pixels, takes the first-maximum
+ * argmax there and writes the colour: rgb [out_height][out_width][3] uint8 (at any byte address) ==
+ * decode_segmap(labels[ys][:, xs]) of the labels the label entries give for the same frame, byte for byte, ys / xs =
+ * tdnet_amd/dataloader.py nearest_index(H, out_height) / (W, out_width): min((long)(o * ((double)n / n_out)), n - 1).
+ * tdnet_set_output_rgb: configuration (not a frame call: it may synchronise; idempotent for equal arguments).  Any output size >= 1 x 1, smaller
+ * than, equal to or larger than the network's.  palette_rgb: [n_colours][3] bytes on the HOST, copied (the library has no colour table of its
+ * own); a label >= n_colours comes out grey (l, l, l), as decode_segmap leaves it.  Per handle: a tdnet_create_shared handle configures its own.
+ * Fails on a handle that is not finalized, sizes below 1, n_colours outside 1..256 and a NULL palette.                                        */
+int  tdnet_set_output_rgb(tdnet_t* h, int out_height, int out_width, const uint8_t* palette_rgb /* [n_colours][3], host */, int n_colours /* 1..256 */);
+/* tdnet_forward_labels / tdnet_forward_u8_labels with the picture in place of the label map: the same frame, the same FIFO step, the same number
+ * of launches.  Without a prior tdnet_set_output_rgb they fail (and change nothing).  They only enqueue.                                       */
+int  tdnet_forward_rgb(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* rgb_dev, void* stream);
+int  tdnet_forward_u8_rgb(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* rgb_dev, void* stream);
+/* the picture of a uint8 label map [H,W] the caller already holds (tdnet_forward_u8_labels, tdnet_argmax_u8, ...)   */
+int  tdnet_labels_rgb(tdnet_t* h, const uint8_t* labels_u8_dev, uint8_t* rgb_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -211,6 +228,7 @@ int  tdnet_propagate_labels(tdnet_t* h, int32_t* labels_dev, void* stream);
 /* the byte forms (see "uint8 frames in, uint8 labels out")                                                        */
 int  tdnet_encode_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, void* stream);
 int  tdnet_propagate_labels_u8(tdnet_t* h, uint8_t* labels_dev, void* stream);
+int  tdnet_propagate_rgb(tdnet_t* h, uint8_t* rgb_dev, void* stream);   /* see "colour map out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

@@ -67,6 +67,13 @@ long tdnet_op_stem_image(const float* img_f32_dev, const uint8_t* src_u8_dev, in
 /* low-resolution logits [C,h,w] -> labels [H,W] (bilinear align_corners=True, first maximum): int32 through the kernel of tdnet_forward_labels
  * (labels_i32_dev != NULL) and / or uint8 (labels_u8_dev != NULL) through the kernel of its uint8 form.  C in 1..256. */
 int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, int W, int32_t* labels_i32_dev, uint8_t* labels_u8_dev, void* stream);
+/* The colour map [oh,ow,3] (uint8, any byte address) of low-resolution logits [C,h,w] upsampled to [H,W] -- through the last kernel of tdnet_forward_rgb
+ * (labels_u8_dev == NULL) -- or of a uint8 label map [H,W] through tdnet_labels_rgb's kernel (labels_u8_dev != NULL; in_dev, C, h, w are then
+ * ignored).  Index tables and colour table are built by the host function tdnet_set_output_rgb uses; palette [n_colours][3] on the host.          */
+int tdnet_op_upsample_argmax_rgb(const float* in_dev, int C, int h, int w, int H, int W, int oh, int ow, const uint8_t* palette, int n_colours,
+                                 uint8_t* rgb_dev, const uint8_t* labels_u8_dev, void* stream);
+/* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
+int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 
 #ifdef __cplusplus
 }

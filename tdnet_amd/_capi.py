@@ -73,6 +73,11 @@ SYMBOLS = {
     "tdnet_argmax_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_encode_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
     "tdnet_propagate_labels_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_output_rgb": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_int]),
+    "tdnet_forward_rgb": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_forward_u8_rgb": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_labels_rgb": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_rgb": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -113,6 +118,8 @@ TEST_SYMBOLS = {
     "tdnet_op_stem_image": (ctypes.c_long, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_upsample_argmax_rgb": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
 }
 

@@ -8,7 +8,7 @@
 //   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier / upsample):
 //                  a switch on the layer's planned route
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
-//   td_ingest.h    (kernels) uint8 image in, uint8 labels out; the host side of its tables is at the end of this file
+//   td_ingest.h    (kernels) uint8 image in, uint8 labels out, colour map out; the host side of their tables is at the end of this file
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -226,6 +226,17 @@ struct U8Input {
     int* yt = nullptr;                                                 // [H][4]
     size_t bytes = 0;                                                  // HBM held by the three tables
 };
+// The colour-map output of a handle (tdnet_set_output_rgb): picture size, palette and the device tables k_upsample_argmax_rgb / k_labels_rgb
+// read.  Per handle, like U8Input.
+struct RgbOutput {
+    bool set = false;
+    int H = 0, W = 0, oh = 0, ow = 0, n_colours = 0;
+    unsigned char palette[768] = {0};                                  // the caller's, kept to recognise an equal call
+    int* ys = nullptr;                                                 // [oh]: nearest_index(H, oh)
+    int* xs = nullptr;                                                 // [ow]: nearest_index(W, ow)
+    unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -306,6 +317,7 @@ struct tdnet {
     std::vector<ProfRec> recs;
     size_t nrec = 0;
     U8Input u8;                                                        // tdnet_set_input_u8
+    RgbOutput rgb;                                                     // tdnet_set_output_rgb
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
     explicit tdnet(TdWeights* w)
@@ -417,5 +429,54 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
     v.set = true;
     u8_free(u);
     u = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// colour-map output: the host side of td_ingest.h's k_upsample_argmax_rgb / k_labels_rgb
+// ---------------------------------------------------------------------------------------------------------------
+// tdnet_amd/dataloader.py nearest_index with the same operations in the same types: the quotient first, in double, then the product, then
+// truncation, then the clamp.  This is the project's rule (tdnet_amd/test.py's resize of the label map since its first version), not cv2's text.
+static void rgb_nearest_index(int n_src, int n_dst, std::vector<int>& idx) {
+    const double scale = (double)n_src / (double)n_dst;
+    idx.resize(n_dst);
+    for (int o = 0; o < n_dst; ++o) idx[o] = (int)std::min<long>((long)((double)o * scale), (long)n_src - 1);
+}
+static void rgb_free(RgbOutput& r) {
+    if (r.ys) hipFree(r.ys);
+    if (r.xs) hipFree(r.xs);
+    if (r.lut) hipFree(r.lut);
+    r = RgbOutput();
+}
+static bool rgb_same(const RgbOutput& r, int oh, int ow, const unsigned char* palette, int n_colours) {
+    return r.set && r.oh == oh && r.ow == ow && r.n_colours == n_colours && palette && n_colours >= 1 && n_colours <= 256 &&
+           memcmp(r.palette, palette, (size_t)3 * n_colours) == 0;
+}
+// Validate, build the two index tables and the 256-entry colour table on the host and upload them into memory `r` owns.  On failure `r` is
+// left as it was.
+static int rgb_build(RgbOutput& r, int H, int W, int oh, int ow, const unsigned char* palette, int n_colours, const char* who) {
+    if (oh < 1 || ow < 1) return td_fail("%s: output size %d x %d must be at least 1 x 1", who, oh, ow);
+    if (oh > 65535) return td_fail("%s: out_height = %d is above the grid's 65535 rows", who, oh);
+    if ((double)oh * ow * 3 >= 2147483648.0) return td_fail("%s: output size %d x %d is too large", who, oh, ow);
+    if (n_colours < 1 || n_colours > 256) return td_fail("%s: n_colours = %d must be in 1..256", who, n_colours);
+    if (!palette) return td_fail("%s: palette_rgb is NULL (the library carries no colour table of its own)", who);
+    if (H < 1 || W < 1) return td_fail("%s: network size %d x %d out of range", who, H, W);
+    RgbOutput v;
+    v.H = H; v.W = W; v.oh = oh; v.ow = ow; v.n_colours = n_colours;
+    memcpy(v.palette, palette, (size_t)3 * n_colours);
+    std::vector<int> ys, xs;
+    rgb_nearest_index(H, oh, ys);
+    rgb_nearest_index(W, ow, xs);
+    std::vector<unsigned> lut(256);
+    for (unsigned l = 0; l < 256; ++l)                                 // decode_segmap: a label outside the table keeps its value in all three channels
+        lut[l] = (int)l < n_colours ? (unsigned)palette[3 * l] | ((unsigned)palette[3 * l + 1] << 8) | ((unsigned)palette[3 * l + 2] << 16) : l * 0x010101u;
+    if (dev_alloc(&v.ys, ys.size()) || dev_alloc(&v.xs, xs.size()) || dev_alloc(&v.lut, lut.size())) { rgb_free(v); return -1; }
+    if (hipMemcpy(v.ys, ys.data(), ys.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v.xs, xs.data(), xs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v.lut, lut.data(), lut.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) { rgb_free(v); return td_fail("%s: table upload failed", who); }
+    v.bytes = (ys.size() + xs.size()) * sizeof(int) + lut.size() * sizeof(unsigned);
+    v.set = true;
+    rgb_free(r);
+    r = v;
     return 0;
 }

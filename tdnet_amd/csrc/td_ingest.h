@@ -183,3 +183,79 @@ TD_KERNEL void k_argmax_u8(const float* __restrict__ logits, unsigned char* __re
     }
     td_u8_store(labels, q, pa, pb, bi);
 }
+
+// ---- colour map out ----------------------------------------------------------------------------------------------------------------
+// What the frame loop does on the host behind the labels (Testing/test.py:61-71; tdnet_amd/test.py save()): the nearest-index sample of the label
+// map to [oh][ow] and decode_segmap.  rgb [oh][ow][3] bytes = lut[labels[ys[oy]][xs[ox]]]: ys / xs are dataloader.nearest_index's tables, built on
+// the host (td_handle.h rgb_build), lut 256 words r | g << 8 | b << 16 (rows >= n_colours grey (l, l, l), as decode_segmap leaves them).
+// A row is 3 ow bytes and starts at any byte address; 4 pixels = 12 bytes = three 4-byte words where row + 3 x is 4-byte aligned, i.e. from
+// x = row (mod 4) on (3 x = -row  <=>  x = row (mod 4), 3 being its own inverse).  Lane 0 of a row: the row & 3 pixels in front of the first such
+// group; lane q >= 1: the group behind it: [xa, xb)
+TD_DEV void td_rgb_run(const unsigned char* row, long q, long ow, long* xa, long* xb) {
+    const long X0 = (long)((size_t)row & 3u);
+    *xa = q == 0 ? 0 : X0 + 4 * (q - 1);
+    *xb = q == 0 ? (X0 < ow ? X0 : ow) : (*xa + 4 < ow ? *xa + 4 : ow);
+}
+TD_DEV void td_rgb_store(unsigned char* row, long q, long xa, long xb, const unsigned* px) {   // px[e]: the lut word of pixel xa + e
+    if (q > 0 && xb - xa == 4) {
+        unsigned* o = reinterpret_cast<unsigned*>(row + 3 * xa);
+        o[0] = px[0] | (px[1] << 24);
+        o[1] = (px[1] >> 8) | (px[2] << 16);
+        o[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+        for (long X = xa; X < xb; ++X) {
+            const unsigned p = px[X - xa];
+            row[3 * X] = (unsigned char)p; row[3 * X + 1] = (unsigned char)(p >> 8); row[3 * X + 2] = (unsigned char)(p >> 16);
+        }
+    }
+}
+// The frame's last launch when a picture is asked for: the x8 bilinear upsample evaluated ONLY at the sampled pixels (Y, X) = (ys[oy], xs[ox]) --
+// td_up_coef and k_upsample_argmax's expression and first-maximum rule, so the label under every output pixel is the one the label entries
+// give -- and the colour looked up.  grid = (ceil((ow / 4 + 2) / 256), oh): row from the block index, Y and the vertical coefficients wave-uniform.
+TD_KERNEL void k_upsample_argmax_rgb(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                     unsigned char* __restrict__ rgb, int C, int h, int w, int H, int W, int oh, int ow) {
+    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = rgb + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    const int Y = ys[oy];
+    const UpCoef cy = td_up_coef(Y, sy, h);
+    UpCoef cx[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cx[e] = td_up_coef(xs[xa + e < ow ? xa + e : ow - 1], sx, w);
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    for (int c = 0; c < C; ++c) {
+        const float* pl = in + (size_t)c * h * w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float v00 = pl[cy.i0 * w + cx[e].i0], v01 = pl[cy.i0 * w + cx[e].i1];
+            const float v10 = pl[cy.i1 * w + cx[e].i0], v11 = pl[cy.i1 * w + cx[e].i1];
+            const float v = (1.f - cy.l) * ((1.f - cx[e].l) * v00 + cx[e].l * v01) + cy.l * ((1.f - cx[e].l) * v10 + cx[e].l * v11);
+            if (c == 0 || v > best[e]) { best[e] = v; bi[e] = c; }
+        }
+    }
+    unsigned px[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = lut[bi[e] & 255];
+    td_rgb_store(orow, q, xa, xb, px);
+}
+// The same picture from a uint8 label map [H][W] the caller already holds (same store layout)
+TD_KERNEL void k_labels_rgb(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                            unsigned char* __restrict__ rgb, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = rgb + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
+    unsigned px[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = lut[lrow[xs[xa + e < ow ? xa + e : ow - 1]]];
+    td_rgb_store(orow, q, xa, xb, px);
+}

@@ -353,3 +353,17 @@ static int launch_upsample_argmax_u8(const float* in, int C, int h, int w, int H
 static void launch_argmax_u8(const float* logits, int C, long HW, unsigned char* labels, hipStream_t s) {
     TD_LAUNCH(k_argmax_u8, dim3((unsigned)((HW / 4 + 2 + 255) / 256)), dim3(256), 0, s, logits, labels, C, HW);
 }
+// the colour map [oh][ow][3] of a frame (tdnet_set_output_rgb; `r` = that configuration): from the low-resolution logits, evaluated at the sampled
+// pixels only, or from a uint8 label map [H][W] (td_ingest.h)
+static int launch_upsample_argmax_rgb(const float* in, int C, int h, int w, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
+    if (r.oh > 65535) return td_fail("colour map: out_height = %d is above the grid's 65535 rows", r.oh);
+    TD_LAUNCH(k_upsample_argmax_rgb, dim3((r.ow / 4 + 2 + 255) / 256, r.oh), dim3(256), 0, s, in, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
+              C, h, w, r.H, r.W, r.oh, r.ow);
+    return 0;
+}
+static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
+    if (r.oh > 65535) return td_fail("colour map: out_height = %d is above the grid's 65535 rows", r.oh);
+    TD_LAUNCH(k_labels_rgb, dim3((r.ow / 4 + 2 + 255) / 256, r.oh), dim3(256), 0, s, labels, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
+              r.W, r.oh, r.ow);
+    return 0;
+}

@@ -142,6 +142,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     for (auto& r : n->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     if (n->vt16) hipFree(n->vt16);
     u8_free(n->u8);
+    rgb_free(n->rgb);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -293,6 +294,49 @@ extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, con
     n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
     return 0;
 }
+// ---- colour map out ----------------------------------------------------------------------------------------------------------------
+// Configuration of the colour-map output (not a frame call: it may synchronise; idempotent for equal arguments).  Tables and palette live in
+// memory this handle owns; a tdnet_create_shared handle has its own configuration.
+extern "C" int tdnet_set_output_rgb(tdnet_t* n, int out_height, int out_width, const uint8_t* palette_rgb, int n_colours) {
+    if (!n) return td_fail("tdnet_set_output_rgb: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_output_rgb: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    if (rgb_same(n->rgb, out_height, out_width, palette_rgb, n_colours)) return 0;
+    if (n->rgb.set) TD_HIP(hipDeviceSynchronize());                   // a frame in flight may still read the tables that are about to go
+    const size_t before = n->rgb.bytes;
+    TD_TRY(rgb_build(n->rgb, n->H, n->W, out_height, out_width, palette_rgb, n_colours, "tdnet_set_output_rgb"));
+    n->ws_bytes += n->rgb.bytes - before;
+    return 0;
+}
+// The labels entries with another last launch: the picture instead of the label map.  Same frame, same FIFO step, same number of launches.
+static int forward_rgb(tdnet* n, const FrameInput& in, int pos_id, uint8_t* rgb, void* stream, const char* who) {
+    TD_ON_DEVICE(n, -1);
+    if (!n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (forward_lowres(n, in, pos_id, s, who)) return -1;
+    prof_begin(n, 2, false, 0, s);
+    const int rc = launch_upsample_argmax_rgb(n->lowres, n->cfg.nclass, n->h, n->w, n->rgb, rgb, s);
+    prof_end(n, s);
+    TD_HIP(hipGetLastError());
+    return rc;
+}
+extern "C" int tdnet_forward_rgb(tdnet_t* n, const float* img, int pos_id, uint8_t* rgb, void* stream) {
+    if (!n || !img || !rgb) return td_fail("tdnet_forward_rgb: null argument");
+    return forward_rgb(n, frame_input_f32(img), pos_id, rgb, stream, "tdnet_forward_rgb");
+}
+extern "C" int tdnet_forward_u8_rgb(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* rgb, void* stream) {
+    if (!n || !img || !rgb) return td_fail("tdnet_forward_u8_rgb: null argument");
+    return forward_rgb(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, rgb, stream, "tdnet_forward_u8_rgb");
+}
+extern "C" int tdnet_labels_rgb(tdnet_t* n, const uint8_t* labels, uint8_t* rgb, void* stream) {
+    if (!n || !labels || !rgb) return td_fail("tdnet_labels_rgb: null argument");
+    TD_ON_DEVICE(n, -1);
+    if (!n->rgb.set) return td_fail("tdnet_labels_rgb: the colour-map output is not configured (call tdnet_set_output_rgb first)");
+    TD_TRY(launch_labels_rgb(labels, n->rgb, rgb, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
 // ---- split frame + cache transport (path-parallel single stream) ------------------------------------
 // Rank g of a path-parallel group serves the frames t = g (mod W): it encodes its frame as soon as the image is there, publishes
 // the resulting cache entry, receives the entries of the frames in between from its peers (in frame order) and only then
@@ -358,6 +402,17 @@ extern "C" int tdnet_propagate_labels_u8(tdnet_t* n, uint8_t* labels, void* stre
     hipStream_t s = (hipStream_t)stream;
     if (propagate_lowres(n, s)) return -1;
     TD_TRY(launch_upsample_argmax_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, s));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_propagate_rgb(tdnet_t* n, uint8_t* rgb, void* stream) {
+    if (!n || !rgb) return td_fail("tdnet_propagate_rgb: null argument");
+    TD_ON_DEVICE(n, -1);
+    if (!n->rgb.set) return td_fail("tdnet_propagate_rgb: the colour-map output is not configured (call tdnet_set_output_rgb first)");
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (propagate_lowres(n, s)) return -1;
+    TD_TRY(launch_upsample_argmax_rgb(n->lowres, n->cfg.nclass, n->h, n->w, n->rgb, rgb, s));
     TD_HIP(hipGetLastError());
     return 0;
 }

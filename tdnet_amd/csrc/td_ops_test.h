@@ -211,6 +211,28 @@ extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, in
     TD_HIP(hipGetLastError());
     return 0;
 }
+// The colour map [oh][ow][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: k_upsample_argmax_rgb) or of a uint8 label map [H][W]
+// (labels_u8 != NULL: k_labels_rgb; in, C, h, w are ignored), through the tables and colour table rgb_build makes for a handle.
+extern "C" int tdnet_op_upsample_argmax_rgb(const float* in, int C, int h, int w, int H, int W, int oh, int ow, const uint8_t* palette, int n_colours,
+                                            uint8_t* rgb, const uint8_t* labels_u8, void* stream) {
+    if (!rgb) return td_fail("tdnet_op_upsample_argmax_rgb: rgb_out is NULL");
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("tdnet_op_upsample_argmax_rgb: logits [C,h,w] with C in 1..256 expected");
+    hipStream_t s = (hipStream_t)stream;
+    RgbOutput r;
+    TD_TRY(rgb_build(r, H, W, oh, ow, palette, n_colours, "tdnet_op_upsample_argmax_rgb"));
+    int rc = labels_u8 ? launch_labels_rgb(labels_u8, r, rgb, s) : launch_upsample_argmax_rgb(in, C, h, w, r, rgb, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_rgb: device error");
+    rgb_free(r);
+    return rc;
+}
+// The index table the colour-map kernels sample through (rgb_build's: dataloader.nearest_index restated in C) -> out_host [n_dst] int32.  Host only.
+extern "C" int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host) {
+    if (n_src < 1 || n_dst < 1 || !out_host) return td_fail("tdnet_op_nearest_index: sizes >= 1 and a host buffer expected");
+    std::vector<int> idx;
+    rgb_nearest_index(n_src, n_dst, idx);
+    memcpy(out_host, idx.data(), idx.size() * sizeof(int));
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // tuning / roofline hooks (not on the product path)

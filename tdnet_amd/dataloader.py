@@ -54,6 +54,13 @@ def resize_linear_u8(img, size):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+def nearest_index(n_src, n_dst):
+    """Source index per destination index of the nearest-sample resize of the label map (test.py:64, cv2.INTER_NEAREST): int64 [n_dst] =
+    min(int64(o * (n_src / n_dst)), n_src - 1) -- the quotient first, in float64, then the product, then truncation.  This is the project's rule:
+    the frame loop (tdnet_amd/test.py) and the library's colour-map kernels (td_handle.h rgb_nearest_index, the same operations in C) share it."""
+    return np.minimum((np.arange(n_dst) * (n_src / n_dst)).astype(np.int64), n_src - 1)
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],

@@ -121,6 +121,31 @@ class Engine:
     def argmax_u8(self, logits_ptr, labels_ptr, stream=None):
         self.lib.check(self.lib.tdnet_argmax_u8(self.h, _ptr(logits_ptr), _ptr(labels_ptr), stream))
 
+    # ---- colour map out (include/tdnet.h) ----
+    def set_output_rgb(self, out_height, out_width, palette):
+        """Frames may be asked for as the colour map uint8 [out_height, out_width, 3]; palette: n_colours x 3 byte values (1..256 rows).  A
+        configuration call (it may synchronise); repeating it with equal arguments does nothing."""
+        pal = None if palette is None else np.ascontiguousarray(np.asarray(palette, dtype=np.uint8))
+        if pal is not None and (pal.ndim != 2 or pal.shape[1] != 3):
+            raise _capi.TdnetError("set_output_rgb: the palette is n_colours rows of 3 bytes")
+        key = (int(out_height), int(out_width), None if pal is None else pal.tobytes())
+        if getattr(self, "_rgb_key", None) == key:
+            return
+        self.lib.check(self.lib.tdnet_set_output_rgb(self.h, key[0], key[1], None if pal is None else pal.ctypes.data, 0 if pal is None else pal.shape[0]))
+        self._rgb_key = key
+
+    def forward_rgb(self, img_ptr, pos_id, rgb_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_rgb(self.h, _ptr(img_ptr), int(pos_id), _ptr(rgb_ptr), stream))
+
+    def forward_u8_rgb(self, img_ptr, pos_id, rgb_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_rgb(self.h, _ptr(img_ptr), int(pos_id), _ptr(rgb_ptr), stream))
+
+    def propagate_rgb(self, rgb_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_rgb(self.h, _ptr(rgb_ptr), stream))
+
+    def labels_rgb(self, labels_ptr, rgb_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_labels_rgb(self.h, _ptr(labels_ptr), _ptr(rgb_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

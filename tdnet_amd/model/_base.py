@@ -350,6 +350,66 @@ class _TDNetBase(nn.Module):
             self._engine.argmax_u8(logits[i].data_ptr(), out[i].data_ptr(), s)
         return out
 
+    # ---- colour map out (not in the reference's model; its loop makes the picture on the host, test.py:61-71) -------------------------
+    # The frame's last kernel writes decode_segmap(labels[ys][:, xs]) directly: uint8 [N, oh, ow, 3], ys / xs = dataloader.nearest_index.
+    # out_size = (oh, ow); palette: n_colours x 3 byte values, None = cityscapesLoader.label_colours.
+    @staticmethod
+    def _palette(palette):
+        if palette is None:
+            from ..dataloader import cityscapesLoader
+            palette = cityscapesLoader.colors
+        return np.ascontiguousarray(np.asarray(palette, dtype=np.uint8))
+
+    @staticmethod
+    def _rgb_size(out_size):
+        if out_size is None or len(out_size) != 2 or int(out_size[0]) < 1 or int(out_size[1]) < 1:
+            raise RuntimeError("out_size must be (oh, ow), at least (1, 1), got %r" % (out_size,))
+        return int(out_size[0]), int(out_size[1])
+
+    def _rgb_out(self, n, out_size, device):
+        oh, ow = self._rgb_size(out_size)
+        return torch.empty((n, oh, ow, 3), device=device, dtype=torch.uint8)
+
+    def forward_rgb(self, img, pos_id, out_size, palette=None):
+        """forward_labels() with the colour map [N, oh, ow, 3] uint8 in place of the label map."""
+        self._rgb_size(out_size)
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
+
+        def one(i, eng, s):
+            eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.forward_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out
+
+    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None):
+        """forward_labels_u8() with the colour map [N, oh, ow, 3] uint8 in place of the label map: bytes in, picture out."""
+        self._rgb_size(out_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
+
+        def one(i, eng, s):
+            eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std)
+        return out
+
+    def labels_rgb(self, labels_u8, out_size, palette=None):
+        """uint8 labels [N, H, W] (CUDA) of this model -> their colour maps [N, oh, ow, 3]."""
+        if self._engine is None:
+            raise RuntimeError("labels_rgb(): no handle yet")
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
+            raise RuntimeError("labels_rgb(): expected uint8 labels [N, %d, %d]" % tuple(self._engine_key[:2]))
+        labels = labels_u8.contiguous()
+        out = self._rgb_out(labels.shape[0], out_size, labels.device)
+        self._engine.set_output_rgb(out.shape[1], out.shape[2], self._palette(palette))
+        s = torch.cuda.current_stream(labels.device).cuda_stream
+        for i in range(labels.shape[0]):
+            self._engine.labels_rgb(labels[i].data_ptr(), out[i].data_ptr(), s)
+        return out
+
     # ---- split frame + cache transport (path-parallel single stream: parallel.PathParallelStream) ------------------
     def encode(self, img, pos_id=0):
         """First half of forward(): backbone + pyramid slice + Encoding; the frame's cache entry is left pending."""
@@ -361,17 +421,25 @@ class _TDNetBase(nn.Module):
         self._pending_shape = (img.shape[2], img.shape[3], img.device)
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
-    def propagate(self, labels=False):
-        """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True) or
-        uint8 labels (labels="u8")."""
+    def propagate(self, labels=False, out_size=None, palette=None):
+        """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
+        uint8 labels (labels="u8") or the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb)."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
+        if isinstance(labels, str) and labels not in ("u8", "rgb"):
+            raise RuntimeError("propagate(): labels must be False, True, \"u8\" or \"rgb\"")
+        if labels == "rgb" and out_size is None:
+            raise RuntimeError("propagate(labels=\"rgb\"): out_size=(oh, ow) is required")
         H, W, dev = self._pending_shape
-        self._pending_shape = None
         s = torch.cuda.current_stream(dev).cuda_stream
+        if labels == "rgb":
+            out = self._rgb_out(1, out_size, dev)
+            self._engine.set_output_rgb(out.shape[1], out.shape[2], self._palette(palette))
+            self._pending_shape = None
+            self._engine.propagate_rgb(out.data_ptr(), s)
+            return out
+        self._pending_shape = None
         if isinstance(labels, str):
-            if labels != "u8":
-                raise RuntimeError("propagate(): labels must be False, True or \"u8\"")
             out = torch.empty((1, H, W), device=dev, dtype=torch.uint8)
             self._engine.propagate_labels_u8(out.data_ptr(), s)
         elif labels:

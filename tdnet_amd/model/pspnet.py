@@ -47,3 +47,9 @@ class pspnet(_TDNetBase):
 
     def forward_labels_u8(self, x, pos_id=None, **kw):
         return super().forward_labels_u8(x[-1:], 0, **kw)
+
+    def forward_rgb(self, x, pos_id=None, out_size=None, palette=None):
+        return super().forward_rgb(x[-1:], 0, out_size, palette)
+
+    def forward_rgb_u8(self, x, pos_id=None, in_size=None, out_size=None, **kw):
+        return super().forward_rgb_u8(x[-1:], 0, in_size, out_size, **kw)

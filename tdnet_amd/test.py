@@ -10,7 +10,8 @@ i > 5 averaged, argmax = output.max(1)[1], quarter-resolution colour PNG per fra
 `--synthetic_seed N` runs on seeded synthetic weights when no checkpoint is available; `--in_size HxW` (default 769x1537,
 test.py:24) must match the checkpoint's LayerNorm shape exactly as in the reference; `--u8` keeps the frames as the decoded bytes (the
 library resizes and normalises them on the device, bit-identically to the loader) and, with `--prefetch`, is the all-bytes loop: uint8
-upload, forward_labels_u8, uint8 label download.
+upload, forward_labels_u8, uint8 label download; `--rgb` has the frame's last kernel write the quarter-size colour map itself (the nearest
+sample of the label map and decode_segmap, byte for byte): the host downloads the picture and encodes the PNG, nothing else.
 """
 import argparse
 import os
@@ -23,11 +24,12 @@ import torch
 def test(args):
     os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu                      # test.py:19
     os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
-    from tdnet_amd.dataloader import cityscapesLoader
+    from tdnet_amd.dataloader import cityscapesLoader, nearest_index
     from tdnet_amd.model import td2_psp50, td4_psp18
     device = torch.device("cuda")
     H, W = (int(v) for v in args.in_size.lower().split("x"))
     u8 = bool(getattr(args, "u8", False))
+    rgb = bool(getattr(args, "rgb", False))
     vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8)
     vid_seq.load_frames()
     if args.model == "td4-psp18":
@@ -46,17 +48,26 @@ def test(args):
     model.eval()
     model.to(device)
 
-    def save(pred, img_name, folder, ori_size):
-        pred = np.squeeze(pred, axis=0).astype(np.int8)
-        # cv2.resize(pred, (W//4, H//4), INTER_NEAREST) (test.py:64): nearest sample at floor(dst * scale)
-        oh, ow = ori_size[1] // 4, ori_size[0] // 4
-        ys = np.minimum((np.arange(oh) * (pred.shape[0] / oh)).astype(np.int64), pred.shape[0] - 1)
-        xs = np.minimum((np.arange(ow) * (pred.shape[1] / ow)).astype(np.int64), pred.shape[1] - 1)
-        decoded = vid_seq.decode_segmap(pred[ys][:, xs])
+    def write_png(picture, img_name, folder):
         save_dir = os.path.join(args.output_path, folder)
         os.makedirs(save_dir, exist_ok=True)
         from PIL import Image
-        Image.fromarray(decoded.astype(np.uint8)).save(os.path.join(save_dir, img_name))
+        Image.fromarray(picture).save(os.path.join(save_dir, img_name))
+
+    def save(pred, img_name, folder, ori_size):
+        pred = np.squeeze(pred, axis=0).astype(np.int8)
+        # cv2.resize(pred, (W//4, H//4), INTER_NEAREST) (test.py:64): nearest sample at floor(dst * scale)
+        ys, xs = nearest_index(pred.shape[0], ori_size[1] // 4), nearest_index(pred.shape[1], ori_size[0] // 4)
+        write_png(vid_seq.decode_segmap(pred[ys][:, xs]).astype(np.uint8), img_name, folder)
+
+    def save_rgb(picture, img_name, folder, ori_size):                 # --rgb: the device wrote the picture
+        write_png(np.squeeze(picture, axis=0), img_name, folder)
+
+    def colour_map(image, pos_id, ori_size):                           # [1, oh, ow, 3] uint8 on the device
+        out_size = (ori_size[1] // 4, ori_size[0] // 4)
+        if u8:
+            return model.forward_rgb_u8(image, pos_id, (H, W), out_size)
+        return model.forward_rgb(image, pos_id, out_size)
 
     timer, i = 0.0, -1
     with torch.no_grad():
@@ -68,11 +79,14 @@ def test(args):
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
             for i, (image, img_name, folder, ori_size) in enumerate(DevicePrefetcher(vid_seq.data, device)):
-                labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
+                if rgb:
+                    labels = colour_map(image, i % path_num, ori_size)
+                else:
+                    labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
-                    save(pred, *tag)
+                    (save_rgb if rgb else save)(pred, *tag)
             for tag, pred in down.drain():
-                save(pred, *tag)
+                (save_rgb if rgb else save)(pred, *tag)
             torch.cuda.synchronize()
             timer = timeit.default_timer() - start_time
             print("---------------------")
@@ -85,12 +99,18 @@ def test(args):
             image = image.to(device)
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
-            output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
+            if rgb:
+                output = colour_map(image, i % path_num, ori_size)
+            else:
+                output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
             torch.cuda.synchronize()
             elapsed_time = timeit.default_timer() - start_time
             if i > 5:
                 timer += elapsed_time
-            save(output.data.max(1)[1].cpu().numpy(), img_name, folder, ori_size)
+            if rgb:
+                save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
+            else:
+                save(output.data.max(1)[1].cpu().numpy(), img_name, folder, ori_size)
             print(" Frame {0:2d}   RunningTime/Latency={1:3.5f} s".format(i + 1, elapsed_time))
     print("---------------------")
     print(" Model: {0:s}".format(args.model))
@@ -112,4 +132,5 @@ if __name__ == "__main__":
     parser.add_argument("--synthetic_seed", nargs="?", type=int, default=None, help="run on seeded synthetic weights")
     parser.add_argument("--prefetch", action="store_true", help="throughput loop: upload of the next frame under the current one, asynchronous label download")
     parser.add_argument("--u8", action="store_true", help="frames stay uint8 HWC at their source size: resize + normalisation on the device (bit-identical); with --prefetch uint8 labels too")
+    parser.add_argument("--rgb", action="store_true", help="the frame's last kernel writes the quarter-size colour map: no label download, resize or decode_segmap on the host")
     test(parser.parse_args())
