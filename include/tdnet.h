@@ -18,7 +18,8 @@
  *     tdnet_warmup(h, stream) does that check explicitly; a frame call on a stream tdnet_warmup has not seen does it lazily
  *     (skipped while the stream is being captured into a hipGraph).  Every caller stream is checked ONCE per handle (the handle remembers
  *     the streams it has seen; alternating between two streams does not repeat the check), for at most 8 distinct streams.  tdnet_finalize_weights, tdnet_create_shared, tdnet_get_stage
- *     synchronise (as do the test library's tdnet_op_* / tdnet_bench_* entries, include/tdnet_test.h).
+ *     and tdnet_score_read synchronise, the configuration calls tdnet_set_input_u8 / tdnet_set_output_rgb / tdnet_set_score may; tdnet_score_reset
+ *     and tdnet_score_export only enqueue (as do the test library's tdnet_op_* / tdnet_bench_* entries, include/tdnet_test.h).
  *   - tensors are fp32 unless an entry says otherwise: image in / logits out are NCHW like the reference, labels int32 [H,W]; internal
  *     layout is NHWC.  The *_u8 entries are the byte ends of the same frame: the image as uint8 HWC RGB at its SOURCE size (resized and
  *     normalised on the device exactly as tdnet_amd/dataloader.py does on the host), labels as uint8 [H,W] (nclass <= 256 always).
@@ -209,6 +210,31 @@ int  tdnet_forward_rgb(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_
 int  tdnet_forward_u8_rgb(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* rgb_dev, void* stream);
 /* the picture of a uint8 label map [H,W] the caller already holds (tdnet_forward_u8_labels, tdnet_argmax_u8, ...)   */
 int  tdnet_labels_rgb(tdnet_t* h, const uint8_t* labels_u8_dev, uint8_t* rgb_dev, void* stream);
+/* ---- score out ----------------------------------------------------------------------------------------------------
+ * What the reference's validation loop does on the host behind the labels (Training/validate.py:59-70, ptsemseg/metrics.py:12-21): the
+ * n_class x n_class confusion matrix, hist[g][l] += 1 over the pixels with 0 <= g < n_class -- counted by the frame's LAST kernel instead, into
+ * a matrix of uint64 [nclass][nclass] the handle owns.  g = gt_map[gt[y][x]], gt uint8 [H,W] at the network size on the device (any byte
+ * address); g >= nclass means "ignore" (255 is Cityscapes' ignore value).  l is the label the label entries give for the same frame.  Integer
+ * counts: exact, independent of the order of the additions.
+ * tdnet_set_score: configuration (not a frame call: it may synchronise; idempotent for an equal map).  gt_map: 256 bytes on the HOST, copied,
+ * NULL = identity; it lets a caller feed raw dataset ids and have them folded to train ids or to "ignore" on the device (the library carries no
+ * dataset table of its own).  Allocates the zeroed matrix; a different map starts a new zeroed matrix.  Per handle: a tdnet_create_shared handle
+ * configures and owns its own.  Matrix and map are counted in tdnet_memory_bytes.  Fails on a handle that is not finalized.                     */
+int  tdnet_set_score(tdnet_t* h, const uint8_t* gt_map /* [256], host | NULL */);
+/* tdnet_forward_labels / tdnet_forward_u8_labels with the other last launch: the frame's counts are ADDED to the handle's matrix, and the uint8
+ * label map [H,W] is written too unless labels_u8_dev is NULL.  The same frame, the same FIFO step, the same number of launches (the fused
+ * form; DESIGN.md 5.7 says what a measurement would have to show for that to change to "one more").  They only
+ * enqueue, and work inside a hipGraph capture (every replay adds its frame).  Without a prior tdnet_set_score they fail naming it and change
+ * nothing (a pending encoded frame stays pending).                                                                                         */
+int  tdnet_forward_score(tdnet_t* h, const float* img_nchw_dev, int pos_id, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);
+int  tdnet_forward_u8_score(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);
+/* the counts of a uint8 label map [H,W] the caller already holds (the unfused form; a label >= nclass is not counted) */
+int  tdnet_labels_score(tdnet_t* h, const uint8_t* labels_u8_dev, const uint8_t* gt_u8_dev, void* stream);
+/* enqueued: the matrix set to zero / copied (nclass * nclass uint64) into a caller's DEVICE buffer, e.g. for an all-reduce without a host hop */
+int  tdnet_score_reset(tdnet_t* h, void* stream);
+int  tdnet_score_export(tdnet_t* h, uint64_t* cm_dev, void* stream);
+/* synchronises `stream`, then copies the matrix to the host; returns the element count (nclass * nclass), <0 on error (capacity too small) */
+long tdnet_score_read(tdnet_t* h, uint64_t* cm_host, size_t capacity, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -229,6 +255,7 @@ int  tdnet_propagate_labels(tdnet_t* h, int32_t* labels_dev, void* stream);
 int  tdnet_encode_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, void* stream);
 int  tdnet_propagate_labels_u8(tdnet_t* h, uint8_t* labels_dev, void* stream);
 int  tdnet_propagate_rgb(tdnet_t* h, uint8_t* rgb_dev, void* stream);   /* see "colour map out" */
+int  tdnet_propagate_score(tdnet_t* h, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);   /* see "score out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

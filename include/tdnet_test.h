@@ -72,6 +72,12 @@ int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, in
  * ignored).  Index tables and colour table are built by the host function tdnet_set_output_rgb uses; palette [n_colours][3] on the host.          */
 int tdnet_op_upsample_argmax_rgb(const float* in_dev, int C, int h, int w, int H, int W, int oh, int ow, const uint8_t* palette, int n_colours,
                                  uint8_t* rgb_dev, const uint8_t* labels_u8_dev, void* stream);
+/* cm_dev [C,C] uint64 -- ACCUMULATED into, not cleared -- += the confusion counts (include/tdnet.h "score out") of gt_dev [H,W] uint8 (any byte
+ * address) through gt_map (256 bytes on the host, NULL = identity) against the labels of low-resolution logits [C,h,w] upsampled to [H,W], through
+ * tdnet_forward_score's last kernel (labels_in_u8_dev == NULL; it also writes the uint8 label map if labels_u8_dev != NULL), or against a uint8
+ * label map [H,W] through tdnet_labels_score's kernel (labels_in_u8_dev != NULL; in_dev, h, w and labels_u8_dev are then ignored).  C in 1..256. */
+int tdnet_op_upsample_argmax_score(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* gt_dev, const uint8_t* gt_map, uint8_t* labels_u8_dev,
+                                   uint64_t* cm_dev, const uint8_t* labels_in_u8_dev, void* stream);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

@@ -9,6 +9,7 @@
 //                  a switch on the layer's planned route
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
 //   td_ingest.h    (kernels) uint8 image in, uint8 labels out, colour map out; the host side of their tables is at the end of this file
+//   td_score.h     (kernels) score out: the confusion matrix against ground truth; its host side is at the end of this file too
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -28,6 +29,7 @@
 #include "td_attn_b3.h"
 #include "td_misc.h"
 #include "td_ingest.h"
+#include "td_score.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -237,6 +239,16 @@ struct RgbOutput {
     unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16
     size_t bytes = 0;
 };
+// The score output of a handle (tdnet_set_score): the device confusion matrix the score kernels add into and the 256-byte ground-truth map they
+// read.  Per handle, like U8Input.
+struct ScoreOutput {
+    bool set = false;
+    int nclass = 0;
+    unsigned char map[256] = {0};                                      // the caller's (identity for NULL), kept to recognise an equal call
+    unsigned long long* cm = nullptr;                                  // [nclass][nclass] counts
+    unsigned char* dmap = nullptr;                                     // [256]
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -318,6 +330,7 @@ struct tdnet {
     size_t nrec = 0;
     U8Input u8;                                                        // tdnet_set_input_u8
     RgbOutput rgb;                                                     // tdnet_set_output_rgb
+    ScoreOutput score;                                                 // tdnet_set_score
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
     explicit tdnet(TdWeights* w)
@@ -478,5 +491,33 @@ static int rgb_build(RgbOutput& r, int H, int W, int oh, int ow, const unsigned 
     v.set = true;
     rgb_free(r);
     r = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// score output: the host side of td_score.h's k_upsample_argmax_score / k_labels_score
+// ---------------------------------------------------------------------------------------------------------------
+static void score_free(ScoreOutput& c) {
+    if (c.cm) hipFree(c.cm);
+    if (c.dmap) hipFree(c.dmap);
+    c = ScoreOutput();
+}
+static void score_map_or_identity(const unsigned char* gt_map, unsigned char* out) {
+    for (int i = 0; i < 256; ++i) out[i] = gt_map ? gt_map[i] : (unsigned char)i;
+}
+// Allocate the zeroed matrix and upload the 256-byte map (gt_map == NULL: identity) into memory `c` owns.  On failure `c` is left as it was.
+static int score_build(ScoreOutput& c, int nclass, const unsigned char* gt_map, const char* who) {
+    if (nclass < 1 || nclass > 256) return td_fail("%s: nclass = %d must be in 1..256", who, nclass);
+    ScoreOutput v;
+    v.nclass = nclass;
+    score_map_or_identity(gt_map, v.map);
+    const size_t bins = (size_t)nclass * nclass;
+    if (dev_alloc(&v.cm, bins) || dev_alloc(&v.dmap, 256)) { score_free(v); return -1; }
+    if (hipMemset(v.cm, 0, bins * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemcpy(v.dmap, v.map, 256, hipMemcpyHostToDevice) != hipSuccess) { score_free(v); return td_fail("%s: matrix / map upload failed", who); }
+    v.bytes = bins * sizeof(unsigned long long) + 256;
+    v.set = true;
+    score_free(c);
+    c = v;
     return 0;
 }

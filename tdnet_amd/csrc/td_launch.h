@@ -367,3 +367,29 @@ static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, un
               r.W, r.oh, r.ow);
     return 0;
 }
+// score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be
+// NULL) or from a uint8 label map the caller holds.  A private LDS histogram per workgroup up to TD_SCORE_LDS_CLASSES classes, straight
+// global atomics above.  The wave-uniform path is OFF in the library's entries until tools/score_probe.py has shown on the device that it
+// pays on coherent input and costs nothing on noise (not measured yet); the tests' operator entry can run either form.
+#define TD_SCORE_WAVE_UNIFORM false
+static int score_lds_bins(int C) { return C <= TD_SCORE_LDS_CLASSES ? C * C : 0; }
+static int launch_upsample_argmax_score(const float* in, int C, int h, int w, int H, int W, const unsigned char* gt, const unsigned char* map,
+                                        unsigned char* labels, unsigned long long* cm, hipStream_t s, bool uniform = TD_SCORE_WAVE_UNIFORM) {
+    if (H > 65535) return td_fail("score: H = %d is above the grid's 65535 rows", H);
+    if (C < 1 || C > 256) return td_fail("score: nclass = %d must be in 1..256", C);
+    const int bins = score_lds_bins(C);
+    const dim3 grid((W / 4 + 2 + 255) / 256, H);
+    if (uniform) TD_LAUNCH((k_upsample_argmax_score<true>), grid, dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
+    else TD_LAUNCH((k_upsample_argmax_score<false>), grid, dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
+    return 0;
+}
+static int launch_labels_score(const unsigned char* labels, int C, int H, int W, const unsigned char* gt, const unsigned char* map, unsigned long long* cm,
+                               hipStream_t s, bool uniform = TD_SCORE_WAVE_UNIFORM) {
+    if (H > 65535) return td_fail("score: H = %d is above the grid's 65535 rows", H);
+    if (C < 1 || C > 256) return td_fail("score: nclass = %d must be in 1..256", C);
+    const int bins = score_lds_bins(C);
+    const dim3 grid((W / 4 + 2 + 255) / 256, H);
+    if (uniform) TD_LAUNCH((k_labels_score<true>), grid, dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
+    else TD_LAUNCH((k_labels_score<false>), grid, dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
+    return 0;
+}

@@ -143,6 +143,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     if (n->vt16) hipFree(n->vt16);
     u8_free(n->u8);
     rgb_free(n->rgb);
+    score_free(n->score);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -337,6 +338,77 @@ extern "C" int tdnet_labels_rgb(tdnet_t* n, const uint8_t* labels, uint8_t* rgb,
     TD_HIP(hipGetLastError());
     return 0;
 }
+// ---- score out -------------------------------------------------------------------------------------------------------------------------
+// Configuration of the score output (not a frame call: it may synchronise; idempotent for an equal map).  The matrix and the map live in memory
+// this handle owns; a tdnet_create_shared handle has its own.  A DIFFERENT map starts a new, zeroed matrix: counts folded two ways do not mix.
+extern "C" int tdnet_set_score(tdnet_t* n, const uint8_t* gt_map) {
+    if (!n) return td_fail("tdnet_set_score: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_score: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    unsigned char m[256];
+    score_map_or_identity(gt_map, m);
+    if (n->score.set && memcmp(n->score.map, m, 256) == 0) return 0;
+    if (n->score.set) TD_HIP(hipDeviceSynchronize());                 // a frame in flight may still add into the matrix that is about to go
+    const size_t before = n->score.bytes;
+    TD_TRY(score_build(n->score, n->cfg.nclass, gt_map, "tdnet_set_score"));
+    n->ws_bytes += n->score.bytes - before;
+    return 0;
+}
+#define TD_NEED_SCORE(n, who) do { if (!(n)->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who); } while (0)
+// The labels entries with another last launch: the frame's counts added to the handle's matrix, the label map written too if asked for.  Same
+// frame, same FIFO step, same number of launches.
+static int forward_score(tdnet* n, const FrameInput& in, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream, const char* who) {
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, who);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (forward_lowres(n, in, pos_id, s, who)) return -1;
+    prof_begin(n, 2, false, 0, s);
+    const int rc = launch_upsample_argmax_score(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, gt, n->score.dmap, labels, n->score.cm, s);
+    prof_end(n, s);
+    TD_HIP(hipGetLastError());
+    return rc;
+}
+extern "C" int tdnet_forward_score(tdnet_t* n, const float* img, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream) {
+    if (!n || !img || !gt) return td_fail("tdnet_forward_score: null argument");
+    return forward_score(n, frame_input_f32(img), pos_id, gt, labels, stream, "tdnet_forward_score");
+}
+extern "C" int tdnet_forward_u8_score(tdnet_t* n, const uint8_t* img, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream) {
+    if (!n || !img || !gt) return td_fail("tdnet_forward_u8_score: null argument");
+    return forward_score(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, gt, labels, stream, "tdnet_forward_u8_score");
+}
+extern "C" int tdnet_labels_score(tdnet_t* n, const uint8_t* labels, const uint8_t* gt, void* stream) {
+    if (!n || !labels || !gt) return td_fail("tdnet_labels_score: null argument");
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, "tdnet_labels_score");
+    TD_TRY(launch_labels_score(labels, n->cfg.nclass, n->H, n->W, gt, n->score.dmap, n->score.cm, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_score_reset(tdnet_t* n, void* stream) {
+    if (!n) return td_fail("tdnet_score_reset: null handle");
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, "tdnet_score_reset");
+    TD_HIP(hipMemsetAsync(n->score.cm, 0, (size_t)n->score.nclass * n->score.nclass * sizeof(unsigned long long), (hipStream_t)stream));
+    return 0;
+}
+extern "C" int tdnet_score_export(tdnet_t* n, uint64_t* cm_dev, void* stream) {
+    if (!n || !cm_dev) return td_fail("tdnet_score_export: null argument");
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, "tdnet_score_export");
+    TD_HIP(hipMemcpyAsync(cm_dev, n->score.cm, (size_t)n->score.nclass * n->score.nclass * sizeof(unsigned long long), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+extern "C" long tdnet_score_read(tdnet_t* n, uint64_t* cm_host, size_t capacity, void* stream) {
+    if (!n || !cm_host) return td_fail("tdnet_score_read: null argument");
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, "tdnet_score_read");
+    const size_t count = (size_t)n->score.nclass * n->score.nclass;
+    if (capacity < count) return td_fail("tdnet_score_read: capacity %zu < %zu", capacity, count);
+    TD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    TD_HIP(hipMemcpy(cm_host, n->score.cm, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return (long)count;
+}
 // ---- split frame + cache transport (path-parallel single stream) ------------------------------------
 // Rank g of a path-parallel group serves the frames t = g (mod W): it encodes its frame as soon as the image is there, publishes
 // the resulting cache entry, receives the entries of the frames in between from its peers (in frame order) and only then
@@ -413,6 +485,17 @@ extern "C" int tdnet_propagate_rgb(tdnet_t* n, uint8_t* rgb, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (propagate_lowres(n, s)) return -1;
     TD_TRY(launch_upsample_argmax_rgb(n->lowres, n->cfg.nclass, n->h, n->w, n->rgb, rgb, s));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_propagate_score(tdnet_t* n, const uint8_t* gt, uint8_t* labels, void* stream) {
+    if (!n || !gt) return td_fail("tdnet_propagate_score: null argument");
+    TD_ON_DEVICE(n, -1);
+    TD_NEED_SCORE(n, "tdnet_propagate_score");
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (propagate_lowres(n, s)) return -1;
+    TD_TRY(launch_upsample_argmax_score(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, gt, n->score.dmap, labels, n->score.cm, s));
     TD_HIP(hipGetLastError());
     return 0;
 }

@@ -225,6 +225,30 @@ extern "C" int tdnet_op_upsample_argmax_rgb(const float* in, int C, int h, int w
     rgb_free(r);
     return rc;
 }
+// cm_dev [C][C] (uint64, ACCUMULATED into, not cleared) += the confusion counts of ground truth gt [H][W] (through gt_map, 256 bytes on the host,
+// NULL = identity) against the labels of low-resolution logits [C][h][w] (labels_in == NULL: k_upsample_argmax_score, which also writes the uint8
+// label map if labels_u8 != NULL) or against a uint8 label map [H][W] (labels_in != NULL: k_labels_score; in, h, w, labels_u8 are ignored).
+// TDNET_SCORE_WAVE_UNIFORM=1 / 0 in the environment (tools/score_probe.py) runs the kernels with / without their wave-uniform path; unset: the
+// form the library's own entries launch.
+extern "C" int tdnet_op_upsample_argmax_score(const float* in, int C, int h, int w, int H, int W, const uint8_t* gt, const uint8_t* gt_map, uint8_t* labels_u8,
+                                              uint64_t* cm, const uint8_t* labels_in, void* stream) {
+    if (!gt || !cm) return td_fail("tdnet_op_upsample_argmax_score: gt and cm expected");
+    if (C < 1 || C > 256 || H < 1 || W < 1) return td_fail("tdnet_op_upsample_argmax_score: C in 1..256 and a size >= 1 x 1 expected");
+    if (!labels_in && (!in || h < 1 || w < 1)) return td_fail("tdnet_op_upsample_argmax_score: logits [C,h,w] expected");
+    const char* env = getenv("TDNET_SCORE_WAVE_UNIFORM");
+    const bool uniform = env && *env ? atoi(env) != 0 : TD_SCORE_WAVE_UNIFORM;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char m[256], *dmap = nullptr;
+    score_map_or_identity(gt_map, m);
+    TD_TRY(dev_alloc(&dmap, 256));
+    int rc = 0;
+    if (hipMemcpy(dmap, m, 256, hipMemcpyHostToDevice) != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_score: map upload failed");
+    if (!rc) rc = labels_in ? launch_labels_score(labels_in, C, H, W, gt, dmap, (unsigned long long*)cm, s, uniform)
+                            : launch_upsample_argmax_score(in, C, h, w, H, W, gt, dmap, labels_u8, (unsigned long long*)cm, s, uniform);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_score: device error");
+    hipFree(dmap);
+    return rc;
+}
 // The index table the colour-map kernels sample through (rgb_build's: dataloader.nearest_index restated in C) -> out_host [n_dst] int32.  Host only.
 extern "C" int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host) {
     if (n_src < 1 || n_dst < 1 || !out_host) return td_fail("tdnet_op_nearest_index: sizes >= 1 and a host buffer expected");

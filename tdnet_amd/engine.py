@@ -146,6 +146,46 @@ class Engine:
     def labels_rgb(self, labels_ptr, rgb_ptr, stream=None):
         self.lib.check(self.lib.tdnet_labels_rgb(self.h, _ptr(labels_ptr), _ptr(rgb_ptr), stream))
 
+    # ---- score out (include/tdnet.h) ----
+    def set_score(self, gt_map=None):
+        """Frames may be scored against ground truth: allocates this handle's zeroed confusion matrix.  gt_map: 256 byte values (ground-truth byte ->
+        class, anything >= nclass = ignore), None = identity.  A configuration call (it may synchronise); repeating it with an equal map does nothing."""
+        m = None if gt_map is None else np.ascontiguousarray(np.asarray(gt_map).astype(np.uint8, casting="unsafe"))
+        if m is not None and (m.shape != (256,) or not np.array_equal(m, np.asarray(gt_map))):
+            raise _capi.TdnetError("set_score: gt_map is 256 values in 0..255")
+        key = (None if m is None else m.tobytes(),)
+        if getattr(self, "_score_key", None) == key:
+            return
+        self.lib.check(self.lib.tdnet_set_score(self.h, None if m is None else m.ctypes.data))
+        self._score_key = key
+
+    def forward_score(self, img_ptr, pos_id, gt_ptr, labels_ptr=None, stream=None):
+        self.lib.check(self.lib.tdnet_forward_score(self.h, _ptr(img_ptr), int(pos_id), _ptr(gt_ptr), _ptr(labels_ptr), stream))
+
+    def forward_u8_score(self, img_ptr, pos_id, gt_ptr, labels_ptr=None, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_score(self.h, _ptr(img_ptr), int(pos_id), _ptr(gt_ptr), _ptr(labels_ptr), stream))
+
+    def propagate_score(self, gt_ptr, labels_ptr=None, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_score(self.h, _ptr(gt_ptr), _ptr(labels_ptr), stream))
+
+    def labels_score(self, labels_ptr, gt_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_labels_score(self.h, _ptr(labels_ptr), _ptr(gt_ptr), stream))
+
+    def score_reset(self, stream=None):
+        self.lib.check(self.lib.tdnet_score_reset(self.h, stream))
+
+    def score_export(self, cm_ptr, stream=None):
+        """Enqueue a copy of the nclass x nclass uint64 counts into a device buffer of the caller's."""
+        self.lib.check(self.lib.tdnet_score_export(self.h, _ptr(cm_ptr), stream))
+
+    def score_read(self, stream=None):
+        """The counts as uint64 [nclass, nclass] on the host (synchronises `stream`)."""
+        n = self.cfg.nclass
+        out = np.zeros((n, n), np.uint64)
+        got = self.lib.check(self.lib.tdnet_score_read(self.h, out.ctypes.data, out.size, stream))
+        assert got == out.size, (got, out.size)
+        return out
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

@@ -410,6 +410,95 @@ class _TDNetBase(nn.Module):
             self._engine.labels_rgb(labels[i].data_ptr(), out[i].data_ptr(), s)
         return out
 
+    # ---- score out (not in the reference's model; its validation loop counts on the host, Training/validate.py:59-70) -----------------------
+    # The frame's last kernel adds the frame's confusion counts against gt_u8 -- uint8 [N, H, W] at the NETWORK size, CUDA -- to a matrix each
+    # handle owns (a batch is N handles: confusion_matrix() sums them).  gt_map: 256 values (ground-truth byte -> class id, >= nclass = ignore),
+    # None = identity.  return_labels: also return the uint8 label map [N, H, W] (the labels forward_labels_u8 gives).
+    @staticmethod
+    def _check_gt_type(gt):
+        if not torch.is_tensor(gt) or gt.dtype != torch.uint8 or gt.dim() != 3:
+            raise RuntimeError("expected the ground truth gt as a torch.uint8 tensor [N, H, W], got %s"
+                               % ("%s %s" % (gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt).__name__))
+
+    def _check_gt(self, gt, n, H, W, device):
+        self._check_gt_type(gt)
+        if tuple(gt.shape) != (n, H, W):
+            raise RuntimeError("expected the ground truth gt as a torch.uint8 tensor [%d, %d, %d] at the network size, got %s"
+                               % (n, H, W, tuple(gt.shape)))
+        if gt.device != device:
+            raise RuntimeError("the ground truth gt must be on the frame's device %s, got %s" % (device, gt.device))
+        return gt.contiguous()
+
+    def forward_score(self, img, gt_u8, pos_id=0, gt_map=None, return_labels=False):
+        """forward_labels() with the frame scored on the device: returns the uint8 labels [N, H, W] if return_labels, else None."""
+        self._check_gt_type(gt_u8)
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        gt = self._check_gt(gt_u8, img.shape[0], img.shape[2], img.shape[3], img.device)
+        out = torch.empty((img.shape[0], img.shape[2], img.shape[3]), device=img.device, dtype=torch.uint8) if return_labels else None
+
+        def one(i, eng, s):
+            eng.set_score(gt_map)
+            eng.forward_score(img[i].data_ptr(), pos_id, gt[i].data_ptr(), None if out is None else out[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out
+
+    def forward_score_u8(self, img_u8, gt_u8, pos_id=0, in_size=None, gt_map=None, return_labels=False, mean=None, std=None):
+        """forward_labels_u8() with the frame scored on the device: bytes in, counts added; the uint8 labels [N, H, W] if return_labels."""
+        self._check_gt_type(gt_u8)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        gt = self._check_gt(gt_u8, img.shape[0], H, W, img.device)
+        out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8) if return_labels else None
+
+        def one(i, eng, s):
+            eng.set_score(gt_map)
+            eng.forward_u8_score(img[i].data_ptr(), pos_id, gt[i].data_ptr(), None if out is None else out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std)
+        return out
+
+    def score_labels(self, labels_u8, gt_u8, gt_map=None):
+        """The unfused form: uint8 labels [N, H, W] (CUDA) of this model counted against gt_u8, sample i on handle i."""
+        if self._engine is None:
+            raise RuntimeError("score_labels(): no handle yet")
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != (H, W):
+            raise RuntimeError("score_labels(): expected uint8 labels [N, %d, %d]" % (H, W))
+        labels = labels_u8.contiguous()
+        gt = self._check_gt(gt_u8, labels.shape[0], H, W, labels.device)
+        engines = [self._engine] + list(self._extra_engines)
+        if labels.shape[0] > len(engines):
+            raise RuntimeError("score_labels(): %d label maps but %d handle(s)" % (labels.shape[0], len(engines)))
+        s = torch.cuda.current_stream(labels.device).cuda_stream
+        for i in range(labels.shape[0]):
+            engines[i].set_score(gt_map)
+            engines[i].labels_score(labels[i].data_ptr(), gt[i].data_ptr(), s)
+
+    def _score_engines(self, who):
+        if self._engine is None:
+            raise RuntimeError("%s(): no handle yet" % who)
+        return [e for e in [self._engine] + list(self._extra_engines) if getattr(e, "_score_key", None) is not None]
+
+    def confusion_matrix(self):
+        """int64 numpy [nclass, nclass]: the counts of every frame scored since the last reset_score(), summed over the batch's handles
+        (synchronises the current stream)."""
+        total = np.zeros((self.nclass, self.nclass), np.int64)
+        for e in self._score_engines("confusion_matrix"):
+            total += e.score_read(torch.cuda.current_stream(self._engine_key[2]).cuda_stream).astype(np.int64)
+        return total
+
+    def get_scores(self):
+        """The reference's runningScore.get_scores() of confusion_matrix(): ({overall / mean / frequency-weighted accuracy, mean IoU}, {class: IoU})."""
+        from ..metrics import runningScore
+        rs = runningScore(self.nclass)
+        rs.add_counts(self.confusion_matrix())
+        return rs.get_scores()
+
+    def reset_score(self):
+        """Zero the matrices (enqueued on the current stream)."""
+        for e in self._score_engines("reset_score"):
+            e.score_reset(torch.cuda.current_stream(self._engine_key[2]).cuda_stream)
+
     # ---- split frame + cache transport (path-parallel single stream: parallel.PathParallelStream) ------------------
     def encode(self, img, pos_id=0):
         """First half of forward(): backbone + pyramid slice + Encoding; the frame's cache entry is left pending."""
@@ -421,13 +510,22 @@ class _TDNetBase(nn.Module):
         self._pending_shape = (img.shape[2], img.shape[3], img.device)
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
-    def propagate(self, labels=False, out_size=None, palette=None):
+    def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None):
         """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
-        uint8 labels (labels="u8") or the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb)."""
+        uint8 labels (labels="u8"), the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb) or, with
+        labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score)."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
-        if isinstance(labels, str) and labels not in ("u8", "rgb"):
-            raise RuntimeError("propagate(): labels must be False, True, \"u8\" or \"rgb\"")
+        if isinstance(labels, str) and labels not in ("u8", "rgb", "score"):
+            raise RuntimeError("propagate(): labels must be False, True, \"u8\", \"rgb\" or \"score\"")
+        if labels == "score":
+            H, W, dev = self._pending_shape
+            gt = self._check_gt(gt, 1, H, W, dev)
+            out = torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+            self._engine.set_score(gt_map)
+            self._pending_shape = None
+            self._engine.propagate_score(gt.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
         if labels == "rgb" and out_size is None:
             raise RuntimeError("propagate(labels=\"rgb\"): out_size=(oh, ow) is required")
         H, W, dev = self._pending_shape

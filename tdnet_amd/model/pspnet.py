@@ -53,3 +53,9 @@ class pspnet(_TDNetBase):
 
     def forward_rgb_u8(self, x, pos_id=None, in_size=None, out_size=None, **kw):
         return super().forward_rgb_u8(x[-1:], 0, in_size, out_size, **kw)
+
+    def forward_score(self, x, gt_u8, pos_id=None, **kw):
+        return super().forward_score(x[-1:], gt_u8[-1:], 0, **kw)
+
+    def forward_score_u8(self, x, gt_u8, pos_id=None, in_size=None, **kw):
+        return super().forward_score_u8(x[-1:], gt_u8[-1:], 0, in_size, **kw)

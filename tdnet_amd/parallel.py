@@ -165,6 +165,22 @@ def allreduce_sum(t):
     return t
 
 
+def allreduce_score(model):
+    """The clip's confusion matrix summed over the ranks without a host hop: every handle of `model` copies its counts into a device buffer
+    (tdnet_score_export, enqueued on the current stream), the buffers are added up as int64 and all-reduced with SUM; returns the int64 CUDA
+    tensor [nclass, nclass] (the same on every rank).  The counts fit int64: they are pixel counts.  The host path (the labels downloaded and
+    counted with oracle/tdnet_ref.confusion_miou, then allreduce_sum) stays what bench.py uses."""
+    dev = torch.device("cuda", model._engine_key[2])
+    n = model.nclass
+    total = torch.zeros((n, n), dtype=torch.int64, device=dev)
+    buf = torch.empty((n, n), dtype=torch.int64, device=dev)           # uint64 counts below 2^63 read as int64
+    s = torch.cuda.current_stream(dev).cuda_stream
+    for e in model._score_engines("allreduce_score"):
+        e.score_export(buf.data_ptr(), s)
+        total += buf
+    return allreduce_sum(total)
+
+
 def allreduce_max(t):
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

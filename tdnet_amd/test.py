@@ -12,6 +12,10 @@ test.py:24) must match the checkpoint's LayerNorm shape exactly as in the refere
 library resizes and normalises them on the device, bit-identically to the loader) and, with `--prefetch`, is the all-bytes loop: uint8
 upload, forward_labels_u8, uint8 label download; `--rgb` has the frame's last kernel write the quarter-size colour map itself (the nearest
 sample of the label map and decode_segmap, byte for byte): the host downloads the picture and encodes the PNG, nothing else.
+`--gt_path DIR` scores the clip against ground truth on the device (single-channel PNGs named like the frames, sampled to `--in_size` with the
+nearest rule when their size differs; `--gt_map FILE`: 256 integers as text, ground-truth byte -> class id, anything >= 19 ignored; default
+identity): the frame's last kernel counts the confusion matrix, and the four scores and the per-class IoU are printed after the timing block
+as Training/validate.py:91-97 prints them.
 """
 import argparse
 import os
@@ -19,6 +23,27 @@ import timeit
 
 import numpy as np
 import torch
+
+
+def load_ground_truth(gt_path, items, size, nearest_index, pin):
+    """One [gt uint8 [1, H, W]] item per frame of `items` ([image, name, folder, size]): the single-channel PNG gt_path/folder/name (or
+    gt_path/name), sampled to size = (H, W) with the label map's nearest rule when its size differs."""
+    from PIL import Image
+    H, W = size
+    out = []
+    for _, img_name, folder, _ in items:
+        path = os.path.join(gt_path, folder, img_name)
+        if not os.path.exists(path):
+            path = os.path.join(gt_path, img_name)
+        im = Image.open(path)
+        if im.mode not in ("L", "P"):
+            raise SystemExit("--gt_path: %s is not a single-channel 8-bit PNG (mode %s)" % (path, im.mode))
+        g = np.array(im, dtype=np.uint8)
+        if g.shape != (H, W):
+            g = g[nearest_index(g.shape[0], H)][:, nearest_index(g.shape[1], W)]
+        t = torch.from_numpy(np.ascontiguousarray(g)[np.newaxis])
+        out.append([t.pin_memory() if pin else t])
+    return out
 
 
 def test(args):
@@ -47,6 +72,25 @@ def test(args):
         raise SystemExit("model must be one of td4-psp18, td2-psp50, td2-psp18, td2-psp34, psp101")
     model.eval()
     model.to(device)
+    gts, gt_map = None, None
+    if getattr(args, "gt_path", None):
+        if rgb:
+            raise SystemExit("--gt_path and --rgb ask for two different last kernels: choose one")
+        gts = load_ground_truth(args.gt_path, vid_seq.data, (H, W), nearest_index, getattr(args, "prefetch", False))
+        if getattr(args, "gt_map", None):
+            gt_map = np.array(open(args.gt_map).read().split(), dtype=np.int64)
+            if gt_map.shape != (256,) or gt_map.min() < 0 or gt_map.max() > 255:
+                raise SystemExit("--gt_map: 256 integers in 0..255 expected, got %d" % gt_map.size)
+            gt_map = gt_map.astype(np.uint8)
+
+    def print_scores():                                                # Training/validate.py:91-97
+        if gts is None:
+            return
+        score, class_iou = model.get_scores()
+        for k, v in score.items():
+            print(k, v)
+        for c in range(model.nclass):
+            print(c, class_iou[c])
 
     def write_png(picture, img_name, folder):
         save_dir = os.path.join(args.output_path, folder)
@@ -78,8 +122,15 @@ def test(args):
             down = LabelDownloader(device)
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
+            gt_feed = iter(DevicePrefetcher(gts, device)) if gts is not None else None   # the ground truth travels with the frame
             for i, (image, img_name, folder, ori_size) in enumerate(DevicePrefetcher(vid_seq.data, device)):
-                if rgb:
+                if gt_feed is not None:
+                    gt = next(gt_feed)[0]
+                    if u8:
+                        labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
+                    else:
+                        labels = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
+                elif rgb:
                     labels = colour_map(image, i % path_num, ori_size)
                 else:
                     labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
@@ -94,12 +145,18 @@ def test(args):
             if i >= 0:
                 print(" {0:d} frames, prefetched upload + asynchronous labels: {1:3.5f} s per frame including the PNG writer".format(i + 1, timer / (i + 1)))
             print("---------------------")
+            print_scores()
             return
         for i, (image, img_name, folder, ori_size) in enumerate(vid_seq.data):
             image = image.to(device)
+            gt = gts[i][0].to(device) if gts is not None else None
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
-            if rgb:
+            if gt is not None and u8:
+                output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
+            elif gt is not None:
+                output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
+            elif rgb:
                 output = colour_map(image, i % path_num, ori_size)
             else:
                 output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
@@ -107,7 +164,9 @@ def test(args):
             elapsed_time = timeit.default_timer() - start_time
             if i > 5:
                 timer += elapsed_time
-            if rgb:
+            if gt is not None:
+                save(output.cpu().numpy(), img_name, folder, ori_size)
+            elif rgb:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
             else:
                 save(output.data.max(1)[1].cpu().numpy(), img_name, folder, ori_size)
@@ -117,6 +176,7 @@ def test(args):
     if i > 5:
         print(" Average  RunningTime/Latency={0:3.5f} s".format(timer / (i - 5)))
     print("---------------------")
+    print_scores()
 
 
 if __name__ == "__main__":
@@ -133,4 +193,6 @@ if __name__ == "__main__":
     parser.add_argument("--prefetch", action="store_true", help="throughput loop: upload of the next frame under the current one, asynchronous label download")
     parser.add_argument("--u8", action="store_true", help="frames stay uint8 HWC at their source size: resize + normalisation on the device (bit-identical); with --prefetch uint8 labels too")
     parser.add_argument("--rgb", action="store_true", help="the frame's last kernel writes the quarter-size colour map: no label download, resize or decode_segmap on the host")
+    parser.add_argument("--gt_path", nargs="?", type=str, default=None, help="ground-truth PNGs (single channel, named like the frames): score the clip on the device and print the scores")
+    parser.add_argument("--gt_map", nargs="?", type=str, default=None, help="text file of 256 integers: ground-truth byte -> class id (>= 19: ignored); default identity")
     test(parser.parse_args())
