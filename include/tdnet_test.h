@@ -2,6 +2,11 @@
  * tdnet_test.h -- entry points of libtdnet_hip_test.so ONLY: single-operator calls (tests/ check each kernel family against torch fp32 / fp64
  * through them) and tuning probes.  libtdnet_hip_test.so is built from the same sources as the product library plus tdnet_amd/csrc/td_ops_test.h
  * and exports everything include/tdnet.h declares as well; the PRODUCT library libtdnet_hip.so exports none of the names below.
+ *
+ * Every *_dev argument is a tensor of exactly the stated size: an entry reads and writes nothing outside it and asks for no alignment beyond a fresh
+ * allocation's 256 bytes (padding a kernel wants -- the attention's 128-row V', the stem image's border -- is made inside the entry).  tests/opcheck.py's
+ * guarded mems (GuardedNumpyMem / GuardedTorchMem: NaN bands around inputs, a fixed pattern around outputs) hold the entries to that, under the
+ * emulator and on the device (tests/ops_edge_cases.py).
  */
 #ifndef TDNET_TEST_H
 #define TDNET_TEST_H
@@ -54,8 +59,17 @@ int tdnet_op_layernorm_hw(const float* x_dev, int HW, int C, const float* g_dev,
 int tdnet_op_ppm(const float* c4_dev, int h, int w, const float* w_host, const float* b_host, int path_num, int pid,
                  float* z_dev, void* stream);
 /* 1x1 classifier conv (+bias): x NHWC [HW,C] dev, w [NC,C] dev, b [NC] dev -> planar out [NC,HW] dev; the frame's routing by NC
- * (<= 32: k_classifier, 33 .. 256: the class-tiled k_classifier_ct, C <= 512)                                    */
+ * (<= 32: k_classifier, all weights in one workgroup's LDS: (NC * C + 256 * NC) * 4 bytes <= 160 KiB, i.e. C <= 1024 at 32 classes;
+ * 33 .. 256: the class-tiled k_classifier_ct, C <= 512).  C a multiple of 16; anything else is an error before a launch.            */
 int tdnet_op_classifier(const float* x_dev, int HW, int C, const float* w_dev, const float* b_dev, int NC, float* out_dev, void* stream);
+/* The FCN head (td4_psp18.py:295-299): conv3x3 stride 1 (+ bias, act 0 none / 1 ReLU) -> 1x1 classifier (+ bias), planned as a frame plans its head
+ * conv.  in [H,W,Cin] dev; w3_host OIHW [Cout,Cin,3,3], b3_host [Cout] or NULL, cls_w_host [NC,Cout], cls_b_host [NC]; out planar [NC,H*W] dev.
+ * fused = 1: the classifier inside the Winograd output transform (tdnet_opts.fusion bit 262144's kernel) -- an error, with nothing launched, where a
+ * frame would not fuse: the plan is not Winograd (opts), Cout is not 64 or 128, NC > 32, act = 2.  fused = 0: the conv into a temporary hidden
+ * map, then the classifier kernel of tdnet_op_classifier.  The two forms give the same bits.                                                     */
+int tdnet_op_head_cls(const float* in_dev, int H, int W, int Cin, const float* w3_host, const float* b3_host, int Cout, int act,
+                      const float* cls_w_host, const float* cls_b_host, int NC, const tdnet_opts* opts /* NULL = defaults */, int fused,
+                      float* out_dev, void* stream);
 /* bilinear align_corners=True (td4_psp18.py:227): planar [C,h,w] -> [C,H,W]                                       */
 int tdnet_op_upsample(const float* in_dev, int C, int h, int w, int H, int W, float* out_dev, void* stream);
 /* The stem's image buffer -- allocated and zeroed as a handle's workspace does -- filled from an fp32 NCHW image [3,H,W] (img_f32_dev) or from

@@ -130,6 +130,8 @@ TEST_SYMBOLS = {
     "tdnet_op_upsample_argmax_score": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_head_cls": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                         c_void_p, c_void_p, ctypes.c_int, c_opts_p, ctypes.c_int, c_void_p, c_void_p]),
 }
 
 

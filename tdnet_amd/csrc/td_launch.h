@@ -326,9 +326,12 @@ static void run_maxpool(tdnet* n, const float* in, int H, int W, int C, float* o
     prof_end(n, s);
 }
 static int run_classifier(tdnet* n, const float* x, int HW, int C, int NC, const float* wgt, const float* bias, float* out, hipStream_t s) {
-    if (C % 16) return td_fail("classifier: C=%d is not a multiple of 16", C);
+    if (C % 16 || C < 16) return td_fail("classifier: C=%d is not a positive multiple of 16", C);
+    if (NC < 1 || NC > 256) return td_fail("classifier: NC=%d must be in 1..256", NC);
+    // NC <= 32: all [NC][C] weights and the [4][NC][64] reduction in one workgroup's LDS, which ends at a CU's 160 KiB (32 classes: C <= 1024)
+    if (NC <= 32 && !classifier_supports(NC, C)) return td_fail("classifier: NC=%d x C=%d needs %ld bytes of LDS, above a CU's %d", NC, C, classifier_lds(NC, C), TD_CU_LDS_BYTES);
     prof_begin(n, 2, false, 0, s);
-    const int grid = (HW + 63) / 64, lds = (NC * C + 4 * NC * 64) * 4;
+    const int grid = (HW + 63) / 64, lds = (int)classifier_lds(NC, C);
     if (NC <= 19) TD_LAUNCH((k_classifier<19>), dim3(grid), dim3(256), lds, s, x, wgt, bias, out, HW, C, NC);
     else if (NC <= 32) TD_LAUNCH((k_classifier<32>), dim3(grid), dim3(256), lds, s, x, wgt, bias, out, HW, C, NC);
     else {                                                             // 33 .. 256 classes: 32-class tiles, each tile's weights in LDS

@@ -382,6 +382,9 @@ TD_KERNEL void k_ln_apply_h(const float* __restrict__ x, const float* __restrict
 // One workgroup = 64 pixels x 4 channel quarters (one wave each): a lane streams its quarter of its pixel's channels (C bytes,
 // whole cache lines) against the LDS-resident weights, the four partial sums meet in LDS and are added in a fixed order.
 // (One thread per pixel, the first version, left three quarters of the SIMDs without a wave at 128x256: 40 us for 17 MB.)
+constexpr int TD_CU_LDS_BYTES = 160 * 1024;                   // gfx950: the LDS of a CU, and the most one workgroup can ask for
+static inline long classifier_lds(int NC, int C) { return ((long)NC * C + 4l * NC * 64) * 4; }
+static inline bool classifier_supports(int NC, int C) { return NC >= 1 && NC <= 32 && C % 16 == 0 && C >= 16 && classifier_lds(NC, C) <= TD_CU_LDS_BYTES; }
 template <int NC_MAX>
 TD_KERNEL void k_classifier(const float* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
                             float* __restrict__ out, int HW, int C, int NC) {

@@ -168,6 +168,39 @@ extern "C" int tdnet_op_classifier(const float* x, int HW, int C, const float* w
     TD_HIP(hipGetLastError());
     return 0;
 }
+// The FCN head's 3x3 conv (stride 1, dilation 1) and its 1x1 classifier, planned as a frame plans head3.  fused = 1: the classifier inside the Winograd
+// output transform (k_wino4_out_cls through run_conv's ClsArgs; the hidden map is not written); fused = 0: run_conv into a temporary hidden map, then
+// run_classifier.  fused = 1 fails before anything is allocated or launched where a frame would not fuse.
+extern "C" int tdnet_op_head_cls(const float* in, int H, int W, int Cin, const float* w3_host, const float* b3_host, int Cout, int act,
+                                 const float* cls_w_host, const float* cls_b_host, int NC, const tdnet_opts* opts, int fused, float* out,
+                                 void* stream) {
+    if (H < 1 || W < 1 || Cin < 1 || Cout < 1) return td_fail("tdnet_op_head_cls: empty input");
+    if (NC < 1 || NC > 256) return td_fail("tdnet_op_head_cls: NC must be in 1..256");
+    if (act < 0 || act > 2) return td_fail("tdnet_op_head_cls: act must be 0, 1 or 2");
+    if (!w3_host || !cls_w_host || !cls_b_host) return td_fail("tdnet_op_head_cls: w3_host, cls_w_host and cls_b_host expected");
+    const tdnet_opts o = opts_or_default(opts);
+    hipStream_t s = (hipStream_t)stream;
+    ConvLayer L;
+    if (plan_conv(L, Cout, Cin, 3, 1, 1, act, false, (long)H * W, o)) return -1;
+    if (fused && (L.route != CR_WINO || L.chunks != 1 || !wino_out_cls_supports(Cout, NC) || wino_act_general(act)))
+        return td_fail("tdnet_op_head_cls: a frame would not fuse this head (Winograd plan in one chunk, Cout 64 or 128, NC <= 32, act 0 or 1)");
+    float *hidden = nullptr, *cw = nullptr, *cb = nullptr;
+    auto cleanup = [&]() {                                             // one release path, also for the error returns
+        for (float* q : {hidden, cw, cb}) if (q) hipFree(q);
+        free_conv_layer(L);
+    };
+    std::vector<float> w(w3_host, w3_host + (size_t)Cout * Cin * 9), b;
+    if (b3_host) b.assign(b3_host, b3_host + Cout);
+    int rc = 0;
+    if (upload_conv(L, w, b) || upload(&cw, std::vector<float>(cls_w_host, cls_w_host + (size_t)NC * Cout)) ||
+        upload(&cb, std::vector<float>(cls_b_host, cls_b_host + NC)) || dev_alloc(&hidden, (size_t)H * W * Cout)) rc = -1;
+    const ClsArgs ca = {cw, cb, out, NC};
+    if (!rc) rc = run_conv(nullptr, L, in, H, W, nullptr, hidden, s, nullptr, nullptr, nullptr, fused ? &ca : nullptr);
+    if (!rc && !fused) rc = run_classifier(nullptr, hidden, H * W, Cout, NC, cw, cb, out, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_head_cls: device error");
+    cleanup();
+    return rc;
+}
 extern "C" int tdnet_op_upsample(const float* in, int C, int h, int w, int H, int W, float* out, void* stream) {
     launch_upsample(in, C, h, w, H, W, out, (hipStream_t)stream);
     TD_HIP(hipStreamSynchronize((hipStream_t)stream));

@@ -1,5 +1,6 @@
 """Operator-level parity checks shared by the emulator tests (CPU, numpy "HBM") and the GPU tests (torch-ROCm HBM).
-Each check builds seeded inputs, runs ONE C-ABI op, and compares with the same op in plain PyTorch fp32 on CPU."""
+Each check builds seeded inputs, runs ONE C-ABI op, and compares with the same op in plain PyTorch fp32 (or fp64) on CPU.
+The Guarded* mems put every tensor between guard bands and check them in verify() (tests/ops_edge_cases.py)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -40,6 +41,98 @@ class TorchMem:
     @property
     def stream(self):
         return torch.cuda.current_stream().cuda_stream
+
+
+class _Guarded:
+    """Guard bands around every tensor a mem hands out: the tensor is the interior of a larger allocation with GUARD bytes in front and
+    behind (a multiple of 256, so the interior keeps a fresh allocation's 256-byte alignment).  The bands of an input (put) hold quiet
+    NaNs -- an out-of-range read that reaches a result poisons it; one that is discarded is allowed -- and those of an output (empty) a
+    fixed pattern, itself a NaN.  verify() asserts that every band of every tensor handed out since the last verify() still holds its
+    fill bit for bit, and that every output interior is finite and free of the 7e7 fill; then the mem forgets those tensors.  The mem
+    owns the allocations until then: mem.ptr(mem.put(x)) on a temporary stays valid through the kernel call."""
+    GUARD = 4096                     # bytes per band
+    IN_BITS = 0x7FC00000             # quiet NaN
+    OUT_BITS = 0x7FC5A5A5            # a quiet NaN with a payload: a fixed pattern no kernel produces
+    FILL = 7e7
+
+    def __init__(self):
+        self._live = []
+
+    def _new(self, shape, bits, is_out):
+        shape = tuple(int(d) for d in shape)
+        n, g = int(np.prod(shape, dtype=np.int64)), self.GUARD // 4
+        buf = self._words(g + n + g, bits)
+        inner = self._interior(buf, g, n, shape)
+        assert self.ptr(inner) % 256 == 0, "interior lost the allocation's alignment"
+        self._live.append((buf, n, bits, is_out, shape))
+        return inner
+
+    def put(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        t = self._new(a.shape, self.IN_BITS, False)
+        self._store(t, a)
+        return t
+
+    def empty(self, shape):
+        t = self._new(shape, self.OUT_BITS, True)
+        self._store(t, np.float32(self.FILL))
+        return t
+
+    def verify(self, untouched=False):
+        """untouched: the calls since the last verify() were refused -- every output interior must still hold its fill instead."""
+        live, self._live = self._live, []
+        g = self.GUARD // 4
+        for i, (buf, n, bits, is_out, shape) in enumerate(live):
+            words = self._host_words(buf)
+            what = "%s #%d %s" % ("output" if is_out else "input", i, shape)
+            for name, band, base in (("in front of", words[:g], -g), ("behind", words[g + n:], n)):
+                bad = np.flatnonzero(band != bits)
+                assert bad.size == 0, "guard band %s %s overwritten: %d words, the first at element %d (0x%08x)" % (
+                    name, what, bad.size, base + int(bad[0]), int(band[bad[0]]) & 0xFFFFFFFF)
+            if is_out and untouched:
+                assert (words[g:g + n].view(np.float32) == np.float32(self.FILL)).all(), "%s was written by a call that should have launched nothing" % what
+            elif is_out:
+                f = words[g:g + n].view(np.float32)
+                assert np.isfinite(f).all(), "%s: %d non-finite values (a read outside an input reached the result)" % (what, int((~np.isfinite(f)).sum()))
+                assert not (f == np.float32(self.FILL)).any(), "%s: %d elements were never written" % (what, int((f == np.float32(self.FILL)).sum()))
+
+
+class GuardedNumpyMem(_Guarded, NumpyMem):
+    """NumpyMem with guard bands (see _Guarded): for the emulator."""
+    def _words(self, total, bits):
+        raw = np.empty(total + 64, np.int32)
+        off = (-(raw.ctypes.data // 4)) % 64                   # the first 256-byte boundary
+        buf = raw[off:off + total]
+        buf[:] = bits
+        return buf
+
+    def _interior(self, buf, g, n, shape):
+        return buf[g:g + n].view(np.float32).reshape(shape)
+
+    def _store(self, t, a):
+        t[...] = a
+
+    def _host_words(self, buf):
+        return buf
+
+
+class GuardedTorchMem(_Guarded, TorchMem):
+    """TorchMem with guard bands (see _Guarded): device memory."""
+    def _words(self, total, bits):
+        return torch.full((total,), bits, dtype=torch.int32, device="cuda")
+
+    def _interior(self, buf, g, n, shape):
+        return buf[g:g + n].view(torch.float32).view(shape)
+
+    def _store(self, t, a):
+        if np.ndim(a) == 0:
+            t.fill_(float(a))
+        else:
+            t.copy_(torch.from_numpy(a))
+
+    def _host_words(self, buf):
+        torch.cuda.synchronize()
+        return buf.cpu().numpy()
 
 
 def conv(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed=0, tol=1e-4, opts=None):
@@ -163,6 +256,35 @@ def layernorm(lib, mem, HW, C, seed=0, tol=1e-4):
     err = float(np.abs(mem.get(out) - ref).max())
     assert err <= tol, ("layernorm", HW, C, err)
     return err
+
+
+def layernorm_flat(lib, mem, HW, C, mean, std, seed=0, factor=4.0):
+    """The plane LayerNorm on nearly constant planes (N(mean, std) with std << mean: what the head normalises when the residual is small),
+    against an fp64 evaluation.  There the variance is of eps's order and far below mean^2, so a kernel that drops eps or forms a one-pass
+    E[x^2] - E[x]^2 is wrong by orders of magnitude -- which opcheck.layernorm's N(1, 3) planes do not show.  The input's own fp32 rounding
+    sets the achievable error, so the gate is relative to it: the kernel's max error may be `factor` times that of F.layer_norm in fp32 on
+    the CPU on the same input (the factor test_gpu_model grants over the CPU path's own error).  The check first proves that the case
+    discriminates: the same fp64 formula without eps is off by more than 100 gates.  Returns kernel error / CPU fp32 error."""
+    g = np.random.default_rng(seed)
+    x = (g.standard_normal((HW, C)) * std + mean).astype(np.float32)
+    gg = g.uniform(0.5, 1.5, HW).astype(np.float32)
+    bb = g.standard_normal(HW).astype(np.float32)
+    x64 = x.astype(np.float64)
+    mu, var = x64.mean(0), x64.var(0)
+    aff = lambda z: z * gg.astype(np.float64)[:, None] + bb.astype(np.float64)[:, None]
+    ref = aff((x64 - mu) / np.sqrt(var + 1e-5))
+    no_eps = aff((x64 - mu) / np.sqrt(var))
+    cpu = F.layer_norm(torch.from_numpy(x).T.contiguous(), (HW,), torch.from_numpy(gg), torch.from_numpy(bb), 1e-5).T.numpy()
+    cpu_err = float(np.abs(cpu - ref).max())
+    gate = factor * cpu_err
+    sep = float(np.abs(no_eps - ref).max())
+    assert cpu_err > 0 and sep > 100 * gate, ("layernorm_flat: the case does not discriminate", HW, C, mean, std, sep, gate)
+    dx, dg, db, out = mem.put(x), mem.put(gg), mem.put(bb), mem.empty((HW, C))
+    lib.check(lib.tdnet_op_layernorm_hw(mem.ptr(dx), HW, C, mem.ptr(dg), mem.ptr(db), mem.ptr(out), mem.stream))
+    err = float(np.abs(mem.get(out) - ref).max())
+    print("layernorm_flat HW=%d C=%d mean=%g std=%g: kernel %.3e, CPU fp32 %.3e, ratio %.2f, without eps %.3e" % (HW, C, mean, std, err, cpu_err, err / cpu_err, sep))
+    assert err <= gate, ("layernorm_flat", HW, C, mean, std, err, cpu_err)
+    return err / cpu_err
 
 
 def ppm(lib, mem, h, w, pid, seed=0, tol=1e-4):

@@ -1,0 +1,130 @@
+"""tests/ops_edge_cases.py through the test-only fiber emulator (tests/emu/), numpy arrays with guard bands standing in for HBM: every case is
+proven here before tests/test_gpu_ops_edges.py runs it on the device.  Also the guarded mem itself: it catches a store past an interior
+and a band value that reaches a result.  CPU only."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import emu_util
+import opcheck
+import ops_edge_cases as cases
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return emu_util.emu_lib()
+
+
+@pytest.fixture()
+def mem():
+    return opcheck.GuardedNumpyMem()
+
+
+def test_guarded_mem_catches_what_it_is_for():
+    mem = opcheck.GuardedNumpyMem()
+    x = mem.put(np.arange(6, dtype=np.float32).reshape(2, 3))
+    out = mem.empty((2, 3))
+    assert mem.ptr(x) % 256 == 0 and mem.ptr(out) % 256 == 0 and opcheck.GuardedNumpyMem.GUARD % 256 == 0 and opcheck.GuardedNumpyMem.GUARD >= 4096
+    out[...] = x                                                       # a correct "kernel"
+    mem.verify()
+    assert mem._live == []                                             # the mem forgets what it verified
+    mem.verify()
+
+    def at(t, i):                                                      # the float at element i relative to the interior of t, bands included
+        return np.ctypeslib.as_array((ctypes.c_float * 1).from_address(t.ctypes.data + 4 * i))
+
+    for tensor_of, where in ((mem.empty, 6), (mem.empty, -1), (mem.put, 6), (mem.put, -1)):   # one float past / before an interior, outputs and inputs
+        t = tensor_of((2, 3)) if tensor_of == mem.empty else tensor_of(np.ones((2, 3), np.float32))
+        t[...] = 1.0
+        at(t, where)[0] = 1.0
+        with pytest.raises(AssertionError, match="guard band"):
+            mem.verify()
+    x, out = mem.put(np.ones((2, 3), np.float32)), mem.empty((2, 3))
+    out[...] = x
+    out[1, 2] = at(x, 6)[0]                                       # the result takes in one value from behind the input
+    with pytest.raises(AssertionError, match="non-finite"):
+        mem.verify()
+    out = mem.empty((2, 3))
+    out[0] = 1.0                                                       # half of the output never written
+    with pytest.raises(AssertionError, match="never written"):
+        mem.verify()
+    out = mem.empty((2, 3))
+    mem.verify(untouched=True)
+    out = mem.empty((2, 3))
+    out[0, 0] = 1.0
+    with pytest.raises(AssertionError, match="launched nothing"):
+        mem.verify(untouched=True)
+
+
+@pytest.mark.parametrize("tile", cases.DIRECT_TILES)
+def test_direct_convs(lib, mem, tile):
+    for a in cases.DIRECT_CONVS:
+        cases.direct_conv(lib, mem, a, tile)
+
+
+def test_winograd_convs(lib, mem):
+    for a in cases.WINO_CONVS:
+        cases.wino_conv(lib, mem, a)
+    for a in cases.CHUNKED_CONVS:
+        cases.chunked_conv(lib, mem, a)
+
+
+def test_split_precision_convs_and_stems(lib, mem):
+    for a, opts in cases.SPLIT_CONVS:
+        cases.split_conv(lib, mem, a, opts)
+    for hw in cases.STEMS:
+        for opts in cases.STEM_OPTS:
+            cases.stem(lib, mem, hw, opts)
+
+
+def test_fp16_storage_convs(lib, mem):
+    for a, tiles in cases.F16_CONVS:
+        for tile in tiles:
+            cases.f16_conv(lib, mem, a, tile)
+
+
+def test_ppm_upsample(lib, mem):
+    for hw in cases.PPMS:
+        for pid in (0, 1):
+            cases.ppm(lib, mem, hw, pid)
+    for a in cases.UPSAMPLES:
+        cases.upsample(lib, mem, a)
+
+
+@pytest.mark.parametrize("online", cases.SCHEDULES)
+def test_attention(lib, mem, online):
+    for a in cases.ATTENTIONS:
+        cases.attention(lib, mem, a, online)
+    for a in cases.SLICED_ATTENTIONS:
+        cases.sliced_attention(lib, mem, a, online)
+    for a in cases.WIDE_ATTENTIONS:
+        cases.wide_attention(lib, mem, a, online)
+
+
+@pytest.mark.parametrize("a", cases.CLASSIFIERS)
+def test_classifier(lib, mem, a):
+    cases.classifier(lib, mem, a)
+
+
+def test_classifier_refusals(lib, mem):
+    cases.classifier_refusals(lib, mem)
+
+
+@pytest.mark.parametrize("a", cases.HEADS)
+def test_head_cls(lib, mem, a):
+    cases.head_cls(lib, mem, a)
+
+
+def test_head_cls_refusals(lib, mem):
+    cases.head_cls_refusals(lib, mem)
+
+
+def test_layernorm(lib, mem):
+    for a in cases.LAYERNORMS:
+        cases.layernorm(lib, mem, a)
+
+
+@pytest.mark.parametrize("a", cases.LAYERNORMS_FLAT)
+def test_layernorm_flat(lib, mem, a):
+    cases.layernorm_flat(lib, mem, a)
