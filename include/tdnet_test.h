@@ -38,6 +38,21 @@ int tdnet_op_conv2d(const float* in_dev, int H, int W, int Cin, const float* w_h
  * 32 + (16 .. 29), i.e. 48 .. 61: the same tile staged tap by tap.  20, 23, 24, 29, 30, 33, 36 (removed forms) fail.                              */
 int tdnet_op_conv2d_f16io(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host,
                           int Cout, int KS, int stride, int dil, const float* resid_dev, int act, int tile, float* out_dev, void* stream);
+/* the same conv with the storage of each side chosen -- the forms only the rim of a frame's fp16 backbone reaches.  in16 != 0: in / resid are rounded to
+ * fp16 maps the kernel reads (the residual's type follows the input's), else the kernel reads the fp32 tensors and rounds while staging; out16 != 0: the
+ * kernel writes an fp16 map that is widened into out_dev, else it writes out_dev.  in16 = 0, out16 = 1: a deep stem's second conv; in16 = 1, out16 = 0:
+ * the backbone's last conv (fp16 residual, not in place) and, on the LDS-DMA tile codes and -1, the head conv on the fp16 LayerNorm map.  Tile codes as
+ * tdnet_op_conv2d_f16io; the LDS-DMA ones need in16.                                                                                                  */
+int tdnet_op_conv2d_f16mix(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host,
+                           int Cout, int KS, int stride, int dil, const float* resid_dev, int act, int tile, int in16, int out16, float* out_dev, void* stream);
+/* MaxPool2d(3, stride 2, pad 1) alone (resnet.py:137): NHWC [H,W,C] -> [(H-1)/2+1,(W-1)/2+1,C], C % 4 == 0.  mode 0: the fp32 kernel; 1: fp32 in, fp16 map
+ * out (widened into out_dev): behind the fp32 stem of a tdnet_opts.precision = 1 frame; 2: the input rounded to an fp16 map first, fp16 in and out: behind
+ * the fp16-MFMA stem and the deep stem (C = 128).                                                                                                        */
+int tdnet_op_maxpool(const float* in_dev, int H, int W, int C, int mode, float* out_dev, void* stream);
+/* the stem as a frame of tdnet_opts.precision = 1 runs it: the 7x7 conv on the fp16 MFMA writing an fp16 map, the max-pool reading and writing fp16,
+ * the result widened into out_dev [H2,W2,64].  tile: -1 = the heuristic's, 0..5 forced; a tile the fp16-MFMA stem does not run on (a frame then keeps
+ * the fp32 stem) is an error with nothing allocated or launched.                                                                                        */
+int tdnet_op_stem_f16(const float* img_dev, int H, int W, const float* w_host, const float* bias_host, int tile, float* out_dev, void* stream);
 /* stem: NCHW image [3,H,W] -> conv7x7 s2 p3 (+bias) -> ReLU -> maxpool3x3 s2 p1 -> NHWC [H2,W2,64] (resnet.py:205-208) */
 int tdnet_op_stem(const float* img_dev, int H, int W, const float* w_host, const float* bias_host,
                   const tdnet_opts* opts /* NULL = defaults */, float* out_dev, void* stream);
@@ -55,6 +70,8 @@ int tdnet_op_attention(const float* q_dev, const float* k_dev, const float* vp_d
                        float* ln_out_dev, float* out_dev, void* stream);
 /* LayerNorm over the (h,w) plane of every channel, affine g,b [h*w] shared by channels (td4_psp18.py:306-312); NHWC */
 int tdnet_op_layernorm_hw(const float* x_dev, int HW, int C, const float* g_dev, const float* b_dev, float* out_dev, void* stream);
+/* the same with the map written as fp16 (what the head conv of a tdnet_opts.precision = 1 frame reads), widened into out_dev: half() of the above bit for bit */
+int tdnet_op_layernorm_hw_f16(const float* x_dev, int HW, int C, const float* g_dev, const float* b_dev, float* out_dev, void* stream);
 /* PPM (td4_psp18.py:271-284): c4 NHWC [h,w,512] -> z NHWC [h,w,512]; w_host: 4 folded [128,512] matrices, b_host 4x[128] */
 int tdnet_op_ppm(const float* c4_dev, int h, int w, const float* w_host, const float* b_host, int path_num, int pid,
                  float* z_dev, void* stream);

@@ -27,12 +27,14 @@ extern "C" int tdnet_op_conv2d(const float* in, int H, int W, int Cin, const flo
     free_conv_layer(L);
     return rc;
 }
-// Test entry for the fp16-activation storage of tdnet_opts.precision = 1: the fp32 arguments are rounded to fp16 maps in HBM, the
-// conv runs with fp16 input / residual / output (k_conv_igemm_h<.., IN16, OUT16>), and the fp16 result is widened into out.
-extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
-                                     int KS, int stride, int dil, const float* resid, int act, int tile, float* out, void* stream) {
-    if (KS != 1 && KS != 3) return td_fail("tdnet_op_conv2d_f16io: KS must be 1 or 3");
-    if (Cin % 64) return td_fail("tdnet_op_conv2d_f16io: Cin must be a multiple of 64");
+// The fp16-MFMA conv of tdnet_opts.precision = 1 with the storage a frame gives it: in16: the input and the residual are rounded to fp16 maps in
+// HBM (k_f2h) and the kernel reads those (IN16; the residual's type follows the input's), else it reads the fp32 arguments and rounds while staging;
+// out16: the kernel writes an fp16 map (OUT16) that is widened into out (k_h2f), else it writes out.  The output never aliases the residual.
+static int op_conv2d_h(const char* who, const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
+                       int KS, int stride, int dil, const float* resid, int act, int tile, bool in16, bool out16, float* out, void* stream) {
+    if (KS != 1 && KS != 3) return td_fail("%s: KS must be 1 or 3", who);
+    if (H < 1 || W < 1 || Cout < 1 || stride < 1 || dil < 1) return td_fail("%s: empty input", who);
+    if (Cin < 64 || Cin % 64) return td_fail("%s: Cin must be a multiple of 64", who);
     // tile 16 / 17 / 18 / 19: the LDS-DMA kernel with 128 / 192 / 256-row tiles, 256 x 256 (td_conv_hd.h); 21: 128 rows on two LDS buffers
     // whatever the grid (16 chooses by the grid); 22: 128 rows, eight waves; 25 / 26: 192 / 128 rows on row images with one barrier per K
     // step; 27 / 28: 256 / 192 rows in the early-landing form only; -1: the heuristic (DMA kernel where it applies)
@@ -42,12 +44,13 @@ extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, con
                                          CD_NONE, CD_NONE, CD_192_STEP, CD_128_STEP, CD_256_EARLY, CD_192_EARLY, CD_NONE};   // 23 .. 29
     static const int code_of_tile_p[6] = {CD_128_P, CD_192_P, CD_NONE,         // 31 / 32: row images with four dedicated loader waves (k_conv_dma_h3p)
                                           CD_128_N, CD_192_N, CD_NONE};        // 34 / 35: narrow tiles, rows x 64 channels (k_conv_dma_h3n)
-    if (tile == 30) return td_fail("tdnet_op_conv2d_f16io: tile 30 (the weights-resident 64 -> 64 kernel) was removed in round 5");
+    if (tile == 30) return td_fail("%s: tile 30 (the weights-resident 64 -> 64 kernel) was removed in round 5", who);
     const int force_rh = tile >= 16 && tile <= 29 ? code_of_tile[tile - 16] : tile >= 31 && tile <= 36 ? code_of_tile_p[tile - 31] : 0;
     if (((tile >= 16 && tile <= 29) || (tile >= 31 && tile <= 36)) && !force_rh)
-        return td_fail("tdnet_op_conv2d_f16io: tile %d names an LDS-DMA form that was removed (no frame launches it)", tile);
+        return td_fail("%s: tile %d names an LDS-DMA form that was removed (no frame launches it)", who, tile);
+    if (force_rh && !in16) return td_fail("%s: tile %d is an LDS-DMA form, which reads an fp16 map (in16)", who, tile);
     if (force_rh) tile = CT_128x128_DEEP;
-    if (tile >= CT_COUNT) return td_fail("tdnet_op_conv2d_f16io: tile must be < %d or 16..36 (+ 32 for 16..29)", CT_COUNT);
+    if (tile >= CT_COUNT) return td_fail("%s: tile must be < %d or 16..36 (+ 32 for 16..29)", who, CT_COUNT);
     hipStream_t s = (hipStream_t)stream;
     tdnet_opts o = opts_or_default(nullptr);
     o.precision = 1;
@@ -56,23 +59,87 @@ extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, con
     if (bias_host) b.assign(bias_host, bias_host + Cout);
     const int pad = dil * (KS / 2);
     const int Ho = out_size(H, KS, stride, dil, pad), Wo = out_size(W, KS, stride, dil, pad);
-    // fp16 maps in and out; the LDS-DMA form: the forced one, or for tile -1 by the map's size alone (RH_BY_SIZE -- not the frame's rule), else none
-    if (plan_conv(L, Cout, Cin, KS, stride, dil, act, false, (long)Ho * Wo, o, tile < 0 ? -1 : tile, 1, true, true, force_rh ? force_rh : tile < 0 ? RH_BY_SIZE : CD_NONE, no_rowimg)) return -1;
-    if (force_rh == CD_256x256 && L.CoutPad % 256) return td_fail("tdnet_op_conv2d_f16io: the 256 x 256 tile needs Cout padded to a multiple of 256");
-    if (force_rh && !conv_dma_supports(Cin, Cout, KS, L.tile)) return td_fail("tdnet_op_conv2d_f16io: this shape cannot run on the LDS-DMA kernel");
-    if (upload_conv(L, w, b)) return -1;
+    // the LDS-DMA form of an fp16 input map: the forced one, or for tile -1 by the map's size alone (RH_BY_SIZE -- not the frame's rule), else none
+    if (plan_conv(L, Cout, Cin, KS, stride, dil, act, false, (long)Ho * Wo, o, tile < 0 ? -1 : tile, 1, in16, out16, force_rh ? force_rh : tile < 0 ? RH_BY_SIZE : CD_NONE, no_rowimg)) return -1;
+    if (force_rh == CD_256x256 && L.CoutPad % 256) return td_fail("%s: the 256 x 256 tile needs Cout padded to a multiple of 256", who);
+    if (force_rh && !conv_dma_supports(Cin, Cout, KS, L.tile)) return td_fail("%s: this shape cannot run on the LDS-DMA kernel", who);
     _Float16 *hin = nullptr, *hres = nullptr, *hout = nullptr;
     const long nin = (long)H * W * Cin, nout = (long)Ho * Wo * Cout;
     auto cleanup = [&]() {                                             // one release path, also for the error returns
         for (_Float16* q : {hin, hout, hres}) if (q) hipFree(q);
         free_conv_layer(L);
     };
-    if (dev_alloc(&hin, (size_t)nin) || dev_alloc(&hout, (size_t)nout) || (resid && dev_alloc(&hres, (size_t)nout))) { cleanup(); return -1; }
-    TD_LAUNCH(k_f2h, dim3(td_grid_for(nin)), dim3(256), 0, s, in, hin, nin);
-    if (resid) TD_LAUNCH(k_f2h, dim3(td_grid_for(nout)), dim3(256), 0, s, resid, hres, nout);
-    int rc = run_conv(nullptr, L, (const float*)hin, H, W, (const float*)hres, (float*)hout, s);
-    TD_LAUNCH(k_h2f, dim3(td_grid_for(nout)), dim3(256), 0, s, (const _Float16*)hout, out, nout);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_conv2d_f16io: device error");
+    if (upload_conv(L, w, b) || (in16 && dev_alloc(&hin, (size_t)nin)) || (out16 && dev_alloc(&hout, (size_t)nout)) ||
+        (in16 && resid && dev_alloc(&hres, (size_t)nout))) { cleanup(); return -1; }
+    if (in16) TD_LAUNCH(k_f2h, dim3(td_grid_for(nin)), dim3(256), 0, s, in, hin, nin);
+    if (in16 && resid) TD_LAUNCH(k_f2h, dim3(td_grid_for(nout)), dim3(256), 0, s, resid, hres, nout);
+    int rc = run_conv(nullptr, L, in16 ? (const float*)hin : in, H, W, in16 ? (const float*)hres : resid, out16 ? (float*)hout : out, s);
+    if (out16) TD_LAUNCH(k_h2f, dim3(td_grid_for(nout)), dim3(256), 0, s, (const _Float16*)hout, out, nout);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    cleanup();
+    return rc;
+}
+// Test entry for the fp16-activation storage of tdnet_opts.precision = 1: the fp32 arguments are rounded to fp16 maps in HBM, the
+// conv runs with fp16 input / residual / output (k_conv_igemm_h<.., IN16, OUT16>), and the fp16 result is widened into out.
+extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
+                                     int KS, int stride, int dil, const float* resid, int act, int tile, float* out, void* stream) {
+    return op_conv2d_h("tdnet_op_conv2d_f16io", in, H, W, Cin, w_host, bias_host, Cout, KS, stride, dil, resid, act, tile, true, true, out, stream);
+}
+// The same with the storage of each side chosen: the forms only the rim of a frame's fp16 backbone reaches.  in16 = 0, out16 = 1: the deep stem's second
+// conv; in16 = 1, out16 = 0: the backbone's last conv (fp16 residual, fp32 c4, not in place) and -- on the LDS-DMA tile codes and -1 -- the head conv
+// reading the fp16 LayerNorm map.  The LDS-DMA codes need in16.
+extern "C" int tdnet_op_conv2d_f16mix(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
+                                      int KS, int stride, int dil, const float* resid, int act, int tile, int in16, int out16, float* out, void* stream) {
+    return op_conv2d_h("tdnet_op_conv2d_f16mix", in, H, W, Cin, w_host, bias_host, Cout, KS, stride, dil, resid, act, tile, in16 != 0, out16 != 0, out, stream);
+}
+// MaxPool2d(3, stride 2, pad 1) alone: NHWC [H,W,C] -> [Ho,Wo,C].  mode = run_maxpool's pool16: 0: k_maxpool3s2, fp32 in and out; 1: k_maxpool3s2_h<false>,
+// fp32 in, the fp16 map widened into out; 2: k_maxpool3s2_h<true>, the input rounded to an fp16 map first (k_f2h).
+extern "C" int tdnet_op_maxpool(const float* in, int H, int W, int C, int mode, float* out, void* stream) {
+    if (H < 1 || W < 1 || C < 4 || C % 4) return td_fail("tdnet_op_maxpool: a map of at least 1 x 1 with C a multiple of 4 expected");
+    if (mode < 0 || mode > 2) return td_fail("tdnet_op_maxpool: mode must be 0, 1 or 2");
+    hipStream_t s = (hipStream_t)stream;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long nin = (long)H * W * C, nout = (long)Ho * Wo * C;
+    _Float16 *hin = nullptr, *hout = nullptr;
+    auto cleanup = [&]() { for (_Float16* q : {hin, hout}) if (q) hipFree(q); };
+    if ((mode == 2 && dev_alloc(&hin, (size_t)nin)) || (mode && dev_alloc(&hout, (size_t)nout))) { cleanup(); return -1; }
+    if (mode == 2) TD_LAUNCH(k_f2h, dim3(td_grid_for(nin)), dim3(256), 0, s, in, hin, nin);
+    run_maxpool(nullptr, mode == 2 ? (const float*)hin : in, H, W, C, mode ? (float*)hout : out, s, mode);
+    if (mode) TD_LAUNCH(k_h2f, dim3(td_grid_for(nout)), dim3(256), 0, s, (const _Float16*)hout, out, nout);
+    int rc = 0;
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_maxpool: device error");
+    cleanup();
+    return rc;
+}
+// The stem as a frame of tdnet_opts.precision = 1 runs it: NCHW image -> the 7x7 conv on the fp16 MFMA writing an fp16 map (CR_STEM_H planned with
+// out16) -> k_maxpool3s2_h<true> -> [H2,W2,64] widened into out.  tile: -1 = the heuristic's, else forced; a tile conv_stem_h_supports refuses --
+// where a frame would fall back to the fp32 stem -- is an error before anything is allocated or launched.
+extern "C" int tdnet_op_stem_f16(const float* img, int H, int W, const float* w_host, const float* bias_host, int tile, float* out, void* stream) {
+    if (H < 1 || W < 1) return td_fail("tdnet_op_stem_f16: empty image");
+    if (tile >= CT_COUNT) return td_fail("tdnet_op_stem_f16: tile must be < %d", CT_COUNT);
+    tdnet_opts o = opts_or_default(nullptr);
+    o.precision = 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int H1 = (H - 1) / 2 + 1, W1 = (W - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+    ConvLayer L;
+    if (plan_conv(L, 64, 3, 7, 2, 1, 1, true, (long)H1 * W1, o, tile < 0 ? -1 : tile, 1, false, true)) return -1;
+    if (L.route != CR_STEM_H || !L.out16) return td_fail("tdnet_op_stem_f16: tile %d is not one the fp16-MFMA stem runs on", (int)L.tile);
+    std::vector<float> w(w_host, w_host + 64 * 3 * 49), b;
+    if (bias_host) b.assign(bias_host, bias_host + 64);
+    float* img4 = nullptr;
+    _Float16 *s1 = nullptr, *pooled = nullptr;
+    auto cleanup = [&]() {
+        if (img4) hipFree(img4);
+        for (_Float16* q : {s1, pooled}) if (q) hipFree(q);
+        free_conv_layer(L);
+    };
+    const long nout = (long)H2 * W2 * 64;
+    if (upload_conv(L, w, b) || dev_alloc(&img4, (size_t)H * W * 4) || dev_alloc(&s1, (size_t)H1 * W1 * 64) || dev_alloc(&pooled, (size_t)nout)) { cleanup(); return -1; }
+    run_stem_pre(nullptr, frame_input_f32(img), H, W, img4, s, false);
+    int rc = run_conv(nullptr, L, img4, H, W, nullptr, (float*)s1, s);
+    run_maxpool(nullptr, (const float*)s1, H1, W1, 64, (float*)pooled, s, 2);
+    TD_LAUNCH(k_h2f, dim3(td_grid_for(nout)), dim3(256), 0, s, (const _Float16*)pooled, out, nout);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_f16: device error");
     cleanup();
     return rc;
 }
@@ -141,6 +208,25 @@ extern "C" int tdnet_op_layernorm_hw(const float* x, int HW, int C, const float*
     TD_HIP(hipGetLastError());
     hipFree(part); hipFree(mean); hipFree(rstd);
     return 0;
+}
+// The plane LayerNorm writing its map as fp16 (run_layernorm with y16: k_ln_apply_h, what the head conv of a tdnet_opts.precision = 1 frame reads), widened into out
+extern "C" int tdnet_op_layernorm_hw_f16(const float* x, int HW, int C, const float* g, const float* b, float* out, void* stream) {
+    if (HW < 1 || C < 4 || C % 4 || (C / 4 <= 256 ? 256 % (C / 4) != 0 : C / 4 > 512)) return td_fail("tdnet_op_layernorm_hw_f16: C must be one of 4*{1,2,4,...,256} or 2048");
+    hipStream_t s = (hipStream_t)stream;
+    float *part = nullptr, *mean = nullptr, *rstd = nullptr;
+    _Float16* y = nullptr;
+    auto cleanup = [&]() {
+        for (float* q : {part, mean, rstd}) if (q) hipFree(q);
+        if (y) hipFree(y);
+    };
+    const long n = (long)HW * C;
+    if (dev_alloc(&part, (size_t)2 * 512 * C) || dev_alloc(&mean, C) || dev_alloc(&rstd, C) || dev_alloc(&y, (size_t)n)) { cleanup(); return -1; }
+    run_layernorm(nullptr, x, HW, C, g, b, part, mean, rstd, (float*)y, s, 0, true);
+    TD_LAUNCH(k_h2f, dim3(td_grid_for(n)), dim3(256), 0, s, (const _Float16*)y, out, n);
+    int rc = 0;
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_layernorm_hw_f16: device error");
+    cleanup();
+    return rc;
 }
 extern "C" int tdnet_op_ppm(const float* c4, int h, int w, const float* w_host, const float* b_host, int path_num, int pid, float* z,
                             void* stream) {

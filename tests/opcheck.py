@@ -163,54 +163,132 @@ def conv(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed
     return err
 
 
-def conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed=0, tol=4e-3, want_out=False):
-    """The fp16-storage conv of tdnet_opts.precision = 1 (input / residual / output maps fp16 in HBM, fp16 MFMA, fp32 accumulate)
-    against an fp64 evaluation on the fp16-rounded operands; what is left is fp32 summation order and the output's own rounding to
-    fp16 (2^-11 relative)."""
+def half(a):
+    """fp32 -> fp16, round to nearest even, widened to fp64: what k_f2h, the kernels' staging converts and the host weight packing do."""
+    return np.asarray(a, np.float32).astype(np.float16).astype(np.float64)
+
+
+def t16(ref):
+    """The gate of an fp16-MFMA product with fp32 accumulation and an fp32 result against fp64 on the same rounded operands
+    (test_gpu_fp16._conv16's): what is left is the fp32 summation."""
+    return 3e-5 * max(1.0, float(np.abs(ref).max()))
+
+
+def gate_f16(ref):
+    """Per-element gate of a result STORED as fp16: half an fp16 ulp of the value (2^-11 relative) + t16, the fp32 value's own error, which may
+    also have put it on the other side of a rounding boundary."""
+    return 2.0 ** -11 * np.abs(ref) + t16(ref)
+
+
+def assert_within(got, ref, gate, what):
+    """|got - ref| <= gate (a scalar or per element); the message carries the worst element.  Returns max(err / gate)."""
+    err = np.abs(np.asarray(got, np.float64) - ref)
+    ratio = err / gate
+    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    assert ratio[i] <= 1.0, what + ("worst element %s: got %.9g, reference %.9g, error %.3e, gate %.3e; %d of %d outside" % (
+        i, float(np.asarray(got)[i]), float(ref[i]), float(err[i]), float(np.broadcast_to(gate, err.shape)[i]), int((ratio > 1.0).sum()), err.size),)
+    return float(ratio[i])
+
+
+def conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed=0, want_out=False, in16=True, out16=True, resid16=False):
+    """The fp16-MFMA conv of tdnet_opts.precision = 1 (fp32 accumulate) against an fp64 evaluation on the operands as the kernel rounds them:
+    the weights (host packing) and the input (k_f2h for an fp16 map, the staging convert for an fp32 one) to fp16; the residual to fp16 only
+    where it is an fp16 map (in16); the bias not at all.  An fp32 result (out16 = False) is gated at t16, an fp16 map per element at gate_f16.
+    in16 = out16 = True: tdnet_op_conv2d_f16io, else tdnet_op_conv2d_f16mix.  resid16: the residual holds fp16 values already, so that the
+    in16 and in32 forms add the same numbers.  Returns max(error / gate)."""
     g = np.random.default_rng(seed)
     x = g.standard_normal((H, W, Cin)).astype(np.float32)
     w = (g.standard_normal((Cout, Cin, KS, KS)) / np.sqrt(Cin * KS * KS)).astype(np.float32)
     b = g.standard_normal(Cout).astype(np.float32)
     pad = dil * (KS // 2)
-    h = lambda a: torch.from_numpy(a).half().double()
-    ref = F.conv2d(h(x).permute(2, 0, 1)[None], h(w), torch.from_numpy(b).double(), stride, pad, dil)
+    ref = F.conv2d(torch.from_numpy(half(x)).permute(2, 0, 1)[None], torch.from_numpy(half(w)), torch.from_numpy(b).double(), stride, pad, dil)
     Ho, Wo = ref.shape[-2:]
     r = None
     if resid:
         r = g.standard_normal((Ho, Wo, Cout)).astype(np.float32)
-        ref = ref + h(r).permute(2, 0, 1)[None]
+        if resid16:
+            r = r.astype(np.float16).astype(np.float32)
+        ref = ref + torch.from_numpy(half(r) if in16 else r.astype(np.float64)).permute(2, 0, 1)[None]
     if act == 1:
         ref = F.relu(ref)
     elif act == 2:
         ref = F.leaky_relu(ref, 0.01)
-    ref = ref[0].permute(1, 2, 0).float().numpy()
+    ref = ref[0].permute(1, 2, 0).numpy()
     dx, dr, out = mem.put(x), (mem.put(r) if resid else None), mem.empty((Ho, Wo, Cout))
-    lib.check(lib.tdnet_op_conv2d_f16io(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, mem.ptr(dr), act,
-                                        -1 if tile is None else tile, mem.ptr(out), mem.stream))
-    got = mem.get(out)
-    err = float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max())
-    assert err <= tol, ("conv_f16io", H, W, Cin, Cout, KS, stride, dil, act, resid, tile, err)
-    return (err, got) if want_out else err
+    t = -1 if tile is None else tile
+    if in16 and out16:
+        lib.check(lib.tdnet_op_conv2d_f16io(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, mem.ptr(dr), act, t,
+                                            mem.ptr(out), mem.stream))
+    else:
+        lib.check(lib.tdnet_op_conv2d_f16mix(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, mem.ptr(dr), act, t,
+                                             int(in16), int(out16), mem.ptr(out), mem.stream))
+    got = np.array(mem.get(out))
+    ratio = assert_within(got, ref, gate_f16(ref) if out16 else t16(ref), ("conv_f16io", H, W, Cin, Cout, KS, stride, dil, act, resid, tile, in16, out16))
+    return (ratio, got) if want_out else ratio
 
 
-def stem(lib, mem, H, W, seed=0, tol=1e-4, opts=None):
-    import ctypes
+def _stem_case(H, W, seed, rounded):
+    """Inputs of the stem checks and the fp64 conv -> ReLU -> max-pool, NHWC; rounded: on the image and the weights as the fp16-MFMA stem
+    rounds them (the image while staging, the weights when packed)."""
     g = np.random.default_rng(seed)
     img = g.standard_normal((3, H, W)).astype(np.float32)
     w = (g.standard_normal((64, 3, 7, 7)) * 0.1).astype(np.float32)
     b = g.standard_normal(64).astype(np.float32)
-    ref = F.max_pool2d(F.relu(F.conv2d(torch.from_numpy(img)[None], torch.from_numpy(w), torch.from_numpy(b), 2, 3)), 3, 2, 1)
-    ref = ref[0].permute(1, 2, 0).numpy()
+    cast = half if rounded else (lambda a: a.astype(np.float64))
+    ref = F.max_pool2d(F.relu(F.conv2d(torch.from_numpy(cast(img))[None], torch.from_numpy(cast(w)), torch.from_numpy(b).double(), 2, 3)), 3, 2, 1)
+    return img, w, b, ref[0].permute(1, 2, 0).numpy()
+
+
+def stem(lib, mem, H, W, seed=0, tol=1e-4, opts=None, want_out=False):
+    """tdnet_op_stem against fp64.  precision = 1 (the fp16-MFMA stem writing fp32): the reference is evaluated on the rounded image and
+    weights and the gate is t16 instead of tol (the max-pool picks, it adds no error)."""
+    import ctypes
+    f16 = (opts or {}).get("precision") == 1
+    img, w, b, ref = _stem_case(H, W, seed, f16)
     di, out = mem.put(img), mem.empty(ref.shape)
     lib.check(lib.tdnet_op_stem(mem.ptr(di), H, W, w.ctypes.data, b.ctypes.data, ctypes.byref(lib.opts(**(opts or {}))), mem.ptr(out), mem.stream))
-    err = float(np.abs(mem.get(out) - ref).max())
-    assert err <= tol, ("stem", H, W, err)
-    return err
+    got = np.array(mem.get(out))
+    err = float(np.abs(got - ref).max())
+    assert err <= (t16(ref) if f16 else tol), ("stem", H, W, opts, err)
+    return (err, got) if want_out else err
+
+
+def stem_f16(lib, mem, H, W, seed=0, tile=None):
+    """tdnet_op_stem_f16 (the fp16-MFMA stem writing an fp16 map, the fp16 max-pool) against fp64 on the rounded image and weights, per
+    element at gate_f16: the stored map is half an ulp from the fp32 value, the pool picks (the values are >= 0 behind the ReLU, so the
+    largest gate of a window is that of its maximum).  And bit for bit half() of tdnet_op_stem with precision = 1 on the same tile: the
+    OUT16 epilogue rounds the value the fp32 epilogue stores, and the maximum commutes with a monotone rounding."""
+    img, w, b, ref = _stem_case(H, W, seed, True)
+    di, out = mem.put(img), mem.empty(ref.shape)
+    lib.check(lib.tdnet_op_stem_f16(mem.ptr(di), H, W, w.ctypes.data, b.ctypes.data, -1 if tile is None else tile, mem.ptr(out), mem.stream))
+    got = np.array(mem.get(out))
+    ratio = assert_within(got, ref, gate_f16(ref), ("stem_f16", H, W, tile))
+    if tile is None:
+        _, wide = stem(lib, mem, H, W, seed, opts={"precision": 1}, want_out=True)
+        assert np.array_equal(got, wide.astype(np.float16).astype(np.float32)), ("stem_f16 != half(fp32-output stem)", H, W)
+    return ratio
+
+
+def maxpool(lib, mem, H, W, C, mode, seed=0):
+    """tdnet_op_maxpool on N(0, 1) data -- negative values, so a padding value of 0 instead of -inf shows at every border -- against
+    F.max_pool2d, BIT FOR BIT: mode 0 the fp32 maximum; modes 1 and 2 half() of it (the maximum commutes with a monotone rounding, so
+    rounding the input first (2) or the result (1) is the same)."""
+    g = np.random.default_rng(seed + 1000 * mode + H * 131 + W)
+    x = g.standard_normal((H, W, C)).astype(np.float32)
+    ref = F.max_pool2d(torch.from_numpy(x).permute(2, 0, 1)[None], 3, 2, 1)[0].permute(1, 2, 0).numpy()
+    assert (ref < 0).any()
+    if mode:
+        ref = ref.astype(np.float16).astype(np.float32)
+    dx, out = mem.put(x), mem.empty(ref.shape)
+    lib.check(lib.tdnet_op_maxpool(mem.ptr(dx), H, W, C, mode, mem.ptr(out), mem.stream))
+    got = np.array(mem.get(out))
+    assert np.array_equal(got, ref), ("maxpool", H, W, C, mode, int((got != ref).sum()), float(np.abs(got - ref).max()))
 
 
 def attention(lib, mem, Lq, Lk, DV, bias=True, resid=True, seed=0, tol=1e-4, qk_scale=1.0, spike=False, online=0, ln=False, ramp=False):
     """online: the single-pass schedule; ln: also check the plane LayerNorm computed from the epilogue's strip statistics;
-    ramp: keys sorted by growing score for every query, so the online reference has to move again and again."""
+    ramp: keys sorted by growing score for every query, so the online reference has to move again and again.
+    online = 16 (the fp16-MFMA kernel): the reference is fp64 on q, k, v' rounded to fp16, gated per element (below); tol is not used."""
     g = np.random.default_rng(seed)
     q = (qk_scale * g.standard_normal((Lq, 64))).astype(np.float32)
     k = (qk_scale * g.standard_normal((Lk, 64))).astype(np.float32)
@@ -223,7 +301,16 @@ def attention(lib, mem, Lq, Lk, DV, bias=True, resid=True, seed=0, tol=1e-4, qk_
     v = g.standard_normal((Lk, DV)).astype(np.float32)
     b = g.standard_normal(DV).astype(np.float32)
     r = g.standard_normal((Lq, DV)).astype(np.float32)
-    ref = torch.softmax(torch.from_numpy(q).double() @ torch.from_numpy(k).double().T / 8.0, 1) @ torch.from_numpy(v).double()
+    f16 = (int(online) & ~(32 | 64)) == 16
+    if f16:
+        # the fp16-MFMA kernel rounds q, k and v' on the way into the MFMAs (td_attn_h.h); q is rounded AFTER its fp32 multiplication by
+        # log2(e) / 8, so the scores are in log2 units and the softmax is 2^s: softmax(ln 2 * qs k^T) with qs = half(q * log2(e) / 8)
+        qs = half(q * (np.float32(1.4426950408889634) / np.float32(8.0)))
+        prob = torch.softmax(float(np.log(2.0)) * (torch.from_numpy(qs) @ torch.from_numpy(half(k)).T), 1)
+        ref = prob @ torch.from_numpy(half(v))
+        amp = (prob @ torch.from_numpy(np.abs(half(v)))).numpy()          # A = sum_j p_j |v'_j| >= |R|
+    else:
+        ref = torch.softmax(torch.from_numpy(q).double() @ torch.from_numpy(k).double().T / 8.0, 1) @ torch.from_numpy(v).double()
     if bias:
         ref = ref + torch.from_numpy(b)
     if resid:
@@ -236,6 +323,18 @@ def attention(lib, mem, Lq, Lk, DV, bias=True, resid=True, seed=0, tol=1e-4, qk_
     lib.check(lib.tdnet_op_attention(mem.ptr(dq), mem.ptr(dk), mem.ptr(dv_), mem.ptr(db) if bias else None,
                                      mem.ptr(dr) if resid else None, Lq, Lk, DV, int(online), mem.ptr(dg), mem.ptr(dbb), mem.ptr(lnout),
                                      mem.ptr(out), mem.stream))
+    if f16:
+        # P is rounded to fp16 as well, 2^-11 relative per element: numerator and normalisation together move an output by at most 2^-10 A;
+        # the rest (fp32 scores, softmax and accumulation) is what the fp32 kernels are held to: 1e-4
+        got = np.array(mem.get(out))
+        assert_within(got, ref.numpy(), 2.0 ** -10 * amp + 1e-4, ("attention fp16", Lq, Lk, DV, bias, resid, online))
+        err = float(np.abs(got - ref.numpy()).max())
+        if ln:                                 # the plane LayerNorm of the kernel's OWN output, from the epilogue's strip statistics, at the fp32 LayerNorm tolerance
+            g64 = got.astype(np.float64)
+            lref = (g64 - g64.mean(0)) / np.sqrt(g64.var(0) + 1e-5) * gg.astype(np.float64)[:, None] + bb.astype(np.float64)[:, None]
+            lerr = float(np.abs(mem.get(lnout) - lref).max())
+            assert lerr <= 1e-4, ("attention fp16 + layernorm", Lq, Lk, DV, online, lerr)
+        return err
     err = float(np.abs(mem.get(out) - ref.float().numpy()).max())
     assert err <= tol, ("attention", Lq, Lk, DV, bias, resid, online, err)
     if ln:
@@ -256,6 +355,21 @@ def layernorm(lib, mem, HW, C, seed=0, tol=1e-4):
     err = float(np.abs(mem.get(out) - ref).max())
     assert err <= tol, ("layernorm", HW, C, err)
     return err
+
+
+def layernorm_f16(lib, mem, HW, C, seed=0):
+    """tdnet_op_layernorm_hw_f16 (k_ln_apply_h: the map the head conv of an fp16-mode frame reads) is half() of tdnet_op_layernorm_hw's
+    output BIT FOR BIT: the same statistics, the same fp32 expression, one rounding (td_misc.h above k_ln_apply_h).  The fp32 output itself
+    is held to fp64 by layernorm()."""
+    g = np.random.default_rng(seed)
+    x = (g.standard_normal((HW, C)) * 3 + 1).astype(np.float32)
+    gg = g.uniform(0.5, 1.5, HW).astype(np.float32)
+    bb = g.standard_normal(HW).astype(np.float32)
+    dx, dg, db, wide, out = mem.put(x), mem.put(gg), mem.put(bb), mem.empty((HW, C)), mem.empty((HW, C))
+    lib.check(lib.tdnet_op_layernorm_hw(mem.ptr(dx), HW, C, mem.ptr(dg), mem.ptr(db), mem.ptr(wide), mem.stream))
+    lib.check(lib.tdnet_op_layernorm_hw_f16(mem.ptr(dx), HW, C, mem.ptr(dg), mem.ptr(db), mem.ptr(out), mem.stream))
+    got, exp = np.array(mem.get(out)), np.array(mem.get(wide)).astype(np.float16).astype(np.float32)
+    assert np.array_equal(got, exp), ("layernorm_f16", HW, C, int((got != exp).sum()), float(np.abs(got - exp).max()))
 
 
 def layernorm_flat(lib, mem, HW, C, mean, std, seed=0, factor=4.0):

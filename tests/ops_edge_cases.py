@@ -6,7 +6,12 @@ Two things the value tests of test_gpu_ops / test_gpu_winograd / test_gpu_fp16 /
     paths exist (Cout = 19 / 130, a last M tile of a few rows, a Winograd tile grid that overhangs the map, a key tile of one key);
   * kernels and launch shapes that otherwise run inside whole frames only, where the 1e-3 logit gate is all that judges them: the three
     classifier kernels, the classifier inside the head conv's output transform, the plane LayerNorm at 2048 channels and at the
-    512-strip cap, the attention as two 256-channel slices and at d_v = 2048.
+    512-strip cap, the attention as two 256-channel slices and at d_v = 2048;
+  * the forms of the fp16 mode (tdnet_opts.precision = 1) that only the rim of a frame's fp16 backbone reaches, where the 3e-2 logit gate
+    is all that judges them: the max-pool alone in its three storage forms (on data with negative values, so the padding value shows),
+    the fp16-MFMA stem writing an fp16 map + the fp16 max-pool, convs with mixed storage (fp32 in / fp16 out, fp16 in + fp16 residual /
+    fp32 out, the latter on every LDS-DMA form), the LayerNorm map as fp16, the fp16 attention on the edge shapes.  Their references are
+    fp64 on the operands as the kernels round them (opcheck.t16 / gate_f16), or bit equality where the code makes two forms the same.
 
 Each function takes (lib, mem) and one entry of its case list; values are checked by the opcheck functions at the tolerance the
 route's existing tests use."""
@@ -39,7 +44,7 @@ CHUNKED_CONVS = [(12, 30, 128, 128, 3, 1, 4, 1, False), (9, 17, 128, 256, 3, 1, 
 # (conv arguments, tdnet_opts)
 SPLIT_CONVS = [((12, 17, 32, 48, 3, 2, 1, 2, True), {"precision": 2}), ((13, 21, 128, 132, 3, 1, 2, 1, False), {"precision": 3})]
 STEMS = [(7, 9), (33, 65)]
-STEM_OPTS = [{}, {"precision": 2}]
+STEM_OPTS = [{}, {"precision": 2}, {"precision": 1}]                   # precision 1: the fp16-MFMA stem writing fp32, against the rounding-aware reference
 # (conv arguments, tiles)
 F16_CONVS = [((13, 21, 128, 160, 3, 1, 1, 1, True), (16, 17, 31, 32)), ((13, 21, 64, 64, 3, 1, 1, 1, True), (34,)),
              ((9, 11, 192, 130, 1, 2, 1, 2, True), (16, None))]
@@ -48,6 +53,7 @@ UPSAMPLES = [(19, 5, 9, 33, 65), (3, 5, 9, 33, 64), (1, 2, 2, 7, 7), (2, 1, 1, 5
 SCHEDULES = [0, 1, 2]
 # (Lq, Lk, DV): one row past a 32-row strip, one key past a 128-key tile
 ATTENTIONS = [(45, 6, 512), (33, 1, 128), (65, 129, 512)]
+ATTENTION_F16 = 16                                                     # tdnet_op_attention's code of the fp16-MFMA kernel (td_attn_h.h), on ATTENTIONS
 
 # ---- 2. the classifier kernels ------------------------------------------------------------------------------------------------------
 # (NC, C, HW): k_classifier<19> / <32> on both sides of 19 and 32, the class-tiled kernel with a ragged last tile; C = 512 with 32
@@ -72,6 +78,21 @@ LAYERNORMS_FLAT = [(45, 128, 5.0, 1e-3), (1000, 512, 50.0, 1e-3), (513, 2048, 5.
 # (Lq, Lk, bias, resid, spike) at d_v = 512 as two 256-channel slices (online | 64)
 SLICED_ATTENTIONS = [(45, 6, True, True, False), (153, 200, True, True, True), (64, 128, False, False, False)]
 WIDE_ATTENTIONS = [(70, 260, 2048), (33, 1, 2048)]                     # four 512-channel launches on a strided V'
+
+# ---- 6. forms of the fp16 mode (tdnet_opts.precision = 1) that otherwise run inside frames only --------------------------------------
+# the max-pool alone: (H, W) x C x mode (0: fp32, 1: fp32 in / fp16 out, 2: fp16 in and out); C = 128: behind the deep stem
+MAXPOOLS = [(1, 1), (2, 3), (7, 9), (8, 10), (33, 65)]
+MAXPOOL_CS = [64, 128]
+MAXPOOL_MODES = [0, 1, 2]
+STEMS_F16 = [(7, 9), (33, 65), (40, 52)]                               # the fp16-MFMA stem writing an fp16 map + the fp16 max-pool
+MIXED_TILES = [3, 4, 5, None]                                          # register-staged tiles for in32 -> out16 and in16 -> out32
+DMA_TILES = [16, 17, 18, 19, 31, 32, 34, 35, None]                     # in16 -> out32 with a residual: the head conv's epilogue of every LDS-DMA form
+
+
+def dma_tiles_for(a):
+    """The LDS-DMA tile codes the conv a can run on: all but the 256 x 256 tile where Cout does not pad to a multiple of 256."""
+    Cout = a[3]
+    return [t for t in DMA_TILES if t != 19 or ((Cout + 127) // 128 * 128) % 256 == 0]
 
 
 def direct_conv(lib, mem, a, tile):
@@ -101,6 +122,74 @@ def stem(lib, mem, hw, opts):
 
 def f16_conv(lib, mem, a, tile):
     opcheck.conv_f16io(lib, mem, *a, tile)
+    mem.verify()
+
+
+def mixed_conv(lib, mem, a, tile):
+    """in32 -> out16 (the deep stem's second conv) and in16 -> out32 (the backbone's last conv: fp16 residual, fp32 output, not in place) on a
+    register-staged tile, each against fp64 on the rounded operands; then, on a forced tile, the relations the kernel makes exact
+    (td_conv_h.h: IN16 / OUT16 change the staging and the epilogue's last step, not the products or their order):
+      * out16 == half(out32) for the same input form;
+      * in32(x) == in16(half(x)): the staging convert is k_f2h's rounding (the residual is given in fp16 values, which both forms then add)."""
+    fwd = lambda in16, out16: opcheck.conv_f16io(lib, mem, *a, tile, want_out=True, in16=in16, out16=out16, resid16=True)[1]
+    h = lambda y: y.astype(np.float16).astype(np.float32)
+    o32_16, o16_32 = fwd(False, True), fwd(True, False)
+    mem.verify()
+    if tile is None:                                                   # the heuristic may send the fp16 map to an LDS-DMA form and the fp32 one not
+        return
+    o16_16, o32_32 = fwd(True, True), fwd(False, False)
+    mem.verify()
+    assert np.array_equal(o16_16, h(o16_32)), ("out16 != half(out32), fp16 map in", a, tile)
+    assert np.array_equal(o32_16, h(o32_32)), ("out16 != half(out32), fp32 map in", a, tile)
+    assert np.array_equal(o32_32, o16_32), ("in32(x) != in16(half(x))", a, tile)
+
+
+def dma_conv_out32(lib, mem, a, tile):
+    """in16 -> out32 with a residual on an LDS-DMA form (the head conv reading the fp16 LayerNorm map: the out16 = false epilogue of
+    k_conv_dma_h / _h3 / _h3p / _h3n) against fp64 on the rounded operands; on a forced form also out16 == half(out32): every form ends in
+    td_store_acc_h, whose OUT16 only rounds what the fp32 form stores."""
+    H, W, Cin, Cout, KS, stride, dil, act, _ = a
+    _, wide = opcheck.conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, True, tile, want_out=True, in16=True, out16=False)
+    mem.verify()
+    if tile is not None:
+        _, narrow = opcheck.conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, True, tile, want_out=True)
+        mem.verify()
+        assert np.array_equal(narrow, wide.astype(np.float16).astype(np.float32)), ("out16 != half(out32) on an LDS-DMA form", a, tile)
+
+
+def mixed_conv_refusals(lib, mem):
+    """An LDS-DMA form needs an fp16 input map; the fp16 stem refuses a tile it has no kernel for: errors, and nothing is launched."""
+    (H, W, Cin, Cout, KS, stride, dil, act, _), _ = F16_CONVS[0]
+    x, w, b = mem.put(np.zeros((H, W, Cin), np.float32)), np.zeros((Cout, Cin, KS, KS), np.float32), np.zeros(Cout, np.float32)
+    out = mem.empty((H, W, Cout))
+    with pytest.raises(_capi.TdnetError):
+        lib.check(lib.tdnet_op_conv2d_f16mix(mem.ptr(x), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, None, act, 16, 0, 0, mem.ptr(out), mem.stream))
+    mem.verify(untouched=True)
+    img, w7, out = mem.put(np.zeros((3, 7, 9), np.float32)), np.zeros((64, 3, 7, 7), np.float32), mem.empty((2, 3, 64))
+    for tile in (0, 1, 3, 4):
+        with pytest.raises(_capi.TdnetError):
+            lib.check(lib.tdnet_op_stem_f16(mem.ptr(img), 7, 9, w7.ctypes.data, None, tile, mem.ptr(out), mem.stream))
+    mem.verify(untouched=True)
+    x, out = mem.put(np.zeros((2, 3, 6), np.float32)), mem.empty((1, 2, 6))
+    for C, mode in ((6, 0), (4, 3)):
+        with pytest.raises(_capi.TdnetError):
+            lib.check(lib.tdnet_op_maxpool(mem.ptr(x), 2, 3, C, mode, mem.ptr(out), mem.stream))
+    mem.verify(untouched=True)
+
+
+def maxpool(lib, mem, hw, C, mode):
+    opcheck.maxpool(lib, mem, *hw, C, mode)
+    mem.verify()
+
+
+def stem_f16(lib, mem, hw):
+    opcheck.stem_f16(lib, mem, *hw)
+    opcheck.stem_f16(lib, mem, *hw, tile=2)                            # the single-stage form of the same 128 x 64 tile
+    mem.verify()
+
+
+def layernorm_f16(lib, mem, a):
+    opcheck.layernorm_f16(lib, mem, *a)
     mem.verify()
 
 

@@ -55,6 +55,34 @@ def test_fp16_storage_convs(lib, mem):
             cases.f16_conv(lib, mem, a, tile)
 
 
+@pytest.mark.parametrize("tile", cases.MIXED_TILES)
+def test_fp16_mixed_storage_convs(lib, mem, tile):
+    for a, _ in cases.F16_CONVS:
+        cases.mixed_conv(lib, mem, a, tile)
+
+
+def test_fp16_lds_dma_convs_writing_fp32(lib, mem):
+    for a, _ in cases.F16_CONVS:
+        for tile in cases.dma_tiles_for(a):
+            cases.dma_conv_out32(lib, mem, a, tile)
+
+
+def test_fp16_entry_refusals(lib, mem):
+    cases.mixed_conv_refusals(lib, mem)
+
+
+@pytest.mark.parametrize("mode", cases.MAXPOOL_MODES)
+def test_maxpool(lib, mem, mode):
+    for hw in cases.MAXPOOLS:
+        for C in cases.MAXPOOL_CS:
+            cases.maxpool(lib, mem, hw, C, mode)
+
+
+def test_fp16_stem_writing_the_fp16_map(lib, mem):
+    for hw in cases.STEMS_F16:
+        cases.stem_f16(lib, mem, hw)
+
+
 def test_ppm_upsample(lib, mem):
     for hw in cases.PPMS:
         for pid in (0, 1):
@@ -71,6 +99,11 @@ def test_attention(lib, mem, online):
         cases.sliced_attention(lib, mem, a, online)
     for a in cases.WIDE_ATTENTIONS:
         cases.wide_attention(lib, mem, a, online)
+
+
+def test_attention_fp16(lib, mem):
+    for a in cases.ATTENTIONS:
+        cases.attention(lib, mem, a, cases.ATTENTION_F16)
 
 
 @pytest.mark.parametrize("a", cases.CLASSIFIERS)
@@ -94,6 +127,11 @@ def test_head_cls_refusals(lib, mem):
 def test_layernorm(lib, mem):
     for a in cases.LAYERNORMS:
         cases.layernorm(lib, mem, a)
+
+
+def test_layernorm_fp16_map(lib, mem):
+    for a in cases.LAYERNORMS:
+        cases.layernorm_f16(lib, mem, a)
 
 
 @pytest.mark.parametrize("a", cases.LAYERNORMS_FLAT)
