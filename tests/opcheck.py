@@ -344,6 +344,142 @@ def attention(lib, mem, Lq, Lk, DV, bias=True, resid=True, seed=0, tol=1e-4, qk_
     return err
 
 
+# ---- tdnet_opts.precision = 2 / 3: fp32 operands as three bf16 parts, six bf16-MFMA products per product (td_gemm_b3.h, td_conv_ad_b3.h,
+# td_attn_b3.h).  A product is carried to ~2^-26; dropping one of the three third-order terms costs ~2^-18 per product, a second-order
+# one ~2^-9 -- both far below the 1e-4 of conv() / attention().  So the split kernels are gated against fp64 RELATIVE to a yardstick on
+# the same inputs, in max and in rms error (rms is the sharp statistic: a lost third-order term moves it by 5.9x .. 19x, max by 3x .. 10x):
+#   * non-Winograd routes: the distance of the plain fp32 torch evaluation on the CPU to fp64.  Under the emulator the unmodified kernels
+#     are at most 1.17x (rms) / 1.25x (max) of it; the gate is 2x / 3x because the device's MFMA adds the 16 products of an instruction in
+#     its own order.  The rms factor stays below 3.0, half the smallest lost-product ratio.
+#   * Winograd routes (both kernels are limited by the transforms, a direct fp32 conv is not comparable): the relation test_gpu_b3 holds
+#     the mode to, 1.25x max / 1.1x rms of the exact-fp32 Winograd kernel ({"winograd": 4}).
+# The floors are test_gpu_b3's: at Lk = 1 the attention is exact and every error is 0.
+SPLIT_GATE = {"max": (3.0, 1e-7), "rms": (2.0, 1e-9)}                  # over the CPU fp32 evaluation's own error
+SPLIT_WINO_GATE = {"max": (1.25, 1e-7), "rms": (1.1, 1e-9)}           # over the exact-fp32 Winograd kernel's error
+SPLIT_DATA = ("normal", "abs", "scaled")
+
+
+def pow2_scales(n):
+    """Per-channel powers of two from 2^-6 to 2^6, neighbours far apart: the 8 values a lane hands to one MFMA span the whole range."""
+    return np.exp2(((np.arange(n) * 5) % 13 - 6).astype(np.float64)).astype(np.float32)
+
+
+def max_rms(got, ref):
+    e = np.abs(np.asarray(got, np.float64) - ref)
+    return float(e.max()), float(np.sqrt((e * e).mean()))
+
+
+def _split_gate(what, errs, yard, gate):
+    """errs: {"cpu32" | "exact" | "split": (max, rms)} against fp64; asserts errs["split"] against errs[yard] and prints every figure."""
+    (fm, cm), (fr, cr) = gate["max"], gate["rms"]
+    s, y = errs["split"], errs[yard]
+    ratio = lambda a, b: "x%.2f" % (a / b) if b > 0 else "-"
+    print("split gate %s: cpu32 %.2e / %.2e | exact %.2e / %.2e (%s / %s) | split %.2e / %.2e (%s / %s of cpu32%s)" % (
+        what, *errs["cpu32"], *errs["exact"], ratio(errs["exact"][0], errs["cpu32"][0]), ratio(errs["exact"][1], errs["cpu32"][1]),
+        *s, ratio(s[0], errs["cpu32"][0]), ratio(s[1], errs["cpu32"][1]),
+        "" if yard == "cpu32" else "; %s / %s of exact" % (ratio(s[0], y[0]), ratio(s[1], y[1]))))
+    assert s[1] <= fr * y[1] + cr, ("split kernel rms error", what, yard, errs)
+    assert s[0] <= fm * y[0] + cm, ("split kernel max error", what, yard, errs)
+    return errs
+
+
+def _conv_data(g, H, W, Cin, Cout, KS, data):
+    x = g.standard_normal((H, W, Cin)).astype(np.float32)
+    w = (g.standard_normal((Cout, Cin, KS, KS)) / np.sqrt(Cin * KS * KS)).astype(np.float32)
+    if data == "abs":                                                  # behind a ReLU: the sums of a product row cancel less
+        x = np.abs(x)
+    elif data == "scaled":                                             # exact in every format: the same products, other exponents per channel
+        s = pow2_scales(Cin)
+        x, w = x * s, w / s[None, :, None, None]
+    else:
+        assert data == "normal", data
+    return x, w
+
+
+def split_conv(lib, mem, H, W, Cin, Cout, KS, stride, dil, opts, wino=False, data="normal", seed=0, stays_exact=False):
+    """A conv of tdnet_opts.precision = 2 / 3 (opts) through tdnet_op_conv2d without bias, residual or activation -- the products alone --
+    against fp64, next to the fp32 torch conv on the CPU and to the exact-fp32 kernel of the same route (opts with precision 0; wino: the
+    Winograd kernel {"winograd": 4}) on the same inputs.  Gate: SPLIT_GATE over the CPU evaluation, wino: SPLIT_WINO_GATE over the exact
+    kernel.  Also: the split kernel really ran -- its sums are not the fp32 MFMA's bit for bit --, or, stays_exact, the plan has no split
+    kernel for this conv and it keeps the exact-fp32 kernel's bits.  Returns the three (max, rms)."""
+    import ctypes
+    g = np.random.default_rng(seed)
+    x, w = _conv_data(g, H, W, Cin, Cout, KS, data)
+    tx, tw, pad = torch.from_numpy(x).permute(2, 0, 1)[None], torch.from_numpy(w), dil * (KS // 2)
+    ref = F.conv2d(tx.double(), tw.double(), None, stride, pad, dil)[0].permute(1, 2, 0).numpy()
+    errs = {"cpu32": max_rms(F.conv2d(tx, tw, None, stride, pad, dil)[0].permute(1, 2, 0).numpy(), ref)}
+    dx, outs = mem.put(x), {}
+    for name, kw in (("exact", {"winograd": 4} if wino else dict(opts, precision=0)), ("split", opts)):
+        out = mem.empty(ref.shape)
+        lib.check(lib.tdnet_op_conv2d(mem.ptr(dx), H, W, Cin, w.ctypes.data, None, Cout, KS, stride, dil, None, 0, ctypes.byref(lib.opts(**kw)), -1,
+                                      mem.ptr(out), mem.stream))
+        outs[name] = np.array(mem.get(out))
+        errs[name] = max_rms(outs[name], ref)
+    what = "conv %dx%d %d->%d k%d s%d d%d %s %s" % (H, W, Cin, Cout, KS, stride, dil, opts, data)
+    if stays_exact:
+        assert np.array_equal(outs["exact"], outs["split"]), ("not the bits of the exact-fp32 kernel", what)
+    else:
+        assert not np.array_equal(outs["exact"], outs["split"]), ("the split kernel did not run: the bits of the exact-fp32 kernel", what)
+    return _split_gate(what, errs, "exact" if wino else "cpu32", SPLIT_WINO_GATE if wino else SPLIT_GATE)
+
+
+def split_stem(lib, mem, H, W, data="normal", seed=0):
+    """The packed-row 7x7 stem of tdnet_opts.precision = 2 (k_conv_adirect_b3<7, 2>) through tdnet_op_stem -- conv -> ReLU -> max-pool, which
+    picks and adds no error -- at SPLIT_GATE over the same chain in fp32 torch on the CPU."""
+    import ctypes
+    img, w, b, _ = _stem_case(H, W, seed, False)
+    if data == "abs":
+        img = np.abs(img)
+    elif data == "scaled":
+        s = np.float32([2.0 ** -6, 1.0, 2.0 ** 6])
+        img, w = img * s[:, None, None], w / s[None, :, None, None]
+    chain = lambda cast: F.max_pool2d(F.relu(F.conv2d(cast(torch.from_numpy(img))[None], cast(torch.from_numpy(w)), cast(torch.from_numpy(b)), 2, 3)), 3, 2, 1)[0].permute(1, 2, 0).numpy()
+    ref = chain(lambda t: t.double())
+    errs = {"cpu32": max_rms(chain(lambda t: t), ref)}
+    di, outs = mem.put(img), {}
+    for name, kw in (("exact", {}), ("split", {"precision": 2})):
+        out = mem.empty(ref.shape)
+        lib.check(lib.tdnet_op_stem(mem.ptr(di), H, W, w.ctypes.data, b.ctypes.data, ctypes.byref(lib.opts(**kw)), mem.ptr(out), mem.stream))
+        outs[name] = np.array(mem.get(out))
+        errs[name] = max_rms(outs[name], ref)
+    what = "stem %dx%d %s" % (H, W, data)
+    assert not np.array_equal(outs["exact"], outs["split"]), ("the split kernel did not run: the bits of the exact-fp32 kernel", what)
+    return _split_gate(what, errs, "cpu32", SPLIT_GATE)
+
+
+def split_attention(lib, mem, Lq, Lk, DV, online, spike=False, ramp=False, data="normal", seed=0):
+    """The attention of tdnet_opts.precision = 2 (td_attn_b3.h; online 17: the form by size, 18: 64 queries per workgroup, 19: 32) without bias
+    and residual against fp64 softmax(q k^T / 8) v', at SPLIT_GATE over the same expression in fp32 torch on the CPU; the exact-fp32
+    single-pass kernel (online = 2) runs beside it for the record.  spike / ramp: attention()'s.  data: "abs": q, k, v' >= 0 (every score
+    positive, no cancellation in P V'); "scaled": q_d * s_d and k_d / s_d (the same scores from other exponents), key j of v' times s_j."""
+    g = np.random.default_rng(seed)
+    q = g.standard_normal((Lq, 64)).astype(np.float32)
+    k = g.standard_normal((Lk, 64)).astype(np.float32)
+    if spike:
+        k[Lk // 2] = 6.0 * q[Lq // 3] / max(1e-6, float(np.linalg.norm(q[Lq // 3]))) * 8.0
+    if ramp:
+        q = np.abs(q) + 0.5
+        k = (np.arange(Lk, dtype=np.float32)[:, None] / max(1, Lk - 1)) * 40.0 * (np.ones(64, np.float32) / 8.0)[None, :] + 0.1 * k
+    v = g.standard_normal((Lk, DV)).astype(np.float32)
+    if data == "abs":
+        q, k, v = np.abs(q), np.abs(k), np.abs(v)
+    elif data == "scaled":
+        s = pow2_scales(64)
+        q, k, v = q * s, k / s, v * pow2_scales(Lk)[:, None]
+    else:
+        assert data == "normal", data
+    tq, tk, tv = torch.from_numpy(q), torch.from_numpy(k), torch.from_numpy(v)
+    ref = (torch.softmax(tq.double() @ tk.double().T / 8.0, 1) @ tv.double()).numpy()
+    errs = {"cpu32": max_rms((torch.softmax(tq @ tk.T / 8.0, 1) @ tv).numpy(), ref)}
+    dq, dk, dv_ = mem.put(q), mem.put(k), mem.put(v)
+    for name, code in (("exact", 2), ("split", int(online))):
+        out = mem.empty((Lq, DV))
+        lib.check(lib.tdnet_op_attention(mem.ptr(dq), mem.ptr(dk), mem.ptr(dv_), None, None, Lq, Lk, DV, code, None, None, None, mem.ptr(out), mem.stream))
+        errs[name] = max_rms(np.array(mem.get(out)), ref)
+    what = "attention (%d, %d, %d) online %d%s%s %s" % (Lq, Lk, DV, online, " spike" if spike else "", " ramp" if ramp else "", data)
+    return _split_gate(what, errs, "cpu32", SPLIT_GATE)
+
+
 def layernorm(lib, mem, HW, C, seed=0, tol=1e-4):
     g = np.random.default_rng(seed)
     x = (g.standard_normal((HW, C)) * 3 + 1).astype(np.float32)

@@ -1,6 +1,6 @@
 """Operator edge cases shared by tests/test_emu_ops_edges.py (CPU, through the emulator) and tests/test_gpu_ops_edges.py (device memory).
 
-Two things the value tests of test_gpu_ops / test_gpu_winograd / test_gpu_fp16 / test_gpu_b3 cannot see:
+What the value tests of test_gpu_ops / test_gpu_winograd / test_gpu_fp16 / test_gpu_b3 cannot see:
   * an access outside a tensor.  Every case here runs on a guarded mem (opcheck.GuardedNumpyMem / GuardedTorchMem: NaN bands around the
     inputs, a fixed pattern around the outputs) and ends with mem.verify(); the shapes are the smallest at which each kernel's ragged
     paths exist (Cout = 19 / 130, a last M tile of a few rows, a Winograd tile grid that overhangs the map, a key tile of one key);
@@ -12,6 +12,12 @@ Two things the value tests of test_gpu_ops / test_gpu_winograd / test_gpu_fp16 /
     the fp16-MFMA stem writing an fp16 map + the fp16 max-pool, convs with mixed storage (fp32 in / fp16 out, fp16 in + fp16 residual /
     fp32 out, the latter on every LDS-DMA form), the LayerNorm map as fp16, the fp16 attention on the edge shapes.  Their references are
     fp64 on the operands as the kernels round them (opcheck.t16 / gate_f16), or bit equality where the code makes two forms the same.
+  * the split kernels of tdnet_opts.precision = 2 / 3 (three bf16 parts per fp32 operand, six bf16-MFMA products per product) on their
+    edge shapes -- every epilogue role of the split GEMM, tiles outnumbering workgroups, the narrow direct convs and the packed-row stem,
+    the three attention forms at 128 / 512 / 2048 channels, the head conv + classifier behind the split GEMM -- where 1e-4 against fp32
+    cannot see a lost product (~2^-18): the products alone against fp64, in max and rms error, relative to the fp32 CPU evaluation's own
+    error (x3 / x2) or, on the Winograd route, to the exact-fp32 Winograd kernel's (x1.25 / x1.1): opcheck.split_conv / split_stem /
+    split_attention, also on non-negative data and on per-channel power-of-two scales.
 
 Each function takes (lib, mem) and one entry of its case list; values are checked by the opcheck functions at the tolerance the
 route's existing tests use."""
@@ -88,6 +94,122 @@ STEMS_F16 = [(7, 9), (33, 65), (40, 52)]                               # the fp1
 MIXED_TILES = [3, 4, 5, None]                                          # register-staged tiles for in32 -> out16 and in16 -> out32
 DMA_TILES = [16, 17, 18, 19, 31, 32, 34, 35, None]                     # in16 -> out32 with a residual: the head conv's epilogue of every LDS-DMA form
 
+# ---- 7. the split kernels of tdnet_opts.precision = 2 / 3 (three bf16 parts per fp32 operand, six bf16-MFMA products per product) -----
+# Each case runs twice on the guarded mem: the full form (bias, residual, activation, LayerNorm statistics) at the route's tolerance, then
+# the products alone against fp64 at a gate that sees ONE lost product of the six (opcheck.SPLIT_GATE / SPLIT_WINO_GATE).
+SPLIT = {"precision": 3}                                               # the split GEMM at any size
+SPLIT_WINO = {"winograd": 4, "precision": 3}
+NARROW = {"precision": 2}
+# (conv arguments, tdnet_opts, Winograd route): k_gemm_b3<2> (1x1), <0> (1x1 + residual), <1> (the 36 Winograd GEMMs).
+# K = 32 is the two-step minimum of gemm_b3_supports, but plan_conv gives a GEMM to the persistent kernels -- k_gemm_b3 among them -- only
+# where gemm_supports(K): K % 64 == 0.  So the K = 32 entries run elsewhere: the 1x1 convs on k_conv_adirect_b3<1, 0> (one step), the
+# Winograd conv on the exact-fp32 batched conv kernel, bit for bit (SPLIT_STAYS_EXACT); K = 64, four steps, is the least k_gemm_b3 sees.
+SPLIT_GEMMS = [((5, 7, 32, 128, 1, 1, 1, 0, False), SPLIT, False),     # K = 32, two 64-column tiles of the split direct kernel
+               ((5, 7, 32, 4, 1, 1, 1, 1, True), SPLIT, False),        # K = 32, N = 4 padded to one tile
+               ((33, 9, 192, 128, 1, 1, 1, 0, False), SPLIT, False),   # twelve steps, a second M tile of 41 rows
+               ((7, 9, 64, 128, 1, 1, 1, 0, True), SPLIT, False),
+               ((11, 19, 64, 160, 1, 1, 1, 2, True), SPLIT, False),    # 32 columns into a second N tile, LeakyReLU
+               ((35, 37, 64, 256, 1, 1, 1, 1, False), dict(SPLIT, gemm_persistent=3), False),   # 12 tiles (the last rows ragged) walked by three workgroups
+               ((1, 1, 32, 32, 3, 1, 1, 0, False), SPLIT_WINO, True),  # K = 32: stays on the exact-fp32 kernel
+               ((1, 1, 64, 32, 3, 1, 1, 0, False), SPLIT_WINO, True),  # one tile row per GEMM, four steps, N = 32
+               ((5, 9, 256, 512, 3, 1, 16, 2, False), SPLIT_WINO, True),
+               ((13, 21, 128, 132, 3, 1, 2, 1, False), SPLIT_WINO, True),
+               ((9, 17, 128, 256, 3, 1, 8, 0, True), dict(SPLIT_WINO, overlap=CHAINS), True),   # row-parity chunks of different size
+               ((12, 14, 128, 132, 3, 1, 1, 1, True), dict(SPLIT_WINO, gemm_persistent=5), True)]   # 72 tiles in 36 batches walked by five workgroups
+SPLIT_STAYS_EXACT = [(1, 1, 32, 32, 3, 1, 1, 0, False)]
+# k_conv_adirect_b3<3, 0> / <1, 0>; the packed-row stem <7, 2> runs on STEMS
+SPLIT_NARROW = [((13, 21, 64, 64, 3, 1, 1, 1, True), NARROW),          # ResNet layer1
+                ((11, 9, 96, 48, 3, 2, 2, 0, False), NARROW),          # 27 steps (odd), stride 2, dilation 2, ragged channels
+                ((9, 17, 64, 40, 1, 2, 1, 0, False), NARROW),          # the strided 1x1 form
+                ((13, 21, 64, 128, 3, 2, 1, 1, False), dict(NARROW, winograd=0)),   # 65 .. 128 output channels as two 64-column tiles
+                ((9, 17, 64, 100, 1, 2, 1, 0, True), NARROW),          # a ragged second column tile, residual
+                ((12, 17, 32, 48, 3, 2, 1, 2, True), NARROW),          # one chunk of 32 channels
+                ((96, 96, 64, 64, 1, 1, 1, 1, True), NARROW)]          # a stride-1 1x1 on >= 8192 pixels: kept off the GEMM route
+# the harder inputs (opcheck.SPLIT_DATA), once per kernel: index into the list above
+SPLIT_GEMMS_HARD = [4, 9]
+SPLIT_NARROW_HARD = [1, 4]
+SPLIT_ONLINES = [17, 18, 19]                                           # 17: the form by size, 18: k_attention_b3w (64 queries), 19: k_attention_b3<1, 4, 4>
+# (Lq, Lk, DV, online, spike, ramp)
+SPLIT_ATTENTIONS = ([(Lq, Lk, DV, o, False, False) for (Lq, Lk, DV) in ATTENTIONS for o in SPLIT_ONLINES if o == 17 or DV % 512 == 0] +
+                    [a + (o, False, False) for a in WIDE_ATTENTIONS for o in SPLIT_ONLINES] +   # four 512-channel launches on ONE pre-split V'
+                    [(64, 128, 512, 18, False, False), (97, 130, 512, 18, False, False),        # k_attention_b3w's second query tile: full, one row
+                     (130, 193, 128, 17, False, False)] +
+                    [(Lq, Lk, DV, o, sp, not sp) for (DV, o) in ((128, 17), (512, 19), (512, 18)) for (Lq, Lk, sp) in ((153, 200, True), (70, 300, False))])
+SPLIT_ATTENTIONS_HARD = [(65, 129, 128, 17), (65, 129, 512, 19), (65, 129, 512, 18)]
+HEAD_SPLIT = dict(WINO, precision=3)                                   # the head conv's 36 GEMMs on k_gemm_b3: CoutPad = gemm_b3_npad(Cout) in front of k_wino4_out_cls
+
+# Measured under the emulator with the unmodified kernels (the device's figures: tests/test_gpu_ops_edges.py).  Errors against fp64 as
+# max / rms; cpu32: the fp32 torch evaluation on the CPU; exact, split: the exact-fp32 and the split kernel as multiples of cpu32 (gate
+# of the split kernel: x3 / x2), on the Winograd route the exact kernel's own error and the split kernel as a multiple of it (gate: x1.25
+# / x1.1).  p2 / p3: precision, w4 / w0: winograd, g: gemm_persistent.  "scaled" equals "normal" to the digit on the convs: the scales
+# are exact, so the kernels form the same products from other exponents.  The largest: x1.50 / x1.21 (11x9 96->48 on abs data).
+# With one of the six MFMAs of a product loop removed -- k_gemm_b3 (second- and third-order terms, either column group), k_conv_adirect_b3
+# (either k block), the Q K^T and P V' loops of k_attention_b3 and k_attention_b3w -- or with a part used twice, 6 to 24 of the cases below
+# miss their gate, in every form of the kernel; a third-order term moves the rms figure to x8.0 .. x29 on the sharpest case (x2.0 on
+# the dullest that still fails), a second-order one to x850 and more.
+# conv 5x7 32->128 k1 p3                       cpu32 7.72e-07 / 1.01e-07   exact x1.01 / x0.98   split x0.75 / x0.75
+# conv 5x7 32->4 k1 p3                         cpu32 4.01e-07 / 8.61e-08   exact x0.79 / x1.00   split x0.60 / x0.68
+# conv 33x9 192->128 k1 p3                     cpu32 1.96e-06 / 2.48e-07   exact x0.91 / x0.99   split x0.82 / x0.64
+# conv 7x9 64->128 k1 p3                       cpu32 1.02e-06 / 1.46e-07   exact x1.11 / x1.01   split x0.77 / x0.68
+# conv 11x19 64->160 k1 p3                     cpu32 1.54e-06 / 1.44e-07   exact x1.00 / x1.01   split x0.68 / x0.68
+# conv 35x37 64->256 k1 p3 g3                  cpu32 1.60e-06 / 1.44e-07   exact x0.89 / x1.00   split x0.71 / x0.68
+# conv 1x1 32->32 k3 w4 p3                     exact 3.29e-07 / 1.21e-07   split x1.00 / x1.00 of it
+# conv 1x1 64->32 k3 w4 p3                     exact 4.14e-07 / 1.23e-07   split x0.42 / x0.67 of it
+# conv 5x9 256->512 k3 d16 w4 p3               exact 2.14e-06 / 2.87e-07   split x0.43 / x0.63 of it
+# conv 13x21 128->132 k3 d2 w4 p3              exact 3.38e-05 / 1.80e-06   split x0.53 / x0.68 of it
+# conv 9x17 128->256 k3 d8 w4 p3 chains        exact 2.66e-06 / 3.76e-07   split x0.81 / x0.67 of it
+# conv 12x14 128->132 k3 w4 p3 g5              exact 3.56e-05 / 2.14e-06   split x0.45 / x0.67 of it
+# conv 13x21 64->64 k3 p2                      cpu32 1.78e-06 / 2.86e-07   exact x1.67 / x1.40   split x1.20 / x0.88
+# conv 11x9 96->48 k3 s2 d2 p2                 cpu32 1.23e-06 / 2.09e-07   exact x2.76 / x1.99   split x0.98 / x1.17
+# conv 9x17 64->40 k1 s2 p2                    cpu32 6.60e-07 / 1.42e-07   exact x1.24 / x1.05   split x1.04 / x0.70
+# conv 13x21 64->128 k3 s2 p2 w0               cpu32 1.65e-06 / 2.65e-07   exact x1.78 / x1.43   split x1.30 / x0.88
+# conv 9x17 64->100 k1 s2 p2                   cpu32 9.69e-07 / 1.42e-07   exact x0.98 / x1.02   split x0.71 / x0.69
+# conv 12x17 32->48 k3 s2 p2                   cpu32 1.94e-06 / 2.76e-07   exact x1.08 / x1.05   split x1.07 / x0.63
+# conv 96x96 64->64 k1 p2                      cpu32 1.58e-06 / 1.48e-07   exact x1.13 / x1.00   split x0.77 / x0.68
+# stem 7x9                                     cpu32 9.96e-07 / 2.03e-07   exact x0.73 / x0.93   split x0.76 / x0.83
+# stem 7x9 abs                                 cpu32 8.83e-07 / 1.67e-07   exact x1.00 / x1.03   split x0.85 / x0.99
+# stem 7x9 scaled                              cpu32 9.96e-07 / 2.03e-07   exact x0.73 / x0.93   split x0.76 / x0.83
+# stem 33x65                                   cpu32 2.19e-06 / 3.31e-07   exact x0.89 / x1.01   split x0.70 / x0.80
+# stem 33x65 abs                               cpu32 2.40e-06 / 2.90e-07   exact x1.00 / x1.00   split x0.71 / x0.79
+# stem 33x65 scaled                            cpu32 2.19e-06 / 3.31e-07   exact x0.89 / x1.01   split x0.70 / x0.80
+# conv 11x19 64->160 k1 p3 abs                 cpu32 1.32e-06 / 1.46e-07   exact x0.97 / x1.00   split x0.69 / x0.67
+# conv 13x21 128->132 k3 d2 w4 p3 abs          exact 2.20e-05 / 1.07e-06   split x0.82 / x0.70 of it
+# conv 11x9 96->48 k3 s2 d2 p2 abs             cpu32 1.47e-06 / 2.24e-07   exact x1.87 / x1.95   split x1.50 / x1.21
+# conv 9x17 64->100 k1 s2 p2 abs               cpu32 1.16e-06 / 1.55e-07   exact x1.03 / x1.02   split x0.64 / x0.66
+# conv 11x19 64->160 k1 p3 scaled              cpu32 1.54e-06 / 1.44e-07   exact x1.00 / x1.01   split x0.68 / x0.68
+# conv 13x21 128->132 k3 d2 w4 p3 scaled       exact 3.38e-05 / 1.80e-06   split x0.53 / x0.68 of it
+# conv 11x9 96->48 k3 s2 d2 p2 scaled          cpu32 1.23e-06 / 2.09e-07   exact x2.76 / x1.99   split x0.98 / x1.17
+# conv 9x17 64->100 k1 s2 p2 scaled            cpu32 9.69e-07 / 1.42e-07   exact x0.98 / x1.02   split x0.71 / x0.69
+# attention (45, 6, 512) online 17/18/19       cpu32 5.23e-07 / 7.68e-08   exact x1.03 / x0.90   split x0.81 / x0.77
+# attention (33, 1, 128) online 17             every error 0
+# attention (65, 129, 512) online 17/18/19     cpu32 3.51e-07 / 4.76e-08   exact x1.58 / x0.94   split x0.68 / x0.67
+# attention (70, 260, 2048) online 17/18/19    cpu32 8.51e-07 / 4.23e-08   exact x0.76 / x1.00   split x0.43 / x0.66
+# attention (33, 1, 2048) online 17/18/19      every error 0
+# attention (64, 128, 512) online 18           cpu32 3.36e-07 / 4.84e-08   exact x0.92 / x0.93   split x0.63 / x0.64
+# attention (97, 130, 512) online 18           cpu32 5.03e-07 / 4.73e-08   exact x0.84 / x0.95   split x0.65 / x0.66
+# attention (130, 193, 128) online 17          cpu32 7.85e-07 / 4.65e-08   exact x0.84 / x1.05   split x0.39 / x0.67
+# attention (153, 200, 128) online 17 spike    cpu32 2.38e-06 / 1.38e-07   exact x0.94 / x1.04   split x0.60 / x0.60
+# attention (70, 300, 128) online 17 ramp      cpu32 7.92e-06 / 1.60e-06   exact x1.03 / x1.03   split x0.88 / x0.72
+# attention (153, 200, 512) online 19 spike    cpu32 2.31e-06 / 1.30e-07   exact x1.06 / x1.00   split x0.58 / x0.54
+# attention (70, 300, 512) online 19 ramp      cpu32 9.43e-06 / 1.65e-06   exact x0.99 / x1.03   split x0.72 / x0.72
+# attention (153, 200, 512) online 18 spike    cpu32 2.31e-06 / 1.30e-07   exact x1.06 / x1.00   split x0.58 / x0.54
+# attention (70, 300, 512) online 18 ramp      cpu32 9.43e-06 / 1.65e-06   exact x0.99 / x1.03   split x0.72 / x0.72
+# attention (65, 129, 128) online 17 abs       cpu32 6.56e-07 / 1.48e-07   exact x1.08 / x1.03   split x0.74 / x0.75
+# attention (65, 129, 512) online 19/18 abs    cpu32 6.62e-07 / 1.47e-07   exact x1.00 / x1.01   split x0.85 / x0.75
+# attention (65, 129, 128) online 17 scaled    cpu32 1.50e-05 / 1.20e-06   exact x0.84 / x0.86   split x0.75 / x0.59
+# attention (65, 129, 512) online 19/18 scaled cpu32 1.49e-05 / 1.18e-06   exact x0.97 / x0.87   split x0.74 / x0.53
+
+
+def conv_id(case):
+    (H, W, Cin, Cout, KS, stride, dil, act, resid), opts = case[0], case[1]
+    extra = "".join("-%s%d" % (k[0], v) for k, v in sorted(opts.items()) if k not in ("precision", "winograd"))
+    return "%dx%d-%dto%d-k%ds%dd%d%s%s" % (H, W, Cin, Cout, KS, stride, dil, "-w4" if opts.get("winograd") == 4 else "-w0" if opts.get("winograd") == 0 else "", extra)
+
+
+def attention_id(a):
+    Lq, Lk, DV, online, spike, ramp = a
+    return "%dx%dx%d-%d%s%s" % (Lq, Lk, DV, online, "-spike" if spike else "", "-ramp" if ramp else "")
+
 
 def dma_tiles_for(a):
     """The LDS-DMA tile codes the conv a can run on: all but the 256 x 256 tile where Cout does not pad to a multiple of 256."""
@@ -118,6 +240,36 @@ def split_conv(lib, mem, a, opts):
 def stem(lib, mem, hw, opts):
     opcheck.stem(lib, mem, *hw, opts=opts)
     mem.verify()
+
+
+def split_gated_conv(lib, mem, a, opts, wino=False, data="normal"):
+    """A SPLIT_GEMMS / SPLIT_NARROW entry: the full form inside the guards at the route's tolerance, then the activation-free, residual-free
+    form at the fp64-referenced gate.  data != "normal": the gate alone on one of the harder inputs."""
+    H, W, Cin, Cout, KS, stride, dil, _, _ = a
+    if data == "normal":
+        opcheck.conv(lib, mem, *a, tol=2e-4 if wino else 1e-4, opts=opts)
+        mem.verify()
+    errs = opcheck.split_conv(lib, mem, H, W, Cin, Cout, KS, stride, dil, opts, wino=wino, data=data, stays_exact=a in SPLIT_STAYS_EXACT)
+    mem.verify()
+    return errs
+
+
+def split_gated_stem(lib, mem, hw, data="normal"):
+    errs = opcheck.split_stem(lib, mem, *hw, data=data)
+    mem.verify()
+    return errs
+
+
+def split_gated_attention(lib, mem, a, data="normal"):
+    """A SPLIT_ATTENTIONS entry: bias + residual + the LayerNorm strip statistics inside the guards at 1e-4, then softmax(q k^T / 8) v' alone at
+    the fp64-referenced gate."""
+    Lq, Lk, DV, online, spike, ramp = a
+    if data == "normal":
+        opcheck.attention(lib, mem, Lq, Lk, DV, online=online, ln=True, spike=spike, ramp=ramp)
+        mem.verify()
+    errs = opcheck.split_attention(lib, mem, Lq, Lk, DV, online, spike=spike, ramp=ramp, data=data)
+    mem.verify()
+    return errs
 
 
 def f16_conv(lib, mem, a, tile):
@@ -267,10 +419,11 @@ def _head_cls(lib, mem, dx, H, W, Cin, w3, b3, Cout, act, cw, cb, NC, opts, fuse
     return rc, out
 
 
-def head_cls(lib, mem, a):
-    """tdnet_op_head_cls: (a) the classifier inside the Winograd output transform gives the bits of conv + classifier kernel, (b) which is
-    within the Winograd operator tolerance (2e-4) of an fp64 conv -> act -> 1x1: the classifier's rows are N(0, 1) / sqrt(Cout), a
-    normalised projection that does not amplify the hidden map's error."""
+def head_cls(lib, mem, a, opts=WINO):
+    """tdnet_op_head_cls with the conv planned by opts (WINO: the exact-fp32 GEMMs; HEAD_SPLIT: k_gemm_b3, planned with CoutPad =
+    gemm_b3_npad(Cout) instead of conv_cout_pad's value): (a) the classifier inside the Winograd output transform gives the bits of conv + classifier kernel,
+    (b) which is within the Winograd operator tolerance (2e-4) of an fp64 conv -> act -> 1x1: the classifier's rows are N(0, 1) /
+    sqrt(Cout), a normalised projection that does not amplify the hidden map's error."""
     Cout, Cin, (H, W) = a
     x, w3, b3, hid = _head_case(Cout, Cin, H, W)
     g = np.random.default_rng(Cout + Cin + H + W)
@@ -282,18 +435,19 @@ def head_cls(lib, mem, a):
             ref = cw.astype(np.float64) @ (np.maximum(hid, 0.0) if act == 1 else hid) + cb[:, None]
             outs = []
             for fused in (0, 1):
-                rc, out = _head_cls(lib, mem, dx, H, W, Cin, w3, b3, Cout, act, cw, cb, NC, WINO, fused)
+                rc, out = _head_cls(lib, mem, dx, H, W, Cin, w3, b3, Cout, act, cw, cb, NC, opts, fused)
                 lib.check(rc)
                 outs.append(mem.get(out).copy())
             err = float(np.abs(outs[0] - ref).max())
-            assert err <= 2e-4, ("head_cls vs fp64", a, NC, act, err)
-            assert np.array_equal(outs[0], outs[1]), ("head_cls: fused != conv + classifier", a, NC, act, float(np.abs(outs[0] - outs[1]).max()))
+            assert err <= 2e-4, ("head_cls vs fp64", a, opts, NC, act, err)
+            assert np.array_equal(outs[0], outs[1]), ("head_cls: fused != conv + classifier", a, opts, NC, act, float(np.abs(outs[0] - outs[1]).max()))
     mem.verify()
 
 
-def head_cls_refusals(lib, mem):
-    """fused = 1 where a frame would not fuse is an error and launches nothing: 33 classes, 96 hidden channels, a direct-conv plan."""
-    for Cout, NC, opts in ((128, 33, WINO), (96, 19, WINO), (128, 19, DIRECT)):
+def head_cls_refusals(lib, mem, wino=WINO):
+    """fused = 1 where a frame would not fuse is an error and launches nothing: 33 classes, 96 hidden channels, a direct-conv plan.
+    wino: the options of the Winograd plans (WINO or HEAD_SPLIT); the direct plan takes their precision."""
+    for Cout, NC, opts in ((128, 33, wino), (96, 19, wino), (128, 19, dict(wino, **DIRECT))):
         x, w3, b3, _ = _head_case(Cout, 128, 5, 9)
         cw, cb = np.zeros((NC, Cout), np.float32), np.zeros(NC, np.float32)
         rc, _ = _head_cls(lib, mem, mem.put(x), 5, 9, 128, w3, b3, Cout, 1, cw, cb, NC, opts, 1)

@@ -166,3 +166,48 @@ def test_layernorm_fp16_map(lib, mem):
 @pytest.mark.parametrize("a", cases.LAYERNORMS_FLAT)
 def test_layernorm_flat(lib, mem, a):
     cases.layernorm_flat(lib, mem, a)
+
+
+# ---- the split kernels of tdnet_opts.precision = 2 / 3: the full form inside the guards, then the products alone at the fp64-referenced gate ----
+@pytest.mark.parametrize("case", cases.SPLIT_GEMMS, ids=cases.conv_id)
+def test_split_gemm_gate(lib, mem, case):
+    cases.split_gated_conv(lib, mem, *case)
+
+
+@pytest.mark.parametrize("case", cases.SPLIT_NARROW, ids=cases.conv_id)
+def test_split_narrow_conv_gate(lib, mem, case):
+    cases.split_gated_conv(lib, mem, *case)
+
+
+@pytest.mark.parametrize("hw", cases.STEMS)
+def test_split_stem_gate(lib, mem, hw):
+    for data in opcheck.SPLIT_DATA:
+        cases.split_gated_stem(lib, mem, hw, data)
+
+
+@pytest.mark.parametrize("data", opcheck.SPLIT_DATA[1:])
+def test_split_convs_on_harder_inputs(lib, mem, data):
+    for i in cases.SPLIT_GEMMS_HARD:
+        cases.split_gated_conv(lib, mem, *cases.SPLIT_GEMMS[i], data=data)
+    for i in cases.SPLIT_NARROW_HARD:
+        cases.split_gated_conv(lib, mem, *cases.SPLIT_NARROW[i], data=data)
+
+
+@pytest.mark.parametrize("a", cases.SPLIT_ATTENTIONS, ids=cases.attention_id)
+def test_split_attention_gate(lib, mem, a):
+    cases.split_gated_attention(lib, mem, a)
+
+
+@pytest.mark.parametrize("data", opcheck.SPLIT_DATA[1:])
+def test_split_attention_on_harder_inputs(lib, mem, data):
+    for a in cases.SPLIT_ATTENTIONS_HARD:
+        cases.split_gated_attention(lib, mem, a + (False, False), data=data)
+
+
+@pytest.mark.parametrize("a", cases.HEADS)
+def test_head_cls_on_the_split_gemm(lib, mem, a):
+    cases.head_cls(lib, mem, a, cases.HEAD_SPLIT)
+
+
+def test_head_cls_refusals_on_the_split_gemm(lib, mem):
+    cases.head_cls_refusals(lib, mem, cases.HEAD_SPLIT)
