@@ -235,6 +235,32 @@ int  tdnet_score_reset(tdnet_t* h, void* stream);
 int  tdnet_score_export(tdnet_t* h, uint64_t* cm_dev, void* stream);
 /* synchronises `stream`, then copies the matrix to the host; returns the element count (nclass * nclass), <0 on error (capacity too small) */
 long tdnet_score_read(tdnet_t* h, uint64_t* cm_host, size_t capacity, void* stream);
+/* ---- confidence out ------------------------------------------------------------------------------------------------
+ * How sure the network is of a pixel's label, from the frame's LAST kernel (every class's upsampled logit passes through its registers
+ * anyway) instead of 4 * nclass bytes of fp32 logits per pixel and a softmax pass of the caller's.  For a pixel (Y, X) let v_c be the
+ * upsampled fp32 logit of class c -- the label entries' expression (bilinear, align_corners, the coefficients of the uint8 label kernel) --
+ * and l the first-maximum argmax, i.e. the label the label entries give.
+ *   confidence  p = 1 / sum_c exp(v_c - v_l), evaluated in fp32 with the maximum subtracted (logits of +-300 do not overflow);
+ *               conf = (uint8) floor(255 p + 0.5): 255 = certain; nclass = 1 gives 255 everywhere.
+ *   layout      uint8 [H][W] at the network size, at any byte address, like the uint8 label map.
+ *   rejection   is defined on the BYTE, so it is exact: the label written is conf < min_conf ? reject_label : l.  min_conf = 0 (the default)
+ *               rejects nothing: the labels are then the label entries' labels byte for byte, whatever the logits hold.  The confidence
+ *               map itself is never altered by rejection.
+ *   non-finite logits: the confidence byte is unspecified; the labels with min_conf = 0 still equal the label entries'.
+ * tdnet_set_confidence: plain host state of the handle -- no allocation, no synchronisation; per handle (a tdnet_create_shared handle has its
+ * own, starting at 0 / 255); fails on values outside 0..255 and then changes nothing.                                                     */
+int  tdnet_set_confidence(tdnet_t* h, int min_conf /* 0..255, 0 = reject nothing */, int reject_label /* 0..255 */);
+/* tdnet_forward_labels / tdnet_forward_u8_labels with the other last launch: the confidence map is written, and the uint8 label map [H,W]
+ * (with the rejection applied) too unless labels_dev is NULL.  The same frame, the same FIFO step, the same tdnet_last_launch_count.  They
+ * work without a prior tdnet_set_confidence (min_conf = 0), only enqueue, and work inside a hipGraph capture: threshold and reject label are
+ * kernel ARGUMENTS read when the entry enqueues, so a captured graph replays the values in force at capture time, not later ones.  A call
+ * rejected by its argument checks changes nothing (a pending encoded frame stays pending).
+ * Composition with the unfused entries: a reject_label >= nclass is not counted by tdnet_labels_score, and one >= n_colours comes out grey
+ * from tdnet_labels_rgb -- so labels_conf followed by tdnet_labels_score is the confusion matrix over the ACCEPTED pixels.                 */
+int  tdnet_forward_labels_conf(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);
+int  tdnet_forward_u8_labels_conf(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);
+/* the unfused form: labels and confidence of full-resolution NCHW logits [nclass,H,W] the caller already holds (v_c = those logits)      */
+int  tdnet_logits_conf(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -256,6 +282,7 @@ int  tdnet_encode_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, void* s
 int  tdnet_propagate_labels_u8(tdnet_t* h, uint8_t* labels_dev, void* stream);
 int  tdnet_propagate_rgb(tdnet_t* h, uint8_t* rgb_dev, void* stream);   /* see "colour map out" */
 int  tdnet_propagate_score(tdnet_t* h, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);   /* see "score out" */
+int  tdnet_propagate_labels_conf(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);   /* see "confidence out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

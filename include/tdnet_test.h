@@ -109,6 +109,13 @@ int tdnet_op_upsample_argmax_rgb(const float* in_dev, int C, int h, int w, int H
  * label map [H,W] through tdnet_labels_score's kernel (labels_in_u8_dev != NULL; in_dev, h, w and labels_u8_dev are then ignored).  C in 1..256. */
 int tdnet_op_upsample_argmax_score(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* gt_dev, const uint8_t* gt_map, uint8_t* labels_u8_dev,
                                    uint64_t* cm_dev, const uint8_t* labels_in_u8_dev, void* stream);
+/* labels_u8_dev [H,W] (or NULL) and conf_u8_dev [H,W] (include/tdnet.h "confidence out"; any byte addresses) of low-resolution logits [C,h,w]
+ * upsampled to [H,W], through the last kernel of the frame entries that give labels and confidence (logits_full_dev == NULL), or of
+ * full-resolution logits [C,H,W] through the kernel of the unfused entry (logits_full_dev != NULL; in_dev, h, w are then ignored).
+ * min_conf, reject_label in 0..255; C in 1..256.  TDNET_CONF_PASSES=1 / 2 in the environment picks the one-pass / two-pass form of the kernels
+ * (tools/conf_probe.py); unset: the form the library's own entries launch.                                                               */
+int tdnet_op_upsample_argmax_conf(const float* in_dev, int C, int h, int w, int H, int W, uint8_t* labels_u8_dev, uint8_t* conf_u8_dev, int min_conf,
+                                  int reject_label, const float* logits_full_dev, void* stream);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

@@ -86,6 +86,11 @@ SYMBOLS = {
     "tdnet_score_reset": (ctypes.c_int, [c_void_p, c_void_p]),
     "tdnet_score_export": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
     "tdnet_score_read": (ctypes.c_long, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_set_confidence": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tdnet_forward_labels_conf": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_forward_u8_labels_conf": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_labels_conf": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_logits_conf": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -134,6 +139,7 @@ TEST_SYMBOLS = {
     "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_rgb": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_score": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
+    "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_head_cls": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,

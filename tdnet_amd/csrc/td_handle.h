@@ -10,6 +10,7 @@
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
 //   td_ingest.h    (kernels) uint8 image in, uint8 labels out, colour map out; the host side of their tables is at the end of this file
 //   td_score.h     (kernels) score out: the confusion matrix against ground truth; its host side is at the end of this file too
+//   td_conf.h      (kernels) confidence out: the softmax probability of the label as a byte, rejection of low-confidence labels
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -30,6 +31,7 @@
 #include "td_misc.h"
 #include "td_ingest.h"
 #include "td_score.h"
+#include "td_conf.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -331,6 +333,7 @@ struct tdnet {
     U8Input u8;                                                        // tdnet_set_input_u8
     RgbOutput rgb;                                                     // tdnet_set_output_rgb
     ScoreOutput score;                                                 // tdnet_set_score
+    int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
     explicit tdnet(TdWeights* w)

@@ -396,3 +396,30 @@ static int launch_labels_score(const unsigned char* labels, int C, int H, int W,
     else TD_LAUNCH((k_labels_score<false>), grid, dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
     return 0;
 }
+// confidence out (td_conf.h): the label entries' last launch that also writes the confidence byte of every pixel and rejects labels below
+// min_conf (labels may be NULL: confidence only), and the unfused form on full-resolution logits the caller holds.  TD_CONF_ONLINE: the
+// one-pass form (running maximum, rescaled running sum: the gathers once) in the library's entries; the tests' operator entry can run
+// either form (DESIGN.md 5.8 has the measurement).
+#define TD_CONF_ONLINE true
+static int conf_check(int C, int H, int min_conf, int reject) {
+    if (H > 65535) return td_fail("confidence: H = %d is above the grid's 65535 rows", H);
+    if (C < 1 || C > 256) return td_fail("confidence: nclass = %d must be in 1..256", C);
+    if (min_conf < 0 || min_conf > 255 || reject < 0 || reject > 255) return td_fail("confidence: min_conf = %d and reject_label = %d must be in 0..255", min_conf, reject);
+    return 0;
+}
+static int launch_upsample_argmax_conf_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, unsigned char* conf, int min_conf, int reject,
+                                          hipStream_t s, bool online = TD_CONF_ONLINE) {
+    TD_TRY(conf_check(C, H, min_conf, reject));
+    const dim3 grid((W / 4 + 2 + 255) / 256, H);
+    if (online) TD_LAUNCH((k_upsample_argmax_conf_u8<true>), grid, dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
+    else TD_LAUNCH((k_upsample_argmax_conf_u8<false>), grid, dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
+    return 0;
+}
+static int launch_logits_conf_u8(const float* logits, int C, long HW, unsigned char* labels, unsigned char* conf, int min_conf, int reject, hipStream_t s,
+                                 bool online = TD_CONF_ONLINE) {
+    TD_TRY(conf_check(C, 1, min_conf, reject));
+    const dim3 grid((unsigned)((HW / 4 + 2 + 255) / 256));
+    if (online) TD_LAUNCH((k_logits_conf_u8<true>), grid, dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
+    else TD_LAUNCH((k_logits_conf_u8<false>), grid, dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
+    return 0;
+}

@@ -409,6 +409,46 @@ extern "C" long tdnet_score_read(tdnet_t* n, uint64_t* cm_host, size_t capacity,
     TD_HIP(hipMemcpy(cm_host, n->score.cm, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return (long)count;
 }
+// ---- confidence out --------------------------------------------------------------------------------------------------------------------
+// Plain host state of the handle (no allocation, no synchronisation): the threshold and the label that replaces a rejected one.  A *_conf entry
+// passes the values in force when it ENQUEUES its last launch (kernel arguments: a captured graph replays the ones it was captured with).
+extern "C" int tdnet_set_confidence(tdnet_t* n, int min_conf, int reject_label) {
+    if (!n) return td_fail("tdnet_set_confidence: null handle");
+    if (min_conf < 0 || min_conf > 255) return td_fail("tdnet_set_confidence: min_conf = %d must be in 0..255", min_conf);
+    if (reject_label < 0 || reject_label > 255) return td_fail("tdnet_set_confidence: reject_label = %d must be in 0..255", reject_label);
+    n->min_conf = min_conf;
+    n->reject_label = reject_label;
+    return 0;
+}
+// The labels entries with another last launch: the confidence map beside (or, labels == NULL, instead of) the label map.  Same frame, same FIFO
+// step, same number of launches.
+static int forward_labels_conf(tdnet* n, const FrameInput& in, int pos_id, uint8_t* labels, uint8_t* conf, void* stream, const char* who) {
+    TD_ON_DEVICE(n, -1);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (forward_lowres(n, in, pos_id, s, who)) return -1;
+    prof_begin(n, 2, false, 0, s);
+    const int rc = launch_upsample_argmax_conf_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, conf, n->min_conf, n->reject_label, s);
+    prof_end(n, s);
+    TD_HIP(hipGetLastError());
+    return rc;
+}
+extern "C" int tdnet_forward_labels_conf(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, uint8_t* conf, void* stream) {
+    if (!n || !img || !conf) return td_fail("tdnet_forward_labels_conf: null argument");
+    return forward_labels_conf(n, frame_input_f32(img), pos_id, labels, conf, stream, "tdnet_forward_labels_conf");
+}
+extern "C" int tdnet_forward_u8_labels_conf(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, uint8_t* conf, void* stream) {
+    if (!n || !img || !conf) return td_fail("tdnet_forward_u8_labels_conf: null argument");
+    return forward_labels_conf(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, labels, conf, stream, "tdnet_forward_u8_labels_conf");
+}
+extern "C" int tdnet_logits_conf(tdnet_t* n, const float* logits, uint8_t* labels, uint8_t* conf, void* stream) {
+    if (!n || !logits || !conf) return td_fail("tdnet_logits_conf: null argument");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_logits_conf: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(launch_logits_conf_u8(logits, n->cfg.nclass, (long)n->H * n->W, labels, conf, n->min_conf, n->reject_label, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
 // ---- split frame + cache transport (path-parallel single stream) ------------------------------------
 // Rank g of a path-parallel group serves the frames t = g (mod W): it encodes its frame as soon as the image is there, publishes
 // the resulting cache entry, receives the entries of the frames in between from its peers (in frame order) and only then
@@ -496,6 +536,17 @@ extern "C" int tdnet_propagate_score(tdnet_t* n, const uint8_t* gt, uint8_t* lab
     hipStream_t s = (hipStream_t)stream;
     if (propagate_lowres(n, s)) return -1;
     TD_TRY(launch_upsample_argmax_score(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, gt, n->score.dmap, labels, n->score.cm, s));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_propagate_labels_conf(tdnet_t* n, uint8_t* labels, uint8_t* conf, void* stream) {
+    if (!n || !conf) return td_fail("tdnet_propagate_labels_conf: null argument");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_labels_conf: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    LaunchCount count_(n);
+    hipStream_t s = (hipStream_t)stream;
+    if (propagate_lowres(n, s)) return -1;
+    TD_TRY(launch_upsample_argmax_conf_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, conf, n->min_conf, n->reject_label, s));
     TD_HIP(hipGetLastError());
     return 0;
 }

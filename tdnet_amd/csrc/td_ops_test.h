@@ -368,6 +368,23 @@ extern "C" int tdnet_op_upsample_argmax_score(const float* in, int C, int h, int
     hipFree(dmap);
     return rc;
 }
+// Labels (labels_u8 != NULL) and confidence bytes [H][W] of low-resolution logits [C][h][w] (logits_full == NULL: k_upsample_argmax_conf_u8) or of
+// full-resolution logits [C][H][W] (logits_full != NULL: k_logits_conf_u8; in, h, w are ignored).  TDNET_CONF_PASSES=1 / 2 in the environment
+// (tools/conf_probe.py) runs the one-pass / two-pass form of the kernels; unset: the form the library's own entries launch.
+extern "C" int tdnet_op_upsample_argmax_conf(const float* in, int C, int h, int w, int H, int W, uint8_t* labels_u8, uint8_t* conf_u8, int min_conf, int reject_label,
+                                             const float* logits_full, void* stream) {
+    if (!conf_u8) return td_fail("tdnet_op_upsample_argmax_conf: a confidence map expected");
+    if (C < 1 || C > 256 || H < 1 || W < 1) return td_fail("tdnet_op_upsample_argmax_conf: C in 1..256 and a size >= 1 x 1 expected");
+    if (min_conf < 0 || min_conf > 255 || reject_label < 0 || reject_label > 255) return td_fail("tdnet_op_upsample_argmax_conf: min_conf and reject_label in 0..255 expected");
+    if (!logits_full && (!in || h < 1 || w < 1)) return td_fail("tdnet_op_upsample_argmax_conf: logits [C,h,w] expected");
+    const char* env = getenv("TDNET_CONF_PASSES");
+    const bool online = env && *env ? atoi(env) != 2 : TD_CONF_ONLINE;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = logits_full ? launch_logits_conf_u8(logits_full, C, (long)H * W, labels_u8, conf_u8, min_conf, reject_label, s, online)
+                         : launch_upsample_argmax_conf_u8(in, C, h, w, H, W, labels_u8, conf_u8, min_conf, reject_label, s, online);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_conf: device error");
+    return rc;
+}
 // The index table the colour-map kernels sample through (rgb_build's: dataloader.nearest_index restated in C) -> out_host [n_dst] int32.  Host only.
 extern "C" int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host) {
     if (n_src < 1 || n_dst < 1 || !out_host) return td_fail("tdnet_op_nearest_index: sizes >= 1 and a host buffer expected");

@@ -186,6 +186,24 @@ class Engine:
         assert got == out.size, (got, out.size)
         return out
 
+    # ---- confidence out (include/tdnet.h) ----
+    def set_confidence(self, min_conf=0, reject_label=255):
+        """Labels whose confidence byte is below min_conf (0..255; 0 rejects nothing) are written as reject_label (0..255) by the *_conf entries.
+        Plain host state of this handle: no allocation, no synchronisation."""
+        self.lib.check(self.lib.tdnet_set_confidence(self.h, int(min_conf), int(reject_label)))
+
+    def forward_labels_conf(self, img_ptr, pos_id, labels_ptr, conf_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_labels_conf(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(conf_ptr), stream))
+
+    def forward_u8_labels_conf(self, img_ptr, pos_id, labels_ptr, conf_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_labels_conf(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(conf_ptr), stream))
+
+    def propagate_labels_conf(self, labels_ptr, conf_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_labels_conf(self.h, _ptr(labels_ptr), _ptr(conf_ptr), stream))
+
+    def logits_conf(self, logits_ptr, labels_ptr, conf_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_logits_conf(self.h, _ptr(logits_ptr), _ptr(labels_ptr), _ptr(conf_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

@@ -499,6 +499,64 @@ class _TDNetBase(nn.Module):
         for e in self._score_engines("reset_score"):
             e.score_reset(torch.cuda.current_stream(self._engine_key[2]).cuda_stream)
 
+    # ---- confidence out (not in the reference's model; a caller of the reference runs softmax over the full-resolution logits itself) -------
+    # The frame's last kernel also writes, per pixel, the softmax probability of the label as a byte (255 = certain; include/tdnet.h
+    # "confidence out"), and writes reject_label in place of a label whose byte is below the threshold.
+    _confidence = (0, 255)
+
+    def set_confidence(self, threshold=0.0, reject_label=255):
+        """Labels with a softmax probability below `threshold` (0..1) come out as reject_label (0..255) from the *_conf methods.  The comparison is
+        made on the confidence BYTE: min_conf = ceil(255 threshold) clamped to 0..255 (a threshold that is k / 255 up to the rounding of the
+        division gives k); 0 rejects nothing.  Applies to every handle of a batch, the ones created later included."""
+        import math
+        min_conf = min(255, max(0, int(math.ceil(255.0 * float(threshold) - 1e-9))))
+        if int(reject_label) != reject_label or not 0 <= int(reject_label) <= 255:
+            raise RuntimeError("set_confidence(): reject_label must be an integer in 0..255, got %r" % (reject_label,))
+        self._confidence = (min_conf, int(reject_label))
+        return self._confidence
+
+    def forward_labels_conf(self, img, pos_id=0):
+        """forward_labels() with the confidence map: (labels uint8 [N, H, W], conf uint8 [N, H, W])."""
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        shape = (img.shape[0], img.shape[2], img.shape[3])
+        out, conf = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_confidence(*self._confidence)
+            eng.forward_labels_conf(img[i].data_ptr(), pos_id, out[i].data_ptr(), conf[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out, conf
+
+    def forward_labels_conf_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+        """forward_labels_u8() with the confidence map: bytes in, (labels uint8 [N, H, W], conf uint8 [N, H, W]) out."""
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        shape = (img.shape[0], H, W)
+        out, conf = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_confidence(*self._confidence)
+            eng.forward_u8_labels_conf(img[i].data_ptr(), pos_id, out[i].data_ptr(), conf[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std)
+        return out, conf
+
+    def logits_conf(self, logits):
+        """The unfused form: logits [N, nclass, H, W] (fp32, CUDA) of this model -> (labels uint8 [N, H, W], conf uint8 [N, H, W])."""
+        if self._engine is None:
+            raise RuntimeError("logits_conf(): no handle yet")
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(logits) or logits.dim() != 4 or tuple(logits.shape[1:]) != (self.nclass, H, W):
+            raise RuntimeError("logits_conf(): expected logits [N, %d, %d, %d]" % (self.nclass, H, W))
+        logits = logits.contiguous().float()
+        shape = (logits.shape[0], H, W)
+        out, conf = torch.empty(shape, device=logits.device, dtype=torch.uint8), torch.empty(shape, device=logits.device, dtype=torch.uint8)
+        s = torch.cuda.current_stream(logits.device).cuda_stream
+        self._engine.set_confidence(*self._confidence)
+        for i in range(logits.shape[0]):
+            self._engine.logits_conf(logits[i].data_ptr(), out[i].data_ptr(), conf[i].data_ptr(), s)
+        return out, conf
+
     # ---- split frame + cache transport (path-parallel single stream: parallel.PathParallelStream) ------------------
     def encode(self, img, pos_id=0):
         """First half of forward(): backbone + pyramid slice + Encoding; the frame's cache entry is left pending."""
@@ -510,12 +568,22 @@ class _TDNetBase(nn.Module):
         self._pending_shape = (img.shape[2], img.shape[3], img.device)
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
-    def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None):
+    def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None, conf=False):
         """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
         uint8 labels (labels="u8"), the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb) or, with
-        labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score)."""
+        labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score).
+        conf=True: (uint8 labels, uint8 confidence), both [1, H, W], as forward_labels_conf gives them (labels must be left False, True or "u8")."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
+        if conf:
+            if labels in ("rgb", "score"):
+                raise RuntimeError("propagate(conf=True): gives uint8 labels and confidence; labels=%r asks for another last kernel" % (labels,))
+            H, W, dev = self._pending_shape
+            out, cmap = torch.empty((1, H, W), device=dev, dtype=torch.uint8), torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+            self._engine.set_confidence(*self._confidence)
+            self._pending_shape = None
+            self._engine.propagate_labels_conf(out.data_ptr(), cmap.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out, cmap
         if isinstance(labels, str) and labels not in ("u8", "rgb", "score"):
             raise RuntimeError("propagate(): labels must be False, True, \"u8\", \"rgb\" or \"score\"")
         if labels == "score":

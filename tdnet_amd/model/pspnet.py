@@ -59,3 +59,9 @@ class pspnet(_TDNetBase):
 
     def forward_score_u8(self, x, gt_u8, pos_id=None, in_size=None, **kw):
         return super().forward_score_u8(x[-1:], gt_u8[-1:], 0, in_size, **kw)
+
+    def forward_labels_conf(self, x, pos_id=None):
+        return super().forward_labels_conf(x[-1:], 0)
+
+    def forward_labels_conf_u8(self, x, pos_id=None, in_size=None, **kw):
+        return super().forward_labels_conf_u8(x[-1:], 0, in_size, **kw)

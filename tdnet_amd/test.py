@@ -16,6 +16,9 @@ sample of the label map and decode_segmap, byte for byte): the host downloads th
 nearest rule when their size differs; `--gt_map FILE`: 256 integers as text, ground-truth byte -> class id, anything >= 19 ignored; default
 identity): the frame's last kernel counts the confusion matrix, and the four scores and the per-class IoU are printed after the timing block
 as Training/validate.py:91-97 prints them.
+`--conf DIR` has the frame's last kernel also write the confidence map (the softmax probability of every pixel's label as a byte, 255 = certain) and
+saves it at the network size as a grey PNG DIR/folder/name beside the picture; `--min_conf T` (0..1) rejects labels below T: such a pixel gets
+label 255 and therefore decode_segmap's grey (255, 255, 255) in the picture.  Either switch selects the frame-by-frame loop's confidence form.
 """
 import argparse
 import os
@@ -83,6 +86,15 @@ def test(args):
                 raise SystemExit("--gt_map: 256 integers in 0..255 expected, got %d" % gt_map.size)
             gt_map = gt_map.astype(np.uint8)
 
+    conf_dir, min_conf = getattr(args, "conf", None), getattr(args, "min_conf", None)
+    with_conf = conf_dir is not None or min_conf is not None
+    if with_conf:
+        if rgb or gts is not None or getattr(args, "prefetch", False):
+            raise SystemExit("--conf / --min_conf select the frame's last kernel of the frame-by-frame loop: not with --rgb, --gt_path or --prefetch")
+        if min_conf is not None and not 0.0 <= min_conf <= 1.0:
+            raise SystemExit("--min_conf: a probability in 0..1 expected, got %r" % (min_conf,))
+        model.set_confidence(min_conf or 0.0, 255)
+
     def print_scores():                                                # Training/validate.py:91-97
         if gts is None:
             return
@@ -103,6 +115,15 @@ def test(args):
         # cv2.resize(pred, (W//4, H//4), INTER_NEAREST) (test.py:64): nearest sample at floor(dst * scale)
         ys, xs = nearest_index(pred.shape[0], ori_size[1] // 4), nearest_index(pred.shape[1], ori_size[0] // 4)
         write_png(vid_seq.decode_segmap(pred[ys][:, xs]).astype(np.uint8), img_name, folder)
+
+    def save_conf(pred, conf, img_name, folder, ori_size):             # --conf / --min_conf: uint8 labels (255 = rejected -> grey) and the confidence map
+        pred = np.squeeze(pred, axis=0).astype(np.int16)
+        ys, xs = nearest_index(pred.shape[0], ori_size[1] // 4), nearest_index(pred.shape[1], ori_size[0] // 4)
+        write_png(vid_seq.decode_segmap(pred[ys][:, xs]).astype(np.uint8), img_name, folder)
+        if conf_dir is not None:
+            os.makedirs(os.path.join(conf_dir, folder), exist_ok=True)
+            from PIL import Image
+            Image.fromarray(np.squeeze(conf, axis=0)).save(os.path.join(conf_dir, folder, img_name))
 
     def save_rgb(picture, img_name, folder, ori_size):                 # --rgb: the device wrote the picture
         write_png(np.squeeze(picture, axis=0), img_name, folder)
@@ -158,6 +179,8 @@ def test(args):
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size)
+            elif with_conf:
+                output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W)) if u8 else model.forward_labels_conf(image, i % path_num)
             else:
                 output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
             torch.cuda.synchronize()
@@ -168,6 +191,8 @@ def test(args):
                 save(output.cpu().numpy(), img_name, folder, ori_size)
             elif rgb:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
+            elif with_conf:
+                save_conf(output.cpu().numpy(), conf.cpu().numpy(), img_name, folder, ori_size)
             else:
                 save(output.data.max(1)[1].cpu().numpy(), img_name, folder, ori_size)
             print(" Frame {0:2d}   RunningTime/Latency={1:3.5f} s".format(i + 1, elapsed_time))
@@ -195,4 +220,6 @@ if __name__ == "__main__":
     parser.add_argument("--rgb", action="store_true", help="the frame's last kernel writes the quarter-size colour map: no label download, resize or decode_segmap on the host")
     parser.add_argument("--gt_path", nargs="?", type=str, default=None, help="ground-truth PNGs (single channel, named like the frames): score the clip on the device and print the scores")
     parser.add_argument("--gt_map", nargs="?", type=str, default=None, help="text file of 256 integers: ground-truth byte -> class id (>= 19: ignored); default identity")
+    parser.add_argument("--conf", nargs="?", type=str, default=None, help="directory for each frame's confidence map (grey PNG at the network size; 255 = certain)")
+    parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
     test(parser.parse_args())
