@@ -5,10 +5,12 @@
 //   td_handle.h    this file
 //   td_weights.h   strict state_dict inventory, BN folding (fp64), plan_conv (which kernel each conv runs on, decided once), packing, upload,
 //                  the row-parity plan, workspace allocation
-//   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier / upsample):
-//                  a switch on the layer's planned route
+//   td_launch.h    one launch helper per operator (conv / Winograd conv / attention / LayerNorm / pyramid / stem / classifier): a switch on
+//                  the layer's planned route; one per output form, and emit_output, a frame's last launch
 //   td_frame.h     the per-frame kernel sequence: FIFO, cache-only attention chain, row-parity chains, encode / finish, stream placement
-//   td_ingest.h    (kernels) uint8 image in, uint8 labels out, colour map out; the host side of their tables is at the end of this file
+//   td_ingest.h    (kernels) uint8 image in; the host side of its tables is at the end of this file
+//   td_out.h       (kernels) the output stage behind the low-resolution logits: upsample, argmax, int32 / uint8 labels, colour map out (the
+//                  host side of its tables is at the end of this file), and the one class loop td_score.h and td_conf.h share with them
 //   td_score.h     (kernels) score out: the confusion matrix against ground truth; its host side is at the end of this file too
 //   td_conf.h      (kernels) confidence out: the softmax probability of the label as a byte, rejection of low-confidence labels
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
@@ -30,6 +32,7 @@
 #include "td_attn_b3.h"
 #include "td_misc.h"
 #include "td_ingest.h"
+#include "td_out.h"
 #include "td_score.h"
 #include "td_conf.h"
 
@@ -449,7 +452,7 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// colour-map output: the host side of td_ingest.h's k_upsample_argmax_rgb / k_labels_rgb
+// colour-map output: the host side of td_out.h's k_upsample_argmax_rgb / k_labels_rgb
 // ---------------------------------------------------------------------------------------------------------------
 // tdnet_amd/dataloader.py nearest_index with the same operations in the same types: the quotient first, in double, then the product, then
 // truncation, then the clamp.  This is the project's rule (tdnet_amd/test.py's resize of the label map since its first version), not cv2's text.

@@ -1,5 +1,5 @@
 // td_launch.h -- one host-side launch helper per operator of the frame (conv / Winograd conv / attention / plane LayerNorm / pyramid slice /
-// stem / classifier / upsample) + the per-launch profiling records.  Part of the td_model.hip translation unit.
+// stem / classifier) and per output form of its last launch + the per-launch profiling records.  Part of the td_model.hip translation unit.
 #pragma once
 #include "td_weights.h"
 
@@ -342,32 +342,53 @@ static int run_classifier(tdnet* n, const float* x, int HW, int C, int NC, const
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the output stage (td_out.h, td_score.h, td_conf.h): one launch function per output form on the raw sizes -- the tests' operator entries have no
+// handle -- and emit_output, the last launch of a frame, on top of them
+// ---------------------------------------------------------------------------------------------------------------
 static void launch_upsample(const float* in, int C, int h, int w, int H, int W, float* out, hipStream_t s) {
     if (W % 4 == 0 && ((size_t)out & 15) == 0 && H <= 65535 && C <= 65535) TD_LAUNCH(k_upsample_x4, dim3((W / 4 + 255) / 256, H, C), dim3(256), 0, s, in, out, C, h, w, H, W);
     else if (H <= 65535 && C <= 65535) TD_LAUNCH(k_upsample_row, dim3((W / 4 + 2 + 255) / 256, H, C), dim3(256), 0, s, in, out, C, h, w, H, W);
     else TD_LAUNCH(k_upsample, dim3(td_grid_for((long)C * H * W, 256, 256 * 16)), dim3(256), 0, s, in, out, C, h, w, H, W);
 }
-// uint8 labels (nclass <= 256): the fused upsample + argmax, and the argmax of full-resolution logits (td_ingest.h)
-static int launch_upsample_argmax_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, hipStream_t s) {
-    if (H > 65535) return td_fail("uint8 labels: H = %d is above the grid's 65535 rows", H);
-    TD_LAUNCH(k_upsample_argmax_u8, dim3((W / 4 + 2 + 255) / 256, H), dim3(256), 0, s, in, labels, C, h, w, H, W);
+static void launch_upsample_argmax(const float* in, int C, int h, int w, int H, int W, int32_t* labels, hipStream_t s) {
+    TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)H * W)), dim3(256), 0, s, in, labels, C, h, w, H, W);
+}
+static void launch_argmax(const float* logits, int C, long HW, int32_t* labels, hipStream_t s) {
+    TD_LAUNCH(k_argmax, dim3(td_grid_for(HW)), dim3(256), 0, s, logits, labels, C, HW);
+}
+// The byte forms share one geometry: a lane per 4 pixels of a row (+ the head and tail lanes of a row that starts at any address), a grid row
+// per output row (`rows`: H, or the picture's out_height), or the HW pixels of a frame as ONE run; and one class range, a label being a byte.
+static int out_check(const char* what, const char* rows_name, int rows, int C) {
+    if (rows > 65535) return td_fail("%s: %s = %d is above the grid's 65535 rows", what, rows_name, rows);
+    if (C < 1 || C > 256) return td_fail("%s: nclass = %d must be in 1..256", what, C);
     return 0;
 }
-static void launch_argmax_u8(const float* logits, int C, long HW, unsigned char* labels, hipStream_t s) {
-    TD_LAUNCH(k_argmax_u8, dim3((unsigned)((HW / 4 + 2 + 255) / 256)), dim3(256), 0, s, logits, labels, C, HW);
+static dim3 out_grid(int W, int rows) { return dim3((W / 4 + 2 + 255) / 256, rows); }
+static dim3 out_grid_run(long HW) { return dim3((unsigned)((HW / 4 + 2 + 255) / 256)); }
+
+// uint8 labels: the fused upsample + argmax, and the argmax of full-resolution logits
+static int launch_upsample_argmax_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, hipStream_t s) {
+    TD_TRY(out_check("uint8 labels", "H", H, C));
+    TD_LAUNCH(k_upsample_argmax_u8, out_grid(W, H), dim3(256), 0, s, in, labels, C, h, w, H, W);
+    return 0;
+}
+static int launch_argmax_u8(const float* logits, int C, long HW, unsigned char* labels, hipStream_t s) {
+    TD_TRY(out_check("uint8 labels", "H", 1, C));
+    TD_LAUNCH(k_argmax_u8, out_grid_run(HW), dim3(256), 0, s, logits, labels, C, HW);
+    return 0;
 }
 // the colour map [oh][ow][3] of a frame (tdnet_set_output_rgb; `r` = that configuration): from the low-resolution logits, evaluated at the sampled
-// pixels only, or from a uint8 label map [H][W] (td_ingest.h)
+// pixels only, or from a uint8 label map [H][W]
 static int launch_upsample_argmax_rgb(const float* in, int C, int h, int w, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
-    if (r.oh > 65535) return td_fail("colour map: out_height = %d is above the grid's 65535 rows", r.oh);
-    TD_LAUNCH(k_upsample_argmax_rgb, dim3((r.ow / 4 + 2 + 255) / 256, r.oh), dim3(256), 0, s, in, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
+    TD_TRY(out_check("colour map", "out_height", r.oh, C));
+    TD_LAUNCH(k_upsample_argmax_rgb, out_grid(r.ow, r.oh), dim3(256), 0, s, in, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
               C, h, w, r.H, r.W, r.oh, r.ow);
     return 0;
 }
 static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
-    if (r.oh > 65535) return td_fail("colour map: out_height = %d is above the grid's 65535 rows", r.oh);
-    TD_LAUNCH(k_labels_rgb, dim3((r.ow / 4 + 2 + 255) / 256, r.oh), dim3(256), 0, s, labels, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
-              r.W, r.oh, r.ow);
+    TD_TRY(out_check("colour map", "out_height", r.oh, 1));
+    TD_LAUNCH(k_labels_rgb, out_grid(r.ow, r.oh), dim3(256), 0, s, labels, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb, r.W, r.oh, r.ow);
     return 0;
 }
 // score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be
@@ -378,22 +399,18 @@ static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, un
 static int score_lds_bins(int C) { return C <= TD_SCORE_LDS_CLASSES ? C * C : 0; }
 static int launch_upsample_argmax_score(const float* in, int C, int h, int w, int H, int W, const unsigned char* gt, const unsigned char* map,
                                         unsigned char* labels, unsigned long long* cm, hipStream_t s, bool uniform = TD_SCORE_WAVE_UNIFORM) {
-    if (H > 65535) return td_fail("score: H = %d is above the grid's 65535 rows", H);
-    if (C < 1 || C > 256) return td_fail("score: nclass = %d must be in 1..256", C);
+    TD_TRY(out_check("score", "H", H, C));
     const int bins = score_lds_bins(C);
-    const dim3 grid((W / 4 + 2 + 255) / 256, H);
-    if (uniform) TD_LAUNCH((k_upsample_argmax_score<true>), grid, dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
-    else TD_LAUNCH((k_upsample_argmax_score<false>), grid, dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
+    if (uniform) TD_LAUNCH((k_upsample_argmax_score<true>), out_grid(W, H), dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
+    else TD_LAUNCH((k_upsample_argmax_score<false>), out_grid(W, H), dim3(256), bins * sizeof(unsigned), s, in, gt, map, labels, cm, C, h, w, H, W, bins);
     return 0;
 }
 static int launch_labels_score(const unsigned char* labels, int C, int H, int W, const unsigned char* gt, const unsigned char* map, unsigned long long* cm,
                                hipStream_t s, bool uniform = TD_SCORE_WAVE_UNIFORM) {
-    if (H > 65535) return td_fail("score: H = %d is above the grid's 65535 rows", H);
-    if (C < 1 || C > 256) return td_fail("score: nclass = %d must be in 1..256", C);
+    TD_TRY(out_check("score", "H", H, C));
     const int bins = score_lds_bins(C);
-    const dim3 grid((W / 4 + 2 + 255) / 256, H);
-    if (uniform) TD_LAUNCH((k_labels_score<true>), grid, dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
-    else TD_LAUNCH((k_labels_score<false>), grid, dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
+    if (uniform) TD_LAUNCH((k_labels_score<true>), out_grid(W, H), dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
+    else TD_LAUNCH((k_labels_score<false>), out_grid(W, H), dim3(256), bins * sizeof(unsigned), s, labels, gt, map, cm, C, W, bins);
     return 0;
 }
 // confidence out (td_conf.h): the label entries' last launch that also writes the confidence byte of every pixel and rejects labels below
@@ -402,24 +419,52 @@ static int launch_labels_score(const unsigned char* labels, int C, int H, int W,
 // either form (DESIGN.md 5.8 has the measurement).
 #define TD_CONF_ONLINE true
 static int conf_check(int C, int H, int min_conf, int reject) {
-    if (H > 65535) return td_fail("confidence: H = %d is above the grid's 65535 rows", H);
-    if (C < 1 || C > 256) return td_fail("confidence: nclass = %d must be in 1..256", C);
+    TD_TRY(out_check("confidence", "H", H, C));
     if (min_conf < 0 || min_conf > 255 || reject < 0 || reject > 255) return td_fail("confidence: min_conf = %d and reject_label = %d must be in 0..255", min_conf, reject);
     return 0;
 }
 static int launch_upsample_argmax_conf_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, unsigned char* conf, int min_conf, int reject,
                                           hipStream_t s, bool online = TD_CONF_ONLINE) {
     TD_TRY(conf_check(C, H, min_conf, reject));
-    const dim3 grid((W / 4 + 2 + 255) / 256, H);
-    if (online) TD_LAUNCH((k_upsample_argmax_conf_u8<true>), grid, dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
-    else TD_LAUNCH((k_upsample_argmax_conf_u8<false>), grid, dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
+    if (online) TD_LAUNCH((k_upsample_argmax_conf_u8<true>), out_grid(W, H), dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
+    else TD_LAUNCH((k_upsample_argmax_conf_u8<false>), out_grid(W, H), dim3(256), 0, s, in, labels, conf, C, h, w, H, W, min_conf, reject);
     return 0;
 }
 static int launch_logits_conf_u8(const float* logits, int C, long HW, unsigned char* labels, unsigned char* conf, int min_conf, int reject, hipStream_t s,
                                  bool online = TD_CONF_ONLINE) {
     TD_TRY(conf_check(C, 1, min_conf, reject));
-    const dim3 grid((unsigned)((HW / 4 + 2 + 255) / 256));
-    if (online) TD_LAUNCH((k_logits_conf_u8<true>), grid, dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
-    else TD_LAUNCH((k_logits_conf_u8<false>), grid, dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
+    if (online) TD_LAUNCH((k_logits_conf_u8<true>), out_grid_run(HW), dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
+    else TD_LAUNCH((k_logits_conf_u8<false>), out_grid_run(HW), dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
     return 0;
+}
+
+// What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF };
+struct FrameOutput {
+    OutKind kind;
+    void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF: may be NULL) | rgb [oh][ow][3]
+    const unsigned char* gt;       // OUT_SCORE: ground truth [H][W]
+    unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]
+};
+// the handle-side precondition of a form: its tables exist
+static int output_configured(const tdnet* n, OutKind kind, const char* who) {
+    if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
+    if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
+    return 0;
+}
+// The last launch of a frame: the handle's low-resolution logits leave in the form `o`.  Confidence takes the threshold in force NOW (kernel
+// arguments: a captured graph replays the ones it was captured with).
+static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char* who) {
+    TD_TRY(output_configured(n, o.kind, who));
+    const float* in = n->lowres;
+    const int C = n->cfg.nclass, h = n->h, w = n->w, H = n->H, W = n->W;
+    switch (o.kind) {
+    case OUT_LOGITS: launch_upsample(in, C, h, w, H, W, (float*)o.dst, s); return 0;
+    case OUT_LABELS_I32: launch_upsample_argmax(in, C, h, w, H, W, (int32_t*)o.dst, s); return 0;
+    case OUT_LABELS_U8: return launch_upsample_argmax_u8(in, C, h, w, H, W, (unsigned char*)o.dst, s);
+    case OUT_RGB: return launch_upsample_argmax_rgb(in, C, h, w, n->rgb, (unsigned char*)o.dst, s);
+    case OUT_SCORE: return launch_upsample_argmax_score(in, C, h, w, H, W, o.gt, n->score.dmap, (unsigned char*)o.dst, n->score.cm, s);
+    case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
+    }
+    return td_fail("internal: unknown output form");
 }

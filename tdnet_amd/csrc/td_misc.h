@@ -1,5 +1,5 @@
 // td_misc.h -- the HBM-bound tail of the TDNet hot path: layout change, max-pool, pyramid pooling, plane LayerNorm,
-// classifier, bilinear upsample, argmax, key/value sub-sampling.  All NHWC fp32, float4 per lane, grid-stride.
+// classifier, key/value sub-sampling.  All NHWC fp32, float4 per lane, grid-stride.  (Upsample, argmax and the output forms: td_out.h.)
 #pragma once
 #include "td_device.h"
 #include "td_conv.h"   // td_ld4 / td_st4
@@ -224,6 +224,12 @@ TD_KERNEL void k_ppm_pool_conv(const float* __restrict__ rowbins, const float* _
         feat[(size_t)bin * FS + f] = s > 0.f ? s : 0.f;
     }
 }
+// The bilinear expression, align_corners=True, of the pyramid below and of the output stage (td_out.h): a value from its four neighbours
+// v<row><column> with the weights ly / lx of row 1 / column 1.  V = float or f32x4.  The one place it is written: every site rounds alike.
+template <class V>
+TD_DEV V td_bilerp(float ly, float lx, V v00, V v01, V v10, V v11) {
+    return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+}
 // z[p] = [ c4[p][pid*XS : +XS] | bilinear(feat_l)(p)[0:FS] for l = 0..3 ]   (align_corners=True, td4_psp18.py:273-284)
 TD_KERNEL void k_ppm_assemble(const float* __restrict__ c4, const float* __restrict__ feat, float* __restrict__ z,
                               int h, int w, int C, int xs_off, int XS, int FS) {
@@ -250,7 +256,7 @@ TD_KERNEL void k_ppm_assemble(const float* __restrict__ c4, const float* __restr
             const float* fb = feat + (size_t)boff * FS + f;
             const f32x4 v00 = td_ld4(fb + (size_t)(y0 * o + x0) * FS), v01 = td_ld4(fb + (size_t)(y0 * o + x1) * FS);
             const f32x4 v10 = td_ld4(fb + (size_t)(y1 * o + x0) * FS), v11 = td_ld4(fb + (size_t)(y1 * o + x1) * FS);
-            v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+            v = td_bilerp(ly, lx, v00, v01, v10, v11);
         }
         td_st4(z + (size_t)pix * ZC + c, v);
     }
@@ -471,114 +477,6 @@ TD_KERNEL void k_classifier_ct(const float* __restrict__ x, const float* __restr
         if (pp >= HW) continue;
         const float sum = ((red[(0 * nc + k) * 64 + pl] + red[(1 * nc + k) * 64 + pl]) + red[(2 * nc + k) * 64 + pl]) + red[(3 * nc + k) * 64 + pl];
         out[(size_t)(k0 + k) * HW + pp] = sum + bias[k0 + k];
-    }
-}
-
-// ---- bilinear, align_corners=True (td4_psp18.py:227): planar [C][h][w] -> [C][H][W] ------------------------------
-struct UpCoef { int i0, i1; float l; };
-TD_DEV UpCoef td_up_coef(int d, float scale, int n_in) {
-    const float f = scale * (float)d;
-    UpCoef c;
-    c.i0 = (int)f;
-    c.i1 = c.i0 + (c.i0 < n_in - 1 ? 1 : 0);
-    c.l = f - (float)c.i0;
-    return c;
-}
-TD_KERNEL void k_upsample(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const long total = (long)C * H * W;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int X = (int)(i % W);
-        const long t = i / W;
-        const int Y = (int)(t % H), c = (int)(t / H);
-        const UpCoef cy = td_up_coef(Y, sy, h), cx = td_up_coef(X, sx, w);
-        const float* pl = in + (size_t)c * h * w;
-        const float v00 = pl[cy.i0 * w + cx.i0], v01 = pl[cy.i0 * w + cx.i1];
-        const float v10 = pl[cy.i1 * w + cx.i0], v11 = pl[cy.i1 * w + cx.i1];
-        out[i] = (1.f - cy.l) * ((1.f - cx.l) * v00 + cx.l * v01) + cy.l * ((1.f - cx.l) * v10 + cx.l * v11);
-    }
-}
-// Any W (769x1537, the reference's native size, is not a multiple of 4, so the rows of the [C][H][W] output start at every alignment).
-// grid = (ceil((W / 4 + 2) / 256), H, C): row and channel from the block index, vertical coefficients wave-uniform.  Lane q >= 1 of a row
-// writes the 16-byte ALIGNED quad X0 + 4 (q - 1) .. + 3 with one store, X0 = the row's first aligned column; lane 0 writes the X0 head
-// elements, the lane of the last (partial) quad its tail, as scalars.  Same expression per element as k_upsample: bit-identical.
-// (Round 5: the grid-stride k_upsample with a 64-bit div / mod per element took 70 us for the 90 MB of a 769x1537 frame, one 4-byte store
-// per lane 48 us.)
-TD_KERNEL void k_upsample_row(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y, c = blockIdx.z;
-    float* orow = out + ((size_t)c * H + Y) * W;
-    const int X0 = (int)((4u - (unsigned)(((size_t)orow >> 2) & 3u)) & 3u);      // columns before the first 16-byte boundary of this row
-    const int xa = q == 0 ? 0 : X0 + 4 * (q - 1), xb = q == 0 ? (X0 < W ? X0 : W) : (xa + 4 < W ? xa + 4 : W);
-    if (xa >= xb) return;
-    const UpCoef cy = td_up_coef(Y, sy, h);
-    const float* r0 = in + ((size_t)c * h + cy.i0) * w;
-    const float* r1 = in + ((size_t)c * h + cy.i1) * w;
-    auto value = [&](int X) {
-        const UpCoef cx = td_up_coef(X, sx, w);
-        return (1.f - cy.l) * ((1.f - cx.l) * r0[cx.i0] + cx.l * r0[cx.i1]) + cy.l * ((1.f - cx.l) * r1[cx.i0] + cx.l * r1[cx.i1]);
-    };
-    if (q > 0 && xb - xa == 4) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = value(xa + e);
-        td_st4(orow + xa, o);
-    } else {
-        for (int X = xa; X < xb; ++X) orow[X] = value(X);
-    }
-}
-// same arithmetic, 4 consecutive output columns per lane and one 16-byte store (W % 4 == 0): the 159 MB logits write
-// of a 1024x2048 frame is the largest single HBM stream of the path
-// grid = (ceil(W/4 / 256), H, C): the row and channel come from the block index (no 64-bit div/mod per thread), the row's
-// vertical coefficients are wave-uniform
-TD_KERNEL void k_upsample_x4(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const int X4 = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y, c = blockIdx.z;
-    if (X4 >= (W >> 2)) return;
-    const UpCoef cy = td_up_coef(Y, sy, h);
-    const float* r0 = in + ((size_t)c * h + cy.i0) * w;
-    const float* r1 = in + ((size_t)c * h + cy.i1) * w;
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const UpCoef cx = td_up_coef(X4 * 4 + e, sx, w);
-        o[e] = (1.f - cy.l) * ((1.f - cx.l) * r0[cx.i0] + cx.l * r0[cx.i1]) + cy.l * ((1.f - cx.l) * r1[cx.i0] + cx.l * r1[cx.i1]);
-    }
-    td_st4(out + ((size_t)c * H + Y) * W + X4 * 4, o);
-}
-// argmax over classes, first maximum wins (== output.max(1)[1], test.py:61); labels int32 [H][W]
-TD_KERNEL void k_argmax(const float* __restrict__ logits, int32_t* __restrict__ labels, int C, long HW) {
-    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (long)gridDim.x * blockDim.x) {
-        float best = logits[p];
-        int bi = 0;
-        for (int c = 1; c < C; ++c) {
-            const float v = logits[(size_t)c * HW + p];
-            if (v > best) { best = v; bi = c; }
-        }
-        labels[p] = bi;
-    }
-}
-// fused upsample + argmax: the same arithmetic as k_upsample followed by k_argmax, without the [C][H][W] round trip
-TD_KERNEL void k_upsample_argmax(const float* __restrict__ in, int32_t* __restrict__ labels, int C, int h, int w, int H, int W) {
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const long total = (long)H * W;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int X = (int)(i % W), Y = (int)(i / W);
-        const UpCoef cy = td_up_coef(Y, sy, h), cx = td_up_coef(X, sx, w);
-        float best = 0.f;
-        int bi = 0;
-        for (int c = 0; c < C; ++c) {
-            const float* pl = in + (size_t)c * h * w;
-            const float v00 = pl[cy.i0 * w + cx.i0], v01 = pl[cy.i0 * w + cx.i1];
-            const float v10 = pl[cy.i1 * w + cx.i0], v11 = pl[cy.i1 * w + cx.i1];
-            const float v = (1.f - cy.l) * ((1.f - cx.l) * v00 + cx.l * v01) + cy.l * ((1.f - cx.l) * v10 + cx.l * v11);
-            if (c == 0 || v > best) { best = v; bi = c; }
-        }
-        labels[i] = bi;
     }
 }
 

@@ -218,65 +218,59 @@ struct LaunchCount {
     explicit LaunchCount(tdnet* n_) : n(n_), l0(td_launch_count) {}
     ~LaunchCount() { n->launches = (int)(td_launch_count - l0); }
 };
-// The frame entries differ in how the image arrives (FrameInput: fp32 NCHW, or uint8 HWC through tdnet_set_input_u8) and in what leaves
-// (logits, int32 labels, uint8 labels); everything between is one frame.  fp32 and uint8 entries may be mixed frame by frame on one handle.
-static int forward_logits(tdnet* n, const FrameInput& in, int pos_id, float* logits, void* stream, const char* who) {
+// The frame entries differ in how the image arrives -- FrameInput: fp32 NCHW, or uint8 HWC through tdnet_set_input_u8; or not at all: the frame
+// tdnet_encode left pending -- and in what leaves (td_launch.h FrameOutput); everything between is one frame, and ONE tail: frame_out.  fp32 and
+// uint8 entries may be mixed frame by frame on one handle.
+struct FrameSource { const FrameInput* img; int pos_id; };            // img == nullptr: the pending encoded frame (the tdnet_propagate* entries)
+static int propagate_lowres(tdnet* n, hipStream_t s);
+// `who` names the entry in the messages of the frame's checks.  The forward route's last launch is a family-2 profile record; the propagate
+// route stays outside the records (tdnet_last_ms / tdnet_last_launches of a split frame are those of its tdnet_encode half).  A form that
+// is not configured is refused before the frame starts: the FIFO and a pending frame stay as they are.
+static int frame_out(tdnet* n, const FrameSource& src, const FrameOutput& out, void* stream, const char* who) {
     TD_ON_DEVICE(n, -1);
+    TD_TRY(output_configured(n, out.kind, who));
     LaunchCount count_(n);
     hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, in, pos_id, s, who)) return -1;
-    prof_begin(n, 2, false, 0, s);
-    launch_upsample(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, logits, s);
-    prof_end(n, s);
+    if (src.img ? forward_lowres(n, *src.img, src.pos_id, s, who) : propagate_lowres(n, s)) return -1;
+    if (src.img) prof_begin(n, 2, false, 0, s);
+    const int rc = emit_output(n, out, s, who);
+    if (src.img) prof_end(n, s);
     TD_HIP(hipGetLastError());
-    return 0;
+    return rc;
 }
+static int frame_out(tdnet* n, const FrameInput& img, int pos_id, const FrameOutput& out, void* stream, const char* who) {
+    return frame_out(n, FrameSource{&img, pos_id}, out, stream, who);
+}
+static inline FrameInput frame_input_u8(const tdnet* n, const uint8_t* img) { return FrameInput{img, TD_IMG_U8, &n->u8}; }
 extern "C" int tdnet_forward(tdnet_t* n, const float* img, int pos_id, float* logits, void* stream) {
     if (!n || !img || !logits) return td_fail("tdnet_forward: null argument");
-    return forward_logits(n, frame_input_f32(img), pos_id, logits, stream, "tdnet_forward");
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_LOGITS, logits}, stream, "tdnet_forward");
 }
 extern "C" int tdnet_forward_u8(tdnet_t* n, const uint8_t* img, int pos_id, float* logits, void* stream) {
     if (!n || !img || !logits) return td_fail("tdnet_forward_u8: null argument");
-    return forward_logits(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, logits, stream, "tdnet_forward_u8");
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_LOGITS, logits}, stream, "tdnet_forward_u8");
 }
 extern "C" int tdnet_argmax(tdnet_t* n, const float* logits, int32_t* labels, void* stream) {
     if (!n || !logits || !labels) return td_fail("tdnet_argmax: null argument");
     TD_ON_DEVICE(n, -1);
-    TD_LAUNCH(k_argmax, dim3(td_grid_for((long)n->H * n->W)), dim3(256), 0, (hipStream_t)stream, logits, labels, n->cfg.nclass, (long)n->H * n->W);
+    launch_argmax(logits, n->cfg.nclass, (long)n->H * n->W, labels, (hipStream_t)stream);
     TD_HIP(hipGetLastError());
     return 0;
 }
 extern "C" int tdnet_argmax_u8(tdnet_t* n, const float* logits, uint8_t* labels, void* stream) {
     if (!n || !logits || !labels) return td_fail("tdnet_argmax_u8: null argument");
     TD_ON_DEVICE(n, -1);
-    launch_argmax_u8(logits, n->cfg.nclass, (long)n->H * n->W, labels, (hipStream_t)stream);
+    TD_TRY(launch_argmax_u8(logits, n->cfg.nclass, (long)n->H * n->W, labels, (hipStream_t)stream));
     TD_HIP(hipGetLastError());
     return 0;
 }
 extern "C" int tdnet_forward_labels(tdnet_t* n, const float* img, int pos_id, int32_t* labels, void* stream) {
     if (!n || !img || !labels) return td_fail("tdnet_forward_labels: null argument");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, frame_input_f32(img), pos_id, s)) return -1;
-    prof_begin(n, 2, false, 0, s);
-    TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)n->H * n->W)), dim3(256), 0, s, (const float*)n->lowres, labels, n->cfg.nclass,
-              n->h, n->w, n->H, n->W);
-    prof_end(n, s);
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_LABELS_I32, labels}, stream, "tdnet_forward");   // its frame checks have always reported as tdnet_forward
 }
 extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, void* stream) {
     if (!n || !img || !labels) return td_fail("tdnet_forward_u8_labels: null argument");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, s, "tdnet_forward_u8_labels")) return -1;
-    prof_begin(n, 2, false, 0, s);
-    const int rc = launch_upsample_argmax_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, s);
-    prof_end(n, s);
-    TD_HIP(hipGetLastError());
-    return rc;
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_LABELS_U8, labels}, stream, "tdnet_forward_u8_labels");
 }
 // Configuration of the uint8 image input (not a frame call: it may synchronise; idempotent for equal arguments).  The tables live in memory this
 // handle owns; a tdnet_create_shared handle has its own configuration.
@@ -310,30 +304,18 @@ extern "C" int tdnet_set_output_rgb(tdnet_t* n, int out_height, int out_width, c
     return 0;
 }
 // The labels entries with another last launch: the picture instead of the label map.  Same frame, same FIFO step, same number of launches.
-static int forward_rgb(tdnet* n, const FrameInput& in, int pos_id, uint8_t* rgb, void* stream, const char* who) {
-    TD_ON_DEVICE(n, -1);
-    if (!n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, in, pos_id, s, who)) return -1;
-    prof_begin(n, 2, false, 0, s);
-    const int rc = launch_upsample_argmax_rgb(n->lowres, n->cfg.nclass, n->h, n->w, n->rgb, rgb, s);
-    prof_end(n, s);
-    TD_HIP(hipGetLastError());
-    return rc;
-}
 extern "C" int tdnet_forward_rgb(tdnet_t* n, const float* img, int pos_id, uint8_t* rgb, void* stream) {
     if (!n || !img || !rgb) return td_fail("tdnet_forward_rgb: null argument");
-    return forward_rgb(n, frame_input_f32(img), pos_id, rgb, stream, "tdnet_forward_rgb");
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_RGB, rgb}, stream, "tdnet_forward_rgb");
 }
 extern "C" int tdnet_forward_u8_rgb(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* rgb, void* stream) {
     if (!n || !img || !rgb) return td_fail("tdnet_forward_u8_rgb: null argument");
-    return forward_rgb(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, rgb, stream, "tdnet_forward_u8_rgb");
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_RGB, rgb}, stream, "tdnet_forward_u8_rgb");
 }
 extern "C" int tdnet_labels_rgb(tdnet_t* n, const uint8_t* labels, uint8_t* rgb, void* stream) {
     if (!n || !labels || !rgb) return td_fail("tdnet_labels_rgb: null argument");
     TD_ON_DEVICE(n, -1);
-    if (!n->rgb.set) return td_fail("tdnet_labels_rgb: the colour-map output is not configured (call tdnet_set_output_rgb first)");
+    TD_TRY(output_configured(n, OUT_RGB, "tdnet_labels_rgb"));
     TD_TRY(launch_labels_rgb(labels, n->rgb, rgb, (hipStream_t)stream));
     TD_HIP(hipGetLastError());
     return 0;
@@ -354,28 +336,16 @@ extern "C" int tdnet_set_score(tdnet_t* n, const uint8_t* gt_map) {
     n->ws_bytes += n->score.bytes - before;
     return 0;
 }
-#define TD_NEED_SCORE(n, who) do { if (!(n)->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who); } while (0)
+#define TD_NEED_SCORE(n, who) TD_TRY(output_configured(n, OUT_SCORE, who))
 // The labels entries with another last launch: the frame's counts added to the handle's matrix, the label map written too if asked for.  Same
 // frame, same FIFO step, same number of launches.
-static int forward_score(tdnet* n, const FrameInput& in, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream, const char* who) {
-    TD_ON_DEVICE(n, -1);
-    TD_NEED_SCORE(n, who);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, in, pos_id, s, who)) return -1;
-    prof_begin(n, 2, false, 0, s);
-    const int rc = launch_upsample_argmax_score(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, gt, n->score.dmap, labels, n->score.cm, s);
-    prof_end(n, s);
-    TD_HIP(hipGetLastError());
-    return rc;
-}
 extern "C" int tdnet_forward_score(tdnet_t* n, const float* img, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream) {
     if (!n || !img || !gt) return td_fail("tdnet_forward_score: null argument");
-    return forward_score(n, frame_input_f32(img), pos_id, gt, labels, stream, "tdnet_forward_score");
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_SCORE, labels, gt}, stream, "tdnet_forward_score");
 }
 extern "C" int tdnet_forward_u8_score(tdnet_t* n, const uint8_t* img, int pos_id, const uint8_t* gt, uint8_t* labels, void* stream) {
     if (!n || !img || !gt) return td_fail("tdnet_forward_u8_score: null argument");
-    return forward_score(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, gt, labels, stream, "tdnet_forward_u8_score");
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_SCORE, labels, gt}, stream, "tdnet_forward_u8_score");
 }
 extern "C" int tdnet_labels_score(tdnet_t* n, const uint8_t* labels, const uint8_t* gt, void* stream) {
     if (!n || !labels || !gt) return td_fail("tdnet_labels_score: null argument");
@@ -422,24 +392,13 @@ extern "C" int tdnet_set_confidence(tdnet_t* n, int min_conf, int reject_label) 
 }
 // The labels entries with another last launch: the confidence map beside (or, labels == NULL, instead of) the label map.  Same frame, same FIFO
 // step, same number of launches.
-static int forward_labels_conf(tdnet* n, const FrameInput& in, int pos_id, uint8_t* labels, uint8_t* conf, void* stream, const char* who) {
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (forward_lowres(n, in, pos_id, s, who)) return -1;
-    prof_begin(n, 2, false, 0, s);
-    const int rc = launch_upsample_argmax_conf_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, conf, n->min_conf, n->reject_label, s);
-    prof_end(n, s);
-    TD_HIP(hipGetLastError());
-    return rc;
-}
 extern "C" int tdnet_forward_labels_conf(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, uint8_t* conf, void* stream) {
     if (!n || !img || !conf) return td_fail("tdnet_forward_labels_conf: null argument");
-    return forward_labels_conf(n, frame_input_f32(img), pos_id, labels, conf, stream, "tdnet_forward_labels_conf");
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_CONF, labels, nullptr, conf}, stream, "tdnet_forward_labels_conf");
 }
 extern "C" int tdnet_forward_u8_labels_conf(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, uint8_t* conf, void* stream) {
     if (!n || !img || !conf) return td_fail("tdnet_forward_u8_labels_conf: null argument");
-    return forward_labels_conf(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, labels, conf, stream, "tdnet_forward_u8_labels_conf");
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_CONF, labels, nullptr, conf}, stream, "tdnet_forward_u8_labels_conf");
 }
 extern "C" int tdnet_logits_conf(tdnet_t* n, const float* logits, uint8_t* labels, uint8_t* conf, void* stream) {
     if (!n || !logits || !conf) return td_fail("tdnet_logits_conf: null argument");
@@ -477,7 +436,7 @@ extern "C" int tdnet_encode(tdnet_t* n, const float* img, int pos_id, void* stre
 }
 extern "C" int tdnet_encode_u8(tdnet_t* n, const uint8_t* img, int pos_id, void* stream) {
     if (!n || !img) return td_fail("tdnet_encode_u8: null argument");
-    return encode_impl(n, FrameInput{img, TD_IMG_U8, &n->u8}, pos_id, stream, "tdnet_encode_u8");
+    return encode_impl(n, frame_input_u8(n, img), pos_id, stream, "tdnet_encode_u8");
 }
 static int propagate_lowres(tdnet* n, hipStream_t s) {
     if (n->pending_slot < 0) return td_fail("tdnet_propagate: no encoded frame (call tdnet_encode first)");
@@ -486,69 +445,31 @@ static int propagate_lowres(tdnet* n, hipStream_t s) {
     if ((steady && launch_chain_now(n, L, s)) || finish_frame(n, L, steady, s)) { rejoin_streams(n, s); n->pending_slot = n->pending_pos = -1; return -1; }
     return 0;
 }
+static const FrameSource pending_frame = {nullptr, -1};
 extern "C" int tdnet_propagate(tdnet_t* n, float* logits, void* stream) {
     if (!n || !logits) return td_fail("tdnet_propagate: null argument");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    launch_upsample(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, logits, s);
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, pending_frame, FrameOutput{OUT_LOGITS, logits}, stream, "tdnet_propagate");
 }
 extern "C" int tdnet_propagate_labels(tdnet_t* n, int32_t* labels, void* stream) {
     if (!n || !labels) return td_fail("tdnet_propagate_labels: null argument");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)n->H * n->W)), dim3(256), 0, s, (const float*)n->lowres, labels, n->cfg.nclass,
-              n->h, n->w, n->H, n->W);
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, pending_frame, FrameOutput{OUT_LABELS_I32, labels}, stream, "tdnet_propagate_labels");
 }
 extern "C" int tdnet_propagate_labels_u8(tdnet_t* n, uint8_t* labels, void* stream) {
     if (!n || !labels) return td_fail("tdnet_propagate_labels_u8: null argument");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    TD_TRY(launch_upsample_argmax_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, s));
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, pending_frame, FrameOutput{OUT_LABELS_U8, labels}, stream, "tdnet_propagate_labels_u8");
 }
 extern "C" int tdnet_propagate_rgb(tdnet_t* n, uint8_t* rgb, void* stream) {
     if (!n || !rgb) return td_fail("tdnet_propagate_rgb: null argument");
-    TD_ON_DEVICE(n, -1);
-    if (!n->rgb.set) return td_fail("tdnet_propagate_rgb: the colour-map output is not configured (call tdnet_set_output_rgb first)");
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    TD_TRY(launch_upsample_argmax_rgb(n->lowres, n->cfg.nclass, n->h, n->w, n->rgb, rgb, s));
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, pending_frame, FrameOutput{OUT_RGB, rgb}, stream, "tdnet_propagate_rgb");
 }
 extern "C" int tdnet_propagate_score(tdnet_t* n, const uint8_t* gt, uint8_t* labels, void* stream) {
     if (!n || !gt) return td_fail("tdnet_propagate_score: null argument");
-    TD_ON_DEVICE(n, -1);
-    TD_NEED_SCORE(n, "tdnet_propagate_score");
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    TD_TRY(launch_upsample_argmax_score(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, gt, n->score.dmap, labels, n->score.cm, s));
-    TD_HIP(hipGetLastError());
-    return 0;
+    return frame_out(n, pending_frame, FrameOutput{OUT_SCORE, labels, gt}, stream, "tdnet_propagate_score");
 }
 extern "C" int tdnet_propagate_labels_conf(tdnet_t* n, uint8_t* labels, uint8_t* conf, void* stream) {
     if (!n || !conf) return td_fail("tdnet_propagate_labels_conf: null argument");
-    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_labels_conf: weights not finalized");
-    TD_ON_DEVICE(n, -1);
-    LaunchCount count_(n);
-    hipStream_t s = (hipStream_t)stream;
-    if (propagate_lowres(n, s)) return -1;
-    TD_TRY(launch_upsample_argmax_conf_u8(n->lowres, n->cfg.nclass, n->h, n->w, n->H, n->W, labels, conf, n->min_conf, n->reject_label, s));
-    TD_HIP(hipGetLastError());
-    return 0;
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_labels_conf: weights not finalized");   // (its siblings leave this to "no encoded frame")
+    return frame_out(n, pending_frame, FrameOutput{OUT_CONF, labels, nullptr, conf}, stream, "tdnet_propagate_labels_conf");
 }
 extern "C" int tdnet_cache_dims(const tdnet_t* n, int* Lk, int* dk, int* dv) {
     if (!n) return td_fail("tdnet_cache_dims: null handle");

@@ -324,7 +324,7 @@ extern "C" long tdnet_op_stem_image(const float* img_f32, const uint8_t* src_u8,
 extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, int H, int W, int32_t* labels_i32, uint8_t* labels_u8, void* stream) {
     if (C < 1 || C > 256) return td_fail("tdnet_op_upsample_argmax: C must be in 1..256");
     hipStream_t s = (hipStream_t)stream;
-    if (labels_i32) TD_LAUNCH(k_upsample_argmax, dim3(td_grid_for((long)H * W)), dim3(256), 0, s, in, labels_i32, C, h, w, H, W);
+    if (labels_i32) launch_upsample_argmax(in, C, h, w, H, W, labels_i32, s);
     if (labels_u8) TD_TRY(launch_upsample_argmax_u8(in, C, h, w, H, W, labels_u8, s));
     TD_HIP(hipStreamSynchronize(s));
     TD_HIP(hipGetLastError());

@@ -1,0 +1,258 @@
+// td_out.h -- the output stage: what happens behind the low-resolution logits [C][h][w].  The x8 bilinear upsample (align_corners=True), the
+// argmax over classes, and the forms in which a frame's labels leave: fp32 logits, int32 labels, uint8 labels, a colour map.  td_score.h
+// (confusion counts) and td_conf.h (confidence bytes) add their accumulator and store to the same body.
+//
+// ONE definition each of what every output form must agree on bit for bit:
+//   td_bilerp (td_misc.h)  the bilinear expression of a pixel from its four source values
+//   td_up_coef             source index pair and weight of an output row / column
+//   td_first_max           the argmax rule: the first maximum wins
+//   td_up_classes          the per-lane body of the sampled kernels: 4 pixels of a row, every class's upsampled logit handed to a step
+//   td_u8_run / _store     the lane split of a byte row that starts at any address, and its packed store
+//   td_px4_*               4 pixels of a full-resolution plane, one 16-byte load where the plane allows
+// The library and the emulator are both built with -ffp-contract=off: the one inlined expression rounds the same at every site.
+// Plain C++ on the TD_* macros: compiles unchanged under tests/emu/td_device.h.
+#pragma once
+#include "td_device.h"
+#include "td_conv.h"   // td_ld4 / td_st4
+#include "td_misc.h"   // td_bilerp
+
+// ---- bilinear, align_corners=True (td4_psp18.py:227): planar [C][h][w] -> [C][H][W] ------------------------------
+struct UpCoef { int i0, i1; float l; };
+TD_DEV UpCoef td_up_coef(int d, float scale, int n_in) {
+    const float f = scale * (float)d;
+    UpCoef c;
+    c.i0 = (int)f;
+    c.i1 = c.i0 + (c.i0 < n_in - 1 ? 1 : 0);
+    c.l = f - (float)c.i0;
+    return c;
+}
+TD_DEV float td_up_scale(int n_in, int n_out) { return (n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
+// output column X of an output row whose source rows are r0 (cy.i0) and r1 (cy.i1)
+TD_DEV float td_up_value(const float* r0, const float* r1, const UpCoef& cy, int X, float sx, int w) {
+    const UpCoef cx = td_up_coef(X, sx, w);
+    return td_bilerp(cy.l, cx.l, r0[cx.i0], r0[cx.i1], r1[cx.i0], r1[cx.i1]);
+}
+TD_KERNEL void k_upsample(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
+    const float sy = td_up_scale(h, H), sx = td_up_scale(w, W);
+    const long total = (long)C * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int X = (int)(i % W);
+        const long t = i / W;
+        const int Y = (int)(t % H), c = (int)(t / H);
+        const UpCoef cy = td_up_coef(Y, sy, h);
+        const float* pl = in + (size_t)c * h * w;
+        out[i] = td_up_value(pl + cy.i0 * w, pl + cy.i1 * w, cy, X, sx, w);
+    }
+}
+// Any W (769x1537, the reference's native size, is not a multiple of 4, so the rows of the [C][H][W] output start at every alignment).
+// grid = (ceil((W / 4 + 2) / 256), H, C): row and channel from the block index, vertical coefficients wave-uniform.  Lane q >= 1 of a row
+// writes the 16-byte ALIGNED quad X0 + 4 (q - 1) .. + 3 with one store, X0 = the row's first aligned column; lane 0 writes the X0 head
+// elements, the lane of the last (partial) quad its tail, as scalars.  Same expression per element as k_upsample: bit-identical.
+// (Round 5: the grid-stride k_upsample with a 64-bit div / mod per element took 70 us for the 90 MB of a 769x1537 frame, one 4-byte store
+// per lane 48 us.)
+TD_KERNEL void k_upsample_row(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
+    const float sy = td_up_scale(h, H), sx = td_up_scale(w, W);
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y, c = blockIdx.z;
+    float* orow = out + ((size_t)c * H + Y) * W;
+    const int X0 = (int)((4u - (unsigned)(((size_t)orow >> 2) & 3u)) & 3u);      // columns before the first 16-byte boundary of this row
+    const int xa = q == 0 ? 0 : X0 + 4 * (q - 1), xb = q == 0 ? (X0 < W ? X0 : W) : (xa + 4 < W ? xa + 4 : W);
+    if (xa >= xb) return;
+    const UpCoef cy = td_up_coef(Y, sy, h);
+    const float* r0 = in + ((size_t)c * h + cy.i0) * w;
+    const float* r1 = in + ((size_t)c * h + cy.i1) * w;
+    if (q > 0 && xb - xa == 4) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = td_up_value(r0, r1, cy, xa + e, sx, w);
+        td_st4(orow + xa, o);
+    } else {
+        for (int X = xa; X < xb; ++X) orow[X] = td_up_value(r0, r1, cy, X, sx, w);
+    }
+}
+// same arithmetic, 4 consecutive output columns per lane and one 16-byte store (W % 4 == 0): the 159 MB logits write
+// of a 1024x2048 frame is the largest single HBM stream of the path
+// grid = (ceil(W/4 / 256), H, C): the row and channel come from the block index (no 64-bit div/mod per thread), the row's
+// vertical coefficients are wave-uniform
+TD_KERNEL void k_upsample_x4(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, int H, int W) {
+    const float sy = td_up_scale(h, H), sx = td_up_scale(w, W);
+    const int X4 = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y, c = blockIdx.z;
+    if (X4 >= (W >> 2)) return;
+    const UpCoef cy = td_up_coef(Y, sy, h);
+    const float* r0 = in + ((size_t)c * h + cy.i0) * w;
+    const float* r1 = in + ((size_t)c * h + cy.i1) * w;
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = td_up_value(r0, r1, cy, X4 * 4 + e, sx, w);
+    td_st4(out + ((size_t)c * H + Y) * W + X4 * 4, o);
+}
+
+// ---- argmax: the first maximum wins (== output.max(1)[1], test.py:61) ---------------------------------------------------------------
+// Class c's value v joins the running maximum `best` (class `bi`) of the classes 0 .. c - 1; true if it took its place.
+TD_DEV bool td_first_max(int c, float v, float& best, int& bi) {
+    const bool up = c == 0 || v > best;
+    if (up) { best = v; bi = c; }
+    return up;
+}
+// labels int32 [H][W] of full-resolution logits
+TD_KERNEL void k_argmax(const float* __restrict__ logits, int32_t* __restrict__ labels, int C, long HW) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (long)gridDim.x * blockDim.x) {
+        float best = 0.f;
+        int bi = 0;
+        for (int c = 0; c < C; ++c) td_first_max(c, logits[(size_t)c * HW + p], best, bi);
+        labels[p] = bi;
+    }
+}
+// fused upsample + argmax: the same arithmetic as k_upsample followed by k_argmax, without the [C][H][W] round trip
+TD_KERNEL void k_upsample_argmax(const float* __restrict__ in, int32_t* __restrict__ labels, int C, int h, int w, int H, int W) {
+    const float sy = td_up_scale(h, H), sx = td_up_scale(w, W);
+    const long total = (long)H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int X = (int)(i % W), Y = (int)(i / W);
+        const UpCoef cy = td_up_coef(Y, sy, h), cx = td_up_coef(X, sx, w);
+        float best = 0.f;
+        int bi = 0;
+        for (int c = 0; c < C; ++c) {
+            const float* pl = in + (size_t)c * h * w;
+            td_first_max(c, td_bilerp(cy.l, cx.l, pl[cy.i0 * w + cx.i0], pl[cy.i0 * w + cx.i1], pl[cy.i1 * w + cx.i0], pl[cy.i1 * w + cx.i1]), best, bi);
+        }
+        labels[i] = bi;
+    }
+}
+
+// ---- the sampled kernels' per-lane body ----------------------------------------------------------------------------------------------
+// A lane's 4 pixels of one output row: the upsampled logit of every class c at full-resolution pixel (Y, xsrc(e)), e = 0 .. 3, handed to
+// step(c, e, v) class by class -- k_upsample_argmax's expression, four gathers per pixel and class.  Y and the vertical coefficients are
+// wave-uniform where Y comes from the block index.  The callers keep their accumulators as plain locals and the step is called inside the
+// unrolled loop over e: everything stays in registers (a coefficient struct handed around cost 10 - 25 VGPRs).
+template <class XSrc, class Step>
+TD_DEV void td_up_classes(const float* __restrict__ in, int C, int h, int w, int H, int W, int Y, XSrc xsrc, Step step) {
+    const float sy = td_up_scale(h, H), sx = td_up_scale(w, W);
+    const UpCoef cy = td_up_coef(Y, sy, h);
+    UpCoef cx[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cx[e] = td_up_coef(xsrc(e), sx, w);
+    for (int c = 0; c < C; ++c) {
+        const float* pl = in + (size_t)c * h * w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            step(c, e, td_bilerp(cy.l, cx[e].l, pl[cy.i0 * w + cx[e].i0], pl[cy.i0 * w + cx[e].i1], pl[cy.i1 * w + cx[e].i0], pl[cy.i1 * w + cx[e].i1]));
+    }
+}
+// pixel e of a lane's run that starts at xa, in a row (or plane) of n: the lanes of a partial run repeat the last pixel
+TD_DEV long td_run_px(long xa, int e, long n) { return xa + e < n ? xa + e : n - 1; }
+
+// ---- uint8 labels ------------------------------------------------------------------------------------------------------------------
+// A lane's run of a label row of W bytes that starts at `row`: lane 0 the bytes in front of the first 4-byte boundary, lane q >= 1 the
+// aligned quad behind it (k_upsample_row's split, in bytes): [xa, xb)
+TD_DEV void td_u8_run(const unsigned char* row, long q, long W, long* xa, long* xb) {
+    const long X0 = (long)((4u - (unsigned)((size_t)row & 3u)) & 3u);
+    *xa = q == 0 ? 0 : X0 + 4 * (q - 1);
+    *xb = q == 0 ? (X0 < W ? X0 : W) : (*xa + 4 < W ? *xa + 4 : W);
+}
+// The bytes b[0 .. xb - xa) of a run: one 4-byte store where the run is a whole quad at an aligned address -- every full quad of the row the
+// split followed (lane 0's run is at most 3 bytes), and those of a second row of the same pixels (td_conf.h) that shares its alignment.
+TD_DEV void td_u8_store(unsigned char* row, long xa, long xb, const int* b) {
+    if (xb - xa == 4 && (((size_t)(row + xa)) & 3u) == 0)
+        *reinterpret_cast<unsigned*>(row + xa) = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+    else
+        for (long X = xa; X < xb; ++X) row[X] = (unsigned char)b[X - xa];
+}
+// Fused upsample + argmax with uint8 labels [H][W] (nclass <= 256), laid out like k_upsample_row: grid = (ceil((W / 4 + 2) / 256), H), row
+// from the block index, 4 consecutive pixels per lane packed into one 4-byte store where the row address allows (W is odd at 769x1537: the
+// rows start at every alignment), scalar head and tail.
+TD_KERNEL void k_upsample_argmax_u8(const float* __restrict__ in, unsigned char* __restrict__ labels, int C, int h, int w, int H, int W) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y;
+    unsigned char* orow = labels + (size_t)Y * W;
+    long xa, xb;
+    td_u8_run(orow, q, W, &xa, &xb);
+    if (xa >= xb) return;
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    td_up_classes(in, C, h, w, H, W, Y, [&](int e) { return (int)td_run_px(xa, e, W); }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+    td_u8_store(orow, xa, xb, bi);
+}
+// 4 pixels pa .. pa + 3 of a full-resolution plane of HW floats: one 16-byte load where the planes allow it (HW % 4 == 0, 16-byte aligned
+// logits and a whole quad that starts at a multiple of 4), scalar loads otherwise
+TD_DEV bool td_px4_vec(const float* logits, long HW, long pa, long pb) { return (HW & 3) == 0 && (((size_t)logits) & 15) == 0 && (pa & 3) == 0 && pb - pa == 4; }
+TD_DEV f32x4 td_px4_load(const float* pl, long pa, long HW, bool vec) {
+    if (vec) return td_ld4(pl + pa);
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = pl[td_run_px(pa, e, HW)];
+    return v;
+}
+// argmax over classes with uint8 labels: k_argmax's rule on 4 consecutive pixels per lane, the HW pixels as one run
+TD_KERNEL void k_argmax_u8(const float* __restrict__ logits, unsigned char* __restrict__ labels, int C, long HW) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long pa, pb;
+    td_u8_run(labels, q, HW, &pa, &pb);
+    if (pa >= pb) return;
+    const bool vec = td_px4_vec(logits, HW, pa, pb);
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    for (int c = 0; c < C; ++c) {
+        const f32x4 v = td_px4_load(logits + (size_t)c * HW, pa, HW, vec);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) td_first_max(c, v[e], best[e], bi[e]);
+    }
+    td_u8_store(labels, pa, pb, bi);
+}
+
+// ---- colour map out ----------------------------------------------------------------------------------------------------------------
+// What the frame loop does on the host behind the labels (Testing/test.py:61-71; tdnet_amd/test.py save()): the nearest-index sample of the label
+// map to [oh][ow] and decode_segmap.  rgb [oh][ow][3] bytes = lut[labels[ys[oy]][xs[ox]]]: ys / xs are dataloader.nearest_index's tables, built on
+// the host (td_handle.h rgb_build), lut 256 words r | g << 8 | b << 16 (rows >= n_colours grey (l, l, l), as decode_segmap leaves them).
+// A row is 3 ow bytes and starts at any byte address; 4 pixels = 12 bytes = three 4-byte words where row + 3 x is 4-byte aligned, i.e. from
+// x = row (mod 4) on (3 x = -row  <=>  x = row (mod 4), 3 being its own inverse).  Lane 0 of a row: the row & 3 pixels in front of the first such
+// group; lane q >= 1: the group behind it: [xa, xb)
+TD_DEV void td_rgb_run(const unsigned char* row, long q, long ow, long* xa, long* xb) {
+    const long X0 = (long)((size_t)row & 3u);
+    *xa = q == 0 ? 0 : X0 + 4 * (q - 1);
+    *xb = q == 0 ? (X0 < ow ? X0 : ow) : (*xa + 4 < ow ? *xa + 4 : ow);
+}
+TD_DEV void td_rgb_store(unsigned char* row, long q, long xa, long xb, const unsigned* px) {   // px[e]: the lut word of pixel xa + e
+    if (q > 0 && xb - xa == 4) {
+        unsigned* o = reinterpret_cast<unsigned*>(row + 3 * xa);
+        o[0] = px[0] | (px[1] << 24);
+        o[1] = (px[1] >> 8) | (px[2] << 16);
+        o[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+        for (long X = xa; X < xb; ++X) {
+            const unsigned p = px[X - xa];
+            row[3 * X] = (unsigned char)p; row[3 * X + 1] = (unsigned char)(p >> 8); row[3 * X + 2] = (unsigned char)(p >> 16);
+        }
+    }
+}
+// The frame's last launch when a picture is asked for: the x8 bilinear upsample evaluated ONLY at the sampled pixels (Y, X) = (ys[oy], xs[ox]),
+// and the colour looked up.  grid = (ceil((ow / 4 + 2) / 256), oh): row from the block index, Y and the vertical coefficients wave-uniform.
+TD_KERNEL void k_upsample_argmax_rgb(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                     unsigned char* __restrict__ rgb, int C, int h, int w, int H, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = rgb + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+    unsigned px[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = lut[bi[e] & 255];
+    td_rgb_store(orow, q, xa, xb, px);
+}
+// The same picture from a uint8 label map [H][W] the caller already holds (same store layout)
+TD_KERNEL void k_labels_rgb(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                            unsigned char* __restrict__ rgb, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = rgb + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
+    unsigned px[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = lut[lrow[xs[td_run_px(xa, e, ow)]]];
+    td_rgb_store(orow, q, xa, xb, px);
+}

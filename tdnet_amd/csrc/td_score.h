@@ -17,8 +17,7 @@
 // there is no inline assembly here: LDS atomics, 64-bit atomicAdd and ordinary vector stores from plain C++.
 #pragma once
 #include "td_device.h"
-#include "td_misc.h"     // UpCoef / td_up_coef
-#include "td_ingest.h"   // td_u8_run / td_u8_store
+#include "td_out.h"      // td_up_classes / td_first_max / td_u8_run / td_u8_store
 
 #define TD_SCORE_LDS_CLASSES 64                                        // private LDS histogram up to 64 x 64 x 4 bytes = 16 KiB per workgroup
 #define TD_SCORE_NONE 0xffffffffu                                      // key of a pixel that is not counted
@@ -109,9 +108,9 @@ TD_DEV void td_score_flush(const unsigned* hist, int bins, unsigned long long* c
     }
 }
 
-// The frame's last launch when a score is asked for: k_upsample_argmax_u8's expression, first-maximum rule, grid and (labels != NULL) store
-// layout -- the label under every pixel is the number the label entries give -- and cm[map[gt]][label] += 1 where map[gt] < C.
-// gt: [H][W] bytes at ANY byte address, read byte by byte (its rows need not share the label rows' alignment).  map: 256 bytes.
+// The frame's last launch when a score is asked for: the output stage's body (td_out.h td_up_classes), first-maximum rule, k_upsample_argmax_u8's
+// grid and (labels != NULL) store -- the label under every pixel is the number the label entries give -- and cm[map[gt]][label] += 1 where
+// map[gt] < C.  gt: [H][W] bytes at ANY byte address, read byte by byte (its rows need not share the label rows' alignment).  map: 256 bytes.
 // lds_bins: C * C (private LDS histogram of that many uint32, the launch's dynamic LDS) or 0 (straight into cm).
 // grid = (ceil((W / 4 + 2) / 256), H); no lane leaves before the flush: the barriers and the wave test need all of them.
 template <bool UNIFORM>
@@ -120,8 +119,6 @@ TD_KERNEL void k_upsample_argmax_score(const float* __restrict__ in, const unsig
     TD_DYN_LDS(smem);
     unsigned* hist = lds_bins ? reinterpret_cast<unsigned*>(smem) : nullptr;
     td_score_zero(hist, lds_bins);
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
     const int q = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y;
     // the lanes' runs follow the LABEL rows' alignment whether or not the map is written: the same split as k_upsample_argmax_u8
     const unsigned char* arow = reinterpret_cast<const unsigned char*>((size_t)labels + (size_t)Y * W);
@@ -129,23 +126,10 @@ TD_KERNEL void k_upsample_argmax_score(const float* __restrict__ in, const unsig
     td_u8_run(arow, q, W, &xa, &xb);
     unsigned key[4] = {TD_SCORE_NONE, TD_SCORE_NONE, TD_SCORE_NONE, TD_SCORE_NONE};
     if (xa < xb) {
-        const UpCoef cy = td_up_coef(Y, sy, h);
-        UpCoef cx[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) cx[e] = td_up_coef((int)(xa + e < W ? xa + e : W - 1), sx, w);
         float best[4] = {0.f, 0.f, 0.f, 0.f};
         int bi[4] = {0, 0, 0, 0};
-        for (int c = 0; c < C; ++c) {
-            const float* pl = in + (size_t)c * h * w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v00 = pl[cy.i0 * w + cx[e].i0], v01 = pl[cy.i0 * w + cx[e].i1];
-                const float v10 = pl[cy.i1 * w + cx[e].i0], v11 = pl[cy.i1 * w + cx[e].i1];
-                const float v = (1.f - cy.l) * ((1.f - cx[e].l) * v00 + cx[e].l * v01) + cy.l * ((1.f - cx[e].l) * v10 + cx[e].l * v11);
-                if (c == 0 || v > best[e]) { best[e] = v; bi[e] = c; }
-            }
-        }
-        if (labels) td_u8_store(labels + (size_t)Y * W, q, xa, xb, bi);
+        td_up_classes(in, C, h, w, H, W, Y, [&](int e) { return (int)td_run_px(xa, e, W); }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+        if (labels) td_u8_store(labels + (size_t)Y * W, xa, xb, bi);
         const unsigned char* grow = gt + (size_t)Y * W;
 #pragma unroll
         for (int e = 0; e < 4; ++e)

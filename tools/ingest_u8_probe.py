@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU-box probe for the byte ends of a frame (csrc/td_ingest.h), to be run under `rocprofv3 --kernel-trace --stats` for the per-kernel times
+"""GPU-box probe for the byte ends of a frame (csrc/td_ingest.h in, csrc/td_out.h out), to be run under `rocprofv3 --kernel-trace --stats` for the per-kernel times
 (the ops themselves allocate and synchronise):
 
   ingest    k_ingest_u8 at HxW same-size and from --src-size, beside k_nchw3_to_rgbpad / k_nchw3_to_nhwc4 on an fp32 image of the same

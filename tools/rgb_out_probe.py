@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU-box probe for the colour-map output (csrc/td_ingest.h k_upsample_argmax_rgb; include/tdnet.h "colour map out"): what does asking a frame
+"""GPU-box probe for the colour-map output (csrc/td_out.h k_upsample_argmax_rgb; include/tdnet.h "colour map out"): what does asking a frame
 for its quarter-size picture instead of its uint8 label map change, on the device and in the frame loop?
 
   frame    device ms per steady-state frame (HIP events around `--frames` frames, no host work between them) of forward_labels_u8 against
