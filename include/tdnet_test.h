@@ -45,6 +45,26 @@ int tdnet_op_conv2d_f16io(const float* in_dev, int H, int W, int Cin, const floa
  * tdnet_op_conv2d_f16io; the LDS-DMA ones need in16.                                                                                                  */
 int tdnet_op_conv2d_f16mix(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host,
                            int Cout, int KS, int stride, int dil, const float* resid_dev, int act, int tile, int in16, int out16, float* out_dev, void* stream);
+/* ng = 1 .. 3 convs of tdnet_opts.precision = 1 through the grouping decision and the launch a frame uses for the Encoding's first / second layers and
+ * for a BasicBlock's conv1 beside its downsample (tdnet_opts.fusion bit 131072: one launch of k_conv_igemm_h_group where the members share a kernel
+ * form, else one launch each).  Every argument up to out_dev is an array of ng entries: member g is in_dev[g] [H[g],W[g],Cin[g]] -> out_dev[g]
+ * [Ho,Wo,Cout[g]] with w_host[g] OIHW, bias_host[g] [Cout[g]] or NULL (bias_host itself may be NULL), act 0 / 1 / 2, no residual, planned as
+ * tdnet_op_conv2d_f16mix plans it for (tile, in16, out16).  Members may name the same in_dev (same sizes): with in16 they read one fp16 map.
+ * fusion: the tdnet_opts.fusion bits of the call.  *grouped (may be NULL): 1 = the grouped kernel ran, 0 = the members ran one by one.  The kernel
+ * forms the same products in the same order either way: each out_dev[g] holds the bits of tdnet_op_conv2d_f16mix on that member alone.       */
+int tdnet_op_conv_group_f16(int ng, const float* const* in_dev, const int* H, const int* W, const int* Cin, const float* const* w_host,
+                            const float* const* bias_host, const int* Cout, const int* KS, const int* stride, const int* dil, const int* act,
+                            float* const* out_dev, int tile, int in16, int out16, int fusion, int* grouped, void* stream);
+/* Both cache entries of a frame in its one launch: q_dev [h,w,C1], v_dev [h,w,C2] -> q_out_dev [hk,wk,C1], v_out_dev [hk,wk,C2] with hk = (h - 1) / 4 + 1,
+ * wk = (w - 1) / 4 + 1: x[::4, ::4] of either map (MaxPool2d(kernel 1, stride 4), transformer.py:26,36), with the grid formula of a frame (a frame
+ * has C1 = 64; the grid is capped at 2048 workgroups of 256 lanes, one lane per float4, grid-stride beyond).  C1, C2 multiples of 4.                  */
+int tdnet_op_cache_subsample(const float* q_dev, const float* v_dev, int h, int w, int C1, int C2, float* q_out_dev, float* v_out_dev, void* stream);
+/* A stride-1 1x1 conv (+ bias, act) on the image rows y % ny == cy only: in [H,W,Cin] -> out [H,W,Cout], through the batched GEMM (batch = row, one
+ * weight set) that runs the downsample conv of one row-parity chain of a frame.  The layer is planned for the whole map as tdnet_op_conv2d plans it with
+ * tile -1, so the written rows hold tdnet_op_conv2d's bits; rows of the other classes are NOT written; a class without rows launches nothing.  An
+ * error, with nothing launched, where the plan is not the persistent-GEMM route (gemm_persistent = 0, Cin % 64 != 0, precision = 1, ...).            */
+int tdnet_op_conv1x1_rows(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout, int act,
+                          const tdnet_opts* opts /* NULL = defaults */, int ny, int cy, float* out_dev, void* stream);
 /* MaxPool2d(3, stride 2, pad 1) alone (resnet.py:137): NHWC [H,W,C] -> [(H-1)/2+1,(W-1)/2+1,C], C % 4 == 0.  mode 0: the fp32 kernel; 1: fp32 in, fp16 map
  * out (widened into out_dev): behind the fp32 stem of a tdnet_opts.precision = 1 frame; 2: the input rounded to an fp16 map first, fp16 in and out: behind
  * the fp16-MFMA stem and the deep stem (C = 128).                                                                                                        */

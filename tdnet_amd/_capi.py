@@ -123,6 +123,10 @@ TEST_SYMBOLS = {
     "tdnet_op_conv2d_f16mix": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_conv_group_f16": (ctypes.c_int, [ctypes.c_int] + [c_void_p] * 12 + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int), c_void_p]),
+    "tdnet_op_cache_subsample": (ctypes.c_int, [c_void_p, c_void_p] + [ctypes.c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_conv1x1_rows": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                             c_opts_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_maxpool": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_stem_f16": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_stem": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_opts_p, c_void_p, c_void_p]),

@@ -147,7 +147,7 @@ static int encode_frame(tdnet* n, PathLayers& L, const FrameInput& img, hipStrea
             const float* res = n->bx;
             if (B.has_ds) {                                            // conv1 and the downsample read the same map: one grouped launch where they share a kernel form
                 const ConvCall both[2] = {{&B.c1, n->bx, ch, cw, n->bt}, {&B.ds, n->bx, ch, cw, n->br}};
-                TD_TRY(run_conv_group(n, both, 2, s, &oh, &ow));
+                TD_TRY(run_conv_group(n, n->opts, both, 2, s, &oh, &ow));
                 res = n->br;
             } else TD_TRY(run_conv(n, B.c1, n->bx, ch, cw, nullptr, n->bt, s, &oh, &ow));
             TD_TRY(run_conv(n, B.c2, n->bt, oh, ow, res, last16 ? n->br : n->bx, s));   // in-place on bx when res == bx (same element)
@@ -170,11 +170,10 @@ static int encode_frame(tdnet* n, PathLayers& L, const FrameInput& img, hipStrea
     CacheSlot& cs = n->slots[slot];
     const ConvCall first[3] = {{&L.enc_v, n->z, n->h, n->w, n->v_cur}, {&L.enc_q0, n->z, n->h, n->w, n->q1}, {&L.enc_k0, n->z, n->h, n->w, n->k1}};
     const ConvCall second[2] = {{&L.enc_q1, n->q1, n->h, n->w, n->q_cur}, {&L.enc_k1, n->k1, n->hk, n->wk, cs.k}};
-    TD_TRY(run_conv_group(n, first, 3, s));
-    TD_TRY(run_conv_group(n, second, 2, s));
+    TD_TRY(run_conv_group(n, n->opts, first, 3, s));
+    TD_TRY(run_conv_group(n, n->opts, second, 2, s));
     prof_begin(n, 2, false, 0, s);                                    // both cache entries (q_, v_) in one launch
-    TD_LAUNCH(k_subsample2, dim3(td_grid_for((long)n->Lk * (16 + DV / 4))), dim3(256), 0, s, (const float*)n->q_cur, cs.q, 64, (const float*)n->v_cur, cs.v, DV,
-              n->w, n->hk, n->wk, 4);
+    launch_cache_subsample(n->q_cur, cs.q, 64, n->v_cur, cs.v, DV, n->w, n->hk, n->wk, s);
     prof_end(n, s);
     n->pending_slot = slot;
     return n->failed ? -1 : 0;

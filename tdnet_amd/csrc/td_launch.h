@@ -207,14 +207,22 @@ static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
 struct ConvCall { const ConvLayer* L; const float* in; int H, W; float* out; };
 // Up to three independent convs in one launch when they share a kernel form (fp16 mode: the register-staged k_conv_igemm_h on the same tile,
 // kernel size and storage types; `fusion` bit 131072); otherwise one launch each, in order.
-static int run_conv_group(tdnet* n, const ConvCall* c, int ng, hipStream_t s, int* Ho_out = nullptr, int* Wo_out = nullptr) {   // Ho / Wo: of c[0]
-    bool same = n && (n->opts.fusion & TDNET_FUSION_CONV_GROUPS) && ng >= 2 && ng <= 3;
+// The grouping decision: a function of the options and the planned layers alone (the tests' operator entry has no handle).
+static bool conv_group_same_form(const tdnet_opts& o, const ConvCall* c, int ng) {
+    bool same = (o.fusion & TDNET_FUSION_CONV_GROUPS) && ng >= 2 && ng <= 3;
     for (int g = 0; same && g < ng; ++g) {
         const ConvLayer& L = *c[g].L;
         const ConvLayer& L0 = *c[0].L;
         same = L.route == CR_CONV_H && L.in16 == L.out16 && L.in16 == L0.in16 && (g == 0 ? (L.KS == 1 || L.KS == 3) : L.KS == 1) &&
                conv_tile_dims(L.tile).BM == conv_tile_dims(L0.tile).BM && conv_tile_dims(L.tile).BN == conv_tile_dims(L0.tile).BN;
     }
+    return same;
+}
+// grouped (tests): whether the grouped kernel ran (1) or the members one by one (0)
+static int run_conv_group(tdnet* n, const tdnet_opts& o, const ConvCall* c, int ng, hipStream_t s, int* Ho_out = nullptr, int* Wo_out = nullptr,   // Ho / Wo: of c[0]
+                          int* grouped = nullptr) {
+    const bool same = conv_group_same_form(o, c, ng);
+    if (grouped) *grouped = same ? 1 : 0;
     if (!same) {
         for (int g = 0; g < ng; ++g) TD_TRY(run_conv(n, *c[g].L, c[g].in, c[g].H, c[g].W, nullptr, c[g].out, s, g == 0 ? Ho_out : nullptr, g == 0 ? Wo_out : nullptr));
         return 0;
@@ -324,6 +332,11 @@ static void run_maxpool(tdnet* n, const float* in, int H, int W, int C, float* o
     } else
         TD_LAUNCH(k_maxpool3s2, dim3(td_grid_for((long)Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, H, W, C, Ho, Wo);
     prof_end(n, s);
+}
+// Both cache entries of a frame in one launch (td_misc.h k_subsample2): q_out [hk][wk][C1] = q[::4, ::4], v_out [hk][wk][C2] = v[::4, ::4] of maps
+// w pixels wide; a lane per float4 of either output, the grid capped by td_grid_for (grid-stride beyond 2048 workgroups).
+static void launch_cache_subsample(const float* q, float* q_out, int C1, const float* v, float* v_out, int C2, int w, int hk, int wk, hipStream_t s) {
+    TD_LAUNCH(k_subsample2, dim3(td_grid_for((long)hk * wk * (C1 / 4 + C2 / 4))), dim3(256), 0, s, q, q_out, C1, v, v_out, C2, w, hk, wk, 4);
 }
 static int run_classifier(tdnet* n, const float* x, int HW, int C, int NC, const float* wgt, const float* bias, float* out, hipStream_t s) {
     if (C % 16 || C < 16) return td_fail("classifier: C=%d is not a positive multiple of 16", C);

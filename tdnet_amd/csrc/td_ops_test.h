@@ -27,11 +27,9 @@ extern "C" int tdnet_op_conv2d(const float* in, int H, int W, int Cin, const flo
     free_conv_layer(L);
     return rc;
 }
-// The fp16-MFMA conv of tdnet_opts.precision = 1 with the storage a frame gives it: in16: the input and the residual are rounded to fp16 maps in
-// HBM (k_f2h) and the kernel reads those (IN16; the residual's type follows the input's), else it reads the fp32 arguments and rounds while staging;
-// out16: the kernel writes an fp16 map (OUT16) that is widened into out (k_h2f), else it writes out.  The output never aliases the residual.
-static int op_conv2d_h(const char* who, const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
-                       int KS, int stride, int dil, const float* resid, int act, int tile, bool in16, bool out16, float* out, void* stream) {
+// The plan of a conv of tdnet_op_conv2d_f16io / _f16mix: tile code -> forced tile / LDS-DMA form, then plan_conv with precision = 1.  Shared by the single-conv entries and
+// tdnet_op_conv_group_f16, so that a group's member is the layer the single entry runs.  Nothing is allocated.
+static int op_plan_conv_h(const char* who, ConvLayer& L, int H, int W, int Cin, int Cout, int KS, int stride, int dil, int act, int tile, bool in16, bool out16) {
     if (KS != 1 && KS != 3) return td_fail("%s: KS must be 1 or 3", who);
     if (H < 1 || W < 1 || Cout < 1 || stride < 1 || dil < 1) return td_fail("%s: empty input", who);
     if (Cin < 64 || Cin % 64) return td_fail("%s: Cin must be a multiple of 64", who);
@@ -51,18 +49,27 @@ static int op_conv2d_h(const char* who, const float* in, int H, int W, int Cin, 
     if (force_rh && !in16) return td_fail("%s: tile %d is an LDS-DMA form, which reads an fp16 map (in16)", who, tile);
     if (force_rh) tile = CT_128x128_DEEP;
     if (tile >= CT_COUNT) return td_fail("%s: tile must be < %d or 16..36 (+ 32 for 16..29)", who, CT_COUNT);
-    hipStream_t s = (hipStream_t)stream;
     tdnet_opts o = opts_or_default(nullptr);
     o.precision = 1;
-    ConvLayer L;
-    std::vector<float> w(w_host, w_host + (size_t)Cout * Cin * KS * KS), b;
-    if (bias_host) b.assign(bias_host, bias_host + Cout);
     const int pad = dil * (KS / 2);
     const int Ho = out_size(H, KS, stride, dil, pad), Wo = out_size(W, KS, stride, dil, pad);
     // the LDS-DMA form of an fp16 input map: the forced one, or for tile -1 by the map's size alone (RH_BY_SIZE -- not the frame's rule), else none
     if (plan_conv(L, Cout, Cin, KS, stride, dil, act, false, (long)Ho * Wo, o, tile < 0 ? -1 : tile, 1, in16, out16, force_rh ? force_rh : tile < 0 ? RH_BY_SIZE : CD_NONE, no_rowimg)) return -1;
     if (force_rh == CD_256x256 && L.CoutPad % 256) return td_fail("%s: the 256 x 256 tile needs Cout padded to a multiple of 256", who);
     if (force_rh && !conv_dma_supports(Cin, Cout, KS, L.tile)) return td_fail("%s: this shape cannot run on the LDS-DMA kernel", who);
+    return 0;
+}
+// The fp16-MFMA conv of tdnet_opts.precision = 1 with the storage a frame gives it: in16: the input and the residual are rounded to fp16 maps in
+// HBM (k_f2h) and the kernel reads those (IN16; the residual's type follows the input's), else it reads the fp32 arguments and rounds while staging;
+// out16: the kernel writes an fp16 map (OUT16) that is widened into out (k_h2f), else it writes out.  The output never aliases the residual.
+static int op_conv2d_h(const char* who, const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
+                       int KS, int stride, int dil, const float* resid, int act, int tile, bool in16, bool out16, float* out, void* stream) {
+    ConvLayer L;
+    TD_TRY(op_plan_conv_h(who, L, H, W, Cin, Cout, KS, stride, dil, act, tile, in16, out16));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<float> w(w_host, w_host + (size_t)Cout * Cin * KS * KS), b;
+    if (bias_host) b.assign(bias_host, bias_host + Cout);
+    const int Ho = out_size(H, KS, stride, dil, L.pad), Wo = out_size(W, KS, stride, dil, L.pad);
     _Float16 *hin = nullptr, *hres = nullptr, *hout = nullptr;
     const long nin = (long)H * W * Cin, nout = (long)Ho * Wo * Cout;
     auto cleanup = [&]() {                                             // one release path, also for the error returns
@@ -91,6 +98,90 @@ extern "C" int tdnet_op_conv2d_f16io(const float* in, int H, int W, int Cin, con
 extern "C" int tdnet_op_conv2d_f16mix(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout,
                                       int KS, int stride, int dil, const float* resid, int act, int tile, int in16, int out16, float* out, void* stream) {
     return op_conv2d_h("tdnet_op_conv2d_f16mix", in, H, W, Cin, w_host, bias_host, Cout, KS, stride, dil, resid, act, tile, in16 != 0, out16 != 0, out, stream);
+}
+// Up to three convs of tdnet_opts.precision = 1 through run_conv_group -- the grouping decision and the launch of a frame (td_launch.h; the Encoding's
+// first / second layers, a BasicBlock's conv1 beside its downsample).  Member g is the layer tdnet_op_conv2d_f16mix plans for (tile, in16, out16); no
+// residual.  Members that name the same in_dev read ONE fp16 map (in16), as the Encoding's first layers read z.  fusion: tdnet_opts.fusion (bit
+// 131072 decides).  *grouped: 1 = k_conv_igemm_h_group ran, 0 = the members one by one.
+extern "C" int tdnet_op_conv_group_f16(int ng, const float* const* in, const int* H, const int* W, const int* Cin, const float* const* w_host,
+                                       const float* const* bias_host, const int* Cout, const int* KS, const int* stride, const int* dil, const int* act,
+                                       float* const* out, int tile, int in16, int out16, int fusion, int* grouped, void* stream) {
+    const char* who = "tdnet_op_conv_group_f16";
+    if (ng < 1 || ng > 3) return td_fail("%s: 1 .. 3 members expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    ConvLayer L[3];
+    int src[3] = {0, 1, 2};                                            // the member whose fp16 input map member g reads
+    long nin[3], nout[3];
+    // every member is validated and planned BEFORE anything is allocated (plan_conv is host arithmetic)
+    for (int g = 0; g < ng; ++g) {
+        if (!in[g] || !out[g] || !w_host[g]) return td_fail("%s: member %d: in, weight and out expected", who, g);
+        TD_TRY(op_plan_conv_h(who, L[g], H[g], W[g], Cin[g], Cout[g], KS[g], stride[g], dil[g], act[g], tile, in16 != 0, out16 != 0));
+        nin[g] = (long)H[g] * W[g] * Cin[g];
+        nout[g] = (long)out_size(H[g], KS[g], stride[g], dil[g], L[g].pad) * out_size(W[g], KS[g], stride[g], dil[g], L[g].pad) * Cout[g];
+        for (int j = g - 1; j >= 0; --j)
+            if (in[j] == in[g]) {
+                if (nin[j] != nin[g] || W[j] != W[g]) return td_fail("%s: members %d and %d share an input of different sizes", who, j, g);
+                src[g] = j;
+            }
+    }
+    _Float16 *hin[3] = {nullptr, nullptr, nullptr}, *hout[3] = {nullptr, nullptr, nullptr};
+    auto cleanup = [&]() {                                             // one release path, also for the error returns
+        for (int g = 0; g < ng; ++g) {
+            if (hin[g]) hipFree(hin[g]);
+            if (hout[g]) hipFree(hout[g]);
+            free_conv_layer(L[g]);
+        }
+    };
+    int rc = 0;
+    for (int g = 0; g < ng && !rc; ++g) {
+        std::vector<float> w(w_host[g], w_host[g] + (size_t)Cout[g] * Cin[g] * KS[g] * KS[g]), b;
+        if (bias_host && bias_host[g]) b.assign(bias_host[g], bias_host[g] + Cout[g]);
+        if (upload_conv(L[g], w, b) || (in16 && src[g] == g && dev_alloc(&hin[g], (size_t)nin[g])) || (out16 && dev_alloc(&hout[g], (size_t)nout[g]))) rc = -1;
+    }
+    if (rc) { cleanup(); return rc; }
+    ConvCall c[3];
+    for (int g = 0; g < ng; ++g) {
+        if (in16 && src[g] == g) TD_LAUNCH(k_f2h, dim3(td_grid_for(nin[g])), dim3(256), 0, s, in[g], hin[g], nin[g]);
+        c[g] = ConvCall{&L[g], in16 ? (const float*)hin[src[g]] : in[g], H[g], W[g], out16 ? (float*)hout[g] : out[g]};
+    }
+    tdnet_opts o = opts_or_default(nullptr);
+    o.precision = 1;
+    o.fusion = fusion;
+    rc = run_conv_group(nullptr, o, c, ng, s, nullptr, nullptr, grouped);
+    for (int g = 0; g < ng; ++g)
+        if (out16) TD_LAUNCH(k_h2f, dim3(td_grid_for(nout[g])), dim3(256), 0, s, (const _Float16*)hout[g], out[g], nout[g]);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    cleanup();
+    return rc;
+}
+// Both cache entries of a frame (Encoding(pre=True)'s q_ and v_): q [h,w,C1], v [h,w,C2] -> q_out [hk,wk,C1], v_out [hk,wk,C2], the stride-4
+// sub-sample, through the launch encode_frame makes (launch_cache_subsample: its grid formula, one launch for both).
+extern "C" int tdnet_op_cache_subsample(const float* q, const float* v, int h, int w, int C1, int C2, float* q_out, float* v_out, void* stream) {
+    if (h < 1 || w < 1 || C1 < 4 || C1 % 4 || C2 < 4 || C2 % 4) return td_fail("tdnet_op_cache_subsample: a map of at least 1 x 1 with C1, C2 multiples of 4 expected");
+    if (!q || !v || !q_out || !v_out) return td_fail("tdnet_op_cache_subsample: q, v, q_out and v_out expected");
+    hipStream_t s = (hipStream_t)stream;
+    launch_cache_subsample(q, q_out, C1, v, v_out, C2, w, key_size(h), key_size(w), s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return td_fail("tdnet_op_cache_subsample: device error");
+    return 0;
+}
+// A stride-1 1x1 conv on the image rows y = ny * i + cy only, through run_ds_rows (td_frame.h: the downsample conv of one row-parity chain -- a batched
+// GEMM, batch = row).  The layer is planned for the WHOLE map, as tdnet_op_conv2d plans it with tile -1; the rows of the other classes of out are not
+// written.  An error, with nothing allocated or launched, where the plan is not the persistent-GEMM route (a frame then runs no row chains).
+extern "C" int tdnet_op_conv1x1_rows(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout, int act,
+                                     const tdnet_opts* opts, int ny, int cy, float* out, void* stream) {
+    if (H < 1 || W < 1 || Cin < 1 || Cout < 1) return td_fail("tdnet_op_conv1x1_rows: empty input");
+    if (ny < 1 || cy < 0 || cy >= ny) return td_fail("tdnet_op_conv1x1_rows: a row class cy in 0 .. ny - 1 expected");
+    const tdnet_opts o = opts_or_default(opts);
+    ConvLayer L;
+    if (plan_conv(L, Cout, Cin, 1, 1, 1, act, false, (long)H * W, o, -1, (o.overlap & TDNET_OVERLAP_CHAINS) ? 2 : 1)) return -1;
+    if (L.route != CR_GEMM1X1) return td_fail("tdnet_op_conv1x1_rows: this conv is not planned as a persistent GEMM: a frame would not run it on image rows");
+    std::vector<float> w(w_host, w_host + (size_t)Cout * Cin), b;
+    if (bias_host) b.assign(bias_host, bias_host + Cout);
+    int rc = upload_conv(L, w, b);
+    if (!rc) rc = run_ds_rows(nullptr, L, in, H, W, out, ny, cy, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_conv1x1_rows: device error");
+    free_conv_layer(L);
+    return rc;
 }
 // MaxPool2d(3, stride 2, pad 1) alone: NHWC [H,W,C] -> [Ho,Wo,C].  mode = run_maxpool's pool16: 0: k_maxpool3s2, fp32 in and out; 1: k_maxpool3s2_h<false>,
 // fp32 in, the fp16 map widened into out; 2: k_maxpool3s2_h<true>, the input rounded to an fp16 map first (k_f2h).

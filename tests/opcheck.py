@@ -1,6 +1,8 @@
 """Operator-level parity checks shared by the emulator tests (CPU, numpy "HBM") and the GPU tests (torch-ROCm HBM).
 Each check builds seeded inputs, runs ONE C-ABI op, and compares with the same op in plain PyTorch fp32 (or fp64) on CPU.
-The Guarded* mems put every tensor between guard bands and check them in verify() (tests/ops_edge_cases.py)."""
+The Guarded* mems put every tensor between guard bands and check them in verify() (tests/ops_edge_cases.py).
+conv_group / cache_subsample / conv1x1_rows check launch forms of a frame -- several convs in one grid, both cache entries in one launch, a
+conv on one row class -- against the single-operator form of the same arithmetic bit for bit; the gate against fp64 is that form's."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -49,7 +51,9 @@ class _Guarded:
     NaNs -- an out-of-range read that reaches a result poisons it; one that is discarded is allowed -- and those of an output (empty) a
     fixed pattern, itself a NaN.  verify() asserts that every band of every tensor handed out since the last verify() still holds its
     fill bit for bit, and that every output interior is finite and free of the 7e7 fill; then the mem forgets those tensors.  The mem
-    owns the allocations until then: mem.ptr(mem.put(x)) on a temporary stays valid through the kernel call."""
+    owns the allocations until then: mem.ptr(mem.put(x)) on a temporary stays valid through the kernel call.
+    empty(shape, unwritten_rows=mask): an output of which the call writes only some rows (a boolean per index of the first axis, True = must
+    NOT be written): verify() holds those rows to the 7e7 fill bit for bit and every other row to "finite and fully written" as usual."""
     GUARD = 4096                     # bytes per band
     IN_BITS = 0x7FC00000             # quiet NaN
     OUT_BITS = 0x7FC5A5A5            # a quiet NaN with a payload: a fixed pattern no kernel produces
@@ -58,13 +62,16 @@ class _Guarded:
     def __init__(self):
         self._live = []
 
-    def _new(self, shape, bits, is_out):
+    def _new(self, shape, bits, is_out, keep=None):
         shape = tuple(int(d) for d in shape)
         n, g = int(np.prod(shape, dtype=np.int64)), self.GUARD // 4
         buf = self._words(g + n + g, bits)
         inner = self._interior(buf, g, n, shape)
         assert self.ptr(inner) % 256 == 0, "interior lost the allocation's alignment"
-        self._live.append((buf, n, bits, is_out, shape))
+        if keep is not None:
+            keep = np.asarray(keep, bool)
+            assert keep.shape == shape[:1], "unwritten_rows: one boolean per index of the first axis"
+        self._live.append((buf, n, bits, is_out, shape, keep))
         return inner
 
     def put(self, a):
@@ -73,8 +80,8 @@ class _Guarded:
         self._store(t, a)
         return t
 
-    def empty(self, shape):
-        t = self._new(shape, self.OUT_BITS, True)
+    def empty(self, shape, unwritten_rows=None):
+        t = self._new(shape, self.OUT_BITS, True, unwritten_rows)
         self._store(t, np.float32(self.FILL))
         return t
 
@@ -82,7 +89,7 @@ class _Guarded:
         """untouched: the calls since the last verify() were refused -- every output interior must still hold its fill instead."""
         live, self._live = self._live, []
         g = self.GUARD // 4
-        for i, (buf, n, bits, is_out, shape) in enumerate(live):
+        for i, (buf, n, bits, is_out, shape, keep) in enumerate(live):
             words = self._host_words(buf)
             what = "%s #%d %s" % ("output" if is_out else "input", i, shape)
             for name, band, base in (("in front of", words[:g], -g), ("behind", words[g + n:], n)):
@@ -93,6 +100,11 @@ class _Guarded:
                 assert (words[g:g + n].view(np.float32) == np.float32(self.FILL)).all(), "%s was written by a call that should have launched nothing" % what
             elif is_out:
                 f = words[g:g + n].view(np.float32)
+                if keep is not None:                                   # rows the call must leave alone: still the fill; the others as any output
+                    f = f.reshape(shape[0], -1)
+                    kept = f[keep].view(np.int32) != np.float32(self.FILL).view(np.int32)
+                    assert not kept.any(), "%s: %d elements in %d rows that must stay unwritten were written" % (what, int(kept.sum()), int(kept.any(1).sum()))
+                    f = f[~keep]
                 assert np.isfinite(f).all(), "%s: %d non-finite values (a read outside an input reached the result)" % (what, int((~np.isfinite(f)).sum()))
                 assert not (f == np.float32(self.FILL)).any(), "%s: %d elements were never written" % (what, int((f == np.float32(self.FILL)).sum()))
 
@@ -190,18 +202,26 @@ def assert_within(got, ref, gate, what):
     return float(ratio[i])
 
 
-def conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed=0, want_out=False, in16=True, out16=True, resid16=False):
+def conv_f16_inputs(seed, H, W, Cin, Cout, KS, x=None):
+    """The seeded (generator, input, weight, bias) of conv_f16io; x: an input given by the caller (members of a group that read one map)."""
+    g = np.random.default_rng(seed)
+    drawn = g.standard_normal((H, W, Cin)).astype(np.float32)          # drawn either way: the weights do not depend on whether x was given
+    x = drawn if x is None else x
+    w = (g.standard_normal((Cout, Cin, KS, KS)) / np.sqrt(Cin * KS * KS)).astype(np.float32)
+    b = g.standard_normal(Cout).astype(np.float32)
+    return g, x, w, b
+
+
+def conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None, seed=0, want_out=False, in16=True, out16=True, resid16=False,
+               x=None, bias=True):
     """The fp16-MFMA conv of tdnet_opts.precision = 1 (fp32 accumulate) against an fp64 evaluation on the operands as the kernel rounds them:
     the weights (host packing) and the input (k_f2h for an fp16 map, the staging convert for an fp32 one) to fp16; the residual to fp16 only
     where it is an fp16 map (in16); the bias not at all.  An fp32 result (out16 = False) is gated at t16, an fp16 map per element at gate_f16.
     in16 = out16 = True: tdnet_op_conv2d_f16io, else tdnet_op_conv2d_f16mix.  resid16: the residual holds fp16 values already, so that the
-    in16 and in32 forms add the same numbers.  Returns max(error / gate)."""
-    g = np.random.default_rng(seed)
-    x = g.standard_normal((H, W, Cin)).astype(np.float32)
-    w = (g.standard_normal((Cout, Cin, KS, KS)) / np.sqrt(Cin * KS * KS)).astype(np.float32)
-    b = g.standard_normal(Cout).astype(np.float32)
+    in16 and in32 forms add the same numbers.  x: the input instead of the seeded one; bias = False: a NULL bias.  Returns max(error / gate)."""
+    g, x, w, b = conv_f16_inputs(seed, H, W, Cin, Cout, KS, x)
     pad = dil * (KS // 2)
-    ref = F.conv2d(torch.from_numpy(half(x)).permute(2, 0, 1)[None], torch.from_numpy(half(w)), torch.from_numpy(b).double(), stride, pad, dil)
+    ref = F.conv2d(torch.from_numpy(half(x)).permute(2, 0, 1)[None], torch.from_numpy(half(w)), torch.from_numpy(b).double() if bias else None, stride, pad, dil)
     Ho, Wo = ref.shape[-2:]
     r = None
     if resid:
@@ -215,16 +235,128 @@ def conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, resid, tile=None
         ref = F.leaky_relu(ref, 0.01)
     ref = ref[0].permute(1, 2, 0).numpy()
     dx, dr, out = mem.put(x), (mem.put(r) if resid else None), mem.empty((Ho, Wo, Cout))
-    t = -1 if tile is None else tile
+    t, pb = -1 if tile is None else tile, b.ctypes.data if bias else None
     if in16 and out16:
-        lib.check(lib.tdnet_op_conv2d_f16io(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, mem.ptr(dr), act, t,
+        lib.check(lib.tdnet_op_conv2d_f16io(mem.ptr(dx), H, W, Cin, w.ctypes.data, pb, Cout, KS, stride, dil, mem.ptr(dr), act, t,
                                             mem.ptr(out), mem.stream))
     else:
-        lib.check(lib.tdnet_op_conv2d_f16mix(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, KS, stride, dil, mem.ptr(dr), act, t,
+        lib.check(lib.tdnet_op_conv2d_f16mix(mem.ptr(dx), H, W, Cin, w.ctypes.data, pb, Cout, KS, stride, dil, mem.ptr(dr), act, t,
                                              int(in16), int(out16), mem.ptr(out), mem.stream))
     got = np.array(mem.get(out))
     ratio = assert_within(got, ref, gate_f16(ref) if out16 else t16(ref), ("conv_f16io", H, W, Cin, Cout, KS, stride, dil, act, resid, tile, in16, out16))
     return (ratio, got) if want_out else ratio
+
+
+def conv_group(lib, mem, members, tile, in16=True, out16=True, fusion=None, grouped=True, seed=0):
+    """tdnet_op_conv_group_f16 -- run_conv_group, the grouping decision and the launch of a frame -- on up to three members
+    (H, W, Cin, Cout, KS, stride, dil, act, bias, share): bias False = a NULL bias; share = None or the index of an EARLIER member whose
+    input map this one reads (one device tensor).  Every member's output equals BIT FOR BIT the output of conv_f16io on that member alone at
+    the same tile and storage (which holds it to the rounding-aware fp64 gate): k_conv_igemm_h_group runs the body of k_conv_igemm_h on a
+    member-local block index, the same products in the same order.  The entry's flag must say `grouped`.  fusion: tdnet_opts.fusion, None =
+    the library default.  Members draw their weights and inputs from different seeds, so one that ran on a neighbour's arguments shows."""
+    import ctypes
+    ng = len(members)
+    xs, ws, bs, singles, shapes = [], [], [], [], []
+    for i, (H, W, Cin, Cout, KS, stride, dil, act, bias, share) in enumerate(members):
+        x = None
+        if share is not None:
+            assert share < i and members[share][:3] == (H, W, Cin), ("conv_group: a shared input needs an earlier member of the same map", members)
+            x = xs[share]
+        _, x, w, b = conv_f16_inputs(seed + 101 * i, H, W, Cin, Cout, KS, x)
+        _, one = conv_f16io(lib, mem, H, W, Cin, Cout, KS, stride, dil, act, False, tile, seed=seed + 101 * i, want_out=True, in16=in16, out16=out16,
+                            x=x, bias=bias)
+        xs.append(x); ws.append(w); bs.append(b if bias else None); singles.append(one); shapes.append(one.shape)
+    dxs = []
+    for i, m in enumerate(members):
+        dxs.append(dxs[m[9]] if m[9] is not None else mem.put(xs[i]))
+    outs = [mem.empty(sh) for sh in shapes]
+    ints = lambda j: (ctypes.c_int * ng)(*[int(m[j]) for m in members])
+    ptrs = lambda v: (ctypes.c_void_p * ng)(*v)
+    flag = ctypes.c_int(-1)
+    fus = lib.opts().fusion if fusion is None else int(fusion)
+    lib.check(lib.tdnet_op_conv_group_f16(ng, ptrs([mem.ptr(d) for d in dxs]), ints(0), ints(1), ints(2), ptrs([w.ctypes.data for w in ws]),
+                                          ptrs([None if b is None else b.ctypes.data for b in bs]), ints(3), ints(4), ints(5), ints(6), ints(7),
+                                          ptrs([mem.ptr(o) for o in outs]), -1 if tile is None else tile, int(in16), int(out16), fus,
+                                          ctypes.byref(flag), mem.stream))
+    assert flag.value == int(grouped), ("conv_group: grouped flag", flag.value, "expected", int(grouped), members, tile, in16, out16, fus)
+    for i, (o, one) in enumerate(zip(outs, singles)):
+        got = np.array(mem.get(o))
+        assert np.array_equal(got, one), ("conv_group: member %d != the single launch" % i, members, tile, in16, out16, int((got != one).sum()),
+                                          float(np.nanmax(np.abs(got - one))))
+    return flag.value
+
+
+def cache_subsample(lib, mem, h, w, C1, C2, seed=0):
+    """tdnet_op_cache_subsample (k_subsample2 through encode_frame's launch): both outputs equal x[::4, ::4] BIT FOR BIT."""
+    g = np.random.default_rng(seed + 131 * h + w)
+    q = g.random((h, w, C1), dtype=np.float32) - 0.5
+    v = g.random((h, w, C2), dtype=np.float32) - 0.5
+    hk, wk = (h - 1) // 4 + 1, (w - 1) // 4 + 1
+    dq, dv, oq, ov = mem.put(q), mem.put(v), mem.empty((hk, wk, C1)), mem.empty((hk, wk, C2))
+    lib.check(lib.tdnet_op_cache_subsample(mem.ptr(dq), mem.ptr(dv), h, w, C1, C2, mem.ptr(oq), mem.ptr(ov), mem.stream))
+    for name, got, src in (("q", mem.get(oq), q), ("v", mem.get(ov), v)):
+        exp = src[::4, ::4]
+        assert exp.shape == (hk, wk, src.shape[2])
+        bad = np.asarray(got) != exp
+        assert not bad.any(), ("cache_subsample: %s != x[::4, ::4]" % name, h, w, C1, C2, int(bad.sum()), tuple(int(i) for i in np.argwhere(bad)[0]))
+
+
+def conv1x1_rows(lib, mem, H, W, Cin, Cout, opts, ny, cy, act=1, seed=0, stays_exact=False):
+    """tdnet_op_conv1x1_rows -- run_ds_rows, the 1x1 downsample conv of one row-parity chain: a batched GEMM, batch = image row, one weight set --
+    on the rows y % ny == cy of an H x W map.  Three checks:
+      1. the written rows equal BIT FOR BIT the same rows of tdnet_op_conv2d on the whole map with the same opts: the plan is the same, and the
+         K order of a dot product does not depend on where its row sits in a tile;
+      2. those rows -- and only those go to the comparison -- pass the gate a 1x1 conv on that kernel already has: conv()'s 1e-4 against the fp32
+         torch conv with bias and activation; with precision >= 2 also split_conv()'s: the products alone (no bias, no activation) against
+         fp64 at SPLIT_GATE over the fp32 CPU evaluation's error on the same rows, and the split kernel really ran (its bits are not the
+         exact-fp32 kernel's), or, stays_exact, the plan has no split kernel for this conv and it keeps the exact kernel's bits;
+      3. the rows of the other classes still hold the output's fill: asserted here, and again by mem.verify() through unwritten_rows.
+    A class without rows (H <= cy) launches nothing.  Returns {"cpu32" | "exact" | "split": (max, rms)} with precision >= 2, else the max error."""
+    import ctypes
+    g = np.random.default_rng(seed)
+    x = g.standard_normal((H, W, Cin)).astype(np.float32)
+    w = (g.standard_normal((Cout, Cin, 1, 1)) / np.sqrt(Cin)).astype(np.float32)
+    b = g.standard_normal(Cout).astype(np.float32)
+    tx, tw = torch.from_numpy(x).permute(2, 0, 1)[None], torch.from_numpy(w)
+    nhwc = lambda t: t[0].permute(1, 2, 0).numpy()
+    ref32 = F.conv2d(tx, tw, torch.from_numpy(b))
+    ref32 = nhwc(F.relu(ref32) if act == 1 else F.leaky_relu(ref32, 0.01) if act == 2 else ref32)
+    other = np.arange(H) % ny != cy
+    dx = mem.put(x)
+
+    def rows(kw, bias, a):
+        out = mem.empty((H, W, Cout), unwritten_rows=other)
+        lib.check(lib.tdnet_op_conv1x1_rows(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data if bias else None, Cout, a, ctypes.byref(lib.opts(**kw)),
+                                            ny, cy, mem.ptr(out), mem.stream))
+        got = np.array(mem.get(out))
+        assert (got[other].view(np.int32) == np.float32(mem.FILL).view(np.int32)).all(), ("conv1x1_rows: rows of another class were written", H, W, Cin, Cout, kw, ny, cy)
+        return got[cy::ny]
+
+    whole = mem.empty((H, W, Cout))
+    lib.check(lib.tdnet_op_conv2d(mem.ptr(dx), H, W, Cin, w.ctypes.data, b.ctypes.data, Cout, 1, 1, 1, None, act, ctypes.byref(lib.opts(**opts)), -1,
+                                  mem.ptr(whole), mem.stream))
+    whole = np.array(mem.get(whole))
+    got = rows(opts, True, act)
+    what = ("conv1x1_rows", H, W, Cin, Cout, opts, ny, cy)
+    assert got.shape[0] == len(range(cy, H, ny))
+    assert np.array_equal(got, whole[cy::ny]), what + ("!= the rows of the whole-map conv", int((got != whole[cy::ny]).sum()))
+    if got.shape[0] == 0:
+        return None
+    err = float(np.abs(got - ref32[cy::ny]).max())
+    assert err <= 1e-4, what + (err,)
+    if opts.get("precision", 0) < 2:
+        return err
+    ref = nhwc(F.conv2d(tx.double(), tw.double()))[cy::ny]
+    errs = {"cpu32": max_rms(nhwc(F.conv2d(tx, tw))[cy::ny], ref)}
+    outs = {name: rows(kw, False, 0) for name, kw in (("exact", dict(opts, precision=0)), ("split", opts))}
+    for name in outs:
+        errs[name] = max_rms(outs[name], ref)
+    label = "conv1x1_rows %dx%d %d->%d %s rows %d mod %d" % (H, W, Cin, Cout, opts, cy, ny)
+    if stays_exact:
+        assert np.array_equal(outs["exact"], outs["split"]), ("not the bits of the exact-fp32 kernel", label)
+    else:
+        assert not np.array_equal(outs["exact"], outs["split"]), ("the split kernel did not run: the bits of the exact-fp32 kernel", label)
+    return _split_gate(label, errs, "cpu32", SPLIT_GATE)
 
 
 def _stem_case(H, W, seed, rounded):

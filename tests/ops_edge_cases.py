@@ -18,6 +18,27 @@ What the value tests of test_gpu_ops / test_gpu_winograd / test_gpu_fp16 / test_
     cannot see a lost product (~2^-18): the products alone against fp64, in max and rms error, relative to the fp32 CPU evaluation's own
     error (x3 / x2) or, on the Winograd route, to the exact-fp32 Winograd kernel's (x1.25 / x1.1): opcheck.split_conv / split_stem /
     split_attention, also on non-negative data and on per-channel power-of-two scales.
+  * three launch forms that ran inside whole frames only (sections 8 to 10), through the function a frame calls:
+      8. grouped fp16 convs -- run_conv_group / k_conv_igemm_h_group, up to three convs in one grid, each block on a member-local (bid, nblk) --
+         against the single launches BIT FOR BIT (opcheck.conv_group; the single launch is held to the rounding-aware fp64 gate by
+         opcheck.conv_f16io), with the entry's "grouped" flag asserted; and the fallbacks that must run the members one by one;
+      9. the cache sub-sample -- k_subsample2 through encode_frame's launch -- against numpy's [::4, ::4] bit for bit, up to a case that needs
+         a second trip of the grid-stride loop;
+     10. the 1x1 downsample conv on one row class -- run_ds_rows, a batched GEMM with one weight set, on k_gemm_persistent and k_gemm_b3 --
+         against the same rows of the whole-map conv bit for bit, at the route's gate on those rows, the other rows still unwritten
+         (opcheck.conv1x1_rows; the guarded mem's unwritten_rows).
+    Section 8: all 36 grouped cases (6 member lists x tiles 3 / 4 / 5 x fp16 / fp32 maps) really ran k_conv_igemm_h_group -- the flag is asserted -- and
+    the 5 fallback cases ran one launch per member; member block counts covered: 1, 5, 9, 10, 15, 18 and 20 (10 | 18 | 15 beside 5 | 9 | 5 beside
+    5 | 9 | 5 on the three-member lists).  Section 10 on the split GEMM (k_gemm_b3, precision 3), written rows only, max / rms error against fp64 as
+    multiples of the fp32 CPU evaluation's (gate x3 + 1e-7 / x2 + 1e-9), rows 0 mod 2 | rows 1 mod 2, under the emulator:
+        5x9 64->128          x0.69 / x0.68 | x0.52 / x0.67        9x17 128->256        x0.63 / x0.64 | x0.70 / x0.65
+        1x9 64->128          x0.61 / x0.65 | no rows              12x70 256->512 g3    x0.65 / x0.63 | x0.54 / x0.63
+        4x300 64->132        x0.45 / x0.67 | x0.73 / x0.67        6x150 64->130        x1.00 / x1.00: N % 4 != 0, the plan keeps the fp32 GEMM
+    (the device's figures: tests/test_gpu_ops_edges.py).  With one defect seeded at a time, under the emulator: a member called with another member's
+    block count, member 0 of the KS0 != KS1 branch with end[1], `<=` in the member pick -- 15, 9 and 18 of the 18 test_conv_groups cases fail;
+    k_subsample2 indexing the source with wo -- the three test_cache_subsample cases; its loop without the grid stride --
+    test_cache_subsample_second_trip_of_the_grid; run_ds_rows with MP = W, or starting at row 0 for cy = 1 -- 20 and 10 of the 24
+    test_row_class_downsample cases (all that have rows to write).
 
 Each function takes (lib, mem) and one entry of its case list; values are checked by the opcheck functions at the tolerance the
 route's existing tests use."""
@@ -198,6 +219,63 @@ HEAD_SPLIT = dict(WINO, precision=3)                                   # the hea
 # attention (65, 129, 512) online 19/18 abs    cpu32 6.62e-07 / 1.47e-07   exact x1.00 / x1.01   split x0.85 / x0.75
 # attention (65, 129, 128) online 17 scaled    cpu32 1.50e-05 / 1.20e-06   exact x0.84 / x0.86   split x0.75 / x0.59
 # attention (65, 129, 512) online 19/18 scaled cpu32 1.49e-05 / 1.18e-06   exact x0.97 / x0.87   split x0.74 / x0.53
+
+# ---- 8. grouped fp16 convs: k_conv_igemm_h_group through run_conv_group (tdnet_opts.fusion bit 131072), whole frames' only route to it ----------
+# A member: (H, W, Cin, Cout, KS, stride, dil, act, bias, share) -- bias False: a NULL bias; share: the earlier member whose input map it reads.
+# 19 x 29 = 551 pixels are 5 M tiles of 128 rows or 9 of 64, the last one ragged (39 rows); 5 x 8 = 40 pixels are one tile.  With Cout 130 /
+# 64 / 19 a member is 10 | 18 | 15, 5 | 9 | 5, 5 | 9 | 5 blocks on tiles 3 | 4 | 5: td_xcd_remap(bid, nblk) is not the identity (nblk >= 9,
+# nblk % 8 != 0) and every end[] boundary falls inside a round of eight.  Activations 0 / 1 / 2 and the NULL bias sit on different members.
+GROUP_TILES = [3, 4, 5]                                                # 128 x 128, 64 x 128, 128 x 64 on the two-stage pipeline
+GROUP_STORAGES = [(True, True), (False, False)]                        # (in16, out16): fp16 maps, and the fp32 maps plan_conv leaves on CR_CONV_H
+CONV_GROUPS = [
+    # the Encoding's first layers: three 1x1 convs on ONE map
+    [(19, 29, 64, 130, 1, 1, 1, 1, True, None), (19, 29, 64, 64, 1, 1, 1, 2, False, 0), (19, 29, 64, 19, 1, 1, 1, 0, True, 0)],
+    [(19, 29, 128, 130, 1, 1, 1, 0, False, None), (19, 29, 128, 64, 1, 1, 1, 1, True, None), (19, 29, 128, 19, 1, 1, 1, 2, True, None)],   # three maps, two K steps
+    # the query / key second layers: the key branch on the 16x smaller grid, one tile
+    [(19, 29, 64, 64, 1, 1, 1, 1, True, None), (5, 8, 64, 64, 1, 1, 1, 0, True, None)],
+    # a BasicBlock's 3x3 stride-2 conv1 beside its 1x1 stride-2 downsample (the KS0 != KS1 branch: member 0 takes (b, end[0]))
+    [(37, 57, 64, 128, 3, 2, 1, 1, True, None), (37, 57, 64, 128, 1, 2, 1, 0, True, 0)],
+    # a dilated block: 3x3 stride 1 dilation 2 beside a 1x1 stride-1 downsample
+    [(19, 29, 128, 256, 3, 1, 2, 1, False, None), (19, 29, 128, 256, 1, 1, 1, 0, True, 0)],
+    # three members with a 3x3 first: the kernel allows it, no frame issues it
+    [(19, 29, 64, 64, 3, 1, 1, 1, True, None), (19, 29, 64, 130, 1, 1, 1, 2, False, 0), (5, 8, 128, 19, 1, 1, 1, 0, True, None)],
+]
+FUSION_CONV_GROUPS = 131072                                            # include/tdnet.h TDNET_FUSION_CONV_GROUPS
+# Where run_conv_group must run the members one by one -- and still give the same bits: (members, tile, in16, out16, clear the fusion bit)
+CONV_GROUP_FALLBACKS = [
+    (CONV_GROUPS[0], 3, True, True, True),                             # the fusion bit cleared
+    ([(9, 11, 192, 130, 1, 2, 1, 2, True, None), (9, 11, 192, 130, 1, 2, 1, 0, False, 0)], 16, True, True, False),   # an LDS-DMA tile code: CR_CONV_DMA
+    (CONV_GROUPS[2], 3, True, False, False),                           # in16 != out16
+    ([(19, 29, 64, 64, 1, 1, 1, 1, True, None), (19, 29, 64, 64, 3, 1, 1, 0, True, 0)], 3, True, True, False),       # a 3x3 as second member
+    ([(19, 29, 64, 100, 1, 1, 1, 1, True, None), (19, 29, 64, 64, 1, 1, 1, 0, True, 0)], None, True, True, False),   # the heuristic's tiles differ: 64 x 128 beside 128 x 64
+]
+
+# ---- 9. the cache sub-sample: k_subsample2 through encode_frame's launch, q_ and v_ in one grid ---------------------------------------------------
+# (h, w): one pixel; 4 x 4 -> 1 x 1; 5 x 9 -> 2 x 3, where the last source row and column are read; 8 x 9, 13 x 21, 6 x 7: neither is
+SUBSAMPLES = [(1, 1), (4, 4), (5, 9), (8, 9), (13, 21), (6, 7)]
+SUBSAMPLE_C1 = 64
+SUBSAMPLE_C2S = [128, 512, 2048]                                       # 2048: the Bottleneck backbones' d_v
+# More work than one pass of the grid -- hk x wk x (16 + 512) float4s against td_grid_for's cap of 2048 workgroups x 256 lanes = 524288 -- so that the
+# grid-stride loop takes a second trip; (h, w, C1, C2).  SECOND_TRIP: one source row, 1 x 4093 -> 1 x 1024, 540672 float4s from 34 MB of source: the
+# smallest map that gets there, run under the emulator and on the device.  GRID_STRIDE: 125 x 125 -> 32 x 32, the same 540672 float4s with rows
+# and columns both strided, on 128 MB of source (+ 4 MB of q): DEVICE ONLY.  tests/test_emu_ops_edges.py leaves it out because the CPU suite would
+# hold that source three times in host memory (the array, its guarded copy, the reference's gather: ~0.4 GB) in every run; the loop bound it is there
+# for is the one SECOND_TRIP already exercises under the emulator.
+SUBSAMPLE_SECOND_TRIP = (1, 4093, 64, 2048)
+SUBSAMPLE_GRID_STRIDE = (125, 125, 64, 2048)
+
+# ---- 10. the 1x1 downsample conv of one row class: run_ds_rows, a batched GEMM with one weight set (GemmArgs.wshare), batch = image row --------
+# (H, W, Cin, Cout), tdnet_opts on top of ROW_OPTS; ny = 2 and both row classes
+ROW_NY = 2
+ROW_CONVS = [((5, 9, 64, 128), {}),
+             ((9, 17, 128, 256), {}),                                  # odd H: the classes differ in row count
+             ((1, 9, 64, 128), {}),                                    # cy = 1: no rows, no launch, everything untouched
+             ((6, 150, 64, 130), {}),                                  # a batch of 150 pixels is wider than one M tile (64 / 128 rows), N ragged
+             ((12, 70, 256, 512), {"gemm_persistent": 3}),             # tiles outnumber workgroups: three walk them all
+             ((4, 300, 64, 132), {})]                                  # wider than the split GEMM's 256-row tile too, four channels into a second N tile
+ROW_OPTS = [{}, {"precision": 3}]                                      # k_gemm_persistent, k_gemm_b3
+ROW_STAYS_EXACT = [(6, 150, 64, 130)]                                  # N % 4 != 0: gemm_b3_supports refuses, precision 3 keeps the fp32 GEMM bit for bit
+
 
 
 def conv_id(case):
@@ -473,3 +551,51 @@ def layernorm_flat(lib, mem, a):
 def wide_attention(lib, mem, a, online):
     opcheck.attention(lib, mem, *a, online=online, ln=True)
     mem.verify()
+
+
+def group_id(members):
+    return "+".join("%dx%d-%dto%d-k%ds%dd%d" % m[:7] for m in members)
+
+
+def row_conv_id(case):
+    (H, W, Cin, Cout), opts = case
+    return "%dx%d-%dto%d%s" % (H, W, Cin, Cout, "".join("-%s%d" % (k[0], v) for k, v in sorted(opts.items())))
+
+
+def conv_group(lib, mem, members, tile):
+    """A CONV_GROUPS entry on one tile, in both storages: the grouped kernel must run and give every member the single launch's bits."""
+    for in16, out16 in GROUP_STORAGES:
+        opcheck.conv_group(lib, mem, members, tile, in16=in16, out16=out16, grouped=True)
+        mem.verify()
+
+
+def conv_group_fallback(lib, mem, case):
+    members, tile, in16, out16, clear = case
+    fusion = lib.opts().fusion & ~FUSION_CONV_GROUPS if clear else None
+    opcheck.conv_group(lib, mem, members, tile, in16=in16, out16=out16, fusion=fusion, grouped=False)
+    mem.verify()
+
+
+def cache_subsample(lib, mem, hw, C2, C1=SUBSAMPLE_C1):
+    opcheck.cache_subsample(lib, mem, *hw, C1, C2)
+    mem.verify()
+
+
+def row_conv(lib, mem, case, opts, cy):
+    """A ROW_CONVS entry under ROW_OPTS' opts on the row class cy (of ROW_NY): opcheck.conv1x1_rows' three checks inside the guards."""
+    shape, extra = case
+    o = dict(opts, **extra)
+    errs = opcheck.conv1x1_rows(lib, mem, *shape, o, ROW_NY, cy, act=1 + cy, stays_exact=shape in ROW_STAYS_EXACT)
+    mem.verify()
+    return errs
+
+
+def row_conv_refusals(lib, mem):
+    """Where a frame would refuse (the plan is not the persistent-GEMM route) the entry is an error and launches nothing: the GEMM switched off,
+    K = 32 (gemm_supports wants K % 64 == 0), the fp16 mode (CR_CONV_H); and a row class outside 0 .. ny - 1."""
+    for (Cin, opts, ny, cy) in ((64, {"gemm_persistent": 0}, 2, 0), (32, {}, 2, 0), (64, {"precision": 1}, 2, 1), (64, {}, 2, 2), (64, {}, 0, 0)):
+        x, w = mem.put(np.zeros((4, 9, Cin), np.float32)), np.zeros((128, Cin), np.float32)
+        out = mem.empty((4, 9, 128))
+        with pytest.raises(_capi.TdnetError):
+            lib.check(lib.tdnet_op_conv1x1_rows(mem.ptr(x), 4, 9, Cin, w.ctypes.data, None, 128, 0, ctypes.byref(lib.opts(**opts)), ny, cy, mem.ptr(out), mem.stream))
+        mem.verify(untouched=True)

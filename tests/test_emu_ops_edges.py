@@ -211,3 +211,40 @@ def test_head_cls_on_the_split_gemm(lib, mem, a):
 
 def test_head_cls_refusals_on_the_split_gemm(lib, mem):
     cases.head_cls_refusals(lib, mem, cases.HEAD_SPLIT)
+
+
+# ---- the launch forms only whole frames reached: grouped fp16 convs, the cache sub-sample, the downsample conv of one row class ----
+@pytest.mark.parametrize("tile", cases.GROUP_TILES)
+@pytest.mark.parametrize("members", cases.CONV_GROUPS, ids=cases.group_id)
+def test_conv_groups(lib, mem, members, tile):
+    cases.conv_group(lib, mem, members, tile)
+
+
+@pytest.mark.parametrize("case", cases.CONV_GROUP_FALLBACKS, ids=["bit-cleared", "lds-dma-tile", "in16-out32", "3x3-second", "tiles-differ"])
+def test_conv_group_fallbacks(lib, mem, case):
+    cases.conv_group_fallback(lib, mem, case)
+
+
+# cases.SUBSAMPLE_GRID_STRIDE (125 x 125 x 2048, device only) is NOT run here: 128 MB of source, held three times by a CPU run (the array, its guarded
+# copy, the reference's gather).  The grid-stride loop's second trip runs here on cases.SUBSAMPLE_SECOND_TRIP, one source row of 34 MB.
+@pytest.mark.parametrize("C2", cases.SUBSAMPLE_C2S)
+def test_cache_subsample(lib, mem, C2):
+    for hw in cases.SUBSAMPLES:
+        cases.cache_subsample(lib, mem, hw, C2)
+
+
+def test_cache_subsample_second_trip_of_the_grid(lib, mem):
+    h, w, C1, C2 = cases.SUBSAMPLE_SECOND_TRIP
+    assert ((h - 1) // 4 + 1) * ((w - 1) // 4 + 1) * (C1 + C2) // 4 > 2048 * 256     # td_grid_for's cap
+    cases.cache_subsample(lib, mem, (h, w), C2, C1)
+
+
+@pytest.mark.parametrize("cy", [0, 1])
+@pytest.mark.parametrize("opts", cases.ROW_OPTS, ids=["fp32", "split"])
+@pytest.mark.parametrize("case", cases.ROW_CONVS, ids=cases.row_conv_id)
+def test_row_class_downsample(lib, mem, case, opts, cy):
+    cases.row_conv(lib, mem, case, opts, cy)
+
+
+def test_row_class_downsample_refusals(lib, mem):
+    cases.row_conv_refusals(lib, mem)

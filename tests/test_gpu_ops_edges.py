@@ -72,6 +72,14 @@ itself 2.5 times what another host's CPU gives (8.51e-7, the emulator table).  r
     attention (65, 129, 512) online 19/18 abs    cpu32 6.62e-07 / 1.47e-07   exact x1.00 / x1.01   split x1.03 / x0.98
     attention (65, 129, 128) online 17 scaled    cpu32 1.50e-05 / 1.20e-06   exact x0.84 / x0.86   split x1.31 / x0.93
     attention (65, 129, 512) online 19/18 scaled cpu32 1.49e-05 / 1.18e-06   exact x0.97 / x0.87   split x1.05 / x0.86
+
+The row-class downsample conv on the split GEMM (opcheck.conv1x1_rows, k_gemm_b3 through run_ds_rows with precision 3), on an MI355X: the written rows
+alone, max / rms against fp64 as multiples of cpu32 (the same gate, x3 max + 1e-7 / x2 rms + 1e-9), rows 0 mod 2 | rows 1 mod 2:
+    5x9 64->128          x0.71 / x0.92 | x0.88 / x0.90        9x17 128->256        x0.80 / x0.89 | x0.89 / x0.90
+    1x9 64->128          x0.71 / x0.89 | no rows              12x70 256->512 g3    x1.09 / x0.87 | x0.81 / x0.87
+    4x300 64->132        x0.65 / x0.93 | x0.85 / x0.93        6x150 64->130        x1.00 / x1.00 (N % 4 != 0: the fp32 GEMM, bit for bit)
+The written rows equal the whole-map conv's bit for bit on both GEMM kernels, the 36 grouped conv cases equal their single launches bit for bit,
+and the 125 x 125 x 2048 cache sub-sample (a second trip of the grid-stride loop) equals [::4, ::4].
 """
 import pytest
 import torch
@@ -248,3 +256,44 @@ def test_head_cls_on_the_split_gemm(lib, mem, a):
 
 def test_head_cls_refusals_on_the_split_gemm(lib, mem):
     cases.head_cls_refusals(lib, mem, cases.HEAD_SPLIT)
+
+
+# ---- the launch forms only whole frames reached: grouped fp16 convs, the cache sub-sample, the downsample conv of one row class ----
+@pytest.mark.parametrize("tile", cases.GROUP_TILES)
+@pytest.mark.parametrize("members", cases.CONV_GROUPS, ids=cases.group_id)
+def test_conv_groups(lib, mem, members, tile):
+    cases.conv_group(lib, mem, members, tile)
+
+
+@pytest.mark.parametrize("case", cases.CONV_GROUP_FALLBACKS, ids=["bit-cleared", "lds-dma-tile", "in16-out32", "3x3-second", "tiles-differ"])
+def test_conv_group_fallbacks(lib, mem, case):
+    cases.conv_group_fallback(lib, mem, case)
+
+
+@pytest.mark.parametrize("C2", cases.SUBSAMPLE_C2S)
+def test_cache_subsample(lib, mem, C2):
+    for hw in cases.SUBSAMPLES:
+        cases.cache_subsample(lib, mem, hw, C2)
+
+
+def test_cache_subsample_beyond_one_pass_of_the_grid(lib, mem):
+    h, w, C1, C2 = cases.SUBSAMPLE_GRID_STRIDE
+    assert ((h - 1) // 4 + 1) * ((w - 1) // 4 + 1) * (C1 + C2) // 4 > 2048 * 256     # td_grid_for's cap: the loop takes a second trip
+    cases.cache_subsample(lib, mem, (h, w), C2, C1)
+
+
+def test_cache_subsample_second_trip_of_the_grid(lib, mem):
+    h, w, C1, C2 = cases.SUBSAMPLE_SECOND_TRIP
+    assert ((h - 1) // 4 + 1) * ((w - 1) // 4 + 1) * (C1 + C2) // 4 > 2048 * 256     # td_grid_for's cap
+    cases.cache_subsample(lib, mem, (h, w), C2, C1)
+
+
+@pytest.mark.parametrize("cy", [0, 1])
+@pytest.mark.parametrize("opts", cases.ROW_OPTS, ids=["fp32", "split"])
+@pytest.mark.parametrize("case", cases.ROW_CONVS, ids=cases.row_conv_id)
+def test_row_class_downsample(lib, mem, case, opts, cy):
+    cases.row_conv(lib, mem, case, opts, cy)
+
+
+def test_row_class_downsample_refusals(lib, mem):
+    cases.row_conv_refusals(lib, mem)
