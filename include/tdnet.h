@@ -62,15 +62,16 @@ typedef struct tdnet_cfg {
 #define TDNET_FUSION_CLS_IN_HEAD 262144    /* the classifier inside the head conv's Winograd output transform */
 #define TDNET_FUSION_SPLIT_NARROW 524288   /* precision 2: the narrow direct convs and the packed-row stem on the split bf16 MFMA */
 #define TDNET_FUSION_LATE_CHAIN 1048576    /* the cache-only attention chain forks in front of the first dilated block */
+#define TDNET_FUSION_PPM_FOLD 2097152      /* fp32: the pyramid folded through the Encoding's first 1x1 convs as 64 basis columns (no `z` map) */
 #define TDNET_OVERLAP_CHAINS 1             /* row-parity chains on two streams */
 #define TDNET_OVERLAP_LOWREG_TRANSFORMS 2  /* the low-register F(4x4) transform kernels everywhere */
 #define TDNET_OVERLAP_CHAINS_ANY_SIZE 4    /* the chains at any map size */
 #define TDNET_OVERLAP_GEMM_DMA 8           /* the Winograd GEMMs on the LDS-DMA-fed kernel */
 #define TDNET_OVERLAP_VW_SHIFT 4           /* bits 4-5: log2 of the channels per lane of the chunked transform kernels */
 #define TDNET_OVERLAP_VW_MASK 0x30
-/* 2072614: the measured default (measurements: DESIGN.md 5, DESIGN_experiments.md) */
+/* 4169766: the measured default (measurements: DESIGN.md 5, DESIGN_experiments.md) */
 #define TDNET_FUSION_DEFAULT (TDNET_FUSION_LN_STATS | TDNET_FUSION_LN_IN_HEAD | TDNET_FUSION_A_DIRECT | TDNET_FUSION_DMA_LOADERS | TDNET_FUSION_DMA_NARROW | \
-                              TDNET_FUSION_STEM_ROWS | TDNET_FUSION_CONV_GROUPS | TDNET_FUSION_CLS_IN_HEAD | TDNET_FUSION_SPLIT_NARROW | TDNET_FUSION_LATE_CHAIN)
+                              TDNET_FUSION_STEM_ROWS | TDNET_FUSION_CONV_GROUPS | TDNET_FUSION_CLS_IN_HEAD | TDNET_FUSION_SPLIT_NARROW | TDNET_FUSION_LATE_CHAIN | TDNET_FUSION_PPM_FOLD)
 #define TDNET_FUSION_MASK TDNET_FUSION_DEFAULT   /* the bits of tdnet_opts.fusion that exist (= the default); the others are cleared and ignored */
 /* 41: row-parity chains with 4 channels per lane (+2 %) on the LDS-DMA-fed GEMM (+0.9 %): profiles/r03a_*, r03m_* */
 #define TDNET_OVERLAP_DEFAULT (TDNET_OVERLAP_CHAINS | TDNET_OVERLAP_GEMM_DMA | (2 << TDNET_OVERLAP_VW_SHIFT))
@@ -107,7 +108,13 @@ typedef struct tdnet_opts {
                                 524288 = precision 2: the convs of bit 32, the packed-row stem and the direct convs of 65 .. 128 output channels on the
                                      split bf16 MFMA (td_conv_ad_b3.h),
                                 1048576 = fp32 / precision 2: the cache-only attention chain forks in front of the backbone's first dilated block (layer3)
-                                     instead of at the frame's start; bit-identical (ignored with precision 1).
+                                     instead of at the frame's start; bit-identical (ignored with precision 1),
+                                2097152 = fp32 (precision 0; ignored otherwise and by the single-frame PSPNet): the pyramid half of the map `z` is never assembled.  Its
+                                     4 FS channels are a linear function of the 50 pooled vectors, so the Encoding's first 1x1 convs (value, query, strided key) run
+                                     over K = XS + 64 instead of XS + 4 FS: c4's channel slice, then a constant [h w][64] table of bilinear coefficients against 64 rows
+                                     G = pooled features x the layer's pyramid weights, computed per frame (k_ppm_fold_g).  Same gates, not bit-identical (another
+                                     summation order); tdnet_get_stage("z") assembles the map on request.  Taken where those convs are planned on the persistent
+                                     GEMM / the direct 1x1 kernel and XS % 64 == 0; otherwise the frame runs as without the bit.
                                 Retired, ignored: 1, 8, 16, 64, 128, 256, 512, 1024, 2048, 4096, 16384 (DESIGN_experiments.md 4.4, 10.10).   */
     int32_t overlap;         /* bit mask (default TDNET_OVERLAP_DEFAULT), on BasicBlock backbones:
                                 1 = the trailing run of even-dilation convs (ResNet layers 3-4: resnet.py:181-198) as its even-row and odd-row halves

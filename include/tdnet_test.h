@@ -95,6 +95,18 @@ int tdnet_op_layernorm_hw_f16(const float* x_dev, int HW, int C, const float* g_
 /* PPM (td4_psp18.py:271-284): c4 NHWC [h,w,512] -> z NHWC [h,w,512]; w_host: 4 folded [128,512] matrices, b_host 4x[128] */
 int tdnet_op_ppm(const float* c4_dev, int h, int w, const float* w_host, const float* b_host, int path_num, int pid,
                  float* z_dev, void* stream);
+/* The first layers of a path's Encoding on c4 [h,w,C] dev as a frame runs them: pyramid pooling, then the value conv (C -> DV), the query conv (C -> 64, LeakyReLU)
+ * and the stride-4 key conv (C -> 64, LeakyReLU).  fold = 1: the pyramid as 64 basis columns (tdnet_opts.fusion bit 2097152: no z map; an error, with nothing
+ * allocated, where a frame would not fold); fold = 0: through the assembled z.  ppm_w_host [4][C/4][C], ppm_b_host [4][C/4] (BN folded; path pid keeps channels
+ * pid C/8 .. of each level); wv / wq / wk_host [Cout][C] with biases (NULL = 0).  v_out [h w][DV], q_out [h w][64], k_out [hk wk][64] dev;
+ * basis_out_dev [h w][64] or NULL: the fold's table of bilinear coefficients (fold = 1 only).                                                            */
+int tdnet_op_enc_first(const float* c4_dev, int h, int w, int C, int pid, const float* ppm_w_host, const float* ppm_b_host, const float* wv_host,
+                       const float* bv_host, int DV, const float* wq_host, const float* bq_host, const float* wk_host, const float* bk_host, int fold,
+                       float* v_out_dev, float* q_out_dev, float* k_out_dev, float* basis_out_dev, void* stream);
+/* A 1x1 conv (stride >= 1) planned as tdnet_op_conv2d plans it, on the TWO-SOURCE form of its kernel with nothing behind the split (k_split == nsteps, null
+ * second source): bit-identical to tdnet_op_conv2d.  An error where the plan is neither the persistent fp32 GEMM nor the fp32 direct 1x1 conv.           */
+int tdnet_op_conv1x1_src2_null(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout, int stride,
+                               const float* resid_dev, int act, const tdnet_opts* opts, int tile, float* out_dev, void* stream);
 /* 1x1 classifier conv (+bias): x NHWC [HW,C] dev, w [NC,C] dev, b [NC] dev -> planar out [NC,HW] dev; the frame's routing by NC
  * (<= 32: k_classifier, all weights in one workgroup's LDS: (NC * C + 256 * NC) * 4 bytes <= 160 KiB, i.e. C <= 1024 at 32 classes;
  * 33 .. 256: the class-tiled k_classifier_ct, C <= 512).  C a multiple of 16; anything else is an error before a launch.            */

@@ -145,6 +145,9 @@ TEST_SYMBOLS = {
     "tdnet_op_upsample_argmax_score": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
     "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
+    "tdnet_op_enc_first": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 4 + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 5),
+    "tdnet_op_conv1x1_src2_null": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                                  c_void_p, ctypes.c_int, c_opts_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_classifier": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_head_cls": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
                                          c_void_p, c_void_p, ctypes.c_int, c_opts_p, ctypes.c_int, c_void_p, c_void_p]),

@@ -43,6 +43,13 @@ struct ConvArgs {
     int act;              // 0 none, 1 ReLU, 2 LeakyReLU(0.01)
     int tiles_n;          // CoutPad / BN
     int nbatch;           // > 1: batched 1x1 GEMMs (Winograd), see k_conv_igemm
+    // Two operand sources (td_conv_ad.h k_conv_adirect<1, 0, true> only): K steps 0 .. k_split - 1 read the map `in` with a pixel stride of ld floats
+    // (its first 32 k_split channels) and the weights wp, steps k_split .. nsteps - 1 the map in2 (same H x W, pixel stride ld2) and the weights wp2
+    // (steps counted from 0 again, same CoutPad); Cin = 32 nsteps.  k_split < 0: one source.  k_split == nsteps: nothing behind the split.
+    int k_split = -1;
+    int ld = 0, ld2 = 0;
+    const float* in2 = nullptr;
+    const float* wp2 = nullptr;
 };
 
 // bijective "block b runs on XCD b%8" -> contiguous range of tiles per XCD (cdna_hip_programming.md T1)

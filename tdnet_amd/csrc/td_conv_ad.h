@@ -17,8 +17,11 @@
 // channels of a kernel row are 21 CONTIGUOUS floats -- a K step is one kernel row: six 16-byte k-groups (21 products, three columns and
 // two groups of zero weights), 24 MFMAs instead of 32; 7 steps, K = 168 instead of 224 for the same 147 products.  The loads are 4-byte
 // aligned 16-byte buffer loads; nothing is masked (the border is in the image, a row past M reads out of range = zeros).
-template <int KS, int STEM>
+// SRC2 (KS = 1, STEM = 0): from K step p.k_split on the lane's A row and the weights come from a second map / weight buffer (ConvArgs) -- the
+// Encoding's strided key conv on c4's channel slice and the pyramid's basis columns (td_misc.h k_ppm_fold_g).  Wave-uniform, in the loaders only.
+template <int KS, int STEM, bool SRC2 = false>
 TD_KERNEL void TD_LAUNCH_BOUNDS(256, 3) k_conv_adirect(ConvArgs p) {
+    static_assert(!SRC2 || (KS == 1 && STEM == 0), "two sources: the 1x1 conv on an NHWC map");
     constexpr int BM = 128, BN = 64, NT = 2;
     constexpr int NTAPS = STEM ? 1 : KS * KS;
     constexpr int NG = STEM == 2 ? 3 : 4;                            // k-group pairs per K step
@@ -37,9 +40,15 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 3) k_conv_adirect(ConvArgs p) {
     const int oy = m / p.Wo, ox = m - oy * p.Wo;
     const int a_by = (m < p.M) ? oy * p.stride - p.pad : -(1 << 28);
     const int a_bx = ox * p.stride - p.pad + (STEM == 2 ? 1 : 0);   // packed-row image: 4 border pixels on the left (16-byte aligned rows), 3 needed
-    const unsigned a_off = (((unsigned)a_by * (unsigned)p.W + (unsigned)a_bx) * (unsigned)p.Cin + (STEM ? 0u : (unsigned)half * 4u)) * 4u;
-    const TdBuf in_buf = td_make_buf(p.in, (unsigned)p.H * (unsigned)p.W * (unsigned)p.Cin * 4u);
-    const TdBuf w_buf = td_make_buf(p.wp, (unsigned)p.nsteps * 8u * (unsigned)p.CoutPad * 16u);
+    const unsigned pix_floats = SRC2 ? (unsigned)p.ld : (unsigned)p.Cin;   // floats between two pixels of the (first) map
+    const unsigned a_off = (((unsigned)a_by * (unsigned)p.W + (unsigned)a_bx) * pix_floats + (STEM ? 0u : (unsigned)half * 4u)) * 4u;
+    const TdBuf in_buf = SRC2 ? td_make_buf(p.in, (((unsigned)p.H * (unsigned)p.W - 1u) * pix_floats + (unsigned)p.k_split * 32u) * 4u)   // the last pixel ends after this source's channels
+                              : td_make_buf(p.in, (unsigned)p.H * (unsigned)p.W * (unsigned)p.Cin * 4u);
+    const TdBuf w_buf = td_make_buf(p.wp, (unsigned)(SRC2 ? p.k_split : p.nsteps) * 8u * (unsigned)p.CoutPad * 16u);
+    // SRC2: the second source (zero-length descriptors where there is none: never read, k_split == nsteps)
+    const unsigned a_off2 = SRC2 ? (((unsigned)a_by * (unsigned)p.W + (unsigned)a_bx) * (unsigned)p.ld2 + (unsigned)half * 4u) * 4u : 0u;
+    const TdBuf in_buf2 = td_make_buf(SRC2 ? p.in2 : p.in, SRC2 && p.k_split < p.nsteps ? (((unsigned)p.H * (unsigned)p.W - 1u) * (unsigned)p.ld2 + (unsigned)(p.nsteps - p.k_split) * 32u) * 4u : 0u);
+    const TdBuf w_buf2 = td_make_buf(SRC2 ? p.wp2 : p.wp, SRC2 ? (unsigned)(p.nsteps - p.k_split) * 8u * (unsigned)p.CoutPad * 16u : 0u);
     unsigned b_off[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -71,18 +80,31 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 3) k_conv_adirect(ConvArgs p) {
             const int dy = ky * p.dil, dx = (la_tap - ky * KS) * p.dil;
             const int iy = a_by + dy, ix = a_bx + dx;
             const bool ok = live && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+            if (SRC2 && la_chunk >= p.k_split) {                   // KS = 1: no tap offsets; the chunk counts from the split
+                const unsigned off2 = ok ? a_off2 + (unsigned)((la_chunk - p.k_split) * 32) * 4u : TD_BUF_OOB;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) ra[g] = td_buf_ld4(in_buf2, off2, (unsigned)g * 32u);
+            } else {
             const unsigned off = ok ? a_off + (unsigned)((dy * p.W + dx) * p.Cin + la_chunk * 32) * 4u : TD_BUF_OOB;
 #pragma unroll
             for (int g = 0; g < 4; ++g) ra[g] = td_buf_ld4(in_buf, off, (unsigned)g * 32u);   // channels 8g + 4 half .. + 3 of the chunk
+            }
         }
         ++la_step;
         if (++la_tap == NTAPS) { la_tap = 0; ++la_chunk; }
     };
     int lb_step = 0;
     auto load_b = [&](f32x4 (&rb)[2]) {
-        const unsigned wsoff = (unsigned)(lb_step < p.nsteps ? lb_step : p.nsteps - 1) * w_step_bytes;
+        const int ws = lb_step < p.nsteps ? lb_step : p.nsteps - 1;
+        if (SRC2 && ws >= p.k_split) {
+            const unsigned wsoff2 = (unsigned)(ws - p.k_split) * w_step_bytes;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) rb[i] = td_buf_ld4(w_buf2, b_off[i], wsoff2);
+        } else {
+        const unsigned wsoff = (unsigned)ws * w_step_bytes;
 #pragma unroll
         for (int i = 0; i < 2; ++i) rb[i] = td_buf_ld4(w_buf, b_off[i], wsoff);
+        }
         ++lb_step;
     };
     auto store_b = [&](int buf, int i, const f32x4 (&rb)[2]) {
@@ -143,6 +165,11 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 3) k_conv_adirect(ConvArgs p) {
 // supported: the 128 x 64 tiles (weights packed for CT_128x64 / CT_128x64_DEEP: same packing), no batching
 static inline bool conv_adirect_supports(ConvTile tile, int nbatch) { return (tile == CT_128x64 || tile == CT_128x64_DEEP) && nbatch <= 1; }
 
+// the two-source form (ConvArgs.k_split >= 0): a 1x1 conv without padding, a split inside its K steps, a second map wherever the split leaves steps for one
+static inline bool conv_adirect_src2_supports(const ConvArgs& a, int KS, int stem) {
+    return KS == 1 && !stem && a.pad == 0 && a.nbatch <= 1 && a.Cin == 32 * a.nsteps && a.k_split >= 1 && a.k_split <= a.nsteps && (a.ld == 0 || a.ld >= 32 * a.k_split) &&
+           (a.k_split == a.nsteps || (a.in2 && a.wp2 && a.ld2 >= 32 * (a.nsteps - a.k_split)));
+}
 // stem: 0 no, 1 the NHWC4 image, 2 the packed-row image (7x7 only; the caller passes the padded image's H, W, Cin = 3, pad = 0)
 static inline void conv_launch_adirect(ConvArgs a, int KS, int stem, hipStream_t s) {
     a.tiles_n = a.CoutPad / 64;
@@ -152,7 +179,10 @@ static inline void conv_launch_adirect(ConvArgs a, int KS, int stem, hipStream_t
     else if (stem && KS == 7) TD_LAUNCH((k_conv_adirect<7, 1>), dim3(grid), dim3(256), lds, s, a);
     else if (stem) TD_LAUNCH((k_conv_adirect<3, 1>), dim3(grid), dim3(256), lds, s, a);
     else if (KS == 3) TD_LAUNCH((k_conv_adirect<3, 0>), dim3(grid), dim3(256), lds, s, a);
-    else TD_LAUNCH((k_conv_adirect<1, 0>), dim3(grid), dim3(256), lds, s, a);
+    else if (a.k_split >= 0) {                                       // two operand sources (conv_adirect_src2_supports: checked by the caller)
+        if (!a.ld) a.ld = a.Cin;
+        TD_LAUNCH((k_conv_adirect<1, 0, true>), dim3(grid), dim3(256), lds, s, a);
+    } else TD_LAUNCH((k_conv_adirect<1, 0>), dim3(grid), dim3(256), lds, s, a);
 }
 // the packed-row image of an H x W frame: [H + 7][Wp][3] floats -- 3 border rows on top, FOUR border pixels on the left (pixel x sits at
 // column x + 4, so that 4 consecutive pixels = 12 floats start on a 16-byte boundary and the layout kernel writes whole 16-byte vectors),

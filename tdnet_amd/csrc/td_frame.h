@@ -162,7 +162,13 @@ static int encode_frame(tdnet* n, PathLayers& L, const FrameInput& img, hipStrea
         TD_TRY(run_classifier(n, n->headmid, n->Lq, n->MID, n->cfg.nclass, L.d_cls_w, L.d_cls_b, n->lowres, s));
         return n->failed ? -1 : 0;
     }
-    run_ppm(n, c4, n->h, n->w, n->C, n->C / 2, n->C / 8, L.d_ppm_w, L.d_ppm_b, L.pid, n->rowpart, n->pooled, n->ppmfeat, n->z, s);
+    // fusion bit 2097152 (plan_enc_fold): z is not assembled; the first layers read c4's slice and the basis table against the frame's G rows
+    const int XS = n->C / 2, FS = n->C / 8;
+    const ConvLayer* const firstL[3] = {&L.enc_v, &L.enc_q0, &L.enc_k0};
+    const PpmFoldArgs fold = n->enc_fold ? ppm_fold_args(firstL, n->fold_g, n->ppmfeat, XS, FS) : PpmFoldArgs();
+    run_ppm(n, c4, n->h, n->w, n->C, XS, FS, L.d_ppm_w, L.d_ppm_b, L.pid, n->rowpart, n->pooled, n->ppmfeat, n->z, s, n->enc_fold ? &fold : nullptr);
+    n->z_pending = n->enc_fold;
+    n->z_path = (int)(&L - &n->paths[0]);
     // Encoding, pre=False (transformer.py:52-56) and pre=True (:34-50) -> pending cache entry; q_ and v_ are the stride-4 subsample of
     // q_cur / v_cur.  The first layers side by side, then the second layers (the k branch on the 16x smaller key grid).
     const int slot = free_slot(n);
@@ -170,6 +176,11 @@ static int encode_frame(tdnet* n, PathLayers& L, const FrameInput& img, hipStrea
     CacheSlot& cs = n->slots[slot];
     const ConvCall first[3] = {{&L.enc_v, n->z, n->h, n->w, n->v_cur}, {&L.enc_q0, n->z, n->h, n->w, n->q1}, {&L.enc_k0, n->z, n->h, n->w, n->k1}};
     const ConvCall second[2] = {{&L.enc_q1, n->q1, n->h, n->w, n->q_cur}, {&L.enc_k1, n->k1, n->hk, n->wk, cs.k}};
+    if (n->enc_fold) {
+        float* const outs[3] = {n->v_cur, n->q1, n->k1};
+        for (int i = 0; i < 3; ++i)
+            TD_TRY(run_conv_src2(n, *firstL[i], c4 + L.pid * XS, n->C, XS / 32, XS / 32 + TD_PPM_BASIS / 32, n->ppm_basis, TD_PPM_BASIS, n->fold_g[i], n->h, n->w, nullptr, outs[i], s));
+    } else
     TD_TRY(run_conv_group(n, n->opts, first, 3, s));
     TD_TRY(run_conv_group(n, n->opts, second, 2, s));
     prof_begin(n, 2, false, 0, s);                                    // both cache entries (q_, v_) in one launch

@@ -27,6 +27,13 @@ struct GemmArgs {
     int MP;               // rows between consecutive batches of a and out (>= M; padded planes of the Winograd workspaces, td_wino.h)
     int wshare = 0;       // nbatch > 1 with ONE weight set and bias for all batches: a 1x1 conv over a strided set of image rows (batch = row,
                           // M = W pixels, MP = row pitch in pixels) -- the downsample conv of one row-parity chain (td_frame.h run_ds_rows); resid must be null
+    // Two operand sources (k_gemm_persistent<.., SRC2 = true>; nbatch == 1): K steps 0 .. k_split - 1 read A = a with row stride lda and the
+    // weights wp, steps k_split .. K/32 - 1 read A = a2 with row stride lda2 and the weights wp2 (steps counted from 0 again, same NPad).
+    // k_split < 0: the one-source kernel (a: row stride K).  k_split == K/32: the two-source kernel with nothing behind the split (a2, wp2 unused).
+    int k_split = -1;
+    int lda = 0, lda2 = 0;
+    const float* a2 = nullptr;
+    const float* wp2 = nullptr;
 #ifdef TD_GEMM_TRACE      // tools/gemm_trace.hip only: per workgroup 64 x u64 -- HW_ID, XCC_ID, start, then (end of K loop, end of epilogue) per tile
     unsigned long long* trace;   // in s_memrealtime ticks (100 MHz); TD_GEMM_TRACE == 2: the end of every two-step period as well
 #endif
@@ -44,9 +51,13 @@ struct GemmArgs {
 // plain epilogue (bias, activation and residual belong to the Winograd output transform: GemmArgs.bias / act / resid are ignored);
 // ROLE 2 = a 1x1 convolution WITHOUT residual: no residual loads in the epilogue (with ROLE 0 they are issued unconditionally --
 // zero-record descriptor when absent -- and, vmcnt being in order, waiting for them means waiting for the next tile's prefetch).
-template <int BM, int BN, int WGM, int WGN, int ROLE>
+// SRC2: the A operand and the weights come from a second pair of buffers from K step p.k_split on (GemmArgs): the Encoding's first 1x1 convs read
+// c4's channel slice, then the pyramid's basis columns against the per-frame G rows (td_misc.h k_ppm_fold_g) -- the concatenated map is never
+// written.  The switch is wave-uniform and lives in the loader alone; SRC2 = false is the kernel as it was.
+template <int BM, int BN, int WGM, int WGN, int ROLE, bool SRC2 = false>
 TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_persistent(GemmArgs p) {
     static_assert(WGM * WGN == 4, "4 waves per block");
+    static_assert(!SRC2 || ROLE != 1, "two sources: a 1x1 conv, not the batched Winograd GEMMs");
     constexpr int WM = BM / WGM, WN = BN / WGN, MT = WM / 32, NT = WN / 32;
     constexpr int AL = BM / 32, BL = BN / 32;
     static_assert((AL == 2 || AL == 4) && (BL == 2 || BL == 4), "staging slots are spread over the 4 k-groups");
@@ -94,13 +105,28 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_persistent(GemmArgs p) {
     TilePos lpos = pos0;
     TdBuf a_buf, w_buf;
     unsigned a_off[AL], b_off[BL];
+    int l_k0 = 0;                                                    // SRC2: the first K step of the source the loader is on
+    auto loader_enter_source = [&](bool second) {                    // SRC2: descriptors and row offsets of one source for the tile at lpos (wave-uniform choice)
+        const unsigned ld = (unsigned)(second ? p.lda2 : p.lda), ks = (unsigned)(second ? nsteps - p.k_split : p.k_split);
+        l_k0 = second ? p.k_split : 0;
+        a_buf = td_make_buf(second ? p.a2 : p.a, ((unsigned)(p.M - 1) * ld + ks * 32u) * 4u);   // the last row ends after this source's K columns
+        w_buf = td_make_buf(second ? p.wp2 : p.wp, ks * w_step_bytes);
+#pragma unroll
+        for (int i = 0; i < AL; ++i) {
+            const int m = lpos.tm * BM + a_row + 32 * i;
+            a_off[i] = m < p.M ? ((unsigned)m * ld + (unsigned)a_kq * 4u) * 4u : TD_BUF_OOB;
+        }
+    };
     auto loader_enter_tile = [&]() {
+        if (SRC2) loader_enter_source(false);
+        else {
         a_buf = td_make_buf(p.a + (size_t)lpos.b * p.MP * p.K, a_bytes);
         w_buf = td_make_buf(p.wp + (p.wshare ? (size_t)0 : (size_t)lpos.b * nsteps * 8 * p.NPad * 4), w_bytes);
 #pragma unroll
         for (int i = 0; i < AL; ++i) {
             const int m = lpos.tm * BM + a_row + 32 * i;
             a_off[i] = m < p.M ? ((unsigned)m * (unsigned)p.K + (unsigned)a_kq * 4u) * 4u : TD_BUF_OOB;
+        }
         }
 #pragma unroll
         for (int i = 0; i < BL; ++i) {
@@ -109,15 +135,17 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_persistent(GemmArgs p) {
         }
     };
     auto load_tile = [&](f32x4 (&ra)[AL], f32x4 (&rb)[BL]) {
-        const unsigned kb = (unsigned)l_step * 128u;                 // 32 floats per step
+        if (SRC2 && l_step == p.k_split) loader_enter_source(true);  // never taken with k_split == nsteps
+        const unsigned kb = (unsigned)(l_step - (SRC2 ? l_k0 : 0)) * 128u;   // 32 floats per step
 #pragma unroll
         for (int i = 0; i < AL; ++i) ra[i] = td_buf_ld4(a_buf, a_off[i], kb);   // the K offset rides in an SGPR: the range check looks at a_off only, so an out-of-range row stays out of range
-        const unsigned wsoff = (unsigned)l_step * w_step_bytes;
+        const unsigned wsoff = (unsigned)(l_step - (SRC2 ? l_k0 : 0)) * w_step_bytes;
 #pragma unroll
         for (int i = 0; i < BL; ++i) rb[i] = td_buf_ld4(w_buf, b_off[i], wsoff);
         if (++l_step == nsteps) {
             l_step = 0;
             if (++l_tile < my_tiles) { advance(lpos); loader_enter_tile(); }   // past the end: stay on the last tile (never consumed)
+            else if (SRC2) loader_enter_tile();                       // ... on its FIRST source again: step 0 counts from there
         }
     };
     auto store_a = [&](int buf, int i, const f32x4 (&ra)[AL]) {
@@ -243,6 +271,12 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_persistent(GemmArgs p) {
 static inline int gemm_blocks_per_cu(ConvTile t) { const ConvTileDims d = conv_tile_dims(t); return d.BM == 128 && d.BN == 128 ? 2 : 3; }
 // the two-step period needs an even number of K steps
 static inline bool gemm_supports(int K) { return K % 64 == 0; }
+// the two-source form (GemmArgs.k_split >= 0): one GEMM, a split inside K, and a second source wherever the split leaves steps for one
+static inline bool gemm_src2_supports(const GemmArgs& a) {
+    const int nsteps = a.K / 32;
+    return gemm_supports(a.K) && a.nbatch == 1 && !a.wshare && a.M >= 1 && a.k_split >= 1 && a.k_split <= nsteps && (a.k_split == nsteps || (a.a2 && a.wp2 && a.lda2 >= 32 * (nsteps - a.k_split))) &&
+           (a.lda == 0 || a.lda >= 32 * a.k_split);
+}
 
 // Tile choice for the persistent kernel.  What matters is how many ROUNDS of the resident workgroups (256 CUs x bpc) the tile
 // list takes, and how full the last round is: a CU working on j < bpc tiles finishes them faster, but not j/bpc faster (one
@@ -273,6 +307,11 @@ static inline void gemm_launch_t(GemmArgs a, int bpc, int grid_cap, hipStream_t 
     const long total = (long)a.tiles_m * a.tiles_n * a.nbatch;
     long grid = grid_cap > 0 ? grid_cap : 256L * bpc;
     if (grid > total) grid = total;
+    if (a.k_split >= 0) {                                             // two operand sources (gemm_src2_supports: checked by the caller)
+        if (!a.lda) a.lda = a.K;
+        if (!a.resid) TD_LAUNCH((k_gemm_persistent<BM, BN, WGM, WGN, 2, true>), dim3((unsigned)grid), dim3(256), (ConvLds<BM, BN>::BYTES), s, a);
+        else TD_LAUNCH((k_gemm_persistent<BM, BN, WGM, WGN, 0, true>), dim3((unsigned)grid), dim3(256), (ConvLds<BM, BN>::BYTES), s, a);
+    } else
     if (a.nbatch > 1 && !a.wshare) TD_LAUNCH((k_gemm_persistent<BM, BN, WGM, WGN, 1>), dim3((unsigned)grid), dim3(256), (ConvLds<BM, BN>::BYTES), s, a);
     else if (!a.resid) TD_LAUNCH((k_gemm_persistent<BM, BN, WGM, WGN, 2>), dim3((unsigned)grid), dim3(256), (ConvLds<BM, BN>::BYTES), s, a);
     else TD_LAUNCH((k_gemm_persistent<BM, BN, WGM, WGN, 0>), dim3((unsigned)grid), dim3(256), (ConvLds<BM, BN>::BYTES), s, a);

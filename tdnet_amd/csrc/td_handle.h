@@ -183,7 +183,7 @@ struct ConvLayer {
 };
 
 // Per-handle kernel configuration (include/tdnet.h tdnet_opts); nothing here is process-wide: two handles in one process may differ.
-static_assert(TDNET_FUSION_DEFAULT == 2072614 && TDNET_FUSION_MASK == 2072614 && TDNET_OVERLAP_DEFAULT == 41 && TDNET_OVERLAP_MASK == 0x3f,
+static_assert(TDNET_FUSION_DEFAULT == 4169766 && TDNET_FUSION_MASK == 4169766 && TDNET_OVERLAP_DEFAULT == 41 && TDNET_OVERLAP_MASK == 0x3f,
               "the named option bits of include/tdnet.h must add up to the documented values");
 static tdnet_opts opts_or_default(const tdnet_opts* o) {
     tdnet_opts d;
@@ -327,6 +327,13 @@ struct tdnet {
     float* c4 = nullptr;                                              // backbone output of the last frame (bx, or br in the fp16-activation mode)
     _Float16* vt16 = nullptr;                                         // fp16 attention: V' re-tiled [LkPad / 8][DV][8]; precision 2: its three bf16 parts (3x that, td_attn_b3.h)
     bool ln_pending = false;                                          // the `ln` map of the last frame was not materialised (fusion bit 4)
+    // The pyramid folded through the Encoding's first 1x1 convs (fusion bit 2097152; td_weights.h plan_enc_fold, td_misc.h k_ppm_fold_g).  All of it is
+    // this handle's: the weight block is shared (tdnet_create_shared) and only read.
+    bool enc_fold = false;                                            // this handle's frames take the fold
+    float* ppm_basis = nullptr;                                       // [h w][64] bilinear coefficients of the 50 bins (+ 14 zero columns): a function of (h, w) alone
+    float* fold_g[3] = {nullptr, nullptr, nullptr};                   // G of enc_v / enc_q0 / enc_k0 as two packed K steps [2][8][CoutPad][4]; rows 50 .. 63 stay zero
+    bool z_pending = false;                                           // the `z` map of the last frame was not assembled
+    int z_path = 0;
     int ln_path = 0;
     bool feat_is_vcur = false;                                        // warm-up frame (td4_psp18.py:142-143): the "feat" stage IS v_cur (no copy is made)
     bool failed = false;                                              // a launch helper reported an error during the current forward

@@ -204,6 +204,30 @@ static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
     return 0;
 }
 
+// A 1x1 conv with two operand sources (td_gemm.h / td_conv_ad.h SRC2): K steps 0 .. k_split - 1 from the map `in` (pixel stride ld floats) and the layer's packed
+// weights, steps k_split .. nsteps - 1 from in2 (pixel stride ld2) and wp2.  k_split == nsteps: no second source -- the layer's own conv on the two-source kernel.
+// Only the persistent fp32 GEMM and the fp32 direct 1x1 conv have the form; any other plan is an error here (plan_enc_fold keeps a frame away from it).
+static int run_conv_src2(tdnet* n, const ConvLayer& L, const float* in, int ld, int k_split, int nsteps, const float* in2, int ld2, const float* wp2,
+                         int H, int W, const float* resid, float* out, hipStream_t s) {
+    if (L.KS != 1 || L.stem || L.wino) return td_fail("internal: two operand sources need a 1x1 conv");
+    const ConvArgs a0 = conv_args(L, in, H, W, resid, out);
+    prof_begin(n, 0, 0, 2.0 * L.Cout * 32.0 * nsteps * a0.M, s);      // the executed FLOP
+    int rc = 0;
+    if (L.route == CR_GEMM1X1 && L.gemm == GK_PERSISTENT) {
+        GemmArgs ga = gemm_args(L, in, a0.M, 1, L.d_bias, resid, out, L.act);
+        ga.K = 32 * nsteps; ga.k_split = k_split; ga.lda = ld; ga.a2 = in2; ga.lda2 = ld2; ga.wp2 = wp2;
+        if (!gemm_src2_supports(ga)) rc = td_fail("internal: the persistent GEMM cannot take this second operand source");
+        else launch_gemm(L, ga, 0, s);
+    } else if (L.route == CR_ADIRECT) {
+        ConvArgs a = a0;
+        a.Cin = 32 * nsteps; a.nsteps = nsteps; a.k_split = k_split; a.ld = ld; a.in2 = in2; a.ld2 = ld2; a.wp2 = wp2;
+        if (resid || !conv_adirect_src2_supports(a, L.KS, 0)) rc = td_fail("internal: the direct 1x1 conv cannot take this second operand source");
+        else conv_launch_adirect(a, 1, 0, s);
+    } else rc = td_fail("internal: this conv's kernel has no second operand source");
+    prof_end(n, s);
+    return rc;
+}
+
 struct ConvCall { const ConvLayer* L; const float* in; int H, W; float* out; };
 // Up to three independent convs in one launch when they share a kernel form (fp16 mode: the register-staged k_conv_igemm_h on the same tile,
 // kernel size and storage types; `fusion` bit 131072); otherwise one launch each, in order.
@@ -284,16 +308,28 @@ static void run_layernorm(tdnet* n, const float* x, int HW, int C, const float* 
     prof_end(n, s);
 }
 
+static void launch_ppm_assemble(const float* c4, const float* ppmfeat, float* z, int h, int w, int C, int xs_off, int XS, int FS, hipStream_t s) {
+    TD_LAUNCH(k_ppm_assemble, dim3(td_grid_for((long)h * w * (C / 4))), dim3(256), 0, s, c4, ppmfeat, z, h, w, C, xs_off, XS, FS);
+}
+// The G launch of the fold for the three first layers of a path's Encoding (g: the handle's buffers, one per layer)
+static PpmFoldArgs ppm_fold_args(const ConvLayer* const L[3], float* const g[3], const float* ppmfeat, int XS, int FS) {
+    PpmFoldArgs a;
+    a.nl = 3; a.feat = ppmfeat; a.XS = XS; a.FS = FS; a.first[0] = 0;
+    for (int i = 0; i < 3; ++i) { a.wp[i] = L[i]->d_wp; a.g[i] = g[i]; a.NPad[i] = L[i]->CoutPad; a.first[i + 1] = a.first[i] + L[i]->CoutPad / 64; }
+    return a;
+}
 // XS = channels of c4 kept (c/path_num, offset pid*XS), FS = channels kept of each pyramid conv (c/(4 path_num))
+// fold != nullptr (fusion bit 2097152, plan_enc_fold): z is not assembled; the pooled features go through the Encoding's first-layer weights instead
+// (k_ppm_fold_g -> the G rows the two-source convs read).  As many launches either way.
 static void run_ppm(tdnet* n, const float* c4, int h, int w, int C, int XS, int FS, const float* wgt, const float* bias, int pid,
-                    float* rowpart, float* pooled, float* ppmfeat, float* z, hipStream_t s) {
+                    float* rowpart, float* pooled, float* ppmfeat, float* z, hipStream_t s, const PpmFoldArgs* fold = nullptr) {
     prof_begin(n, 2, false, 0, s);
     const PpmAtoms at = ppm_atoms(w);                                 // the row is read once: atoms between the bin edges of all four levels
     (void)pooled;
     TD_LAUNCH(k_ppm_rowbins, dim3(h * ((C + 511) / 512)), dim3(1024), at.n * 512 * 4, s, c4, rowpart, w, C, at);   // rowpart: [h][12][C] row bins
     TD_LAUNCH(k_ppm_pool_conv, dim3(50 * (FS / 64)), dim3(256), (256 + C) * 4, s, (const float*)rowpart, wgt, bias, ppmfeat, h, w, C, FS);
-    TD_LAUNCH(k_ppm_assemble, dim3(td_grid_for((long)h * w * (C / 4))), dim3(256), 0, s, c4, (const float*)ppmfeat, z, h, w, C,
-              pid * XS, XS, FS);
+    if (fold) TD_LAUNCH(k_ppm_fold_g, dim3(TD_PPM_BINS * fold->first[fold->nl]), dim3(256), 256 * 4, s, *fold);
+    else launch_ppm_assemble(c4, ppmfeat, z, h, w, C, pid * XS, XS, FS, s);
     prof_end(n, s);
 }
 

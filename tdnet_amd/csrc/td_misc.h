@@ -4,6 +4,8 @@
 #include "td_device.h"
 #include "td_conv.h"   // td_ld4 / td_st4
 
+#include <vector>
+
 static inline int td_grid_for(long work_items, int block = 256, int max_blocks = 256 * 8) {
     long g = (work_items + block - 1) / block;
     if (g < 1) g = 1;
@@ -259,6 +261,83 @@ TD_KERNEL void k_ppm_assemble(const float* __restrict__ c4, const float* __restr
             v = td_bilerp(ly, lx, v00, v01, v10, v11);
         }
         td_st4(z + (size_t)pix * ZC + c, v);
+    }
+}
+
+// ---- The pyramid folded through the Encoding's first 1x1 convs (fusion bit 2097152) --------------------------------------------------------
+// The 4 FS pyramid channels of z[p] are a linear function of the 50 pooled vectors: z[p][XS + FS l + f] = sum_j B[p][j] feat[j][f] over the bins j of
+// level l, B the bilinear coefficients above.  A 1x1 conv W on z is linear up to its bias and activation, so
+//     W z[p] = W[:, :XS] c4slice[p] + sum_j B[p][j] G[j][:],      G[j][n] = sum_f feat[j][f] W[n][XS + FS lvl(j) + f]
+// and the conv is a GEMM over K = XS + 64 (50 basis columns padded to 64) with a second operand source behind step XS / 32 (td_gemm.h / td_conv_ad.h
+// SRC2): A = the basis table B, weights = G.  z is never written.  (A non-finite pooled bin reaches every pixel through 0 * Inf; through the level-1 bin,
+// which spans the map, it already did.)
+constexpr int TD_PPM_BINS = 50, TD_PPM_BASIS = 64;
+// B[h w][64] on the host, once per geometry: each coefficient in double from k_ppm_assemble's expressions (the float sy / fy / ly, so the taps are the
+// kernel's own), the four tap weights of a level ACCUMULATED onto their bins (taps coincide at the borders and for o = 1), rounded once to float.  Bin
+// order = k_ppm_pool_conv's (level-major, then by, then bx); columns 50 .. 63 are zero; every row sums to 4.
+static inline void ppm_basis_table(int h, int w, std::vector<float>& B) {
+    B.assign((size_t)h * w * TD_PPM_BASIS, 0.f);
+    static const int lv[4] = {1, 2, 3, 6}, boff[4] = {0, 1, 5, 14};
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            double row[TD_PPM_BINS] = {0.0};
+            for (int l = 0; l < 4; ++l) {
+                const int o = lv[l];
+                const float sy = (h > 1) ? (float)(o - 1) / (float)(h - 1) : 0.f;
+                const float sx = (w > 1) ? (float)(o - 1) / (float)(w - 1) : 0.f;
+                const float fy = sy * (float)y, fx = sx * (float)x;
+                const int y0 = (int)fy, x0 = (int)fx;
+                const int y1 = y0 + (y0 < o - 1 ? 1 : 0), x1 = x0 + (x0 < o - 1 ? 1 : 0);
+                const double ly = (double)(fy - (float)y0), lx = (double)(fx - (float)x0);
+                row[boff[l] + y0 * o + x0] += (1.0 - ly) * (1.0 - lx);
+                row[boff[l] + y0 * o + x1] += (1.0 - ly) * lx;
+                row[boff[l] + y1 * o + x0] += ly * (1.0 - lx);
+                row[boff[l] + y1 * o + x1] += ly * lx;
+            }
+            float* out = B.data() + ((size_t)y * w + x) * TD_PPM_BASIS;
+            for (int j = 0; j < TD_PPM_BINS; ++j) out[j] = (float)row[j];
+        }
+}
+// G of up to three layers in one launch, written straight into the packed K-step layout the conv kernels read ([2][8][NPad][4]: row j = step j / 32,
+// k-group (j % 32) / 4, element j % 4), from the layers' own packed weights (steps XS / 32 .. of [K/32][8][NPad][4]; BN folded in).  Packed columns
+// (slots) in, the same slots out: the tile's column permutation never has to be undone.  Rows 50 .. 63 are zeroed once, when the buffers are made.
+// grid = 50 bins x (sum of NPad / 64) slot groups, block = 256 = 64 slots x 4 slices of FS.  FIXED summation order: thread (slot, slice) adds its
+// FS / 4 products in ascending f, one fma chain from 0; the four slices are combined as ((s0 + s1) + s2) + s3.
+struct PpmFoldArgs {
+    const float* wp[3];   // packed weights of the layer (shared weight block: read only)
+    float* g[3];          // [2][8][NPad][4], handle-owned
+    int NPad[3];
+    int first[4];         // slot group at which layer i starts; first[nl] = total
+    int nl;
+    const float* feat;    // [50][FS]
+    int XS, FS;
+};
+TD_KERNEL void k_ppm_fold_g(PpmFoldArgs p) {
+    TD_DYN_LDS(smem);
+    float* red = reinterpret_cast<float*>(smem);               // [4][64]
+    const int total = p.first[p.nl], bin = blockIdx.x / total, grp = blockIdx.x % total;
+    const int li = (p.nl > 2 && grp >= p.first[2]) ? 2 : (p.nl > 1 && grp >= p.first[1]) ? 1 : 0;
+    const int fl = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int NPad = p.NPad[li], slot = (grp - p.first[li]) * 64 + fl;
+    const int lvl = bin >= 14 ? 3 : bin >= 5 ? 2 : bin >= 1 ? 1 : 0;
+    const int fq = p.FS >> 2;
+    const float* ft = p.feat + (size_t)bin * p.FS + sl * fq;
+    const float* wp = p.wp[li];
+    const int k0 = p.XS + p.FS * lvl + sl * fq;                  // a multiple of 4: one 16-byte k-group element run per load
+    float s = 0.f;
+#pragma unroll 4
+    for (int f = 0; f < fq; f += 4) {
+        const int k = k0 + f;
+        const f32x4 wv = td_ld4(wp + ((size_t)((k >> 5) * 8 + ((k & 31) >> 2)) * NPad + slot) * 4);
+        const f32x4 fv = td_ld4(ft + f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(fv[e], wv[e], s);
+    }
+    red[sl * 64 + fl] = s;
+    __syncthreads();
+    if (sl == 0) {
+        s = ((red[fl] + red[64 + fl]) + red[128 + fl]) + red[192 + fl];
+        p.g[li][((size_t)((bin >> 5) * 8 + ((bin & 31) >> 2)) * NPad + slot) * 4 + (bin & 3)] = s;
     }
 }
 

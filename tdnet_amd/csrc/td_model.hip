@@ -136,7 +136,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     TD_ON_DEVICE(n);
     for (float* q : {n->img4, n->s1, n->s1b, n->bx, n->bt, n->br, n->bu, n->rowpart, n->pooled, n->ppmfeat, n->z, n->v_cur, n->q1, n->q_cur,
                      n->k1, n->vp, n->chain_a, n->chain_b, n->feat, n->ln_part, n->ln_mean, n->ln_rstd, n->ln, n->headmid,
-                     n->lowres, n->stage_tmp, n->logits_tmp, n->wino_v, n->wino_m})
+                     n->lowres, n->stage_tmp, n->logits_tmp, n->wino_v, n->wino_m, n->ppm_basis, n->fold_g[0], n->fold_g[1], n->fold_g[2]})
         if (q) hipFree(q);
     for (auto& s : n->slots) { if (s.q) hipFree(s.q); if (s.k) hipFree(s.k); if (s.v) hipFree(s.v); }
     for (auto& r : n->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
@@ -546,6 +546,11 @@ extern "C" long tdnet_get_stage(tdnet_t* n, const char* name, float* host, size_
                   (const float*)n->ln_mean, (const float*)n->ln_rstd, (const float*)PL.d_ln_g, (const float*)PL.d_ln_b, n->ln, n->Lq, n->DV);
         TD_HIP(hipDeviceSynchronize());
         n->ln_pending = false;
+    }
+    if (s == "z" && n->z_pending) {                                    // fusion bit 2097152 skipped this map: assemble it now from c4 and the pooled features, same kernel
+        launch_ppm_assemble(n->c4, n->ppmfeat, n->z, n->h, n->w, n->C, n->paths[n->z_path].pid * (n->C / 2), n->C / 2, n->C / 8, (hipStream_t)0);
+        TD_HIP(hipDeviceSynchronize());
+        n->z_pending = false;
     }
     if (nhwc_map && !planar) {                                         // [HW][C] -> [C][HW] like the reference's NCHW maps
         TD_LAUNCH(k_nhwc_to_nchw, dim3(td_grid_for((long)count)), dim3(256), 0, (hipStream_t)0, src, n->stage_tmp, rows, (int)C);

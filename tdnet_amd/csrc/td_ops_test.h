@@ -338,6 +338,89 @@ extern "C" int tdnet_op_ppm(const float* c4, int h, int w, const float* w_host, 
     for (float* q : {dw, db, rowpart, pooled, ppmfeat}) hipFree(q);
     return 0;
 }
+// The first layers of a path's Encoding on c4 as a frame runs them (td_frame.h encode_frame): pyramid pooling, then the value conv (C -> DV, no activation), the
+// query conv (C -> 64, LeakyReLU) and the stride-4 key conv (C -> 64, LeakyReLU), planned with the default options for an h x w map.  fold = 1: the pyramid as 64
+// basis columns (fusion bit 2097152: k_ppm_fold_g + the two-source kernels; an error, before anything is allocated, where plan_enc_fold refuses); fold = 0: through
+// the assembled map z.  ppm_w [4][C/4][C] / ppm_b [4][C/4]: the BN-folded pyramid convs, of which path `pid` keeps channels pid * C/8 .. of each; wv / wq / wk [Cout][C]
+// and their biases likewise folded.  basis_out (device, [h w][64], may be NULL): the fold's coefficient table.
+extern "C" int tdnet_op_enc_first(const float* c4, int h, int w, int C, int pid, const float* ppm_w, const float* ppm_b, const float* wv, const float* bv, int DV,
+                                  const float* wq, const float* bq, const float* wk, const float* bk, int fold, float* v_out, float* q_out, float* k_out,
+                                  float* basis_out, void* stream) {
+    const char* who = "tdnet_op_enc_first";
+    if (h < 1 || w < 1 || C < 512 || C % 512 || DV < 1 || pid < 0 || pid > 1) return td_fail("%s: a map of at least 1 x 1, C a multiple of 512 and pid 0 / 1 expected", who);
+    if (!c4 || !ppm_w || !ppm_b || !wv || !wq || !wk || !v_out || !q_out || !k_out) return td_fail("%s: null argument", who);
+    hipStream_t s = (hipStream_t)stream;
+    const tdnet_opts o = opts_or_default(nullptr);
+    const int XS = C / 2, FS = C / 8, F4 = C / 4, hk = key_size(h), wk_ = key_size(w);
+    ConvLayer L[3];
+    if (plan_conv(L[0], DV, C, 1, 1, 1, 0, false, (long)h * w, o) || plan_conv(L[1], 64, C, 1, 1, 1, 2, false, (long)h * w, o) ||
+        plan_conv(L[2], 64, C, 1, 4, 1, 2, false, (long)hk * wk_, o)) return -1;
+    if (fold && !plan_enc_fold(o, L[0], L[1], L[2], XS, FS)) return td_fail("%s: a frame would not fold these layers", who);
+    std::vector<float> pw((size_t)4 * FS * C), pb((size_t)4 * FS);
+    for (int j = 0; j < 4; ++j)
+        for (int f = 0; f < FS; ++f) {
+            for (int c = 0; c < C; ++c) pw[((size_t)j * C + c) * FS + f] = ppm_w[((size_t)j * F4 + pid * FS + f) * C + c];
+            pb[j * FS + f] = ppm_b[j * F4 + pid * FS + f];
+        }
+    float *dw = nullptr, *db = nullptr, *rowpart = nullptr, *pooled = nullptr, *ppmfeat = nullptr, *z = nullptr, *basis = nullptr, *g[3] = {nullptr, nullptr, nullptr};
+    auto cleanup = [&]() {
+        for (float* q : {dw, db, rowpart, pooled, ppmfeat, z, basis, g[0], g[1], g[2]}) if (q) hipFree(q);
+        for (ConvLayer& l : L) free_conv_layer(l);
+    };
+    const float* const wh[3] = {wv, wq, wk};
+    const float* const bh[3] = {bv, bq, bk};
+    int rc = 0;
+    for (int i = 0; i < 3 && !rc; ++i) {
+        std::vector<float> wi(wh[i], wh[i] + (size_t)L[i].Cout * C), bi;
+        if (bh[i]) bi.assign(bh[i], bh[i] + L[i].Cout);
+        rc = upload_conv(L[i], wi, bi);
+    }
+    if (!rc && (upload(&dw, pw) || upload(&db, pb) || dev_alloc(&rowpart, (size_t)h * 36 * C) || dev_alloc(&pooled, (size_t)50 * C) || dev_alloc(&ppmfeat, (size_t)50 * FS))) rc = -1;
+    if (!rc && !fold && dev_alloc(&z, (size_t)h * w * C)) rc = -1;
+    if (!rc && fold) {
+        std::vector<float> B;
+        ppm_basis_table(h, w, B);
+        if (upload(&basis, B)) rc = -1;
+        for (int i = 0; i < 3 && !rc; ++i) {
+            const size_t cnt = (size_t)2 * 8 * L[i].CoutPad * 4;
+            if (dev_alloc(&g[i], cnt) || hipMemsetAsync(g[i], 0, cnt * sizeof(float), s) != hipSuccess) rc = -1;
+        }
+        if (!rc && basis_out && hipMemcpyAsync(basis_out, basis, B.size() * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
+    }
+    float* const outs[3] = {v_out, q_out, k_out};
+    if (!rc) {
+        const ConvLayer* const Lp[3] = {&L[0], &L[1], &L[2]};
+        const PpmFoldArgs fa = fold ? ppm_fold_args(Lp, g, ppmfeat, XS, FS) : PpmFoldArgs();
+        run_ppm(nullptr, c4, h, w, C, XS, FS, dw, db, pid, rowpart, pooled, ppmfeat, z, s, fold ? &fa : nullptr);
+        for (int i = 0; i < 3 && !rc; ++i)
+            rc = fold ? run_conv_src2(nullptr, L[i], c4 + pid * XS, C, XS / 32, XS / 32 + TD_PPM_BASIS / 32, basis, TD_PPM_BASIS, g[i], h, w, nullptr, outs[i], s)
+                      : run_conv(nullptr, L[i], z, h, w, nullptr, outs[i], s);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    cleanup();
+    return rc;
+}
+// A 1x1 conv planned as tdnet_op_conv2d plans it, run on the TWO-SOURCE form of its kernel with nothing behind the split (k_split == nsteps, null second
+// source): the same products in the same order as the one-source kernel.  An error, with nothing allocated or launched, where the plan is neither the persistent
+// fp32 GEMM nor the fp32 direct 1x1 conv (those two have the form).
+extern "C" int tdnet_op_conv1x1_src2_null(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout, int stride,
+                                          const float* resid, int act, const tdnet_opts* opts, int tile, float* out, void* stream) {
+    const char* who = "tdnet_op_conv1x1_src2_null";
+    if (H < 1 || W < 1 || Cin < 1 || Cout < 1 || stride < 1) return td_fail("%s: empty input", who);
+    if (tile >= CT_COUNT) return td_fail("%s: tile must be < %d", who, CT_COUNT);
+    const tdnet_opts o = opts_or_default(opts);
+    ConvLayer L;
+    const long M = (long)out_size(H, 1, stride, 1, 0) * out_size(W, 1, stride, 1, 0);
+    if (plan_conv(L, Cout, Cin, 1, stride, 1, act, false, M, o, tile < 0 ? -1 : tile)) return -1;
+    if (!((L.route == CR_GEMM1X1 && L.gemm == GK_PERSISTENT) || (L.route == CR_ADIRECT && !resid))) return td_fail("%s: this conv's kernel has no two-source form", who);
+    std::vector<float> w(w_host, w_host + (size_t)Cout * Cin), b;
+    if (bias_host) b.assign(bias_host, bias_host + Cout);
+    int rc = upload_conv(L, w, b);
+    if (!rc) rc = run_conv_src2(nullptr, L, in, Cin, L.nsteps, L.nsteps, nullptr, 0, nullptr, H, W, resid, out, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    free_conv_layer(L);
+    return rc;
+}
 extern "C" int tdnet_op_classifier(const float* x, int HW, int C, const float* w, const float* b, int NC, float* out, void* stream) {
     if (NC < 1 || NC > 256) return td_fail("tdnet_op_classifier: NC must be in 1..256");
     TD_TRY(run_classifier(nullptr, x, HW, C, NC, w, b, out, (hipStream_t)stream));

@@ -109,6 +109,16 @@ static int plan_conv(ConvLayer& L, int Cout, int Cin, int KS, int stride, int di
     return 0;
 }
 
+// Whether a frame folds the pyramid through the Encoding's first 1x1 convs (fusion bit 2097152) instead of assembling z: decided once, from the options and the
+// three planned layers alone.  The two-source kernel forms exist for the persistent fp32 GEMM and the fp32 direct 1x1 conv; the split is at K step XS / 32 and
+// K = XS + 64 must stay a whole number of two-step periods.  False: the frame runs as without the bit.
+static bool plan_enc_fold(const tdnet_opts& o, const ConvLayer& v, const ConvLayer& q0, const ConvLayer& k0, int XS, int FS) {
+    const auto gemm = [](const ConvLayer& L) { return L.route == CR_GEMM1X1 && L.gemm == GK_PERSISTENT; };
+    return (o.fusion & TDNET_FUSION_PPM_FOLD) && o.precision == 0 && gemm(v) && gemm(q0) && k0.route == CR_ADIRECT && k0.KS == 1 && !k0.stem &&
+           XS >= 64 && XS % 64 == 0 && FS % 16 == 0 && v.Cin == XS + 4 * FS && q0.Cin == v.Cin && k0.Cin == v.Cin &&
+           v.CoutPad % 64 == 0 && q0.CoutPad % 64 == 0 && k0.CoutPad % 64 == 0;
+}
+
 // pack `count` elements of T on the host, allocate, copy: the device image of a layer's weights
 template <typename T, typename Pack>
 static int upload_packed(float** d, size_t count, Pack pack) {
@@ -356,6 +366,21 @@ static int alloc_workspace(tdnet* n) {
         }
     }
     if (psp) return 0;
+    {   // the pyramid fold: the basis table of this geometry and the G buffers (zeroed: rows 50 .. 63 are never written again)
+        const PathLayers& L0 = n->paths[0];
+        n->enc_fold = plan_enc_fold(n->opts, L0.enc_v, L0.enc_q0, L0.enc_k0, (int)(C / 2), (int)FS);
+        if (n->enc_fold) {
+            std::vector<float> B;
+            ppm_basis_table(n->h, n->w, B);
+            TD_TRY(upload(&n->ppm_basis, B));
+            const ConvLayer* Ls[3] = {&L0.enc_v, &L0.enc_q0, &L0.enc_k0};
+            for (int i = 0; i < 3; ++i) {
+                const size_t cnt = (size_t)2 * 8 * Ls[i]->CoutPad * 4;
+                if (dev_alloc(&n->fold_g[i], cnt)) return -1;
+                TD_HIP(hipMemset(n->fold_g[i], 0, cnt * sizeof(float)));
+            }
+        }
+    }
     if (dev_alloc(&n->v_cur, hw * n->DV) || dev_alloc(&n->q1, hw * 64) || dev_alloc(&n->q_cur, hw * 64)) return -1;
     if (dev_alloc(&n->k1, lk * 64) || dev_alloc(&n->vp, (size_t)attn_vp_rows((int)lk) * n->DV) || dev_alloc(&n->chain_a, lk * n->DV) || dev_alloc(&n->chain_b, lk * n->DV)) return -1;
     TD_HIP(hipMemset(n->vp, 0, (size_t)attn_vp_rows((int)lk) * n->DV * sizeof(float)));   // padding rows of V' stay zero (td_attn.h load_v)
