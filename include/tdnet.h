@@ -18,7 +18,7 @@
  *     tdnet_warmup(h, stream) does that check explicitly; a frame call on a stream tdnet_warmup has not seen does it lazily
  *     (skipped while the stream is being captured into a hipGraph).  Every caller stream is checked ONCE per handle (the handle remembers
  *     the streams it has seen; alternating between two streams does not repeat the check), for at most 8 distinct streams.  tdnet_finalize_weights, tdnet_create_shared, tdnet_get_stage
- *     and tdnet_score_read synchronise, the configuration calls tdnet_set_input_u8 / tdnet_set_output_rgb / tdnet_set_score may; tdnet_score_reset
+ *     and tdnet_score_read synchronise, the configuration calls tdnet_set_input_u8 / tdnet_set_input_nv12 / tdnet_set_output_rgb / tdnet_set_score may; tdnet_score_reset
  *     and tdnet_score_export only enqueue (as do the test library's tdnet_op_* / tdnet_bench_* entries, include/tdnet_test.h).
  *   - tensors are fp32 unless an entry says otherwise: image in / logits out are NCHW like the reference, labels int32 [H,W]; internal
  *     layout is NHWC.  The *_u8 entries are the byte ends of the same frame: the image as uint8 HWC RGB at its SOURCE size (resized and
@@ -200,6 +200,40 @@ int  tdnet_forward_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, float*
 int  tdnet_forward_u8_labels(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* [H,W] */, void* stream);
 /* tdnet_argmax with uint8 labels [H,W] (the same labels, one byte each).                                            */
 int  tdnet_argmax_u8(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev, void* stream);
+/* ---- NV12 frames in -------------------------------------------------------------------------------------------------
+ * What a video decoder hands over, taken by the frame's first kernel as it is: the colour conversion joins the resize and the normalisation
+ * in that ONE launch (no RGB intermediate, no extra launch), BIT-IDENTICALLY to converting on the host and calling the uint8 entries.
+ * Surface: one device allocation.  Y plane at `base`: row y starts at base + y * pitch and holds src_width bytes.  UV plane at
+ * base + uv_offset: chroma row j starts at base + uv_offset + j * pitch and holds U, V byte pairs -- ceil(src_height / 2) rows of
+ * ceil(src_width / 2) pairs.  Odd sizes are legal, `base` may be any byte address.  Nothing outside
+ * [base, base + uv_offset + (ceil(src_height / 2) - 1) * pitch + 2 * ceil(src_width / 2)) is read, and the result does not depend on the bytes
+ * of the pitch padding or of the gap between the planes.
+ * Per source pixel (y, x): Y = Yplane[y][x], (U, V) = UVplane[y >> 1][x >> 1] (chroma replicated, as OpenCV's COLOR_YUV2RGB_NV12), then in int32
+ *     yy = max(0, Y - yoff) * CY;  u = U - 128;  v = V - 128
+ *     R = clamp8((yy + (1 << 19) + CVR * v) >> 20)
+ *     G = clamp8((yy + (1 << 19) + CVG * v + CUG * u) >> 20)
+ *     B = clamp8((yy + (1 << 19) + CUB * u) >> 20)
+ * with an arithmetic >>, clamp8 to 0..255 and the constants rint(c * 2^20) of the decimal coefficients, computed once on the host
+ * (|sum| <= 6.0e8 < 2^31):
+ *     standard                  decimals (CY, CUB, CUG, CVG, CVR)              yoff  CY       CUB      CUG      CVG      CVR
+ *     0 TDNET_YUV_BT601_LIMITED 1.164, 2.018, -0.391, -0.813, 1.596            16    1220542  2116026  -409993  -852492  1673527   (OpenCV's integers)
+ *     1 TDNET_YUV_BT709_LIMITED 1.164, 2.112, -0.213, -0.533, 1.793            16    1220542  2214593  -223347  -558891  1880097
+ *     2 TDNET_YUV_BT601_FULL    1, 1.772, -0.344136, -0.714136, 1.402          0     1048576  1858077  -360853  -748826  1470104
+ *     3 TDNET_YUV_BT709_FULL    1, 1.8556, -0.187324, -0.468124, 1.5748        0     1048576  1945738  -196423  -490864  1651297
+ * The frame is then exactly what tdnet_set_input_u8 defines on those RGB bytes: each of the four taps of the resize is converted and clamped
+ * FIRST, then interpolated (never YUV interpolated and converted afterwards), then normalised.
+ * tdnet_set_input_nv12: configuration (not a frame call: it may synchronise; idempotent for equal arguments; per handle).  A handle has ONE
+ * byte-input configuration at a time: after this call the byte entries (the tdnet_forward_u8* entries and tdnet_encode_u8) read their image
+ * pointer as the surface's `base`; a later tdnet_set_input_u8 switches back to packed RGB.  Fails -- leaving the previous configuration in
+ * force and the FIFO alone -- on a handle that is not finalized, sizes below 1, pitch < 2 * ceil(src_width / 2),
+ * uv_offset < src_height * pitch, an extent of 2^31 bytes or more, a standard outside 0..3, a zero or non-finite std, a non-finite mean, and a
+ * column downscale beyond what the kernel stages.                                                                      */
+#define TDNET_YUV_BT601_LIMITED 0
+#define TDNET_YUV_BT709_LIMITED 1
+#define TDNET_YUV_BT601_FULL 2
+#define TDNET_YUV_BT709_FULL 3
+int  tdnet_set_input_nv12(tdnet_t* h, int src_height, int src_width, int pitch, size_t uv_offset, int standard,
+                          const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
 /* ---- colour map out ------------------------------------------------------------------------------------------------
  * What the reference's loop does on the host behind the labels (Testing/test.py:61-71): the label map resized with nearest sampling and
  * decode_segmap -- done by the frame's LAST kernel instead.  It evaluates the x8 upsample only at the sampled pixels, takes the first-maximum

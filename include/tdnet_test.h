@@ -127,6 +127,9 @@ int tdnet_op_upsample(const float* in_dev, int C, int h, int w, int H, int W, fl
  * out_dev.  Returns its float count (out_dev == NULL: nothing else happens), <0 on error.                              */
 long tdnet_op_stem_image(const float* img_f32_dev, const uint8_t* src_u8_dev, int Hs, int Ws, int H, int W, const double* mean, const double* std,
                          int rows, float* out_dev, size_t capacity, void* stream);
+/* tdnet_op_stem_image from an NV12 surface at any byte address (include/tdnet.h "NV12 frames in"; the arguments of tdnet_set_input_nv12).   */
+long tdnet_op_stem_image_nv12(const uint8_t* surf_dev, int Hs, int Ws, int pitch, size_t uv_offset, int standard, int H, int W, const double* mean,
+                              const double* std, int rows, float* out_dev, size_t capacity, void* stream);
 /* low-resolution logits [C,h,w] -> labels [H,W] (bilinear align_corners=True, first maximum): int32 through the kernel of tdnet_forward_labels
  * (labels_i32_dev != NULL) and / or uint8 (labels_u8_dev != NULL) through the kernel of its uint8 form.  C in 1..256. */
 int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, int W, int32_t* labels_i32_dev, uint8_t* labels_u8_dev, void* stream);

@@ -220,10 +220,15 @@ struct PathLayers {
     int pid = 0;
 };
 struct CacheSlot { float* q = nullptr; float* k = nullptr; float* v = nullptr; };
-// The uint8 image input of a handle (tdnet_set_input_u8): source size, normalisation and the device tables k_ingest_u8 reads.  Per handle:
-// tdnet_create_shared handles configure their own.
+// The uint8 image input of a handle (tdnet_set_input_u8 / tdnet_set_input_nv12: ONE configuration at a time): source size, normalisation and
+// the device tables k_ingest_u8 / k_ingest_nv12 read.  Per handle: tdnet_create_shared handles configure their own.
+struct Nv12Layout { int pitch; size_t uv_offset; int standard; };      // tdnet_set_input_nv12's surface arguments
 struct U8Input {
     bool set = false;
+    bool nv12 = false;                                                 // false: packed RGB [Hs][Ws][3]; true: an NV12 surface
+    int pitch = 0, standard = 0, span_c = 0;                           // NV12: row pitch, TDNET_YUV_*, LDS bytes per staged chroma span
+    size_t uv_offset = 0, extent = 0;                                  // NV12: the UV plane's offset; the bytes [base, base + extent) the kernel may read
+    int coef[6] = {0, 0, 0, 0, 0, 0};                                  // NV12: yoff, CY, CUB, CUG, CVG, CVR (nv12_coeffs)
     int Hs = 0, Ws = 0, H = 0, W = 0, Wt = 0;                          // Wt: W rounded up to a multiple of 4 (the x tables' row length)
     double mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
     bool resize = false;                                               // false: source size == network size, lookup only
@@ -340,7 +345,7 @@ struct tdnet {
     bool prof = false;
     std::vector<ProfRec> recs;
     size_t nrec = 0;
-    U8Input u8;                                                        // tdnet_set_input_u8
+    U8Input u8;                                                        // tdnet_set_input_u8 / tdnet_set_input_nv12
     RgbOutput rgb;                                                     // tdnet_set_output_rgb
     ScoreOutput score;                                                 // tdnet_set_score
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
@@ -401,20 +406,42 @@ static void u8_free(U8Input& u) {
     u = U8Input();
 }
 constexpr int TD_INGEST_LDS_MAX = 64 * 1024;
+// include/tdnet.h "NV12 frames in": yoff and rint(c 2^20) of the decimal coefficients (CY, CUB, CUG, CVG, CVR) of TDNET_YUV_* 0..3.  Row 0
+// reproduces OpenCV's published integers (1220542, 2116026, -409993, -852492, 1673527).
+static void nv12_coeffs(int standard, int coef[6]) {
+    static const double dec[4][5] = {{1.164, 2.018, -0.391, -0.813, 1.596}, {1.164, 2.112, -0.213, -0.533, 1.793},
+                                     {1.0, 1.772, -0.344136, -0.714136, 1.402}, {1.0, 1.8556, -0.187324, -0.468124, 1.5748}};
+    coef[0] = standard < 2 ? 16 : 0;
+    for (int i = 0; i < 5; ++i) coef[1 + i] = (int)nearbyint(dec[standard][i] * 1048576.0);
+}
 // Validate, build the tables on the host and upload them into memory `u` owns.  NULL mean / std: the loader's (dataloader.py:52-53).
-static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who) {
+// nv: the source is an NV12 surface of that layout (k_ingest_nv12) instead of packed RGB; the tables are the same.  On failure `u` is left as it was.
+static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who, const Nv12Layout* nv = nullptr) {
     static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};
     if (!mean) mean = mean0;
     if (!std_) std_ = std0;
     if (Hs < 1 || Ws < 1) return td_fail("%s: source size %d x %d must be at least 1 x 1", who, Hs, Ws);
     if (H < 1 || W < 1 || H > 65535) return td_fail("%s: network size %d x %d out of range", who, H, W);
-    if ((double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
+    if (!nv && (double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
+    double extent = 0.0;
+    if (nv) {
+        const int cw = (Ws - 1) / 2 + 1, chh = (Hs - 1) / 2 + 1;       // chroma pairs per row, chroma rows
+        if (nv->pitch < 2 * cw) return td_fail("%s: pitch %d is below the %d bytes a row of %d columns holds", who, nv->pitch, 2 * cw, Ws);
+        if ((double)nv->uv_offset < (double)Hs * nv->pitch) return td_fail("%s: uv_offset %zu is inside the Y plane (%d rows of pitch %d)", who, nv->uv_offset, Hs, nv->pitch);
+        extent = (double)nv->uv_offset + (double)(chh - 1) * nv->pitch + 2.0 * cw;
+        if (extent >= 2147483648.0) return td_fail("%s: the surface's extent (uv_offset %zu, pitch %d, %d rows) is 2^31 bytes or more", who, nv->uv_offset, nv->pitch, Hs);
+        if (nv->standard < 0 || nv->standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, nv->standard);
+    }
     for (int c = 0; c < 3; ++c) {
         if (!std::isfinite(mean[c])) return td_fail("%s: mean[%d] is not finite", who, c);
         if (!std::isfinite(std_[c]) || std_[c] == 0.0) return td_fail("%s: std[%d] must be finite and non-zero", who, c);
     }
     U8Input v;
     v.Hs = Hs; v.Ws = Ws; v.H = H; v.W = W; v.Wt = (W + 3) / 4 * 4;
+    if (nv) {
+        v.nv12 = true; v.pitch = nv->pitch; v.uv_offset = nv->uv_offset; v.standard = nv->standard; v.extent = (size_t)extent;
+        nv12_coeffs(nv->standard, v.coef);
+    }
     for (int c = 0; c < 3; ++c) { v.mean[c] = mean[c]; v.std[c] = std_[c]; }
     v.resize = !(Hs == H && Ws == W);
     std::vector<float> lut(768);
@@ -433,18 +460,21 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
         yt.resize((size_t)4 * H);
         for (int y = 0; y < H; ++y) { yt[4 * y] = y0[y]; yt[4 * y + 1] = y1[y]; yt[4 * y + 2] = b0[y]; yt[4 * y + 3] = b1[y]; }
     }
-    // the workgroup size: the largest whose two staged spans (+ up to 15 bytes in front of the first, rounded to 16) fit beside the table
+    // the workgroup size: the largest whose two staged spans (+ up to 15 bytes in front of the first, rounded to 16) fit beside the table;
+    // NV12: two Y spans of a byte per column and two chroma spans of a byte pair per two columns
     bool fits = false;
     for (int threads = 256; threads >= 64 && !fits; threads >>= 1) {
-        long span = 0;
+        long span = 0, span_c = 0;
         for (int xs = 0; xs < W; xs += 4 * threads) {
             const int xe = std::min(xs + 4 * threads, W);
-            const long cols = v.resize ? (long)x1[xe - 1] - x0[xs] + 1 : xe - xs;
-            span = std::max(span, (cols * 3 + 15 + 15) / 16 * 16);
+            const int cl = v.resize ? x0[xs] : xs, ch = v.resize ? x1[xe - 1] : xe - 1;
+            const long cols = (long)ch - cl + 1;
+            span = std::max(span, (cols * (nv ? 1 : 3) + 15 + 15) / 16 * 16);
+            if (nv) span_c = std::max(span_c, (((long)(ch >> 1) - (cl >> 1) + 1) * 2 + 15 + 15) / 16 * 16);
         }
-        if (TD_INGEST_LUT_BYTES + 2 * span <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; }
+        if (TD_INGEST_LUT_BYTES + 2 * span + 2 * span_c <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; v.span_c = (int)span_c; }
     }
-    if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about 20x)", who, Ws, W);
+    if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about %s)", who, Ws, W, nv ? "60x" : "20x");
     if (upload(&v.lut, lut)) return -1;
     if (v.resize) {
         if (dev_alloc(&v.xt, xt.size()) || dev_alloc(&v.yt, yt.size())) { u8_free(v); return -1; }

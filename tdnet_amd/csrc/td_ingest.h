@@ -35,8 +35,8 @@ struct IngestArgs {
 };
 constexpr int TD_INGEST_LUT_BYTES = 3 * 256 * 4;
 
-TD_DEV void ingest_stage_row(const IngestArgs& a, unsigned char* dst, size_t first, size_t nbytes) {   // bytes [first, first + nbytes) of the image -> dst + (first & 15)
-    const size_t lo = (size_t)a.src, hi = lo + (size_t)a.Hs * a.Ws * 3;
+// bytes [first, first + nbytes) behind address lo -> dst + ((lo + first) & 15); [lo, hi) is the extent nothing outside of which is read
+TD_DEV void ingest_stage_row(size_t lo, size_t hi, unsigned char* dst, size_t first, size_t nbytes) {
     const size_t g0 = lo + first, al = g0 & ~(size_t)15;
     const int nchunks = (int)((g0 + nbytes - al + 15) >> 4);
     for (int k = threadIdx.x; k < nchunks; k += blockDim.x) {
@@ -69,8 +69,9 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
     }
     const size_t nbytes = (size_t)(ch - cl + 1) * 3;
     const size_t f0 = ((size_t)y0 * a.Ws + cl) * 3, f1 = ((size_t)y1 * a.Ws + cl) * 3;
-    ingest_stage_row(a, row0, f0, nbytes);
-    if (a.resize) ingest_stage_row(a, row1, f1, nbytes);
+    const size_t lo = (size_t)a.src, hi = lo + (size_t)a.Hs * a.Ws * 3;
+    ingest_stage_row(lo, hi, row0, f0, nbytes);
+    if (a.resize) ingest_stage_row(lo, hi, row1, f1, nbytes);
     __syncthreads();
     const int x = xs + (int)threadIdx.x * 4;
     if (x >= a.W) return;
@@ -95,6 +96,123 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int c = 0; c < 3; ++c) f[3 * e + c] = x + e < a.W ? lut[c * 256 + row0[o0 + 3 * (x + e) + c]] : 0.f;
+    }
+    if (a.Wp) {
+        float* o = a.out + ((size_t)(y + 3) * a.Wp + x + 4) * 3;                   // 16-byte aligned: Wp % 4 == 0, x % 4 == 0
+        if (x + 4 <= a.W) {
+            const f32x4 v0 = {f[0], f[1], f[2], f[3]}, v1 = {f[4], f[5], f[6], f[7]}, v2 = {f[8], f[9], f[10], f[11]};
+            td_st4(o, v0); td_st4(o + 4, v1); td_st4(o + 8, v2);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (x + e < a.W) { o[3 * e] = f[3 * e]; o[3 * e + 1] = f[3 * e + 1]; o[3 * e + 2] = f[3 * e + 2]; }
+        }
+    } else {
+        float* o = a.out + ((size_t)y * a.W + x) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (x + e < a.W) { const f32x4 v = {f[3 * e], f[3 * e + 1], f[3 * e + 2], 0.f}; td_st4(o + 4 * e, v); }
+    }
+}
+
+// ---- NV12 surface -> the stem's image buffer ---------------------------------------------------------------------------------------
+// What a video decoder hands over (include/tdnet.h "NV12 frames in"): a Y plane [Hs] rows of Ws bytes at src, an interleaved U, V plane of
+// ceil(Hs / 2) rows of ceil(Ws / 2) byte pairs at src + uv_offset, both with the row pitch `pitch`.  Per source pixel (y, x), all int32:
+//   Y = Yplane[y][x], (U, V) = UVplane[y >> 1][x >> 1] (chroma replicated);  yy = max(0, Y - yoff) CY, u = U - 128, v = V - 128
+//   R = clamp8((yy + 2^19 + CVR v) >> 20), G = clamp8((yy + 2^19 + CVG v + CUG u) >> 20), B = clamp8((yy + 2^19 + CUB u) >> 20)
+// (|sum| <= 6.0e8 < 2^31 for the four coefficient rows of td_handle.h nv12_coeffs), and the frame is what k_ingest_u8 makes of THOSE bytes:
+// each of the four taps is converted and clamped first, then resize_linear_u8's fixed point interpolates, then the table normalises.
+// The same grid, strip, tables and stores as k_ingest_u8.  A workgroup stages the spans of Y rows y0 and y1 (columns cl .. ch) and of chroma
+// rows y0 >> 1 and y1 >> 1 (byte pairs cl >> 1 .. ch >> 1, i.e. from column cl & ~1; once when the two rows coincide -- wave-uniform) with
+// ingest_stage_row: nothing outside [src, src + extent) is read, extent = uv_offset + (ceil(Hs / 2) - 1) pitch + 2 ceil(Ws / 2); bytes of the
+// pitch padding or of the gap between the planes may land in LDS but no tap indexes them.  The taps are converted in registers (3
+// multiply-adds, a shift and a clamp per channel): no second pass over LDS, no second barrier.
+struct IngestNv12Args {
+    const unsigned char* src;      // the surface's base, any byte alignment
+    float* out;
+    const float* lut;              // [3][256]
+    const int* xt;                 // as IngestArgs
+    const int* yt;
+    int Hs, Ws, H, W, Wt;
+    int Wp;                        // as IngestArgs
+    int resize;
+    int span, span_c;              // LDS bytes per staged Y span / chroma span (multiples of 16; td_handle.h u8_build)
+    int pitch;
+    unsigned uv_offset, extent;    // < 2^31
+    int yoff, cy, cub, cug, cvg, cvr;
+};
+TD_DEV int ingest_clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+TD_DEV void ingest_nv12_rgb(const IngestNv12Args& a, int Y, int U, int V, int* p) {
+    int yy = Y - a.yoff;
+    yy = (yy < 0 ? 0 : yy) * a.cy + (1 << 19);
+    const int u = U - 128, v = V - 128;
+    p[0] = ingest_clamp8((yy + a.cvr * v) >> 20);
+    p[1] = ingest_clamp8((yy + a.cvg * v + a.cug * u) >> 20);
+    p[2] = ingest_clamp8((yy + a.cub * u) >> 20);
+}
+
+TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
+    TD_DYN_LDS(smem);
+    float* lut = reinterpret_cast<float*>(smem);                                   // [3][256]
+    unsigned char* yr0 = reinterpret_cast<unsigned char*>(smem) + TD_INGEST_LUT_BYTES;   // the staged span of Y row y0 ...
+    unsigned char* yr1 = yr0 + a.span;                                             // ... of y1 (resize only) ...
+    unsigned char* uv0 = yr1 + a.span;                                             // ... of chroma row y0 >> 1 ...
+    unsigned char* uv1 = uv0 + a.span_c;                                           // ... and of y1 >> 1 where that is another row
+    const int y = blockIdx.y, xs = blockIdx.x * blockDim.x * 4;
+    const int xe = xs + (int)blockDim.x * 4 < a.W ? xs + (int)blockDim.x * 4 : a.W;   // the strip: output columns [xs, xe)
+    for (int i = threadIdx.x; i < 768; i += blockDim.x) lut[i] = a.lut[i];
+    int y0 = y, y1 = y, b0 = 0, b1 = 0, cl = xs, ch = xe - 1;                      // source columns [cl, ch]
+    if (a.resize) {
+        const td_i32x4 t = *reinterpret_cast<const td_i32x4*>(a.yt + 4 * y);
+        y0 = t[0]; y1 = t[1]; b0 = t[2]; b1 = t[3];
+        cl = a.xt[xs]; ch = a.xt[a.Wt + xe - 1];
+    }
+    const int cc = cl & ~1;                                                        // the chroma span's first byte within its row
+    const size_t ny = (size_t)(ch - cl + 1), nc = (size_t)((ch >> 1) - (cl >> 1) + 1) * 2;
+    const size_t f0 = (size_t)y0 * a.pitch + cl, f1 = (size_t)y1 * a.pitch + cl;
+    const size_t c0 = (size_t)a.uv_offset + (size_t)(y0 >> 1) * a.pitch + cc, c1 = (size_t)a.uv_offset + (size_t)(y1 >> 1) * a.pitch + cc;
+    const bool two = (y0 >> 1) != (y1 >> 1);                                       // false without resize: y0 == y1
+    const size_t lo = (size_t)a.src, hi = lo + a.extent;
+    ingest_stage_row(lo, hi, yr0, f0, ny);
+    if (a.resize) ingest_stage_row(lo, hi, yr1, f1, ny);
+    ingest_stage_row(lo, hi, uv0, c0, nc);
+    if (two) ingest_stage_row(lo, hi, uv1, c1, nc);
+    __syncthreads();
+    const int x = xs + (int)threadIdx.x * 4;
+    if (x >= a.W) return;
+    const int o0 = (int)((lo + f0) & 15) - cl, o1 = (int)((lo + f1) & 15) - cl;    // yr0[o0 + column]: the Y byte of source row y0
+    const int q0 = (int)((lo + c0) & 15) - cc;                                     // uv0[q0 + (column & ~1)]: its U, the next byte its V
+    const unsigned char* uvb = two ? uv1 : uv0;                                    // the chroma row of source row y1
+    const int q1 = two ? (int)((lo + c1) & 15) - cc : q0;
+    float f[12];
+    if (a.resize) {
+        const td_i32x4 s0 = *reinterpret_cast<const td_i32x4*>(a.xt + x), s1 = *reinterpret_cast<const td_i32x4*>(a.xt + a.Wt + x);
+        const td_i32x4 a0 = *reinterpret_cast<const td_i32x4*>(a.xt + 2 * a.Wt + x), a1 = *reinterpret_cast<const td_i32x4*>(a.xt + 3 * a.Wt + x);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ca = s0[e] & ~1, cb = s1[e] & ~1;
+            int p00[3], p01[3], p10[3], p11[3];                                    // the four taps, converted and clamped
+            ingest_nv12_rgb(a, yr0[o0 + s0[e]], uv0[q0 + ca], uv0[q0 + ca + 1], p00);
+            ingest_nv12_rgb(a, yr0[o0 + s1[e]], uv0[q0 + cb], uv0[q0 + cb + 1], p01);
+            ingest_nv12_rgb(a, yr1[o1 + s0[e]], uvb[q1 + ca], uvb[q1 + ca + 1], p10);
+            ingest_nv12_rgb(a, yr1[o1 + s1[e]], uvb[q1 + cb], uvb[q1 + cb + 1], p11);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int r0 = p00[c] * a0[e] + p01[c] * a1[e];
+                const int r1 = p10[c] * a0[e] + p11[c] * a1[e];
+                const int v = ingest_clamp8((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+                f[3 * e + c] = lut[c * 256 + v];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int p[3] = {0, 0, 0};
+            const bool in = x + e < a.W;
+            if (in) { const int cx = (x + e) & ~1; ingest_nv12_rgb(a, yr0[o0 + x + e], uv0[q0 + cx], uv0[q0 + cx + 1], p); }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[3 * e + c] = in ? lut[c * 256 + p[c]] : 0.f;
+        }
     }
     if (a.Wp) {
         float* o = a.out + ((size_t)(y + 3) * a.Wp + x + 4) * 3;                   // 16-byte aligned: Wp % 4 == 0, x % 4 == 0

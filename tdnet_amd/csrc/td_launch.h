@@ -334,8 +334,8 @@ static void run_ppm(tdnet* n, const float* c4, int h, int w, int C, int XS, int 
 }
 
 // The image of a frame as the caller handed it over: fp32 NCHW [3][H][W] at the network size, or uint8 HWC [Hs][Ws][3] at the source size the
-// handle was configured for (tdnet_set_input_u8; `u8` = that configuration).  Everything behind the stem's image buffer is the same frame.
-enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };
+// handle was configured for (tdnet_set_input_u8; `u8` = that configuration), or the NV12 surface tdnet_set_input_nv12 described.  Everything behind the stem's image buffer is the same frame.
+enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };                               // TD_IMG_U8: the handle's byte input, packed RGB or (U8Input::nv12) an NV12 surface
 struct FrameInput { const void* p; int kind; const U8Input* u8; };
 static inline FrameInput frame_input_f32(const float* img) { return FrameInput{img, TD_IMG_F32, nullptr}; }
 // rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
@@ -344,6 +344,13 @@ static void run_stem_pre(tdnet* n, const FrameInput& in, int H, int W, float* im
     switch (in.kind) {
     case TD_IMG_U8: {                                                  // resize + normalise + layout in the same one launch (td_ingest.h)
         const U8Input& u = *in.u8;
+        if (u.nv12) {                                                  // colour conversion too, in the same one launch
+            const IngestNv12Args a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
+                                      u.span, u.span_c, u.pitch, (unsigned)u.uv_offset, (unsigned)u.extent,
+                                      u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5]};
+            TD_LAUNCH(k_ingest_nv12, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span + 2 * u.span_c, s, a);
+            break;
+        }
         const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0, u.span};
         TD_LAUNCH(k_ingest_u8, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span, s, a);
         break;

@@ -282,11 +282,30 @@ extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, con
     const double* m = mean ? mean : mean0;
     const double* sd = std_ ? std_ : std0;
     const U8Input& u = n->u8;
-    if (u.set && u.Hs == src_height && u.Ws == src_width && memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
+    if (u.set && !u.nv12 && u.Hs == src_height && u.Ws == src_width && memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
     if (u.set) TD_HIP(hipDeviceSynchronize());                        // a frame in flight may still read the tables that are about to go
     const size_t before = n->u8.bytes;
     TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_u8"));
     n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
+    return 0;
+}
+// The other form of the handle's ONE byte-input configuration: the byte entries' image pointer is then the base of an NV12 surface of this
+// layout (td_ingest.h k_ingest_nv12), until a tdnet_set_input_u8 switches back.  A failed call leaves the previous configuration in force.
+extern "C" int tdnet_set_input_nv12(tdnet_t* n, int src_height, int src_width, int pitch, size_t uv_offset, int standard, const double* mean, const double* std_) {
+    if (!n) return td_fail("tdnet_set_input_nv12: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_nv12: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};   // dataloader.py:52-53
+    const double* m = mean ? mean : mean0;
+    const double* sd = std_ ? std_ : std0;
+    const U8Input& u = n->u8;
+    if (u.set && u.nv12 && u.Hs == src_height && u.Ws == src_width && u.pitch == pitch && u.uv_offset == uv_offset && u.standard == standard &&
+        memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
+    if (u.set) TD_HIP(hipDeviceSynchronize());                        // a frame in flight may still read the tables that are about to go
+    const size_t before = n->u8.bytes;
+    const Nv12Layout nv = {pitch, uv_offset, standard};
+    TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_nv12", &nv));
+    n->ws_bytes += n->u8.bytes - before;
     return 0;
 }
 // ---- colour map out ----------------------------------------------------------------------------------------------------------------

@@ -493,6 +493,31 @@ extern "C" long tdnet_op_stem_image(const float* img_f32, const uint8_t* src_u8,
     u8_free(u);
     return rc;
 }
+// tdnet_op_stem_image from an NV12 surface: k_ingest_nv12 with the configuration tdnet_set_input_nv12 would build
+extern "C" long tdnet_op_stem_image_nv12(const uint8_t* surf, int Hs, int Ws, int pitch, size_t uv_offset, int standard, int H, int W, const double* mean,
+                                         const double* std_, int rows, float* out, size_t capacity, void* stream) {
+    if (H < 1 || W < 1) return td_fail("tdnet_op_stem_image_nv12: empty image");
+    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
+    if (!out) return (long)img_floats;
+    if (!surf) return td_fail("tdnet_op_stem_image_nv12: surf is NULL");
+    if (capacity < img_floats) return td_fail("tdnet_op_stem_image_nv12: capacity %zu < %zu", capacity, img_floats);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    const Nv12Layout nv = {pitch, uv_offset, standard};
+    if (u8_build(u, Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image_nv12", &nv)) return -1;
+    float* img4 = nullptr;
+    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
+    long rc = (long)img_floats;
+    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: memset failed");
+    if (rc >= 0) {
+        run_stem_pre(nullptr, FrameInput{surf, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
+        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: copy failed");
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: device error");
+    hipFree(img4);
+    u8_free(u);
+    return rc;
+}
 // low-resolution logits [C][h][w] -> labels [H][W]: int32 through k_upsample_argmax (labels_i32 != NULL) and / or uint8 through
 // k_upsample_argmax_u8 (labels_u8 != NULL)
 extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, int H, int W, int32_t* labels_i32, uint8_t* labels_u8, void* stream) {

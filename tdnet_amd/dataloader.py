@@ -54,6 +54,69 @@ def resize_linear_u8(img, size):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+# ---- NV12 surfaces (include/tdnet.h "NV12 frames in") ----------------------------------------------------------------------------
+# standard -> (yoff, decimal coefficients CY, CUB, CUG, CVG, CVR): BT.601 limited (OpenCV's COLOR_YUV2RGB_NV12), BT.709 limited, BT.601 full, BT.709 full
+NV12_STANDARDS = {0: (16, (1.164, 2.018, -0.391, -0.813, 1.596)), 1: (16, (1.164, 2.112, -0.213, -0.533, 1.793)),
+                  2: (0, (1.0, 1.772, -0.344136, -0.714136, 1.402)), 3: (0, (1.0, 1.8556, -0.187324, -0.468124, 1.5748))}
+
+
+def nv12_coeffs(standard):
+    """(yoff, CY, CUB, CUG, CVG, CVR): the 20-bit fixed-point constants rint(c * 2^20) of the conversion."""
+    yoff, dec = NV12_STANDARDS[int(standard)]
+    return (yoff,) + tuple(int(np.rint(c * 1048576.0)) for c in dec)
+
+
+def nv12_extent(Hs, Ws, pitch, uv_offset):
+    """Bytes of a surface from its base to the end of its last chroma pair: nothing behind them is ever read."""
+    return int(uv_offset) + ((int(Hs) + 1) // 2 - 1) * int(pitch) + 2 * ((int(Ws) + 1) // 2)
+
+
+def nv12_to_rgb_u8(surface, Hs, Ws, pitch, uv_offset, standard=0):
+    """The oracle of the library's NV12 input: the bytes of a surface (Y plane at 0, row pitch `pitch`; interleaved U, V plane at uv_offset,
+    the same pitch, ceil(Hs / 2) rows of ceil(Ws / 2) pairs) -> uint8 RGB [Hs, Ws, 3].  Chroma is replicated (pixel (y, x) takes pair
+    (y >> 1, x >> 1)); per pixel, in integers that fit int32 (asserted):
+        yy = max(0, Y - yoff) * CY;  u = U - 128;  v = V - 128
+        R = clamp8((yy + 2^19 + CVR v) >> 20);  G = clamp8((yy + 2^19 + CVG v + CUG u) >> 20);  B = clamp8((yy + 2^19 + CUB u) >> 20)
+    This restates what cv2.cvtColor(COLOR_YUV2RGB_NV12) computes for standard 0; cv2 is absent here, so tests/test_nv12_host.py pins it by
+    hand-derived answers."""
+    s = np.asarray(surface).reshape(-1)
+    Hs, Ws, pitch, uv_offset = int(Hs), int(Ws), int(pitch), int(uv_offset)
+    assert s.dtype == np.uint8 and Hs >= 1 and Ws >= 1 and pitch >= 2 * ((Ws + 1) // 2) and uv_offset >= Hs * pitch
+    assert s.size >= nv12_extent(Hs, Ws, pitch, uv_offset)
+    yoff, CY, CUB, CUG, CVG, CVR = nv12_coeffs(standard)
+    ys, xs = np.arange(Hs)[:, None], np.arange(Ws)[None, :]
+    Y = s[ys * pitch + xs].astype(np.int64)
+    cidx = uv_offset + (ys >> 1) * pitch + (xs >> 1) * 2
+    u, v = s[cidx].astype(np.int64) - 128, s[cidx + 1].astype(np.int64) - 128
+    yy = np.maximum(0, Y - yoff) * CY + (1 << 19)
+    sums = np.stack([yy + CVR * v, yy + CVG * v + CUG * u, yy + CUB * u], axis=-1)
+    assert np.abs(sums).max() < 2 ** 31 and np.abs(CVG * v).max() < 2 ** 31
+    return np.clip(sums >> 20, 0, 255).astype(np.uint8)
+
+
+def rgb_to_nv12(img_u8, pitch=None, standard=0):
+    """A deterministic NV12 surface of an RGB image [Hs, Ws, 3], for tests and the command line: uint8 [Hs + ceil(Hs / 2), pitch] -- the Y
+    plane, then the UV plane at uv_offset = Hs * pitch.  The forward matrix (the inverse of the standard's decimal coefficients) in float64,
+    rounded to nearest; chroma is the mean over each 2 x 2 block (over the pixels that exist at an odd edge).  pitch: default the row's bytes
+    rounded up to 256, as decoders pad; the padding is zero.  Not an exact inverse of nv12_to_rgb_u8 -- it only has to be a function."""
+    img = np.asarray(img_u8)
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3
+    Hs, Ws = img.shape[:2]
+    hc, wc = (Hs + 1) // 2, (Ws + 1) // 2
+    pitch = (2 * wc + 255) // 256 * 256 if pitch is None else int(pitch)
+    assert pitch >= 2 * wc
+    yoff, (cy, cub, cug, cvg, cvr) = NV12_STANDARDS[int(standard)]
+    inv = np.linalg.inv(np.array([[cy, 0.0, cvr], [cy, cug, cvg], [cy, cub, 0.0]], dtype=np.float64))   # (Y - yoff, u, v) -> (R, G, B), inverted
+    yuv = img.astype(np.float64) @ inv.T
+    surf = np.zeros((Hs + hc, pitch), np.uint8)
+    surf[:Hs, :Ws] = np.clip(np.rint(yuv[..., 0] + yoff), 0, 255).astype(np.uint8)
+    pad = np.full((2 * hc, 2 * wc, 2), np.nan)
+    pad[:Hs, :Ws] = yuv[..., 1:]
+    chroma = np.nanmean(pad.reshape(hc, 2, wc, 2, 2), axis=(1, 3))
+    surf[Hs:, :2 * wc] = np.clip(np.rint(chroma + 128.0), 0, 255).astype(np.uint8).reshape(hc, 2 * wc)
+    return surf
+
+
 def nearest_index(n_src, n_dst):
     """Source index per destination index of the nearest-sample resize of the label map (test.py:64, cv2.INTER_NEAREST): int64 [n_dst] =
     min(int64(o * (n_src / n_dst)), n_src - 1) -- the quotient first, in float64, then the product, then truncation.  This is the project's rule:
@@ -67,8 +130,10 @@ class cityscapesLoader():
               [255, 0, 0], [0, 0, 142], [0, 0, 70], [0, 60, 100], [0, 80, 100], [0, 0, 230], [119, 11, 32]]
     label_colours = dict(zip(range(19), colors))
 
-    def __init__(self, img_path, in_size, pin_memory=False, as_uint8=False):
+    def __init__(self, img_path, in_size, pin_memory=False, as_uint8=False, as_nv12=False, nv12_standard=0):
         self.img_path = img_path
+        self.as_nv12 = bool(as_nv12)                     # not in the reference: frames become NV12 surfaces [1, Hs + ceil(Hs / 2), pitch] (rgb_to_nv12: what a video decoder hands over), items carry (Hs, Ws) as a fifth element (model.forward_nv12 / forward_labels_nv12 convert, resize and normalise on the device)
+        self.nv12_standard = int(nv12_standard)
         self.as_uint8 = bool(as_uint8)                   # not in the reference: frames stay the decoded bytes [1, Hs, Ws, 3] (model.forward_u8 / forward_labels_u8 resize and normalise on the device, bit-identically)
         self.pin_memory = bool(pin_memory)               # not in the reference: frames land in page-locked memory (DevicePrefetcher uploads them without a bounce copy)
         self.n_classes = 19
@@ -94,6 +159,10 @@ class cityscapesLoader():
             img_name = path.split('/')[-1]
             folder = path.split('/')[-2]
             im = np.asarray(Image.open(path).convert("RGB"))
+            if self.as_nv12:
+                t = torch.from_numpy(rgb_to_nv12(im, standard=self.nv12_standard)[np.newaxis])
+                self.data.append([t.pin_memory() if self.pin_memory else t, img_name, folder, self.size, (im.shape[0], im.shape[1])])
+                continue
             if self.as_uint8:                                          # no resize, no normalisation: a quarter of the fp32 frame's bytes (at equal size)
                 t = torch.from_numpy(np.ascontiguousarray(im)[np.newaxis])
                 self.data.append([t.pin_memory() if self.pin_memory else t, img_name, folder, self.size])
@@ -112,8 +181,9 @@ class cityscapesLoader():
 
 
 class DevicePrefetcher:
-    """Iterate `loader.data` items ([img [1,3,H,W] fp32 CPU -- or [1,Hs,Ws,3] uint8 from cityscapesLoader(as_uint8=True): the device buffers
-    take the items' dtype --, name, folder, size], dataloader.py:73) with the image ALREADY ON THE DEVICE:
+    """Iterate `loader.data` items ([img [1,3,H,W] fp32 CPU -- or [1,Hs,Ws,3] uint8 from cityscapesLoader(as_uint8=True), or an NV12 surface
+    [1,rows,pitch] uint8 from as_nv12=True: the device buffers take the items' dtype and shape, further elements travel as they are --, name,
+    folder, size], dataloader.py:73) with the image ALREADY ON THE DEVICE:
     the host->device copy of item i + 1 runs on a copy stream while the caller's stream computes item i.  Page-locked frames
     (cityscapesLoader(..., pin_memory=True)) upload asynchronously; a pageable frame is staged by the HIP runtime while the host waits (still
     under the device's previous frame; an own bounce copy into pinned memory was measured SLOWER than that: 106 against 149 frames/s).

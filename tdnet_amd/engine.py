@@ -104,7 +104,25 @@ class Engine:
         m = None if key[2] is None else (ctypes.c_double * 3)(*key[2])
         sd = None if key[3] is None else (ctypes.c_double * 3)(*key[3])
         self.lib.check(self.lib.tdnet_set_input_u8(self.h, key[0], key[1], m, sd))
-        self._u8_key = key
+        self._u8_key, self._nv12_key = key, None                       # ONE byte-input configuration per handle
+
+    def set_input_nv12(self, src_height, src_width, pitch, uv_offset=None, standard=0, mean=None, std=None):
+        """Frames will arrive as NV12 surfaces (include/tdnet.h "NV12 frames in"): the byte entries (forward_u8, ...) then read their image
+        pointer as the surface's base, until set_input_u8 switches back.  uv_offset None: src_height * pitch.  A configuration call (it may
+        synchronise); repeating it with equal arguments does nothing."""
+        key = (int(src_height), int(src_width), int(pitch), int(src_height) * int(pitch) if uv_offset is None else int(uv_offset), int(standard),
+               None if mean is None else tuple(float(v) for v in mean), None if std is None else tuple(float(v) for v in std))
+        if getattr(self, "_nv12_key", None) == key:
+            return
+        for v in key[5:]:
+            if v is not None and len(v) != 3:
+                raise _capi.TdnetError("set_input_nv12: mean and std are three numbers each")
+        if uv_offset is not None and key[3] < 0:
+            raise _capi.TdnetError("set_input_nv12: uv_offset must not be negative")
+        m = None if key[5] is None else (ctypes.c_double * 3)(*key[5])
+        sd = None if key[6] is None else (ctypes.c_double * 3)(*key[6])
+        self.lib.check(self.lib.tdnet_set_input_nv12(self.h, key[0], key[1], key[2], key[3], key[4], m, sd))
+        self._nv12_key, self._u8_key = key, None
 
     def forward_u8(self, img_ptr, pos_id, logits_ptr, stream=None):
         self.lib.check(self.lib.tdnet_forward_u8(self.h, _ptr(img_ptr), int(pos_id), _ptr(logits_ptr), stream))

@@ -304,11 +304,15 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("the network size is not known yet: pass in_size=(H, W), or call ensure_engine(H, W, device) first")
         return self._engine_key[0], self._engine_key[1]
 
-    def _u8_call(self, img, size, call, mean, std):
+    def _u8_call(self, img, size, call, mean, std, nv12=None):
+        """nv12: None, or (Hs, Ws, pitch, uv_offset, standard) -- img is then a batch of NV12 surfaces and the handles are configured for those."""
         Hs, Ws = int(img.shape[1]), int(img.shape[2])
 
         def one(i, eng, s):
-            eng.set_input_u8(Hs, Ws, mean, std)                        # (re)configured when the source size changes; a no-op otherwise
+            if nv12 is None:
+                eng.set_input_u8(Hs, Ws, mean, std)                    # (re)configured when the source size changes; a no-op otherwise
+            else:
+                eng.set_input_nv12(*nv12, mean=mean, std=std)
             call(i, eng, s)
         self._for_each_sample(img, one, size)
 
@@ -349,6 +353,109 @@ class _TDNetBase(nn.Module):
         for i in range(logits.shape[0]):
             self._engine.argmax_u8(logits[i].data_ptr(), out[i].data_ptr(), s)
         return out
+
+    # ---- NV12 frames in (not in the reference; include/tdnet.h "NV12 frames in") ---------------------------------------------------------
+    # surf: torch.uint8 CUDA tensor [N, rows, pitch] -- N decoder surfaces as they are: the Y plane's rows from byte 0, the interleaved UV
+    # plane's from uv_offset (None: Hs * pitch), both with the row pitch.  src_size = (Hs, Ws) is the picture's size.  The library converts
+    # (standard: 0 BT.601 limited, 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full), resizes and normalises in the frame's first launch,
+    # bit-identically to forward_u8(dataloader.nv12_to_rgb_u8(surface)).
+    def _check_frame_nv12(self, surf, pos_id, src_size, in_size, uv_offset, standard):
+        """-> ((H, W), (Hs, Ws, pitch, uv_offset, standard)).  The error classes of _check_frame_u8; nothing is built before it passes."""
+        if not torch.is_tensor(surf) or surf.dtype != torch.uint8:
+            raise RuntimeError("expected a torch.uint8 surface tensor [N,rows,pitch], got %s" % (surf.dtype if torch.is_tensor(surf) else type(surf).__name__))
+        if surf.dim() != 3 or surf.shape[0] < 1:
+            raise RuntimeError("expected a uint8 surface tensor [N,rows,pitch] (NV12: Y rows, then UV rows) with N >= 1, got shape %s" % (tuple(surf.shape),))
+        if src_size is None or len(src_size) != 2 or int(src_size[0]) < 1 or int(src_size[1]) < 1:
+            raise RuntimeError("src_size must be (Hs, Ws), at least (1, 1), got %r" % (src_size,))
+        Hs, Ws, pitch = int(src_size[0]), int(src_size[1]), int(surf.shape[2])
+        off = Hs * pitch if uv_offset is None else int(uv_offset)
+        if standard not in (0, 1, 2, 3):
+            raise RuntimeError("standard must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full), got %r" % (standard,))
+        if pitch < 2 * ((Ws + 1) // 2):
+            raise RuntimeError("the surface's pitch %d is below the %d bytes a row of %d columns holds" % (pitch, 2 * ((Ws + 1) // 2), Ws))
+        if off < Hs * pitch:
+            raise RuntimeError("uv_offset %d is inside the Y plane (%d rows of pitch %d)" % (off, Hs, pitch))
+        extent = off + ((Hs + 1) // 2 - 1) * pitch + 2 * ((Ws + 1) // 2)
+        if int(surf.shape[1]) * pitch < extent:
+            raise RuntimeError("a surface of %d rows x pitch %d holds %d bytes, a %d x %d picture with uv_offset %d needs %d"
+                               % (surf.shape[1], pitch, int(surf.shape[1]) * pitch, Hs, Ws, off, extent))
+        if surf.device.type != "cuda":
+            raise TdnetError("tdnet_amd runs on MI355X only: got a %s tensor (no CPU fallback)" % surf.device.type)
+        if pos_id not in range(self.path_num):
+            raise RuntimeError("pos_id must be t mod %d" % self.path_num)
+        if in_size is not None:
+            return (int(in_size[0]), int(in_size[1])), (Hs, Ws, pitch, off, int(standard))
+        if self._engine_key is None:
+            raise RuntimeError("the network size is not known yet: pass in_size=(H, W), or call ensure_engine(H, W, device) first")
+        return (self._engine_key[0], self._engine_key[1]), (Hs, Ws, pitch, off, int(standard))
+
+    def forward_nv12(self, surf, pos_id=0, src_size=None, in_size=None, uv_offset=None, standard=0, mean=None, std=None):
+        """forward() on decoder surfaces: logits [N, nclass, H, W] at the network size."""
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        out = torch.empty((img.shape[0], self.nclass, H, W), device=img.device, dtype=torch.float32)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, nv)
+        return out
+
+    def forward_labels_nv12(self, surf, pos_id=0, src_size=None, in_size=None, uv_offset=None, standard=0, mean=None, std=None):
+        """forward_labels() on decoder surfaces, labels as uint8 [N, H, W]."""
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, nv)
+        return out
+
+    def encode_nv12(self, surf, pos_id=0, src_size=None, in_size=None, uv_offset=None, standard=0, mean=None, std=None):
+        """encode() on a decoder surface."""
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        if surf.shape[0] != 1:
+            raise RuntimeError("encode_nv12(): the split frame serves ONE stream (batch size 1)")
+        img = surf.contiguous()
+        eng = self._engine_for(H, W, img.device.index or 0, 1)
+        eng.set_input_nv12(*nv, mean=mean, std=std)
+        self._pending_shape = (H, W, img.device)
+        eng.encode_u8(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
+
+    def forward_rgb_nv12(self, surf, pos_id, src_size, in_size, out_size, palette=None, uv_offset=None, standard=0, mean=None, std=None):
+        """forward_labels_nv12() with the colour map [N, oh, ow, 3] uint8 in place of the label map: a decoder surface in, a picture out."""
+        self._rgb_size(out_size)
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
+
+        def one(i, eng, s):
+            eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, nv)
+        return out
+
+    def forward_score_nv12(self, surf, gt_u8, pos_id=0, src_size=None, in_size=None, gt_map=None, return_labels=False, uv_offset=None, standard=0,
+                           mean=None, std=None):
+        """forward_labels_nv12() with the frame scored on the device (see forward_score_u8)."""
+        self._check_gt_type(gt_u8)
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        gt = self._check_gt(gt_u8, img.shape[0], H, W, img.device)
+        out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8) if return_labels else None
+
+        def one(i, eng, s):
+            eng.set_score(gt_map)
+            eng.forward_u8_score(img[i].data_ptr(), pos_id, gt[i].data_ptr(), None if out is None else out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, nv)
+        return out
+
+    def forward_labels_conf_nv12(self, surf, pos_id=0, src_size=None, in_size=None, uv_offset=None, standard=0, mean=None, std=None):
+        """forward_labels_nv12() with the confidence map: (labels uint8 [N, H, W], conf uint8 [N, H, W])."""
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        shape = (img.shape[0], H, W)
+        out, conf = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_confidence(*self._confidence)
+            eng.forward_u8_labels_conf(img[i].data_ptr(), pos_id, out[i].data_ptr(), conf[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, nv)
+        return out, conf
 
     # ---- colour map out (not in the reference's model; its loop makes the picture on the host, test.py:61-71) -------------------------
     # The frame's last kernel writes decode_segmap(labels[ys][:, xs]) directly: uint8 [N, oh, ow, 3], ys / xs = dataloader.nearest_index.

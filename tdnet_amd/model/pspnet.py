@@ -65,3 +65,18 @@ class pspnet(_TDNetBase):
 
     def forward_labels_conf_u8(self, x, pos_id=None, in_size=None, **kw):
         return super().forward_labels_conf_u8(x[-1:], 0, in_size, **kw)
+
+    def forward_nv12(self, x, pos_id=None, src_size=None, **kw):
+        return super().forward_nv12(x[-1:], 0, src_size, **kw)
+
+    def forward_labels_nv12(self, x, pos_id=None, src_size=None, **kw):
+        return super().forward_labels_nv12(x[-1:], 0, src_size, **kw)
+
+    def forward_rgb_nv12(self, x, pos_id=None, src_size=None, in_size=None, out_size=None, **kw):
+        return super().forward_rgb_nv12(x[-1:], 0, src_size, in_size, out_size, **kw)
+
+    def forward_score_nv12(self, x, gt_u8, pos_id=None, src_size=None, **kw):
+        return super().forward_score_nv12(x[-1:], gt_u8[-1:], 0, src_size, **kw)
+
+    def forward_labels_conf_nv12(self, x, pos_id=None, src_size=None, **kw):
+        return super().forward_labels_conf_nv12(x[-1:], 0, src_size, **kw)

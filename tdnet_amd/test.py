@@ -10,7 +10,9 @@ i > 5 averaged, argmax = output.max(1)[1], quarter-resolution colour PNG per fra
 `--synthetic_seed N` runs on seeded synthetic weights when no checkpoint is available; `--in_size HxW` (default 769x1537,
 test.py:24) must match the checkpoint's LayerNorm shape exactly as in the reference; `--u8` keeps the frames as the decoded bytes (the
 library resizes and normalises them on the device, bit-identically to the loader) and, with `--prefetch`, is the all-bytes loop: uint8
-upload, forward_labels_u8, uint8 label download; `--rgb` has the frame's last kernel write the quarter-size colour map itself (the nearest
+upload, forward_labels_u8, uint8 label download; `--nv12` turns every frame into an NV12 surface on the host (dataloader.rgb_to_nv12: what a
+video decoder would hand over; `--nv12_standard` 0..3) and feeds the surfaces: conversion, resize and normalisation in the frame's first
+launch, combinable with `--prefetch`, `--rgb`, `--gt_path` and `--conf` like `--u8`; `--rgb` has the frame's last kernel write the quarter-size colour map itself (the nearest
 sample of the label map and decode_segmap, byte for byte): the host downloads the picture and encodes the PNG, nothing else.
 `--gt_path DIR` scores the clip against ground truth on the device (single-channel PNGs named like the frames, sampled to `--in_size` with the
 nearest rule when their size differs; `--gt_map FILE`: 256 integers as text, ground-truth byte -> class id, anything >= 19 ignored; default
@@ -34,7 +36,8 @@ def load_ground_truth(gt_path, items, size, nearest_index, pin):
     from PIL import Image
     H, W = size
     out = []
-    for _, img_name, folder, _ in items:
+    for item in items:
+        img_name, folder = item[1], item[2]
         path = os.path.join(gt_path, folder, img_name)
         if not os.path.exists(path):
             path = os.path.join(gt_path, img_name)
@@ -57,8 +60,13 @@ def test(args):
     device = torch.device("cuda")
     H, W = (int(v) for v in args.in_size.lower().split("x"))
     u8 = bool(getattr(args, "u8", False))
+    nv12 = bool(getattr(args, "nv12", False))
+    nv12_std = int(getattr(args, "nv12_standard", 0) or 0)
+    if nv12 and u8:
+        raise SystemExit("--nv12 and --u8 are two forms of the byte input: choose one")
     rgb = bool(getattr(args, "rgb", False))
-    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8)
+    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8, as_nv12=nv12,
+                               nv12_standard=nv12_std)
     vid_seq.load_frames()
     if args.model == "td4-psp18":
         path_num = 4
@@ -128,8 +136,10 @@ def test(args):
     def save_rgb(picture, img_name, folder, ori_size):                 # --rgb: the device wrote the picture
         write_png(np.squeeze(picture, axis=0), img_name, folder)
 
-    def colour_map(image, pos_id, ori_size):                           # [1, oh, ow, 3] uint8 on the device
+    def colour_map(image, pos_id, ori_size, src_size=None):            # [1, oh, ow, 3] uint8 on the device
         out_size = (ori_size[1] // 4, ori_size[0] // 4)
+        if nv12:
+            return model.forward_rgb_nv12(image, pos_id, src_size, (H, W), out_size, standard=nv12_std)
         if u8:
             return model.forward_rgb_u8(image, pos_id, (H, W), out_size)
         return model.forward_rgb(image, pos_id, out_size)
@@ -144,15 +154,20 @@ def test(args):
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
             gt_feed = iter(DevicePrefetcher(gts, device)) if gts is not None else None   # the ground truth travels with the frame
-            for i, (image, img_name, folder, ori_size) in enumerate(DevicePrefetcher(vid_seq.data, device)):
+            for i, (image, img_name, folder, ori_size, *rest) in enumerate(DevicePrefetcher(vid_seq.data, device)):
+                src_size = rest[0] if nv12 else None                   # an NV12 item carries the picture's (Hs, Ws)
                 if gt_feed is not None:
                     gt = next(gt_feed)[0]
-                    if u8:
+                    if nv12:
+                        labels = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
+                    elif u8:
                         labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
                     else:
                         labels = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
                 elif rgb:
-                    labels = colour_map(image, i % path_num, ori_size)
+                    labels = colour_map(image, i % path_num, ori_size, src_size)
+                elif nv12:
+                    labels = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
                     labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
@@ -168,17 +183,24 @@ def test(args):
             print("---------------------")
             print_scores()
             return
-        for i, (image, img_name, folder, ori_size) in enumerate(vid_seq.data):
+        for i, (image, img_name, folder, ori_size, *rest) in enumerate(vid_seq.data):
+            src_size = rest[0] if nv12 else None
             image = image.to(device)
             gt = gts[i][0].to(device) if gts is not None else None
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
-            if gt is not None and u8:
+            if gt is not None and nv12:
+                output = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
+            elif gt is not None and u8:
                 output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
             elif gt is not None:
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
             elif rgb:
-                output = colour_map(image, i % path_num, ori_size)
+                output = colour_map(image, i % path_num, ori_size, src_size)
+            elif with_conf and nv12:
+                output, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
+            elif nv12:
+                output = model.forward_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
             elif with_conf:
                 output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W)) if u8 else model.forward_labels_conf(image, i % path_num)
             else:
@@ -217,6 +239,8 @@ if __name__ == "__main__":
     parser.add_argument("--synthetic_seed", nargs="?", type=int, default=None, help="run on seeded synthetic weights")
     parser.add_argument("--prefetch", action="store_true", help="throughput loop: upload of the next frame under the current one, asynchronous label download")
     parser.add_argument("--u8", action="store_true", help="frames stay uint8 HWC at their source size: resize + normalisation on the device (bit-identical); with --prefetch uint8 labels too")
+    parser.add_argument("--nv12", action="store_true", help="frames go to the device as NV12 surfaces (Y plane + interleaved UV plane, padded pitch): colour conversion, resize and normalisation in the frame's first launch")
+    parser.add_argument("--nv12_standard", nargs="?", type=int, default=0, help="the surfaces' YUV standard: 0 BT.601 limited (default), 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full")
     parser.add_argument("--rgb", action="store_true", help="the frame's last kernel writes the quarter-size colour map: no label download, resize or decode_segmap on the host")
     parser.add_argument("--gt_path", nargs="?", type=str, default=None, help="ground-truth PNGs (single channel, named like the frames): score the clip on the device and print the scores")
     parser.add_argument("--gt_map", nargs="?", type=str, default=None, help="text file of 256 integers: ground-truth byte -> class id (>= 19: ignored); default identity")
