@@ -251,6 +251,40 @@ int  tdnet_forward_rgb(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_
 int  tdnet_forward_u8_rgb(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* rgb_dev, void* stream);
 /* the picture of a uint8 label map [H,W] the caller already holds (tdnet_forward_u8_labels, tdnet_argmax_u8, ...)   */
 int  tdnet_labels_rgb(tdnet_t* h, const uint8_t* labels_u8_dev, uint8_t* rgb_dev, void* stream);
+/* ---- overlay out --------------------------------------------------------------------------------------------------
+ * The picture people look at for video segmentation: the class colours blended over the frame they belong to, at the FRAME's own size, written by
+ * the frame's LAST kernel.  Exact, integer:
+ *   geometry   out [Hs][Ws][3] uint8 RGB, contiguous, at any byte address; Hs x Ws = the source size of the handle's byte-input configuration in
+ *              force (tdnet_set_input_u8 or tdnet_set_input_nv12).  Source pixel (y, x) takes the label of network pixel (ys[y], xs[x]),
+ *              ys = nearest_index(H, Hs), xs = nearest_index(W, Ws) -- the rule of "colour map out", i.e. exactly what the colour-map entries sample
+ *              for out_height = Hs, out_width = Ws; the label is the first-maximum argmax there, the label the label entries give.
+ *   source     s = (sR, sG, sB) of pixel (y, x), read at the source's own resolution (nothing is resized).  Packed RGB: the three bytes at
+ *              src[(y * Ws + x) * 3 ..].  NV12: the conversion "NV12 frames in" defines for that pixel -- Y = Yplane[y][x],
+ *              (U, V) = UVplane[y >> 1][x >> 1], the 20-bit integer formulas with the configured standard's constants, clamped to 0..255.
+ *   colour     palette_rgba [n_colours][4] bytes on the HOST, copied: r, g, b, a.  a = 0 leaves the source pixel untouched, a = 255 replaces it;
+ *              the blend weight is A = a + (a >> 7), 0..255 -> 0..256.  A label >= n_colours has A = 0: the source pixel shows through unchanged
+ *              (so a reject_label >= n_colours from the confidence entries shows the bare frame).  This differs ON PURPOSE from the colour map's
+ *              grey (l, l, l): an overlay has a frame to fall back on, a colour map has not.
+ *   blend      per channel, in int32: out = (c * A + s * (256 - A) + 128) >> 8.  At most (255 * 256 + 128) >> 8 = 255: no clamp; A = 0 gives s
+ *              and A = 256 gives c, exactly.
+ *   memory     nothing outside the source extent is read (packed RGB: [src, src + 3 Hs Ws); NV12: the extent "NV12 frames in" defines), the result
+ *              does not depend on pitch padding or on the gap between the planes, nothing outside [out, out + 3 Hs Ws) is written.  out must not
+ *              overlap the source extent: the entries check this on the host and fail without enqueueing anything.
+ * tdnet_set_output_overlay: configuration (not a frame call: it may synchronise; idempotent for equal arguments; per handle: a tdnet_create_shared
+ * handle configures its own).  Independent of the order of the input configuration: it may come before or after it, and a later input configuration
+ * with another source size or format takes effect on the next frame (the index tables belong to the pair network size / source size and are rebuilt
+ * when either changes).  Its tables are counted in tdnet_memory_bytes.  Fails -- leaving the previous configuration in force -- on a handle that is not
+ * finalized, n_colours outside 1..256 and a NULL palette.                                                                                      */
+int  tdnet_set_output_overlay(tdnet_t* h, const uint8_t* palette_rgba /* [n_colours][4], host */, int n_colours /* 1..256 */);
+/* tdnet_forward_u8_labels with the overlay in place of the label map: img_dev is read by the handle's byte-input configuration (packed RGB, or the
+ * surface's base) and is BOTH the frame's image (first launch) and the overlay's source (last launch).  The same frame, the same FIFO step, the same
+ * tdnet_last_launch_count.  It only enqueues and works inside a hipGraph capture.  It fails -- changing nothing, a pending encoded frame stays
+ * pending -- when the overlay or the byte input is not configured (the message names the missing tdnet_set_* call), on a NULL argument and on
+ * overlap.  There is no fp32-image entry: an fp32 tensor has no source bytes to blend over.                                                  */
+int  tdnet_forward_u8_overlay(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* out_dev, void* stream);
+/* the unfused form: the overlay of a uint8 label map [H,W] the caller already holds over the source img_dev; after tdnet_forward_u8_labels_conf it is
+ * the overlay over the ACCEPTED pixels only (given a reject_label >= n_colours)                                                               */
+int  tdnet_labels_overlay(tdnet_t* h, const uint8_t* labels_u8_dev, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 /* ---- score out ----------------------------------------------------------------------------------------------------
  * What the reference's validation loop does on the host behind the labels (Training/validate.py:59-70, ptsemseg/metrics.py:12-21): the
  * n_class x n_class confusion matrix, hist[g][l] += 1 over the pixels with 0 <= g < n_class -- counted by the frame's LAST kernel instead, into
@@ -322,6 +356,8 @@ int  tdnet_propagate_labels(tdnet_t* h, int32_t* labels_dev, void* stream);
 int  tdnet_encode_u8(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, void* stream);
 int  tdnet_propagate_labels_u8(tdnet_t* h, uint8_t* labels_dev, void* stream);
 int  tdnet_propagate_rgb(tdnet_t* h, uint8_t* rgb_dev, void* stream);   /* see "colour map out" */
+/* the split frame's overlay: the caller passes the source again (the library does not remember pointers across calls); see "overlay out" */
+int  tdnet_propagate_overlay(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 int  tdnet_propagate_score(tdnet_t* h, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);   /* see "score out" */
 int  tdnet_propagate_labels_conf(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);   /* see "confidence out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */

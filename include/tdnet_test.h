@@ -138,6 +138,13 @@ int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, in
  * ignored).  Index tables and colour table are built by the host function tdnet_set_output_rgb uses; palette [n_colours][3] on the host.          */
 int tdnet_op_upsample_argmax_rgb(const float* in_dev, int C, int h, int w, int H, int W, int oh, int ow, const uint8_t* palette, int n_colours,
                                  uint8_t* rgb_dev, const uint8_t* labels_u8_dev, void* stream);
+/* The overlay [Hs,Ws,3] (uint8, any byte address; include/tdnet.h "overlay out") of low-resolution logits [C,h,w] upsampled to [H,W] -- through the last
+ * kernel of the overlay frame entries (labels_u8_dev == NULL) -- or of a uint8 label map [H,W] through the kernel of the unfused overlay entry
+ * (labels_u8_dev != NULL; in_dev, C, h, w are then ignored), over the source frame src_dev: packed RGB [Hs,Ws,3] (nv12 = 0; pitch, uv_offset and standard
+ * are ignored) or an NV12 surface (nv12 = 1) of that layout, at any byte address.  The source description, the index tables and the colour table are
+ * built by the host functions the handle's configuration calls use; palette_rgba [n_colours][4] on the host.                                         */
+int tdnet_op_overlay(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* src_dev, int nv12, int Hs, int Ws,
+                     int pitch, size_t uv_offset, int standard, const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
 /* cm_dev [C,C] uint64 -- ACCUMULATED into, not cleared -- += the confusion counts (include/tdnet.h "score out") of gt_dev [H,W] uint8 (any byte
  * address) through gt_map (256 bytes on the host, NULL = identity) against the labels of low-resolution logits [C,h,w] upsampled to [H,W], through
  * tdnet_forward_score's last kernel (labels_in_u8_dev == NULL; it also writes the uint8 label map if labels_u8_dev != NULL), or against a uint8

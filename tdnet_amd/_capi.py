@@ -80,6 +80,10 @@ SYMBOLS = {
     "tdnet_forward_u8_rgb": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_labels_rgb": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_propagate_rgb": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_output_overlay": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int]),
+    "tdnet_forward_u8_overlay": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_labels_overlay": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_overlay": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_set_score": (ctypes.c_int, [c_void_p, c_void_p]),
     "tdnet_forward_score": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_forward_u8_score": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
@@ -146,6 +150,8 @@ TEST_SYMBOLS = {
                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_rgb": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_overlay": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_size_t, ctypes.c_int, c_void_p, ctypes.c_int,
+                                        c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_score": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
     "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),

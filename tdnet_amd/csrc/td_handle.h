@@ -249,6 +249,19 @@ struct RgbOutput {
     unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16
     size_t bytes = 0;
 };
+// The overlay output of a handle (tdnet_set_output_overlay): palette with opacity, the colour table k_upsample_argmax_overlay / k_labels_overlay read,
+// and the index tables of the pair (network size, source size) -- the source size is the byte input's, so the tables follow U8Input (overlay_tables).
+// Per handle, like U8Input.
+struct OverlayOutput {
+    bool set = false;
+    int n_colours = 0;
+    unsigned char palette[1024] = {0};                                 // the caller's r, g, b, a rows, kept to recognise an equal call
+    unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16 | a << 24; 0 for a label >= n_colours
+    int H = 0, W = 0, Hs = 0, Ws = 0;                                  // the pair ys / xs were built for (Hs == 0: not built yet)
+    int* ys = nullptr;                                                 // [Hs]: nearest_index(H, Hs)
+    int* xs = nullptr;                                                 // [Ws]: nearest_index(W, Ws)
+    size_t bytes = 0;
+};
 // The score output of a handle (tdnet_set_score): the device confusion matrix the score kernels add into and the 256-byte ground-truth map they
 // read.  Per handle, like U8Input.
 struct ScoreOutput {
@@ -347,6 +360,7 @@ struct tdnet {
     size_t nrec = 0;
     U8Input u8;                                                        // tdnet_set_input_u8 / tdnet_set_input_nv12
     RgbOutput rgb;                                                     // tdnet_set_output_rgb
+    OverlayOutput overlay;                                             // tdnet_set_output_overlay
     ScoreOutput score;                                                 // tdnet_set_score
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
@@ -534,6 +548,64 @@ static int rgb_build(RgbOutput& r, int H, int W, int oh, int ow, const unsigned 
     v.set = true;
     rgb_free(r);
     r = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// overlay output: the host side of td_out.h's k_upsample_argmax_overlay / k_labels_overlay
+// ---------------------------------------------------------------------------------------------------------------
+static void overlay_free_tables(OverlayOutput& o) {
+    if (o.ys) hipFree(o.ys);
+    if (o.xs) hipFree(o.xs);
+    o.bytes -= ((size_t)o.Hs + (size_t)o.Ws) * sizeof(int);
+    o.ys = o.xs = nullptr;
+    o.H = o.W = o.Hs = o.Ws = 0;
+}
+static void overlay_free(OverlayOutput& o) {
+    if (o.Hs) overlay_free_tables(o);
+    if (o.lut) hipFree(o.lut);
+    o = OverlayOutput();
+}
+static bool overlay_same(const OverlayOutput& o, const unsigned char* palette, int n_colours) {
+    return o.set && o.n_colours == n_colours && palette && n_colours >= 1 && n_colours <= 256 && memcmp(o.palette, palette, (size_t)4 * n_colours) == 0;
+}
+// Validate and upload the 256-word colour + opacity table.  The index tables are not its business (overlay_tables).  On failure `o` is left as it was.
+static int overlay_build(OverlayOutput& o, const unsigned char* palette, int n_colours, const char* who) {
+    if (n_colours < 1 || n_colours > 256) return td_fail("%s: n_colours = %d must be in 1..256", who, n_colours);
+    if (!palette) return td_fail("%s: palette_rgba is NULL (the library carries no colour table of its own)", who);
+    std::vector<unsigned> lut(256, 0u);                                // a label outside the table has a = 0: the source pixel shows through
+    for (int l = 0; l < n_colours; ++l)
+        lut[l] = (unsigned)palette[4 * l] | ((unsigned)palette[4 * l + 1] << 8) | ((unsigned)palette[4 * l + 2] << 16) | ((unsigned)palette[4 * l + 3] << 24);
+    unsigned* d = nullptr;
+    if (dev_alloc(&d, lut.size())) return -1;
+    if (hipMemcpy(d, lut.data(), lut.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return td_fail("%s: table upload failed", who); }
+    if (o.lut) hipFree(o.lut);
+    else o.bytes += lut.size() * sizeof(unsigned);
+    o.lut = d;
+    o.n_colours = n_colours;
+    memset(o.palette, 0, sizeof(o.palette));
+    memcpy(o.palette, palette, (size_t)4 * n_colours);
+    o.set = true;
+    return 0;
+}
+// The index tables of the pair (network H x W, source Hs x Ws): built when the overlay is configured on a handle that has a byte input, and again
+// when a later byte-input configuration changes the source size.  On failure the tables are gone (a frame entry then says so).
+static int overlay_tables(OverlayOutput& o, int H, int W, int Hs, int Ws, const char* who) {
+    if (o.Hs == Hs && o.Ws == Ws && o.H == H && o.W == W) return 0;
+    if (o.Hs) overlay_free_tables(o);
+    if (Hs < 1 || Ws < 1 || H < 1 || W < 1) return td_fail("%s: overlay: sizes must be at least 1 x 1", who);
+    if (Hs > 65535) return td_fail("%s: overlay: src_height = %d is above the grid's 65535 rows", who, Hs);
+    if ((double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: overlay: a %d x %d picture is too large", who, Hs, Ws);
+    std::vector<int> ys, xs;
+    rgb_nearest_index(H, Hs, ys);
+    rgb_nearest_index(W, Ws, xs);
+    int *dy = nullptr, *dx = nullptr;
+    if (dev_alloc(&dy, ys.size()) || dev_alloc(&dx, xs.size())) { if (dy) hipFree(dy); return -1; }
+    if (hipMemcpy(dy, ys.data(), ys.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dx, xs.data(), xs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dy); hipFree(dx); return td_fail("%s: overlay: table upload failed", who); }
+    o.ys = dy; o.xs = dx;
+    o.H = H; o.W = W; o.Hs = Hs; o.Ws = Ws;
+    o.bytes += (ys.size() + xs.size()) * sizeof(int);
     return 0;
 }
 

@@ -447,6 +447,34 @@ static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, un
     TD_LAUNCH(k_labels_rgb, out_grid(r.ow, r.oh), dim3(256), 0, s, labels, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb, r.W, r.oh, r.ow);
     return 0;
 }
+// the overlay [Hs][Ws][3] of a frame (tdnet_set_output_overlay; `o` = that configuration, `u` = the byte input `src` is read by): the class colours blended
+// over the source frame, from the low-resolution logits or from a uint8 label map [H][W]
+static OverlaySrc overlay_src(const U8Input& u, const unsigned char* src) {
+    return OverlaySrc{src, u.pitch, (unsigned)u.uv_offset, u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5]};
+}
+static int overlay_check_tables(const OverlayOutput& o, const U8Input& u) {
+    if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("overlay: the index tables of this source size are missing (their allocation failed)");
+    return 0;
+}
+static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, const OverlayOutput& o, const U8Input& u, const unsigned char* src,
+                                          unsigned char* out, hipStream_t s) {
+    TD_TRY(out_check("overlay", "src_height", o.Hs, C));
+    TD_TRY(overlay_check_tables(o, u));
+    const OverlaySrc sd = overlay_src(u, src);
+    if (u.nv12) TD_LAUNCH((k_upsample_argmax_overlay<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out,
+                          C, h, w, o.H, o.W, o.Hs, o.Ws);
+    else TD_LAUNCH((k_upsample_argmax_overlay<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out,
+                   C, h, w, o.H, o.W, o.Hs, o.Ws);
+    return 0;
+}
+static int launch_labels_overlay(const unsigned char* labels, const OverlayOutput& o, const U8Input& u, const unsigned char* src, unsigned char* out, hipStream_t s) {
+    TD_TRY(out_check("overlay", "src_height", o.Hs, 1));
+    TD_TRY(overlay_check_tables(o, u));
+    const OverlaySrc sd = overlay_src(u, src);
+    if (u.nv12) TD_LAUNCH((k_labels_overlay<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws);
+    else TD_LAUNCH((k_labels_overlay<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws);
+    return 0;
+}
 // score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be
 // NULL) or from a uint8 label map the caller holds.  A private LDS histogram per workgroup up to TD_SCORE_LDS_CLASSES classes, straight
 // global atomics above.  The wave-uniform path is OFF in the library's entries until tools/score_probe.py has shown on the device that it
@@ -495,17 +523,21 @@ static int launch_logits_conf_u8(const float* logits, int C, long HW, unsigned c
 }
 
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY };
 struct FrameOutput {
     OutKind kind;
-    void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF: may be NULL) | rgb [oh][ow][3]
+    void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF: may be NULL) | rgb [oh][ow][3] | overlay [Hs][Ws][3]
     const unsigned char* gt;       // OUT_SCORE: ground truth [H][W]
     unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]
+    const unsigned char* src;      // OUT_OVERLAY: the source frame, read by the handle's byte-input configuration
 };
 // the handle-side precondition of a form: its tables exist
 static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
     if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
+    if (kind == OUT_OVERLAY && !n->overlay.set) return td_fail("%s: the overlay output is not configured (call tdnet_set_output_overlay first)", who);
+    if (kind == OUT_OVERLAY && !n->u8.set)
+        return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or tdnet_set_input_nv12 first): the overlay is written at its source size", who);
     return 0;
 }
 // The last launch of a frame: the handle's low-resolution logits leave in the form `o`.  Confidence takes the threshold in force NOW (kernel
@@ -521,6 +553,7 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
     case OUT_RGB: return launch_upsample_argmax_rgb(in, C, h, w, n->rgb, (unsigned char*)o.dst, s);
     case OUT_SCORE: return launch_upsample_argmax_score(in, C, h, w, H, W, o.gt, n->score.dmap, (unsigned char*)o.dst, n->score.cm, s);
     case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
+    case OUT_OVERLAY: return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);
     }
     return td_fail("internal: unknown output form");
 }

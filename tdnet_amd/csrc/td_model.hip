@@ -143,6 +143,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     if (n->vt16) hipFree(n->vt16);
     u8_free(n->u8);
     rgb_free(n->rgb);
+    overlay_free(n->overlay);
     score_free(n->score);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
@@ -272,6 +273,15 @@ extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_i
     if (!n || !img || !labels) return td_fail("tdnet_forward_u8_labels: null argument");
     return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_LABELS_U8, labels}, stream, "tdnet_forward_u8_labels");
 }
+// The overlay's index tables belong to the pair (network size, source size): a byte-input configuration that changed the source size rebuilds them
+// (the caller has synchronised: the previous tables existed only beside a previous input configuration).  Nothing to do without an overlay.
+static int overlay_follow_input(tdnet* n, const char* who) {
+    if (!n->overlay.set) return 0;
+    const size_t before = n->overlay.bytes;
+    const int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
+    n->ws_bytes += n->overlay.bytes - before;
+    return rc;
+}
 // Configuration of the uint8 image input (not a frame call: it may synchronise; idempotent for equal arguments).  The tables live in memory this
 // handle owns; a tdnet_create_shared handle has its own configuration.
 extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, const double* mean, const double* std_) {
@@ -287,7 +297,7 @@ extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, con
     const size_t before = n->u8.bytes;
     TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_u8"));
     n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
-    return 0;
+    return overlay_follow_input(n, "tdnet_set_input_u8");
 }
 // The other form of the handle's ONE byte-input configuration: the byte entries' image pointer is then the base of an NV12 surface of this
 // layout (td_ingest.h k_ingest_nv12), until a tdnet_set_input_u8 switches back.  A failed call leaves the previous configuration in force.
@@ -306,7 +316,7 @@ extern "C" int tdnet_set_input_nv12(tdnet_t* n, int src_height, int src_width, i
     const Nv12Layout nv = {pitch, uv_offset, standard};
     TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_nv12", &nv));
     n->ws_bytes += n->u8.bytes - before;
-    return 0;
+    return overlay_follow_input(n, "tdnet_set_input_nv12");
 }
 // ---- colour map out ----------------------------------------------------------------------------------------------------------------
 // Configuration of the colour-map output (not a frame call: it may synchronise; idempotent for equal arguments).  Tables and palette live in
@@ -336,6 +346,47 @@ extern "C" int tdnet_labels_rgb(tdnet_t* n, const uint8_t* labels, uint8_t* rgb,
     TD_ON_DEVICE(n, -1);
     TD_TRY(output_configured(n, OUT_RGB, "tdnet_labels_rgb"));
     TD_TRY(launch_labels_rgb(labels, n->rgb, rgb, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// ---- overlay out -----------------------------------------------------------------------------------------------------------------------
+// Configuration of the overlay output (not a frame call: it may synchronise; idempotent for equal arguments).  Independent of the order of the
+// byte-input configuration: the index tables are built here if the handle has one, by tdnet_set_input_u8 / tdnet_set_input_nv12 otherwise.
+extern "C" int tdnet_set_output_overlay(tdnet_t* n, const uint8_t* palette_rgba, int n_colours) {
+    if (!n) return td_fail("tdnet_set_output_overlay: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_output_overlay: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    if (overlay_same(n->overlay, palette_rgba, n_colours)) return 0;
+    if (n->overlay.set) TD_HIP(hipDeviceSynchronize());               // a frame in flight may still read the table that is about to go
+    const size_t before = n->overlay.bytes;
+    TD_TRY(overlay_build(n->overlay, palette_rgba, n_colours, "tdnet_set_output_overlay"));
+    const int rc = n->u8.set ? overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, "tdnet_set_output_overlay") : 0;
+    n->ws_bytes += n->overlay.bytes - before;
+    return rc;
+}
+// What every overlay entry checks on the host before anything is enqueued: both configurations exist, and `out` [Hs][Ws][3] does not overlap the
+// source extent (packed RGB: 3 Hs Ws bytes; NV12: the surface's extent) -- the kernel reads the source while it writes the picture.
+static int overlay_args(const tdnet* n, const uint8_t* src, const uint8_t* out, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(output_configured(n, OUT_OVERLAY, who));
+    const U8Input& u = n->u8;
+    const size_t nout = (size_t)3 * u.Hs * u.Ws, nsrc = u.nv12 ? u.extent : nout;
+    const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+    if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
+    return 0;
+}
+// The labels entries with another last launch: the overlay instead of the label map; the image pointer is the frame's image (first launch) AND the
+// overlay's source (last launch).  Same frame, same FIFO step, same number of launches.
+extern "C" int tdnet_forward_u8_overlay(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_forward_u8_overlay: null argument");
+    TD_TRY(overlay_args(n, img, out, "tdnet_forward_u8_overlay"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_OVERLAY, out, nullptr, nullptr, img}, stream, "tdnet_forward_u8_overlay");
+}
+extern "C" int tdnet_labels_overlay(tdnet_t* n, const uint8_t* labels, const uint8_t* img, uint8_t* out, void* stream) {
+    if (!n || !labels || !img || !out) return td_fail("tdnet_labels_overlay: null argument");
+    TD_TRY(overlay_args(n, img, out, "tdnet_labels_overlay"));
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(launch_labels_overlay(labels, n->overlay, n->u8, img, out, (hipStream_t)stream));
     TD_HIP(hipGetLastError());
     return 0;
 }
@@ -480,6 +531,11 @@ extern "C" int tdnet_propagate_labels_u8(tdnet_t* n, uint8_t* labels, void* stre
 extern "C" int tdnet_propagate_rgb(tdnet_t* n, uint8_t* rgb, void* stream) {
     if (!n || !rgb) return td_fail("tdnet_propagate_rgb: null argument");
     return frame_out(n, pending_frame, FrameOutput{OUT_RGB, rgb}, stream, "tdnet_propagate_rgb");
+}
+extern "C" int tdnet_propagate_overlay(tdnet_t* n, const uint8_t* img, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_propagate_overlay: null argument");
+    TD_TRY(overlay_args(n, img, out, "tdnet_propagate_overlay"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_OVERLAY, out, nullptr, nullptr, img}, stream, "tdnet_propagate_overlay");
 }
 extern "C" int tdnet_propagate_score(tdnet_t* n, const uint8_t* gt, uint8_t* labels, void* stream) {
     if (!n || !gt) return td_fail("tdnet_propagate_score: null argument");

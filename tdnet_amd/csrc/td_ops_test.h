@@ -543,6 +543,27 @@ extern "C" int tdnet_op_upsample_argmax_rgb(const float* in, int C, int h, int w
     rgb_free(r);
     return rc;
 }
+// The overlay [Hs][Ws][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: k_upsample_argmax_overlay) or of a uint8 label map [H][W] (labels_u8 != NULL:
+// k_labels_overlay; in, C, h, w are ignored) over a source frame: packed RGB [Hs][Ws][3] (nv12 == 0; pitch, uv_offset, standard ignored) or an NV12 surface,
+// through the byte-input description u8_build makes and the tables overlay_build / overlay_tables make for a handle.
+extern "C" int tdnet_op_overlay(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* src, int nv12, int Hs, int Ws, int pitch,
+                                size_t uv_offset, int standard, const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
+    const char* who = "tdnet_op_overlay";
+    if (!src || !out) return td_fail("%s: src and out expected", who);
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    OverlayOutput o;
+    const Nv12Layout nv = {pitch, uv_offset, standard};
+    TD_TRY(u8_build(u, Hs, Ws, H, W, nullptr, nullptr, who, nv12 ? &nv : nullptr));
+    int rc = overlay_build(o, palette_rgba, n_colours, who);
+    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, src, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, src, out, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
 // cm_dev [C][C] (uint64, ACCUMULATED into, not cleared) += the confusion counts of ground truth gt [H][W] (through gt_map, 256 bytes on the host,
 // NULL = identity) against the labels of low-resolution logits [C][h][w] (labels_in == NULL: k_upsample_argmax_score, which also writes the uint8
 // label map if labels_u8 != NULL) or against a uint8 label map [H][W] (labels_in != NULL: k_labels_score; in, h, w, labels_u8 are ignored).

@@ -1,5 +1,5 @@
 // td_out.h -- the output stage: what happens behind the low-resolution logits [C][h][w].  The x8 bilinear upsample (align_corners=True), the
-// argmax over classes, and the forms in which a frame's labels leave: fp32 logits, int32 labels, uint8 labels, a colour map.  td_score.h
+// argmax over classes, and the forms in which a frame's labels leave: fp32 logits, int32 labels, uint8 labels, a colour map, an overlay.  td_score.h
 // (confusion counts) and td_conf.h (confidence bytes) add their accumulator and store to the same body.
 //
 // ONE definition each of what every output form must agree on bit for bit:
@@ -15,6 +15,7 @@
 #include "td_device.h"
 #include "td_conv.h"   // td_ld4 / td_st4
 #include "td_misc.h"   // td_bilerp
+#include "td_ingest.h" // ingest_nv12_rgb: the one NV12 -> RGB conversion (overlay out reads the source frame)
 
 // ---- bilinear, align_corners=True (td4_psp18.py:227): planar [C][h][w] -> [C][H][W] ------------------------------
 struct UpCoef { int i0, i1; float l; };
@@ -254,5 +255,103 @@ TD_KERNEL void k_labels_rgb(const unsigned char* __restrict__ labels, const int*
     unsigned px[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) px[e] = lut[lrow[xs[td_run_px(xa, e, ow)]]];
+    td_rgb_store(orow, q, xa, xb, px);
+}
+
+// ---- overlay out -------------------------------------------------------------------------------------------------------------------
+// The picture people look at (include/tdnet.h "overlay out"): the class colours blended over the SOURCE frame, at the source's size.  The colour-map
+// kernels' geometry with oh x ow = Hs x Ws (ys / xs = nearest_index(H, Hs) / (W, Ws); lane split and store: td_rgb_run / td_rgb_store), and per
+// pixel the source bytes s and the table word r | g << 8 | b << 16 | a << 24 (0 for a label >= n_colours):
+//   A = a + (a >> 7)  (0..255 -> 0..256),   out_c = (c A + s_c (256 - A) + 128) >> 8   per channel, int32: A = 0 gives s, A = 256 gives c, no clamp.
+// The source is read at its own resolution, directly from the caller's buffer -- no LDS, no barrier, the early returns of the siblings stay: the
+// lane of an aligned group copies its 12 source bytes (packed RGB: a row starts at any byte, 3 Ws is odd at 1537) or its 4 Y bytes and its 2 - 3
+// chroma pairs (NV12) with byte-aligned loads the compiler is free to merge; head and tail lanes read pixel by pixel.  Only bytes of pixels
+// (y, x < Ws) and of chroma pairs (y >> 1, x >> 1) are addressed: nothing outside the source extent, none of the pitch padding or of the gap between
+// the planes.  (Why not ingest_stage_row: DESIGN.md 5.10.)  NV12 pixels are converted by ingest_nv12_rgb, the rule of "NV12 frames in".
+struct OverlaySrc {
+    const unsigned char* src;      // packed RGB [Hs][Ws][3], or the NV12 surface's base; any byte address
+    int pitch;                     // NV12: row pitch of both planes
+    unsigned uv_offset;            // NV12: < 2^31
+    int yoff, cy, cub, cug, cvg, cvr;   // NV12: td_handle.h nv12_coeffs
+};
+// R and B share one multiply: the fields (c A + s (256 - A) + 128) <= 65408 of bits 0..15 and 16..31 do not carry into each other
+TD_DEV unsigned td_overlay_blend(unsigned lutw, unsigned s) {         // s = sR | sG << 8 | sB << 16
+    const unsigned a = lutw >> 24, A = a + (a >> 7), B = 256u - A;
+    const unsigned rb = (((lutw & 0x00FF00FFu) * A + (s & 0x00FF00FFu) * B + 0x00800080u) >> 8) & 0x00FF00FFu;
+    const unsigned g = (((lutw >> 8) & 0xFFu) * A + ((s >> 8) & 0xFFu) * B + 128u) & 0xFF00u;
+    return rb | g;
+}
+// s[e] = the source pixel (y, xa + e) as sR | sG << 8 | sB << 16 (a partial run repeats its last pixel, td_run_px); quad: the run is a whole group
+template <bool NV12>
+TD_DEV void td_overlay_src(const OverlaySrc& o, int y, long xa, long ow, bool quad, unsigned* s) {
+    if (NV12) {
+        const unsigned char* yr = o.src + (size_t)y * o.pitch;
+        const unsigned char* cr = o.src + o.uv_offset + (size_t)(y >> 1) * o.pitch;    // the chroma row: wave-uniform like y
+        IngestNv12Args k = IngestNv12Args();                           // ingest_nv12_rgb reads the six constants only
+        k.yoff = o.yoff; k.cy = o.cy; k.cub = o.cub; k.cug = o.cug; k.cvg = o.cvg; k.cvr = o.cvr;
+        unsigned yw = 0;
+        if (quad) __builtin_memcpy(&yw, yr + xa, 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long x = td_run_px(xa, e, ow), cx = x & ~1L;
+            const int Y = quad ? (int)((yw >> (8 * e)) & 255u) : (int)yr[x];
+            int p[3];
+            ingest_nv12_rgb(k, Y, cr[cx], cr[cx + 1], p);
+            s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+        }
+    } else {
+        const unsigned char* r = o.src + (size_t)y * ow * 3;           // ow == Ws
+        if (quad) {
+            unsigned v[3];
+            __builtin_memcpy(v, r + 3 * xa, 12);
+            s[0] = v[0] & 0xFFFFFFu;
+            s[1] = ((v[0] >> 24) | (v[1] << 8)) & 0xFFFFFFu;
+            s[2] = ((v[1] >> 16) | (v[2] << 16)) & 0xFFFFFFu;
+            s[3] = v[2] >> 8;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned char* p = r + 3 * td_run_px(xa, e, ow);
+                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+            }
+        }
+    }
+}
+// The frame's last launch when the overlay is asked for: k_upsample_argmax_rgb's body (grid, lane split, class loop, argmax rule, store) + the
+// source pixel and the blend.  No branch on A: the blend with A = 0 returns the source.  The launch bound asks for the sibling's 5 waves per SIMD: without
+// it the allocator settles at 98 / 100 VGPRs and 4 waves, with it at 84 / 86 (k_upsample_argmax_rgb: 84), no spill either way.
+template <bool NV12>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                         OverlaySrc o, unsigned char* __restrict__ out, int C, int h, int w, int H, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = out + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+    unsigned s[4], px[4];
+    td_overlay_src<NV12>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
+    td_rgb_store(orow, q, xa, xb, px);
+}
+// The same picture from a uint8 label map [H][W] the caller already holds (k_labels_rgb's body + the same)
+template <bool NV12>
+TD_KERNEL void k_labels_overlay(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                OverlaySrc o, unsigned char* __restrict__ out, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = out + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
+    unsigned s[4], px[4];
+    td_overlay_src<NV12>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
     td_rgb_store(orow, q, xa, xb, px);
 }

@@ -124,6 +124,28 @@ def nearest_index(n_src, n_dst):
     return np.minimum((np.arange(n_dst) * (n_src / n_dst)).astype(np.int64), n_src - 1)
 
 
+def overlay_u8(src_rgb_u8, labels, palette_rgba):
+    """The oracle of the library's overlay output (include/tdnet.h "overlay out"): uint8 [Hs, Ws, 3].  src_rgb_u8 [Hs, Ws, 3] is the frame at
+    its own size, labels [H, W] the label map at the network size, palette_rgba [n, 4] bytes r, g, b, a.  Source pixel (y, x) takes the label
+    at (nearest_index(H, Hs)[y], nearest_index(W, Ws)[x]); a label >= n has weight 0.  Per channel, in int32:
+        A = a + (a >> 7);  out = (c * A + s * (256 - A) + 128) >> 8
+    so a = 0 returns the source byte and a = 255 the palette's, exactly, and nothing needs a clamp."""
+    src, lab, pal = np.asarray(src_rgb_u8), np.asarray(labels), np.asarray(palette_rgba)
+    assert src.dtype == np.uint8 and src.ndim == 3 and src.shape[2] == 3 and lab.ndim == 2
+    assert pal.dtype == np.uint8 and pal.ndim == 2 and pal.shape[1] == 4 and 1 <= pal.shape[0] <= 256
+    Hs, Ws = src.shape[:2]
+    H, W = lab.shape
+    l = lab[nearest_index(H, Hs)][:, nearest_index(W, Ws)].astype(np.int64)
+    table = np.zeros((max(256, int(l.max()) + 1), 4), np.int32)       # rows >= n stay zero: A = 0
+    table[:pal.shape[0]] = pal
+    assert l.min() >= 0
+    c, a = table[l][..., :3], table[l][..., 3:]
+    A = a + (a >> 7)
+    out = (c * A + src.astype(np.int32) * (256 - A) + 128) >> 8
+    assert out.min() >= 0 and out.max() <= 255
+    return out.astype(np.uint8)
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],

@@ -164,6 +164,29 @@ class Engine:
     def labels_rgb(self, labels_ptr, rgb_ptr, stream=None):
         self.lib.check(self.lib.tdnet_labels_rgb(self.h, _ptr(labels_ptr), _ptr(rgb_ptr), stream))
 
+    # ---- overlay out (include/tdnet.h) ----
+    def set_output_overlay(self, palette_rgba):
+        """Frames may be asked for as the overlay uint8 [Hs, Ws, 3] over their source bytes; palette_rgba: n_colours x 4 byte values r, g, b, a
+        (1..256 rows; a = 0 leaves the source, a = 255 replaces it).  A configuration call (it may synchronise); repeating it with equal arguments
+        does nothing.  Before or after set_input_u8 / set_input_nv12."""
+        pal = None if palette_rgba is None else np.ascontiguousarray(np.asarray(palette_rgba, dtype=np.uint8))
+        if pal is not None and (pal.ndim != 2 or pal.shape[1] != 4):
+            raise _capi.TdnetError("set_output_overlay: the palette is n_colours rows of 4 bytes (r, g, b, a)")
+        key = (None if pal is None else pal.tobytes(),)
+        if getattr(self, "_overlay_key", None) == key:
+            return
+        self.lib.check(self.lib.tdnet_set_output_overlay(self.h, None if pal is None else pal.ctypes.data, 0 if pal is None else pal.shape[0]))
+        self._overlay_key = key
+
+    def forward_u8_overlay(self, img_ptr, pos_id, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_overlay(self.h, _ptr(img_ptr), int(pos_id), _ptr(out_ptr), stream))
+
+    def propagate_overlay(self, img_ptr, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_overlay(self.h, _ptr(img_ptr), _ptr(out_ptr), stream))
+
+    def labels_overlay(self, labels_ptr, img_ptr, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_labels_overlay(self.h, _ptr(labels_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
+
     # ---- score out (include/tdnet.h) ----
     def set_score(self, gt_map=None):
         """Frames may be scored against ground truth: allocates this handle's zeroed confusion matrix.  gt_map: 256 byte values (ground-truth byte ->

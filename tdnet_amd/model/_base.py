@@ -517,6 +517,90 @@ class _TDNetBase(nn.Module):
             self._engine.labels_rgb(labels[i].data_ptr(), out[i].data_ptr(), s)
         return out
 
+    # ---- overlay out (not in the reference; include/tdnet.h "overlay out") ---------------------------------------------------------------
+    # The frame's last kernel blends the class colours over the SOURCE bytes, at the source's size: uint8 [N, Hs, Ws, 3].  palette: [n, 3] byte
+    # values (None = cityscapesLoader.label_colours) with `alpha` in 0..1 -- a scalar or one per class -- giving the opacity byte rint(255 alpha);
+    # or [n, 4] bytes r, g, b, a taken as they are (alpha is then ignored).  a = 0 leaves the frame, a = 255 replaces it; labels >= n show the frame.
+    @classmethod
+    def _palette_rgba(cls, palette, alpha):
+        if palette is not None:
+            p = np.asarray(palette)
+            if p.ndim != 2 or p.shape[1] not in (3, 4) or not 1 <= p.shape[0] <= 256:
+                raise RuntimeError("palette must be [n, 3] colours or [n, 4] bytes r, g, b, a with n in 1..256, got shape %s" % (p.shape,))
+            if p.shape[1] == 4:
+                return np.ascontiguousarray(p.astype(np.uint8))
+        pal = cls._palette(palette)
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != pal.shape[0]) or not np.isfinite(a).all() or (a < 0).any() or (a > 1).any():
+            raise RuntimeError("alpha must be a number in 0..1 or one per palette row (%d), got %r" % (pal.shape[0], alpha))
+        out = np.empty((pal.shape[0], 4), np.uint8)
+        out[:, :3] = pal
+        out[:, 3] = np.rint(255.0 * a).astype(np.uint8)
+        return out
+
+    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None):
+        """forward_labels_u8() with the overlay [N, Hs, Ws, 3] uint8 in place of the label map: the frame's bytes in, the tinted frame out."""
+        pal = self._palette_rgba(palette, alpha)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        img = img_u8.contiguous()
+        out = torch.empty(tuple(img.shape), device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_output_overlay(pal)
+            eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std)
+        return out
+
+    def forward_overlay_nv12(self, surf, pos_id, src_size, in_size, palette=None, alpha=0.5, uv_offset=None, standard=0, mean=None, std=None):
+        """forward_labels_nv12() with the overlay [N, Hs, Ws, 3] uint8 RGB in place of the label map: a decoder surface in, the tinted frame out."""
+        pal = self._palette_rgba(palette, alpha)
+        (H, W), nv = self._check_frame_nv12(surf, pos_id, src_size, in_size, uv_offset, standard)
+        img = surf.contiguous()
+        out = torch.empty((img.shape[0], nv[0], nv[1], 3), device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_output_overlay(pal)
+            eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, nv)
+        return out
+
+    def _overlay_source(self, who, src, n, src_size, uv_offset, standard):
+        """The source of an unfused / split overlay -> (contiguous tensor, (Hs, Ws), nv12 arguments or None): uint8 [N, Hs, Ws, 3] packed RGB, or
+        with src_size=(Hs, Ws) NV12 surfaces [N, rows, pitch]."""
+        if not torch.is_tensor(src) or src.dtype != torch.uint8:
+            raise RuntimeError("%s: expected the source frames as a torch.uint8 tensor, got %s" % (who, src.dtype if torch.is_tensor(src) else type(src).__name__))
+        if src_size is None:
+            if src.dim() != 4 or src.shape[3] != 3 or src.shape[0] != n or src.shape[1] < 1 or src.shape[2] < 1:
+                raise RuntimeError("%s: expected uint8 source frames [%d, Hs, Ws, 3], got shape %s" % (who, n, tuple(src.shape)))
+            return src.contiguous(), (int(src.shape[1]), int(src.shape[2])), None
+        _, nv = self._check_frame_nv12(src, 0, src_size, self._engine_key[:2], uv_offset, standard)
+        if src.shape[0] != n:
+            raise RuntimeError("%s: expected %d surfaces, got %d" % (who, n, src.shape[0]))
+        return src.contiguous(), (nv[0], nv[1]), nv
+
+    def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None):
+        """uint8 labels [N, H, W] (CUDA) of this model blended over their source frames -> [N, Hs, Ws, 3]; src: uint8 [N, Hs, Ws, 3], or with
+        src_size=(Hs, Ws) NV12 surfaces [N, rows, pitch].  After forward_labels_conf_u8 with a reject_label outside the palette: the overlay over
+        the accepted pixels only."""
+        if self._engine is None:
+            raise RuntimeError("labels_overlay(): no handle yet")
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
+            raise RuntimeError("labels_overlay(): expected uint8 labels [N, %d, %d]" % tuple(self._engine_key[:2]))
+        labels = labels_u8.contiguous()
+        img, (Hs, Ws), nv = self._overlay_source("labels_overlay()", src, labels.shape[0], src_size, uv_offset, standard)
+        pal = self._palette_rgba(palette, alpha)
+        out = torch.empty((labels.shape[0], Hs, Ws, 3), device=labels.device, dtype=torch.uint8)
+        eng = self._engine
+        if nv is None:
+            eng.set_input_u8(Hs, Ws, mean, std)
+        else:
+            eng.set_input_nv12(*nv, mean=mean, std=std)
+        eng.set_output_overlay(pal)
+        s = torch.cuda.current_stream(labels.device).cuda_stream
+        for i in range(labels.shape[0]):
+            eng.labels_overlay(labels[i].data_ptr(), img[i].data_ptr(), out[i].data_ptr(), s)
+        return out
+
     # ---- score out (not in the reference's model; its validation loop counts on the host, Training/validate.py:59-70) -----------------------
     # The frame's last kernel adds the frame's confusion counts against gt_u8 -- uint8 [N, H, W] at the NETWORK size, CUDA -- to a matrix each
     # handle owns (a batch is N handles: confusion_matrix() sums them).  gt_map: 256 values (ground-truth byte -> class id, >= nclass = ignore),
@@ -675,15 +759,19 @@ class _TDNetBase(nn.Module):
         self._pending_shape = (img.shape[2], img.shape[3], img.device)
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
-    def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None, conf=False):
+    def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None, conf=False, src=None, alpha=0.5, src_size=None,
+                  uv_offset=None, standard=0):
         """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
         uint8 labels (labels="u8"), the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb) or, with
         labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score).
-        conf=True: (uint8 labels, uint8 confidence), both [1, H, W], as forward_labels_conf gives them (labels must be left False, True or "u8")."""
+        conf=True: (uint8 labels, uint8 confidence), both [1, H, W], as forward_labels_conf gives them (labels must be left False, True or "u8").
+        labels="overlay" with src = the frame that was encoded (uint8 [1, Hs, Ws, 3], or with src_size=(Hs, Ws) the NV12 surface [1, rows, pitch]):
+        the overlay [1, Hs, Ws, 3] as forward_overlay_u8 / forward_overlay_nv12 give it (palette, alpha as there); the source is passed again
+        because the library does not remember pointers across calls."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
         if conf:
-            if labels in ("rgb", "score"):
+            if labels in ("rgb", "score", "overlay"):
                 raise RuntimeError("propagate(conf=True): gives uint8 labels and confidence; labels=%r asks for another last kernel" % (labels,))
             H, W, dev = self._pending_shape
             out, cmap = torch.empty((1, H, W), device=dev, dtype=torch.uint8), torch.empty((1, H, W), device=dev, dtype=torch.uint8)
@@ -691,8 +779,22 @@ class _TDNetBase(nn.Module):
             self._pending_shape = None
             self._engine.propagate_labels_conf(out.data_ptr(), cmap.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             return out, cmap
-        if isinstance(labels, str) and labels not in ("u8", "rgb", "score"):
-            raise RuntimeError("propagate(): labels must be False, True, \"u8\", \"rgb\" or \"score\"")
+        if isinstance(labels, str) and labels not in ("u8", "rgb", "score", "overlay"):
+            raise RuntimeError("propagate(): labels must be False, True, \"u8\", \"rgb\", \"score\" or \"overlay\"")
+        if labels == "overlay":
+            H, W, dev = self._pending_shape
+            pal = self._palette_rgba(palette, alpha)
+            img, (Hs, Ws), nv = self._overlay_source("propagate(labels=\"overlay\")", src, 1, src_size, uv_offset, standard)
+            if img.device != dev:
+                raise RuntimeError("propagate(labels=\"overlay\"): src must be on the frame's device %s, got %s" % (dev, img.device))
+            key = getattr(self._engine, "_u8_key", None) or getattr(self._engine, "_nv12_key", None)   # encode_u8 / encode_nv12 configured the input
+            if key is None or (Hs, Ws) != tuple(key[:2]) or (nv is None) != (getattr(self._engine, "_u8_key", None) is not None):
+                raise RuntimeError("propagate(labels=\"overlay\"): src is not of the size and format of the frame that was encoded (encode_u8 / encode_nv12)")
+            out = torch.empty((1, Hs, Ws, 3), device=dev, dtype=torch.uint8)
+            self._engine.set_output_overlay(pal)
+            self._pending_shape = None
+            self._engine.propagate_overlay(img.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
         if labels == "score":
             H, W, dev = self._pending_shape
             gt = self._check_gt(gt, 1, H, W, dev)

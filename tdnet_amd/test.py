@@ -21,6 +21,8 @@ as Training/validate.py:91-97 prints them.
 `--conf DIR` has the frame's last kernel also write the confidence map (the softmax probability of every pixel's label as a byte, 255 = certain) and
 saves it at the network size as a grey PNG DIR/folder/name beside the picture; `--min_conf T` (0..1) rejects labels below T: such a pixel gets
 label 255 and therefore decode_segmap's grey (255, 255, 255) in the picture.  Either switch selects the frame-by-frame loop's confidence form.
+`--overlay ALPHA` (0..1, with `--u8` or `--nv12`) has the frame's last kernel blend the class colours over the frame's own bytes and writes that
+SOURCE-size picture instead of the quarter-size colour map (include/tdnet.h "overlay out"); with `--min_conf` the rejected pixels show the bare frame.
 """
 import argparse
 import os
@@ -65,6 +67,14 @@ def test(args):
     if nv12 and u8:
         raise SystemExit("--nv12 and --u8 are two forms of the byte input: choose one")
     rgb = bool(getattr(args, "rgb", False))
+    overlay = getattr(args, "overlay", None)
+    if overlay is not None:                                            # checked before anything is loaded
+        if not (u8 or nv12):
+            raise SystemExit("--overlay blends the class colours over the frame's own bytes: give --u8 or --nv12 with it (an fp32 tensor has no source bytes)")
+        if rgb or getattr(args, "gt_path", None):
+            raise SystemExit("--overlay, --rgb and --gt_path ask for different last kernels: choose one")
+        if not 0.0 <= overlay <= 1.0:
+            raise SystemExit("--overlay: an opacity in 0..1 expected, got %r" % (overlay,))
     vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8, as_nv12=nv12,
                                nv12_standard=nv12_std)
     vid_seq.load_frames()
@@ -144,6 +154,11 @@ def test(args):
             return model.forward_rgb_u8(image, pos_id, (H, W), out_size)
         return model.forward_rgb(image, pos_id, out_size)
 
+    def overlay_picture(image, pos_id, src_size=None):                 # --overlay: [1, Hs, Ws, 3] uint8 on the device, at the source's size
+        if nv12:
+            return model.forward_overlay_nv12(image, pos_id, src_size, (H, W), alpha=overlay, standard=nv12_std)
+        return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay)
+
     timer, i = 0.0, -1
     with torch.no_grad():
         if args.prefetch:
@@ -166,14 +181,16 @@ def test(args):
                         labels = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
                 elif rgb:
                     labels = colour_map(image, i % path_num, ori_size, src_size)
+                elif overlay is not None:
+                    labels = overlay_picture(image, i % path_num, src_size)
                 elif nv12:
                     labels = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
                     labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
-                    (save_rgb if rgb else save)(pred, *tag)
+                    (save_rgb if rgb or overlay is not None else save)(pred, *tag)
             for tag, pred in down.drain():
-                (save_rgb if rgb else save)(pred, *tag)
+                (save_rgb if rgb or overlay is not None else save)(pred, *tag)
             torch.cuda.synchronize()
             timer = timeit.default_timer() - start_time
             print("---------------------")
@@ -197,6 +214,14 @@ def test(args):
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size)
+            elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
+                if nv12:
+                    l8, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
+                else:
+                    l8, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W))
+                output = model.labels_overlay(l8, image, alpha=overlay, src_size=src_size, standard=nv12_std)
+            elif overlay is not None:
+                output = overlay_picture(image, i % path_num, src_size)
             elif with_conf and nv12:
                 output, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
             elif nv12:
@@ -211,8 +236,12 @@ def test(args):
                 timer += elapsed_time
             if gt is not None:
                 save(output.cpu().numpy(), img_name, folder, ori_size)
-            elif rgb:
+            elif rgb or overlay is not None:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
+                if overlay is not None and conf_dir is not None:
+                    os.makedirs(os.path.join(conf_dir, folder), exist_ok=True)
+                    from PIL import Image
+                    Image.fromarray(np.squeeze(conf.cpu().numpy(), axis=0)).save(os.path.join(conf_dir, folder, img_name))
             elif with_conf:
                 save_conf(output.cpu().numpy(), conf.cpu().numpy(), img_name, folder, ori_size)
             else:
@@ -246,4 +275,5 @@ if __name__ == "__main__":
     parser.add_argument("--gt_map", nargs="?", type=str, default=None, help="text file of 256 integers: ground-truth byte -> class id (>= 19: ignored); default identity")
     parser.add_argument("--conf", nargs="?", type=str, default=None, help="directory for each frame's confidence map (grey PNG at the network size; 255 = certain)")
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
+    parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     test(parser.parse_args())
