@@ -234,6 +234,47 @@ int  tdnet_argmax_u8(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_d
 #define TDNET_YUV_BT709_FULL 3
 int  tdnet_set_input_nv12(tdnet_t* h, int src_height, int src_width, int pitch, size_t uv_offset, int standard,
                           const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
+/* ---- source views -----------------------------------------------------------------------------------------------------
+ * What producers really hand over: b g r or 4-byte pixels (cv2, capture APIs), rows with a pitch (image libraries, mapped surfaces), and a frame of
+ * another aspect than the network's, of which a rectangle is wanted (a centre crop, a region of interest, a decoder's display rectangle).  A VIEW is a
+ * rectangle of a pitched frame in one of five pixel formats; the handle reads it in the frame's first launch (and, for "overlay out", in its last),
+ * BIT-IDENTICALLY to cropping and reordering on the host and calling the existing entries, with the same tdnet_last_launch_count.
+ *   definition  (h, w) = (crop_height, crop_width) -- all four crop fields 0: the whole frame -- and rgb[y][x] = the R, G, B of frame pixel
+ *               (crop_y + y, crop_x + x).  Packed formats: the three colour bytes at base + (crop_y + y) * pitch + (crop_x + x) * bpp, in the order the
+ *               format names.  NV12: the conversion of "NV12 frames in" at the frame's ABSOLUTE coordinates, Y = Yplane[crop_y + y][crop_x + x],
+ *               (U, V) = UVplane[(crop_y + y) >> 1][(crop_x + x) >> 1] -- an odd origin shifts the chroma phase.  The frame is then exactly what
+ *               tdnet_set_input_u8(h, w, mean, std) computes on those contiguous RGB bytes: every resize tap converted first, interpolated afterwards,
+ *               the same coefficient tables for h x w -> H x W.
+ *   memory      nothing outside [base, base + extent) is read; packed: extent = (height - 1) * pitch + width * bpp, NV12: the extent "NV12 frames in"
+ *               defines for the whole frame.  `base` may be any byte address.  The result does not depend on any byte outside the rectangle's pixels
+ *               (NV12: outside the chroma pairs covering it): not on pitch padding, the x byte of the 32-bit formats, the plane gap or the rest of
+ *               the frame.
+ *   overlay     with a view in force "overlay out" writes out [h][w][3], contiguous 3-byte pixels in the SOURCE's colour order -- r g b for RGB24,
+ *               RGBA32 and NV12, b g r for BGR24 and BGRA32 (what a cv2 caller displays) -- over the view's pixels; only bytes of the rectangle's
+ *               pixels are read (NV12: and their chroma pairs; 32-bit: possibly the pixel's x byte), and out must not overlap the FRAME's extent.
+ * tdnet_set_input_view: configuration like its two siblings (not a frame call: it may synchronise; idempotent for equal arguments; per handle; ONE
+ * byte-input configuration at a time): afterwards every byte entry (tdnet_forward_u8*, tdnet_encode_u8, tdnet_propagate_overlay,
+ * tdnet_labels_overlay) reads its image pointer as the frame's `base`.  tdnet_set_input_u8 / tdnet_set_input_nv12 are the two obvious views.
+ * Fails -- leaving the previous configuration in force and the FIFO alone, the message naming the offending field -- on a handle that is not
+ * finalized, a NULL view, a format outside 0..4, frame or rectangle sizes below 1, a rectangle not inside the frame, a negative origin, a pitch below
+ * a row's bytes, a non-zero reserved, a non-zero standard / uv_offset on a packed format, the NV12 conditions of tdnet_set_input_nv12, an extent of
+ * 2^31 bytes or more, a bad mean or std, and a column downscale beyond what the kernel stages (a strip of 256 output columns may span about
+ * 10400 source columns of 3 bytes, 7800 of 4 bytes, 15600 of NV12).                                                                     */
+#define TDNET_PIX_RGB24  0   /* 3 bytes per pixel: r g b                      */
+#define TDNET_PIX_BGR24  1   /* 3 bytes per pixel: b g r                      */
+#define TDNET_PIX_RGBA32 2   /* 4 bytes per pixel: r g b x, x is never used   */
+#define TDNET_PIX_BGRA32 3   /* 4 bytes per pixel: b g r x                    */
+#define TDNET_PIX_NV12   4   /* "NV12 frames in": Y plane + interleaved U,V   */
+typedef struct tdnet_view {
+    int32_t  format;                 /* TDNET_PIX_*                                                                  */
+    int32_t  height, width;          /* the WHOLE frame, in pixels: the extent follows from it                       */
+    int32_t  pitch;                  /* bytes per row; 0 = tight (width * bpp; NV12: 2 * ceil(width / 2))           */
+    int32_t  crop_y, crop_x, crop_height, crop_width;   /* the rectangle; all four 0 = the whole frame              */
+    int32_t  standard;               /* NV12: TDNET_YUV_*; otherwise must be 0                                       */
+    int32_t  reserved[5];            /* must be 0                                                                    */
+    uint64_t uv_offset;              /* NV12: 0 = height * pitch; otherwise must be 0                                */
+} tdnet_view;
+int  tdnet_set_input_view(tdnet_t* h, const tdnet_view* v, const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
 /* ---- colour map out ------------------------------------------------------------------------------------------------
  * What the reference's loop does on the host behind the labels (Testing/test.py:61-71): the label map resized with nearest sampling and
  * decode_segmap -- done by the frame's LAST kernel instead.  It evaluates the x8 upsample only at the sampled pixels, takes the first-maximum

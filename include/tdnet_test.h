@@ -130,6 +130,9 @@ long tdnet_op_stem_image(const float* img_f32_dev, const uint8_t* src_u8_dev, in
 /* tdnet_op_stem_image from an NV12 surface at any byte address (include/tdnet.h "NV12 frames in"; the arguments of tdnet_set_input_nv12).   */
 long tdnet_op_stem_image_nv12(const uint8_t* surf_dev, int Hs, int Ws, int pitch, size_t uv_offset, int standard, int H, int W, const double* mean,
                               const double* std, int rows, float* out_dev, size_t capacity, void* stream);
+/* tdnet_op_stem_image from a source view (include/tdnet.h "source views"; the arguments of tdnet_set_input_view): base_dev at any byte address. */
+long tdnet_op_stem_image_view(const uint8_t* base_dev, const tdnet_view* view, int H, int W, const double* mean, const double* std, int rows, float* out_dev,
+                              size_t capacity, void* stream);
 /* low-resolution logits [C,h,w] -> labels [H,W] (bilinear align_corners=True, first maximum): int32 through the kernel of tdnet_forward_labels
  * (labels_i32_dev != NULL) and / or uint8 (labels_u8_dev != NULL) through the kernel of its uint8 form.  C in 1..256. */
 int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, int W, int32_t* labels_i32_dev, uint8_t* labels_u8_dev, void* stream);
@@ -145,6 +148,9 @@ int tdnet_op_upsample_argmax_rgb(const float* in_dev, int C, int h, int w, int H
  * built by the host functions the handle's configuration calls use; palette_rgba [n_colours][4] on the host.                                         */
 int tdnet_op_overlay(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* src_dev, int nv12, int Hs, int Ws,
                      int pitch, size_t uv_offset, int standard, const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
+/* tdnet_op_overlay with a source view in place of its source arguments: out_dev [h,w,3] of the view's rectangle h x w, in the source's colour order. */
+int tdnet_op_overlay_view(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* base_dev, const tdnet_view* view,
+                          const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
 /* cm_dev [C,C] uint64 -- ACCUMULATED into, not cleared -- += the confusion counts (include/tdnet.h "score out") of gt_dev [H,W] uint8 (any byte
  * address) through gt_map (256 bytes on the host, NULL = identity) against the labels of low-resolution logits [C,h,w] upsampled to [H,W], through
  * tdnet_forward_score's last kernel (labels_in_u8_dev == NULL; it also writes the uint8 label map if labels_u8_dev != NULL), or against a uint8

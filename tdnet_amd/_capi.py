@@ -38,6 +38,13 @@ class TdnetArch(ctypes.Structure):
         return {"dilated": self.dilated, "multi_grid": self.multi_grid}
 
 
+class TdnetView(ctypes.Structure):
+    """include/tdnet.h tdnet_view: a rectangle of a pitched frame in one of the TDNET_PIX_* formats."""
+    _fields_ = [("format", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("pitch", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_x", ctypes.c_int32), ("crop_height", ctypes.c_int32), ("crop_width", ctypes.c_int32),
+                ("standard", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5), ("uv_offset", ctypes.c_uint64)]
+
+
 class TdnetError(RuntimeError):
     pass
 
@@ -46,6 +53,7 @@ class TdnetError(RuntimeError):
 WINOGRAD_DEFAULT = 3          # include/tdnet.h TDNET_WINOGRAD_DEFAULT: F(4x4,3x3) for the wide stride-1 3x3 convs
 c_opts_p = ctypes.POINTER(TdnetOpts)
 c_arch_p = ctypes.POINTER(TdnetArch)
+c_view_p = ctypes.POINTER(TdnetView)
 
 SYMBOLS = {
     "tdnet_opts_default": (None, [c_opts_p]),
@@ -70,6 +78,7 @@ SYMBOLS = {
     "tdnet_set_input_u8": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tdnet_set_input_nv12": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "tdnet_set_input_view": (ctypes.c_int, [c_void_p, c_view_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tdnet_forward_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_forward_u8_labels": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_argmax_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -148,6 +157,9 @@ TEST_SYMBOLS = {
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "tdnet_op_stem_image_nv12": (ctypes.c_long, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_op_stem_image_view": (ctypes.c_long, [c_void_p, c_view_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_op_overlay_view": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_view_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_rgb": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_overlay": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_size_t, ctypes.c_int, c_void_p, ctypes.c_int,

@@ -220,14 +220,30 @@ struct PathLayers {
     int pid = 0;
 };
 struct CacheSlot { float* q = nullptr; float* k = nullptr; float* v = nullptr; };
-// The uint8 image input of a handle (tdnet_set_input_u8 / tdnet_set_input_nv12: ONE configuration at a time): source size, normalisation and
+// The uint8 image input of a handle (tdnet_set_input_u8 / tdnet_set_input_nv12 / tdnet_set_input_view: ONE configuration at a time): source size, normalisation and
 // the device tables k_ingest_u8 / k_ingest_nv12 read.  Per handle: tdnet_create_shared handles configure their own.
 struct Nv12Layout { int pitch; size_t uv_offset; int standard; };      // tdnet_set_input_nv12's surface arguments
+// What the byte entries' image pointer is the base of (include/tdnet.h "source views"): a frame fh x fw of `format` with rows `pitch` bytes apart
+// (0: tight), of which the image is the rectangle Hs x Ws at (oy, ox).  tdnet_set_input_u8 and tdnet_set_input_nv12 are the two obvious views.
+struct SrcView {
+    int format = 0;                                                    // TDNET_PIX_*
+    int fh = 0, fw = 0, pitch = 0, oy = 0, ox = 0;
+    size_t uv_offset = 0;                                              // NV12
+    int standard = 0;                                                  // NV12
+};
+static SrcView src_view_rgb(int Hs, int Ws) { SrcView v; v.fh = Hs; v.fw = Ws; return v; }
+static SrcView src_view_nv12(int Hs, int Ws, const Nv12Layout& nv) {
+    SrcView v; v.format = TDNET_PIX_NV12; v.fh = Hs; v.fw = Ws; v.pitch = nv.pitch; v.uv_offset = nv.uv_offset; v.standard = nv.standard; return v;
+}
+static int src_view_bpp(int format) { return format == TDNET_PIX_NV12 ? 1 : format >= TDNET_PIX_RGBA32 ? 4 : 3; }
 struct U8Input {
     bool set = false;
-    bool nv12 = false;                                                 // false: packed RGB [Hs][Ws][3]; true: an NV12 surface
-    int pitch = 0, standard = 0, span_c = 0;                           // NV12: row pitch, TDNET_YUV_*, LDS bytes per staged chroma span
-    size_t uv_offset = 0, extent = 0;                                  // NV12: the UV plane's offset; the bytes [base, base + extent) the kernel may read
+    bool nv12 = false;                                                 // false: packed pixels; true: an NV12 surface
+    int format = 0, bpp = 3;                                           // TDNET_PIX_*; bytes per packed pixel
+    bool swap = false;                                                 // packed: the colour bytes are b g r
+    int fh = 0, fw = 0, oy = 0, ox = 0;                                // the whole frame; the origin of the rectangle Hs x Ws the image is
+    int pitch = 0, standard = 0, span_c = 0;                           // bytes per frame row; NV12: TDNET_YUV_*, LDS bytes per staged chroma span
+    size_t uv_offset = 0, extent = 0;                                  // NV12: the UV plane's offset; the bytes [base, base + extent) of the whole frame: nothing else is read
     int coef[6] = {0, 0, 0, 0, 0, 0};                                  // NV12: yoff, CY, CUB, CUG, CVG, CVR (nv12_coeffs)
     int Hs = 0, Ws = 0, H = 0, W = 0, Wt = 0;                          // Wt: W rounded up to a multiple of 4 (the x tables' row length)
     double mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
@@ -257,6 +273,7 @@ struct OverlayOutput {
     int n_colours = 0;
     unsigned char palette[1024] = {0};                                 // the caller's r, g, b, a rows, kept to recognise an equal call
     unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16 | a << 24; 0 for a label >= n_colours
+    bool swap = false;                                                 // the table holds b | g << 8 | r << 16 | a << 24: the source's bytes are b g r, and so is the picture
     int H = 0, W = 0, Hs = 0, Ws = 0;                                  // the pair ys / xs were built for (Hs == 0: not built yet)
     int* ys = nullptr;                                                 // [Hs]: nearest_index(H, Hs)
     int* xs = nullptr;                                                 // [Ws]: nearest_index(W, Ws)
@@ -429,22 +446,28 @@ static void nv12_coeffs(int standard, int coef[6]) {
     for (int i = 0; i < 5; ++i) coef[1 + i] = (int)nearbyint(dec[standard][i] * 1048576.0);
 }
 // Validate, build the tables on the host and upload them into memory `u` owns.  NULL mean / std: the loader's (dataloader.py:52-53).
-// nv: the source is an NV12 surface of that layout (k_ingest_nv12) instead of packed RGB; the tables are the same.  On failure `u` is left as it was.
-static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who, const Nv12Layout* nv = nullptr) {
+// sv: what the image pointer is the base of -- the tables are those of the rectangle Hs x Ws whatever the format.  On failure `u` is left as it was.
+static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who) {
     static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};
     if (!mean) mean = mean0;
     if (!std_) std_ = std0;
+    const bool nv = sv.format == TDNET_PIX_NV12;
+    const int bpp = src_view_bpp(sv.format);
     if (Hs < 1 || Ws < 1) return td_fail("%s: source size %d x %d must be at least 1 x 1", who, Hs, Ws);
     if (H < 1 || W < 1 || H > 65535) return td_fail("%s: network size %d x %d out of range", who, H, W);
     if (!nv && (double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
+    const int pitch = nv || sv.pitch ? sv.pitch : sv.fw * bpp;         // packed, 0: tight (a row that overflows was refused above or by view_resolve)
     double extent = 0.0;
     if (nv) {
-        const int cw = (Ws - 1) / 2 + 1, chh = (Hs - 1) / 2 + 1;       // chroma pairs per row, chroma rows
-        if (nv->pitch < 2 * cw) return td_fail("%s: pitch %d is below the %d bytes a row of %d columns holds", who, nv->pitch, 2 * cw, Ws);
-        if ((double)nv->uv_offset < (double)Hs * nv->pitch) return td_fail("%s: uv_offset %zu is inside the Y plane (%d rows of pitch %d)", who, nv->uv_offset, Hs, nv->pitch);
-        extent = (double)nv->uv_offset + (double)(chh - 1) * nv->pitch + 2.0 * cw;
-        if (extent >= 2147483648.0) return td_fail("%s: the surface's extent (uv_offset %zu, pitch %d, %d rows) is 2^31 bytes or more", who, nv->uv_offset, nv->pitch, Hs);
-        if (nv->standard < 0 || nv->standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, nv->standard);
+        const int cw = (sv.fw - 1) / 2 + 1, chh = (sv.fh - 1) / 2 + 1;  // chroma pairs per row, chroma rows
+        if (pitch < 2 * cw) return td_fail("%s: pitch %d is below the %d bytes a row of %d columns holds", who, pitch, 2 * cw, sv.fw);
+        if ((double)sv.uv_offset < (double)sv.fh * pitch) return td_fail("%s: uv_offset %zu is inside the Y plane (%d rows of pitch %d)", who, sv.uv_offset, sv.fh, pitch);
+        extent = (double)sv.uv_offset + (double)(chh - 1) * pitch + 2.0 * cw;
+        if (extent >= 2147483648.0) return td_fail("%s: the surface's extent (uv_offset %zu, pitch %d, %d rows) is 2^31 bytes or more", who, sv.uv_offset, pitch, sv.fh);
+        if (sv.standard < 0 || sv.standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, sv.standard);
+    } else {
+        extent = (double)(sv.fh - 1) * pitch + (double)sv.fw * bpp;
+        if (extent >= 2147483648.0) return td_fail("%s: the frame's extent (pitch %d, %d rows) is 2^31 bytes or more", who, pitch, sv.fh);
     }
     for (int c = 0; c < 3; ++c) {
         if (!std::isfinite(mean[c])) return td_fail("%s: mean[%d] is not finite", who, c);
@@ -452,9 +475,11 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
     }
     U8Input v;
     v.Hs = Hs; v.Ws = Ws; v.H = H; v.W = W; v.Wt = (W + 3) / 4 * 4;
+    v.format = sv.format; v.bpp = bpp; v.swap = sv.format == TDNET_PIX_BGR24 || sv.format == TDNET_PIX_BGRA32;
+    v.fh = sv.fh; v.fw = sv.fw; v.oy = sv.oy; v.ox = sv.ox; v.pitch = pitch; v.extent = (size_t)extent;
     if (nv) {
-        v.nv12 = true; v.pitch = nv->pitch; v.uv_offset = nv->uv_offset; v.standard = nv->standard; v.extent = (size_t)extent;
-        nv12_coeffs(nv->standard, v.coef);
+        v.nv12 = true; v.uv_offset = sv.uv_offset; v.standard = sv.standard;
+        nv12_coeffs(sv.standard, v.coef);
     }
     for (int c = 0; c < 3; ++c) { v.mean[c] = mean[c]; v.std[c] = std_[c]; }
     v.resize = !(Hs == H && Ws == W);
@@ -475,7 +500,7 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
         for (int y = 0; y < H; ++y) { yt[4 * y] = y0[y]; yt[4 * y + 1] = y1[y]; yt[4 * y + 2] = b0[y]; yt[4 * y + 3] = b1[y]; }
     }
     // the workgroup size: the largest whose two staged spans (+ up to 15 bytes in front of the first, rounded to 16) fit beside the table;
-    // NV12: two Y spans of a byte per column and two chroma spans of a byte pair per two columns
+    // NV12: two Y spans of a byte per column and two chroma spans of a byte pair per two columns OF THE FRAME (the origin's parity counts)
     bool fits = false;
     for (int threads = 256; threads >= 64 && !fits; threads >>= 1) {
         long span = 0, span_c = 0;
@@ -483,12 +508,12 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
             const int xe = std::min(xs + 4 * threads, W);
             const int cl = v.resize ? x0[xs] : xs, ch = v.resize ? x1[xe - 1] : xe - 1;
             const long cols = (long)ch - cl + 1;
-            span = std::max(span, (cols * (nv ? 1 : 3) + 15 + 15) / 16 * 16);
-            if (nv) span_c = std::max(span_c, (((long)(ch >> 1) - (cl >> 1) + 1) * 2 + 15 + 15) / 16 * 16);
+            span = std::max(span, (cols * bpp + 15 + 15) / 16 * 16);
+            if (nv) span_c = std::max(span_c, (((long)((sv.ox + ch) >> 1) - ((sv.ox + cl) >> 1) + 1) * 2 + 15 + 15) / 16 * 16);
         }
         if (TD_INGEST_LUT_BYTES + 2 * span + 2 * span_c <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; v.span_c = (int)span_c; }
     }
-    if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about %s)", who, Ws, W, nv ? "60x" : "20x");
+    if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about %s)", who, Ws, W, nv ? "60x" : bpp == 4 ? "30x: 4 bytes per staged column" : "20x");
     if (upload(&v.lut, lut)) return -1;
     if (v.resize) {
         if (dev_alloc(&v.xt, xt.size()) || dev_alloc(&v.yt, yt.size())) { u8_free(v); return -1; }
@@ -500,6 +525,53 @@ static int u8_build(U8Input& u, int Hs, int Ws, int H, int W, const double* mean
     u8_free(u);
     u = v;
     return 0;
+}
+
+// tdnet_view -> (SrcView, Hs x Ws) with every default resolved, or the failure that names the offending field.  What is a property of the
+// surface or of the tables (the NV12 conditions, the extent, mean / std, the staged span) is u8_build's to check.
+static int view_resolve(const tdnet_view* t, SrcView& sv, int& Hs, int& Ws, const char* who) {
+    if (!t) return td_fail("%s: view is NULL", who);
+    if (t->format < 0 || t->format > TDNET_PIX_NV12) return td_fail("%s: format %d is not one of TDNET_PIX_* (0..4)", who, t->format);
+    for (int i = 0; i < 5; ++i)
+        if (t->reserved[i]) return td_fail("%s: reserved[%d] = %d must be 0", who, i, t->reserved[i]);
+    if (t->height < 1 || t->width < 1) return td_fail("%s: height x width = %d x %d must be at least 1 x 1", who, t->height, t->width);
+    const bool whole = !t->crop_y && !t->crop_x && !t->crop_height && !t->crop_width;
+    const int oy = t->crop_y, ox = t->crop_x, h = whole ? t->height : t->crop_height, w = whole ? t->width : t->crop_width;
+    if (oy < 0 || ox < 0) return td_fail("%s: crop_y, crop_x = %d, %d: the origin must not be negative", who, oy, ox);
+    if (h < 1 || w < 1) return td_fail("%s: crop_height x crop_width = %d x %d must be at least 1 x 1", who, h, w);
+    if (h > t->height || oy > t->height - h) return td_fail("%s: crop_y + crop_height = %d + %d is not inside the frame's height %d", who, oy, h, t->height);
+    if (w > t->width || ox > t->width - w) return td_fail("%s: crop_x + crop_width = %d + %d is not inside the frame's width %d", who, ox, w, t->width);
+    const bool nv = t->format == TDNET_PIX_NV12;
+    const int bpp = src_view_bpp(t->format);
+    if (t->pitch < 0) return td_fail("%s: pitch %d is negative", who, t->pitch);
+    sv = SrcView();
+    sv.format = t->format; sv.fh = t->height; sv.fw = t->width; sv.oy = oy; sv.ox = ox;
+    if (nv) {
+        sv.pitch = t->pitch ? t->pitch : 2 * ((t->width - 1) / 2 + 1);
+        if (!t->uv_offset && (double)t->height * sv.pitch >= 2147483648.0)
+            return td_fail("%s: the surface's extent (height %d, pitch %d) is 2^31 bytes or more", who, t->height, sv.pitch);
+        sv.uv_offset = t->uv_offset ? (size_t)t->uv_offset : (size_t)t->height * sv.pitch;
+        sv.standard = t->standard;
+    } else {
+        if (t->standard) return td_fail("%s: standard = %d must be 0 for a packed format", who, t->standard);
+        if (t->uv_offset) return td_fail("%s: uv_offset = %llu must be 0 for a packed format", who, (unsigned long long)t->uv_offset);
+        const double row = (double)t->width * bpp;
+        if (row >= 2147483648.0) return td_fail("%s: the frame's extent (a row of %d pixels) is 2^31 bytes or more", who, t->width);
+        if (t->pitch && t->pitch < (int)row) return td_fail("%s: pitch %d is below the %d bytes a row of %d pixels holds", who, t->pitch, (int)row, t->width);
+        sv.pitch = t->pitch ? t->pitch : (int)row;
+        if ((double)(t->height - 1) * sv.pitch + row >= 2147483648.0)
+            return td_fail("%s: the frame's extent (pitch %d, %d rows) is 2^31 bytes or more", who, sv.pitch, t->height);
+    }
+    Hs = h; Ws = w;
+    return 0;
+}
+// the configuration in force is the one these arguments would build (a packed pitch of 0 as u8_build resolves it)
+static bool u8_same(const U8Input& u, const SrcView& sv, int Hs, int Ws, const double* m, const double* sd) {
+    if (!u.set || u.format != sv.format || u.Hs != Hs || u.Ws != Ws || u.fh != sv.fh || u.fw != sv.fw || u.oy != sv.oy || u.ox != sv.ox) return false;
+    const bool nv = sv.format == TDNET_PIX_NV12;
+    const long pitch = nv || sv.pitch ? sv.pitch : (long)sv.fw * src_view_bpp(sv.format);
+    if (u.pitch != pitch || (nv && (u.uv_offset != sv.uv_offset || u.standard != sv.standard))) return false;
+    return memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -570,12 +642,26 @@ static bool overlay_same(const OverlayOutput& o, const unsigned char* palette, i
     return o.set && o.n_colours == n_colours && palette && n_colours >= 1 && n_colours <= 256 && memcmp(o.palette, palette, (size_t)4 * n_colours) == 0;
 }
 // Validate and upload the 256-word colour + opacity table.  The index tables are not its business (overlay_tables).  On failure `o` is left as it was.
-static int overlay_build(OverlayOutput& o, const unsigned char* palette, int n_colours, const char* who) {
+static void overlay_lut_words(const unsigned char* palette, int n_colours, bool swap, std::vector<unsigned>& lut) {
+    lut.assign(256, 0u);                                               // a label outside the table has a = 0: the source pixel shows through
+    for (int l = 0; l < n_colours; ++l)
+        lut[l] = (unsigned)palette[4 * l + (swap ? 2 : 0)] | ((unsigned)palette[4 * l + 1] << 8) | ((unsigned)palette[4 * l + (swap ? 0 : 2)] << 16) | ((unsigned)palette[4 * l + 3] << 24);
+}
+// The colour order follows the source's (include/tdnet.h "source views"): the blend is per channel, so a b g r source is the r g b path with the
+// table's r and b exchanged.  The caller has synchronised (a byte-input configuration call).
+static int overlay_set_swap(OverlayOutput& o, bool swap, const char* who) {
+    if (!o.set || o.swap == swap) return 0;
+    std::vector<unsigned> lut;
+    overlay_lut_words(o.palette, o.n_colours, swap, lut);
+    if (hipMemcpy(o.lut, lut.data(), lut.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) return td_fail("%s: overlay: table upload failed", who);
+    o.swap = swap;
+    return 0;
+}
+static int overlay_build(OverlayOutput& o, const unsigned char* palette, int n_colours, const char* who, bool swap = false) {
     if (n_colours < 1 || n_colours > 256) return td_fail("%s: n_colours = %d must be in 1..256", who, n_colours);
     if (!palette) return td_fail("%s: palette_rgba is NULL (the library carries no colour table of its own)", who);
-    std::vector<unsigned> lut(256, 0u);                                // a label outside the table has a = 0: the source pixel shows through
-    for (int l = 0; l < n_colours; ++l)
-        lut[l] = (unsigned)palette[4 * l] | ((unsigned)palette[4 * l + 1] << 8) | ((unsigned)palette[4 * l + 2] << 16) | ((unsigned)palette[4 * l + 3] << 24);
+    std::vector<unsigned> lut;
+    overlay_lut_words(palette, n_colours, swap, lut);
     unsigned* d = nullptr;
     if (dev_alloc(&d, lut.size())) return -1;
     if (hipMemcpy(d, lut.data(), lut.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return td_fail("%s: table upload failed", who); }
@@ -583,6 +669,7 @@ static int overlay_build(OverlayOutput& o, const unsigned char* palette, int n_c
     else o.bytes += lut.size() * sizeof(unsigned);
     o.lut = d;
     o.n_colours = n_colours;
+    o.swap = swap;
     memset(o.palette, 0, sizeof(o.palette));
     memcpy(o.palette, palette, (size_t)4 * n_colours);
     o.set = true;

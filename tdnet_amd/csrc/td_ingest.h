@@ -22,8 +22,12 @@ typedef int td_i32x4 __attribute__((ext_vector_type(4)));
 // A lane then produces 4 consecutive pixels = 12 floats: three 16-byte stores into the packed-row image out[(y + 3) Wp + x + 4][3]
 // (k_nchw3_to_rgbpad's pattern; scalar stores for the last, partial quad of a row whose W % 4 != 0), or four into NHWC4.  Only the interior
 // is written: the packed-row image's zero border is written once, when the buffer is allocated.
+// A source VIEW (include/tdnet.h "source views"): the Hs x Ws image is the rectangle at (oy, ox) of a frame whose rows lie `pitch` bytes apart
+// and whose pixels are BPP = 3 or 4 bytes (the 4th never indexed), colour bytes in the order r g b or (SWAP) b g r.  A row's staged span starts
+// at (oy + y0) pitch + (ox + cl) BPP and holds cols * BPP bytes; taps step by BPP and channel c reads byte c or 2 - c.  [src, src + extent) is
+// the WHOLE frame: nothing outside it is read.  The tight RGB image of tdnet_set_input_u8 is the view pitch = 3 Ws, oy = ox = 0.
 struct IngestArgs {
-    const unsigned char* src;      // [Hs][Ws][3] RGB, any byte alignment
+    const unsigned char* src;      // the frame's base, any byte alignment
     float* out;
     const float* lut;              // [3][256]
     const int* xt;                 // resize: [4][Wt] = x0 | x1 | a0 | a1 per output column, Wt = W rounded up to 4 (padding = the last column)
@@ -31,7 +35,9 @@ struct IngestArgs {
     int Hs, Ws, H, W, Wt;
     int Wp;                        // stem_rows_wp(W): the packed-row image; 0: NHWC4 with a zero 4th channel
     int resize;                    // 0: same size, lookup only
-    int span;                      // LDS bytes per staged source row (multiple of 16; td_handle.h u8_plan)
+    int span;                      // LDS bytes per staged source row (multiple of 16; td_handle.h u8_build)
+    int pitch, oy, ox;             // the view: bytes per frame row, the rectangle's origin
+    unsigned extent;               // < 2^31: the bytes of the whole frame
 };
 constexpr int TD_INGEST_LUT_BYTES = 3 * 256 * 4;
 
@@ -53,6 +59,7 @@ TD_DEV void ingest_stage_row(size_t lo, size_t hi, unsigned char* dst, size_t fi
     }
 }
 
+template <int BPP, bool SWAP>
 TD_KERNEL void k_ingest_u8(IngestArgs a) {
     TD_DYN_LDS(smem);
     float* lut = reinterpret_cast<float*>(smem);                                   // [3][256]
@@ -67,16 +74,17 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
         y0 = t[0]; y1 = t[1]; b0 = t[2]; b1 = t[3];
         cl = a.xt[xs]; ch = a.xt[a.Wt + xe - 1];
     }
-    const size_t nbytes = (size_t)(ch - cl + 1) * 3;
-    const size_t f0 = ((size_t)y0 * a.Ws + cl) * 3, f1 = ((size_t)y1 * a.Ws + cl) * 3;
-    const size_t lo = (size_t)a.src, hi = lo + (size_t)a.Hs * a.Ws * 3;
+    const size_t nbytes = (size_t)(ch - cl + 1) * BPP;
+    const size_t f0 = (size_t)(a.oy + y0) * a.pitch + (size_t)(a.ox + cl) * BPP, f1 = (size_t)(a.oy + y1) * a.pitch + (size_t)(a.ox + cl) * BPP;
+    const size_t lo = (size_t)a.src, hi = lo + a.extent;
     ingest_stage_row(lo, hi, row0, f0, nbytes);
     if (a.resize) ingest_stage_row(lo, hi, row1, f1, nbytes);
     __syncthreads();
     const int x = xs + (int)threadIdx.x * 4;
     if (x >= a.W) return;
-    const int o0 = (int)(((size_t)a.src + f0) & 15) - cl * 3;                      // row0[o0 + 3 * column + c]: the byte of source row y0
-    const int o1 = (int)(((size_t)a.src + f1) & 15) - cl * 3;
+    const int o0 = (int)(((size_t)a.src + f0) & 15) - cl * BPP + (SWAP ? 2 : 0);   // row0[o0 + BPP * column + c] (SWAP: - c): the byte of source row y0
+    const int o1 = (int)(((size_t)a.src + f1) & 15) - cl * BPP + (SWAP ? 2 : 0);
+    constexpr int CS = SWAP ? -1 : 1;
     float f[12];
     if (a.resize) {
         const td_i32x4 s0 = *reinterpret_cast<const td_i32x4*>(a.xt + x), s1 = *reinterpret_cast<const td_i32x4*>(a.xt + a.Wt + x);
@@ -85,8 +93,8 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const int r0 = (int)row0[o0 + 3 * s0[e] + c] * a0[e] + (int)row0[o0 + 3 * s1[e] + c] * a1[e];
-                const int r1 = (int)row1[o1 + 3 * s0[e] + c] * a0[e] + (int)row1[o1 + 3 * s1[e] + c] * a1[e];
+                const int r0 = (int)row0[o0 + BPP * s0[e] + CS * c] * a0[e] + (int)row0[o0 + BPP * s1[e] + CS * c] * a1[e];
+                const int r1 = (int)row1[o1 + BPP * s0[e] + CS * c] * a0[e] + (int)row1[o1 + BPP * s1[e] + CS * c] * a1[e];
                 int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
                 v = v < 0 ? 0 : v > 255 ? 255 : v;
                 f[3 * e + c] = lut[c * 256 + v];
@@ -95,7 +103,7 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) f[3 * e + c] = x + e < a.W ? lut[c * 256 + row0[o0 + 3 * (x + e) + c]] : 0.f;
+            for (int c = 0; c < 3; ++c) f[3 * e + c] = x + e < a.W ? lut[c * 256 + row0[o0 + BPP * (x + e) + CS * c]] : 0.f;
     }
     if (a.Wp) {
         float* o = a.out + ((size_t)(y + 3) * a.Wp + x + 4) * 3;                   // 16-byte aligned: Wp % 4 == 0, x % 4 == 0
@@ -127,6 +135,9 @@ TD_KERNEL void k_ingest_u8(IngestArgs a) {
 // ingest_stage_row: nothing outside [src, src + extent) is read, extent = uv_offset + (ceil(Hs / 2) - 1) pitch + 2 ceil(Ws / 2); bytes of the
 // pitch padding or of the gap between the planes may land in LDS but no tap indexes them.  The taps are converted in registers (3
 // multiply-adds, a shift and a clamp per channel): no second pass over LDS, no second barrier.
+// A source view (oy, ox) shifts every address to the frame's absolute coordinates: Y at (oy + y) pitch + ox + column, chroma row (oy + y) >> 1 (the
+// `two` test is on those rows), chroma byte (ox + column) & ~1; the staged chroma span runs from (ox + cl) & ~1 to the pair of ox + ch.  An odd
+// origin therefore shifts the chroma phase, as cropping the converted picture on the host does.
 struct IngestNv12Args {
     const unsigned char* src;      // the surface's base, any byte alignment
     float* out;
@@ -140,6 +151,7 @@ struct IngestNv12Args {
     int pitch;
     unsigned uv_offset, extent;    // < 2^31
     int yoff, cy, cub, cug, cvg, cvr;
+    int oy, ox;                    // a source view's origin (0, 0: the whole surface): source pixel (y, x) is frame pixel (oy + y, ox + x)
 };
 TD_DEV int ingest_clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 TD_DEV void ingest_nv12_rgb(const IngestNv12Args& a, int Y, int U, int V, int* p) {
@@ -167,11 +179,13 @@ TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
         y0 = t[0]; y1 = t[1]; b0 = t[2]; b1 = t[3];
         cl = a.xt[xs]; ch = a.xt[a.Wt + xe - 1];
     }
-    const int cc = cl & ~1;                                                        // the chroma span's first byte within its row
-    const size_t ny = (size_t)(ch - cl + 1), nc = (size_t)((ch >> 1) - (cl >> 1) + 1) * 2;
-    const size_t f0 = (size_t)y0 * a.pitch + cl, f1 = (size_t)y1 * a.pitch + cl;
-    const size_t c0 = (size_t)a.uv_offset + (size_t)(y0 >> 1) * a.pitch + cc, c1 = (size_t)a.uv_offset + (size_t)(y1 >> 1) * a.pitch + cc;
-    const bool two = (y0 >> 1) != (y1 >> 1);                                       // false without resize: y0 == y1
+    const int g0 = a.oy + y0, g1 = a.oy + y1;                                      // the frame's rows and ...
+    const int gl = a.ox + cl, gh = a.ox + ch;                                      // ... columns: chroma goes by THEIR parity
+    const int cc = gl & ~1;                                                        // the chroma span's first byte within its row
+    const size_t ny = (size_t)(ch - cl + 1), nc = (size_t)((gh >> 1) - (gl >> 1) + 1) * 2;
+    const size_t f0 = (size_t)g0 * a.pitch + gl, f1 = (size_t)g1 * a.pitch + gl;
+    const size_t c0 = (size_t)a.uv_offset + (size_t)(g0 >> 1) * a.pitch + cc, c1 = (size_t)a.uv_offset + (size_t)(g1 >> 1) * a.pitch + cc;
+    const bool two = (g0 >> 1) != (g1 >> 1);                                       // false without resize: y0 == y1
     const size_t lo = (size_t)a.src, hi = lo + a.extent;
     ingest_stage_row(lo, hi, yr0, f0, ny);
     if (a.resize) ingest_stage_row(lo, hi, yr1, f1, ny);
@@ -181,7 +195,7 @@ TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
     const int x = xs + (int)threadIdx.x * 4;
     if (x >= a.W) return;
     const int o0 = (int)((lo + f0) & 15) - cl, o1 = (int)((lo + f1) & 15) - cl;    // yr0[o0 + column]: the Y byte of source row y0
-    const int q0 = (int)((lo + c0) & 15) - cc;                                     // uv0[q0 + (column & ~1)]: its U, the next byte its V
+    const int q0 = (int)((lo + c0) & 15) - cc;                                     // uv0[q0 + ((ox + column) & ~1)]: its U, the next byte its V
     const unsigned char* uvb = two ? uv1 : uv0;                                    // the chroma row of source row y1
     const int q1 = two ? (int)((lo + c1) & 15) - cc : q0;
     float f[12];
@@ -190,7 +204,7 @@ TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
         const td_i32x4 a0 = *reinterpret_cast<const td_i32x4*>(a.xt + 2 * a.Wt + x), a1 = *reinterpret_cast<const td_i32x4*>(a.xt + 3 * a.Wt + x);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int ca = s0[e] & ~1, cb = s1[e] & ~1;
+            const int ca = (a.ox + s0[e]) & ~1, cb = (a.ox + s1[e]) & ~1;
             int p00[3], p01[3], p10[3], p11[3];                                    // the four taps, converted and clamped
             ingest_nv12_rgb(a, yr0[o0 + s0[e]], uv0[q0 + ca], uv0[q0 + ca + 1], p00);
             ingest_nv12_rgb(a, yr0[o0 + s1[e]], uv0[q0 + cb], uv0[q0 + cb + 1], p01);
@@ -209,7 +223,7 @@ TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
         for (int e = 0; e < 4; ++e) {
             int p[3] = {0, 0, 0};
             const bool in = x + e < a.W;
-            if (in) { const int cx = (x + e) & ~1; ingest_nv12_rgb(a, yr0[o0 + x + e], uv0[q0 + cx], uv0[q0 + cx + 1], p); }
+            if (in) { const int cx = (a.ox + x + e) & ~1; ingest_nv12_rgb(a, yr0[o0 + x + e], uv0[q0 + cx], uv0[q0 + cx + 1], p); }
 #pragma unroll
             for (int c = 0; c < 3; ++c) f[3 * e + c] = in ? lut[c * 256 + p[c]] : 0.f;
         }

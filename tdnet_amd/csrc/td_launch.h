@@ -334,8 +334,8 @@ static void run_ppm(tdnet* n, const float* c4, int h, int w, int C, int XS, int 
 }
 
 // The image of a frame as the caller handed it over: fp32 NCHW [3][H][W] at the network size, or uint8 HWC [Hs][Ws][3] at the source size the
-// handle was configured for (tdnet_set_input_u8; `u8` = that configuration), or the NV12 surface tdnet_set_input_nv12 described.  Everything behind the stem's image buffer is the same frame.
-enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };                               // TD_IMG_U8: the handle's byte input, packed RGB or (U8Input::nv12) an NV12 surface
+// handle was configured for (tdnet_set_input_u8; `u8` = that configuration), or the NV12 surface tdnet_set_input_nv12 described, or the frame of which tdnet_set_input_view described a rectangle.  Everything behind the stem's image buffer is the same frame.
+enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };                               // TD_IMG_U8: the handle's byte input (U8Input: packed pixels or an NV12 surface, whole or a rectangle)
 struct FrameInput { const void* p; int kind; const U8Input* u8; };
 static inline FrameInput frame_input_f32(const float* img) { return FrameInput{img, TD_IMG_F32, nullptr}; }
 // rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
@@ -347,12 +347,18 @@ static void run_stem_pre(tdnet* n, const FrameInput& in, int H, int W, float* im
         if (u.nv12) {                                                  // colour conversion too, in the same one launch
             const IngestNv12Args a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
                                       u.span, u.span_c, u.pitch, (unsigned)u.uv_offset, (unsigned)u.extent,
-                                      u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5]};
+                                      u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
             TD_LAUNCH(k_ingest_nv12, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span + 2 * u.span_c, s, a);
             break;
         }
-        const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0, u.span};
-        TD_LAUNCH(k_ingest_u8, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span, s, a);
+        const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0, u.span,
+                              u.pitch, u.oy, u.ox, (unsigned)u.extent};
+        const dim3 grid((W + 4 * u.threads - 1) / (4 * u.threads), H), block(u.threads);
+        const int lds = TD_INGEST_LUT_BYTES + 2 * u.span;
+        if (u.bpp == 3 && !u.swap) TD_LAUNCH((k_ingest_u8<3, false>), grid, block, lds, s, a);   // the format is the instantiation: RGB24 pays nothing for the others
+        else if (u.bpp == 3) TD_LAUNCH((k_ingest_u8<3, true>), grid, block, lds, s, a);
+        else if (!u.swap) TD_LAUNCH((k_ingest_u8<4, false>), grid, block, lds, s, a);
+        else TD_LAUNCH((k_ingest_u8<4, true>), grid, block, lds, s, a);
         break;
     }
     default: {
@@ -450,10 +456,16 @@ static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, un
 // the overlay [Hs][Ws][3] of a frame (tdnet_set_output_overlay; `o` = that configuration, `u` = the byte input `src` is read by): the class colours blended
 // over the source frame, from the low-resolution logits or from a uint8 label map [H][W]
 static OverlaySrc overlay_src(const U8Input& u, const unsigned char* src) {
-    return OverlaySrc{src, u.pitch, (unsigned)u.uv_offset, u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5]};
+    return OverlaySrc{src, u.pitch, (unsigned)u.uv_offset, u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
+}
+// the source form and whether it is a VIEW (an origin, or packed rows with a pitch): 2 * form + view
+static int overlay_src_form(const U8Input& u) {
+    const bool view = u.oy || u.ox || u.bpp == 4 || (!u.nv12 && u.pitch != 3 * u.Ws);
+    return 2 * (u.nv12 ? TD_SRC_NV12 : u.bpp == 4 ? TD_SRC_P32 : TD_SRC_P24) + (view ? 1 : 0);
 }
 static int overlay_check_tables(const OverlayOutput& o, const U8Input& u) {
     if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("overlay: the index tables of this source size are missing (their allocation failed)");
+    if (o.swap != u.swap) return td_fail("overlay: the colour table is not in the source's colour order (its upload failed)");
     return 0;
 }
 static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, const OverlayOutput& o, const U8Input& u, const unsigned char* src,
@@ -461,18 +473,31 @@ static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, 
     TD_TRY(out_check("overlay", "src_height", o.Hs, C));
     TD_TRY(overlay_check_tables(o, u));
     const OverlaySrc sd = overlay_src(u, src);
-    if (u.nv12) TD_LAUNCH((k_upsample_argmax_overlay<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out,
-                          C, h, w, o.H, o.W, o.Hs, o.Ws);
-    else TD_LAUNCH((k_upsample_argmax_overlay<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out,
-                   C, h, w, o.H, o.W, o.Hs, o.Ws);
+    switch (overlay_src_form(u)) {
+#define TD_OVL(SRC, VIEW) TD_LAUNCH((k_upsample_argmax_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, \
+                              C, h, w, o.H, o.W, o.Hs, o.Ws)
+    case 2 * TD_SRC_P24: TD_OVL(TD_SRC_P24, false); break;
+    case 2 * TD_SRC_P24 + 1: TD_OVL(TD_SRC_P24, true); break;
+    case 2 * TD_SRC_NV12: TD_OVL(TD_SRC_NV12, false); break;
+    case 2 * TD_SRC_NV12 + 1: TD_OVL(TD_SRC_NV12, true); break;
+    default: TD_OVL(TD_SRC_P32, true);
+#undef TD_OVL
+    }
     return 0;
 }
 static int launch_labels_overlay(const unsigned char* labels, const OverlayOutput& o, const U8Input& u, const unsigned char* src, unsigned char* out, hipStream_t s) {
     TD_TRY(out_check("overlay", "src_height", o.Hs, 1));
     TD_TRY(overlay_check_tables(o, u));
     const OverlaySrc sd = overlay_src(u, src);
-    if (u.nv12) TD_LAUNCH((k_labels_overlay<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws);
-    else TD_LAUNCH((k_labels_overlay<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws);
+    switch (overlay_src_form(u)) {
+#define TD_OVL(SRC, VIEW) TD_LAUNCH((k_labels_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws)
+    case 2 * TD_SRC_P24: TD_OVL(TD_SRC_P24, false); break;
+    case 2 * TD_SRC_P24 + 1: TD_OVL(TD_SRC_P24, true); break;
+    case 2 * TD_SRC_NV12: TD_OVL(TD_SRC_NV12, false); break;
+    case 2 * TD_SRC_NV12 + 1: TD_OVL(TD_SRC_NV12, true); break;
+    default: TD_OVL(TD_SRC_P32, true);
+#undef TD_OVL
+    }
     return 0;
 }
 // score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be

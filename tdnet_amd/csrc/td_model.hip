@@ -278,45 +278,46 @@ extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_i
 static int overlay_follow_input(tdnet* n, const char* who) {
     if (!n->overlay.set) return 0;
     const size_t before = n->overlay.bytes;
-    const int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
+    int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
     n->ws_bytes += n->overlay.bytes - before;
+    if (!rc) rc = overlay_set_swap(n->overlay, n->u8.swap, who);       // the picture's colour order is the source's
     return rc;
 }
-// Configuration of the uint8 image input (not a frame call: it may synchronise; idempotent for equal arguments).  The tables live in memory this
-// handle owns; a tdnet_create_shared handle has its own configuration.
+// The handle's ONE byte-input configuration, whichever entry describes it (not a frame call: it may synchronise; idempotent for equal arguments).  The
+// tables live in memory this handle owns; a tdnet_create_shared handle has its own configuration.  A failed call leaves the previous one in force.
+static int set_input(tdnet* n, const SrcView& sv, int Hs, int Ws, const double* mean, const double* std_, const char* who) {
+    TD_ON_DEVICE(n, -1);
+    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};   // dataloader.py:52-53
+    const double* m = mean ? mean : mean0;
+    const double* sd = std_ ? std_ : std0;
+    if (u8_same(n->u8, sv, Hs, Ws, m, sd)) return 0;
+    if (n->u8.set) TD_HIP(hipDeviceSynchronize());                    // a frame in flight may still read the tables that are about to go
+    const size_t before = n->u8.bytes;
+    TD_TRY(u8_build(n->u8, sv, Hs, Ws, n->H, n->W, m, sd, who));
+    n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
+    return overlay_follow_input(n, who);
+}
+// packed RGB [src_height][src_width][3]: the whole, tight RGB24 view
 extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, const double* mean, const double* std_) {
     if (!n) return td_fail("tdnet_set_input_u8: null handle");
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_u8: weights not finalized");
-    TD_ON_DEVICE(n, -1);
-    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};   // dataloader.py:52-53
-    const double* m = mean ? mean : mean0;
-    const double* sd = std_ ? std_ : std0;
-    const U8Input& u = n->u8;
-    if (u.set && !u.nv12 && u.Hs == src_height && u.Ws == src_width && memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
-    if (u.set) TD_HIP(hipDeviceSynchronize());                        // a frame in flight may still read the tables that are about to go
-    const size_t before = n->u8.bytes;
-    TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_u8"));
-    n->ws_bytes += n->u8.bytes - before;                               // tdnet_memory_bytes: the tables belong to this handle
-    return overlay_follow_input(n, "tdnet_set_input_u8");
+    return set_input(n, src_view_rgb(src_height, src_width), src_height, src_width, mean, std_, "tdnet_set_input_u8");
 }
-// The other form of the handle's ONE byte-input configuration: the byte entries' image pointer is then the base of an NV12 surface of this
-// layout (td_ingest.h k_ingest_nv12), until a tdnet_set_input_u8 switches back.  A failed call leaves the previous configuration in force.
+// an NV12 surface of this layout (td_ingest.h k_ingest_nv12): the whole NV12 view
 extern "C" int tdnet_set_input_nv12(tdnet_t* n, int src_height, int src_width, int pitch, size_t uv_offset, int standard, const double* mean, const double* std_) {
     if (!n) return td_fail("tdnet_set_input_nv12: null handle");
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_nv12: weights not finalized");
-    TD_ON_DEVICE(n, -1);
-    static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};   // dataloader.py:52-53
-    const double* m = mean ? mean : mean0;
-    const double* sd = std_ ? std_ : std0;
-    const U8Input& u = n->u8;
-    if (u.set && u.nv12 && u.Hs == src_height && u.Ws == src_width && u.pitch == pitch && u.uv_offset == uv_offset && u.standard == standard &&
-        memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0) return 0;
-    if (u.set) TD_HIP(hipDeviceSynchronize());                        // a frame in flight may still read the tables that are about to go
-    const size_t before = n->u8.bytes;
     const Nv12Layout nv = {pitch, uv_offset, standard};
-    TD_TRY(u8_build(n->u8, src_height, src_width, n->H, n->W, m, sd, "tdnet_set_input_nv12", &nv));
-    n->ws_bytes += n->u8.bytes - before;
-    return overlay_follow_input(n, "tdnet_set_input_nv12");
+    return set_input(n, src_view_nv12(src_height, src_width, nv), src_height, src_width, mean, std_, "tdnet_set_input_nv12");
+}
+// a rectangle of a pitched frame in one of the five pixel formats (include/tdnet.h "source views")
+extern "C" int tdnet_set_input_view(tdnet_t* n, const tdnet_view* v, const double* mean, const double* std_) {
+    if (!n) return td_fail("tdnet_set_input_view: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_view: weights not finalized");
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(view_resolve(v, sv, Hs, Ws, "tdnet_set_input_view"));
+    return set_input(n, sv, Hs, Ws, mean, std_, "tdnet_set_input_view");
 }
 // ---- colour map out ----------------------------------------------------------------------------------------------------------------
 // Configuration of the colour-map output (not a frame call: it may synchronise; idempotent for equal arguments).  Tables and palette live in
@@ -360,17 +361,18 @@ extern "C" int tdnet_set_output_overlay(tdnet_t* n, const uint8_t* palette_rgba,
     if (n->overlay.set) TD_HIP(hipDeviceSynchronize());               // a frame in flight may still read the table that is about to go
     const size_t before = n->overlay.bytes;
     TD_TRY(overlay_build(n->overlay, palette_rgba, n_colours, "tdnet_set_output_overlay"));
-    const int rc = n->u8.set ? overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, "tdnet_set_output_overlay") : 0;
+    int rc = n->u8.set ? overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, "tdnet_set_output_overlay") : 0;
     n->ws_bytes += n->overlay.bytes - before;
+    if (!rc && n->u8.set) rc = overlay_set_swap(n->overlay, n->u8.swap, "tdnet_set_output_overlay");
     return rc;
 }
 // What every overlay entry checks on the host before anything is enqueued: both configurations exist, and `out` [Hs][Ws][3] does not overlap the
-// source extent (packed RGB: 3 Hs Ws bytes; NV12: the surface's extent) -- the kernel reads the source while it writes the picture.
+// source extent (the WHOLE frame's, whatever rectangle of it the view is) -- the kernel reads the source while it writes the picture.
 static int overlay_args(const tdnet* n, const uint8_t* src, const uint8_t* out, const char* who) {
     if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
     TD_TRY(output_configured(n, OUT_OVERLAY, who));
     const U8Input& u = n->u8;
-    const size_t nout = (size_t)3 * u.Hs * u.Ws, nsrc = u.nv12 ? u.extent : nout;
+    const size_t nout = (size_t)3 * u.Hs * u.Ws, nsrc = u.extent;
     const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
     if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
     return 0;

@@ -479,7 +479,7 @@ extern "C" long tdnet_op_stem_image(const float* img_f32, const uint8_t* src_u8,
     if (capacity < img_floats) return td_fail("tdnet_op_stem_image: capacity %zu < %zu", capacity, img_floats);
     hipStream_t s = (hipStream_t)stream;
     U8Input u;
-    if (src_u8 && u8_build(u, Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image")) return -1;
+    if (src_u8 && u8_build(u, src_view_rgb(Hs, Ws), Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image")) return -1;
     float* img4 = nullptr;
     if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
     long rc = (long)img_floats;
@@ -504,7 +504,7 @@ extern "C" long tdnet_op_stem_image_nv12(const uint8_t* surf, int Hs, int Ws, in
     hipStream_t s = (hipStream_t)stream;
     U8Input u;
     const Nv12Layout nv = {pitch, uv_offset, standard};
-    if (u8_build(u, Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image_nv12", &nv)) return -1;
+    if (u8_build(u, src_view_nv12(Hs, Ws, nv), Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image_nv12")) return -1;
     float* img4 = nullptr;
     if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
     long rc = (long)img_floats;
@@ -514,6 +514,33 @@ extern "C" long tdnet_op_stem_image_nv12(const uint8_t* surf, int Hs, int Ws, in
         if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: copy failed");
     }
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: device error");
+    hipFree(img4);
+    u8_free(u);
+    return rc;
+}
+// tdnet_op_stem_image from a source view: the ingest kernel of the view's format with the configuration tdnet_set_input_view would build
+extern "C" long tdnet_op_stem_image_view(const uint8_t* base, const tdnet_view* view, int H, int W, const double* mean, const double* std_, int rows, float* out,
+                                         size_t capacity, void* stream) {
+    const char* who = "tdnet_op_stem_image_view";
+    if (H < 1 || W < 1) return td_fail("%s: empty image", who);
+    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
+    if (!out) return (long)img_floats;
+    if (!base) return td_fail("%s: base is NULL", who);
+    if (capacity < img_floats) return td_fail("%s: capacity %zu < %zu", who, capacity, img_floats);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    if (view_resolve(view, sv, Hs, Ws, who) || u8_build(u, sv, Hs, Ws, H, W, mean, std_, who)) return -1;
+    float* img4 = nullptr;
+    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
+    long rc = (long)img_floats;
+    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("%s: memset failed", who);
+    if (rc >= 0) {
+        run_stem_pre(nullptr, FrameInput{base, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
+        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
     hipFree(img4);
     u8_free(u);
     return rc;
@@ -555,10 +582,31 @@ extern "C" int tdnet_op_overlay(const float* in, int C, int h, int w, int H, int
     U8Input u;
     OverlayOutput o;
     const Nv12Layout nv = {pitch, uv_offset, standard};
-    TD_TRY(u8_build(u, Hs, Ws, H, W, nullptr, nullptr, who, nv12 ? &nv : nullptr));
+    TD_TRY(u8_build(u, nv12 ? src_view_nv12(Hs, Ws, nv) : src_view_rgb(Hs, Ws), Hs, Ws, H, W, nullptr, nullptr, who));
     int rc = overlay_build(o, palette_rgba, n_colours, who);
     if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
     if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, src, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, src, out, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
+// tdnet_op_overlay with a source view in place of its source arguments: out [h][w][3] of the view's rectangle, in the source's colour order
+extern "C" int tdnet_op_overlay_view(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* base, const tdnet_view* view,
+                                     const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
+    const char* who = "tdnet_op_overlay_view";
+    if (!base || !out) return td_fail("%s: base and out expected", who);
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(view_resolve(view, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    int rc = overlay_build(o, palette_rgba, n_colours, who, u.swap);
+    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, base, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, base, out, s);
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
     overlay_free(o);
     u8_free(u);

@@ -269,11 +269,15 @@ TD_KERNEL void k_labels_rgb(const unsigned char* __restrict__ labels, const int*
 // (y, x < Ws) and of chroma pairs (y >> 1, x >> 1) are addressed: nothing outside the source extent, none of the pitch padding or of the gap between
 // the planes.  (Why not ingest_stage_row: DESIGN.md 5.10.)  NV12 pixels are converted by ingest_nv12_rgb, the rule of "NV12 frames in".
 struct OverlaySrc {
-    const unsigned char* src;      // packed RGB [Hs][Ws][3], or the NV12 surface's base; any byte address
-    int pitch;                     // NV12: row pitch of both planes
+    const unsigned char* src;      // the frame's base (packed pixels, or the NV12 surface); any byte address
+    int pitch;                     // bytes per frame row (NV12: of both planes)
     unsigned uv_offset;            // NV12: < 2^31
     int yoff, cy, cub, cug, cvg, cvr;   // NV12: td_handle.h nv12_coeffs
+    int oy, ox;                    // a source view's origin: picture pixel (y, x) is frame pixel (oy + y, ox + x)
 };
+// The source forms: packed 3-byte pixels, an NV12 surface, packed 4-byte pixels (the 4th byte read with its pixel, never used).  A b g r source
+// needs no form of its own: the blend is per channel, so the host exchanges r and b in the colour table and the picture comes out b g r too.
+enum { TD_SRC_P24 = 0, TD_SRC_NV12 = 1, TD_SRC_P32 = 2 };
 // R and B share one multiply: the fields (c A + s (256 - A) + 128) <= 65408 of bits 0..15 and 16..31 do not carry into each other
 TD_DEV unsigned td_overlay_blend(unsigned lutw, unsigned s) {         // s = sR | sG << 8 | sB << 16
     const unsigned a = lutw >> 24, A = a + (a >> 7), B = 256u - A;
@@ -282,25 +286,43 @@ TD_DEV unsigned td_overlay_blend(unsigned lutw, unsigned s) {         // s = sR 
     return rb | g;
 }
 // s[e] = the source pixel (y, xa + e) as sR | sG << 8 | sB << 16 (a partial run repeats its last pixel, td_run_px); quad: the run is a whole group
-template <bool NV12>
+// VIEW = false: the whole frame, packed pixels tight -- the origin and the pitch are constants of the form, not arguments: what the entries that
+// predate the views reach compiles to what it was (measured: DESIGN.md 5.11)
+template <int SRC, bool VIEW>
 TD_DEV void td_overlay_src(const OverlaySrc& o, int y, long xa, long ow, bool quad, unsigned* s) {
-    if (NV12) {
-        const unsigned char* yr = o.src + (size_t)y * o.pitch;
-        const unsigned char* cr = o.src + o.uv_offset + (size_t)(y >> 1) * o.pitch;    // the chroma row: wave-uniform like y
+    const int oy = VIEW ? o.oy : 0, ox = VIEW ? o.ox : 0;
+    if (SRC == TD_SRC_NV12) {
+        const int gy = oy + y;
+        const unsigned char* yr = o.src + (size_t)gy * o.pitch + ox;
+        const unsigned char* cr = o.src + o.uv_offset + (size_t)(gy >> 1) * o.pitch;   // the chroma row: wave-uniform like y
         IngestNv12Args k = IngestNv12Args();                           // ingest_nv12_rgb reads the six constants only
         k.yoff = o.yoff; k.cy = o.cy; k.cub = o.cub; k.cug = o.cug; k.cvg = o.cvg; k.cvr = o.cvr;
         unsigned yw = 0;
         if (quad) __builtin_memcpy(&yw, yr + xa, 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const long x = td_run_px(xa, e, ow), cx = x & ~1L;
+            const long x = td_run_px(xa, e, ow), cx = (ox + x) & ~1L;
             const int Y = quad ? (int)((yw >> (8 * e)) & 255u) : (int)yr[x];
             int p[3];
             ingest_nv12_rgb(k, Y, cr[cx], cr[cx + 1], p);
             s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
         }
+    } else if (SRC == TD_SRC_P32) {
+        const unsigned char* r = o.src + (size_t)(oy + y) * o.pitch + (size_t)ox * 4;
+        if (quad) {
+            unsigned v[4];
+            __builtin_memcpy(v, r + 4 * xa, 16);                       // ONE 16-byte read: four whole pixels of the rectangle
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] = v[e] & 0xFFFFFFu;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned char* p = r + 4 * td_run_px(xa, e, ow);
+                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+            }
+        }
     } else {
-        const unsigned char* r = o.src + (size_t)y * ow * 3;           // ow == Ws
+        const unsigned char* r = VIEW ? o.src + (size_t)(oy + y) * o.pitch + (size_t)ox * 3 : o.src + (size_t)y * ow * 3;   // tight: pitch = 3 ow
         if (quad) {
             unsigned v[3];
             __builtin_memcpy(v, r + 3 * xa, 12);
@@ -320,7 +342,7 @@ TD_DEV void td_overlay_src(const OverlaySrc& o, int y, long xa, long ow, bool qu
 // The frame's last launch when the overlay is asked for: k_upsample_argmax_rgb's body (grid, lane split, class loop, argmax rule, store) + the
 // source pixel and the blend.  No branch on A: the blend with A = 0 returns the source.  The launch bound asks for the sibling's 5 waves per SIMD: without
 // it the allocator settles at 98 / 100 VGPRs and 4 waves, with it at 84 / 86 (k_upsample_argmax_rgb: 84), no spill either way.
-template <bool NV12>
+template <int SRC, bool VIEW>
 TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
                                          OverlaySrc o, unsigned char* __restrict__ out, int C, int h, int w, int H, int W, int oh, int ow) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
@@ -333,13 +355,13 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay(const float* _
     int bi[4] = {0, 0, 0, 0};
     td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
     unsigned s[4], px[4];
-    td_overlay_src<NV12>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
+    td_overlay_src<SRC, VIEW>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
 #pragma unroll
     for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
     td_rgb_store(orow, q, xa, xb, px);
 }
 // The same picture from a uint8 label map [H][W] the caller already holds (k_labels_rgb's body + the same)
-template <bool NV12>
+template <int SRC, bool VIEW>
 TD_KERNEL void k_labels_overlay(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
                                 OverlaySrc o, unsigned char* __restrict__ out, int W, int oh, int ow) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
@@ -350,7 +372,7 @@ TD_KERNEL void k_labels_overlay(const unsigned char* __restrict__ labels, const 
     if (xa >= xb) return;
     const unsigned char* lrow = labels + (size_t)ys[oy] * W;
     unsigned s[4], px[4];
-    td_overlay_src<NV12>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
+    td_overlay_src<SRC, VIEW>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
 #pragma unroll
     for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
     td_rgb_store(orow, q, xa, xb, px);

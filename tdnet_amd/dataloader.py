@@ -117,6 +117,99 @@ def rgb_to_nv12(img_u8, pitch=None, standard=0):
     return surf
 
 
+# ---- source views (include/tdnet.h "source views") -----------------------------------------------------------------------------------
+PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32, PIX_NV12 = 0, 1, 2, 3, 4
+PIX_BPP = {PIX_RGB24: 3, PIX_BGR24: 3, PIX_RGBA32: 4, PIX_BGRA32: 4}
+PIX_BGR = (PIX_BGR24, PIX_BGRA32)                        # the colour bytes are b g r: the overlay comes out b g r too
+
+
+class SourceView:
+    """A rectangle of a pitched frame in one of the five pixel formats (tdnet_view).  height, width: the WHOLE frame; pitch 0: tight
+    (width * bpp; NV12: 2 * ceil(width / 2)); crop = (y, x, h, w) or None: the whole frame; NV12: standard, and uv_offset None = height * pitch.
+    Nothing is validated here beyond what the derived values need: the library's tdnet_set_input_view is the judge."""
+
+    def __init__(self, format, height, width, pitch=0, crop=None, standard=0, uv_offset=None):
+        self.format, self.height, self.width, self.standard = int(format), int(height), int(width), int(standard)
+        if self.format not in (PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32, PIX_NV12):
+            raise ValueError("SourceView: format %r is not one of PIX_* (0..4)" % (format,))
+        self.pitch = int(pitch)
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        if self.crop is not None and len(self.crop) != 4:
+            raise ValueError("SourceView: crop is (y, x, height, width)")
+        self.uv_offset = None if uv_offset is None else int(uv_offset)
+
+    @property
+    def nv12(self):
+        return self.format == PIX_NV12
+
+    @property
+    def bpp(self):
+        return 1 if self.nv12 else PIX_BPP[self.format]
+
+    @property
+    def row_pitch(self):
+        """The pitch in force: the given one, or the tight one."""
+        return self.pitch if self.pitch else (2 * ((self.width + 1) // 2) if self.nv12 else self.width * self.bpp)
+
+    @property
+    def uv(self):
+        """NV12: the UV plane's offset in force (None or 0: height * pitch, as the C ABI reads 0)."""
+        return self.uv_offset if self.uv_offset else self.height * self.row_pitch
+
+    @property
+    def rect(self):
+        """(y, x, h, w) of the rectangle in force."""
+        return (0, 0, self.height, self.width) if self.crop is None or self.crop == (0, 0, 0, 0) else self.crop
+
+    @property
+    def size(self):
+        return self.rect[2:]
+
+    def key(self):
+        return (self.format, self.height, self.width, self.row_pitch) + self.rect + ((self.standard, self.uv) if self.nv12 else (0, 0))
+
+    def __repr__(self):
+        return "SourceView(format=%d, %dx%d, pitch=%d, rect=%r)" % (self.format, self.height, self.width, self.row_pitch, self.rect)
+
+
+def view_extent(view):
+    """Bytes from the frame's base to the end of its last pixel (NV12: of its last chroma pair): nothing behind them is ever read."""
+    if view.nv12:
+        return nv12_extent(view.height, view.width, view.row_pitch, view.uv)
+    return (view.height - 1) * view.row_pitch + view.width * view.bpp
+
+
+def view_to_rgb_u8(buf, view):
+    """The oracle of the library's source views: the bytes of a frame -> uint8 RGB [h, w, 3] of the view's rectangle.  Packed formats: the three
+    colour bytes of every pixel of the rectangle, reordered to r g b.  NV12: nv12_to_rgb_u8 of the WHOLE surface, then sliced -- chroma goes by
+    the frame's coordinates, so an odd origin shifts its phase."""
+    s = np.asarray(buf).reshape(-1)
+    assert s.dtype == np.uint8 and s.size >= view_extent(view), (s.dtype, s.size, view_extent(view))
+    y, x, h, w = view.rect
+    assert 0 <= y and 0 <= x and h >= 1 and w >= 1 and y + h <= view.height and x + w <= view.width
+    if view.nv12:
+        return np.ascontiguousarray(nv12_to_rgb_u8(s, view.height, view.width, view.row_pitch, view.uv, view.standard)[y:y + h, x:x + w])
+    bpp, pitch = view.bpp, view.row_pitch
+    assert pitch >= view.width * bpp
+    idx = ((y + np.arange(h))[:, None, None] * pitch + (x + np.arange(w))[None, :, None] * bpp +
+           (np.array([2, 1, 0]) if view.format in PIX_BGR else np.arange(3))[None, None, :])
+    return s[idx]
+
+
+def pack_view(rgb_frame, view, fill=0):
+    """A host generator for the packed formats: the bytes [0, view_extent) of the WHOLE frame rgb_frame [height, width, 3] in the view's format and
+    pitch; pitch padding and the x bytes of the 32-bit formats hold `fill`."""
+    img = np.asarray(rgb_frame)
+    assert not view.nv12 and img.dtype == np.uint8 and img.shape == (view.height, view.width, 3)
+    bpp, pitch = view.bpp, view.row_pitch
+    assert pitch >= view.width * bpp
+    out = np.full(view_extent(view), fill, np.uint8)
+    idx = (np.arange(view.height)[:, None, None] * pitch + np.arange(view.width)[None, :, None] * bpp +
+           (np.array([2, 1, 0]) if view.format in PIX_BGR else np.arange(3))[None, None, :])
+    out[idx] = img
+    return out
+
+
 def nearest_index(n_src, n_dst):
     """Source index per destination index of the nearest-sample resize of the label map (test.py:64, cv2.INTER_NEAREST): int64 [n_dst] =
     min(int64(o * (n_src / n_dst)), n_src - 1) -- the quotient first, in float64, then the product, then truncation.  This is the project's rule:

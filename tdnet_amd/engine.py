@@ -19,6 +19,16 @@ def _ptr(a):
     return a.ctypes.data
 
 
+def view_struct(view):
+    """_capi.TdnetView of a dataloader.SourceView, as the caller stated it (0 / None stay the C ABI's defaults)."""
+    t = _capi.TdnetView()
+    t.format, t.height, t.width, t.pitch, t.standard = view.format, view.height, view.width, view.pitch, view.standard
+    if view.crop is not None:
+        t.crop_y, t.crop_x, t.crop_height, t.crop_width = view.crop
+    t.uv_offset = 0 if view.uv_offset is None else view.uv_offset
+    return t
+
+
 class Engine:
     def __init__(self, model, backbone, nclass, height, width, device=0, lib=None, opts=None, _shared_from=None, arch=None):
         """opts: None (library defaults) or a dict of tdnet_opts fields (winograd=, precision=, pipeline=, ...): per handle.
@@ -104,7 +114,7 @@ class Engine:
         m = None if key[2] is None else (ctypes.c_double * 3)(*key[2])
         sd = None if key[3] is None else (ctypes.c_double * 3)(*key[3])
         self.lib.check(self.lib.tdnet_set_input_u8(self.h, key[0], key[1], m, sd))
-        self._u8_key, self._nv12_key = key, None                       # ONE byte-input configuration per handle
+        self._u8_key, self._nv12_key, self._view_key = key, None, None   # ONE byte-input configuration per handle
 
     def set_input_nv12(self, src_height, src_width, pitch, uv_offset=None, standard=0, mean=None, std=None):
         """Frames will arrive as NV12 surfaces (include/tdnet.h "NV12 frames in"): the byte entries (forward_u8, ...) then read their image
@@ -122,7 +132,24 @@ class Engine:
         m = None if key[5] is None else (ctypes.c_double * 3)(*key[5])
         sd = None if key[6] is None else (ctypes.c_double * 3)(*key[6])
         self.lib.check(self.lib.tdnet_set_input_nv12(self.h, key[0], key[1], key[2], key[3], key[4], m, sd))
-        self._nv12_key, self._u8_key = key, None
+        self._nv12_key, self._u8_key, self._view_key = key, None, None
+
+    def set_input_view(self, view, mean=None, std=None):
+        """Frames will arrive as a source view (include/tdnet.h "source views"; `view`: a dataloader.SourceView): the byte entries then read
+        their image pointer as the base of the WHOLE frame and take the view's rectangle of it, until another set_input_* call.  A configuration
+        call (it may synchronise); repeating it with equal arguments does nothing."""
+        key = (view.key(), None if mean is None else tuple(float(v) for v in mean), None if std is None else tuple(float(v) for v in std))
+        if getattr(self, "_view_key", None) == key:
+            return
+        for v in key[1:]:
+            if v is not None and len(v) != 3:
+                raise _capi.TdnetError("set_input_view: mean and std are three numbers each")
+        if view.uv_offset is not None and view.uv_offset < 0:
+            raise _capi.TdnetError("set_input_view: uv_offset must not be negative")
+        m = None if key[1] is None else (ctypes.c_double * 3)(*key[1])
+        sd = None if key[2] is None else (ctypes.c_double * 3)(*key[2])
+        self.lib.check(self.lib.tdnet_set_input_view(self.h, ctypes.byref(view_struct(view)), m, sd))
+        self._view_key, self._u8_key, self._nv12_key = key, None, None
 
     def forward_u8(self, img_ptr, pos_id, logits_ptr, stream=None):
         self.lib.check(self.lib.tdnet_forward_u8(self.h, _ptr(img_ptr), int(pos_id), _ptr(logits_ptr), stream))

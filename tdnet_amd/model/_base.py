@@ -287,14 +287,41 @@ class _TDNetBase(nn.Module):
     # the network size and normalises on the device, bit-identically to cityscapesLoader (resize_linear_u8 + normalise), so
     # forward_u8(frame_bytes) == forward(loader_tensor).  The NETWORK size is the one the handle was built for: by ensure_engine(H, W, device)
     # or an earlier frame; a model without a handle takes it from in_size=(H, W) (as cityscapesLoader does).
-    def _check_frame_u8(self, img, pos_id, in_size):
+    # view: a dataloader.SourceView (include/tdnet.h "source views") -- img_u8 is then a contiguous uint8 tensor [N, nbytes], nbytes >= view_extent(view):
+    # N WHOLE frames in the view's format and pitch, of which the library reads the view's rectangle (b g r or 4-byte pixels, a crop, an NV12 surface
+    # with a display rectangle), bit-identically to forward_u8(dataloader.view_to_rgb_u8(frame, view)).
+    def _check_frame_view(self, img, view):
+        """The error classes of _check_frame_u8 for a batch of whole frames read through `view`; nothing is built before it passes."""
+        from ..dataloader import SourceView, view_extent
+        if not isinstance(view, SourceView):
+            raise RuntimeError("view must be a dataloader.SourceView, got %s" % type(view).__name__)
         if not torch.is_tensor(img) or img.dtype != torch.uint8:
+            raise RuntimeError("expected a torch.uint8 frame tensor [N,nbytes], got %s" % (img.dtype if torch.is_tensor(img) else type(img).__name__))
+        if img.dim() != 2 or img.shape[0] < 1:
+            raise RuntimeError("expected a uint8 frame tensor [N,nbytes] (whole frames read through the view) with N >= 1, got shape %s" % (tuple(img.shape),))
+        if not img.is_contiguous():
+            raise RuntimeError("expected a CONTIGUOUS uint8 frame tensor [N,nbytes]: the view's pitch describes the rows")
+        y, x, h, w = view.rect
+        if view.height < 1 or view.width < 1 or h < 1 or w < 1 or y < 0 or x < 0 or y + h > view.height or x + w > view.width:
+            raise RuntimeError("the view's rectangle (y, x, h, w) = %r is not inside its %d x %d frame" % (view.rect, view.height, view.width))
+        row = 2 * ((view.width + 1) // 2) if view.nv12 else view.width * view.bpp
+        if view.row_pitch < row:
+            raise RuntimeError("the view's pitch %d is below the %d bytes a row of %d pixels holds" % (view.row_pitch, row, view.width))
+        if view.nv12 and view.uv < view.height * view.row_pitch:
+            raise RuntimeError("the view's uv_offset %d is inside the Y plane (%d rows of pitch %d)" % (view.uv, view.height, view.row_pitch))
+        if int(img.shape[1]) < view_extent(view):
+            raise RuntimeError("a frame tensor of %d bytes per sample is below the %d bytes the view's frame needs" % (img.shape[1], view_extent(view)))
+
+    def _check_frame_u8(self, img, pos_id, in_size, view=None):
+        if view is not None:
+            self._check_frame_view(img, view)
+        elif not torch.is_tensor(img) or img.dtype != torch.uint8:
             raise RuntimeError("expected a torch.uint8 image tensor [N,Hs,Ws,3], got %s" % (img.dtype if torch.is_tensor(img) else type(img).__name__))
-        if img.dim() != 4 or img.shape[3] != 3:
+        if view is None and (img.dim() != 4 or img.shape[3] != 3):
             raise RuntimeError("expected a uint8 image tensor [N,Hs,Ws,3] (HWC, RGB), got shape %s" % (tuple(img.shape),))
         if img.device.type != "cuda":
             raise TdnetError("tdnet_amd runs on MI355X only: got a %s tensor (no CPU fallback)" % img.device.type)
-        if img.shape[0] < 1 or img.shape[1] < 1 or img.shape[2] < 1:
+        if view is None and (img.shape[0] < 1 or img.shape[1] < 1 or img.shape[2] < 1):
             raise RuntimeError("expected a uint8 image tensor [N,Hs,Ws,3] with N, Hs, Ws >= 1")
         if pos_id not in range(self.path_num):
             raise RuntimeError("pos_id must be t mod %d" % self.path_num)
@@ -304,42 +331,48 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("the network size is not known yet: pass in_size=(H, W), or call ensure_engine(H, W, device) first")
         return self._engine_key[0], self._engine_key[1]
 
-    def _u8_call(self, img, size, call, mean, std, nv12=None):
-        """nv12: None, or (Hs, Ws, pitch, uv_offset, standard) -- img is then a batch of NV12 surfaces and the handles are configured for those."""
-        Hs, Ws = int(img.shape[1]), int(img.shape[2])
+    def _u8_call(self, img, size, call, mean, std, nv12=None, view=None):
+        """nv12: None, or (Hs, Ws, pitch, uv_offset, standard) -- img is then a batch of NV12 surfaces and the handles are configured for those.
+        view: None, or a SourceView -- img is then a batch of whole frames [N, nbytes] read through it."""
+        Hs, Ws = (0, 0) if view is not None else (int(img.shape[1]), int(img.shape[2]))
 
         def one(i, eng, s):
-            if nv12 is None:
+            if view is not None:
+                eng.set_input_view(view, mean, std)
+            elif nv12 is None:
                 eng.set_input_u8(Hs, Ws, mean, std)                    # (re)configured when the source size changes; a no-op otherwise
             else:
                 eng.set_input_nv12(*nv12, mean=mean, std=std)
             call(i, eng, s)
         self._for_each_sample(img, one, size)
 
-    def forward_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+    def forward_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
         """forward() on the decoded bytes: logits [N, nclass, H, W] at the network size."""
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         out = torch.empty((img.shape[0], self.nclass, H, W), device=img.device, dtype=torch.float32)
-        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, view=view)
         return out
 
-    def forward_labels_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+    def forward_labels_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
         """forward_labels() on the decoded bytes, labels as uint8 [N, H, W] (the same labels: nclass <= 256)."""
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8)
-        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std)
+        self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, view=view)
         return out
 
-    def encode_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+    def encode_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
         """encode() on the decoded bytes."""
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         if img_u8.shape[0] != 1:
             raise RuntimeError("encode_u8(): the split frame serves ONE stream (batch size 1)")
         img = img_u8.contiguous()
         eng = self._engine_for(H, W, img.device.index or 0, 1)
-        eng.set_input_u8(int(img.shape[1]), int(img.shape[2]), mean, std)
+        if view is not None:
+            eng.set_input_view(view, mean, std)
+        else:
+            eng.set_input_u8(int(img.shape[1]), int(img.shape[2]), mean, std)
         self._pending_shape = (H, W, img.device)
         eng.encode_u8(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
@@ -490,17 +523,17 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, one)
         return out
 
-    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None):
+    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None, view=None):
         """forward_labels_u8() with the colour map [N, oh, ow, 3] uint8 in place of the label map: bytes in, picture out."""
         self._rgb_size(out_size)
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
 
         def one(i, eng, s):
             eng.set_output_rgb(out.shape[1], out.shape[2], pal)
             eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
-        self._u8_call(img, (H, W), one, mean, std)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
 
     def labels_rgb(self, labels_u8, out_size, palette=None):
@@ -538,17 +571,17 @@ class _TDNetBase(nn.Module):
         out[:, 3] = np.rint(255.0 * a).astype(np.uint8)
         return out
 
-    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None):
+    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None, view=None):
         """forward_labels_u8() with the overlay [N, Hs, Ws, 3] uint8 in place of the label map: the frame's bytes in, the tinted frame out."""
         pal = self._palette_rgba(palette, alpha)
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
-        out = torch.empty(tuple(img.shape), device=img.device, dtype=torch.uint8)
+        out = torch.empty(tuple(img.shape) if view is None else (img.shape[0],) + tuple(view.size) + (3,), device=img.device, dtype=torch.uint8)   # a view: [N, h, w, 3] in the source's colour order
 
         def one(i, eng, s):
             eng.set_output_overlay(pal)
             eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
-        self._u8_call(img, (H, W), one, mean, std)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
 
     def forward_overlay_nv12(self, surf, pos_id, src_size, in_size, palette=None, alpha=0.5, uv_offset=None, standard=0, mean=None, std=None):
@@ -578,7 +611,7 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("%s: expected %d surfaces, got %d" % (who, n, src.shape[0]))
         return src.contiguous(), (nv[0], nv[1]), nv
 
-    def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None):
+    def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None, view=None):
         """uint8 labels [N, H, W] (CUDA) of this model blended over their source frames -> [N, Hs, Ws, 3]; src: uint8 [N, Hs, Ws, 3], or with
         src_size=(Hs, Ws) NV12 surfaces [N, rows, pitch].  After forward_labels_conf_u8 with a reject_label outside the palette: the overlay over
         the accepted pixels only."""
@@ -587,11 +620,19 @@ class _TDNetBase(nn.Module):
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
             raise RuntimeError("labels_overlay(): expected uint8 labels [N, %d, %d]" % tuple(self._engine_key[:2]))
         labels = labels_u8.contiguous()
-        img, (Hs, Ws), nv = self._overlay_source("labels_overlay()", src, labels.shape[0], src_size, uv_offset, standard)
+        if view is not None:                                           # src: whole frames [N, nbytes] read through the view; the overlay of its rectangle
+            self._check_frame_view(src, view)
+            if src.shape[0] != labels.shape[0]:
+                raise RuntimeError("labels_overlay(): expected %d frames, got %d" % (labels.shape[0], src.shape[0]))
+            img, (Hs, Ws), nv = src, view.size, None
+        else:
+            img, (Hs, Ws), nv = self._overlay_source("labels_overlay()", src, labels.shape[0], src_size, uv_offset, standard)
         pal = self._palette_rgba(palette, alpha)
         out = torch.empty((labels.shape[0], Hs, Ws, 3), device=labels.device, dtype=torch.uint8)
         eng = self._engine
-        if nv is None:
+        if view is not None:
+            eng.set_input_view(view, mean, std)
+        elif nv is None:
             eng.set_input_u8(Hs, Ws, mean, std)
         else:
             eng.set_input_nv12(*nv, mean=mean, std=std)
@@ -634,10 +675,10 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, one)
         return out
 
-    def forward_score_u8(self, img_u8, gt_u8, pos_id=0, in_size=None, gt_map=None, return_labels=False, mean=None, std=None):
+    def forward_score_u8(self, img_u8, gt_u8, pos_id=0, in_size=None, gt_map=None, return_labels=False, mean=None, std=None, view=None):
         """forward_labels_u8() with the frame scored on the device: bytes in, counts added; the uint8 labels [N, H, W] if return_labels."""
         self._check_gt_type(gt_u8)
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         gt = self._check_gt(gt_u8, img.shape[0], H, W, img.device)
         out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8) if return_labels else None
@@ -645,7 +686,7 @@ class _TDNetBase(nn.Module):
         def one(i, eng, s):
             eng.set_score(gt_map)
             eng.forward_u8_score(img[i].data_ptr(), pos_id, gt[i].data_ptr(), None if out is None else out[i].data_ptr(), s)
-        self._u8_call(img, (H, W), one, mean, std)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
 
     def score_labels(self, labels_u8, gt_u8, gt_map=None):
@@ -719,9 +760,9 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, one)
         return out, conf
 
-    def forward_labels_conf_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None):
+    def forward_labels_conf_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
         """forward_labels_u8() with the confidence map: bytes in, (labels uint8 [N, H, W], conf uint8 [N, H, W]) out."""
-        H, W = self._check_frame_u8(img_u8, pos_id, in_size)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         shape = (img.shape[0], H, W)
         out, conf = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
@@ -729,7 +770,7 @@ class _TDNetBase(nn.Module):
         def one(i, eng, s):
             eng.set_confidence(*self._confidence)
             eng.forward_u8_labels_conf(img[i].data_ptr(), pos_id, out[i].data_ptr(), conf[i].data_ptr(), s)
-        self._u8_call(img, (H, W), one, mean, std)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
         return out, conf
 
     def logits_conf(self, logits):

@@ -23,6 +23,8 @@ saves it at the network size as a grey PNG DIR/folder/name beside the picture; `
 label 255 and therefore decode_segmap's grey (255, 255, 255) in the picture.  Either switch selects the frame-by-frame loop's confidence form.
 `--overlay ALPHA` (0..1, with `--u8` or `--nv12`) has the frame's last kernel blend the class colours over the frame's own bytes and writes that
 SOURCE-size picture instead of the quarter-size colour map (include/tdnet.h "overlay out"); with `--min_conf` the rejected pixels show the bare frame.
+`--crop Y,X,H,W` (with `--u8` or `--nv12`) uploads the frames WHOLE and has the device take that rectangle of them in the frame's first launch
+(include/tdnet.h "source views"): the result is the one of the pre-cropped frames; with `--overlay` the picture is the rectangle's.
 """
 import argparse
 import os
@@ -66,6 +68,16 @@ def test(args):
     nv12_std = int(getattr(args, "nv12_standard", 0) or 0)
     if nv12 and u8:
         raise SystemExit("--nv12 and --u8 are two forms of the byte input: choose one")
+    crop = getattr(args, "crop", None)
+    if crop is not None:                                               # checked before anything is loaded
+        if not (u8 or nv12):
+            raise SystemExit("--crop takes a rectangle of the frame's own bytes: give --u8 or --nv12 with it")
+        try:
+            crop = tuple(int(v) for v in str(crop).split(","))
+        except ValueError:
+            crop = ()
+        if len(crop) != 4 or min(crop[:2]) < 0 or min(crop[2:]) < 1:
+            raise SystemExit("--crop: Y,X,H,W expected (the rectangle's origin and size in frame pixels), got %r" % (args.crop,))
     rgb = bool(getattr(args, "rgb", False))
     overlay = getattr(args, "overlay", None)
     if overlay is not None:                                            # checked before anything is loaded
@@ -146,18 +158,30 @@ def test(args):
     def save_rgb(picture, img_name, folder, ori_size):                 # --rgb: the device wrote the picture
         write_png(np.squeeze(picture, axis=0), img_name, folder)
 
-    def colour_map(image, pos_id, ori_size, src_size=None):            # [1, oh, ow, 3] uint8 on the device
-        out_size = (ori_size[1] // 4, ori_size[0] // 4)
+    def through_view(image, src_size):
+        """--crop: the WHOLE frame as bytes [1, nbytes] and the view that takes the rectangle of it (the frame is uploaded as it is; the byte
+        methods read the rectangle in the frame's first launch, the overlay in its last)."""
+        from tdnet_amd.dataloader import PIX_NV12, PIX_RGB24, SourceView
         if nv12:
+            v = SourceView(PIX_NV12, src_size[0], src_size[1], pitch=int(image.shape[2]), crop=crop, standard=nv12_std)
+        else:
+            v = SourceView(PIX_RGB24, int(image.shape[1]), int(image.shape[2]), crop=crop)
+        return image.reshape(1, -1), v
+
+    nvp, byte = nv12 and crop is None, u8 or crop is not None          # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
+
+    def colour_map(image, pos_id, ori_size, src_size=None, view=None):   # [1, oh, ow, 3] uint8 on the device
+        out_size = (ori_size[1] // 4, ori_size[0] // 4)
+        if nvp:
             return model.forward_rgb_nv12(image, pos_id, src_size, (H, W), out_size, standard=nv12_std)
-        if u8:
-            return model.forward_rgb_u8(image, pos_id, (H, W), out_size)
+        if byte:
+            return model.forward_rgb_u8(image, pos_id, (H, W), out_size, view=view)
         return model.forward_rgb(image, pos_id, out_size)
 
-    def overlay_picture(image, pos_id, src_size=None):                 # --overlay: [1, Hs, Ws, 3] uint8 on the device, at the source's size
-        if nv12:
+    def overlay_picture(image, pos_id, src_size=None, view=None):      # --overlay: [1, Hs, Ws, 3] uint8 on the device, at the source's (--crop: the rectangle's) size
+        if nvp:
             return model.forward_overlay_nv12(image, pos_id, src_size, (H, W), alpha=overlay, standard=nv12_std)
-        return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay)
+        return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay, view=view)
 
     timer, i = 0.0, -1
     with torch.no_grad():
@@ -171,22 +195,25 @@ def test(args):
             gt_feed = iter(DevicePrefetcher(gts, device)) if gts is not None else None   # the ground truth travels with the frame
             for i, (image, img_name, folder, ori_size, *rest) in enumerate(DevicePrefetcher(vid_seq.data, device)):
                 src_size = rest[0] if nv12 else None                   # an NV12 item carries the picture's (Hs, Ws)
+                view = None
+                if crop is not None:
+                    image, view = through_view(image, src_size)
                 if gt_feed is not None:
                     gt = next(gt_feed)[0]
-                    if nv12:
+                    if nvp:
                         labels = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
-                    elif u8:
-                        labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
+                    elif byte:
+                        labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, view=view)
                     else:
                         labels = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
                 elif rgb:
-                    labels = colour_map(image, i % path_num, ori_size, src_size)
+                    labels = colour_map(image, i % path_num, ori_size, src_size, view)
                 elif overlay is not None:
-                    labels = overlay_picture(image, i % path_num, src_size)
-                elif nv12:
+                    labels = overlay_picture(image, i % path_num, src_size, view)
+                elif nvp:
                     labels = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
-                    labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model.forward_labels(image, pos_id=i % path_num)
+                    labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W), view=view) if byte else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
                     (save_rgb if rgb or overlay is not None else save)(pred, *tag)
             for tag, pred in down.drain():
@@ -203,33 +230,36 @@ def test(args):
         for i, (image, img_name, folder, ori_size, *rest) in enumerate(vid_seq.data):
             src_size = rest[0] if nv12 else None
             image = image.to(device)
+            view = None
+            if crop is not None:
+                image, view = through_view(image, src_size)
             gt = gts[i][0].to(device) if gts is not None else None
             torch.cuda.synchronize()
             start_time = timeit.default_timer()
-            if gt is not None and nv12:
+            if gt is not None and nvp:
                 output = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
-            elif gt is not None and u8:
-                output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True)
+            elif gt is not None and byte:
+                output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, view=view)
             elif gt is not None:
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
             elif rgb:
-                output = colour_map(image, i % path_num, ori_size, src_size)
+                output = colour_map(image, i % path_num, ori_size, src_size, view)
             elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
-                if nv12:
+                if nvp:
                     l8, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
-                    l8, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W))
-                output = model.labels_overlay(l8, image, alpha=overlay, src_size=src_size, standard=nv12_std)
+                    l8, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), view=view)
+                output = model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, view=view)
             elif overlay is not None:
-                output = overlay_picture(image, i % path_num, src_size)
-            elif with_conf and nv12:
+                output = overlay_picture(image, i % path_num, src_size, view)
+            elif with_conf and nvp:
                 output, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
-            elif nv12:
+            elif nvp:
                 output = model.forward_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
             elif with_conf:
-                output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W)) if u8 else model.forward_labels_conf(image, i % path_num)
+                output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), view=view) if byte else model.forward_labels_conf(image, i % path_num)
             else:
-                output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W)) if u8 else model(image, pos_id=i % path_num)
+                output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W), view=view) if byte else model(image, pos_id=i % path_num)
             torch.cuda.synchronize()
             elapsed_time = timeit.default_timer() - start_time
             if i > 5:
@@ -276,4 +306,5 @@ if __name__ == "__main__":
     parser.add_argument("--conf", nargs="?", type=str, default=None, help="directory for each frame's confidence map (grey PNG at the network size; 255 = certain)")
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
+    parser.add_argument("--crop", nargs="?", type=str, default=None, help="with --u8 or --nv12: Y,X,H,W -- the frames are uploaded whole and the rectangle is taken on the device, in the frame's first launch (a source view)")
     test(parser.parse_args())
