@@ -326,6 +326,42 @@ int  tdnet_forward_u8_overlay(tdnet_t* h, const uint8_t* img_dev, int pos_id, ui
 /* the unfused form: the overlay of a uint8 label map [H,W] the caller already holds over the source img_dev; after tdnet_forward_u8_labels_conf it is
  * the overlay over the ACCEPTED pixels only (given a reject_label >= n_colours)                                                               */
 int  tdnet_labels_overlay(tdnet_t* h, const uint8_t* labels_u8_dev, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
+/* ---- destination views --------------------------------------------------------------------------------------------
+ * The mirror of "source views": the picture a frame's LAST kernel writes -- the colour map or the overlay -- goes straight into a rectangle of a
+ * pitched RGB / BGR / RGBA / BGRA frame or of an NV12 surface, the forms a compositor or an encoder takes, instead of a contiguous [h][w][3] block.
+ * While a destination view is in force the picture pointer of EVERY picture entry (tdnet_forward_rgb, tdnet_forward_u8_rgb, tdnet_propagate_rgb,
+ * tdnet_labels_rgb, tdnet_forward_u8_overlay, tdnet_propagate_overlay, tdnet_labels_overlay) is the destination frame's `base`, at any byte address.
+ * The same picture, the same FIFO step, the same tdnet_last_launch_count; the entries still only enqueue and work inside a hipGraph capture.  Label,
+ * logit, score and confidence entries are unaffected.  Let P[y][x] = (R, G, B) be the picture the entry writes without a view, as true r, g, b (an
+ * overlay over a b g r source view writes the bytes B, G, R today).  The view's rectangle h x w must be the picture's size -- out_height x out_width
+ * for the colour map, the source (rectangle's) size for the overlay: nothing is resized.  The configuration calls are independent of each other's
+ * order, so the FRAME entry checks this: on a mismatch it fails without enqueueing, naming both sizes; a pending encoded frame stays pending.
+ *   packed     at base + (crop_y + y) * pitch + (crop_x + x) * bpp the three colour bytes in the order the DESTINATION format names (the source's
+ *              order no longer decides); the x byte of the 32-bit formats is written as 255.
+ *   NV12       crop_y and crop_x must be even (the rectangle starts on the chroma grid); h and w may be odd.  K = rint(c * 2^20) of
+ *                standard           yoff   Y: r, g, b            U: r, g, b                  V: r, g, b
+ *                0 BT601 limited    16     .257 .504 .098        -.148 -.291 .439            .439 -.368 -.071
+ *                1 BT709 limited    16     .183 .614 .062        -.101 -.339 .439            .439 -.399 -.040
+ *                2 BT601 full        0     .299 .587 .114        -.168736 -.331264 .5        .5 -.418688 -.081312
+ *                3 BT709 full        0     .2126 .7152 .0722     -.114572 -.385428 .5        .5 -.454153 -.045847
+ *              in int32 with arithmetic shifts:
+ *                Yplane[crop_y + y][crop_x + x] = clamp8((KYR R + KYG G + KYB B + (yoff << 20) + (1 << 19)) >> 20)
+ *              and for the chroma pair (j, i) of the FRAME: S = the per-channel sum of P over the rectangle's pixels whose frame coordinates
+ *              (Y >> 1, X >> 1) are (j, i), n in {1, 2, 4} their number, m = 4 / n,
+ *                U = clamp8((m (KUR S_R + KUG S_G + KUB S_B) + (128 << 22) + (1 << 21)) >> 22),  V likewise with the V row.
+ *              Every sum stays below 2^31 in magnitude (m S <= 1020, the positive coefficients of a row sum to <= 0.5).
+ *   memory     only the bytes of the rectangle's pixels are written (NV12: its Y bytes and the chroma pairs covering it): pitch padding, the plane
+ *              gap, the rest of the frame and everything outside [base, base + extent) keep their bytes.  The destination FRAME's extent must not
+ *              overlap the source frame's extent: the overlay entries check this on the host and fail without enqueueing.  In-place compositing is
+ *              not supported.
+ * tdnet_set_output_view: configuration like its siblings (not a frame call; idempotent for equal arguments; per handle: a tdnet_create_shared handle
+ * has its own; independent of the order of the other tdnet_set_* calls).  It allocates nothing: the view travels as kernel arguments, read when an
+ * entry enqueues (a captured graph replays the view it was captured with).  v = NULL: contiguous [h][w][3] again, byte for byte.  Fails -- leaving
+ * the previous configuration in force and the FIFO alone, the message naming the offending field -- on a handle that is not finalized, a format outside
+ * 0..4, frame or rectangle sizes below 1, a rectangle not inside the frame, a negative origin, a pitch below a row's bytes, a non-zero reserved, a
+ * non-zero standard / uv_offset on a packed format, the NV12 conditions of tdnet_set_input_nv12 (pitch, uv_offset, standard, extent), an odd NV12
+ * origin, and a rectangle of more than 65535 rows.                                                                                            */
+int  tdnet_set_output_view(tdnet_t* h, const tdnet_view* v /* NULL = contiguous [h][w][3] */);
 /* ---- score out ----------------------------------------------------------------------------------------------------
  * What the reference's validation loop does on the host behind the labels (Training/validate.py:59-70, ptsemseg/metrics.py:12-21): the
  * n_class x n_class confusion matrix, hist[g][l] += 1 over the pixels with 0 <= g < n_class -- counted by the frame's LAST kernel instead, into

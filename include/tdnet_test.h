@@ -151,6 +151,12 @@ int tdnet_op_overlay(const float* in_dev, int C, int h, int w, int H, int W, con
 /* tdnet_op_overlay with a source view in place of its source arguments: out_dev [h,w,3] of the view's rectangle h x w, in the source's colour order. */
 int tdnet_op_overlay_view(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* base_dev, const tdnet_view* view,
                           const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
+/* The picture into a destination view (include/tdnet.h "destination views"), through exactly the kernels the frame entries launch with one in force:
+ * of low-resolution logits [C,h,w] (labels_u8_dev == NULL) or of a uint8 label map [H,W] (in_dev, C, h, w are then ignored); the overlay over the source
+ * view (src_base_dev, src_view; palette [n_colours][4] r g b a on the host) or, src_base_dev == NULL, the colour map oh x ow (palette [n_colours][3];
+ * src_view ignored).  dst_base_dev: the destination frame's base, at any byte address; the view's rectangle must be the picture's size.           */
+int tdnet_op_picture_view(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* palette, int n_colours,
+                          const uint8_t* src_base_dev, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base_dev, const tdnet_view* dst_view, void* stream);
 /* cm_dev [C,C] uint64 -- ACCUMULATED into, not cleared -- += the confusion counts (include/tdnet.h "score out") of gt_dev [H,W] uint8 (any byte
  * address) through gt_map (256 bytes on the host, NULL = identity) against the labels of low-resolution logits [C,h,w] upsampled to [H,W], through
  * tdnet_forward_score's last kernel (labels_in_u8_dev == NULL; it also writes the uint8 label map if labels_u8_dev != NULL), or against a uint8

@@ -93,6 +93,7 @@ SYMBOLS = {
     "tdnet_forward_u8_overlay": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_labels_overlay": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_propagate_overlay": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_output_view": (ctypes.c_int, [c_void_p, c_view_p]),
     "tdnet_set_score": (ctypes.c_int, [c_void_p, c_void_p]),
     "tdnet_forward_score": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_forward_u8_score": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
@@ -160,6 +161,8 @@ TEST_SYMBOLS = {
     "tdnet_op_stem_image_view": (ctypes.c_long, [c_void_p, c_view_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                  ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "tdnet_op_overlay_view": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_view_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_picture_view": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_view_p, ctypes.c_int, ctypes.c_int,
+                                             c_void_p, c_view_p, c_void_p]),
     "tdnet_op_upsample_argmax": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_rgb": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_op_overlay": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_size_t, ctypes.c_int, c_void_p, ctypes.c_int,

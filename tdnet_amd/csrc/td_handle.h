@@ -279,6 +279,16 @@ struct OverlayOutput {
     int* xs = nullptr;                                                 // [Ws]: nearest_index(W, Ws)
     size_t bytes = 0;
 };
+// The destination view of a handle (tdnet_set_output_view): where the picture entries write -- the rectangle h x w at (oy, ox) of a frame fh x fw of
+// `format` whose rows are `pitch` bytes apart.  Plain host state (the kernels take it as arguments): nothing is allocated.  Per handle, like U8Input.
+struct DstOutput {
+    bool set = false;
+    int format = 0, bpp = 3;                                           // TDNET_PIX_*; bytes per packed pixel
+    bool swap = false;                                                 // packed: the colour bytes are b g r
+    int fh = 0, fw = 0, oy = 0, ox = 0, h = 0, w = 0, pitch = 0, standard = 0;
+    size_t uv_offset = 0, extent = 0;                                  // NV12; the bytes [base, base + extent) of the whole frame: nothing else is written
+    int yoff = 0, ky[3] = {0, 0, 0}, ku[3] = {0, 0, 0}, kv[3] = {0, 0, 0};   // NV12: nv12_forward_coeffs, rows over r, g, b
+};
 // The score output of a handle (tdnet_set_score): the device confusion matrix the score kernels add into and the 256-byte ground-truth map they
 // read.  Per handle, like U8Input.
 struct ScoreOutput {
@@ -378,7 +388,8 @@ struct tdnet {
     U8Input u8;                                                        // tdnet_set_input_u8 / tdnet_set_input_nv12
     RgbOutput rgb;                                                     // tdnet_set_output_rgb
     OverlayOutput overlay;                                             // tdnet_set_output_overlay
-    ScoreOutput score;                                                 // tdnet_set_score
+    DstOutput dst;                                                     // tdnet_set_output_view
+    ScoreOutput score;                                                // tdnet_set_score
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
@@ -445,6 +456,35 @@ static void nv12_coeffs(int standard, int coef[6]) {
     coef[0] = standard < 2 ? 16 : 0;
     for (int i = 0; i < 5; ++i) coef[1 + i] = (int)nearbyint(dec[standard][i] * 1048576.0);
 }
+// What a frame of a view must satisfy as a surface, source or destination alike: tdnet_set_input_nv12's pitch / uv_offset / standard conditions, and an
+// extent [base, base + extent) below 2^31 bytes.  pitch: the one in force.
+static int view_surface_check(const SrcView& sv, int pitch, const char* who, double* extent_out) {
+    double extent = 0.0;
+    if (sv.format == TDNET_PIX_NV12) {
+        const int cw = (sv.fw - 1) / 2 + 1, chh = (sv.fh - 1) / 2 + 1;  // chroma pairs per row, chroma rows
+        if (pitch < 2 * cw) return td_fail("%s: pitch %d is below the %d bytes a row of %d columns holds", who, pitch, 2 * cw, sv.fw);
+        if ((double)sv.uv_offset < (double)sv.fh * pitch) return td_fail("%s: uv_offset %zu is inside the Y plane (%d rows of pitch %d)", who, sv.uv_offset, sv.fh, pitch);
+        extent = (double)sv.uv_offset + (double)(chh - 1) * pitch + 2.0 * cw;
+        if (extent >= 2147483648.0) return td_fail("%s: the surface's extent (uv_offset %zu, pitch %d, %d rows) is 2^31 bytes or more", who, sv.uv_offset, pitch, sv.fh);
+        if (sv.standard < 0 || sv.standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, sv.standard);
+    } else {
+        extent = (double)(sv.fh - 1) * pitch + (double)sv.fw * src_view_bpp(sv.format);
+        if (extent >= 2147483648.0) return td_fail("%s: the frame's extent (pitch %d, %d rows) is 2^31 bytes or more", who, pitch, sv.fh);
+    }
+    *extent_out = extent;
+    return 0;
+}
+// include/tdnet.h "destination views": yoff and rint(c 2^20) of the forward matrix's decimals, rows Y, U, V over r, g, b, of TDNET_YUV_* 0..3
+static void nv12_forward_coeffs(int standard, int* yoff, int ky[3], int ku[3], int kv[3]) {
+    static const double dec[4][9] = {{.257, .504, .098, -.148, -.291, .439, .439, -.368, -.071}, {.183, .614, .062, -.101, -.339, .439, .439, -.399, -.040},
+                                     {.299, .587, .114, -.168736, -.331264, .5, .5, -.418688, -.081312}, {.2126, .7152, .0722, -.114572, -.385428, .5, .5, -.454153, -.045847}};
+    *yoff = standard < 2 ? 16 : 0;
+    for (int i = 0; i < 3; ++i) {
+        ky[i] = (int)nearbyint(dec[standard][i] * 1048576.0);
+        ku[i] = (int)nearbyint(dec[standard][3 + i] * 1048576.0);
+        kv[i] = (int)nearbyint(dec[standard][6 + i] * 1048576.0);
+    }
+}
 // Validate, build the tables on the host and upload them into memory `u` owns.  NULL mean / std: the loader's (dataloader.py:52-53).
 // sv: what the image pointer is the base of -- the tables are those of the rectangle Hs x Ws whatever the format.  On failure `u` is left as it was.
 static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who) {
@@ -458,17 +498,7 @@ static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W,
     if (!nv && (double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
     const int pitch = nv || sv.pitch ? sv.pitch : sv.fw * bpp;         // packed, 0: tight (a row that overflows was refused above or by view_resolve)
     double extent = 0.0;
-    if (nv) {
-        const int cw = (sv.fw - 1) / 2 + 1, chh = (sv.fh - 1) / 2 + 1;  // chroma pairs per row, chroma rows
-        if (pitch < 2 * cw) return td_fail("%s: pitch %d is below the %d bytes a row of %d columns holds", who, pitch, 2 * cw, sv.fw);
-        if ((double)sv.uv_offset < (double)sv.fh * pitch) return td_fail("%s: uv_offset %zu is inside the Y plane (%d rows of pitch %d)", who, sv.uv_offset, sv.fh, pitch);
-        extent = (double)sv.uv_offset + (double)(chh - 1) * pitch + 2.0 * cw;
-        if (extent >= 2147483648.0) return td_fail("%s: the surface's extent (uv_offset %zu, pitch %d, %d rows) is 2^31 bytes or more", who, sv.uv_offset, pitch, sv.fh);
-        if (sv.standard < 0 || sv.standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, sv.standard);
-    } else {
-        extent = (double)(sv.fh - 1) * pitch + (double)sv.fw * bpp;
-        if (extent >= 2147483648.0) return td_fail("%s: the frame's extent (pitch %d, %d rows) is 2^31 bytes or more", who, pitch, sv.fh);
-    }
+    TD_TRY(view_surface_check(sv, pitch, who, &extent));
     for (int c = 0; c < 3; ++c) {
         if (!std::isfinite(mean[c])) return td_fail("%s: mean[%d] is not finite", who, c);
         if (!std::isfinite(std_[c]) || std_[c] == 0.0) return td_fail("%s: std[%d] must be finite and non-zero", who, c);
@@ -572,6 +602,29 @@ static bool u8_same(const U8Input& u, const SrcView& sv, int Hs, int Ws, const d
     const long pitch = nv || sv.pitch ? sv.pitch : (long)sv.fw * src_view_bpp(sv.format);
     if (u.pitch != pitch || (nv && (u.uv_offset != sv.uv_offset || u.standard != sv.standard))) return false;
     return memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0;
+}
+
+// tdnet_view -> the destination view it describes, or the failure that names the offending field.  On failure `d` is left as it was.
+static int dst_build(DstOutput& d, const tdnet_view* t, const char* who) {
+    SrcView sv;
+    int h = 0, w = 0;
+    TD_TRY(view_resolve(t, sv, h, w, who));
+    double extent = 0.0;
+    TD_TRY(view_surface_check(sv, sv.pitch, who, &extent));
+    if (h > 65535) return td_fail("%s: the rectangle's height %d is above the grid's 65535 rows", who, h);
+    const bool nv = sv.format == TDNET_PIX_NV12;
+    if (nv && (sv.oy & 1)) return td_fail("%s: crop_y = %d must be even for an NV12 destination (the rectangle starts on the chroma grid)", who, sv.oy);
+    if (nv && (sv.ox & 1)) return td_fail("%s: crop_x = %d must be even for an NV12 destination (the rectangle starts on the chroma grid)", who, sv.ox);
+    DstOutput v;
+    v.set = true;
+    v.format = sv.format; v.bpp = src_view_bpp(sv.format); v.swap = sv.format == TDNET_PIX_BGR24 || sv.format == TDNET_PIX_BGRA32;
+    v.fh = sv.fh; v.fw = sv.fw; v.oy = sv.oy; v.ox = sv.ox; v.h = h; v.w = w; v.pitch = sv.pitch; v.extent = (size_t)extent;
+    if (nv) {
+        v.uv_offset = sv.uv_offset; v.standard = sv.standard;
+        nv12_forward_coeffs(sv.standard, &v.yoff, v.ky, v.ku, v.kv);
+    }
+    d = v;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -500,6 +500,49 @@ static int launch_labels_overlay(const unsigned char* labels, const OverlayOutpu
     }
     return 0;
 }
+// The picture into a destination view (tdnet_set_output_view; `d` = that configuration, `base` = the destination frame's base): the colour map (r != NULL)
+// or the overlay (o, u, src), from the low-resolution logits (labels == NULL) or from a uint8 label map.  One launch, like the contiguous forms.  The
+// picture's size must be the rectangle's: the frame entries check that before anything is enqueued (td_model.hip picture_dst_check), and here again.
+template <bool LABELS, bool OVERLAY, int SRC>
+static void launch_picture_form(const PicArgs& a, const OverlaySrc& sd, const DstView& dv, int form, hipStream_t s) {
+    if (form == TD_DST_NV12) TD_LAUNCH((k_picture_nv12<LABELS, OVERLAY, SRC>), dim3(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2), dim3(256), 0, s, a, sd, dv);
+    else if (form == TD_DST_P32) TD_LAUNCH((k_picture_packed<TD_DST_P32, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
+    else TD_LAUNCH((k_picture_packed<TD_DST_P24, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
+}
+template <bool LABELS>
+static void launch_picture_src(const PicArgs& a, const OverlaySrc& sd, const DstView& dv, int form, int src_form, hipStream_t s) {
+    if (src_form < 0) launch_picture_form<LABELS, false, TD_SRC_P24>(a, sd, dv, form, s);          // the colour map: no source
+    else if (src_form == TD_SRC_NV12) launch_picture_form<LABELS, true, TD_SRC_NV12>(a, sd, dv, form, s);
+    else if (src_form == TD_SRC_P32) launch_picture_form<LABELS, true, TD_SRC_P32>(a, sd, dv, form, s);
+    else launch_picture_form<LABELS, true, TD_SRC_P24>(a, sd, dv, form, s);
+}
+static int launch_picture_dst(const float* in, int C, int h, int w, const unsigned char* labels, const RgbOutput* r, const OverlayOutput* o, const U8Input* u,
+                              const unsigned char* src, const DstOutput& d, unsigned char* base, hipStream_t s) {
+    const char* what = r ? "colour map" : "overlay";
+    PicArgs a;
+    if (r) a = PicArgs{in, labels, r->ys, r->xs, r->lut, C, h, w, r->H, r->W, r->oh, r->ow};
+    else {
+        TD_TRY(overlay_check_tables(*o, *u));
+        a = PicArgs{in, labels, o->ys, o->xs, o->lut, C, h, w, o->H, o->W, o->Hs, o->Ws};
+    }
+    TD_TRY(out_check(what, "height", a.oh, labels ? 1 : C));
+    if (!d.set || a.oh != d.h || a.ow != d.w) return td_fail("%s: the picture %d x %d is not the destination rectangle %d x %d", what, a.oh, a.ow, d.h, d.w);
+    const bool src_bgr = !r && u->swap;                                // the picture word's bytes are b g r: the overlay's table and source are
+    DstView dv = DstView();
+    dv.base = base; dv.pitch = d.pitch; dv.uv_offset = (unsigned)d.uv_offset; dv.oy = d.oy; dv.ox = d.ox;
+    dv.swap = d.format != TDNET_PIX_NV12 && d.swap != src_bgr;
+    dv.yoff = d.yoff;
+    for (int i = 0; i < 3; ++i) {                                      // NV12 behind a b g r picture: the r and b constants exchanged
+        const int k = src_bgr ? 2 - i : i;
+        dv.ky[i] = d.ky[k]; dv.ku[i] = d.ku[k]; dv.kv[i] = d.kv[k];
+    }
+    const OverlaySrc sd = r ? OverlaySrc() : overlay_src(*u, src);
+    const int form = d.format == TDNET_PIX_NV12 ? TD_DST_NV12 : d.bpp == 4 ? TD_DST_P32 : TD_DST_P24;
+    const int src_form = r ? -1 : overlay_src_form(*u) / 2;
+    if (labels) launch_picture_src<true>(a, sd, dv, form, src_form, s);
+    else launch_picture_src<false>(a, sd, dv, form, src_form, s);
+    return 0;
+}
 // score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be
 // NULL) or from a uint8 label map the caller holds.  A private LDS histogram per workgroup up to TD_SCORE_LDS_CLASSES classes, straight
 // global atomics above.  The wave-uniform path is OFF in the library's entries until tools/score_probe.py has shown on the device that it
@@ -552,6 +595,7 @@ enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OU
 struct FrameOutput {
     OutKind kind;
     void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF: may be NULL) | rgb [oh][ow][3] | overlay [Hs][Ws][3]
+                                   // (the two pictures with a destination view in force: the destination frame's base)
     const unsigned char* gt;       // OUT_SCORE: ground truth [H][W]
     unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]
     const unsigned char* src;      // OUT_OVERLAY: the source frame, read by the handle's byte-input configuration
@@ -575,10 +619,14 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
     case OUT_LOGITS: launch_upsample(in, C, h, w, H, W, (float*)o.dst, s); return 0;
     case OUT_LABELS_I32: launch_upsample_argmax(in, C, h, w, H, W, (int32_t*)o.dst, s); return 0;
     case OUT_LABELS_U8: return launch_upsample_argmax_u8(in, C, h, w, H, W, (unsigned char*)o.dst, s);
-    case OUT_RGB: return launch_upsample_argmax_rgb(in, C, h, w, n->rgb, (unsigned char*)o.dst, s);
+    case OUT_RGB:
+        if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, &n->rgb, nullptr, nullptr, nullptr, n->dst, (unsigned char*)o.dst, s);
+        return launch_upsample_argmax_rgb(in, C, h, w, n->rgb, (unsigned char*)o.dst, s);
     case OUT_SCORE: return launch_upsample_argmax_score(in, C, h, w, H, W, o.gt, n->score.dmap, (unsigned char*)o.dst, n->score.cm, s);
     case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
-    case OUT_OVERLAY: return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);
+    case OUT_OVERLAY:
+        if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, nullptr, &n->overlay, &n->u8, o.src, n->dst, (unsigned char*)o.dst, s);
+        return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);
     }
     return td_fail("internal: unknown output form");
 }

@@ -227,9 +227,21 @@ static int propagate_lowres(tdnet* n, hipStream_t s);
 // `who` names the entry in the messages of the frame's checks.  The forward route's last launch is a family-2 profile record; the propagate
 // route stays outside the records (tdnet_last_ms / tdnet_last_launches of a split frame are those of its tdnet_encode half).  A form that
 // is not configured is refused before the frame starts: the FIFO and a pending frame stay as they are.
+// With a destination view in force (tdnet_set_output_view) the picture must be the view's rectangle.  The configurations are independent of each other's
+// order, so it is the frame entry that checks, on the host, before anything is enqueued; `kind`'s own configuration exists (output_configured).
+static int picture_dst_check(const tdnet* n, OutKind kind, const char* who) {
+    if (!n->dst.set || (kind != OUT_RGB && kind != OUT_OVERLAY)) return 0;
+    const bool rgb = kind == OUT_RGB;
+    const int ph = rgb ? n->rgb.oh : n->u8.Hs, pw = rgb ? n->rgb.ow : n->u8.Ws;
+    if (ph != n->dst.h || pw != n->dst.w)
+        return td_fail("%s: the %s is %d x %d but the destination view's rectangle is %d x %d (tdnet_set_output_view: nothing is resized)", who,
+                       rgb ? "colour map" : "overlay", ph, pw, n->dst.h, n->dst.w);
+    return 0;
+}
 static int frame_out(tdnet* n, const FrameSource& src, const FrameOutput& out, void* stream, const char* who) {
     TD_ON_DEVICE(n, -1);
     TD_TRY(output_configured(n, out.kind, who));
+    TD_TRY(picture_dst_check(n, out.kind, who));
     LaunchCount count_(n);
     hipStream_t s = (hipStream_t)stream;
     if (src.img ? forward_lowres(n, *src.img, src.pos_id, s, who) : propagate_lowres(n, s)) return -1;
@@ -346,6 +358,9 @@ extern "C" int tdnet_labels_rgb(tdnet_t* n, const uint8_t* labels, uint8_t* rgb,
     if (!n || !labels || !rgb) return td_fail("tdnet_labels_rgb: null argument");
     TD_ON_DEVICE(n, -1);
     TD_TRY(output_configured(n, OUT_RGB, "tdnet_labels_rgb"));
+    TD_TRY(picture_dst_check(n, OUT_RGB, "tdnet_labels_rgb"));
+    if (n->dst.set) TD_TRY(launch_picture_dst(nullptr, 0, 0, 0, labels, &n->rgb, nullptr, nullptr, nullptr, n->dst, rgb, (hipStream_t)stream));
+    else
     TD_TRY(launch_labels_rgb(labels, n->rgb, rgb, (hipStream_t)stream));
     TD_HIP(hipGetLastError());
     return 0;
@@ -371,8 +386,9 @@ extern "C" int tdnet_set_output_overlay(tdnet_t* n, const uint8_t* palette_rgba,
 static int overlay_args(const tdnet* n, const uint8_t* src, const uint8_t* out, const char* who) {
     if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
     TD_TRY(output_configured(n, OUT_OVERLAY, who));
+    TD_TRY(picture_dst_check(n, OUT_OVERLAY, who));
     const U8Input& u = n->u8;
-    const size_t nout = (size_t)3 * u.Hs * u.Ws, nsrc = u.extent;
+    const size_t nout = n->dst.set ? n->dst.extent : (size_t)3 * u.Hs * u.Ws, nsrc = u.extent;   // a destination view: the WHOLE destination frame's extent
     const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
     if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
     return 0;
@@ -388,9 +404,21 @@ extern "C" int tdnet_labels_overlay(tdnet_t* n, const uint8_t* labels, const uin
     if (!n || !labels || !img || !out) return td_fail("tdnet_labels_overlay: null argument");
     TD_TRY(overlay_args(n, img, out, "tdnet_labels_overlay"));
     TD_ON_DEVICE(n, -1);
+    if (n->dst.set) TD_TRY(launch_picture_dst(nullptr, 0, 0, 0, labels, nullptr, &n->overlay, &n->u8, img, n->dst, out, (hipStream_t)stream));
+    else
     TD_TRY(launch_labels_overlay(labels, n->overlay, n->u8, img, out, (hipStream_t)stream));
     TD_HIP(hipGetLastError());
     return 0;
+}
+// ---- destination views -----------------------------------------------------------------------------------------------------------------
+// Configuration of where the picture entries write (include/tdnet.h "destination views"): plain host state of the handle -- the kernels take it as
+// arguments when an entry enqueues, so nothing is allocated and nothing in flight reads it; idempotent; per handle.  NULL: contiguous [h][w][3] again.  A
+// failed call leaves the previous configuration in force.
+extern "C" int tdnet_set_output_view(tdnet_t* n, const tdnet_view* v) {
+    if (!n) return td_fail("tdnet_set_output_view: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_output_view: weights not finalized");
+    if (!v) { n->dst = DstOutput(); return 0; }
+    return dst_build(n->dst, v, "tdnet_set_output_view");
 }
 // ---- score out -------------------------------------------------------------------------------------------------------------------------
 // Configuration of the score output (not a frame call: it may synchronise; idempotent for an equal map).  The matrix and the map live in memory

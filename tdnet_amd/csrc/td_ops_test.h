@@ -612,6 +612,40 @@ extern "C" int tdnet_op_overlay_view(const float* in, int C, int h, int w, int H
     u8_free(u);
     return rc;
 }
+// The picture into a destination view (include/tdnet.h "destination views") through exactly the kernels the frame entries launch with one in force: of
+// low-resolution logits [C][h][w] (labels_u8 == NULL) or of a uint8 label map [H][W]; the overlay over the source view (src_base, src_view; palette
+// [n][4]) or, src_base == NULL, the colour map oh x ow (palette [n][3]).  dst_base: the destination frame's base, at any byte address.
+extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
+                                     const uint8_t* src_base, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base, const tdnet_view* dst_view, void* stream) {
+    const char* who = "tdnet_op_picture_view";
+    if (!dst_base || !dst_view) return td_fail("%s: dst_base and dst_view expected", who);
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    DstOutput d;
+    TD_TRY(dst_build(d, dst_view, who));
+    int rc = 0;
+    if (!src_base) {
+        RgbOutput r;
+        TD_TRY(rgb_build(r, H, W, oh, ow, palette, n_colours, who));
+        rc = launch_picture_dst(in, C, h, w, labels_u8, &r, nullptr, nullptr, nullptr, d, dst_base, s);
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+        rgb_free(r);
+        return rc;
+    }
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(view_resolve(src_view, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    rc = overlay_build(o, palette, n_colours, who, u.swap);
+    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = launch_picture_dst(in, C, h, w, labels_u8, nullptr, &o, &u, src_base, d, dst_base, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
 // cm_dev [C][C] (uint64, ACCUMULATED into, not cleared) += the confusion counts of ground truth gt [H][W] (through gt_map, 256 bytes on the host,
 // NULL = identity) against the labels of low-resolution logits [C][h][w] (labels_in == NULL: k_upsample_argmax_score, which also writes the uint8
 // label map if labels_u8 != NULL) or against a uint8 label map [H][W] (labels_in != NULL: k_labels_score; in, h, w, labels_u8 are ignored).

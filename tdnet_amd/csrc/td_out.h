@@ -377,3 +377,128 @@ TD_KERNEL void k_labels_overlay(const unsigned char* __restrict__ labels, const 
     for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
     td_rgb_store(orow, q, xa, xb, px);
 }
+
+// ---- destination views -------------------------------------------------------------------------------------------------------------
+// The picture (colour map or overlay) written into a rectangle of a pitched frame instead of a contiguous [h][w][3] block (include/tdnet.h
+// "destination views"): packed 3-byte pixels, packed 4-byte pixels (x = 255), or an NV12 surface.  The kernels above stay what they are -- the
+// contiguous destination is their constant; these forms take the rectangle's origin, the pitch and the colour order as arguments and always read an
+// overlay's source through the VIEW = true readers.  One per-lane body (td_picture_px4) for the four pictures: the class loop, the argmax rule, the
+// colour table, the source readers and the blend are the ones above.
+enum { TD_DST_P24 = 1, TD_DST_P32 = 2, TD_DST_NV12 = 3 };
+struct PicArgs {
+    const float* in;               // low-resolution logits [C][h][w] (the fused forms)
+    const unsigned char* labels;   // uint8 label map [H][W] (the label-map forms)
+    const int* ys; const int* xs;  // [oh], [ow]: the sampled network pixel of a picture row / column
+    const unsigned* lut;           // [256]: the colour-map or the overlay table
+    int C, h, w, H, W, oh, ow;
+};
+struct DstView {
+    unsigned char* base;           // the destination frame's base; any byte address
+    int pitch;                     // bytes per frame row (NV12: of both planes)
+    unsigned uv_offset;            // NV12: < 2^31
+    int oy, ox;                    // the rectangle's origin: picture pixel (y, x) is frame pixel (oy + y, ox + x); NV12: both even
+    int swap;                      // packed: the destination's colour order is not the picture word's -- bytes 0 and 2 are exchanged at the store
+    int yoff, ky[3], ku[3], kv[3]; // NV12: rint(c 2^20) of the forward matrix, in the order of the picture word's bytes (the host exchanges r and b behind a b g r source)
+};
+// The 4 pixels xa .. xa + 3 of picture row y as words c0 | c1 << 8 | c2 << 16 (a partial run repeats its last pixel): the colour table's word of
+// the label -- the first-maximum argmax at the sampled pixel, or the label map's byte -- blended over the source pixel for the overlay.
+template <bool LABELS, bool OVERLAY, int SRC>
+TD_DEV void td_picture_px4(const PicArgs& a, const OverlaySrc& o, int y, long xa, unsigned* px) {
+    if (LABELS) {
+        const unsigned char* lrow = a.labels + (size_t)a.ys[y] * a.W;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = a.lut[lrow[a.xs[td_run_px(xa, e, a.ow)]]];
+    } else {
+        float best[4] = {0.f, 0.f, 0.f, 0.f};
+        int bi[4] = {0, 0, 0, 0};
+        td_up_classes(a.in, a.C, a.h, a.w, a.H, a.W, a.ys[y], [&](int e) { return a.xs[td_run_px(xa, e, a.ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = a.lut[bi[e] & 255];
+    }
+    if (OVERLAY) {
+        unsigned s[4];
+        td_overlay_src<SRC, true>(o, y, xa, a.ow, xa + 4 <= a.ow, s);   // a whole run is read at once: four pixels of the rectangle
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
+    }
+}
+TD_DEV unsigned td_swap_rb(unsigned p) { return (p & 0xFF00u) | ((p >> 16) & 0xFFu) | ((p & 0xFFu) << 16); }
+// A lane's run of a row of 4-byte pixels that starts at `row`: lane 0 the pixels in front of the first 16-byte boundary (none where the row is not
+// 4-byte aligned: no run of it is ever aligned), lane q >= 1 the four behind it: [xa, xb)
+TD_DEV void td_p32_run(const unsigned char* row, long q, long ow, long* xa, long* xb) {
+    const unsigned r = (unsigned)((size_t)row & 15u);
+    const long X0 = (r & 3u) ? 0 : (long)(((16u - r) & 15u) >> 2);
+    *xa = q == 0 ? 0 : X0 + 4 * (q - 1);
+    *xb = q == 0 ? (X0 < ow ? X0 : ow) : (*xa + 4 < ow ? *xa + 4 : ow);
+}
+struct alignas(16) TdPx4 { unsigned v[4]; };
+// px[e]: the colour word of pixel xa + e; the x byte is 255.  ONE 16-byte store where the run is four pixels at a 16-byte boundary
+TD_DEV void td_p32_store(unsigned char* row, long xa, long xb, const unsigned* px) {
+    unsigned char* p = row + 4 * xa;
+    if (xb - xa == 4 && (((size_t)p) & 15u) == 0) {
+        TdPx4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v.v[e] = px[e] | 0xFF000000u;
+        *reinterpret_cast<TdPx4*>(p) = v;
+    } else {
+        for (long X = xa; X < xb; ++X, p += 4) {
+            const unsigned w = px[X - xa];
+            p[0] = (unsigned char)w; p[1] = (unsigned char)(w >> 8); p[2] = (unsigned char)(w >> 16); p[3] = 255;
+        }
+    }
+}
+// Packed destinations: k_upsample_argmax_rgb's geometry (a grid row per picture row, the lane split by the row's address) on the rectangle's rows.
+template <int DST, bool LABELS, bool OVERLAY, int SRC>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_picture_packed(PicArgs a, OverlaySrc o, DstView d) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= a.oh) return;
+    unsigned char* row = d.base + (size_t)(d.oy + y) * d.pitch + (size_t)d.ox * (DST == TD_DST_P32 ? 4 : 3);
+    long xa, xb;
+    if (DST == TD_DST_P32) td_p32_run(row, q, a.ow, &xa, &xb);
+    else td_rgb_run(row, q, a.ow, &xa, &xb);
+    if (xa >= xb) return;
+    unsigned px[4];
+    td_picture_px4<LABELS, OVERLAY, SRC>(a, o, y, xa, px);
+    if (d.swap) {                                                      // wave-uniform
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_swap_rb(px[e]);
+    }
+    if (DST == TD_DST_P32) td_p32_store(row, xa, xb, px);
+    else td_rgb_store(row, q, xa, xb, px);
+}
+// NV12 destination.  A lane owns the 2-row x 4-column block (j, q) of the rectangle, which the even origin aligns to the frame's chroma grid: rows
+// 2 j and 2 j + 1, columns 4 q .. 4 q + 3, the chroma pairs (oy / 2 + j, ox / 2 + 2 q) and the one behind it.  Row by row: the picture's four pixels,
+// their luma bytes stored, their colours added to the two pairs' sums; then the pairs.  At the rectangle's odd last row / column a pair covers n = 2
+// or 1 pixels and its sum is scaled by m = 4 / n.  All in int32 (|m S K| <= 1020 * 0.5 * 2^20, + 2^29 + 2^21 < 2^31), arithmetic shifts.  No LDS, no
+// barrier, no cross-lane traffic; grid = (ceil(ceil(ow / 4) / 256), ceil(oh / 2)).
+TD_DEV int td_chroma8(const int* k, const int* s, int m) { return ingest_clamp8((m * (k[0] * s[0] + k[1] * s[1] + k[2] * s[2]) + (128 << 22) + (1 << 21)) >> 22); }
+// The launch bound asks for 4 waves per SIMD, not the siblings' 5: two rows' worth of state (the pairs' six sums beside the class loop's accumulators and
+// coefficients) does not fit 96 VGPRs -- the fused overlay forms spilled 2 - 21 registers there -- and a lane does two rows' work anyway.
+template <bool LABELS, bool OVERLAY, int SRC>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_nv12(PicArgs a, OverlaySrc o, DstView d) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    const long xa = 4L * q;
+    if (2 * j >= a.oh || xa >= a.ow) return;
+    const int nx = a.ow - xa < 4 ? (int)(a.ow - xa) : 4, ny = a.oh - 2 * j < 2 ? 1 : 2;
+    int s0[3] = {0, 0, 0}, s1[3] = {0, 0, 0};                          // the colour sums of the pair of columns 0, 1 and of columns 2, 3
+    for (int r = 0; r < ny; ++r) {
+        unsigned px[4];
+        td_picture_px4<LABELS, OVERLAY, SRC>(a, o, 2 * j + r, xa, px);
+        int yb[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c0 = (int)(px[e] & 255u), c1 = (int)((px[e] >> 8) & 255u), c2 = (int)((px[e] >> 16) & 255u);
+            yb[e] = ingest_clamp8((d.ky[0] * c0 + d.ky[1] * c1 + d.ky[2] * c2 + (d.yoff << 20) + (1 << 19)) >> 20);
+            if (e < nx) {
+                int* s = e < 2 ? s0 : s1;
+                s[0] += c0; s[1] += c1; s[2] += c2;
+            }
+        }
+        td_u8_store(d.base + (size_t)(d.oy + 2 * j + r) * d.pitch + d.ox, xa, xa + nx, yb);
+    }
+    const int m0 = 4 / (ny * (nx < 2 ? nx : 2)), m1 = nx > 2 ? 4 / (ny * (nx - 2)) : 0;
+    int cb[4];
+    cb[0] = td_chroma8(d.ku, s0, m0); cb[1] = td_chroma8(d.kv, s0, m0);
+    cb[2] = td_chroma8(d.ku, s1, m1); cb[3] = td_chroma8(d.kv, s1, m1);
+    td_u8_store(d.base + d.uv_offset + (size_t)((d.oy >> 1) + j) * d.pitch + d.ox, xa, xa + (nx > 2 ? 4 : 2), cb);
+}

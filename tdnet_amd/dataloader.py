@@ -210,6 +210,77 @@ def pack_view(rgb_frame, view, fill=0):
     return out
 
 
+# ---- destination views (include/tdnet.h "destination views") --------------------------------------------------------------------------
+# standard -> (yoff, decimal rows Y, U, V over r, g, b) of the forward matrix
+NV12_FORWARD = {0: (16, ((.257, .504, .098), (-.148, -.291, .439), (.439, -.368, -.071))),
+                1: (16, ((.183, .614, .062), (-.101, -.339, .439), (.439, -.399, -.040))),
+                2: (0, ((.299, .587, .114), (-.168736, -.331264, .5), (.5, -.418688, -.081312))),
+                3: (0, ((.2126, .7152, .0722), (-.114572, -.385428, .5), (.5, -.454153, -.045847)))}
+
+
+def nv12_forward_coeffs(standard):
+    """(yoff, K int64 [3, 3]): K = rint(c * 2^20) of the forward matrix, rows Y, U, V over r, g, b."""
+    yoff, rows = NV12_FORWARD[int(standard)]
+    return yoff, np.array([[int(np.rint(c * 1048576.0)) for c in row] for row in rows], np.int64)
+
+
+def nv12_from_rgb_u8(rgb, standard=0, planes=False):
+    """The integer oracle of the library's NV12 destination: uint8 RGB [H, W, 3] -> the tight NV12 surface uint8 [H + ceil(H / 2), 2 * ceil(W / 2)]
+    (the Y plane, then the interleaved U, V plane; an odd W leaves one zero byte behind every Y row), or with planes=True (Y [H, W],
+    UV [ceil(H / 2), ceil(W / 2), 2]).  Per pixel and per chroma pair, in integers that fit int32 (asserted), arithmetic shifts:
+        Y = clamp8((KYR R + KYG G + KYB B + (yoff << 20) + (1 << 19)) >> 20)
+        S = the sum of the n in {1, 2, 4} pixels of the pair's 2 x 2 block that exist, m = 4 / n
+        U = clamp8((m (KUR S_R + KUG S_G + KUB S_B) + (128 << 22) + (1 << 21)) >> 22);  V likewise with the V row.
+    Not rgb_to_nv12, the float generator of test surfaces: this one is a definition, pinned by hand in tests/test_dst_view_host.py."""
+    img = np.asarray(rgb)
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3 and img.shape[0] >= 1 and img.shape[1] >= 1
+    H, W = img.shape[:2]
+    hc, wc = (H + 1) // 2, (W + 1) // 2
+    yoff, K = nv12_forward_coeffs(standard)
+    p = img.astype(np.int64)
+    ysum = p @ K[0] + (yoff << 20) + (1 << 19)
+    assert (p @ np.abs(K[0])).max() + (yoff << 20) + (1 << 19) < 2 ** 31
+    Y = np.clip(ysum >> 20, 0, 255).astype(np.uint8)
+    S, cnt = np.zeros((2 * hc, 2 * wc, 3), np.int64), np.zeros((2 * hc, 2 * wc), np.int64)
+    S[:H, :W], cnt[:H, :W] = p, 1
+    S, n = S.reshape(hc, 2, wc, 2, 3).sum(axis=(1, 3)), cnt.reshape(hc, 2, wc, 2).sum(axis=(1, 3))
+    assert np.isin(n, (1, 2, 4)).all()
+    m = (4 // n)[..., None]
+    assert (m * (S @ np.abs(K[1:]).T)).max() + (128 << 22) + (1 << 21) < 2 ** 31      # every partial sum, whatever the order
+    UV = np.clip((m * (S @ K[1:].T) + (128 << 22) + (1 << 21)) >> 22, 0, 255).astype(np.uint8)
+    if planes:
+        return Y, UV
+    surf = np.zeros((H + hc, 2 * wc), np.uint8)
+    surf[:H, :W] = Y
+    surf[H:] = UV.reshape(hc, 2 * wc)
+    return surf
+
+
+def write_view(frame_bytes, view, picture_rgb):
+    """The host oracle of the library's destination views: a COPY of a frame's bytes with picture_rgb [h, w, 3] (true r, g, b) pasted into the view's
+    rectangle, in any of the five formats.  Packed: the three colour bytes in the format's order, the x byte of the 32-bit formats 255.  NV12 (even
+    origin): nv12_from_rgb_u8 of the picture -- its Y bytes and the chroma pairs covering the rectangle.  Every other byte keeps its value."""
+    s = np.array(np.asarray(frame_bytes).reshape(-1), copy=True)
+    pic = np.asarray(picture_rgb)
+    y, x, h, w = view.rect
+    assert s.dtype == np.uint8 and s.size >= view_extent(view) and pic.dtype == np.uint8 and pic.shape == (h, w, 3), (s.dtype, s.size, pic.shape, view.rect)
+    assert 0 <= y and 0 <= x and y + h <= view.height and x + w <= view.width
+    pitch = view.row_pitch
+    if view.nv12:
+        assert y % 2 == 0 and x % 2 == 0, "an NV12 destination starts on the chroma grid"
+        Y, UV = nv12_from_rgb_u8(pic, view.standard, planes=True)
+        s[(y + np.arange(h))[:, None] * pitch + (x + np.arange(w))[None, :]] = Y
+        hc, wc = UV.shape[:2]
+        s[view.uv + (y // 2 + np.arange(hc))[:, None, None] * pitch + (x + 2 * np.arange(wc))[None, :, None] + np.arange(2)[None, None, :]] = UV
+        return s
+    bpp = view.bpp
+    at = (y + np.arange(h))[:, None] * pitch + (x + np.arange(w))[None, :] * bpp
+    s[at[..., None] + (np.array([2, 1, 0]) if view.format in PIX_BGR else np.arange(3))[None, None, :]] = pic
+    if bpp == 4:
+        s[at + 3] = 255
+    return s
+
+
 def nearest_index(n_src, n_dst):
     """Source index per destination index of the nearest-sample resize of the label map (test.py:64, cv2.INTER_NEAREST): int64 [n_dst] =
     min(int64(o * (n_src / n_dst)), n_src - 1) -- the quotient first, in float64, then the product, then truncation.  This is the project's rule:

@@ -214,6 +214,15 @@ class Engine:
     def labels_overlay(self, labels_ptr, img_ptr, out_ptr, stream=None):
         self.lib.check(self.lib.tdnet_labels_overlay(self.h, _ptr(labels_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
 
+    # ---- destination views (include/tdnet.h) ----
+    def set_output_view(self, view):
+        """The picture entries (forward_rgb, forward_u8_rgb, propagate_rgb, labels_rgb, forward_u8_overlay, propagate_overlay, labels_overlay) will
+        write into `view`'s rectangle of a pitched frame (a dataloader.SourceView; their picture pointer is then the frame's base); None: the
+        contiguous [h, w, 3] block again.  The rectangle must be the picture's size: the frame entries check that.  A configuration call."""
+        if view is not None and view.uv_offset is not None and view.uv_offset < 0:
+            raise _capi.TdnetError("set_output_view: uv_offset must not be negative")
+        self.lib.check(self.lib.tdnet_set_output_view(self.h, None if view is None else ctypes.byref(view_struct(view))))
+
     # ---- score out (include/tdnet.h) ----
     def set_score(self, gt_map=None):
         """Frames may be scored against ground truth: allocates this handle's zeroed confusion matrix.  gt_map: 256 byte values (ground-truth byte ->

@@ -458,6 +458,7 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.set_output_view(None)
             eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, nv)
         return out
@@ -506,45 +507,97 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("out_size must be (oh, ow), at least (1, 1), got %r" % (out_size,))
         return int(out_size[0]), int(out_size[1])
 
+    # out_view: a dataloader.SourceView (include/tdnet.h "destination views") -- the picture is then written into the view's rectangle of a pitched RGB /
+    # BGR / RGBA / BGRA / NV12 frame and the method returns a uint8 tensor [N, nbytes], nbytes >= view_extent(out_view): N whole destination frames.
+    # out: that tensor supplied by the caller (only the rectangle's bytes are written: the rest of a frame the caller composed stays); None: zeros.  The
+    # rectangle must be the picture's size; the source's colour order no longer decides the picture's, the destination format does.
+    def _dst_out(self, out_view, out, size, n, device):
+        """The tensor [N, nbytes] the entries write into: the caller's, checked, or zeros."""
+        from ..dataloader import view_extent
+        self._dst_check(out_view, out, size, n)
+        if out is None:
+            return torch.zeros((n, view_extent(out_view)), device=device, dtype=torch.uint8)
+        if out.device != device:
+            raise RuntimeError("out must be on the frames' device %s, got %s" % (device, out.device))
+        return out
+
+    @staticmethod
+    def _dst_check(out_view, out, size, n):
+        """The checks of a destination view and tensor, made before an engine exists (and before the frames' device is looked at, like view=)."""
+        from ..dataloader import SourceView, view_extent
+        if not isinstance(out_view, SourceView):
+            raise RuntimeError("out_view must be a dataloader.SourceView, got %s" % type(out_view).__name__)
+        y, x, h, w = out_view.rect
+        if out_view.height < 1 or out_view.width < 1 or h < 1 or w < 1 or y < 0 or x < 0 or y + h > out_view.height or x + w > out_view.width:
+            raise RuntimeError("out_view's rectangle (y, x, h, w) = %r is not inside its %d x %d frame" % (out_view.rect, out_view.height, out_view.width))
+        if (h, w) != tuple(int(v) for v in size):
+            raise RuntimeError("out_view's rectangle is %d x %d but the picture is %d x %d: nothing is resized" % (h, w, size[0], size[1]))
+        row = 2 * ((out_view.width + 1) // 2) if out_view.nv12 else out_view.width * out_view.bpp
+        if out_view.row_pitch < row:
+            raise RuntimeError("out_view's pitch %d is below the %d bytes a row of %d pixels holds" % (out_view.row_pitch, row, out_view.width))
+        if out_view.nv12 and out_view.uv < out_view.height * out_view.row_pitch:
+            raise RuntimeError("out_view's uv_offset %d is inside the Y plane (%d rows of pitch %d)" % (out_view.uv, out_view.height, out_view.row_pitch))
+        if out_view.nv12 and (y % 2 or x % 2):
+            raise RuntimeError("out_view's origin (%d, %d) must be even for an NV12 destination" % (y, x))
+        need = view_extent(out_view)
+        if out is None:
+            return
+        if not torch.is_tensor(out) or out.dtype != torch.uint8:
+            raise RuntimeError("out must be a torch.uint8 tensor, got %s" % (out.dtype if torch.is_tensor(out) else type(out).__name__))
+        if out.dim() != 2 or out.shape[0] != n:
+            raise RuntimeError("out must be a uint8 tensor [N,nbytes] with N = %d (whole destination frames), got shape %s" % (n, tuple(out.shape)))
+        if not out.is_contiguous():
+            raise RuntimeError("out must be a CONTIGUOUS uint8 tensor [N,nbytes]: out_view's pitch describes the rows")
+        if int(out.shape[1]) < need:
+            raise RuntimeError("out holds %d bytes per sample, below the %d bytes out_view's frame needs" % (out.shape[1], need))
+
     def _rgb_out(self, n, out_size, device):
         oh, ow = self._rgb_size(out_size)
         return torch.empty((n, oh, ow, 3), device=device, dtype=torch.uint8)
 
-    def forward_rgb(self, img, pos_id, out_size, palette=None):
-        """forward_labels() with the colour map [N, oh, ow, 3] uint8 in place of the label map."""
-        self._rgb_size(out_size)
+    def forward_rgb(self, img, pos_id, out_size, palette=None, out_view=None, out=None):
+        """forward_labels() with the colour map [N, oh, ow, 3] uint8 in place of the label map (out_view: see _dst_out)."""
+        oh, ow = self._rgb_size(out_size)
         self._check_frame(img, pos_id)
+        out = self._dst_out(out_view, out, (oh, ow), img.shape[0], img.device) if out_view is not None else self._rgb_out(img.shape[0], out_size, img.device)
         img = img.contiguous().float()
-        out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
+        pal = self._palette(palette)
 
         def one(i, eng, s):
-            eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.set_output_rgb(oh, ow, pal)
+            eng.set_output_view(out_view)
             eng.forward_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._for_each_sample(img, one)
         return out
 
-    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None, view=None):
-        """forward_labels_u8() with the colour map [N, oh, ow, 3] uint8 in place of the label map: bytes in, picture out."""
-        self._rgb_size(out_size)
+    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None, view=None, out_view=None, out=None):
+        """forward_labels_u8() with the colour map [N, oh, ow, 3] uint8 in place of the label map: bytes in, picture out (out_view: see _dst_out)."""
+        oh, ow = self._rgb_size(out_size)
+        if out_view is not None and torch.is_tensor(img_u8) and img_u8.dim() >= 1:
+            self._dst_check(out_view, out, (oh, ow), img_u8.shape[0])
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
-        out, pal = self._rgb_out(img.shape[0], out_size, img.device), self._palette(palette)
+        out = self._dst_out(out_view, out, (oh, ow), img.shape[0], img.device) if out_view is not None else self._rgb_out(img.shape[0], out_size, img.device)
+        pal = self._palette(palette)
 
         def one(i, eng, s):
-            eng.set_output_rgb(out.shape[1], out.shape[2], pal)
+            eng.set_output_rgb(oh, ow, pal)
+            eng.set_output_view(out_view)
             eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
 
-    def labels_rgb(self, labels_u8, out_size, palette=None):
-        """uint8 labels [N, H, W] (CUDA) of this model -> their colour maps [N, oh, ow, 3]."""
+    def labels_rgb(self, labels_u8, out_size, palette=None, out_view=None, out=None):
+        """uint8 labels [N, H, W] (CUDA) of this model -> their colour maps [N, oh, ow, 3] (out_view: see _dst_out)."""
         if self._engine is None:
             raise RuntimeError("labels_rgb(): no handle yet")
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
             raise RuntimeError("labels_rgb(): expected uint8 labels [N, %d, %d]" % tuple(self._engine_key[:2]))
         labels = labels_u8.contiguous()
-        out = self._rgb_out(labels.shape[0], out_size, labels.device)
-        self._engine.set_output_rgb(out.shape[1], out.shape[2], self._palette(palette))
+        oh, ow = self._rgb_size(out_size)
+        out = self._dst_out(out_view, out, (oh, ow), labels.shape[0], labels.device) if out_view is not None else self._rgb_out(labels.shape[0], out_size, labels.device)
+        self._engine.set_output_rgb(oh, ow, self._palette(palette))
+        self._engine.set_output_view(out_view)
         s = torch.cuda.current_stream(labels.device).cuda_stream
         for i in range(labels.shape[0]):
             self._engine.labels_rgb(labels[i].data_ptr(), out[i].data_ptr(), s)
@@ -571,15 +624,24 @@ class _TDNetBase(nn.Module):
         out[:, 3] = np.rint(255.0 * a).astype(np.uint8)
         return out
 
-    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None, view=None):
-        """forward_labels_u8() with the overlay [N, Hs, Ws, 3] uint8 in place of the label map: the frame's bytes in, the tinted frame out."""
+    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None, view=None, out_view=None, out=None):
+        """forward_labels_u8() with the overlay [N, Hs, Ws, 3] uint8 in place of the label map: the frame's bytes in, the tinted frame out
+        (out_view: see _dst_out)."""
         pal = self._palette_rgba(palette, alpha)
+        if view is not None:
+            self._check_frame_view(img_u8, view)
+        if out_view is not None and torch.is_tensor(img_u8) and (view is not None or img_u8.dim() == 4):
+            self._dst_check(out_view, out, tuple(view.size) if view is not None else tuple(img_u8.shape[1:3]), img_u8.shape[0])
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
-        out = torch.empty(tuple(img.shape) if view is None else (img.shape[0],) + tuple(view.size) + (3,), device=img.device, dtype=torch.uint8)   # a view: [N, h, w, 3] in the source's colour order
+        if out_view is not None:
+            out = self._dst_out(out_view, out, tuple(view.size) if view is not None else (int(img.shape[1]), int(img.shape[2])), img.shape[0], img.device)
+        else:
+            out = torch.empty(tuple(img.shape) if view is None else (img.shape[0],) + tuple(view.size) + (3,), device=img.device, dtype=torch.uint8)   # a view: [N, h, w, 3] in the source's colour order
 
         def one(i, eng, s):
             eng.set_output_overlay(pal)
+            eng.set_output_view(out_view)
             eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
@@ -593,6 +655,7 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             eng.set_output_overlay(pal)
+            eng.set_output_view(None)
             eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, nv)
         return out
@@ -611,10 +674,11 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("%s: expected %d surfaces, got %d" % (who, n, src.shape[0]))
         return src.contiguous(), (nv[0], nv[1]), nv
 
-    def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None, view=None):
+    def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None, view=None,
+                       out_view=None, out=None):
         """uint8 labels [N, H, W] (CUDA) of this model blended over their source frames -> [N, Hs, Ws, 3]; src: uint8 [N, Hs, Ws, 3], or with
         src_size=(Hs, Ws) NV12 surfaces [N, rows, pitch].  After forward_labels_conf_u8 with a reject_label outside the palette: the overlay over
-        the accepted pixels only."""
+        the accepted pixels only (out_view: see _dst_out)."""
         if self._engine is None:
             raise RuntimeError("labels_overlay(): no handle yet")
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
@@ -628,7 +692,10 @@ class _TDNetBase(nn.Module):
         else:
             img, (Hs, Ws), nv = self._overlay_source("labels_overlay()", src, labels.shape[0], src_size, uv_offset, standard)
         pal = self._palette_rgba(palette, alpha)
-        out = torch.empty((labels.shape[0], Hs, Ws, 3), device=labels.device, dtype=torch.uint8)
+        if out_view is not None:
+            out = self._dst_out(out_view, out, (Hs, Ws), labels.shape[0], labels.device)
+        else:
+            out = torch.empty((labels.shape[0], Hs, Ws, 3), device=labels.device, dtype=torch.uint8)
         eng = self._engine
         if view is not None:
             eng.set_input_view(view, mean, std)
@@ -637,6 +704,7 @@ class _TDNetBase(nn.Module):
         else:
             eng.set_input_nv12(*nv, mean=mean, std=std)
         eng.set_output_overlay(pal)
+        eng.set_output_view(out_view)
         s = torch.cuda.current_stream(labels.device).cuda_stream
         for i in range(labels.shape[0]):
             eng.labels_overlay(labels[i].data_ptr(), img[i].data_ptr(), out[i].data_ptr(), s)
@@ -833,6 +901,7 @@ class _TDNetBase(nn.Module):
                 raise RuntimeError("propagate(labels=\"overlay\"): src is not of the size and format of the frame that was encoded (encode_u8 / encode_nv12)")
             out = torch.empty((1, Hs, Ws, 3), device=dev, dtype=torch.uint8)
             self._engine.set_output_overlay(pal)
+            self._engine.set_output_view(None)
             self._pending_shape = None
             self._engine.propagate_overlay(img.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             return out
@@ -851,6 +920,7 @@ class _TDNetBase(nn.Module):
         if labels == "rgb":
             out = self._rgb_out(1, out_size, dev)
             self._engine.set_output_rgb(out.shape[1], out.shape[2], self._palette(palette))
+            self._engine.set_output_view(None)
             self._pending_shape = None
             self._engine.propagate_rgb(out.data_ptr(), s)
             return out

@@ -87,6 +87,12 @@ def test(args):
             raise SystemExit("--overlay, --rgb and --gt_path ask for different last kernels: choose one")
         if not 0.0 <= overlay <= 1.0:
             raise SystemExit("--overlay: an opacity in 0..1 expected, got %r" % (overlay,))
+    out_nv12 = getattr(args, "out_nv12", None)
+    if out_nv12 is not None:                                           # checked before anything is loaded
+        if not (u8 or nv12) or not (rgb or overlay is not None):
+            raise SystemExit("--out_nv12 writes the frame's picture as NV12 surfaces: give --rgb or --overlay, and --u8 or --nv12, with it")
+        if getattr(args, "prefetch", False) or getattr(args, "gt_path", None) or getattr(args, "conf", None) is not None or getattr(args, "min_conf", None) is not None:
+            raise SystemExit("--out_nv12 belongs to the frame-by-frame picture loop: not with --prefetch, --gt_path, --conf or --min_conf")
     vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8, as_nv12=nv12,
                                nv12_standard=nv12_std)
     vid_seq.load_frames()
@@ -183,6 +189,27 @@ def test(args):
             return model.forward_overlay_nv12(image, pos_id, src_size, (H, W), alpha=overlay, standard=nv12_std)
         return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay, view=view)
 
+    raw_files = {}
+
+    def pictures_nv12(l8, image, ori_size, src_size, view, folder):
+        """--out_nv12: the picture of the frame's uint8 labels twice, by the unfused entries -- contiguous RGB for the PNG (byte for byte the fused entry's)
+        and through an NV12 destination view, the whole tight surface, appended to the clip's raw file (what `-f rawvideo -pix_fmt nv12` reads)."""
+        from tdnet_amd.dataloader import PIX_NV12, SourceView
+        if rgb:
+            size = (ori_size[1] // 4, ori_size[0] // 4)
+            draw = lambda **kw: model.labels_rgb(l8, size, **kw)
+        else:
+            draw = lambda **kw: model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, view=view, **kw)
+        picture = draw()
+        surf = draw(out_view=SourceView(PIX_NV12, int(picture.shape[1]), int(picture.shape[2]), standard=nv12_std))
+        if folder not in raw_files:                                    # one raw file per clip: the first clip's is FILE itself
+            root, ext = os.path.splitext(out_nv12)
+            raw_files[folder] = out_nv12 if not raw_files else root + "." + folder + ext
+            open(raw_files[folder], "wb").close()
+        with open(raw_files[folder], "ab") as f:
+            f.write(surf[0].cpu().numpy().tobytes())
+        return picture
+
     timer, i = 0.0, -1
     with torch.no_grad():
         if args.prefetch:
@@ -242,6 +269,10 @@ def test(args):
                 output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, view=view)
             elif gt is not None:
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
+            elif out_nv12 is not None:
+                l8 = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std) if nvp else \
+                    model.forward_labels_u8(image, i % path_num, (H, W), view=view)
+                output = pictures_nv12(l8, image, ori_size, src_size, view, folder)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size, view)
             elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
@@ -306,5 +337,6 @@ if __name__ == "__main__":
     parser.add_argument("--conf", nargs="?", type=str, default=None, help="directory for each frame's confidence map (grey PNG at the network size; 255 = certain)")
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
+    parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
     parser.add_argument("--crop", nargs="?", type=str, default=None, help="with --u8 or --nv12: Y,X,H,W -- the frames are uploaded whole and the rectangle is taken on the device, in the frame's first launch (a source view)")
     test(parser.parse_args())
