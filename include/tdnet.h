@@ -63,15 +63,17 @@ typedef struct tdnet_cfg {
 #define TDNET_FUSION_SPLIT_NARROW 524288   /* precision 2: the narrow direct convs and the packed-row stem on the split bf16 MFMA */
 #define TDNET_FUSION_LATE_CHAIN 1048576    /* the cache-only attention chain forks in front of the first dilated block */
 #define TDNET_FUSION_PPM_FOLD 2097152      /* fp32: the pyramid folded through the Encoding's first 1x1 convs as 64 basis columns (no `z` map) */
+#define TDNET_FUSION_WINO_F64 4194304     /* fp32: ResNet layer1's 64 -> 64 3x3 convs on the fused Winograd F(4x4) kernel (large maps) */
 #define TDNET_OVERLAP_CHAINS 1             /* row-parity chains on two streams */
 #define TDNET_OVERLAP_LOWREG_TRANSFORMS 2  /* the low-register F(4x4) transform kernels everywhere */
 #define TDNET_OVERLAP_CHAINS_ANY_SIZE 4    /* the chains at any map size */
 #define TDNET_OVERLAP_GEMM_DMA 8           /* the Winograd GEMMs on the LDS-DMA-fed kernel */
 #define TDNET_OVERLAP_VW_SHIFT 4           /* bits 4-5: log2 of the channels per lane of the chunked transform kernels */
 #define TDNET_OVERLAP_VW_MASK 0x30
-/* 4169766: the measured default (measurements: DESIGN.md 5, DESIGN_experiments.md) */
+/* 8364070: the measured default (measurements: DESIGN.md 5, DESIGN_experiments.md) */
 #define TDNET_FUSION_DEFAULT (TDNET_FUSION_LN_STATS | TDNET_FUSION_LN_IN_HEAD | TDNET_FUSION_A_DIRECT | TDNET_FUSION_DMA_LOADERS | TDNET_FUSION_DMA_NARROW | \
-                              TDNET_FUSION_STEM_ROWS | TDNET_FUSION_CONV_GROUPS | TDNET_FUSION_CLS_IN_HEAD | TDNET_FUSION_SPLIT_NARROW | TDNET_FUSION_LATE_CHAIN | TDNET_FUSION_PPM_FOLD)
+                              TDNET_FUSION_STEM_ROWS | TDNET_FUSION_CONV_GROUPS | TDNET_FUSION_CLS_IN_HEAD | TDNET_FUSION_SPLIT_NARROW | TDNET_FUSION_LATE_CHAIN | TDNET_FUSION_PPM_FOLD | \
+                              TDNET_FUSION_WINO_F64)
 #define TDNET_FUSION_MASK TDNET_FUSION_DEFAULT   /* the bits of tdnet_opts.fusion that exist (= the default); the others are cleared and ignored */
 /* 41: row-parity chains with 4 channels per lane (+2 %) on the LDS-DMA-fed GEMM (+0.9 %): profiles/r03a_*, r03m_* */
 #define TDNET_OVERLAP_DEFAULT (TDNET_OVERLAP_CHAINS | TDNET_OVERLAP_GEMM_DMA | (2 << TDNET_OVERLAP_VW_SHIFT))
@@ -115,6 +117,9 @@ typedef struct tdnet_opts {
                                      G = pooled features x the layer's pyramid weights, computed per frame (k_ppm_fold_g).  Same gates, not bit-identical (another
                                      summation order); tdnet_get_stage("z") assembles the map on request.  Taken where those convs are planned on the persistent
                                      GEMM / the direct 1x1 kernel and XS % 64 == 0; otherwise the frame runs as without the bit.
+                                4194304 = fp32 (precision 0) with winograd >= 3: a 3x3 stride-1 conv from 64 to 64 channels (ResNet layer1, the deep stem's second conv)
+                                     on a map of >= 32768 output pixels runs on ONE fused Winograd F(4x4,3x3) kernel that keeps the transformed tiles in LDS
+                                     (k_wino4_f64, td_wino_f64.h) instead of the direct kernel.  Same gates, not bit-identical; smaller maps keep the direct kernel.
                                 Retired, ignored: 1, 8, 16, 64, 128, 256, 512, 1024, 2048, 4096, 16384 (DESIGN_experiments.md 4.4, 10.10).   */
     int32_t overlap;         /* bit mask (default TDNET_OVERLAP_DEFAULT), on BasicBlock backbones:
                                 1 = the trailing run of even-dilation convs (ResNet layers 3-4: resnet.py:181-198) as its even-row and odd-row halves

@@ -19,7 +19,7 @@ extern "C" {
 /* Roofline / tuning probes: sustained fp32-MFMA TFLOP/s of a register-only MFMA loop, and the average device ms of
  * `iters` launches of one conv configuration (random data, tile as in tdnet_op_conv2d).                             */
 double tdnet_bench_mfma_peak(int waves_per_simd, int iters, void* stream);
-double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int stride, int dil, int tile /* -1: heuristic */, int iters,
+double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int stride, int dil, int tile /* -1: heuristic, -2: the fused 64-channel Winograd kernel at any size */, int iters,
                         const tdnet_opts* opts /* NULL = defaults */, void* stream);
 
 /* ---- single-operator entry points (used by tests/ to check each kernel family against torch fp32) -------------- */
@@ -30,6 +30,11 @@ int tdnet_op_conv2d(const float* in_dev, int H, int W, int Cin, const float* w_h
                     const tdnet_opts* opts /* NULL = defaults */,
                     int tile /* -1 = heuristic; 0: 128x128, 1: 64x128, 2: 128x64, 3..5: the same on the two-stage pipeline */,
                     float* out_dev, void* stream);
+/* A conv on the fused 64-channel Winograd F(4x4,3x3) kernel (k_wino4_f64, tdnet_opts.fusion bit 4194304) at ANY map size: a frame takes that route only from
+ * 32768 output pixels on, so small maps reach the kernel through this entry alone.  Arguments as tdnet_op_conv2d's.  The route takes Cin = Cout = 64, KS 3,
+ * stride 1, dil 1, act 0 / 1; anything else fails before a byte is allocated or a kernel launched.                                                     */
+int tdnet_op_conv_wino_f64(const float* in_dev, int H, int W, int Cin, const float* w_host, const float* bias_host,
+                           int Cout, int KS, int stride, int dil, const float* resid_dev, int act, float* out_dev, void* stream);
 /* the same conv with the fp16 activation STORAGE of tdnet_opts.precision = 1: in / resid are rounded to fp16 maps in HBM, the kernel
  * reads and writes fp16 (fp16 MFMA, fp32 accumulate), the fp16 result is widened into out_dev.  Cin % 64 == 0.
  * tile: -1 = heuristic, 0..5 as tdnet_op_conv2d, or a form of the LDS-DMA kernel (td_conv_hd.h): 16 / 17 / 18 / 19 = 128 / 192 / 256 rows,

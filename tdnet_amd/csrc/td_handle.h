@@ -23,6 +23,7 @@
 #include "td_conv_hd.h"
 #include "td_conv_ad.h"
 #include "td_wino.h"
+#include "td_wino_f64.h"
 #include "td_gemm.h"
 #include "td_gemm_dma.h"
 #include "td_gemm_b3.h"
@@ -152,7 +153,8 @@ enum ConvRoute {
     CR_STEM_H,                                                         // precision 1: the 7x7 stem on the fp16 MFMA (td_conv_h.h)
     CR_CONV_H,                                                         // precision 1: fp16-MFMA operands, register-staged (td_conv_h.h)
     CR_CONV_DMA,                                                       // precision 1, fp16 map in: the LDS-DMA kernel, tile form `rh` (td_conv_hd.h)
-    CR_WINO                                                            // Winograd F(4x4,3x3): d_wp = 36 packed 1x1 weight sets, `gemm` runs them (td_wino.h)
+    CR_WINO,                                                           // Winograd F(4x4,3x3): d_wp = 36 packed 1x1 weight sets, `gemm` runs them (td_wino.h)
+    CR_WINO_F64                                                        // fp32, 64 -> 64 3x3 on a large map: the fused F(4x4,3x3) kernel, one launch (td_wino_f64.h; fusion bit 4194304)
 };
 enum GemmKernel {
     GK_CONV,                                                           // one tile per workgroup on the conv kernel (gemm_persistent = 0, or K % 64 != 0)
@@ -183,7 +185,7 @@ struct ConvLayer {
 };
 
 // Per-handle kernel configuration (include/tdnet.h tdnet_opts); nothing here is process-wide: two handles in one process may differ.
-static_assert(TDNET_FUSION_DEFAULT == 4169766 && TDNET_FUSION_MASK == 4169766 && TDNET_OVERLAP_DEFAULT == 41 && TDNET_OVERLAP_MASK == 0x3f,
+static_assert(TDNET_FUSION_DEFAULT == 8364070 && TDNET_FUSION_MASK == 8364070 && TDNET_OVERLAP_DEFAULT == 41 && TDNET_OVERLAP_MASK == 0x3f,
               "the named option bits of include/tdnet.h must add up to the documented values");
 static tdnet_opts opts_or_default(const tdnet_opts* o) {
     tdnet_opts d;

@@ -176,10 +176,13 @@ static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
         }
         return run_wino(n, L, in, H, W, resid, out, s, lnf, WinoChunk(), nullptr, nullptr, cls);
     }
+    if (L.route == CR_WINO_F64 && !wino_f64_size_ok(H, W)) return td_fail("internal: this map is too large for the fused Winograd kernel");
     const ConvArgs a = conv_args(L, in, H, W, resid, out);
+    // the fused F(4x4) kernel's record carries the executed FLOP (36 products per tile, channel pair: a quarter of the direct conv's)
+    const double flops = L.route == CR_WINO_F64 ? 2.0 * 36 * (double)wino_tiles(H, W, 1, 4) * L.Cin * L.Cout : L.flops_per_pixel() * a.M;
     // dominant: bits 0-1 = 1 for the 128x128-tile / LDS-DMA 3x3 convs (the kernel set of rounds 3-4), bit 2 = EVERY 3x3 conv that reads an fp16 map
     // (the fixed set of the fp16 mode's roofline since round 5: routing a layer to another kernel does not change it)
-    prof_begin(n, 0, (((L.tile == CT_128x128 || L.tile == CT_128x128_DEEP || L.rh) && L.KS == 3 && !L.stem) ? 1 : 0) | ((L.h16() && L.in16 && L.KS == 3 && !L.stem) ? 4 : 0), L.flops_per_pixel() * a.M, s);
+    prof_begin(n, 0, (((L.tile == CT_128x128 || L.tile == CT_128x128_DEEP || L.rh) && L.KS == 3 && !L.stem) ? 1 : 0) | ((L.h16() && L.in16 && L.KS == 3 && !L.stem) ? 4 : 0), flops, s);
     switch (L.route) {
     case CR_STEM_H: conv_launch_stem_h(a, L.out16, s); break;
     case CR_CONV_DMA: launch_conv_dma_forms(L, a, s); break;
@@ -196,6 +199,7 @@ static int run_conv(tdnet* n, const ConvLayer& L, const float* in, int H, int W,
     }
     case CR_ADIRECT: conv_launch_adirect(a, L.KS, L.stem ? 1 : 0, s); break;
     case CR_IGEMM: conv_launch(a, L.tile, L.KS, L.stem, s); break;
+    case CR_WINO_F64: wino_f64_launch(in, L.d_wp, L.d_bias, resid, out, H, W, L.act, s); break;   // (size checked above)
     case CR_WINO: break;                                               // (ran above)
     }
     prof_end(n, s);

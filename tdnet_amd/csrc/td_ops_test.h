@@ -27,6 +27,37 @@ extern "C" int tdnet_op_conv2d(const float* in, int H, int W, int Cin, const flo
     free_conv_layer(L);
     return rc;
 }
+// The plan of tdnet_op_conv_wino_f64 (and tdnet_bench_conv's tile -2): the fused 64-channel Winograd route (fusion bit 4194304, td_wino_f64.h) whatever the
+// map size -- plan_conv's own rule with the size it asks for.  An error, nothing allocated, for a conv the route does not take.
+static int op_plan_wino_f64(const char* who, ConvLayer& L, int H, int W, int Cin, int Cout, int KS, int stride, int dil, int act) {
+    tdnet_opts o = opts_or_default(nullptr);
+    o.fusion |= TDNET_FUSION_WINO_F64;
+    if (H < 1 || W < 1) return td_fail("%s: empty input", who);
+    if (!plan_wino_f64(o, Cout, Cin, KS, stride, dil, act, false, false, 1))
+        return td_fail("%s: the fused Winograd kernel takes a 3x3 stride-1 dilation-1 conv from 64 to 64 channels with act 0 or 1 (got %d -> %d, KS %d, stride %d, dil %d, act %d)",
+                       who, Cin, Cout, KS, stride, dil, act);
+    if (!wino_f64_size_ok(H, W))
+        return td_fail("%s: the fused Winograd kernel addresses a map of at most %ld pixels with its 32-bit byte offsets (got %d x %d)", who, TD_WINO_F64_MAX_PIXELS, H, W);
+    TD_TRY(plan_conv(L, Cout, Cin, KS, stride, dil, act, false, std::max<long>((long)H * W, TD_WINO_F64_MIN_PIXELS), o));
+    if (L.route != CR_WINO_F64) return td_fail("%s: internal: the conv was not planned on the fused Winograd kernel", who);
+    return 0;
+}
+// A conv on the fused 64-channel Winograd F(4x4) kernel (k_wino4_f64) at ANY map size -- a frame takes the route from TD_WINO_F64_MIN_PIXELS output pixels on.
+// Arguments as tdnet_op_conv2d's (resid may be NULL).
+extern "C" int tdnet_op_conv_wino_f64(const float* in, int H, int W, int Cin, const float* w_host, const float* bias_host, int Cout, int KS,
+                                      int stride, int dil, const float* resid, int act, float* out, void* stream) {
+    const char* who = "tdnet_op_conv_wino_f64";
+    if (!in || !w_host || !out) return td_fail("%s: in, weight and out expected", who);
+    ConvLayer L;
+    TD_TRY(op_plan_wino_f64(who, L, H, W, Cin, Cout, KS, stride, dil, act));
+    std::vector<float> w(w_host, w_host + (size_t)Cout * Cin * KS * KS), b;
+    if (bias_host) b.assign(bias_host, bias_host + Cout);
+    int rc = upload_conv(L, w, b);
+    if (!rc) rc = run_conv(nullptr, L, in, H, W, resid, out, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    free_conv_layer(L);
+    return rc;
+}
 // The plan of a conv of tdnet_op_conv2d_f16io / _f16mix: tile code -> forced tile / LDS-DMA form, then plan_conv with precision = 1.  Shared by the single-conv entries and
 // tdnet_op_conv_group_f16, so that a group's member is the layer the single entry runs.  Nothing is allocated.
 static int op_plan_conv_h(const char* who, ConvLayer& L, int H, int W, int Cin, int Cout, int KS, int stride, int dil, int act, int tile, bool in16, bool out16) {
@@ -740,7 +771,7 @@ extern "C" double tdnet_bench_mfma_peak(int waves_per_simd, int iters, void* str
 extern "C" double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int stride, int dil, int tile, int iters,
                                    const tdnet_opts* opts, void* stream) {
     const tdnet_opts o = opts_or_default(opts);
-    if ((KS != 1 && KS != 3) || Cin % 32 || tile < -1 || tile >= CT_COUNT) { td_fail("tdnet_bench_conv: bad arguments"); return -1.0; }
+    if ((KS != 1 && KS != 3) || Cin % 32 || tile < -2 || tile >= CT_COUNT) { td_fail("tdnet_bench_conv: bad arguments"); return -1.0; }
     hipStream_t s = (hipStream_t)stream;
     ConvLayer L;
     std::vector<float> w((size_t)Cout * Cin * KS * KS), x((size_t)H * W * Cin), b(Cout, 0.1f);
@@ -751,7 +782,9 @@ extern "C" double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int 
     const int pad_ = dil * (KS / 2);
     const long M_ = (long)out_size(H, KS, stride, dil, pad_) * out_size(W, KS, stride, dil, pad_);
     // tile -1: the heuristic's choice for this M; overlap bit 1: the conv as its 2 row classes one after the other on the stream
-    if (plan_conv(L, Cout, Cin, KS, stride, dil, 1, false, M_, o, tile, (o.overlap & TDNET_OVERLAP_CHAINS) ? 2 : 1) || upload_conv(L, w, b)) return -1.0;
+    // tile -2: the fused 64-channel Winograd kernel whatever the map size (tdnet_op_conv_wino_f64's plan; opts are not read)
+    if ((tile == -2 ? op_plan_wino_f64("tdnet_bench_conv", L, H, W, Cin, Cout, KS, stride, dil, 1)
+                    : plan_conv(L, Cout, Cin, KS, stride, dil, 1, false, M_, o, tile, (o.overlap & TDNET_OVERLAP_CHAINS) ? 2 : 1)) || upload_conv(L, w, b)) return -1.0;
     float *din = nullptr, *dout = nullptr;
     if (upload(&din, x)) return -1.0;
     const int Ho = out_size(H, KS, stride, dil, L.pad), Wo = out_size(W, KS, stride, dil, L.pad);

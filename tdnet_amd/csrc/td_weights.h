@@ -28,6 +28,13 @@ static int plan_dma_form(const ConvLayer& c, long M, const tdnet_opts& o) {
     return rh;
 }
 
+// Whether the options and the conv's geometry admit the fused 64-channel Winograd kernel (fusion bit 4194304); plan_conv adds the size rule
+// M >= TD_WINO_F64_MIN_PIXELS, the tests' operator entry (tdnet_op_conv_wino_f64) runs the route at any size.
+static bool plan_wino_f64(const tdnet_opts& o, int Cout, int Cin, int KS, int stride, int dil, int act, bool stem, bool forced_tile, int chunks) {
+    return (o.fusion & TDNET_FUSION_WINO_F64) && o.winograd >= 3 && o.precision == 0 && !forced_tile && chunks == 1 &&
+           wino_f64_supports(Cout, Cin, KS, stride, dil, act, stem);
+}
+
 // Which kernel a conv layer with an output of M pixels runs on: route, GEMM kernel, tile, CoutPad, nsteps, rh -- and with them the format upload_conv packs
 // the weights in.  Decided here once, from the geometry and the options alone: pure host arithmetic, no HIP call, no allocation.
 // in16 / out16: the layer's maps are stored as fp16 (they hold for the fp16 routes only); rh: see RH_FRAME; rowimg_off: ConvLayer.
@@ -43,6 +50,12 @@ static int plan_conv(ConvLayer& L, int Cout, int Cin, int KS, int stride, int di
     const bool pers_gemm = o.gemm_persistent && gemm_supports(Cin);     // a GEMM over this K runs on the persistent kernels
     const bool split = o.precision >= 2;                                // the fp32-accurate kernels on the bf16 MFMA
     const bool split_narrow = split && (o.fusion & TDNET_FUSION_A_DIRECT) && (o.fusion & TDNET_FUSION_SPLIT_NARROW);
+    // fp32, 64 -> 64 channels on a large map (ResNet layer1): the fused F(4x4) kernel, V and M in LDS (td_wino_f64.h); ahead of the unfused route of winograd = 4
+    if (plan_wino_f64(o, Cout, Cin, KS, stride, dil, act, stem, forced, chunks) && M >= TD_WINO_F64_MIN_PIXELS && M <= TD_WINO_F64_MAX_PIXELS) {   // a larger map keeps the direct kernel
+        L.route = CR_WINO_F64;
+        L.nsteps = 0; L.CoutPad = Cout;
+        return 0;
+    }
     if (o.winograd && o.precision != 1 && !stem && KS == 3 && stride == 1 && Cin % 32 == 0 && Cout % 4 == 0 && (o.winograd == 4 || (Cin >= 128 && Cout >= 128))) {
         L.route = CR_WINO;
         L.wino = 4;
@@ -142,7 +155,9 @@ static int upload_conv(ConvLayer& L, const std::vector<float>& w, const std::vec
         const size_t per = L.gemm == GK_B3 ? gemm_b3_packed_bytes(Cin, Cout) / 2 : tile_image;
         if (L.gemm == GK_B3) TD_TRY(upload_packed<bf16>(&L.d_wp, nb * per, [&](bf16* p) { for (int bi = 0; bi < nb; ++bi) gemm_b3_pack(U[bi].data(), Cout, Cin, p + bi * per); }));
         else TD_TRY(upload_packed<float>(&L.d_wp, nb * per, [&](float* p) { for (int bi = 0; bi < nb; ++bi) conv_pack_weights(U[bi].data(), Cout, Cin, 1, 0, L.tile, p + bi * per); }));
-    } else if (L.route == CR_STEM_H)
+    } else if (L.route == CR_WINO_F64)
+        TD_TRY(upload_packed<float>(&L.d_wp, wino_f64_packed_floats(), [&](float* p) { wino_f64_pack(w.data(), p); }));
+    else if (L.route == CR_STEM_H)
         TD_TRY(upload_packed<_Float16>(&L.d_wp, 2 * tile_image, [&](_Float16* p) { conv_pack_weights_stem_h(w.data(), Cout, L.tile, p); }));
     else if (L.h16())
         TD_TRY(upload_packed<_Float16>(&L.d_wp, 2 * tile_image, [&](_Float16* p) { conv_pack_weights_h(w.data(), Cout, Cin, KS, L.tile, p); }));

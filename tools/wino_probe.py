@@ -14,7 +14,7 @@ for (nm, H, W, Cin, Cout, d) in SHAPES:
     gf = 2.0 * H * W * Cout * Cin * 9 / 1e9
     out = []
     for mode in (0, 4):
-        o = lib.opts(winograd=mode)
+        o = lib.opts(winograd=mode, fusion=lib.opts().fusion & ~4194304)   # bit 4194304 clear: "F4" is the unfused route for layer1's shape too (the fused kernel: tools/wino_f64_probe.py)
         ms = min(lib.tdnet_bench_conv(H, W, Cin, Cout, 3, 1, d, -1, 20, ctypes.byref(o), None) for _ in range(2))
         out.append("%s %.3f ms (%.0f TF eff.)" % ({0: "direct", 4: "F4"}[mode], ms, gf / ms))
     print("%-24s %6.1f GFLOP  %s" % (nm, gf, "   ".join(out)), flush=True)

@@ -9,7 +9,7 @@ SHAPES = [("layer4 512->512 d4", 128, 256, 512, 512, 4), ("layer4 256->512 d4", 
           ("layer3.0 128->256 d1", 128, 256, 128, 256, 1), ("head 512->128", 128, 256, 512, 128, 1), ("layer2 128->128", 128, 256, 128, 128, 1),
           ("layer1 64->64", 256, 512, 64, 64, 1), ("native l4 512->512 d4", 97, 193, 512, 512, 4), ("native l3 256->256 d2", 97, 193, 256, 256, 2)]
 names = {3: "128x128", 4: "64x128", 5: "128x64", -1: "auto"}
-o = lib.opts(winograd=4)
+o = lib.opts(winograd=4, fusion=lib.opts().fusion & ~4194304)   # bit 4194304 clear: layer1's shape on the unfused route too, not on k_wino4_f64 (tools/wino_f64_probe.py times that)
 for (nm, H, W, Cin, Cout, d) in SHAPES:
     row = []
     for t in (-1, 3, 4, 5):
