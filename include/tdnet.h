@@ -280,6 +280,76 @@ typedef struct tdnet_view {
     uint64_t uv_offset;              /* NV12: 0 = height * pitch; otherwise must be 0                                */
 } tdnet_view;
 int  tdnet_set_input_view(tdnet_t* h, const tdnet_view* v, const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
+/* ---- surfaces: NV21, I420 / YV12, P010, YUY2, UYVY, and NV12 with a chroma pitch of its own ------------------------------
+ * What the other producers hand over: 10-bit hardware decoders (P010), software decoders (I420 / YV12: three planes, a chroma pitch of its own), Android and
+ * camera stacks (NV21), webcams and capture cards (YUY2 / UYVY, packed 4:2:2).  A SURFACE is a rectangle of a YUV frame whose planes lie in ONE allocation
+ * behind `base`; the handle reads it in the frame's first launch (and, for "overlay out", in its last), BIT-IDENTICALLY to converting on the host and calling
+ * the uint8 entries, with the same FIFO step and the same tdnet_last_launch_count.  The contract of "source views"; a struct of its own because tdnet_view
+ * has one pitch and one chroma offset.
+ *   samples     (Y, X) = a pixel's ABSOLUTE frame coordinates, crop origin + rectangle coordinates (an odd origin shifts the chroma phase).
+ *               w16(p) = p[0] | p[1] << 8, read bytewise: `base` may be any byte address, an odd one included, also for P010.
+ *                 layout  luma                            U                                                              V
+ *                 NV12    base[Y pitch + X]               base[u_offset + (Y >> 1) chroma_pitch + 2 (X >> 1)]            the next byte
+ *                 NV21    as NV12                         the byte after V                                               base[u_offset + (Y >> 1) chroma_pitch + 2 (X >> 1)]
+ *                 I420    as NV12                         base[u_offset + (Y >> 1) chroma_pitch + (X >> 1)]              base[v_offset + ...], the same index
+ *                 P010    w16(base + Y pitch + 2 X) >> 6  w16(base + u_offset + (Y >> 1) chroma_pitch + 4 (X >> 1)) >> 6 the next word >> 6
+ *                 YUY2    base[Y pitch + 2 X]             base[Y pitch + 4 (X >> 1) + 1]                                 ... + 3
+ *                 UYVY    base[Y pitch + 2 X + 1]         base[Y pitch + 4 (X >> 1)]                                     ... + 2
+ *               Row bytes, the lower bounds of the pitches, cw = ceil(width / 2): luma width (P010: 2 width; 4:2:2: 4 cw); chroma 2 cw (I420: cw; P010: 4 cw).
+ *   8 bit       exactly the int32 formulas and constants of "NV12 frames in" on that (Y, U, V).
+ *   P010        the same five decimals per standard with K = rint(c * 2^18), on the 10-bit samples (the low 6 bits of every word are ignored):
+ *                 yy = max(0, Y10 - 4 yoff) * CY + (1 << 19);  u = U10 - 512;  v = V10 - 512
+ *                 R = clamp8((yy + CVR v) >> 20);  G = clamp8((yy + CVG v + CUG u) >> 20);  B = clamp8((yy + CUB u) >> 20)
+ *               (|sum| <= 5.96e8 < 2^31 over the four standards; BT.709 limited: CY 305136, CUB 553648, CUG -55837, CVG -139723, CVR 470024).  ONE rounding
+ *               from 10 bits: the samples are not truncated to 8 bits first.
+ *               The frame is then exactly what tdnet_set_input_u8(crop_height, crop_width, mean, std) computes on those RGB bytes: every resize tap converted
+ *               and clamped first, then interpolated, then normalised.  "Overlay out" over a surface writes r g b, as for NV12.
+ *   memory      extent = the largest end over the planes (last row's start + row bytes).  Nothing outside [base, base + extent) is read, and the result does
+ *               not depend on any byte that is not a sample covering the rectangle: not on pitch padding, plane gaps, the other samples of the frame or the
+ *               low 6 bits of P010's words.  The overlay entries keep refusing an out that overlaps the extent.
+ * tdnet_set_input_surface: the fourth sibling of tdnet_set_input_u8 / tdnet_set_input_nv12 / tdnet_set_input_view (configuration, not a frame call: it may
+ * synchronise; idempotent for equal arguments; per handle; ONE byte-input configuration at a time; independent of the order of the other tdnet_set_* calls):
+ * afterwards every byte entry reads its image pointer as the surface's `base`.  Its tables are counted in tdnet_memory_bytes.  Fails -- leaving the previous
+ * configuration in force and the FIFO alone, the message naming this call and the offending field -- on a handle that is not finalized, a NULL surface, a layout
+ * outside 0..5, frame or rectangle sizes below 1, a rectangle not inside the frame, a negative origin, a pitch or chroma_pitch below its row's bytes, a
+ * non-zero reserved, a standard outside 0..3, chroma_pitch / u_offset / v_offset non-zero where the struct says 0, planes that overlap each other or the luma
+ * plane (in any order: V before U is legal), an extent of 2^31 bytes or more, a bad mean or std, and a column downscale beyond what one strip stages (P010
+ * stages twice the bytes of the 8-bit layouts).
+ * Surfaces as DESTINATIONS: the mirror, with the contract of "destination views" -- the picture entries' picture pointer is the surface's `base`, the
+ * rectangle must be the picture's size (the frame entry checks, naming both), the same picture, FIFO step and tdnet_last_launch_count, entries only enqueue and
+ * work inside a hipGraph capture.  Layouts NV12, NV21, I420 and P010; YUY2 / UYVY are refused by name (no encoder takes them).  crop_y and crop_x must be even;
+ * h and w may be odd.
+ *   8 bit       the forward formulas, constants K = rint(c * 2^20) and chroma averaging (S over the n in {1, 2, 4} pixels of a pair, m = 4 / n) of
+ *               "destination views"; the bytes are placed by the table above.
+ *   P010        the same K:
+ *                 Y10 = clamp10((KYR R + KYG G + KYB B + (yoff << 20) + (1 << 17)) >> 18)
+ *                 U10 = clamp10((m (KUR S_R + KUG S_G + KUB S_B) + (128 << 22) + (1 << 19)) >> 20),  V10 likewise with the V row,
+ *               each stored as the word value << 6, little-endian, the low bits zero (BT.601 limited white: 940 / 512 / 512; BT.709 limited: 940 / 511 / 512, its U decimals sum to -0.001).  Every sum stays below 2^31.
+ *   memory      only the sample bytes of the rectangle are written (its luma samples and the chroma samples covering it); everything else inside and outside
+ *               [base, base + extent) keeps its bytes.  The overlay entries refuse a destination extent that overlaps the source extent.
+ * tdnet_set_output_surface and tdnet_set_output_view replace each other: ONE destination at a time, NULL to either restores the contiguous [h][w][3] block.
+ * Configuration like tdnet_set_output_view (plain host state: nothing is allocated; idempotent; per handle; independent of the order of the other tdnet_set_*
+ * calls).  Fails -- leaving the previous destination in force and the FIFO alone, the message naming this call and the offending field -- on the conditions of
+ * tdnet_set_input_surface that concern the surface, a YUY2 / UYVY layout, an odd origin, and a rectangle of more than 65535 rows.                        */
+#define TDNET_SURF_NV12 0   /* Y plane; U,V byte pairs                                  4:2:0 */
+#define TDNET_SURF_NV21 1   /* Y plane; V,U byte pairs                                  4:2:0 */
+#define TDNET_SURF_I420 2   /* Y, U, V planes (YV12 = the two chroma offsets exchanged) 4:2:0 */
+#define TDNET_SURF_P010 3   /* NV12 in 16-bit little-endian words, the sample in bits 15..6    */
+#define TDNET_SURF_YUY2 4   /* one plane, per pixel pair the bytes Y0 U Y1 V            4:2:2 */
+#define TDNET_SURF_UYVY 5   /* one plane, per pixel pair the bytes U Y0 V Y1            4:2:2 */
+typedef struct tdnet_surface {
+    int32_t  layout;                 /* TDNET_SURF_* */
+    int32_t  height, width;          /* the WHOLE frame, in pixels */
+    int32_t  pitch;                  /* bytes per luma (or packed) row; 0 = tight */
+    int32_t  chroma_pitch;           /* bytes per chroma row; 0 = pitch (NV12, NV21, P010), (pitch + 1) / 2 (I420); must be 0 for 4:2:2 */
+    int32_t  crop_y, crop_x, crop_height, crop_width;   /* all four 0 = the whole frame */
+    int32_t  standard;               /* TDNET_YUV_* */
+    int32_t  reserved[4];            /* must be 0 */
+    uint64_t u_offset;               /* the interleaved chroma plane, or I420's U plane; 0 = height * pitch; must be 0 for 4:2:2 */
+    uint64_t v_offset;               /* I420's V plane; 0 = u_offset + ceil(height / 2) * chroma_pitch; otherwise must be 0 */
+} tdnet_surface;
+int  tdnet_set_input_surface(tdnet_t* h, const tdnet_surface* s, const double* mean /* [3] | NULL */, const double* std /* [3] | NULL */);
+int  tdnet_set_output_surface(tdnet_t* h, const tdnet_surface* s /* NULL = contiguous [h][w][3] */);
 /* ---- colour map out ------------------------------------------------------------------------------------------------
  * What the reference's loop does on the host behind the labels (Testing/test.py:61-71): the label map resized with nearest sampling and
  * decode_segmap -- done by the frame's LAST kernel instead.  It evaluates the x8 upsample only at the sampled pixels, takes the first-maximum

@@ -138,6 +138,9 @@ long tdnet_op_stem_image_nv12(const uint8_t* surf_dev, int Hs, int Ws, int pitch
 /* tdnet_op_stem_image from a source view (include/tdnet.h "source views"; the arguments of tdnet_set_input_view): base_dev at any byte address. */
 long tdnet_op_stem_image_view(const uint8_t* base_dev, const tdnet_view* view, int H, int W, const double* mean, const double* std, int rows, float* out_dev,
                               size_t capacity, void* stream);
+/* tdnet_op_stem_image from a YUV surface (include/tdnet.h "surfaces"; the arguments of tdnet_set_input_surface): base_dev at any byte address. */
+long tdnet_op_stem_image_surface(const uint8_t* base_dev, const tdnet_surface* surface, int H, int W, const double* mean, const double* std, int rows, float* out_dev,
+                                 size_t capacity, void* stream);
 /* low-resolution logits [C,h,w] -> labels [H,W] (bilinear align_corners=True, first maximum): int32 through the kernel of tdnet_forward_labels
  * (labels_i32_dev != NULL) and / or uint8 (labels_u8_dev != NULL) through the kernel of its uint8 form.  C in 1..256. */
 int tdnet_op_upsample_argmax(const float* in_dev, int C, int h, int w, int H, int W, int32_t* labels_i32_dev, uint8_t* labels_u8_dev, void* stream);
@@ -156,6 +159,14 @@ int tdnet_op_overlay(const float* in_dev, int C, int h, int w, int H, int W, con
 /* tdnet_op_overlay with a source view in place of its source arguments: out_dev [h,w,3] of the view's rectangle h x w, in the source's colour order. */
 int tdnet_op_overlay_view(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* base_dev, const tdnet_view* view,
                           const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
+/* tdnet_op_overlay with a YUV surface in place of its source arguments: out_dev [h,w,3] of the surface's rectangle h x w, r g b. */
+int tdnet_op_overlay_surface(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* base_dev, const tdnet_surface* surface,
+                             const uint8_t* palette_rgba, int n_colours, uint8_t* out_dev, void* stream);
+/* tdnet_op_picture_view with surfaces: the destination is dst_surface (a 4:2:0 layout) or, dst_surface == NULL, dst_view; the overlay's source is src_surface
+ * or, src_surface == NULL, src_view; src_base_dev == NULL: the colour map oh x ow.  Exactly the kernels the frame entries launch for that pair.       */
+int tdnet_op_picture_surface(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_u8_dev, const uint8_t* palette, int n_colours,
+                             const uint8_t* src_base_dev, const tdnet_surface* src_surface, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base_dev,
+                             const tdnet_surface* dst_surface, const tdnet_view* dst_view, void* stream);
 /* The picture into a destination view (include/tdnet.h "destination views"), through exactly the kernels the frame entries launch with one in force:
  * of low-resolution logits [C,h,w] (labels_u8_dev == NULL) or of a uint8 label map [H,W] (in_dev, C, h, w are then ignored); the overlay over the source
  * view (src_base_dev, src_view; palette [n_colours][4] r g b a on the host) or, src_base_dev == NULL, the colour map oh x ow (palette [n_colours][3];

@@ -45,6 +45,13 @@ class TdnetView(ctypes.Structure):
                 ("standard", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5), ("uv_offset", ctypes.c_uint64)]
 
 
+class TdnetSurface(ctypes.Structure):
+    """include/tdnet.h tdnet_surface: a rectangle of a YUV frame in one of the TDNET_SURF_* layouts, its planes in one allocation."""
+    _fields_ = [("layout", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("pitch", ctypes.c_int32), ("chroma_pitch", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_x", ctypes.c_int32), ("crop_height", ctypes.c_int32), ("crop_width", ctypes.c_int32),
+                ("standard", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4), ("u_offset", ctypes.c_uint64), ("v_offset", ctypes.c_uint64)]
+
+
 class TdnetError(RuntimeError):
     pass
 
@@ -54,6 +61,7 @@ WINOGRAD_DEFAULT = 3          # include/tdnet.h TDNET_WINOGRAD_DEFAULT: F(4x4,3x
 c_opts_p = ctypes.POINTER(TdnetOpts)
 c_arch_p = ctypes.POINTER(TdnetArch)
 c_view_p = ctypes.POINTER(TdnetView)
+c_surface_p = ctypes.POINTER(TdnetSurface)
 
 SYMBOLS = {
     "tdnet_opts_default": (None, [c_opts_p]),
@@ -79,6 +87,8 @@ SYMBOLS = {
     "tdnet_set_input_nv12": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tdnet_set_input_view": (ctypes.c_int, [c_void_p, c_view_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "tdnet_set_input_surface": (ctypes.c_int, [c_void_p, c_surface_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "tdnet_set_output_surface": (ctypes.c_int, [c_void_p, c_surface_p]),
     "tdnet_forward_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_forward_u8_labels": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_argmax_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -162,6 +172,11 @@ TEST_SYMBOLS = {
                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "tdnet_op_stem_image_view": (ctypes.c_long, [c_void_p, c_view_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                  ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_op_stem_image_surface": (ctypes.c_long, [c_void_p, c_surface_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                    ctypes.c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tdnet_op_overlay_surface": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_surface_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_picture_surface": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_surface_p, c_view_p, ctypes.c_int, ctypes.c_int,
+                                                c_void_p, c_surface_p, c_view_p, c_void_p]),
     "tdnet_op_overlay_view": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_view_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_picture_view": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_view_p, ctypes.c_int, ctypes.c_int,
                                              c_void_p, c_view_p, c_void_p]),

@@ -232,6 +232,10 @@ struct SrcView {
     int fh = 0, fw = 0, pitch = 0, oy = 0, ox = 0;
     size_t uv_offset = 0;                                              // NV12
     int standard = 0;                                                  // NV12
+    // a YUV surface (include/tdnet.h "surfaces"; surface_resolve): `format` is then TDNET_PIX_NV12 for the readers that only ask "packed or not"
+    bool surf = false;
+    int layout = 0, cpitch = 0;                                        // TDNET_SURF_*; bytes per chroma row (pitch for 4:2:2)
+    size_t u_off = 0, v_off = 0, extent = 0;                           // resolved plane offsets (4:2:2: 0); the surface's extent
 };
 static SrcView src_view_rgb(int Hs, int Ws) { SrcView v; v.fh = Hs; v.fw = Ws; return v; }
 static SrcView src_view_nv12(int Hs, int Ws, const Nv12Layout& nv) {
@@ -241,6 +245,9 @@ static int src_view_bpp(int format) { return format == TDNET_PIX_NV12 ? 1 : form
 struct U8Input {
     bool set = false;
     bool nv12 = false;                                                 // false: packed pixels; true: an NV12 surface
+    bool surf = false;                                                 // a YUV surface (tdnet_set_input_surface): k_ingest_surface reads it; nv12 is false then
+    int layout = 0, cpitch = 0;                                        // surf: TDNET_SURF_*; bytes per chroma row
+    size_t u_off = 0, v_off = 0;                                       // surf: the resolved plane offsets
     int format = 0, bpp = 3;                                           // TDNET_PIX_*; bytes per packed pixel
     bool swap = false;                                                 // packed: the colour bytes are b g r
     int fh = 0, fw = 0, oy = 0, ox = 0;                                // the whole frame; the origin of the rectangle Hs x Ws the image is
@@ -290,6 +297,10 @@ struct DstOutput {
     int fh = 0, fw = 0, oy = 0, ox = 0, h = 0, w = 0, pitch = 0, standard = 0;
     size_t uv_offset = 0, extent = 0;                                  // NV12; the bytes [base, base + extent) of the whole frame: nothing else is written
     int yoff = 0, ky[3] = {0, 0, 0}, ku[3] = {0, 0, 0}, kv[3] = {0, 0, 0};   // NV12: nv12_forward_coeffs, rows over r, g, b
+    // a 4:2:0 surface (tdnet_set_output_surface; dst_surface_build): format is TDNET_PIX_NV12, uv_offset = u_off; the view and the surface replace each other
+    bool surf = false;
+    int layout = 0, cpitch = 0;                                        // TDNET_SURF_* (NV12, NV21, I420, P010); bytes per chroma row
+    size_t u_off = 0, v_off = 0;
 };
 // The score output of a handle (tdnet_set_score): the device confusion matrix the score kernels add into and the 256-byte ground-truth map they
 // read.  Per handle, like U8Input.
@@ -487,20 +498,101 @@ static void nv12_forward_coeffs(int standard, int* yoff, int ky[3], int ku[3], i
         kv[i] = (int)nearbyint(dec[standard][6 + i] * 1048576.0);
     }
 }
+// ---- YUV surfaces (include/tdnet.h "surfaces"): the host side of td_ingest.h k_ingest_surface / td_out.h td_overlay_src_surf ----
+// What a layout is to the kernels (td_ingest.h SurfLayout has the table): bytes between luma samples, the luma sample's offset, the vertical chroma
+// shift, bytes between chroma pairs, the offsets of U and V within a pair, the chroma spans staged per source row, 16-bit samples.
+struct SurfForm { int lstride = 1, loff = 0, cshift = 1, cstep = 2, uo = 0, vo = 1, planes = 1; bool wide = false; };
+static SurfForm surf_form(int layout) {
+    SurfForm f;
+    switch (layout) {
+    case TDNET_SURF_NV21: f.uo = 1; f.vo = 0; break;
+    case TDNET_SURF_I420: f.cstep = 1; f.uo = f.vo = 0; f.planes = 2; break;
+    case TDNET_SURF_P010: f.lstride = 2; f.cstep = 4; f.vo = 2; f.wide = true; break;
+    case TDNET_SURF_YUY2: f.lstride = 2; f.cshift = 0; f.cstep = 4; f.uo = 1; f.vo = 3; f.planes = 0; break;
+    case TDNET_SURF_UYVY: f.lstride = 2; f.loff = 1; f.cshift = 0; f.cstep = 4; f.uo = 0; f.vo = 2; f.planes = 0; break;
+    default: break;                                                    // TDNET_SURF_NV12
+    }
+    return f;
+}
+// yoff and rint(c 2^20) of nv12_coeffs' decimals; 10-bit samples: 4 yoff and rint(c 2^18) -- the sum is shifted by 20 either way
+static void surf_coeffs(int standard, bool wide, int coef[6]) {
+    nv12_coeffs(standard, coef);
+    if (!wide) return;
+    static const double dec[4][5] = {{1.164, 2.018, -0.391, -0.813, 1.596}, {1.164, 2.112, -0.213, -0.533, 1.793},
+                                     {1.0, 1.772, -0.344136, -0.714136, 1.402}, {1.0, 1.8556, -0.187324, -0.468124, 1.5748}};
+    coef[0] *= 4;
+    for (int i = 0; i < 5; ++i) coef[1 + i] = (int)nearbyint(dec[standard][i] * 262144.0);
+}
+// tdnet_surface -> (SrcView, Hs x Ws) with every default resolved and the planes checked, or the failure that names the offending field.  mean / std
+// and the staged span are u8_build's to check.
+static int surface_resolve(const tdnet_surface* t, SrcView& sv, int& Hs, int& Ws, const char* who) {
+    if (!t) return td_fail("%s: surface is NULL", who);
+    if (t->layout < 0 || t->layout > TDNET_SURF_UYVY) return td_fail("%s: layout %d is not one of TDNET_SURF_* (0..5)", who, t->layout);
+    for (int i = 0; i < 4; ++i)
+        if (t->reserved[i]) return td_fail("%s: reserved[%d] = %d must be 0", who, i, t->reserved[i]);
+    if (t->height < 1 || t->width < 1) return td_fail("%s: height x width = %d x %d must be at least 1 x 1", who, t->height, t->width);
+    const bool whole = !t->crop_y && !t->crop_x && !t->crop_height && !t->crop_width;
+    const int oy = t->crop_y, ox = t->crop_x, h = whole ? t->height : t->crop_height, w = whole ? t->width : t->crop_width;
+    if (oy < 0 || ox < 0) return td_fail("%s: crop_y, crop_x = %d, %d: the origin must not be negative", who, oy, ox);
+    if (h < 1 || w < 1) return td_fail("%s: crop_height x crop_width = %d x %d must be at least 1 x 1", who, h, w);
+    if (h > t->height || oy > t->height - h) return td_fail("%s: crop_y + crop_height = %d + %d is not inside the frame's height %d", who, oy, h, t->height);
+    if (w > t->width || ox > t->width - w) return td_fail("%s: crop_x + crop_width = %d + %d is not inside the frame's width %d", who, ox, w, t->width);
+    if (t->standard < 0 || t->standard > 3) return td_fail("%s: standard %d is not one of TDNET_YUV_* (0..3)", who, t->standard);
+    const SurfForm f = surf_form(t->layout);
+    const double cw = (double)((t->width - 1) / 2 + 1), chh = (double)((t->height - 1) / 2 + 1);
+    const double lrow = f.planes ? (double)t->width * f.lstride : 4.0 * cw, crow = f.cstep * cw;   // bytes of a luma (packed) row / of a chroma row
+    if (lrow >= 2147483648.0) return td_fail("%s: the surface's extent (a row of %d pixels) is 2^31 bytes or more", who, t->width);
+    if (t->pitch < 0) return td_fail("%s: pitch %d is negative", who, t->pitch);
+    if (t->pitch && t->pitch < lrow) return td_fail("%s: pitch %d is below the %.0f bytes a row of %d pixels holds", who, t->pitch, lrow, t->width);
+    const double pitch = t->pitch ? t->pitch : lrow;
+    double ext = (t->height - 1) * pitch + lrow;                       // the luma (packed) plane: [0, ext)
+    sv = SrcView();
+    sv.surf = true; sv.layout = t->layout; sv.format = TDNET_PIX_NV12; sv.fh = t->height; sv.fw = t->width; sv.oy = oy; sv.ox = ox; sv.standard = t->standard;
+    if (!f.planes) {
+        if (t->chroma_pitch) return td_fail("%s: chroma_pitch = %d must be 0 for a 4:2:2 layout (the chroma lies in the packed rows)", who, t->chroma_pitch);
+        if (t->u_offset) return td_fail("%s: u_offset = %llu must be 0 for a 4:2:2 layout", who, (unsigned long long)t->u_offset);
+        if (t->v_offset) return td_fail("%s: v_offset = %llu must be 0 for a 4:2:2 layout", who, (unsigned long long)t->v_offset);
+        if (ext >= 2147483648.0) return td_fail("%s: the surface's extent (pitch %.0f, %d rows) is 2^31 bytes or more", who, pitch, t->height);
+        sv.pitch = sv.cpitch = (int)pitch;
+    } else {
+        if (f.planes != 2 && t->v_offset) return td_fail("%s: v_offset = %llu must be 0 for a layout with one chroma plane", who, (unsigned long long)t->v_offset);
+        if (t->chroma_pitch < 0) return td_fail("%s: chroma_pitch %d is negative", who, t->chroma_pitch);
+        if (t->chroma_pitch && t->chroma_pitch < crow) return td_fail("%s: chroma_pitch %d is below the %.0f bytes a chroma row of %d columns holds", who, t->chroma_pitch, crow, t->width);
+        const double cpitch = t->chroma_pitch ? t->chroma_pitch : f.planes == 2 ? floor((pitch + 1) / 2) : pitch;
+        if (cpitch < crow) return td_fail("%s: chroma_pitch 0 resolves to %.0f, below the %.0f bytes a chroma row of %d columns holds (pitch %.0f)", who, cpitch, crow, t->width, pitch);
+        if ((double)t->u_offset >= 2147483648.0 || (double)t->v_offset >= 2147483648.0 || t->height * pitch >= 2147483648.0)
+            return td_fail("%s: the surface's extent (u_offset %llu, v_offset %llu, pitch %.0f, %d rows) is 2^31 bytes or more", who, (unsigned long long)t->u_offset,
+                           (unsigned long long)t->v_offset, pitch, t->height);
+        const double plane = (chh - 1) * cpitch + crow;                // bytes from a chroma plane's start to its end
+        const double u0 = t->u_offset ? (double)t->u_offset : t->height * pitch;
+        const double v0 = f.planes != 2 ? u0 : t->v_offset ? (double)t->v_offset : u0 + chh * cpitch;
+        if (u0 < ext) return td_fail("%s: u_offset %.0f is inside the luma plane (%d rows of pitch %.0f: %.0f bytes)", who, u0, t->height, pitch, ext);
+        if (f.planes == 2) {
+            if (v0 < ext) return td_fail("%s: v_offset %.0f is inside the luma plane (%d rows of pitch %.0f: %.0f bytes)", who, v0, t->height, pitch, ext);
+            if (u0 < v0 + plane && v0 < u0 + plane) return td_fail("%s: the chroma planes at u_offset %.0f and v_offset %.0f (%.0f bytes each) overlap", who, u0, v0, plane);
+        }
+        ext = std::max(u0, v0) + plane;
+        if (ext >= 2147483648.0) return td_fail("%s: the surface's extent (u_offset %.0f, v_offset %.0f, chroma_pitch %.0f) is 2^31 bytes or more", who, u0, v0, cpitch);
+        sv.pitch = (int)pitch; sv.cpitch = (int)cpitch; sv.u_off = (size_t)u0; sv.v_off = (size_t)v0;
+    }
+    sv.extent = (size_t)ext;
+    Hs = h; Ws = w;
+    return 0;
+}
 // Validate, build the tables on the host and upload them into memory `u` owns.  NULL mean / std: the loader's (dataloader.py:52-53).
 // sv: what the image pointer is the base of -- the tables are those of the rectangle Hs x Ws whatever the format.  On failure `u` is left as it was.
 static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W, const double* mean, const double* std_, const char* who) {
     static const double mean0[3] = {.485, .456, .406}, std0[3] = {.229, .224, .225};
     if (!mean) mean = mean0;
     if (!std_) std_ = std0;
-    const bool nv = sv.format == TDNET_PIX_NV12;
+    const bool nv = sv.format == TDNET_PIX_NV12 && !sv.surf;
     const int bpp = src_view_bpp(sv.format);
     if (Hs < 1 || Ws < 1) return td_fail("%s: source size %d x %d must be at least 1 x 1", who, Hs, Ws);
     if (H < 1 || W < 1 || H > 65535) return td_fail("%s: network size %d x %d out of range", who, H, W);
-    if (!nv && (double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
+    if (!nv && !sv.surf && (double)Hs * Ws * 3 >= 2147483648.0) return td_fail("%s: source size %d x %d is too large", who, Hs, Ws);
     const int pitch = nv || sv.pitch ? sv.pitch : sv.fw * bpp;         // packed, 0: tight (a row that overflows was refused above or by view_resolve)
-    double extent = 0.0;
-    TD_TRY(view_surface_check(sv, pitch, who, &extent));
+    double extent = (double)sv.extent;                                 // a surface: surface_resolve has checked it
+    if (!sv.surf) TD_TRY(view_surface_check(sv, pitch, who, &extent));
     for (int c = 0; c < 3; ++c) {
         if (!std::isfinite(mean[c])) return td_fail("%s: mean[%d] is not finite", who, c);
         if (!std::isfinite(std_[c]) || std_[c] == 0.0) return td_fail("%s: std[%d] must be finite and non-zero", who, c);
@@ -512,6 +604,11 @@ static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W,
     if (nv) {
         v.nv12 = true; v.uv_offset = sv.uv_offset; v.standard = sv.standard;
         nv12_coeffs(sv.standard, v.coef);
+    }
+    const SurfForm sf = sv.surf ? surf_form(sv.layout) : SurfForm();
+    if (sv.surf) {
+        v.surf = true; v.layout = sv.layout; v.cpitch = sv.cpitch; v.u_off = sv.u_off; v.v_off = sv.v_off; v.standard = sv.standard;
+        surf_coeffs(sv.standard, sf.wide, v.coef);
     }
     for (int c = 0; c < 3; ++c) { v.mean[c] = mean[c]; v.std[c] = std_[c]; }
     v.resize = !(Hs == H && Ws == W);
@@ -540,11 +637,20 @@ static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W,
             const int xe = std::min(xs + 4 * threads, W);
             const int cl = v.resize ? x0[xs] : xs, ch = v.resize ? x1[xe - 1] : xe - 1;
             const long cols = (long)ch - cl + 1;
+            const long pairs = (long)((sv.ox + ch) >> 1) - ((sv.ox + cl) >> 1) + 1;
+            if (sv.surf) {                                             // k_ingest_surface: 4:2:2 stages whole pixel pairs, chroma included
+                span = std::max(span, ((sf.planes ? cols * sf.lstride : 4 * pairs) + 15 + 15) / 16 * 16);
+                if (sf.planes) span_c = std::max(span_c, (pairs * sf.cstep + 15 + 15) / 16 * 16);
+                continue;
+            }
             span = std::max(span, (cols * bpp + 15 + 15) / 16 * 16);
             if (nv) span_c = std::max(span_c, (((long)((sv.ox + ch) >> 1) - ((sv.ox + cl) >> 1) + 1) * 2 + 15 + 15) / 16 * 16);
         }
-        if (TD_INGEST_LUT_BYTES + 2 * span + 2 * span_c <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; v.span_c = (int)span_c; }
+        if (TD_INGEST_LUT_BYTES + 2 * span + 2 * (sv.surf ? sf.planes : 1) * span_c <= TD_INGEST_LDS_MAX) { fits = true; v.threads = threads; v.span = (int)span; v.span_c = (int)span_c; }
     }
+    if (!fits && sv.surf)
+        return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (%d bytes per column%s)", who, Ws, W, sf.lstride,
+                       sf.planes == 2 ? " and two chroma planes" : "");
     if (!fits) return td_fail("%s: a %d -> %d column downscale is beyond what the ingest kernel stages (about %s)", who, Ws, W, nv ? "60x" : bpp == 4 ? "30x: 4 bytes per staged column" : "20x");
     if (upload(&v.lut, lut)) return -1;
     if (v.resize) {
@@ -599,8 +705,10 @@ static int view_resolve(const tdnet_view* t, SrcView& sv, int& Hs, int& Ws, cons
 }
 // the configuration in force is the one these arguments would build (a packed pitch of 0 as u8_build resolves it)
 static bool u8_same(const U8Input& u, const SrcView& sv, int Hs, int Ws, const double* m, const double* sd) {
+    if (u.surf != sv.surf) return false;
+    if (sv.surf && (u.layout != sv.layout || u.cpitch != sv.cpitch || u.u_off != sv.u_off || u.v_off != sv.v_off || u.standard != sv.standard)) return false;
     if (!u.set || u.format != sv.format || u.Hs != Hs || u.Ws != Ws || u.fh != sv.fh || u.fw != sv.fw || u.oy != sv.oy || u.ox != sv.ox) return false;
-    const bool nv = sv.format == TDNET_PIX_NV12;
+    const bool nv = sv.format == TDNET_PIX_NV12 && !sv.surf;
     const long pitch = nv || sv.pitch ? sv.pitch : (long)sv.fw * src_view_bpp(sv.format);
     if (u.pitch != pitch || (nv && (u.uv_offset != sv.uv_offset || u.standard != sv.standard))) return false;
     return memcmp(u.mean, m, sizeof(u.mean)) == 0 && memcmp(u.std, sd, sizeof(u.std)) == 0;
@@ -625,6 +733,27 @@ static int dst_build(DstOutput& d, const tdnet_view* t, const char* who) {
         v.uv_offset = sv.uv_offset; v.standard = sv.standard;
         nv12_forward_coeffs(sv.standard, &v.yoff, v.ky, v.ku, v.kv);
     }
+    d = v;
+    return 0;
+}
+
+// tdnet_surface -> the destination surface it describes, or the failure that names the offending field.  On failure `d` is left as it was.
+static int dst_surface_build(DstOutput& d, const tdnet_surface* t, const char* who) {
+    if (t && (t->layout == TDNET_SURF_YUY2 || t->layout == TDNET_SURF_UYVY))
+        return td_fail("%s: layout %d (%s) is not a destination layout: no encoder takes packed 4:2:2 (NV12, NV21, I420 and P010 are)", who, t->layout,
+                       t->layout == TDNET_SURF_YUY2 ? "YUY2" : "UYVY");
+    SrcView sv;
+    int h = 0, w = 0;
+    TD_TRY(surface_resolve(t, sv, h, w, who));
+    if (h > 65535) return td_fail("%s: the rectangle's height %d is above the grid's 65535 rows", who, h);
+    if (sv.oy & 1) return td_fail("%s: crop_y = %d must be even for a 4:2:0 destination (the rectangle starts on the chroma grid)", who, sv.oy);
+    if (sv.ox & 1) return td_fail("%s: crop_x = %d must be even for a 4:2:0 destination (the rectangle starts on the chroma grid)", who, sv.ox);
+    DstOutput v;
+    v.set = true; v.surf = true;
+    v.format = TDNET_PIX_NV12; v.bpp = 1; v.layout = sv.layout;
+    v.fh = sv.fh; v.fw = sv.fw; v.oy = sv.oy; v.ox = sv.ox; v.h = h; v.w = w; v.pitch = sv.pitch; v.cpitch = sv.cpitch; v.extent = sv.extent;
+    v.u_off = sv.u_off; v.v_off = sv.v_off; v.uv_offset = sv.u_off; v.standard = sv.standard;
+    nv12_forward_coeffs(sv.standard, &v.yoff, v.ky, v.ku, v.kv);
     d = v;
     return 0;
 }

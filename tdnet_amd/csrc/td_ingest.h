@@ -245,3 +245,165 @@ TD_KERNEL void k_ingest_nv12(IngestNv12Args a) {
             if (x + e < a.W) { const f32x4 v = {f[3 * e], f[3 * e + 1], f[3 * e + 2], 0.f}; td_st4(o + 4 * e, v); }
     }
 }
+
+// ---- YUV surfaces -> the stem's image buffer ---------------------------------------------------------------------------------------
+// What decoders and capture devices hand over beside NV12 (include/tdnet.h "surfaces"): NV12 with a chroma pitch of its own, NV21, I420 / YV12,
+// P010, YUY2, UYVY.  The layout is a handful of wave-uniform ARGUMENTS, not an instantiation; only the sample width is a template parameter.  For
+// frame pixel (Y, X) -- absolute coordinates: origin + rectangle coordinates --
+//   luma   base[Y pitch + lstride X + loff]
+//   U      base[u_off + (Y >> cshift) cpitch + cstep (X >> 1) + uo]        V      base[v_off + (Y >> cshift) cpitch + cstep (X >> 1) + vo]
+// and a 16-bit sample is the little-endian word at that address, read bytewise, >> 6:
+//   layout   lstride loff  cshift cstep  uo vo   u_off / v_off
+//   NV12     1       0     1      2      0  1    the chroma plane, twice
+//   NV21     1       0     1      2      1  0    the chroma plane, twice
+//   I420     1       0     1      1      0  0    the U plane / the V plane
+//   P010     2       0     1      4      0  2    the chroma plane, twice                (WIDE)
+//   YUY2     2       0     0      4      1  3    0 / 0: the chroma lies in the luma row (cpitch = pitch)
+//   UYVY     2       1     0      4      0  2    0 / 0
+// Conversion: ingest_nv12_rgb's formulas with the sample's mid-point and luma offset as arguments (8 bit: 128, yoff, K = rint(c 2^20); P010: 512,
+// 4 yoff, K = rint(c 2^18): one rounding from 10 bits, |sum| <= 5.96e8 < 2^31).
+// k_ingest_nv12's grid, strip, tables and stores.  A workgroup stages with ingest_stage_row, per source row y0 / y1: the luma span (4:2:2: widened to
+// whole pixel pairs, so that the row's chroma is in it), and -- 4:2:0 only -- the span of the chroma row (I420: one of the U and one of the V
+// plane), the second row's only where it is another chroma row.  One barrier; the taps are assembled and converted in registers.
+struct SurfLayout {
+    int pitch, cpitch;             // bytes per luma (or packed) row / per chroma row
+    unsigned u_off, v_off;         // < 2^31
+    int lstride, loff, cshift, cstep, uo, vo;
+    int planes;                    // chroma spans staged per source row: 0 (4:2:2), 1 (interleaved), 2 (I420)
+    int yoff, mid, cy, cub, cug, cvg, cvr;
+    int oy, ox;                    // the rectangle's origin
+};
+struct IngestSurfArgs {
+    const unsigned char* src;      // the surface's base, any byte alignment
+    float* out;
+    const float* lut;              // [3][256]
+    const int* xt;                 // as IngestArgs
+    const int* yt;
+    int Hs, Ws, H, W, Wt;
+    int Wp;                        // as IngestArgs
+    int resize;
+    int span, span_c;              // LDS bytes per staged luma span / chroma span (multiples of 16; td_handle.h u8_build)
+    unsigned extent;               // < 2^31
+    SurfLayout l;
+};
+TD_DEV void ingest_surf_rgb(const SurfLayout& l, int Y, int U, int V, int* p) {
+    int yy = Y - l.yoff;
+    yy = (yy < 0 ? 0 : yy) * l.cy + (1 << 19);
+    const int u = U - l.mid, v = V - l.mid;
+    p[0] = ingest_clamp8((yy + l.cvr * v) >> 20);
+    p[1] = ingest_clamp8((yy + l.cvg * v + l.cug * u) >> 20);
+    p[2] = ingest_clamp8((yy + l.cub * u) >> 20);
+}
+// the sample at p: a byte, or the 10 bits in bits 15..6 of the little-endian word there (p at any byte address)
+template <bool WIDE>
+TD_DEV int surf_sample(const unsigned char* p) { return WIDE ? (int)(((unsigned)p[0] | ((unsigned)p[1] << 8)) >> 6) : (int)p[0]; }
+// frame column gx of a staged source row: sm + lp, + up, + vp are where column 0's luma sample / pair 0's U / V would lie in LDS (offsets, possibly
+// negative: only columns of the staged span are asked for)
+template <bool WIDE>
+TD_DEV void ingest_surf_tap(const SurfLayout& l, const unsigned char* sm, int lp, int up, int vp, int gx, int* p) {
+    const int c = l.cstep * (gx >> 1);
+    ingest_surf_rgb(l, surf_sample<WIDE>(sm + lp + l.lstride * gx), surf_sample<WIDE>(sm + up + c), surf_sample<WIDE>(sm + vp + c), p);
+}
+
+template <bool WIDE>
+TD_KERNEL void k_ingest_surface(IngestSurfArgs a) {
+    TD_DYN_LDS(smem);
+    const SurfLayout& l = a.l;
+    float* lut = reinterpret_cast<float*>(smem);                                   // [3][256]
+    unsigned char* yr0 = reinterpret_cast<unsigned char*>(smem) + TD_INGEST_LUT_BYTES;   // the staged luma span of source row y0 ...
+    unsigned char* yr1 = yr0 + a.span;                                             // ... of y1 (resize only) ...
+    unsigned char* cs = yr1 + a.span;                                              // ... and the chroma spans: [row][planes] of span_c bytes
+    const int y = blockIdx.y, xs = blockIdx.x * blockDim.x * 4;
+    const int xe = xs + (int)blockDim.x * 4 < a.W ? xs + (int)blockDim.x * 4 : a.W;   // the strip: output columns [xs, xe)
+    for (int i = threadIdx.x; i < 768; i += blockDim.x) lut[i] = a.lut[i];
+    int y0 = y, y1 = y, b0 = 0, b1 = 0, cl = xs, ch = xe - 1;                      // source columns [cl, ch]
+    if (a.resize) {
+        const td_i32x4 t = *reinterpret_cast<const td_i32x4*>(a.yt + 4 * y);
+        y0 = t[0]; y1 = t[1]; b0 = t[2]; b1 = t[3];
+        cl = a.xt[xs]; ch = a.xt[a.Wt + xe - 1];
+    }
+    const int g0 = l.oy + y0, g1 = l.oy + y1;                                      // the frame's rows and ...
+    const int gl = l.ox + cl, gh = l.ox + ch;                                      // ... columns: chroma goes by THEIR parity
+    const int npair = (gh >> 1) - (gl >> 1) + 1;
+    const int lb = l.planes ? l.lstride * gl : 4 * (gl >> 1);                       // the luma span's first byte within its row (4:2:2: the pair's)
+    const size_t ny = l.planes ? (size_t)l.lstride * (size_t)(ch - cl + 1) : (size_t)4 * npair;
+    const int cb = l.cstep * (gl >> 1);                                            // the chroma span's first byte within its row
+    const size_t nc = (size_t)l.cstep * npair;
+    const size_t f0 = (size_t)g0 * l.pitch + lb, f1 = (size_t)g1 * l.pitch + lb;
+    const size_t cu0 = (size_t)l.u_off + (size_t)(g0 >> 1) * l.cpitch + cb, cu1 = (size_t)l.u_off + (size_t)(g1 >> 1) * l.cpitch + cb;
+    const size_t cv0 = (size_t)l.v_off + (size_t)(g0 >> 1) * l.cpitch + cb, cv1 = (size_t)l.v_off + (size_t)(g1 >> 1) * l.cpitch + cb;
+    const bool two = (g0 >> 1) != (g1 >> 1);                                       // false without resize: y0 == y1
+    const size_t lo = (size_t)a.src, hi = lo + a.extent;
+    ingest_stage_row(lo, hi, yr0, f0, ny);
+    if (a.resize) ingest_stage_row(lo, hi, yr1, f1, ny);
+    if (l.planes) {                                                                // wave-uniform
+        ingest_stage_row(lo, hi, cs, cu0, nc);
+        if (l.planes == 2) ingest_stage_row(lo, hi, cs + a.span_c, cv0, nc);
+        if (two) {
+            ingest_stage_row(lo, hi, cs + l.planes * a.span_c, cu1, nc);
+            if (l.planes == 2) ingest_stage_row(lo, hi, cs + 3 * a.span_c, cv1, nc);
+        }
+    }
+    __syncthreads();
+    const int x = xs + (int)threadIdx.x * 4;
+    if (x >= a.W) return;
+    const unsigned char* sm = reinterpret_cast<const unsigned char*>(smem);
+    const int q0 = TD_INGEST_LUT_BYTES, q1 = q0 + a.span, qc = q1 + a.span;        // LDS offsets of yr0, yr1, cs
+    const int lp0 = q0 + (int)((lo + f0) & 15) - lb + l.loff;                      // sm[lp0 + lstride * column]: the luma sample of frame column `column`, row y0
+    const int lp1 = q1 + (int)((lo + f1) & 15) - lb + l.loff;
+    int up0, vp0, up1, vp1;                                                        // sm[up0 + cstep * pair]: the U sample of that pair, row y0; ...
+    if (l.planes == 0) {                                                           // 4:2:2: in the luma row
+        up0 = lp0 - l.loff + l.uo; vp0 = lp0 - l.loff + l.vo;
+        up1 = lp1 - l.loff + l.uo; vp1 = lp1 - l.loff + l.vo;
+    } else {
+        up0 = qc + (int)((lo + cu0) & 15) - cb + l.uo;
+        vp0 = l.planes == 2 ? qc + a.span_c + (int)((lo + cv0) & 15) - cb : up0 - l.uo + l.vo;
+        up1 = two ? qc + l.planes * a.span_c + (int)((lo + cu1) & 15) - cb + l.uo : up0;
+        vp1 = !two ? vp0 : l.planes == 2 ? qc + 3 * a.span_c + (int)((lo + cv1) & 15) - cb : up1 - l.uo + l.vo;
+    }
+    float f[12];
+    if (a.resize) {
+        const td_i32x4 s0 = *reinterpret_cast<const td_i32x4*>(a.xt + x), s1 = *reinterpret_cast<const td_i32x4*>(a.xt + a.Wt + x);
+        const td_i32x4 a0 = *reinterpret_cast<const td_i32x4*>(a.xt + 2 * a.Wt + x), a1 = *reinterpret_cast<const td_i32x4*>(a.xt + 3 * a.Wt + x);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int p00[3], p01[3], p10[3], p11[3];                                    // the four taps, converted and clamped
+            ingest_surf_tap<WIDE>(l, sm, lp0, up0, vp0, l.ox + s0[e], p00);
+            ingest_surf_tap<WIDE>(l, sm, lp0, up0, vp0, l.ox + s1[e], p01);
+            ingest_surf_tap<WIDE>(l, sm, lp1, up1, vp1, l.ox + s0[e], p10);
+            ingest_surf_tap<WIDE>(l, sm, lp1, up1, vp1, l.ox + s1[e], p11);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int r0 = p00[c] * a0[e] + p01[c] * a1[e];
+                const int r1 = p10[c] * a0[e] + p11[c] * a1[e];
+                const int v = ingest_clamp8((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+                f[3 * e + c] = lut[c * 256 + v];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int p[3] = {0, 0, 0};
+            const bool in = x + e < a.W;
+            if (in) ingest_surf_tap<WIDE>(l, sm, lp0, up0, vp0, l.ox + x + e, p);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[3 * e + c] = in ? lut[c * 256 + p[c]] : 0.f;
+        }
+    }
+    if (a.Wp) {
+        float* o = a.out + ((size_t)(y + 3) * a.Wp + x + 4) * 3;                   // 16-byte aligned: Wp % 4 == 0, x % 4 == 0
+        if (x + 4 <= a.W) {
+            const f32x4 v0 = {f[0], f[1], f[2], f[3]}, v1 = {f[4], f[5], f[6], f[7]}, v2 = {f[8], f[9], f[10], f[11]};
+            td_st4(o, v0); td_st4(o + 4, v1); td_st4(o + 8, v2);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (x + e < a.W) { o[3 * e] = f[3 * e]; o[3 * e + 1] = f[3 * e + 1]; o[3 * e + 2] = f[3 * e + 2]; }
+        }
+    } else {
+        float* o = a.out + ((size_t)y * a.W + x) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (x + e < a.W) { const f32x4 v = {f[3 * e], f[3 * e + 1], f[3 * e + 2], 0.f}; td_st4(o + 4 * e, v); }
+    }
+}

@@ -343,11 +343,27 @@ enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };                               // TD_IMG_
 struct FrameInput { const void* p; int kind; const U8Input* u8; };
 static inline FrameInput frame_input_f32(const float* img) { return FrameInput{img, TD_IMG_F32, nullptr}; }
 // rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
+// the kernels' description of the surface a byte input is (td_ingest.h SurfLayout; td_handle.h surf_form, surf_coeffs)
+static SurfLayout surf_layout(const U8Input& u) {
+    const SurfForm f = surf_form(u.layout);
+    return SurfLayout{u.pitch, u.cpitch, (unsigned)u.u_off, (unsigned)u.v_off, f.lstride, f.loff, f.cshift, f.cstep, f.uo, f.vo, f.planes,
+                      u.coef[0], f.wide ? 512 : 128, u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
+}
 static void run_stem_pre(tdnet* n, const FrameInput& in, int H, int W, float* img4, hipStream_t s, bool rows = false) {
     prof_begin(n, 2, false, 0, s);
     switch (in.kind) {
     case TD_IMG_U8: {                                                  // resize + normalise + layout in the same one launch (td_ingest.h)
         const U8Input& u = *in.u8;
+        if (u.surf) {                                                  // a YUV surface: the layout is arguments, the sample width the instantiation
+            const SurfLayout l = surf_layout(u);
+            const IngestSurfArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
+                                      u.span, u.span_c, (unsigned)u.extent, l};
+            const dim3 grid((W + 4 * u.threads - 1) / (4 * u.threads), H), block(u.threads);
+            const int lds = TD_INGEST_LUT_BYTES + 2 * u.span + 2 * l.planes * u.span_c;
+            if (l.mid == 512) TD_LAUNCH((k_ingest_surface<true>), grid, block, lds, s, a);
+            else TD_LAUNCH((k_ingest_surface<false>), grid, block, lds, s, a);
+            break;
+        }
         if (u.nv12) {                                                  // colour conversion too, in the same one launch
             const IngestNv12Args a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
                                       u.span, u.span_c, u.pitch, (unsigned)u.uv_offset, (unsigned)u.extent,
@@ -476,6 +492,12 @@ static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, 
                                           unsigned char* out, hipStream_t s) {
     TD_TRY(out_check("overlay", "src_height", o.Hs, C));
     TD_TRY(overlay_check_tables(o, u));
+    if (u.surf) {                                                      // a YUV surface: td_out.h td_overlay_src_surf
+        const SurfLayout l = surf_layout(u);
+        if (l.mid == 512) TD_LAUNCH((k_upsample_argmax_overlay_surf<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, C, h, w, o.H, o.W, o.Hs, o.Ws);
+        else TD_LAUNCH((k_upsample_argmax_overlay_surf<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, C, h, w, o.H, o.W, o.Hs, o.Ws);
+        return 0;
+    }
     const OverlaySrc sd = overlay_src(u, src);
     switch (overlay_src_form(u)) {
 #define TD_OVL(SRC, VIEW) TD_LAUNCH((k_upsample_argmax_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, \
@@ -492,6 +514,12 @@ static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, 
 static int launch_labels_overlay(const unsigned char* labels, const OverlayOutput& o, const U8Input& u, const unsigned char* src, unsigned char* out, hipStream_t s) {
     TD_TRY(out_check("overlay", "src_height", o.Hs, 1));
     TD_TRY(overlay_check_tables(o, u));
+    if (u.surf) {
+        const SurfLayout l = surf_layout(u);
+        if (l.mid == 512) TD_LAUNCH((k_labels_overlay_surf<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, o.W, o.Hs, o.Ws);
+        else TD_LAUNCH((k_labels_overlay_surf<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, o.W, o.Hs, o.Ws);
+        return 0;
+    }
     const OverlaySrc sd = overlay_src(u, src);
     switch (overlay_src_form(u)) {
 #define TD_OVL(SRC, VIEW) TD_LAUNCH((k_labels_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws)
@@ -512,6 +540,31 @@ static void launch_picture_form(const PicArgs& a, const OverlaySrc& sd, const Ds
     if (form == TD_DST_NV12) TD_LAUNCH((k_picture_nv12<LABELS, OVERLAY, SRC>), dim3(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2), dim3(256), 0, s, a, sd, dv);
     else if (form == TD_DST_P32) TD_LAUNCH((k_picture_packed<TD_DST_P32, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
     else TD_LAUNCH((k_picture_packed<TD_DST_P24, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
+}
+// The surface forms (td_out.h k_picture_surface): a 4:2:0 surface destination, or an NV12 destination view behind a surface source
+template <bool LABELS, bool OVERLAY, int SRC>
+static void launch_picture_surf_form(const PicArgs& a, const OverlaySrc& sd, const SurfLayout& sl, const DstSurf& ds, bool wide, hipStream_t s) {
+    const dim3 grid(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2);
+    if (wide) TD_LAUNCH((k_picture_surface<LABELS, OVERLAY, SRC, true>), grid, dim3(256), 0, s, a, sd, sl, ds);
+    else TD_LAUNCH((k_picture_surface<LABELS, OVERLAY, SRC, false>), grid, dim3(256), 0, s, a, sd, sl, ds);
+}
+template <bool LABELS>
+static void launch_picture_surf(const PicArgs& a, const OverlaySrc& sd, const SurfLayout& sl, const DstSurf& ds, bool wide, int src_form, hipStream_t s) {
+    if (src_form < 0) launch_picture_surf_form<LABELS, false, TD_SRC_P24>(a, sd, sl, ds, wide, s);   // the colour map: no source
+    else if (src_form == TD_SRC_NV12) launch_picture_surf_form<LABELS, true, TD_SRC_NV12>(a, sd, sl, ds, wide, s);
+    else if (src_form == TD_SRC_P32) launch_picture_surf_form<LABELS, true, TD_SRC_P32>(a, sd, sl, ds, wide, s);
+    else if (src_form == TD_SRC_SURF8) launch_picture_surf_form<LABELS, true, TD_SRC_SURF8>(a, sd, sl, ds, wide, s);
+    else if (src_form == TD_SRC_SURF16) launch_picture_surf_form<LABELS, true, TD_SRC_SURF16>(a, sd, sl, ds, wide, s);
+    else launch_picture_surf_form<LABELS, true, TD_SRC_P24>(a, sd, sl, ds, wide, s);
+}
+// a packed destination view behind a surface source (td_out.h k_picture_packed_surf)
+template <bool LABELS>
+static void launch_picture_packed_surf(const PicArgs& a, const unsigned char* src, const SurfLayout& sl, const DstView& dv, int form, bool wide, hipStream_t s) {
+    const dim3 grid = out_grid(a.ow, a.oh);
+    if (form == TD_DST_P32 && wide) TD_LAUNCH((k_picture_packed_surf<TD_DST_P32, LABELS, true>), grid, dim3(256), 0, s, a, src, sl, dv);
+    else if (form == TD_DST_P32) TD_LAUNCH((k_picture_packed_surf<TD_DST_P32, LABELS, false>), grid, dim3(256), 0, s, a, src, sl, dv);
+    else if (wide) TD_LAUNCH((k_picture_packed_surf<TD_DST_P24, LABELS, true>), grid, dim3(256), 0, s, a, src, sl, dv);
+    else TD_LAUNCH((k_picture_packed_surf<TD_DST_P24, LABELS, false>), grid, dim3(256), 0, s, a, src, sl, dv);
 }
 template <bool LABELS>
 static void launch_picture_src(const PicArgs& a, const OverlaySrc& sd, const DstView& dv, int form, int src_form, hipStream_t s) {
@@ -542,7 +595,28 @@ static int launch_picture_dst(const float* in, int C, int h, int w, const unsign
     }
     const OverlaySrc sd = r ? OverlaySrc() : overlay_src(*u, src);
     const int form = d.format == TDNET_PIX_NV12 ? TD_DST_NV12 : d.bpp == 4 ? TD_DST_P32 : TD_DST_P24;
-    const int src_form = r ? -1 : overlay_src_form(*u) / 2;
+    const bool src_surf = !r && u->surf;
+    const SurfLayout sl = src_surf ? surf_layout(*u) : SurfLayout();
+    const int src_form = r ? -1 : src_surf ? (sl.mid == 512 ? TD_SRC_SURF16 : TD_SRC_SURF8) : overlay_src_form(*u) / 2;
+    // An NV12 surface whose planes share one pitch IS the NV12 view: it takes k_picture_nv12.  Every other surface, and any 4:2:0 destination behind a surface
+    // source, takes k_picture_surface; a packed destination behind a surface source k_picture_packed_surf.
+    const bool plain_nv12 = !d.surf || (d.layout == TDNET_SURF_NV12 && d.cpitch == d.pitch);
+    if (form == TD_DST_NV12 && (src_surf || !plain_nv12)) {
+        const SurfForm f = d.surf ? surf_form(d.layout) : SurfForm();
+        DstSurf ds = DstSurf();
+        ds.base = base; ds.pitch = d.pitch; ds.cpitch = d.surf ? d.cpitch : d.pitch;
+        ds.u_off = (unsigned)(d.surf ? d.u_off : d.uv_offset); ds.v_off = (unsigned)(d.surf ? d.v_off : d.uv_offset);
+        ds.oy = d.oy; ds.ox = d.ox; ds.cstep = f.cstep; ds.uo = f.uo; ds.vo = f.vo; ds.yoff = dv.yoff;
+        for (int i = 0; i < 3; ++i) { ds.ky[i] = dv.ky[i]; ds.ku[i] = dv.ku[i]; ds.kv[i] = dv.kv[i]; }
+        if (labels) launch_picture_surf<true>(a, sd, sl, ds, f.wide, src_form, s);
+        else launch_picture_surf<false>(a, sd, sl, ds, f.wide, src_form, s);
+        return 0;
+    }
+    if (src_surf) {
+        if (labels) launch_picture_packed_surf<true>(a, src, sl, dv, form, sl.mid == 512, s);
+        else launch_picture_packed_surf<false>(a, src, sl, dv, form, sl.mid == 512, s);
+        return 0;
+    }
     if (labels) launch_picture_src<true>(a, sd, dv, form, src_form, s);
     else launch_picture_src<false>(a, sd, dv, form, src_form, s);
     return 0;

@@ -331,6 +331,15 @@ extern "C" int tdnet_set_input_view(tdnet_t* n, const tdnet_view* v, const doubl
     TD_TRY(view_resolve(v, sv, Hs, Ws, "tdnet_set_input_view"));
     return set_input(n, sv, Hs, Ws, mean, std_, "tdnet_set_input_view");
 }
+// a rectangle of a YUV surface in one of the six layouts (include/tdnet.h "surfaces")
+extern "C" int tdnet_set_input_surface(tdnet_t* n, const tdnet_surface* t, const double* mean, const double* std_) {
+    if (!n) return td_fail("tdnet_set_input_surface: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_surface: weights not finalized");
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(surface_resolve(t, sv, Hs, Ws, "tdnet_set_input_surface"));
+    return set_input(n, sv, Hs, Ws, mean, std_, "tdnet_set_input_surface");
+}
 // ---- colour map out ----------------------------------------------------------------------------------------------------------------
 // Configuration of the colour-map output (not a frame call: it may synchronise; idempotent for equal arguments).  Tables and palette live in
 // memory this handle owns; a tdnet_create_shared handle has its own configuration.
@@ -419,6 +428,13 @@ extern "C" int tdnet_set_output_view(tdnet_t* n, const tdnet_view* v) {
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_output_view: weights not finalized");
     if (!v) { n->dst = DstOutput(); return 0; }
     return dst_build(n->dst, v, "tdnet_set_output_view");
+}
+// The same for a rectangle of a 4:2:0 surface (include/tdnet.h "surfaces"); the view and the surface replace each other: ONE destination at a time
+extern "C" int tdnet_set_output_surface(tdnet_t* n, const tdnet_surface* t) {
+    if (!n) return td_fail("tdnet_set_output_surface: null handle");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_output_surface: weights not finalized");
+    if (!t) { n->dst = DstOutput(); return 0; }
+    return dst_surface_build(n->dst, t, "tdnet_set_output_surface");
 }
 // ---- score out -------------------------------------------------------------------------------------------------------------------------
 // Configuration of the score output (not a frame call: it may synchronise; idempotent for an equal map).  The matrix and the map live in memory

@@ -576,6 +576,33 @@ extern "C" long tdnet_op_stem_image_view(const uint8_t* base, const tdnet_view* 
     u8_free(u);
     return rc;
 }
+// tdnet_op_stem_image from a YUV surface: k_ingest_surface with the configuration tdnet_set_input_surface would build
+extern "C" long tdnet_op_stem_image_surface(const uint8_t* base, const tdnet_surface* surface, int H, int W, const double* mean, const double* std_, int rows, float* out,
+                                            size_t capacity, void* stream) {
+    const char* who = "tdnet_op_stem_image_surface";
+    if (H < 1 || W < 1) return td_fail("%s: empty image", who);
+    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
+    if (!out) return (long)img_floats;
+    if (!base) return td_fail("%s: base is NULL", who);
+    if (capacity < img_floats) return td_fail("%s: capacity %zu < %zu", who, capacity, img_floats);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    if (surface_resolve(surface, sv, Hs, Ws, who) || u8_build(u, sv, Hs, Ws, H, W, mean, std_, who)) return -1;
+    float* img4 = nullptr;
+    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
+    long rc = (long)img_floats;
+    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("%s: memset failed", who);
+    if (rc >= 0) {
+        run_stem_pre(nullptr, FrameInput{base, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
+        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    hipFree(img4);
+    u8_free(u);
+    return rc;
+}
 // low-resolution logits [C][h][w] -> labels [H][W]: int32 through k_upsample_argmax (labels_i32 != NULL) and / or uint8 through
 // k_upsample_argmax_u8 (labels_u8 != NULL)
 extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, int H, int W, int32_t* labels_i32, uint8_t* labels_u8, void* stream) {
@@ -643,6 +670,27 @@ extern "C" int tdnet_op_overlay_view(const float* in, int C, int h, int w, int H
     u8_free(u);
     return rc;
 }
+// tdnet_op_overlay with a YUV surface in place of its source arguments: out [h][w][3] of the surface's rectangle, r g b
+extern "C" int tdnet_op_overlay_surface(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* base, const tdnet_surface* surface,
+                                        const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
+    const char* who = "tdnet_op_overlay_surface";
+    if (!base || !out) return td_fail("%s: base and out expected", who);
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(surface_resolve(surface, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    int rc = overlay_build(o, palette_rgba, n_colours, who);
+    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, base, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, base, out, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
 // The picture into a destination view (include/tdnet.h "destination views") through exactly the kernels the frame entries launch with one in force: of
 // low-resolution logits [C][h][w] (labels_u8 == NULL) or of a uint8 label map [H][W]; the overlay over the source view (src_base, src_view; palette
 // [n][4]) or, src_base == NULL, the colour map oh x ow (palette [n][3]).  dst_base: the destination frame's base, at any byte address.
@@ -668,6 +716,42 @@ extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H
     SrcView sv;
     int Hs = 0, Ws = 0;
     TD_TRY(view_resolve(src_view, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    rc = overlay_build(o, palette, n_colours, who, u.swap);
+    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = launch_picture_dst(in, C, h, w, labels_u8, nullptr, &o, &u, src_base, d, dst_base, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
+// tdnet_op_picture_view with surfaces on either side: the destination a 4:2:0 surface (dst_surface) or a view (dst_view), the overlay's source a surface
+// (src_surface) or a view (src_view); src_base == NULL: the colour map oh x ow
+extern "C" int tdnet_op_picture_surface(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
+                                        const uint8_t* src_base, const tdnet_surface* src_surface, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base,
+                                        const tdnet_surface* dst_surface, const tdnet_view* dst_view, void* stream) {
+    const char* who = "tdnet_op_picture_surface";
+    if (!dst_base || (!dst_surface && !dst_view)) return td_fail("%s: dst_base and dst_surface or dst_view expected", who);
+    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    hipStream_t s = (hipStream_t)stream;
+    DstOutput d;
+    if (dst_surface) TD_TRY(dst_surface_build(d, dst_surface, who));
+    else TD_TRY(dst_build(d, dst_view, who));
+    int rc = 0;
+    if (!src_base) {
+        RgbOutput r;
+        TD_TRY(rgb_build(r, H, W, oh, ow, palette, n_colours, who));
+        rc = launch_picture_dst(in, C, h, w, labels_u8, &r, nullptr, nullptr, nullptr, d, dst_base, s);
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+        rgb_free(r);
+        return rc;
+    }
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    if (src_surface) TD_TRY(surface_resolve(src_surface, sv, Hs, Ws, who));
+    else TD_TRY(view_resolve(src_view, sv, Hs, Ws, who));
     TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
     rc = overlay_build(o, palette, n_colours, who, u.swap);
     if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);

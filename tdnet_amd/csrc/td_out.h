@@ -502,3 +502,167 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_nv12(PicArgs a, OverlaySrc o, 
     cb[2] = td_chroma8(d.ku, s1, m1); cb[3] = td_chroma8(d.kv, s1, m1);
     td_u8_store(d.base + d.uv_offset + (size_t)((d.oy >> 1) + j) * d.pitch + d.ox, xa, xa + (nx > 2 ? 4 : 2), cb);
 }
+
+// ---- overlay out over a YUV surface ------------------------------------------------------------------------------------------------
+// The overlay kernels above with the source read from a surface (include/tdnet.h "surfaces"; td_ingest.h SurfLayout): per pixel of the rectangle its
+// luma sample and the U and V samples covering it, with byte-aligned loads, converted by ingest_surf_rgb.  No LDS, no barrier, the early returns of the
+// siblings; only sample bytes that cover the rectangle are addressed.  Kernels of their own: OverlaySrc and the kernels that take it stay what they are.
+template <bool WIDE>
+TD_DEV void td_overlay_src_surf(const unsigned char* src, const SurfLayout& l, int y, long xa, long ow, unsigned* s) {
+    const int gy = l.oy + y;
+    const unsigned char* lr = src + (size_t)gy * l.pitch + l.loff;                 // wave-uniform like y
+    const size_t crow = (size_t)(gy >> l.cshift) * l.cpitch;
+    const unsigned char* ur = src + l.u_off + crow + l.uo;
+    const unsigned char* vr = src + l.v_off + crow + l.vo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const long gx = l.ox + td_run_px(xa, e, ow), c = (long)l.cstep * (gx >> 1);
+        int p[3];
+        ingest_surf_rgb(l, surf_sample<WIDE>(lr + (long)l.lstride * gx), surf_sample<WIDE>(ur + c), surf_sample<WIDE>(vr + c), p);
+        s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+    }
+}
+template <bool WIDE>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay_surf(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                         const unsigned char* __restrict__ src, SurfLayout l, unsigned char* __restrict__ out, int C, int h, int w, int H, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = out + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+    unsigned s[4], px[4];
+    td_overlay_src_surf<WIDE>(src, l, oy, xa, ow, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
+    td_rgb_store(orow, q, xa, xb, px);
+}
+template <bool WIDE>
+TD_KERNEL void k_labels_overlay_surf(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
+                                     const unsigned char* __restrict__ src, SurfLayout l, unsigned char* __restrict__ out, int W, int oh, int ow) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (oy >= oh) return;
+    unsigned char* orow = out + (size_t)oy * ow * 3;
+    long xa, xb;
+    td_rgb_run(orow, q, ow, &xa, &xb);
+    if (xa >= xb) return;
+    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
+    unsigned s[4], px[4];
+    td_overlay_src_surf<WIDE>(src, l, oy, xa, ow, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
+    td_rgb_store(orow, q, xa, xb, px);
+}
+
+// ---- surface destinations ------------------------------------------------------------------------------------------------------------
+// The picture written into a rectangle of a 4:2:0 surface -- NV12 with a chroma pitch of its own, NV21, I420 / YV12, P010 (include/tdnet.h "surfaces") --
+// and the overlay over a surface SOURCE into any destination.  k_picture_nv12's lane block (2 rows x 4 columns, the even origin aligns it to the chroma
+// grid), sums and scaling m = 4 / n; the layout is wave-uniform arguments, the destination's sample width the instantiation:
+//   8 bit   Y = clamp8((K . c + (yoff << 20) + (1 << 19)) >> 20),   U = clamp8((m K . S + (128 << 22) + (1 << 21)) >> 22)     (td_chroma8)
+//   P010    Y10 = clamp10((K . c + (yoff << 20) + (1 << 17)) >> 18), U10 = clamp10((m K . S + (128 << 22) + (1 << 19)) >> 20), stored as value << 6,
+//           little-endian, bytewise unless the run is 8-byte aligned (the base may be an odd address).
+// The sources: the three forms of "overlay out" above through td_overlay_src<SRC, true>, and a surface through td_overlay_src_surf.
+enum { TD_SRC_SURF8 = 3, TD_SRC_SURF16 = 4 };
+struct DstSurf {
+    unsigned char* base;           // the destination surface's base; any byte address
+    int pitch, cpitch;             // bytes per luma row / per chroma row
+    unsigned u_off, v_off;         // < 2^31 (one chroma plane: equal)
+    int oy, ox;                    // the rectangle's origin, both even
+    int cstep, uo, vo;             // bytes between the chroma pairs of a plane's row; where U and V lie in a pair
+    int yoff, ky[3], ku[3], kv[3]; // rint(c 2^20) of the forward matrix, in the order of the picture word's bytes
+};
+template <bool LABELS, bool OVERLAY, int SRC>
+TD_DEV void td_picture_px4s(const PicArgs& a, const OverlaySrc& o, const SurfLayout& sl, int y, long xa, unsigned* px) {
+    if (OVERLAY && SRC >= TD_SRC_SURF8) {
+        td_picture_px4<LABELS, false, TD_SRC_P24>(a, o, y, xa, px);
+        unsigned s[4];
+        td_overlay_src_surf<SRC == TD_SRC_SURF16>(o.src, sl, y, xa, a.ow, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
+    } else {
+        td_picture_px4<LABELS, OVERLAY, (SRC >= TD_SRC_SURF8 ? TD_SRC_P24 : SRC)>(a, o, y, xa, px);
+    }
+}
+TD_DEV int td_clamp10(int v) { return v < 0 ? 0 : v > 1023 ? 1023 : v; }
+TD_DEV int td_chroma10(const int* k, const int* s, int m) { return td_clamp10((m * (k[0] * s[0] + k[1] * s[1] + k[2] * s[2]) + (128 << 22) + (1 << 19)) >> 20); }
+// n (1..4) 10-bit values as words value << 6 at p: ONE 8-byte store where all four are there and p is 8-byte aligned, bytes otherwise
+struct alignas(8) TdW4 { unsigned v[2]; };
+TD_DEV void td_w16_store(unsigned char* p, int n, const int* b) {
+    if (n == 4 && (((size_t)p) & 7u) == 0) {
+        TdW4 w;
+        w.v[0] = ((unsigned)b[0] << 6) | ((unsigned)b[1] << 22);
+        w.v[1] = ((unsigned)b[2] << 6) | ((unsigned)b[3] << 22);
+        *reinterpret_cast<TdW4*>(p) = w;
+    } else {
+        for (int i = 0; i < n; ++i) { const unsigned w = (unsigned)b[i] << 6; p[2 * i] = (unsigned char)w; p[2 * i + 1] = (unsigned char)(w >> 8); }
+    }
+}
+template <bool LABELS, bool OVERLAY, int SRC, bool WIDE>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_surface(PicArgs a, OverlaySrc o, SurfLayout sl, DstSurf d) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    const long xa = 4L * q;
+    if (2 * j >= a.oh || xa >= a.ow) return;
+    const int nx = a.ow - xa < 4 ? (int)(a.ow - xa) : 4, ny = a.oh - 2 * j < 2 ? 1 : 2;
+    int s0[3] = {0, 0, 0}, s1[3] = {0, 0, 0};                          // the colour sums of the pair of columns 0, 1 and of columns 2, 3
+    for (int r = 0; r < ny; ++r) {
+        unsigned px[4];
+        td_picture_px4s<LABELS, OVERLAY, SRC>(a, o, sl, 2 * j + r, xa, px);
+        int yb[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c0 = (int)(px[e] & 255u), c1 = (int)((px[e] >> 8) & 255u), c2 = (int)((px[e] >> 16) & 255u);
+            const int t = d.ky[0] * c0 + d.ky[1] * c1 + d.ky[2] * c2 + (d.yoff << 20);
+            yb[e] = WIDE ? td_clamp10((t + (1 << 17)) >> 18) : ingest_clamp8((t + (1 << 19)) >> 20);
+            if (e < nx) {
+                int* s = e < 2 ? s0 : s1;
+                s[0] += c0; s[1] += c1; s[2] += c2;
+            }
+        }
+        unsigned char* yrow = d.base + (size_t)(d.oy + 2 * j + r) * d.pitch;
+        if (WIDE) td_w16_store(yrow + 2 * ((size_t)d.ox + xa), nx, yb);
+        else td_u8_store(yrow + d.ox, xa, xa + nx, yb);
+    }
+    const int m0 = 4 / (ny * (nx < 2 ? nx : 2)), m1 = nx > 2 ? 4 / (ny * (nx - 2)) : 0;
+    const int np = nx > 2 ? 2 : 1;                                     // chroma pairs of this block
+    const int u0 = WIDE ? td_chroma10(d.ku, s0, m0) : td_chroma8(d.ku, s0, m0), v0 = WIDE ? td_chroma10(d.kv, s0, m0) : td_chroma8(d.kv, s0, m0);
+    const int u1 = WIDE ? td_chroma10(d.ku, s1, m1) : td_chroma8(d.ku, s1, m1), v1 = WIDE ? td_chroma10(d.kv, s1, m1) : td_chroma8(d.kv, s1, m1);
+    const size_t crow = (size_t)((d.oy >> 1) + j) * d.cpitch, pair = (size_t)(d.ox >> 1) + 2 * (size_t)q;   // the chroma row, the block's first pair
+    if (WIDE) {                                                        // U, V word pairs: 8 bytes per two pairs
+        const int cb[4] = {u0, v0, u1, v1};
+        td_w16_store(d.base + d.u_off + crow + 4 * pair, 2 * np, cb);
+    } else if (d.cstep == 2) {                                         // interleaved byte pairs, U first or (NV21) V first: wave-uniform
+        const bool vu = d.uo != 0;
+        const int cb[4] = {vu ? v0 : u0, vu ? u0 : v0, vu ? v1 : u1, vu ? u1 : v1};
+        td_u8_store(d.base + d.u_off + crow + d.ox, xa, xa + 2 * np, cb);
+    } else {                                                           // I420: a row of the U plane and a row of the V plane
+        unsigned char* up = d.base + d.u_off + crow + pair;
+        unsigned char* vp = d.base + d.v_off + crow + pair;
+        up[0] = (unsigned char)u0; vp[0] = (unsigned char)v0;
+        if (np == 2) { up[1] = (unsigned char)u1; vp[1] = (unsigned char)v1; }
+    }
+}
+// Packed destinations of the overlay over a surface source: k_picture_packed with the source read by td_overlay_src_surf
+template <int DST, bool LABELS, bool WIDE>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_picture_packed_surf(PicArgs a, const unsigned char* __restrict__ src, SurfLayout sl, DstView d) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= a.oh) return;
+    unsigned char* row = d.base + (size_t)(d.oy + y) * d.pitch + (size_t)d.ox * (DST == TD_DST_P32 ? 4 : 3);
+    long xa, xb;
+    if (DST == TD_DST_P32) td_p32_run(row, q, a.ow, &xa, &xb);
+    else td_rgb_run(row, q, a.ow, &xa, &xb);
+    if (xa >= xb) return;
+    unsigned px[4], s[4];
+    td_picture_px4<LABELS, false, TD_SRC_P24>(a, OverlaySrc(), y, xa, px);
+    td_overlay_src_surf<WIDE>(src, sl, y, xa, a.ow, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
+    if (d.swap) {                                                      // wave-uniform
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_swap_rb(px[e]);
+    }
+    if (DST == TD_DST_P32) td_p32_store(row, xa, xb, px);
+    else td_rgb_store(row, q, xa, xb, px);
+}

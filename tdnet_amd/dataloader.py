@@ -281,6 +281,222 @@ def write_view(frame_bytes, view, picture_rgb):
     return s
 
 
+# ---- surfaces (include/tdnet.h "surfaces") ----------------------------------------------------------------------------------------------
+SURF_NV12, SURF_NV21, SURF_I420, SURF_P010, SURF_YUY2, SURF_UYVY = 0, 1, 2, 3, 4, 5
+SURF_NAMES = {"nv12": SURF_NV12, "nv21": SURF_NV21, "i420": SURF_I420, "p010": SURF_P010, "yuy2": SURF_YUY2, "uyvy": SURF_UYVY}
+SURF_422 = (SURF_YUY2, SURF_UYVY)
+SURF_DST = (SURF_NV12, SURF_NV21, SURF_I420, SURF_P010)          # the layouts a destination may have
+# layout -> (bytes between luma samples, the luma sample's offset, bytes between chroma pairs, U's offset in a pair, V's offset in a pair)
+_SURF_FORM = {SURF_NV12: (1, 0, 2, 0, 1), SURF_NV21: (1, 0, 2, 1, 0), SURF_I420: (1, 0, 1, 0, 0), SURF_P010: (2, 0, 4, 0, 2),
+              SURF_YUY2: (2, 0, 4, 1, 3), SURF_UYVY: (2, 1, 4, 0, 2)}
+
+
+class Surface:
+    """A rectangle of a YUV frame whose planes lie in one allocation (tdnet_surface), every default resolved as include/tdnet.h says: pitch 0 = tight;
+    chroma_pitch 0 = pitch (NV12, NV21, P010) or (pitch + 1) // 2 (I420); u_offset None / 0 = height * pitch; v_offset None / 0 = u_offset +
+    ceil(height / 2) * chroma_pitch (I420).  crop = (y, x, h, w) or None: the whole frame.  YV12 is I420 with the two chroma offsets exchanged.
+    Nothing is validated here beyond what the derived values need: the library's tdnet_set_input_surface / tdnet_set_output_surface are the judges."""
+
+    def __init__(self, layout, height, width, pitch=0, chroma_pitch=0, crop=None, standard=0, u_offset=None, v_offset=None):
+        self.layout = SURF_NAMES[layout.lower()] if isinstance(layout, str) else int(layout)
+        if self.layout not in _SURF_FORM:
+            raise ValueError("Surface: layout %r is not one of SURF_* (0..5)" % (layout,))
+        self.height, self.width, self.pitch, self.chroma_pitch, self.standard = int(height), int(width), int(pitch), int(chroma_pitch), int(standard)
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        if self.crop is not None and len(self.crop) != 4:
+            raise ValueError("Surface: crop is (y, x, height, width)")
+        self.u_offset = None if u_offset is None else int(u_offset)
+        self.v_offset = None if v_offset is None else int(v_offset)
+
+    @property
+    def wide(self):
+        """16-bit words with the 10-bit sample in bits 15..6."""
+        return self.layout == SURF_P010
+
+    @property
+    def packed422(self):
+        return self.layout in SURF_422
+
+    @property
+    def chroma_size(self):
+        """(rows, pairs per row) of the chroma samples."""
+        return (self.height if self.packed422 else (self.height + 1) // 2), (self.width + 1) // 2
+
+    @property
+    def luma_row_bytes(self):
+        return 4 * ((self.width + 1) // 2) if self.packed422 else self.width * _SURF_FORM[self.layout][0]
+
+    @property
+    def chroma_row_bytes(self):
+        return _SURF_FORM[self.layout][2] * ((self.width + 1) // 2)
+
+    @property
+    def row_pitch(self):
+        return self.pitch if self.pitch else self.luma_row_bytes
+
+    @property
+    def cpitch(self):
+        if self.packed422:
+            return self.row_pitch
+        if self.chroma_pitch:
+            return self.chroma_pitch
+        return (self.row_pitch + 1) // 2 if self.layout == SURF_I420 else self.row_pitch
+
+    @property
+    def u_off(self):
+        return 0 if self.packed422 else self.u_offset if self.u_offset else self.height * self.row_pitch
+
+    @property
+    def v_off(self):
+        if self.layout != SURF_I420:
+            return self.u_off
+        return self.v_offset if self.v_offset else self.u_off + ((self.height + 1) // 2) * self.cpitch
+
+    @property
+    def rect(self):
+        return (0, 0, self.height, self.width) if self.crop is None or self.crop == (0, 0, 0, 0) else self.crop
+
+    @property
+    def size(self):
+        return self.rect[2:]
+
+    def key(self):
+        return (self.layout, self.height, self.width, self.row_pitch, self.cpitch) + self.rect + (self.standard, self.u_off, self.v_off)
+
+    def __repr__(self):
+        return "Surface(layout=%d, %dx%d, pitch=%d, chroma_pitch=%d, u=%d, v=%d, rect=%r)" % (self.layout, self.height, self.width, self.row_pitch, self.cpitch,
+                                                                                               self.u_off, self.v_off, self.rect)
+
+
+def surface_sample_index(surface):
+    """(luma [height, width], U [rows, pairs], V [rows, pairs]): the byte index of every sample of the WHOLE frame (of its low byte for P010), by the
+    table of include/tdnet.h "surfaces".  Pixel (Y, X) takes chroma sample (Y >> 1, X >> 1) -- 4:2:2: (Y, X >> 1)."""
+    s = surface
+    ls, lo, cs, uo, vo = _SURF_FORM[s.layout]
+    rows, pairs = s.chroma_size
+    luma = np.arange(s.height)[:, None] * s.row_pitch + np.arange(s.width)[None, :] * ls + lo
+    c = np.arange(rows)[:, None] * s.cpitch + np.arange(pairs)[None, :] * cs
+    return luma, s.u_off + c + uo, s.v_off + c + vo
+
+
+def surface_extent(surface):
+    """Bytes from the surface's base to the largest end over its planes (last row's start + row bytes): nothing behind them is ever touched."""
+    s = surface
+    end = (s.height - 1) * s.row_pitch + s.luma_row_bytes
+    if not s.packed422:
+        plane = (s.chroma_size[0] - 1) * s.cpitch + s.chroma_row_bytes
+        end = max(end, s.u_off + plane, s.v_off + plane)
+    return end
+
+
+def _surface_samples(buf, surface, idx):
+    return (buf[idx].astype(np.int64) | (buf[idx + 1].astype(np.int64) << 8)) >> 6 if surface.wide else buf[idx].astype(np.int64)
+
+
+def surface_to_rgb_u8(buf, surface):
+    """The oracle of the library's surface input: the bytes of a frame -> uint8 RGB [h, w, 3] of the surface's rectangle.  Every pixel of the WHOLE frame
+    is converted at its absolute coordinates, then the rectangle is sliced: an odd origin shifts the chroma phase.  8 bit: nv12_to_rgb_u8's formulas.
+    P010, on the 10-bit samples w16 >> 6, K = rint(c * 2^18):
+        yy = max(0, Y10 - 4 yoff) * CY + 2^19;  u = U10 - 512;  v = V10 - 512;  R = clamp8((yy + CVR v) >> 20) ...
+    in integers that fit int32 (asserted)."""
+    b = np.asarray(buf).reshape(-1)
+    s = surface
+    assert b.dtype == np.uint8 and b.size >= surface_extent(s), (b.dtype, b.size, surface_extent(s))
+    y, x, h, w = s.rect
+    assert 0 <= y and 0 <= x and h >= 1 and w >= 1 and y + h <= s.height and x + w <= s.width
+    li, ui, vi = surface_sample_index(s)
+    cy_, cx_ = (np.arange(s.height) >> (0 if s.packed422 else 1))[:, None], (np.arange(s.width) >> 1)[None, :]
+    Y, U, V = _surface_samples(b, s, li), _surface_samples(b, s, ui)[cy_, cx_], _surface_samples(b, s, vi)[cy_, cx_]
+    yoff, dec = NV12_STANDARDS[int(s.standard)]
+    bits = 18 if s.wide else 20
+    CY, CUB, CUG, CVG, CVR = (int(np.rint(c * float(1 << bits))) for c in dec)
+    mid, yoff = (512, 4 * yoff) if s.wide else (128, yoff)
+    u, v = U - mid, V - mid
+    yy = np.maximum(0, Y - yoff) * CY + (1 << 19)
+    sums = np.stack([yy + CVR * v, yy + CVG * v + CUG * u, yy + CUB * u], axis=-1)
+    assert np.abs(sums).max() < 2 ** 31 and np.abs(CVG * v).max() < 2 ** 31
+    return np.ascontiguousarray(np.clip(sums >> 20, 0, 255).astype(np.uint8)[y:y + h, x:x + w])
+
+
+def surface_from_samples(Y, U, V, surface, fill=0, low_bits=None):
+    """The bytes [0, surface_extent) of the WHOLE frame from its samples: Y [height, width], U and V [chroma rows, pairs] -- bytes, or 10-bit values for
+    P010, whose words' low 6 bits take low_bits (an int, or an array of three of the samples' shapes; default 0).  Every other byte holds `fill`."""
+    s = surface
+    li, ui, vi = surface_sample_index(s)
+    out = np.full(surface_extent(s), fill, np.uint8)
+    lows = [0, 0, 0] if low_bits is None else [low_bits] * 3 if np.isscalar(low_bits) else list(low_bits)
+    for idx, val, low in ((li, Y, lows[0]), (ui, U, lows[1]), (vi, V, lows[2])):
+        val = np.asarray(val).astype(np.int64)
+        assert val.shape == idx.shape and val.min() >= 0 and val.max() < (1024 if s.wide else 256), (val.shape, idx.shape)
+        if s.wide:
+            word = (val << 6) | (np.asarray(low).astype(np.int64) & 63)
+            out[idx], out[idx + 1] = (word & 255).astype(np.uint8), (word >> 8).astype(np.uint8)
+        else:
+            out[idx] = val.astype(np.uint8)
+    return out
+
+
+def _surface_forward(pic, surface):
+    """(Y [h, w], U, V [ceil(h / 2), ceil(w / 2)]) of a picture [h, w, 3] placed at an EVEN origin, by the forward formulas of "destination views" (8 bit) and
+    of "surfaces" (P010): the samples a 4:2:0 destination takes."""
+    if not surface.wide:
+        Y, UV = nv12_from_rgb_u8(pic, surface.standard, planes=True)
+        return Y.astype(np.int64), UV[..., 0].astype(np.int64), UV[..., 1].astype(np.int64)
+    H, W = pic.shape[:2]
+    hc, wc = (H + 1) // 2, (W + 1) // 2
+    yoff, K = nv12_forward_coeffs(surface.standard)
+    p = pic.astype(np.int64)
+    assert (p @ np.abs(K[0])).max() + (yoff << 20) + (1 << 17) < 2 ** 31
+    Y = np.clip((p @ K[0] + (yoff << 20) + (1 << 17)) >> 18, 0, 1023)
+    S, cnt = np.zeros((2 * hc, 2 * wc, 3), np.int64), np.zeros((2 * hc, 2 * wc), np.int64)
+    S[:H, :W], cnt[:H, :W] = p, 1
+    S, n = S.reshape(hc, 2, wc, 2, 3).sum(axis=(1, 3)), cnt.reshape(hc, 2, wc, 2).sum(axis=(1, 3))
+    m = (4 // n)[..., None]
+    assert (m * (S @ np.abs(K[1:]).T)).max() + (128 << 22) + (1 << 19) < 2 ** 31
+    UV = np.clip((m * (S @ K[1:].T) + (128 << 22) + (1 << 19)) >> 20, 0, 1023)
+    return Y, UV[..., 0], UV[..., 1]
+
+
+def pack_surface(rgb_frame, surface, fill=0):
+    """A host generator: the bytes [0, surface_extent) of the WHOLE frame rgb_frame [height, width, 3] in the surface's layout; padding and gaps hold
+    `fill`.  4:2:0: the forward formulas a destination uses; 4:2:2: their luma, and per pixel pair of a row the chroma of that pair's mean -- it only
+    has to be a function, surface_to_rgb_u8 is not its inverse."""
+    img = np.asarray(rgb_frame)
+    s = surface
+    assert img.dtype == np.uint8 and img.shape == (s.height, s.width, 3)
+    if not s.packed422:
+        return surface_from_samples(*_surface_forward(img, s), s, fill)
+    yoff, K = nv12_forward_coeffs(s.standard)
+    p = img.astype(np.int64)
+    Y = np.clip((p @ K[0] + (yoff << 20) + (1 << 19)) >> 20, 0, 255)
+    wc = (s.width + 1) // 2
+    pad = np.concatenate([p, p[:, -1:]], axis=1)[:, :2 * wc].reshape(s.height, wc, 2, 3).sum(axis=2)
+    UV = np.clip((2 * (pad @ K[1:].T) + (128 << 22) + (1 << 21)) >> 22, 0, 255)
+    return surface_from_samples(Y, UV[..., 0], UV[..., 1], s, fill)
+
+
+def write_surface(frame_bytes, surface, picture_rgb):
+    """The host oracle of the library's surface destinations (NV12, NV21, I420, P010; even origin): a COPY of a frame's bytes with picture_rgb [h, w, 3]
+    (true r, g, b) written into the surface's rectangle -- its luma samples and the chroma samples covering it, by the forward formulas; P010 stores
+    value << 6, little-endian, the low bits zero.  Every other byte keeps its value."""
+    s = surface
+    b = np.array(np.asarray(frame_bytes).reshape(-1), copy=True)
+    pic = np.asarray(picture_rgb)
+    y, x, h, w = s.rect
+    assert s.layout in SURF_DST, "YUY2 / UYVY are not destination layouts"
+    assert b.dtype == np.uint8 and b.size >= surface_extent(s) and pic.dtype == np.uint8 and pic.shape == (h, w, 3), (b.dtype, b.size, pic.shape, s.rect)
+    assert 0 <= y and 0 <= x and y + h <= s.height and x + w <= s.width and y % 2 == 0 and x % 2 == 0, "a 4:2:0 destination starts on the chroma grid"
+    Y, U, V = _surface_forward(pic, s)
+    li, ui, vi = surface_sample_index(s)
+    hc, wc = U.shape
+    for idx, val in ((li[y:y + h, x:x + w], Y), (ui[y // 2:y // 2 + hc, x // 2:x // 2 + wc], U), (vi[y // 2:y // 2 + hc, x // 2:x // 2 + wc], V)):
+        if s.wide:
+            b[idx], b[idx + 1] = ((val << 6) & 255).astype(np.uint8), (val >> 2).astype(np.uint8)
+        else:
+            b[idx] = val.astype(np.uint8)
+    return b
+
+
 def nearest_index(n_src, n_dst):
     """Source index per destination index of the nearest-sample resize of the label map (test.py:64, cv2.INTER_NEAREST): int64 [n_dst] =
     min(int64(o * (n_src / n_dst)), n_src - 1) -- the quotient first, in float64, then the product, then truncation.  This is the project's rule:

@@ -29,6 +29,18 @@ def view_struct(view):
     return t
 
 
+def surface_struct(surface):
+    """_capi.TdnetSurface of a dataloader.Surface, as the caller stated it (0 / None stay the C ABI's defaults)."""
+    t = _capi.TdnetSurface()
+    t.layout, t.height, t.width, t.pitch, t.chroma_pitch, t.standard = (surface.layout, surface.height, surface.width, surface.pitch, surface.chroma_pitch,
+                                                                        surface.standard)
+    if surface.crop is not None:
+        t.crop_y, t.crop_x, t.crop_height, t.crop_width = surface.crop
+    t.u_offset = 0 if surface.u_offset is None else surface.u_offset
+    t.v_offset = 0 if surface.v_offset is None else surface.v_offset
+    return t
+
+
 class Engine:
     def __init__(self, model, backbone, nclass, height, width, device=0, lib=None, opts=None, _shared_from=None, arch=None):
         """opts: None (library defaults) or a dict of tdnet_opts fields (winograd=, precision=, pipeline=, ...): per handle.
@@ -151,6 +163,21 @@ class Engine:
         self.lib.check(self.lib.tdnet_set_input_view(self.h, ctypes.byref(view_struct(view)), m, sd))
         self._view_key, self._u8_key, self._nv12_key = key, None, None
 
+    def set_input_surface(self, surface, mean=None, std=None):
+        """Frames will arrive as YUV surfaces (include/tdnet.h "surfaces"; `surface`: a dataloader.Surface -- NV12, NV21, I420 / YV12, P010, YUY2, UYVY):
+        the byte entries then read their image pointer as the surface's base and take its rectangle, until another set_input_* call.  A configuration
+        call (it may synchronise); the library recognises equal arguments itself."""
+        for v in (mean, std):
+            if v is not None and len(v) != 3:
+                raise _capi.TdnetError("set_input_surface: mean and std are three numbers each")
+        for name in ("u_offset", "v_offset"):
+            if getattr(surface, name) is not None and getattr(surface, name) < 0:
+                raise _capi.TdnetError("set_input_surface: %s must not be negative" % name)
+        m = None if mean is None else (ctypes.c_double * 3)(*[float(v) for v in mean])
+        sd = None if std is None else (ctypes.c_double * 3)(*[float(v) for v in std])
+        self.lib.check(self.lib.tdnet_set_input_surface(self.h, ctypes.byref(surface_struct(surface)), m, sd))
+        self._u8_key, self._nv12_key, self._view_key = None, None, None   # ONE byte-input configuration per handle
+
     def forward_u8(self, img_ptr, pos_id, logits_ptr, stream=None):
         self.lib.check(self.lib.tdnet_forward_u8(self.h, _ptr(img_ptr), int(pos_id), _ptr(logits_ptr), stream))
 
@@ -215,6 +242,14 @@ class Engine:
         self.lib.check(self.lib.tdnet_labels_overlay(self.h, _ptr(labels_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
 
     # ---- destination views (include/tdnet.h) ----
+    def set_output_surface(self, surface):
+        """The picture entries write into `surface`'s rectangle of a 4:2:0 frame (a dataloader.Surface: NV12, NV21, I420 / YV12 or P010; their picture
+        pointer is then the surface's base); None: the contiguous block again.  Replaces a destination view, and is replaced by one."""
+        for name in ("u_offset", "v_offset"):
+            if surface is not None and getattr(surface, name) is not None and getattr(surface, name) < 0:
+                raise _capi.TdnetError("set_output_surface: %s must not be negative" % name)
+        self.lib.check(self.lib.tdnet_set_output_surface(self.h, None if surface is None else ctypes.byref(surface_struct(surface))))
+
     def set_output_view(self, view):
         """The picture entries (forward_rgb, forward_u8_rgb, propagate_rgb, labels_rgb, forward_u8_overlay, propagate_overlay, labels_overlay) will
         write into `view`'s rectangle of a pitched frame (a dataloader.SourceView; their picture pointer is then the frame's base); None: the

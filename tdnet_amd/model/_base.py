@@ -290,11 +290,65 @@ class _TDNetBase(nn.Module):
     # view: a dataloader.SourceView (include/tdnet.h "source views") -- img_u8 is then a contiguous uint8 tensor [N, nbytes], nbytes >= view_extent(view):
     # N WHOLE frames in the view's format and pitch, of which the library reads the view's rectangle (b g r or 4-byte pixels, a crop, an NV12 surface
     # with a display rectangle), bit-identically to forward_u8(dataloader.view_to_rgb_u8(frame, view)).
+    # surface: a dataloader.Surface (include/tdnet.h "surfaces") in place of view -- img_u8 is then N WHOLE YUV frames [N, nbytes], nbytes >=
+    # surface_extent(surface), in one of the layouts NV12 / NV21 / I420 (YV12) / P010 / YUY2 / UYVY, bit-identically to
+    # forward_u8(dataloader.surface_to_rgb_u8(frame, surface)).  out_surface: a 4:2:0 Surface in place of out_view.  Giving both of a pair is an error.
+    @staticmethod
+    def _one_of(a, b, name_a, name_b):
+        """view= and surface= (out_view= and out_surface=) describe the same thing two ways: at most one of them."""
+        if a is not None and b is not None:
+            raise RuntimeError("give %s or %s, not both" % (name_a, name_b))
+        return a if b is None else b
+
+    @staticmethod
+    def _is_surface(x):
+        from ..dataloader import Surface
+        return isinstance(x, Surface)
+
+    def _set_in(self, eng, view, mean, std):
+        (eng.set_input_surface if self._is_surface(view) else eng.set_input_view)(view, mean, std)
+
+    def _set_out(self, eng, out_view):
+        """The destination of the picture entries: a view, a surface, or None (either call restores the contiguous block)."""
+        (eng.set_output_surface if self._is_surface(out_view) else eng.set_output_view)(out_view)
+
+    @classmethod
+    def _frame_extent(cls, x):
+        from ..dataloader import surface_extent, view_extent
+        return surface_extent(x) if cls._is_surface(x) else view_extent(x)
+
+    @staticmethod
+    def _check_surface(s, what, dst=False):
+        """What the derived values of a Surface need, before an engine exists; the library judges the rest."""
+        from ..dataloader import SURF_DST
+        y, x, h, w = s.rect
+        if s.height < 1 or s.width < 1 or h < 1 or w < 1 or y < 0 or x < 0 or y + h > s.height or x + w > s.width:
+            raise RuntimeError("%s's rectangle (y, x, h, w) = %r is not inside its %d x %d frame" % (what, s.rect, s.height, s.width))
+        if s.row_pitch < s.luma_row_bytes:
+            raise RuntimeError("%s's pitch %d is below the %d bytes a row of %d pixels holds" % (what, s.row_pitch, s.luma_row_bytes, s.width))
+        if not s.packed422 and s.cpitch < s.chroma_row_bytes:
+            raise RuntimeError("%s's chroma pitch %d is below the %d bytes a chroma row of %d pixels holds" % (what, s.cpitch, s.chroma_row_bytes, s.width))
+        if dst and s.layout not in SURF_DST:
+            raise RuntimeError("%s: YUY2 / UYVY are not destination layouts (NV12, NV21, I420 and P010 are)" % what)
+        if dst and (y % 2 or x % 2):
+            raise RuntimeError("%s's origin (%d, %d) must be even for a 4:2:0 destination" % (what, y, x))
+
     def _check_frame_view(self, img, view):
         """The error classes of _check_frame_u8 for a batch of whole frames read through `view`; nothing is built before it passes."""
-        from ..dataloader import SourceView, view_extent
-        if not isinstance(view, SourceView):
-            raise RuntimeError("view must be a dataloader.SourceView, got %s" % type(view).__name__)
+        from ..dataloader import SourceView, Surface, view_extent
+        if not isinstance(view, (SourceView, Surface)):
+            raise RuntimeError("view must be a dataloader.SourceView (surface: a dataloader.Surface), got %s" % type(view).__name__)
+        if isinstance(view, Surface):
+            if not torch.is_tensor(img) or img.dtype != torch.uint8:
+                raise RuntimeError("expected a torch.uint8 frame tensor [N,nbytes], got %s" % (img.dtype if torch.is_tensor(img) else type(img).__name__))
+            if img.dim() != 2 or img.shape[0] < 1:
+                raise RuntimeError("expected a uint8 frame tensor [N,nbytes] (whole surfaces) with N >= 1, got shape %s" % (tuple(img.shape),))
+            if not img.is_contiguous():
+                raise RuntimeError("expected a CONTIGUOUS uint8 frame tensor [N,nbytes]: the surface's pitches describe the rows")
+            self._check_surface(view, "the surface")
+            if int(img.shape[1]) < self._frame_extent(view):
+                raise RuntimeError("a frame tensor of %d bytes per sample is below the %d bytes the surface needs" % (img.shape[1], self._frame_extent(view)))
+            return
         if not torch.is_tensor(img) or img.dtype != torch.uint8:
             raise RuntimeError("expected a torch.uint8 frame tensor [N,nbytes], got %s" % (img.dtype if torch.is_tensor(img) else type(img).__name__))
         if img.dim() != 2 or img.shape[0] < 1:
@@ -338,7 +392,7 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             if view is not None:
-                eng.set_input_view(view, mean, std)
+                self._set_in(eng, view, mean, std)
             elif nv12 is None:
                 eng.set_input_u8(Hs, Ws, mean, std)                    # (re)configured when the source size changes; a no-op otherwise
             else:
@@ -346,31 +400,34 @@ class _TDNetBase(nn.Module):
             call(i, eng, s)
         self._for_each_sample(img, one, size)
 
-    def forward_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
+    def forward_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
         """forward() on the decoded bytes: logits [N, nclass, H, W] at the network size."""
+        view = self._one_of(view, surface, "view", "surface")
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         out = torch.empty((img.shape[0], self.nclass, H, W), device=img.device, dtype=torch.float32)
         self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, view=view)
         return out
 
-    def forward_labels_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
+    def forward_labels_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
         """forward_labels() on the decoded bytes, labels as uint8 [N, H, W] (the same labels: nclass <= 256)."""
+        view = self._one_of(view, surface, "view", "surface")
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8)
         self._u8_call(img, (H, W), lambda i, eng, s: eng.forward_u8_labels(img[i].data_ptr(), pos_id, out[i].data_ptr(), s), mean, std, view=view)
         return out
 
-    def encode_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
+    def encode_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
         """encode() on the decoded bytes."""
+        view = self._one_of(view, surface, "view", "surface")
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         if img_u8.shape[0] != 1:
             raise RuntimeError("encode_u8(): the split frame serves ONE stream (batch size 1)")
         img = img_u8.contiguous()
         eng = self._engine_for(H, W, img.device.index or 0, 1)
         if view is not None:
-            eng.set_input_view(view, mean, std)
+            self._set_in(eng, view, mean, std)
         else:
             eng.set_input_u8(int(img.shape[1]), int(img.shape[2]), mean, std)
         self._pending_shape = (H, W, img.device)
@@ -516,17 +573,23 @@ class _TDNetBase(nn.Module):
         from ..dataloader import view_extent
         self._dst_check(out_view, out, size, n)
         if out is None:
-            return torch.zeros((n, view_extent(out_view)), device=device, dtype=torch.uint8)
+            return torch.zeros((n, self._frame_extent(out_view)), device=device, dtype=torch.uint8)
         if out.device != device:
             raise RuntimeError("out must be on the frames' device %s, got %s" % (device, out.device))
         return out
 
-    @staticmethod
-    def _dst_check(out_view, out, size, n):
-        """The checks of a destination view and tensor, made before an engine exists (and before the frames' device is looked at, like view=)."""
-        from ..dataloader import SourceView, view_extent
-        if not isinstance(out_view, SourceView):
-            raise RuntimeError("out_view must be a dataloader.SourceView, got %s" % type(out_view).__name__)
+    @classmethod
+    def _dst_check(cls, out_view, out, size, n):
+        """The checks of a destination view (or surface) and tensor, made before an engine exists (and before the frames' device is looked at, like view=)."""
+        from ..dataloader import SourceView, Surface, view_extent
+        if not isinstance(out_view, (SourceView, Surface)):
+            raise RuntimeError("out_view must be a dataloader.SourceView (out_surface: a dataloader.Surface), got %s" % type(out_view).__name__)
+        if isinstance(out_view, Surface):
+            cls._check_surface(out_view, "out_surface", dst=True)
+            if tuple(out_view.size) != tuple(int(v) for v in size):
+                raise RuntimeError("out_surface's rectangle is %d x %d but the picture is %d x %d: nothing is resized" % (tuple(out_view.size) + (size[0], size[1])))
+            cls._dst_tensor_check(out, n, cls._frame_extent(out_view), "out_surface")
+            return
         y, x, h, w = out_view.rect
         if out_view.height < 1 or out_view.width < 1 or h < 1 or w < 1 or y < 0 or x < 0 or y + h > out_view.height or x + w > out_view.width:
             raise RuntimeError("out_view's rectangle (y, x, h, w) = %r is not inside its %d x %d frame" % (out_view.rect, out_view.height, out_view.width))
@@ -539,7 +602,10 @@ class _TDNetBase(nn.Module):
             raise RuntimeError("out_view's uv_offset %d is inside the Y plane (%d rows of pitch %d)" % (out_view.uv, out_view.height, out_view.row_pitch))
         if out_view.nv12 and (y % 2 or x % 2):
             raise RuntimeError("out_view's origin (%d, %d) must be even for an NV12 destination" % (y, x))
-        need = view_extent(out_view)
+        cls._dst_tensor_check(out, n, view_extent(out_view), "out_view")
+
+    @staticmethod
+    def _dst_tensor_check(out, n, need, what):
         if out is None:
             return
         if not torch.is_tensor(out) or out.dtype != torch.uint8:
@@ -547,16 +613,17 @@ class _TDNetBase(nn.Module):
         if out.dim() != 2 or out.shape[0] != n:
             raise RuntimeError("out must be a uint8 tensor [N,nbytes] with N = %d (whole destination frames), got shape %s" % (n, tuple(out.shape)))
         if not out.is_contiguous():
-            raise RuntimeError("out must be a CONTIGUOUS uint8 tensor [N,nbytes]: out_view's pitch describes the rows")
+            raise RuntimeError("out must be a CONTIGUOUS uint8 tensor [N,nbytes]: %s's pitch describes the rows" % what)
         if int(out.shape[1]) < need:
-            raise RuntimeError("out holds %d bytes per sample, below the %d bytes out_view's frame needs" % (out.shape[1], need))
+            raise RuntimeError("out holds %d bytes per sample, below the %d bytes %s's frame needs" % (out.shape[1], need, what))
 
     def _rgb_out(self, n, out_size, device):
         oh, ow = self._rgb_size(out_size)
         return torch.empty((n, oh, ow, 3), device=device, dtype=torch.uint8)
 
-    def forward_rgb(self, img, pos_id, out_size, palette=None, out_view=None, out=None):
+    def forward_rgb(self, img, pos_id, out_size, palette=None, out_view=None, out=None, out_surface=None):
         """forward_labels() with the colour map [N, oh, ow, 3] uint8 in place of the label map (out_view: see _dst_out)."""
+        out_view = self._one_of(out_view, out_surface, "out_view", "out_surface")
         oh, ow = self._rgb_size(out_size)
         self._check_frame(img, pos_id)
         out = self._dst_out(out_view, out, (oh, ow), img.shape[0], img.device) if out_view is not None else self._rgb_out(img.shape[0], out_size, img.device)
@@ -565,13 +632,15 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             eng.set_output_rgb(oh, ow, pal)
-            eng.set_output_view(out_view)
+            self._set_out(eng, out_view)
             eng.forward_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._for_each_sample(img, one)
         return out
 
-    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None, view=None, out_view=None, out=None):
+    def forward_rgb_u8(self, img_u8, pos_id, in_size, out_size, palette=None, mean=None, std=None, view=None, out_view=None, out=None, surface=None, out_surface=None):
         """forward_labels_u8() with the colour map [N, oh, ow, 3] uint8 in place of the label map: bytes in, picture out (out_view: see _dst_out)."""
+        view = self._one_of(view, surface, "view", "surface")
+        out_view = self._one_of(out_view, out_surface, "out_view", "out_surface")
         oh, ow = self._rgb_size(out_size)
         if out_view is not None and torch.is_tensor(img_u8) and img_u8.dim() >= 1:
             self._dst_check(out_view, out, (oh, ow), img_u8.shape[0])
@@ -582,13 +651,14 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             eng.set_output_rgb(oh, ow, pal)
-            eng.set_output_view(out_view)
+            self._set_out(eng, out_view)
             eng.forward_u8_rgb(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
 
-    def labels_rgb(self, labels_u8, out_size, palette=None, out_view=None, out=None):
+    def labels_rgb(self, labels_u8, out_size, palette=None, out_view=None, out=None, out_surface=None):
         """uint8 labels [N, H, W] (CUDA) of this model -> their colour maps [N, oh, ow, 3] (out_view: see _dst_out)."""
+        out_view = self._one_of(out_view, out_surface, "out_view", "out_surface")
         if self._engine is None:
             raise RuntimeError("labels_rgb(): no handle yet")
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
@@ -597,7 +667,7 @@ class _TDNetBase(nn.Module):
         oh, ow = self._rgb_size(out_size)
         out = self._dst_out(out_view, out, (oh, ow), labels.shape[0], labels.device) if out_view is not None else self._rgb_out(labels.shape[0], out_size, labels.device)
         self._engine.set_output_rgb(oh, ow, self._palette(palette))
-        self._engine.set_output_view(out_view)
+        self._set_out(self._engine, out_view)
         s = torch.cuda.current_stream(labels.device).cuda_stream
         for i in range(labels.shape[0]):
             self._engine.labels_rgb(labels[i].data_ptr(), out[i].data_ptr(), s)
@@ -624,9 +694,11 @@ class _TDNetBase(nn.Module):
         out[:, 3] = np.rint(255.0 * a).astype(np.uint8)
         return out
 
-    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None, view=None, out_view=None, out=None):
+    def forward_overlay_u8(self, img_u8, pos_id, in_size, palette=None, alpha=0.5, mean=None, std=None, view=None, out_view=None, out=None, surface=None, out_surface=None):
         """forward_labels_u8() with the overlay [N, Hs, Ws, 3] uint8 in place of the label map: the frame's bytes in, the tinted frame out
         (out_view: see _dst_out)."""
+        view = self._one_of(view, surface, "view", "surface")
+        out_view = self._one_of(out_view, out_surface, "out_view", "out_surface")
         pal = self._palette_rgba(palette, alpha)
         if view is not None:
             self._check_frame_view(img_u8, view)
@@ -641,7 +713,7 @@ class _TDNetBase(nn.Module):
 
         def one(i, eng, s):
             eng.set_output_overlay(pal)
-            eng.set_output_view(out_view)
+            self._set_out(eng, out_view)
             eng.forward_u8_overlay(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, view=view)
         return out
@@ -675,10 +747,12 @@ class _TDNetBase(nn.Module):
         return src.contiguous(), (nv[0], nv[1]), nv
 
     def labels_overlay(self, labels_u8, src, palette=None, alpha=0.5, src_size=None, uv_offset=None, standard=0, mean=None, std=None, view=None,
-                       out_view=None, out=None):
+                       out_view=None, out=None, surface=None, out_surface=None):
         """uint8 labels [N, H, W] (CUDA) of this model blended over their source frames -> [N, Hs, Ws, 3]; src: uint8 [N, Hs, Ws, 3], or with
         src_size=(Hs, Ws) NV12 surfaces [N, rows, pitch].  After forward_labels_conf_u8 with a reject_label outside the palette: the overlay over
         the accepted pixels only (out_view: see _dst_out)."""
+        view = self._one_of(view, surface, "view", "surface")
+        out_view = self._one_of(out_view, out_surface, "out_view", "out_surface")
         if self._engine is None:
             raise RuntimeError("labels_overlay(): no handle yet")
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != tuple(self._engine_key[:2]):
@@ -698,13 +772,13 @@ class _TDNetBase(nn.Module):
             out = torch.empty((labels.shape[0], Hs, Ws, 3), device=labels.device, dtype=torch.uint8)
         eng = self._engine
         if view is not None:
-            eng.set_input_view(view, mean, std)
+            self._set_in(eng, view, mean, std)
         elif nv is None:
             eng.set_input_u8(Hs, Ws, mean, std)
         else:
             eng.set_input_nv12(*nv, mean=mean, std=std)
         eng.set_output_overlay(pal)
-        eng.set_output_view(out_view)
+        self._set_out(eng, out_view)
         s = torch.cuda.current_stream(labels.device).cuda_stream
         for i in range(labels.shape[0]):
             eng.labels_overlay(labels[i].data_ptr(), img[i].data_ptr(), out[i].data_ptr(), s)
@@ -743,8 +817,9 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, one)
         return out
 
-    def forward_score_u8(self, img_u8, gt_u8, pos_id=0, in_size=None, gt_map=None, return_labels=False, mean=None, std=None, view=None):
+    def forward_score_u8(self, img_u8, gt_u8, pos_id=0, in_size=None, gt_map=None, return_labels=False, mean=None, std=None, view=None, surface=None):
         """forward_labels_u8() with the frame scored on the device: bytes in, counts added; the uint8 labels [N, H, W] if return_labels."""
+        view = self._one_of(view, surface, "view", "surface")
         self._check_gt_type(gt_u8)
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
@@ -828,8 +903,9 @@ class _TDNetBase(nn.Module):
         self._for_each_sample(img, one)
         return out, conf
 
-    def forward_labels_conf_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None):
+    def forward_labels_conf_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
         """forward_labels_u8() with the confidence map: bytes in, (labels uint8 [N, H, W], conf uint8 [N, H, W]) out."""
+        view = self._one_of(view, surface, "view", "surface")
         H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
         img = img_u8.contiguous()
         shape = (img.shape[0], H, W)

@@ -25,6 +25,10 @@ label 255 and therefore decode_segmap's grey (255, 255, 255) in the picture.  Ei
 SOURCE-size picture instead of the quarter-size colour map (include/tdnet.h "overlay out"); with `--min_conf` the rejected pixels show the bare frame.
 `--crop Y,X,H,W` (with `--u8` or `--nv12`) uploads the frames WHOLE and has the device take that rectangle of them in the frame's first launch
 (include/tdnet.h "source views"): the result is the one of the pre-cropped frames; with `--overlay` the picture is the rectangle's.
+`--yuv LAYOUT` (nv12, nv21, i420, p010, yuy2, uyvy) turns every frame into a tight surface of that layout on the host (dataloader.pack_surface;
+`--nv12_standard` 0..3) and feeds the surfaces (include/tdnet.h "surfaces"); it combines with what `--nv12` combines with, `--crop` included.
+`--out_yuv LAYOUT:FILE` is `--out_nv12`'s sibling for the destination layouts nv12, nv21, i420 and p010: the device writes every frame's picture through a
+destination surface, appended to the raw file.
 """
 import argparse
 import os
@@ -56,6 +60,13 @@ def load_ground_truth(gt_path, items, size, nearest_index, pin):
     return out
 
 
+def yuv_surface(layout, height, width, standard, crop=None):
+    """The tight surface --yuv packs a frame into and --out_yuv has the device write: no padding in any row (the chroma rows' own bytes are their pitch)."""
+    from tdnet_amd.dataloader import Surface
+    t = Surface(layout, height, width)
+    return Surface(layout, height, width, chroma_pitch=0 if t.packed422 else t.chroma_row_bytes, crop=crop, standard=standard)
+
+
 def test(args):
     os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu                      # test.py:19
     os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -66,11 +77,18 @@ def test(args):
     u8 = bool(getattr(args, "u8", False))
     nv12 = bool(getattr(args, "nv12", False))
     nv12_std = int(getattr(args, "nv12_standard", 0) or 0)
-    if nv12 and u8:
-        raise SystemExit("--nv12 and --u8 are two forms of the byte input: choose one")
+    yuv = getattr(args, "yuv", None)
+    if yuv is not None:                                                # checked before anything is loaded
+        from tdnet_amd.dataloader import SURF_NAMES
+        if str(yuv).lower() not in SURF_NAMES:
+            raise SystemExit("--yuv: one of %s expected, got %r" % (", ".join(sorted(SURF_NAMES)), yuv))
+        yuv = SURF_NAMES[str(yuv).lower()]
+    if sum((nv12, u8, yuv is not None)) > 1:
+        raise SystemExit("--nv12%s and --u8 are two forms of the byte input: choose one" % ("" if yuv is None else ", --yuv"))
+    bytes_in = u8 or nv12 or yuv is not None
     crop = getattr(args, "crop", None)
     if crop is not None:                                               # checked before anything is loaded
-        if not (u8 or nv12):
+        if not bytes_in:
             raise SystemExit("--crop takes a rectangle of the frame's own bytes: give --u8 or --nv12 with it")
         try:
             crop = tuple(int(v) for v in str(crop).split(","))
@@ -81,21 +99,37 @@ def test(args):
     rgb = bool(getattr(args, "rgb", False))
     overlay = getattr(args, "overlay", None)
     if overlay is not None:                                            # checked before anything is loaded
-        if not (u8 or nv12):
+        if not bytes_in:
             raise SystemExit("--overlay blends the class colours over the frame's own bytes: give --u8 or --nv12 with it (an fp32 tensor has no source bytes)")
         if rgb or getattr(args, "gt_path", None):
             raise SystemExit("--overlay, --rgb and --gt_path ask for different last kernels: choose one")
         if not 0.0 <= overlay <= 1.0:
             raise SystemExit("--overlay: an opacity in 0..1 expected, got %r" % (overlay,))
-    out_nv12 = getattr(args, "out_nv12", None)
+    out_nv12, out_yuv = getattr(args, "out_nv12", None), getattr(args, "out_yuv", None)
+    out_layout = None
+    if out_yuv is not None:                                            # LAYOUT:FILE; checked before anything is loaded
+        from tdnet_amd.dataloader import SURF_DST, SURF_NAMES
+        name, _, path = str(out_yuv).partition(":")
+        if SURF_NAMES.get(name.lower()) not in SURF_DST or not path:
+            raise SystemExit("--out_yuv: LAYOUT:FILE expected with LAYOUT one of nv12, nv21, i420, p010 (no encoder takes yuy2 / uyvy), got %r" % (out_yuv,))
+        if out_nv12 is not None:
+            raise SystemExit("--out_yuv and --out_nv12 name the same raw file two ways: choose one")
+        out_layout, out_nv12 = SURF_NAMES[name.lower()], path
     if out_nv12 is not None:                                           # checked before anything is loaded
-        if not (u8 or nv12) or not (rgb or overlay is not None):
+        if not bytes_in or not (rgb or overlay is not None):
             raise SystemExit("--out_nv12 writes the frame's picture as NV12 surfaces: give --rgb or --overlay, and --u8 or --nv12, with it")
         if getattr(args, "prefetch", False) or getattr(args, "gt_path", None) or getattr(args, "conf", None) is not None or getattr(args, "min_conf", None) is not None:
             raise SystemExit("--out_nv12 belongs to the frame-by-frame picture loop: not with --prefetch, --gt_path, --conf or --min_conf")
-    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8, as_nv12=nv12,
+    vid_seq = cityscapesLoader(img_path=args.img_path, in_size=(H, W), pin_memory=getattr(args, "prefetch", False), as_uint8=u8 or yuv is not None, as_nv12=nv12,
                                nv12_standard=nv12_std)
     vid_seq.load_frames()
+    if yuv is not None:                                                # every frame a tight surface [1, nbytes]; the item carries (Hs, Ws) like an NV12 item
+        from tdnet_amd.dataloader import pack_surface
+        for item in vid_seq.data:
+            frame = item[0][0].numpy()
+            t = torch.from_numpy(pack_surface(frame, yuv_surface(yuv, frame.shape[0], frame.shape[1], nv12_std))[np.newaxis])
+            item[0] = t.pin_memory() if getattr(args, "prefetch", False) else t
+            item.append((frame.shape[0], frame.shape[1]))
     if args.model == "td4-psp18":
         path_num = 4
         model = td4_psp18.td4_psp18(nclass=19, path_num=path_num, model_path=args._td4_psp18_path, synthetic_seed=args.synthetic_seed)
@@ -168,26 +202,32 @@ def test(args):
         """--crop: the WHOLE frame as bytes [1, nbytes] and the view that takes the rectangle of it (the frame is uploaded as it is; the byte
         methods read the rectangle in the frame's first launch, the overlay in its last)."""
         from tdnet_amd.dataloader import PIX_NV12, PIX_RGB24, SourceView
+        if yuv is not None:
+            return image.reshape(1, -1), yuv_surface(yuv, src_size[0], src_size[1], nv12_std, crop)
         if nv12:
             v = SourceView(PIX_NV12, src_size[0], src_size[1], pitch=int(image.shape[2]), crop=crop, standard=nv12_std)
         else:
             v = SourceView(PIX_RGB24, int(image.shape[1]), int(image.shape[2]), crop=crop)
         return image.reshape(1, -1), v
 
-    nvp, byte = nv12 and crop is None, u8 or crop is not None          # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
+    nvp, byte = nv12 and crop is None, u8 or crop is not None or yuv is not None   # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
+    described = crop is not None or yuv is not None                    # the frame goes up WHOLE with a description: a source view, or (--yuv) a surface
+
+    def vk(v):
+        return {"surface": v} if yuv is not None else {"view": v}
 
     def colour_map(image, pos_id, ori_size, src_size=None, view=None):   # [1, oh, ow, 3] uint8 on the device
         out_size = (ori_size[1] // 4, ori_size[0] // 4)
         if nvp:
             return model.forward_rgb_nv12(image, pos_id, src_size, (H, W), out_size, standard=nv12_std)
         if byte:
-            return model.forward_rgb_u8(image, pos_id, (H, W), out_size, view=view)
+            return model.forward_rgb_u8(image, pos_id, (H, W), out_size, **vk(view))
         return model.forward_rgb(image, pos_id, out_size)
 
     def overlay_picture(image, pos_id, src_size=None, view=None):      # --overlay: [1, Hs, Ws, 3] uint8 on the device, at the source's (--crop: the rectangle's) size
         if nvp:
             return model.forward_overlay_nv12(image, pos_id, src_size, (H, W), alpha=overlay, standard=nv12_std)
-        return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay, view=view)
+        return model.forward_overlay_u8(image, pos_id, (H, W), alpha=overlay, **vk(view))
 
     raw_files = {}
 
@@ -199,9 +239,12 @@ def test(args):
             size = (ori_size[1] // 4, ori_size[0] // 4)
             draw = lambda **kw: model.labels_rgb(l8, size, **kw)
         else:
-            draw = lambda **kw: model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, view=view, **kw)
+            draw = lambda **kw: model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, **vk(view), **kw)
         picture = draw()
-        surf = draw(out_view=SourceView(PIX_NV12, int(picture.shape[1]), int(picture.shape[2]), standard=nv12_std))
+        if out_layout is not None:                                     # --out_yuv: a destination surface
+            surf = draw(out_surface=yuv_surface(out_layout, int(picture.shape[1]), int(picture.shape[2]), nv12_std))
+        else:
+            surf = draw(out_view=SourceView(PIX_NV12, int(picture.shape[1]), int(picture.shape[2]), standard=nv12_std))
         if folder not in raw_files:                                    # one raw file per clip: the first clip's is FILE itself
             root, ext = os.path.splitext(out_nv12)
             raw_files[folder] = out_nv12 if not raw_files else root + "." + folder + ext
@@ -221,16 +264,16 @@ def test(args):
             start_time = timeit.default_timer()
             gt_feed = iter(DevicePrefetcher(gts, device)) if gts is not None else None   # the ground truth travels with the frame
             for i, (image, img_name, folder, ori_size, *rest) in enumerate(DevicePrefetcher(vid_seq.data, device)):
-                src_size = rest[0] if nv12 else None                   # an NV12 item carries the picture's (Hs, Ws)
+                src_size = rest[0] if nv12 or yuv is not None else None   # an NV12 / --yuv item carries the picture's (Hs, Ws)
                 view = None
-                if crop is not None:
+                if described:
                     image, view = through_view(image, src_size)
                 if gt_feed is not None:
                     gt = next(gt_feed)[0]
                     if nvp:
                         labels = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
                     elif byte:
-                        labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, view=view)
+                        labels = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, **vk(view))
                     else:
                         labels = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
                 elif rgb:
@@ -240,7 +283,7 @@ def test(args):
                 elif nvp:
                     labels = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
-                    labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W), view=view) if byte else model.forward_labels(image, pos_id=i % path_num)
+                    labels = model.forward_labels_u8(image, pos_id=i % path_num, in_size=(H, W), **vk(view)) if byte else model.forward_labels(image, pos_id=i % path_num)
                 for tag, pred in down.submit(labels, (img_name, folder, ori_size)):
                     (save_rgb if rgb or overlay is not None else save)(pred, *tag)
             for tag, pred in down.drain():
@@ -255,10 +298,10 @@ def test(args):
             print_scores()
             return
         for i, (image, img_name, folder, ori_size, *rest) in enumerate(vid_seq.data):
-            src_size = rest[0] if nv12 else None
+            src_size = rest[0] if nv12 or yuv is not None else None
             image = image.to(device)
             view = None
-            if crop is not None:
+            if described:
                 image, view = through_view(image, src_size)
             gt = gts[i][0].to(device) if gts is not None else None
             torch.cuda.synchronize()
@@ -266,12 +309,12 @@ def test(args):
             if gt is not None and nvp:
                 output = model.forward_score_nv12(image, gt, i % path_num, src_size, (H, W), gt_map=gt_map, return_labels=True, standard=nv12_std)
             elif gt is not None and byte:
-                output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, view=view)
+                output = model.forward_score_u8(image, gt, i % path_num, (H, W), gt_map=gt_map, return_labels=True, **vk(view))
             elif gt is not None:
                 output = model.forward_score(image, gt, i % path_num, gt_map=gt_map, return_labels=True)
             elif out_nv12 is not None:
                 l8 = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std) if nvp else \
-                    model.forward_labels_u8(image, i % path_num, (H, W), view=view)
+                    model.forward_labels_u8(image, i % path_num, (H, W), **vk(view))
                 output = pictures_nv12(l8, image, ori_size, src_size, view, folder)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size, view)
@@ -279,8 +322,8 @@ def test(args):
                 if nvp:
                     l8, conf = model.forward_labels_conf_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
                 else:
-                    l8, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), view=view)
-                output = model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, view=view)
+                    l8, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), **vk(view))
+                output = model.labels_overlay(l8, image, alpha=overlay, src_size=src_size if nvp else None, standard=nv12_std, **vk(view))
             elif overlay is not None:
                 output = overlay_picture(image, i % path_num, src_size, view)
             elif with_conf and nvp:
@@ -288,9 +331,9 @@ def test(args):
             elif nvp:
                 output = model.forward_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std)
             elif with_conf:
-                output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), view=view) if byte else model.forward_labels_conf(image, i % path_num)
+                output, conf = model.forward_labels_conf_u8(image, i % path_num, (H, W), **vk(view)) if byte else model.forward_labels_conf(image, i % path_num)
             else:
-                output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W), view=view) if byte else model(image, pos_id=i % path_num)
+                output = model.forward_u8(image, pos_id=i % path_num, in_size=(H, W), **vk(view)) if byte else model(image, pos_id=i % path_num)
             torch.cuda.synchronize()
             elapsed_time = timeit.default_timer() - start_time
             if i > 5:
@@ -338,5 +381,7 @@ if __name__ == "__main__":
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
+    parser.add_argument("--yuv", nargs="?", type=str, default=None, help="frames go to the device as tight surfaces of this layout (nv12, nv21, i420, p010, yuy2, uyvy; --nv12_standard): conversion, resize and normalisation in the frame's first launch; combines with what --nv12 combines with, --crop included")
+    parser.add_argument("--out_yuv", nargs="?", type=str, default=None, help="LAYOUT:FILE -- --out_nv12's sibling for nv12, nv21, i420 and p010: every frame's picture appended to FILE as a tight surface of that layout, written by the device through a destination surface")
     parser.add_argument("--crop", nargs="?", type=str, default=None, help="with --u8 or --nv12: Y,X,H,W -- the frames are uploaded whole and the rectangle is taken on the device, in the frame's first launch (a source view)")
     test(parser.parse_args())

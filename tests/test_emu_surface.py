@@ -1,0 +1,166 @@
+"""Surfaces (include/tdnet.h "surfaces") on the CPU through the kernel emulator: the surface ingest kernel of every layout against the fp32 route fed
+the oracle's image, the overlay kernels over every layout against the host oracle, the picture kernels into the four destination layouts against
+dataloader.write_surface, whole frames given as surfaces against the same frames given as RGB bytes, and the error paths.  An out-of-extent access
+shows here as a host fault or a changed guard byte.  Every comparison is exact."""
+import numpy as np
+import pytest
+
+import emu_util
+import surface_cases as cases
+from tdnet_amd import _capi, arch, weights
+from tdnet_amd.dataloader import SURF_DST, SURF_I420, SURF_NV12, SURF_P010, SURF_YUY2, surface_to_rgb_u8
+from tdnet_amd.engine import Engine
+
+
+class HostMem:
+    """The scenarios' memory: numpy arrays stand in for HBM."""
+    stream = None
+
+    def up(self, a, off=0):
+        flat = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        holder = np.full(flat.size + 64, 0xA5, np.uint8)
+        holder[off:off + flat.size] = flat
+        return holder, holder.ctypes.data + off
+
+    def out(self, shape, dtype, fill):
+        return np.full(shape, fill, dtype)
+
+    def addr(self, buf):
+        return buf.ctypes.data
+
+    def get(self, buf):
+        return buf
+
+
+MEM = HostMem()
+
+IDS = [cases.NAMES[l] for l in cases.LAYOUTS]
+LAYOUT_VARIANTS = [(l, v) for l in cases.LAYOUTS for v in cases.variants(l)]
+LV_IDS = ["%s_%s" % (cases.NAMES[l], v) for l, v in LAYOUT_VARIANTS]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return emu_util.emu_lib()
+
+
+@pytest.mark.parametrize("layout,variant", LAYOUT_VARIANTS, ids=LV_IDS)
+@pytest.mark.parametrize("name,rect,net", cases.RECTS, ids=[c[0] for c in cases.RECTS])
+def test_surfaces_match_the_rgb_route_bit_for_bit(lib, name, rect, net, layout, variant):
+    cases.run_stem_case(lib, MEM, cases.surface(layout, rect, variant), net, fills=(0x00, 0xFF) if variant != "tight" or name == "phase_3_7" else (0x00,))
+
+
+@pytest.mark.parametrize("layout", cases.LAYOUTS, ids=IDS)
+@pytest.mark.parametrize("standard", [0, 1, 2, 3])
+def test_all_four_standards_at_an_odd_origin(lib, standard, layout):
+    surf = cases.surface(layout, (3, 7, 41, 83), "padded", standard=standard)
+    if standard:
+        assert not np.array_equal(cases.expected_image(surf, 33, 65), cases.expected_image(cases.surface(layout, (3, 7, 41, 83), "padded"), 33, 65))
+    cases.run_stem_case(lib, MEM, surf, (33, 65), offsets=(1,), fills=(0x33,))
+
+
+def test_whole_nv12_surface_with_one_pitch_is_the_nv12_entry_bit_for_bit(lib):
+    """What tdnet_set_input_nv12 describes, described as a surface: the same stem image through the other kernel."""
+    H, W = 33, 65
+    surf = cases.surface(SURF_NV12, None, "tight")
+    s = cases.surface_bytes(surf)
+    holder, addr = MEM.up(s, 1)
+    for rows in (1, 0):
+        n = cases.vc.stem_buffer_size(lib, H, W, rows)
+        out = np.full(n, np.float32(1234.5), np.float32)
+        assert lib.check(lib.tdnet_op_stem_image_nv12(addr, surf.height, surf.width, surf.row_pitch, surf.u_off, 0, H, W, None, None, rows, out.ctypes.data, n, None)) == n
+        assert np.array_equal(cases.stem_image_surface(lib, MEM, addr, surf, H, W, rows), out.view(np.uint32))
+
+
+def test_other_mean_and_std(lib):
+    surf = cases.surface(SURF_P010, (3, 7, 41, 83), "padded")
+    holder, addr = MEM.up(cases.surface_bytes(surf), 3)
+    want_img = cases.expected_image(surf, 33, 65, 0, cases.u8cases.ALT_MEAN, cases.u8cases.ALT_STD)
+    assert not np.array_equal(want_img, cases.expected_image(surf, 33, 65))
+    for rows in (1, 0):
+        assert np.array_equal(cases.stem_image_surface(lib, MEM, addr, surf, 33, 65, rows, cases.u8cases.ALT_MEAN, cases.u8cases.ALT_STD),
+                              cases.vc.stem_image_ref(lib, MEM, 33, 65, rows, want_img))
+
+
+@pytest.mark.parametrize("layout", cases.LAYOUTS, ids=IDS)
+@pytest.mark.parametrize("rect", cases.OVERLAY_RECTS, ids=["2_5", "3_4"])
+def test_overlay_over_surfaces(lib, rect, layout):
+    cases.run_overlay_case(lib, MEM, cases.surface(layout, rect, "v_first" if layout == SURF_I420 else "padded", standard=1))
+
+
+@pytest.mark.parametrize("layout,variant", [(l, v) for l in SURF_DST for v in cases.variants(l)], ids=["%s_%s" % (cases.NAMES[l], v) for l in SURF_DST for v in cases.variants(l)])
+@pytest.mark.parametrize("case", cases.DST_CASES)
+def test_pictures_into_surfaces(lib, case, layout, variant):
+    cases.run_dest_case(lib, MEM, layout, variant, case, standard=1 if variant == "padded" else 2,
+                        offsets=(0, 1, 2, 3) if variant == "padded" else (1,))
+
+
+@pytest.mark.parametrize("standard", [0, 3])
+def test_pictures_into_surfaces_other_standards(lib, standard):
+    for layout in (SURF_I420, SURF_P010):
+        cases.run_dest_case(lib, MEM, layout, "padded", "corner_odd", standard=standard, sources=("nv12_view", "uyvy"), offsets=(3,))
+
+
+def test_destination_views_behind_a_surface_source(lib):
+    cases.run_view_dest_behind_surface_source(lib, MEM)
+
+
+def _engine(lib, H=33, W=65):
+    spec = arch.model_spec("td2", 19, "resnet18")
+    e = Engine(2, 18, 19, H, W, 0, lib=lib)
+    e.load_state_dict(weights.synth_state_dict(spec, arch.feat_size(H), arch.feat_size(W), 0))
+    return e
+
+
+def test_frames_given_as_surfaces_equal_frames_given_as_rgb_bytes(lib):
+    a = _engine(lib, *cases.NET)
+    cases.run_surface_scenario(a, MEM, layouts=(SURF_P010,))           # the device runs every layout (tests/test_gpu_surface.py)
+    cases.run_output_scenario(a, MEM, dst_layouts=(SURF_I420,))
+    a.close()
+
+
+def test_errors_leave_the_configuration_and_the_fifo_alone(lib):
+    H, W = cases.NET
+    e = _engine(lib, H, W)
+    surf = cases.surface(SURF_I420, cases.SCENARIO_RECT, "padded")
+    s = cases.surface_bytes(surf)
+    rgb = surface_to_rgb_u8(s, surf)
+    ref = np.zeros((1, 19, H, W), np.float32)
+    bad = cases.bad_surfaces()
+    with pytest.raises(_capi.TdnetError, match="reserved"):            # a rejected configuration configures nothing
+        e.lib.check(e.lib.tdnet_set_input_surface(e.h, next(t for m, t, _, _ in bad if m == "reserved"), None, None))
+    with pytest.raises(_capi.TdnetError, match="tdnet_set_input_u8"):
+        e.forward_u8(s, 0, ref)
+    assert e.fifo_len() == 0
+    e.set_input_surface(surf)                                          # the previous configuration a surface ...
+    e.forward_u8(s, 0, ref)
+    cases.run_error_cases(e, MEM, "surface", s.ctypes.data, ref.view(np.uint32).copy(), H, W)
+    e.set_input_u8(41, 83)                                             # ... and plain packed RGB
+    e.reset()
+    e.forward_u8(rgb, 0, ref)
+    cases.run_error_cases(e, MEM, "u8", rgb.ctypes.data, ref.view(np.uint32).copy(), H, W)
+    # the destination: every bad surface leaves the one in force, the FIFO and a pending frame alone
+    e.set_input_surface(surf)
+    e.set_output_overlay(cases.vc.overlay_palette())
+    dsurf = cases.surface(SURF_P010, (2, 6, 41, 83), "padded", frame=cases.DST_FRAME, standard=1)
+    e.set_output_surface(dsurf)
+    holder, addr = MEM.up(s, 1)
+    cases.run_output_error_cases(e, MEM, addr, dsurf, H, W)
+    fresh = Engine(2, 18, 19, H, W, 0, lib=lib)
+    for call, name in ((lambda: fresh.set_input_surface(surf), "tdnet_set_input_surface"), (lambda: fresh.set_output_surface(dsurf), "tdnet_set_output_surface")):
+        with pytest.raises(_capi.TdnetError, match="not finalized") as err:
+            call()
+        assert name in str(err.value)
+    fresh.close()
+    e.close()
+
+
+def test_the_eight_bit_layouts_still_fit_where_p010s_downscale_limit_is_passed(lib):
+    """2 x 12000 -> 33 x 65: the 8-bit layouts stage two bytes per source column and row (luma + chroma) and fit one strip's LDS; P010 stages four."""
+    e = _engine(lib)
+    for layout in (SURF_NV12, SURF_I420, SURF_YUY2):
+        e.set_input_surface(cases.surface(layout, None, "tight", frame=(2, 12000)))
+    with pytest.raises(_capi.TdnetError, match="downscale") as err:
+        e.set_input_surface(cases.surface(SURF_P010, None, "tight", frame=(2, 12000)))
+    assert "tdnet_set_input_surface" in str(err.value)
+    e.close()
