@@ -223,7 +223,7 @@ struct PathLayers {
 };
 struct CacheSlot { float* q = nullptr; float* k = nullptr; float* v = nullptr; };
 // The uint8 image input of a handle (tdnet_set_input_u8 / tdnet_set_input_nv12 / tdnet_set_input_view: ONE configuration at a time): source size, normalisation and
-// the device tables k_ingest_u8 / k_ingest_nv12 read.  Per handle: tdnet_create_shared handles configure their own.
+// the device tables k_ingest (td_ingest.h) reads.  Per handle: tdnet_create_shared handles configure their own.
 struct Nv12Layout { int pitch; size_t uv_offset; int standard; };      // tdnet_set_input_nv12's surface arguments
 // What the byte entries' image pointer is the base of (include/tdnet.h "source views"): a frame fh x fw of `format` with rows `pitch` bytes apart
 // (0: tight), of which the image is the rectangle Hs x Ws at (oy, ox).  tdnet_set_input_u8 and tdnet_set_input_nv12 are the two obvious views.
@@ -245,7 +245,7 @@ static int src_view_bpp(int format) { return format == TDNET_PIX_NV12 ? 1 : form
 struct U8Input {
     bool set = false;
     bool nv12 = false;                                                 // false: packed pixels; true: an NV12 surface
-    bool surf = false;                                                 // a YUV surface (tdnet_set_input_surface): k_ingest_surface reads it; nv12 is false then
+    bool surf = false;                                                 // a YUV surface (tdnet_set_input_surface): the layout reaches the kernels as arguments; nv12 is false then
     int layout = 0, cpitch = 0;                                        // surf: TDNET_SURF_*; bytes per chroma row
     size_t u_off = 0, v_off = 0;                                       // surf: the resolved plane offsets
     int format = 0, bpp = 3;                                           // TDNET_PIX_*; bytes per packed pixel
@@ -263,7 +263,7 @@ struct U8Input {
     int* yt = nullptr;                                                 // [H][4]
     size_t bytes = 0;                                                  // HBM held by the three tables
 };
-// The colour-map output of a handle (tdnet_set_output_rgb): picture size, palette and the device tables k_upsample_argmax_rgb / k_labels_rgb
+// The colour-map output of a handle (tdnet_set_output_rgb): picture size, palette and the device tables the picture kernels (td_out.h k_picture_rows / k_picture_420)
 // read.  Per handle, like U8Input.
 struct RgbOutput {
     bool set = false;
@@ -274,7 +274,7 @@ struct RgbOutput {
     unsigned* lut = nullptr;                                           // [256]: r | g << 8 | b << 16
     size_t bytes = 0;
 };
-// The overlay output of a handle (tdnet_set_output_overlay): palette with opacity, the colour table k_upsample_argmax_overlay / k_labels_overlay read,
+// The overlay output of a handle (tdnet_set_output_overlay): palette with opacity, the colour table the picture kernels read,
 // and the index tables of the pair (network size, source size) -- the source size is the byte input's, so the tables follow U8Input (overlay_tables).
 // Per handle, like U8Input.
 struct OverlayOutput {
@@ -498,8 +498,8 @@ static void nv12_forward_coeffs(int standard, int* yoff, int ky[3], int ku[3], i
         kv[i] = (int)nearbyint(dec[standard][6 + i] * 1048576.0);
     }
 }
-// ---- YUV surfaces (include/tdnet.h "surfaces"): the host side of td_ingest.h k_ingest_surface / td_out.h td_overlay_src_surf ----
-// What a layout is to the kernels (td_ingest.h SurfLayout has the table): bytes between luma samples, the luma sample's offset, the vertical chroma
+// ---- YUV surfaces (include/tdnet.h "surfaces"): the host side of td_ingest.h IngestYuv / td_out.h td_src_px4 ----
+// What a layout is to the kernels (td_ingest.h SrcLayout has the table): bytes between luma samples, the luma sample's offset, the vertical chroma
 // shift, bytes between chroma pairs, the offsets of U and V within a pair, the chroma spans staged per source row, 16-bit samples.
 struct SurfForm { int lstride = 1, loff = 0, cshift = 1, cstep = 2, uo = 0, vo = 1, planes = 1; bool wide = false; };
 static SurfForm surf_form(int layout) {
@@ -638,7 +638,7 @@ static int u8_build(U8Input& u, const SrcView& sv, int Hs, int Ws, int H, int W,
             const int cl = v.resize ? x0[xs] : xs, ch = v.resize ? x1[xe - 1] : xe - 1;
             const long cols = (long)ch - cl + 1;
             const long pairs = (long)((sv.ox + ch) >> 1) - ((sv.ox + cl) >> 1) + 1;
-            if (sv.surf) {                                             // k_ingest_surface: 4:2:2 stages whole pixel pairs, chroma included
+            if (sv.surf) {                                             // IngestYuv: 4:2:2 stages whole pixel pairs, chroma included
                 span = std::max(span, ((sf.planes ? cols * sf.lstride : 4 * pairs) + 15 + 15) / 16 * 16);
                 if (sf.planes) span_c = std::max(span_c, (pairs * sf.cstep + 15 + 15) / 16 * 16);
                 continue;
@@ -759,7 +759,7 @@ static int dst_surface_build(DstOutput& d, const tdnet_surface* t, const char* w
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// colour-map output: the host side of td_out.h's k_upsample_argmax_rgb / k_labels_rgb
+// colour-map output: the host side of td_out.h's colour map (TD_SRC_NONE)
 // ---------------------------------------------------------------------------------------------------------------
 // tdnet_amd/dataloader.py nearest_index with the same operations in the same types: the quotient first, in double, then the product, then
 // truncation, then the clamp.  This is the project's rule (tdnet_amd/test.py's resize of the label map since its first version), not cv2's text.
@@ -808,7 +808,7 @@ static int rgb_build(RgbOutput& r, int H, int W, int oh, int ow, const unsigned 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// overlay output: the host side of td_out.h's k_upsample_argmax_overlay / k_labels_overlay
+// overlay output: the host side of td_out.h's overlay (td_src_px4, td_overlay_blend)
 // ---------------------------------------------------------------------------------------------------------------
 static void overlay_free_tables(OverlayOutput& o) {
     if (o.ys) hipFree(o.ys);

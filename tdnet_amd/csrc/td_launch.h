@@ -343,42 +343,33 @@ enum { TD_IMG_F32 = 0, TD_IMG_U8 = 1 };                               // TD_IMG_
 struct FrameInput { const void* p; int kind; const U8Input* u8; };
 static inline FrameInput frame_input_f32(const float* img) { return FrameInput{img, TD_IMG_F32, nullptr}; }
 // rows: the packed-row image of the 7x7 stem (ConvLayer::stem_rows(); img4 then holds [H + 7][W + 8][3] with a zero border) instead of NHWC4
-// the kernels' description of the surface a byte input is (td_ingest.h SurfLayout; td_handle.h surf_form, surf_coeffs)
-static SurfLayout surf_layout(const U8Input& u) {
-    const SurfForm f = surf_form(u.layout);
-    return SurfLayout{u.pitch, u.cpitch, (unsigned)u.u_off, (unsigned)u.v_off, f.lstride, f.loff, f.cshift, f.cstep, f.uo, f.vo, f.planes,
-                      u.coef[0], f.wide ? 512 : 128, u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
+// the kernels' description of the frame a byte input is (td_ingest.h SrcLayout; td_handle.h surf_form, surf_coeffs): packed pixels use pitch and origin only; an
+// NV12 surface or view is the NV12 row of the layout table (SurfForm's default) with both planes on one pitch
+static SrcLayout src_layout(const U8Input& u) {
+    const SurfForm f = u.surf ? surf_form(u.layout) : SurfForm();
+    return SrcLayout{u.pitch, u.surf ? u.cpitch : u.pitch, (unsigned)(u.surf ? u.u_off : u.uv_offset), (unsigned)(u.surf ? u.v_off : u.uv_offset),
+                     f.lstride, f.loff, f.cshift, f.cstep, f.uo, f.vo, u.surf ? f.planes : u.nv12 ? 1 : 0,
+                     u.coef[0], f.wide ? 512 : 128, u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
 }
 static void run_stem_pre(tdnet* n, const FrameInput& in, int H, int W, float* img4, hipStream_t s, bool rows = false) {
     prof_begin(n, 2, false, 0, s);
     switch (in.kind) {
-    case TD_IMG_U8: {                                                  // resize + normalise + layout in the same one launch (td_ingest.h)
+    case TD_IMG_U8: {                                                  // resize + normalise (+ colour conversion) + layout in the same one launch (td_ingest.h)
         const U8Input& u = *in.u8;
-        if (u.surf) {                                                  // a YUV surface: the layout is arguments, the sample width the instantiation
-            const SurfLayout l = surf_layout(u);
-            const IngestSurfArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
-                                      u.span, u.span_c, (unsigned)u.extent, l};
-            const dim3 grid((W + 4 * u.threads - 1) / (4 * u.threads), H), block(u.threads);
-            const int lds = TD_INGEST_LUT_BYTES + 2 * u.span + 2 * l.planes * u.span_c;
-            if (l.mid == 512) TD_LAUNCH((k_ingest_surface<true>), grid, block, lds, s, a);
-            else TD_LAUNCH((k_ingest_surface<false>), grid, block, lds, s, a);
-            break;
-        }
-        if (u.nv12) {                                                  // colour conversion too, in the same one launch
-            const IngestNv12Args a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
-                                      u.span, u.span_c, u.pitch, (unsigned)u.uv_offset, (unsigned)u.extent,
-                                      u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
-            TD_LAUNCH(k_ingest_nv12, dim3((W + 4 * u.threads - 1) / (4 * u.threads), H), dim3(u.threads), TD_INGEST_LUT_BYTES + 2 * u.span + 2 * u.span_c, s, a);
-            break;
-        }
-        const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0, u.span,
-                              u.pitch, u.oy, u.ox, (unsigned)u.extent};
+        const SrcLayout l = src_layout(u);
+        const IngestArgs a = {(const unsigned char*)in.p, img4, u.lut, u.xt, u.yt, u.Hs, u.Ws, H, W, u.Wt, rows ? stem_rows_wp(W) : 0, u.resize ? 1 : 0,
+                              u.span, u.span_c, (unsigned)u.extent};
         const dim3 grid((W + 4 * u.threads - 1) / (4 * u.threads), H), block(u.threads);
-        const int lds = TD_INGEST_LUT_BYTES + 2 * u.span;
-        if (u.bpp == 3 && !u.swap) TD_LAUNCH((k_ingest_u8<3, false>), grid, block, lds, s, a);   // the format is the instantiation: RGB24 pays nothing for the others
-        else if (u.bpp == 3) TD_LAUNCH((k_ingest_u8<3, true>), grid, block, lds, s, a);
-        else if (!u.swap) TD_LAUNCH((k_ingest_u8<4, false>), grid, block, lds, s, a);
-        else TD_LAUNCH((k_ingest_u8<4, true>), grid, block, lds, s, a);
+        const int lds = TD_INGEST_LUT_BYTES + 2 * u.span + 2 * l.planes * u.span_c;
+#define TD_INGEST(...) TD_LAUNCH((k_ingest<__VA_ARGS__>), grid, block, lds, s, a, l)
+        if (u.surf && l.mid == 512) TD_INGEST(IngestYuv<true, YuvFormArgs>);   // a YUV surface: the layout is arguments, the sample width the instantiation
+        else if (u.surf) TD_INGEST(IngestYuv<false, YuvFormArgs>);
+        else if (u.nv12) TD_INGEST(IngestYuv<false, YuvFormNv12>);      // the NV12 row as constants
+        else if (u.bpp == 3 && !u.swap) TD_INGEST(IngestPacked<3, false>);   // the format is the instantiation: RGB24 pays nothing for the others
+        else if (u.bpp == 3) TD_INGEST(IngestPacked<3, true>);
+        else if (!u.swap) TD_INGEST(IngestPacked<4, false>);
+        else TD_INGEST(IngestPacked<4, true>);
+#undef TD_INGEST
         break;
     }
     default: {
@@ -460,166 +451,109 @@ static int launch_argmax_u8(const float* logits, int C, long HW, unsigned char* 
     TD_LAUNCH(k_argmax_u8, out_grid_run(HW), dim3(256), 0, s, logits, labels, C, HW);
     return 0;
 }
-// the colour map [oh][ow][3] of a frame (tdnet_set_output_rgb; `r` = that configuration): from the low-resolution logits, evaluated at the sampled
-// pixels only, or from a uint8 label map [H][W]
-static int launch_upsample_argmax_rgb(const float* in, int C, int h, int w, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
-    TD_TRY(out_check("colour map", "out_height", r.oh, C));
-    TD_LAUNCH(k_upsample_argmax_rgb, out_grid(r.ow, r.oh), dim3(256), 0, s, in, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb,
-              C, h, w, r.H, r.W, r.oh, r.ow);
-    return 0;
+// ---- pictures (td_out.h "pictures out"): the colour map and the overlay, into a contiguous block or a destination view ----
+// ONE dispatch: every (source form, destination form, sample width) cell that exists, label-map and fused form of each.  R: k_picture_rows, B: k_picture_420.
+// A frame with a destination in force reads a packed or NV12 source through the view reader (DESIGN.md 5.12 bounds the count that way): the tight forms
+// exist for the contiguous block only.  YuvFormNv12 takes no surface source: behind one, the NV12 view goes through the argument form.
+#define TD_PICTURE_CELLS(R, B) \
+    R(NONE, RGB) R(P24T, RGB) R(P24, RGB) R(P32, RGB) R(NV12T, RGB) R(NV12, RGB) R(SURF8, RGB) R(SURF16, RGB) \
+    R(NONE, P24) R(P24, P24) R(P32, P24) R(NV12, P24) R(SURF8, P24) R(SURF16, P24) \
+    R(NONE, P32) R(P24, P32) R(P32, P32) R(NV12, P32) R(SURF8, P32) R(SURF16, P32) \
+    B(NONE, NV12, false, YuvFormNv12) B(P24, NV12, false, YuvFormNv12) B(P32, NV12, false, YuvFormNv12) B(NV12, NV12, false, YuvFormNv12) \
+    B(NONE, YUV420, false, YuvFormArgs) B(P24, YUV420, false, YuvFormArgs) B(P32, YUV420, false, YuvFormArgs) B(NV12, YUV420, false, YuvFormArgs) \
+    B(SURF8, YUV420, false, YuvFormArgs) B(SURF16, YUV420, false, YuvFormArgs) \
+    B(NONE, YUV420, true, YuvFormArgs) B(P24, YUV420, true, YuvFormArgs) B(P32, YUV420, true, YuvFormArgs) B(NV12, YUV420, true, YuvFormArgs) \
+    B(SURF8, YUV420, true, YuvFormArgs) B(SURF16, YUV420, true, YuvFormArgs)
+#define TD_PICTURE_KEY(src, dst, wide) (((src) * 8 + (dst)) * 2 + ((wide) ? 1 : 0))
+// a.labels != NULL: the label-map form.  src, l: the overlay's source (TD_SRC_NONE: unused).  wide: a 4:2:0 destination of 16-bit samples.
+static int launch_picture(const PicArgs& a, int src_form, const unsigned char* src, const SrcLayout& l, int dst_form, bool wide, const PicDst& d, hipStream_t s) {
+    const bool labels = a.labels != nullptr;
+    const dim3 rows = out_grid(a.ow, a.oh), blocks(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2);
+    switch (TD_PICTURE_KEY(src_form, dst_form, wide)) {
+#define TD_R(SRC, DST) case TD_PICTURE_KEY(TD_SRC_##SRC, TD_DST_##DST, false): \
+        if (labels) TD_LAUNCH((k_picture_rows<true, TD_SRC_##SRC, TD_DST_##DST>), rows, dim3(256), 0, s, a, src, l, d); \
+        else TD_LAUNCH((k_picture_rows<false, TD_SRC_##SRC, TD_DST_##DST>), rows, dim3(256), 0, s, a, src, l, d); \
+        return 0;
+#define TD_B(SRC, DST, WIDE, F) case TD_PICTURE_KEY(TD_SRC_##SRC, TD_DST_##DST, WIDE): \
+        if (labels) TD_LAUNCH((k_picture_420<true, TD_SRC_##SRC, WIDE, F>), blocks, dim3(256), 0, s, a, src, l, d); \
+        else TD_LAUNCH((k_picture_420<false, TD_SRC_##SRC, WIDE, F>), blocks, dim3(256), 0, s, a, src, l, d); \
+        return 0;
+    TD_PICTURE_CELLS(TD_R, TD_B)
+#undef TD_R
+#undef TD_B
+    }
+    return td_fail("internal: no picture kernel for source form %d into destination form %d", src_form, dst_form);
 }
-static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
-    TD_TRY(out_check("colour map", "out_height", r.oh, 1));
-    TD_LAUNCH(k_labels_rgb, out_grid(r.ow, r.oh), dim3(256), 0, s, labels, (const int*)r.ys, (const int*)r.xs, (const unsigned*)r.lut, rgb, r.W, r.oh, r.ow);
-    return 0;
-}
-// the overlay [Hs][Ws][3] of a frame (tdnet_set_output_overlay; `o` = that configuration, `u` = the byte input `src` is read by): the class colours blended
-// over the source frame, from the low-resolution logits or from a uint8 label map [H][W]
-static OverlaySrc overlay_src(const U8Input& u, const unsigned char* src) {
-    return OverlaySrc{src, u.pitch, (unsigned)u.uv_offset, u.coef[0], u.coef[1], u.coef[2], u.coef[3], u.coef[4], u.coef[5], u.oy, u.ox};
-}
-// the source form and whether it is a VIEW (an origin, or packed rows with a pitch): 2 * form + view
-static int overlay_src_form(const U8Input& u) {
-    const bool view = u.oy || u.ox || u.bpp == 4 || (!u.nv12 && u.pitch != 3 * u.Ws);
-    return 2 * (u.nv12 ? TD_SRC_NV12 : u.bpp == 4 ? TD_SRC_P32 : TD_SRC_P24) + (view ? 1 : 0);
+// the source form of a byte input (`u`; td_out.h TD_SRC_*).  tight: the destination is the contiguous block, so the whole tight frame may take the form
+// whose origin and pitch are constants; a VIEW is an origin, 4-byte pixels, or packed rows with a pitch
+static int picture_src_form(const U8Input& u, bool tight) {
+    if (u.surf) return surf_form(u.layout).wide ? TD_SRC_SURF16 : TD_SRC_SURF8;
+    const bool view = !tight || u.oy || u.ox || u.bpp == 4 || (!u.nv12 && u.pitch != 3 * u.Ws);
+    if (u.nv12) return view ? TD_SRC_NV12 : TD_SRC_NV12T;
+    return u.bpp == 4 ? TD_SRC_P32 : view ? TD_SRC_P24 : TD_SRC_P24T;
 }
 static int overlay_check_tables(const OverlayOutput& o, const U8Input& u) {
     if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("overlay: the index tables of this source size are missing (their allocation failed)");
     if (o.swap != u.swap) return td_fail("overlay: the colour table is not in the source's colour order (its upload failed)");
     return 0;
 }
+// the colour map [oh][ow][3] of a frame (tdnet_set_output_rgb; `r` = that configuration) or its overlay [Hs][Ws][3] (tdnet_set_output_overlay; `o` = that
+// configuration): from the low-resolution logits, evaluated at the sampled pixels only, or (labels != NULL) from a uint8 label map [H][W]
+static PicArgs picture_args(const float* in, const unsigned char* labels, int C, int h, int w, const RgbOutput& r) {
+    return PicArgs{in, labels, r.ys, r.xs, r.lut, C, h, w, r.H, r.W, r.oh, r.ow};
+}
+static PicArgs picture_args(const float* in, const unsigned char* labels, int C, int h, int w, const OverlayOutput& o) {
+    return PicArgs{in, labels, o.ys, o.xs, o.lut, C, h, w, o.H, o.W, o.Hs, o.Ws};
+}
+static PicDst picture_block(unsigned char* out) { PicDst d = PicDst(); d.base = out; return d; }
+static int launch_upsample_argmax_rgb(const float* in, int C, int h, int w, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
+    TD_TRY(out_check("colour map", "out_height", r.oh, C));
+    return launch_picture(picture_args(in, nullptr, C, h, w, r), TD_SRC_NONE, nullptr, SrcLayout(), TD_DST_RGB, false, picture_block(rgb), s);
+}
+static int launch_labels_rgb(const unsigned char* labels, const RgbOutput& r, unsigned char* rgb, hipStream_t s) {
+    TD_TRY(out_check("colour map", "out_height", r.oh, 1));
+    return launch_picture(picture_args(nullptr, labels, 0, 0, 0, r), TD_SRC_NONE, nullptr, SrcLayout(), TD_DST_RGB, false, picture_block(rgb), s);
+}
+// `u` = the byte input `src` is read by
 static int launch_upsample_argmax_overlay(const float* in, int C, int h, int w, const OverlayOutput& o, const U8Input& u, const unsigned char* src,
                                           unsigned char* out, hipStream_t s) {
     TD_TRY(out_check("overlay", "src_height", o.Hs, C));
     TD_TRY(overlay_check_tables(o, u));
-    if (u.surf) {                                                      // a YUV surface: td_out.h td_overlay_src_surf
-        const SurfLayout l = surf_layout(u);
-        if (l.mid == 512) TD_LAUNCH((k_upsample_argmax_overlay_surf<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, C, h, w, o.H, o.W, o.Hs, o.Ws);
-        else TD_LAUNCH((k_upsample_argmax_overlay_surf<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, C, h, w, o.H, o.W, o.Hs, o.Ws);
-        return 0;
-    }
-    const OverlaySrc sd = overlay_src(u, src);
-    switch (overlay_src_form(u)) {
-#define TD_OVL(SRC, VIEW) TD_LAUNCH((k_upsample_argmax_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, in, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, \
-                              C, h, w, o.H, o.W, o.Hs, o.Ws)
-    case 2 * TD_SRC_P24: TD_OVL(TD_SRC_P24, false); break;
-    case 2 * TD_SRC_P24 + 1: TD_OVL(TD_SRC_P24, true); break;
-    case 2 * TD_SRC_NV12: TD_OVL(TD_SRC_NV12, false); break;
-    case 2 * TD_SRC_NV12 + 1: TD_OVL(TD_SRC_NV12, true); break;
-    default: TD_OVL(TD_SRC_P32, true);
-#undef TD_OVL
-    }
-    return 0;
+    return launch_picture(picture_args(in, nullptr, C, h, w, o), picture_src_form(u, true), src, src_layout(u), TD_DST_RGB, false, picture_block(out), s);
 }
 static int launch_labels_overlay(const unsigned char* labels, const OverlayOutput& o, const U8Input& u, const unsigned char* src, unsigned char* out, hipStream_t s) {
     TD_TRY(out_check("overlay", "src_height", o.Hs, 1));
     TD_TRY(overlay_check_tables(o, u));
-    if (u.surf) {
-        const SurfLayout l = surf_layout(u);
-        if (l.mid == 512) TD_LAUNCH((k_labels_overlay_surf<true>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, o.W, o.Hs, o.Ws);
-        else TD_LAUNCH((k_labels_overlay_surf<false>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, src, l, out, o.W, o.Hs, o.Ws);
-        return 0;
-    }
-    const OverlaySrc sd = overlay_src(u, src);
-    switch (overlay_src_form(u)) {
-#define TD_OVL(SRC, VIEW) TD_LAUNCH((k_labels_overlay<SRC, VIEW>), out_grid(o.Ws, o.Hs), dim3(256), 0, s, labels, (const int*)o.ys, (const int*)o.xs, (const unsigned*)o.lut, sd, out, o.W, o.Hs, o.Ws)
-    case 2 * TD_SRC_P24: TD_OVL(TD_SRC_P24, false); break;
-    case 2 * TD_SRC_P24 + 1: TD_OVL(TD_SRC_P24, true); break;
-    case 2 * TD_SRC_NV12: TD_OVL(TD_SRC_NV12, false); break;
-    case 2 * TD_SRC_NV12 + 1: TD_OVL(TD_SRC_NV12, true); break;
-    default: TD_OVL(TD_SRC_P32, true);
-#undef TD_OVL
-    }
-    return 0;
+    return launch_picture(picture_args(nullptr, labels, 0, 0, 0, o), picture_src_form(u, true), src, src_layout(u), TD_DST_RGB, false, picture_block(out), s);
 }
-// The picture into a destination view (tdnet_set_output_view; `d` = that configuration, `base` = the destination frame's base): the colour map (r != NULL)
-// or the overlay (o, u, src), from the low-resolution logits (labels == NULL) or from a uint8 label map.  One launch, like the contiguous forms.  The
-// picture's size must be the rectangle's: the frame entries check that before anything is enqueued (td_model.hip picture_dst_check), and here again.
-template <bool LABELS, bool OVERLAY, int SRC>
-static void launch_picture_form(const PicArgs& a, const OverlaySrc& sd, const DstView& dv, int form, hipStream_t s) {
-    if (form == TD_DST_NV12) TD_LAUNCH((k_picture_nv12<LABELS, OVERLAY, SRC>), dim3(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2), dim3(256), 0, s, a, sd, dv);
-    else if (form == TD_DST_P32) TD_LAUNCH((k_picture_packed<TD_DST_P32, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
-    else TD_LAUNCH((k_picture_packed<TD_DST_P24, LABELS, OVERLAY, SRC>), out_grid(a.ow, a.oh), dim3(256), 0, s, a, sd, dv);
-}
-// The surface forms (td_out.h k_picture_surface): a 4:2:0 surface destination, or an NV12 destination view behind a surface source
-template <bool LABELS, bool OVERLAY, int SRC>
-static void launch_picture_surf_form(const PicArgs& a, const OverlaySrc& sd, const SurfLayout& sl, const DstSurf& ds, bool wide, hipStream_t s) {
-    const dim3 grid(((a.ow + 3) / 4 + 255) / 256, (a.oh + 1) / 2);
-    if (wide) TD_LAUNCH((k_picture_surface<LABELS, OVERLAY, SRC, true>), grid, dim3(256), 0, s, a, sd, sl, ds);
-    else TD_LAUNCH((k_picture_surface<LABELS, OVERLAY, SRC, false>), grid, dim3(256), 0, s, a, sd, sl, ds);
-}
-template <bool LABELS>
-static void launch_picture_surf(const PicArgs& a, const OverlaySrc& sd, const SurfLayout& sl, const DstSurf& ds, bool wide, int src_form, hipStream_t s) {
-    if (src_form < 0) launch_picture_surf_form<LABELS, false, TD_SRC_P24>(a, sd, sl, ds, wide, s);   // the colour map: no source
-    else if (src_form == TD_SRC_NV12) launch_picture_surf_form<LABELS, true, TD_SRC_NV12>(a, sd, sl, ds, wide, s);
-    else if (src_form == TD_SRC_P32) launch_picture_surf_form<LABELS, true, TD_SRC_P32>(a, sd, sl, ds, wide, s);
-    else if (src_form == TD_SRC_SURF8) launch_picture_surf_form<LABELS, true, TD_SRC_SURF8>(a, sd, sl, ds, wide, s);
-    else if (src_form == TD_SRC_SURF16) launch_picture_surf_form<LABELS, true, TD_SRC_SURF16>(a, sd, sl, ds, wide, s);
-    else launch_picture_surf_form<LABELS, true, TD_SRC_P24>(a, sd, sl, ds, wide, s);
-}
-// a packed destination view behind a surface source (td_out.h k_picture_packed_surf)
-template <bool LABELS>
-static void launch_picture_packed_surf(const PicArgs& a, const unsigned char* src, const SurfLayout& sl, const DstView& dv, int form, bool wide, hipStream_t s) {
-    const dim3 grid = out_grid(a.ow, a.oh);
-    if (form == TD_DST_P32 && wide) TD_LAUNCH((k_picture_packed_surf<TD_DST_P32, LABELS, true>), grid, dim3(256), 0, s, a, src, sl, dv);
-    else if (form == TD_DST_P32) TD_LAUNCH((k_picture_packed_surf<TD_DST_P32, LABELS, false>), grid, dim3(256), 0, s, a, src, sl, dv);
-    else if (wide) TD_LAUNCH((k_picture_packed_surf<TD_DST_P24, LABELS, true>), grid, dim3(256), 0, s, a, src, sl, dv);
-    else TD_LAUNCH((k_picture_packed_surf<TD_DST_P24, LABELS, false>), grid, dim3(256), 0, s, a, src, sl, dv);
-}
-template <bool LABELS>
-static void launch_picture_src(const PicArgs& a, const OverlaySrc& sd, const DstView& dv, int form, int src_form, hipStream_t s) {
-    if (src_form < 0) launch_picture_form<LABELS, false, TD_SRC_P24>(a, sd, dv, form, s);          // the colour map: no source
-    else if (src_form == TD_SRC_NV12) launch_picture_form<LABELS, true, TD_SRC_NV12>(a, sd, dv, form, s);
-    else if (src_form == TD_SRC_P32) launch_picture_form<LABELS, true, TD_SRC_P32>(a, sd, dv, form, s);
-    else launch_picture_form<LABELS, true, TD_SRC_P24>(a, sd, dv, form, s);
-}
+// The picture into a destination view (tdnet_set_output_view / tdnet_set_output_surface; `d` = that configuration, `base` = the destination frame's base): the
+// colour map (r != NULL) or the overlay (o, u, src), from the low-resolution logits (labels == NULL) or from a uint8 label map.  One launch, like the contiguous
+// forms.  The picture's size must be the rectangle's: the frame entries check that before anything is enqueued (td_model.hip picture_dst_check), and here again.
 static int launch_picture_dst(const float* in, int C, int h, int w, const unsigned char* labels, const RgbOutput* r, const OverlayOutput* o, const U8Input* u,
                               const unsigned char* src, const DstOutput& d, unsigned char* base, hipStream_t s) {
     const char* what = r ? "colour map" : "overlay";
-    PicArgs a;
-    if (r) a = PicArgs{in, labels, r->ys, r->xs, r->lut, C, h, w, r->H, r->W, r->oh, r->ow};
-    else {
-        TD_TRY(overlay_check_tables(*o, *u));
-        a = PicArgs{in, labels, o->ys, o->xs, o->lut, C, h, w, o->H, o->W, o->Hs, o->Ws};
-    }
+    if (!r) TD_TRY(overlay_check_tables(*o, *u));
+    const PicArgs a = r ? picture_args(in, labels, C, h, w, *r) : picture_args(in, labels, C, h, w, *o);
     TD_TRY(out_check(what, "height", a.oh, labels ? 1 : C));
     if (!d.set || a.oh != d.h || a.ow != d.w) return td_fail("%s: the picture %d x %d is not the destination rectangle %d x %d", what, a.oh, a.ow, d.h, d.w);
     const bool src_bgr = !r && u->swap;                                // the picture word's bytes are b g r: the overlay's table and source are
-    DstView dv = DstView();
-    dv.base = base; dv.pitch = d.pitch; dv.uv_offset = (unsigned)d.uv_offset; dv.oy = d.oy; dv.ox = d.ox;
-    dv.swap = d.format != TDNET_PIX_NV12 && d.swap != src_bgr;
-    dv.yoff = d.yoff;
-    for (int i = 0; i < 3; ++i) {                                      // NV12 behind a b g r picture: the r and b constants exchanged
-        const int k = src_bgr ? 2 - i : i;
-        dv.ky[i] = d.ky[k]; dv.ku[i] = d.ku[k]; dv.kv[i] = d.kv[k];
-    }
-    const OverlaySrc sd = r ? OverlaySrc() : overlay_src(*u, src);
-    const int form = d.format == TDNET_PIX_NV12 ? TD_DST_NV12 : d.bpp == 4 ? TD_DST_P32 : TD_DST_P24;
     const bool src_surf = !r && u->surf;
-    const SurfLayout sl = src_surf ? surf_layout(*u) : SurfLayout();
-    const int src_form = r ? -1 : src_surf ? (sl.mid == 512 ? TD_SRC_SURF16 : TD_SRC_SURF8) : overlay_src_form(*u) / 2;
-    // An NV12 surface whose planes share one pitch IS the NV12 view: it takes k_picture_nv12.  Every other surface, and any 4:2:0 destination behind a surface
-    // source, takes k_picture_surface; a packed destination behind a surface source k_picture_packed_surf.
+    const bool yuv = d.format == TDNET_PIX_NV12;                       // a 4:2:0 destination: the NV12 view, or a surface
+    const SurfForm f = d.surf ? surf_form(d.layout) : SurfForm();      // the view: the NV12 row, both planes on one pitch
+    PicDst pd = PicDst();
+    pd.base = base; pd.pitch = d.pitch; pd.cpitch = d.surf ? d.cpitch : d.pitch;
+    pd.u_off = (unsigned)(d.surf ? d.u_off : d.uv_offset); pd.v_off = (unsigned)(d.surf ? d.v_off : d.uv_offset);
+    pd.oy = d.oy; pd.ox = d.ox; pd.swap = !yuv && d.swap != src_bgr;
+    pd.cstep = f.cstep; pd.uo = f.uo; pd.vo = f.vo; pd.yoff = d.yoff;
+    for (int i = 0; i < 3; ++i) {                                      // 4:2:0 behind a b g r picture: the r and b constants exchanged
+        const int k = src_bgr ? 2 - i : i;
+        pd.ky[i] = d.ky[k]; pd.ku[i] = d.ku[k]; pd.kv[i] = d.kv[k];
+    }
+    // An NV12 surface whose planes share one pitch IS the NV12 view: its layout is constants.  Every other surface, and any 4:2:0 destination behind a surface
+    // source, takes its layout from the arguments.
     const bool plain_nv12 = !d.surf || (d.layout == TDNET_SURF_NV12 && d.cpitch == d.pitch);
-    if (form == TD_DST_NV12 && (src_surf || !plain_nv12)) {
-        const SurfForm f = d.surf ? surf_form(d.layout) : SurfForm();
-        DstSurf ds = DstSurf();
-        ds.base = base; ds.pitch = d.pitch; ds.cpitch = d.surf ? d.cpitch : d.pitch;
-        ds.u_off = (unsigned)(d.surf ? d.u_off : d.uv_offset); ds.v_off = (unsigned)(d.surf ? d.v_off : d.uv_offset);
-        ds.oy = d.oy; ds.ox = d.ox; ds.cstep = f.cstep; ds.uo = f.uo; ds.vo = f.vo; ds.yoff = dv.yoff;
-        for (int i = 0; i < 3; ++i) { ds.ky[i] = dv.ky[i]; ds.ku[i] = dv.ku[i]; ds.kv[i] = dv.kv[i]; }
-        if (labels) launch_picture_surf<true>(a, sd, sl, ds, f.wide, src_form, s);
-        else launch_picture_surf<false>(a, sd, sl, ds, f.wide, src_form, s);
-        return 0;
-    }
-    if (src_surf) {
-        if (labels) launch_picture_packed_surf<true>(a, src, sl, dv, form, sl.mid == 512, s);
-        else launch_picture_packed_surf<false>(a, src, sl, dv, form, sl.mid == 512, s);
-        return 0;
-    }
-    if (labels) launch_picture_src<true>(a, sd, dv, form, src_form, s);
-    else launch_picture_src<false>(a, sd, dv, form, src_form, s);
-    return 0;
+    const int dst_form = !yuv ? (d.bpp == 4 ? TD_DST_P32 : TD_DST_P24) : (src_surf || !plain_nv12) ? TD_DST_YUV420 : TD_DST_NV12;
+    return launch_picture(a, r ? TD_SRC_NONE : picture_src_form(*u, false), src, r ? SrcLayout() : src_layout(*u), dst_form, yuv && f.wide, pd, s);
 }
 // score out (td_score.h): cm[map[gt]][label] += 1 over a frame, labels from the low-resolution logits (optionally written too: labels may be
 // NULL) or from a uint8 label map the caller holds.  A private LDS histogram per workgroup up to TD_SCORE_LDS_CLASSES classes, straight

@@ -315,7 +315,7 @@ extern "C" int tdnet_set_input_u8(tdnet_t* n, int src_height, int src_width, con
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_u8: weights not finalized");
     return set_input(n, src_view_rgb(src_height, src_width), src_height, src_width, mean, std_, "tdnet_set_input_u8");
 }
-// an NV12 surface of this layout (td_ingest.h k_ingest_nv12): the whole NV12 view
+// an NV12 surface of this layout (td_ingest.h IngestYuv with YuvFormNv12): the whole NV12 view
 extern "C" int tdnet_set_input_nv12(tdnet_t* n, int src_height, int src_width, int pitch, size_t uv_offset, int standard, const double* mean, const double* std_) {
     if (!n) return td_fail("tdnet_set_input_nv12: null handle");
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_set_input_nv12: weights not finalized");

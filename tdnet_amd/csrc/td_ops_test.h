@@ -499,109 +499,63 @@ extern "C" int tdnet_op_upsample(const float* in, int C, int h, int w, int H, in
     return 0;
 }
 // The stem's image buffer, allocated and zeroed as the workspace does (td_weights.h alloc_workspace), filled from an fp32 NCHW image (img_f32 != NULL:
-// run_stem_pre's fp32 kernels) or from a uint8 source (src_u8: the ingest kernel with the tables tdnet_set_input_u8 would build), then copied
-// WHOLE -- border included -- to out_dev.  rows: the packed-row layout, else NHWC4.  Returns the buffer's float count (out_dev == NULL: only that).
+// run_stem_pre's fp32 kernels) or from a byte source (src: the ingest kernel with the tables the handle's tdnet_set_input_* would build for what `resolve`
+// says the source is), then copied WHOLE -- border included -- to out_dev.  rows: the packed-row layout, else NHWC4.  Returns the buffer's float count
+// (out_dev == NULL: only that).  ONE body for the four entries below; bad_ptr: what to say about the entry's pointers, or NULL.
+template <class Resolve>   // int resolve(SrcView&, int& Hs, int& Ws): 0, or nonzero behind td_fail
+static long op_stem_image(const char* who, const float* img_f32, const uint8_t* src, const char* bad_ptr, Resolve resolve, int H, int W, const double* mean,
+                          const double* std_, int rows, float* out, size_t capacity, void* stream) {
+    if (H < 1 || W < 1) return td_fail("%s: empty image", who);
+    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
+    if (!out) return (long)img_floats;
+    if (bad_ptr) return td_fail("%s: %s", who, bad_ptr);
+    if (capacity < img_floats) return td_fail("%s: capacity %zu < %zu", who, capacity, img_floats);
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    if (src) {
+        SrcView sv;
+        int Hs = 0, Ws = 0;
+        if (resolve(sv, Hs, Ws) || u8_build(u, sv, Hs, Ws, H, W, mean, std_, who)) return -1;
+    }
+    float* img4 = nullptr;
+    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
+    long rc = (long)img_floats;
+    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("%s: memset failed", who);
+    if (rc >= 0) {
+        run_stem_pre(nullptr, src ? FrameInput{src, TD_IMG_U8, &u} : frame_input_f32(img_f32), H, W, img4, s, rows != 0);
+        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    hipFree(img4);
+    u8_free(u);
+    return rc;
+}
+// from an fp32 image or a tight RGB image [Hs][Ws][3] (tdnet_set_input_u8)
 extern "C" long tdnet_op_stem_image(const float* img_f32, const uint8_t* src_u8, int Hs, int Ws, int H, int W, const double* mean, const double* std_,
                                     int rows, float* out, size_t capacity, void* stream) {
-    if (H < 1 || W < 1) return td_fail("tdnet_op_stem_image: empty image");
-    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
-    if (!out) return (long)img_floats;
-    if ((img_f32 != nullptr) == (src_u8 != nullptr)) return td_fail("tdnet_op_stem_image: give exactly one of img_f32 and src_u8");
-    if (capacity < img_floats) return td_fail("tdnet_op_stem_image: capacity %zu < %zu", capacity, img_floats);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    if (src_u8 && u8_build(u, src_view_rgb(Hs, Ws), Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image")) return -1;
-    float* img4 = nullptr;
-    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
-    long rc = (long)img_floats;
-    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("tdnet_op_stem_image: memset failed");
-    if (rc >= 0) {
-        run_stem_pre(nullptr, src_u8 ? FrameInput{src_u8, TD_IMG_U8, &u} : frame_input_f32(img_f32), H, W, img4, s, rows != 0);
-        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("tdnet_op_stem_image: copy failed");
-    }
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_image: device error");
-    hipFree(img4);
-    u8_free(u);
-    return rc;
+    return op_stem_image("tdnet_op_stem_image", img_f32, src_u8, (img_f32 != nullptr) == (src_u8 != nullptr) ? "give exactly one of img_f32 and src_u8" : nullptr,
+                         [&](SrcView& sv, int& hs, int& ws) { sv = src_view_rgb(Hs, Ws); hs = Hs; ws = Ws; return 0; }, H, W, mean, std_, rows, out, capacity, stream);
 }
-// tdnet_op_stem_image from an NV12 surface: k_ingest_nv12 with the configuration tdnet_set_input_nv12 would build
+// from an NV12 surface (tdnet_set_input_nv12)
 extern "C" long tdnet_op_stem_image_nv12(const uint8_t* surf, int Hs, int Ws, int pitch, size_t uv_offset, int standard, int H, int W, const double* mean,
                                          const double* std_, int rows, float* out, size_t capacity, void* stream) {
-    if (H < 1 || W < 1) return td_fail("tdnet_op_stem_image_nv12: empty image");
-    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
-    if (!out) return (long)img_floats;
-    if (!surf) return td_fail("tdnet_op_stem_image_nv12: surf is NULL");
-    if (capacity < img_floats) return td_fail("tdnet_op_stem_image_nv12: capacity %zu < %zu", capacity, img_floats);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    const Nv12Layout nv = {pitch, uv_offset, standard};
-    if (u8_build(u, src_view_nv12(Hs, Ws, nv), Hs, Ws, H, W, mean, std_, "tdnet_op_stem_image_nv12")) return -1;
-    float* img4 = nullptr;
-    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
-    long rc = (long)img_floats;
-    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: memset failed");
-    if (rc >= 0) {
-        run_stem_pre(nullptr, FrameInput{surf, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
-        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: copy failed");
-    }
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_stem_image_nv12: device error");
-    hipFree(img4);
-    u8_free(u);
-    return rc;
+    return op_stem_image("tdnet_op_stem_image_nv12", nullptr, surf, surf ? nullptr : "surf is NULL",
+                         [&](SrcView& sv, int& hs, int& ws) { sv = src_view_nv12(Hs, Ws, Nv12Layout{pitch, uv_offset, standard}); hs = Hs; ws = Ws; return 0; },
+                         H, W, mean, std_, rows, out, capacity, stream);
 }
-// tdnet_op_stem_image from a source view: the ingest kernel of the view's format with the configuration tdnet_set_input_view would build
+// from a source view (tdnet_set_input_view)
 extern "C" long tdnet_op_stem_image_view(const uint8_t* base, const tdnet_view* view, int H, int W, const double* mean, const double* std_, int rows, float* out,
                                          size_t capacity, void* stream) {
     const char* who = "tdnet_op_stem_image_view";
-    if (H < 1 || W < 1) return td_fail("%s: empty image", who);
-    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
-    if (!out) return (long)img_floats;
-    if (!base) return td_fail("%s: base is NULL", who);
-    if (capacity < img_floats) return td_fail("%s: capacity %zu < %zu", who, capacity, img_floats);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    SrcView sv;
-    int Hs = 0, Ws = 0;
-    if (view_resolve(view, sv, Hs, Ws, who) || u8_build(u, sv, Hs, Ws, H, W, mean, std_, who)) return -1;
-    float* img4 = nullptr;
-    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
-    long rc = (long)img_floats;
-    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("%s: memset failed", who);
-    if (rc >= 0) {
-        run_stem_pre(nullptr, FrameInput{base, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
-        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
-    }
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-    hipFree(img4);
-    u8_free(u);
-    return rc;
+    return op_stem_image(who, nullptr, base, base ? nullptr : "base is NULL", [&](SrcView& sv, int& hs, int& ws) { return view_resolve(view, sv, hs, ws, who); },
+                         H, W, mean, std_, rows, out, capacity, stream);
 }
-// tdnet_op_stem_image from a YUV surface: k_ingest_surface with the configuration tdnet_set_input_surface would build
+// from a YUV surface (tdnet_set_input_surface)
 extern "C" long tdnet_op_stem_image_surface(const uint8_t* base, const tdnet_surface* surface, int H, int W, const double* mean, const double* std_, int rows, float* out,
                                             size_t capacity, void* stream) {
     const char* who = "tdnet_op_stem_image_surface";
-    if (H < 1 || W < 1) return td_fail("%s: empty image", who);
-    const size_t img_floats = std::max((size_t)H * W * 4, rows ? (size_t)stem_rows_hp(H) * stem_rows_wp(W) * 3 + 4 : (size_t)0);
-    if (!out) return (long)img_floats;
-    if (!base) return td_fail("%s: base is NULL", who);
-    if (capacity < img_floats) return td_fail("%s: capacity %zu < %zu", who, capacity, img_floats);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    SrcView sv;
-    int Hs = 0, Ws = 0;
-    if (surface_resolve(surface, sv, Hs, Ws, who) || u8_build(u, sv, Hs, Ws, H, W, mean, std_, who)) return -1;
-    float* img4 = nullptr;
-    if (dev_alloc(&img4, img_floats)) { u8_free(u); return -1; }
-    long rc = (long)img_floats;
-    if (hipMemsetAsync(img4, 0, img_floats * sizeof(float), s) != hipSuccess) rc = td_fail("%s: memset failed", who);
-    if (rc >= 0) {
-        run_stem_pre(nullptr, FrameInput{base, TD_IMG_U8, &u}, H, W, img4, s, rows != 0);
-        if (hipMemcpyAsync(out, img4, img_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
-    }
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-    hipFree(img4);
-    u8_free(u);
-    return rc;
+    return op_stem_image(who, nullptr, base, base ? nullptr : "base is NULL", [&](SrcView& sv, int& hs, int& ws) { return surface_resolve(surface, sv, hs, ws, who); },
+                         H, W, mean, std_, rows, out, capacity, stream);
 }
 // low-resolution logits [C][h][w] -> labels [H][W]: int32 through k_upsample_argmax (labels_i32 != NULL) and / or uint8 through
 // k_upsample_argmax_u8 (labels_u8 != NULL)
@@ -614,8 +568,8 @@ extern "C" int tdnet_op_upsample_argmax(const float* in, int C, int h, int w, in
     TD_HIP(hipGetLastError());
     return 0;
 }
-// The colour map [oh][ow][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: k_upsample_argmax_rgb) or of a uint8 label map [H][W]
-// (labels_u8 != NULL: k_labels_rgb; in, C, h, w are ignored), through the tables and colour table rgb_build makes for a handle.
+// The colour map [oh][ow][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: the fused form) or of a uint8 label map [H][W]
+// (labels_u8 != NULL; in, C, h, w are ignored), through the tables and colour table rgb_build makes for a handle.
 extern "C" int tdnet_op_upsample_argmax_rgb(const float* in, int C, int h, int w, int H, int W, int oh, int ow, const uint8_t* palette, int n_colours,
                                             uint8_t* rgb, const uint8_t* labels_u8, void* stream) {
     if (!rgb) return td_fail("tdnet_op_upsample_argmax_rgb: rgb_out is NULL");
@@ -628,20 +582,22 @@ extern "C" int tdnet_op_upsample_argmax_rgb(const float* in, int C, int h, int w
     rgb_free(r);
     return rc;
 }
-// The overlay [Hs][Ws][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: k_upsample_argmax_overlay) or of a uint8 label map [H][W] (labels_u8 != NULL:
-// k_labels_overlay; in, C, h, w are ignored) over a source frame: packed RGB [Hs][Ws][3] (nv12 == 0; pitch, uv_offset, standard ignored) or an NV12 surface,
-// through the byte-input description u8_build makes and the tables overlay_build / overlay_tables make for a handle.
-extern "C" int tdnet_op_overlay(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* src, int nv12, int Hs, int Ws, int pitch,
-                                size_t uv_offset, int standard, const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
-    const char* who = "tdnet_op_overlay";
-    if (!src || !out) return td_fail("%s: src and out expected", who);
+// The overlay [Hs][Ws][3] of low-resolution logits [C][h][w] (labels_u8 == NULL: the fused form) or of a uint8 label map [H][W] (labels_u8 != NULL; in, C, h, w
+// are ignored) over the source frame `resolve` describes, through the byte-input description u8_build makes and the tables overlay_build / overlay_tables make
+// for a handle; out in the source's colour order.  ONE body for the three entries below; src_name: what the entry calls its source pointer.
+template <class Resolve>   // int resolve(SrcView&, int& Hs, int& Ws): 0, or nonzero behind td_fail
+static int op_overlay(const char* who, const char* src_name, const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* src, Resolve resolve,
+                      const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
+    if (!src || !out) return td_fail("%s: %s and out expected", who, src_name);
     if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
     hipStream_t s = (hipStream_t)stream;
     U8Input u;
     OverlayOutput o;
-    const Nv12Layout nv = {pitch, uv_offset, standard};
-    TD_TRY(u8_build(u, nv12 ? src_view_nv12(Hs, Ws, nv) : src_view_rgb(Hs, Ws), Hs, Ws, H, W, nullptr, nullptr, who));
-    int rc = overlay_build(o, palette_rgba, n_colours, who);
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(resolve(sv, Hs, Ws));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    int rc = overlay_build(o, palette_rgba, n_colours, who, u.swap);
     if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
     if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, src, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, src, out, s);
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
@@ -649,59 +605,37 @@ extern "C" int tdnet_op_overlay(const float* in, int C, int h, int w, int H, int
     u8_free(u);
     return rc;
 }
-// tdnet_op_overlay with a source view in place of its source arguments: out [h][w][3] of the view's rectangle, in the source's colour order
+// over packed RGB [Hs][Ws][3] (nv12 == 0; pitch, uv_offset, standard ignored) or an NV12 surface
+extern "C" int tdnet_op_overlay(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* src, int nv12, int Hs, int Ws, int pitch,
+                                size_t uv_offset, int standard, const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
+    return op_overlay("tdnet_op_overlay", "src", in, C, h, w, H, W, labels_u8, src, [&](SrcView& sv, int& hs, int& ws) {
+        sv = nv12 ? src_view_nv12(Hs, Ws, Nv12Layout{pitch, uv_offset, standard}) : src_view_rgb(Hs, Ws); hs = Hs; ws = Ws; return 0; }, palette_rgba, n_colours, out, stream);
+}
+// over a source view: out [h][w][3] of the view's rectangle
 extern "C" int tdnet_op_overlay_view(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* base, const tdnet_view* view,
                                      const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
     const char* who = "tdnet_op_overlay_view";
-    if (!base || !out) return td_fail("%s: base and out expected", who);
-    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    OverlayOutput o;
-    SrcView sv;
-    int Hs = 0, Ws = 0;
-    TD_TRY(view_resolve(view, sv, Hs, Ws, who));
-    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
-    int rc = overlay_build(o, palette_rgba, n_colours, who, u.swap);
-    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
-    if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, base, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, base, out, s);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-    overlay_free(o);
-    u8_free(u);
-    return rc;
+    return op_overlay(who, "base", in, C, h, w, H, W, labels_u8, base, [&](SrcView& sv, int& hs, int& ws) { return view_resolve(view, sv, hs, ws, who); },
+                      palette_rgba, n_colours, out, stream);
 }
-// tdnet_op_overlay with a YUV surface in place of its source arguments: out [h][w][3] of the surface's rectangle, r g b
+// over a YUV surface: out [h][w][3] of the surface's rectangle, r g b
 extern "C" int tdnet_op_overlay_surface(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* base, const tdnet_surface* surface,
                                         const uint8_t* palette_rgba, int n_colours, uint8_t* out, void* stream) {
     const char* who = "tdnet_op_overlay_surface";
-    if (!base || !out) return td_fail("%s: base and out expected", who);
-    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
-    hipStream_t s = (hipStream_t)stream;
-    U8Input u;
-    OverlayOutput o;
-    SrcView sv;
-    int Hs = 0, Ws = 0;
-    TD_TRY(surface_resolve(surface, sv, Hs, Ws, who));
-    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
-    int rc = overlay_build(o, palette_rgba, n_colours, who);
-    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
-    if (!rc) rc = labels_u8 ? launch_labels_overlay(labels_u8, o, u, base, out, s) : launch_upsample_argmax_overlay(in, C, h, w, o, u, base, out, s);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-    overlay_free(o);
-    u8_free(u);
-    return rc;
+    return op_overlay(who, "base", in, C, h, w, H, W, labels_u8, base, [&](SrcView& sv, int& hs, int& ws) { return surface_resolve(surface, sv, hs, ws, who); },
+                      palette_rgba, n_colours, out, stream);
 }
-// The picture into a destination view (include/tdnet.h "destination views") through exactly the kernels the frame entries launch with one in force: of
-// low-resolution logits [C][h][w] (labels_u8 == NULL) or of a uint8 label map [H][W]; the overlay over the source view (src_base, src_view; palette
-// [n][4]) or, src_base == NULL, the colour map oh x ow (palette [n][3]).  dst_base: the destination frame's base, at any byte address.
-extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
-                                     const uint8_t* src_base, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base, const tdnet_view* dst_view, void* stream) {
-    const char* who = "tdnet_op_picture_view";
-    if (!dst_base || !dst_view) return td_fail("%s: dst_base and dst_view expected", who);
+// The picture into a destination view (include/tdnet.h "destination views", "surfaces") through exactly the kernels the frame entries launch with one in force: of
+// low-resolution logits [C][h][w] (labels_u8 == NULL) or of a uint8 label map [H][W]; the overlay over the source (src_base, what resolve_src describes;
+// palette [n][4]) or, src_base == NULL, the colour map oh x ow (palette [n][3]).  dst_base: the destination frame's base, at any byte address.  ONE body
+// for the two entries below.
+template <class ResolveDst, class ResolveSrc>   // int resolve_dst(DstOutput&), int resolve_src(SrcView&, int& Hs, int& Ws): 0, or nonzero behind td_fail
+static int op_picture(const char* who, const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
+                      const uint8_t* src_base, ResolveSrc resolve_src, int oh, int ow, uint8_t* dst_base, ResolveDst resolve_dst, void* stream) {
     if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
     hipStream_t s = (hipStream_t)stream;
     DstOutput d;
-    TD_TRY(dst_build(d, dst_view, who));
+    TD_TRY(resolve_dst(d));
     int rc = 0;
     if (!src_base) {
         RgbOutput r;
@@ -715,7 +649,7 @@ extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H
     OverlayOutput o;
     SrcView sv;
     int Hs = 0, Ws = 0;
-    TD_TRY(view_resolve(src_view, sv, Hs, Ws, who));
+    TD_TRY(resolve_src(sv, Hs, Ws));
     TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
     rc = overlay_build(o, palette, n_colours, who, u.swap);
     if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
@@ -725,41 +659,23 @@ extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H
     u8_free(u);
     return rc;
 }
-// tdnet_op_picture_view with surfaces on either side: the destination a 4:2:0 surface (dst_surface) or a view (dst_view), the overlay's source a surface
-// (src_surface) or a view (src_view); src_base == NULL: the colour map oh x ow
+// views on both sides
+extern "C" int tdnet_op_picture_view(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
+                                     const uint8_t* src_base, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base, const tdnet_view* dst_view, void* stream) {
+    const char* who = "tdnet_op_picture_view";
+    if (!dst_base || !dst_view) return td_fail("%s: dst_base and dst_view expected", who);
+    return op_picture(who, in, C, h, w, H, W, labels_u8, palette, n_colours, src_base, [&](SrcView& sv, int& hs, int& ws) { return view_resolve(src_view, sv, hs, ws, who); },
+                      oh, ow, dst_base, [&](DstOutput& d) { return dst_build(d, dst_view, who); }, stream);
+}
+// surfaces on either side: the destination a 4:2:0 surface (dst_surface) or a view (dst_view), the overlay's source a surface (src_surface) or a view (src_view)
 extern "C" int tdnet_op_picture_surface(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_u8, const uint8_t* palette, int n_colours,
                                         const uint8_t* src_base, const tdnet_surface* src_surface, const tdnet_view* src_view, int oh, int ow, uint8_t* dst_base,
                                         const tdnet_surface* dst_surface, const tdnet_view* dst_view, void* stream) {
     const char* who = "tdnet_op_picture_surface";
     if (!dst_base || (!dst_surface && !dst_view)) return td_fail("%s: dst_base and dst_surface or dst_view expected", who);
-    if (!labels_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
-    hipStream_t s = (hipStream_t)stream;
-    DstOutput d;
-    if (dst_surface) TD_TRY(dst_surface_build(d, dst_surface, who));
-    else TD_TRY(dst_build(d, dst_view, who));
-    int rc = 0;
-    if (!src_base) {
-        RgbOutput r;
-        TD_TRY(rgb_build(r, H, W, oh, ow, palette, n_colours, who));
-        rc = launch_picture_dst(in, C, h, w, labels_u8, &r, nullptr, nullptr, nullptr, d, dst_base, s);
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-        rgb_free(r);
-        return rc;
-    }
-    U8Input u;
-    OverlayOutput o;
-    SrcView sv;
-    int Hs = 0, Ws = 0;
-    if (src_surface) TD_TRY(surface_resolve(src_surface, sv, Hs, Ws, who));
-    else TD_TRY(view_resolve(src_view, sv, Hs, Ws, who));
-    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
-    rc = overlay_build(o, palette, n_colours, who, u.swap);
-    if (!rc) rc = overlay_tables(o, H, W, Hs, Ws, who);
-    if (!rc) rc = launch_picture_dst(in, C, h, w, labels_u8, nullptr, &o, &u, src_base, d, dst_base, s);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
-    overlay_free(o);
-    u8_free(u);
-    return rc;
+    return op_picture(who, in, C, h, w, H, W, labels_u8, palette, n_colours, src_base,
+                      [&](SrcView& sv, int& hs, int& ws) { return src_surface ? surface_resolve(src_surface, sv, hs, ws, who) : view_resolve(src_view, sv, hs, ws, who); },
+                      oh, ow, dst_base, [&](DstOutput& d) { return dst_surface ? dst_surface_build(d, dst_surface, who) : dst_build(d, dst_view, who); }, stream);
 }
 // cm_dev [C][C] (uint64, ACCUMULATED into, not cleared) += the confusion counts of ground truth gt [H][W] (through gt_map, 256 bytes on the host,
 // NULL = identity) against the labels of low-resolution logits [C][h][w] (labels_in == NULL: k_upsample_argmax_score, which also writes the uint8

@@ -15,7 +15,8 @@
 #include "td_device.h"
 #include "td_conv.h"   // td_ld4 / td_st4
 #include "td_misc.h"   // td_bilerp
-#include "td_ingest.h" // ingest_nv12_rgb: the one NV12 -> RGB conversion (overlay out reads the source frame)
+#include <type_traits>
+#include "td_ingest.h" // SrcLayout, the forms, yuv_rgb: the one YUV -> RGB conversion (overlay out reads the source frame)
 
 // ---- bilinear, align_corners=True (td4_psp18.py:227): planar [C][h][w] -> [C][H][W] ------------------------------
 struct UpCoef { int i0, i1; float l; };
@@ -199,11 +200,161 @@ TD_KERNEL void k_argmax_u8(const float* __restrict__ logits, unsigned char* __re
     td_u8_store(labels, pa, pb, bi);
 }
 
-// ---- colour map out ----------------------------------------------------------------------------------------------------------------
-// What the frame loop does on the host behind the labels (Testing/test.py:61-71; tdnet_amd/test.py save()): the nearest-index sample of the label
-// map to [oh][ow] and decode_segmap.  rgb [oh][ow][3] bytes = lut[labels[ys[oy]][xs[ox]]]: ys / xs are dataloader.nearest_index's tables, built on
-// the host (td_handle.h rgb_build), lut 256 words r | g << 8 | b << 16 (rows >= n_colours grey (l, l, l), as decode_segmap leaves them).
-// A row is 3 ow bytes and starts at any byte address; 4 pixels = 12 bytes = three 4-byte words where row + 3 x is 4-byte aligned, i.e. from
+// ---- pictures out ------------------------------------------------------------------------------------------------------------------
+// The colour map (include/tdnet.h "colour map out"): what the frame loop does on the host behind the labels (Testing/test.py:61-71; tdnet_amd/test.py
+// save()): the nearest-index sample of the label map to [oh][ow] and decode_segmap.  rgb [oh][ow][3] bytes = lut[labels[ys[oy]][xs[ox]]]: ys / xs are
+// dataloader.nearest_index's tables, built on the host (td_handle.h rgb_build), lut 256 words r | g << 8 | b << 16 (rows >= n_colours grey (l, l, l), as
+// decode_segmap leaves them).
+// The overlay ("overlay out"): the class colours blended over the SOURCE frame, at the source's size -- the same geometry with oh x ow = Hs x Ws
+// (ys / xs = nearest_index(H, Hs) / (W, Ws)), and per pixel the source bytes s and the table word r | g << 8 | b << 16 | a << 24 (0 for a label >= n_colours):
+//   A = a + (a >> 7)  (0..255 -> 0..256),   out_c = (c A + s_c (256 - A) + 128) >> 8   per channel, int32: A = 0 gives s, A = 256 gives c, no clamp.
+// Either picture goes into a contiguous [oh][ow][3] block, or into a rectangle of a pitched frame ("destination views", "surfaces"): packed 3-byte
+// pixels, packed 4-byte pixels (x = 255), or a 4:2:0 surface.
+// ONE per-lane body (td_picture_px4: the label from the class loop or from a label map, the colour word, the source pixel and the blend) under TWO
+// geometries: k_picture_rows -- a lane owns 4 pixels of one row -- for the contiguous and the packed destinations, k_picture_420 -- a lane owns a
+// 2-row x 4-column block on the chroma grid -- for the 4:2:0 ones.  What differs beyond that is a policy: the source form (td_src_px4), the destination
+// of a row, the form (td_ingest.h YuvFormArgs / YuvFormNv12) a 4:2:0 destination's layout comes from.
+struct PicArgs {
+    const float* in;               // low-resolution logits [C][h][w] (the fused forms)
+    const unsigned char* labels;   // uint8 label map [H][W] (the label-map forms)
+    const int* ys; const int* xs;  // [oh], [ow]: the sampled network pixel of a picture row / column
+    const unsigned* lut;           // [256]: the colour-map or the overlay table
+    int C, h, w, H, W, oh, ow;
+};
+// The source forms of the overlay; TD_SRC_NONE: the colour map.  The source is described by td_ingest.h's SrcLayout and read at its own resolution,
+// directly from the caller's buffer -- no LDS, no barrier, the early returns stay (why not ingest_stage_row: DESIGN.md 5.10).  A b g r source needs no
+// form of its own: the blend is per channel, so the host exchanges r and b in the colour table and the picture comes out b g r too.
+//   P24T, NV12T   the whole frame, packed 3-byte pixels tight / an NV12 surface: the origin (and the packed pitch, 3 ow) are constants of the form, not
+//                 arguments -- what the entries that predate the views reach compiles to what it was (measured: DESIGN.md 5.11)
+//   P24, P32      packed 3- / 4-byte pixels (the 4th byte read with its pixel, never used) of a view: origin and pitch are arguments
+//   NV12          an NV12 view.  Both NV12 forms are the YUV reader with the layout's numbers as constants (YuvFormNv12)
+//   SURF8, SURF16 a YUV surface of 8- / 16-bit samples: the layout is arguments (YuvFormArgs)
+enum { TD_SRC_NONE = 0, TD_SRC_P24T, TD_SRC_P24, TD_SRC_P32, TD_SRC_NV12T, TD_SRC_NV12, TD_SRC_SURF8, TD_SRC_SURF16 };
+// The destination forms (PicDst below)
+enum { TD_DST_RGB = 0, TD_DST_P24 = 1, TD_DST_P32 = 2,              // k_picture_rows' DST
+       TD_DST_NV12 = 3, TD_DST_YUV420 = 4 };                         // k_picture_420 with YuvFormNv12 / YuvFormArgs (the launch's names for them)
+// R and B share one multiply: the fields (c A + s (256 - A) + 128) <= 65408 of bits 0..15 and 16..31 do not carry into each other
+TD_DEV unsigned td_overlay_blend(unsigned lutw, unsigned s) {         // s = sR | sG << 8 | sB << 16
+    const unsigned a = lutw >> 24, A = a + (a >> 7), B = 256u - A;
+    const unsigned rb = (((lutw & 0x00FF00FFu) * A + (s & 0x00FF00FFu) * B + 0x00800080u) >> 8) & 0x00FF00FFu;
+    const unsigned g = (((lutw >> 8) & 0xFFu) * A + ((s >> 8) & 0xFFu) * B + 128u) & 0xFF00u;
+    return rb | g;
+}
+// s[e] = the source pixel (y, xa + e) as sR | sG << 8 | sB << 16 (a partial run repeats its last pixel, td_run_px).  quad: the run is a whole group the
+// lane may read at once -- its 12 or 16 packed bytes, or (NV12) its 4 Y bytes -- with byte-aligned loads the compiler is free to merge; otherwise, and for
+// a surface's samples and all chroma, pixel by pixel.  Only bytes of pixels (y, x < ow) and of the chroma samples covering them are addressed: nothing
+// outside the source extent, none of the pitch padding or of the gap between the planes.
+template <int SRC>
+TD_DEV void td_src_px4(const unsigned char* src, const SrcLayout& l, int y, long xa, long ow, bool quad, unsigned* s) {
+    constexpr bool VIEW = SRC != TD_SRC_P24T && SRC != TD_SRC_NV12T;
+    const int oy = VIEW ? l.oy : 0, ox = VIEW ? l.ox : 0;
+    if (SRC >= TD_SRC_NV12T) {
+        typedef typename std::conditional<(SRC >= TD_SRC_SURF8), YuvFormArgs, YuvFormNv12>::type F;
+        constexpr bool WIDE = SRC == TD_SRC_SURF16;
+        const int gy = oy + y;
+        const unsigned char* lr = src + (size_t)gy * l.pitch + F::loff(l);               // wave-uniform like y
+        const size_t crow = (size_t)(gy >> F::cshift(l)) * F::cpitch(l);
+        const unsigned char* ur = src + F::u_off(l) + crow + F::uo(l);
+        const unsigned char* vr = src + F::v_off(l) + crow + F::vo(l);
+        unsigned yw = 0;
+        if (F::luma_bytes && quad) __builtin_memcpy(&yw, lr + ox + xa, 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long gx = ox + td_run_px(xa, e, ow), c = (long)F::cstep(l) * (gx >> 1);
+            const int Y = F::luma_bytes && quad ? (int)((yw >> (8 * e)) & 255u) : surf_sample<WIDE>(lr + (long)F::lstride(l) * gx);
+            int p[3];
+            yuv_rgb<F>(l, Y, surf_sample<WIDE>(ur + c), surf_sample<WIDE>(vr + c), p);
+            s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+        }
+    } else if (SRC == TD_SRC_P32) {
+        const unsigned char* r = src + (size_t)(oy + y) * l.pitch + (size_t)ox * 4;
+        if (quad) {
+            unsigned v[4];
+            __builtin_memcpy(v, r + 4 * xa, 16);                       // ONE 16-byte read: four whole pixels of the rectangle
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] = v[e] & 0xFFFFFFu;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned char* p = r + 4 * td_run_px(xa, e, ow);
+                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+            }
+        }
+    } else {
+        const unsigned char* r = VIEW ? src + (size_t)(oy + y) * l.pitch + (size_t)ox * 3 : src + (size_t)y * ow * 3;   // tight: pitch = 3 ow
+        if (quad) {
+            unsigned v[3];
+            __builtin_memcpy(v, r + 3 * xa, 12);
+            s[0] = v[0] & 0xFFFFFFu;
+            s[1] = ((v[0] >> 24) | (v[1] << 8)) & 0xFFFFFFu;
+            s[2] = ((v[1] >> 16) | (v[2] << 16)) & 0xFFFFFFu;
+            s[3] = v[2] >> 8;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned char* p = r + 3 * td_run_px(xa, e, ow);
+                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+            }
+        }
+    }
+}
+// The 4 pixels xa .. xa + 3 of picture row y as words c0 | c1 << 8 | c2 << 16 (a partial run repeats its last pixel): the colour table's word of
+// the label -- the first-maximum argmax of the x8 bilinear upsample evaluated ONLY at the sampled pixel (Y, X) = (ys[y], xs[x]), or the label map's
+// byte -- blended over the source pixel for the overlay.  No branch on A: the blend with A = 0 returns the source.
+template <bool LABELS, int SRC, int DST>
+TD_DEV void td_picture_px4(const PicArgs& a, const unsigned char* src, const SrcLayout& l, int y, int q, long xa, long xb, unsigned* px) {
+    if (!LABELS && SRC != TD_SRC_NONE && DST == TD_DST_RGB) {
+        // The fused overlay into the contiguous block keeps the text of the kernel it had before this body (k_upsample_argmax_overlay): the arguments in
+        // locals, the source pixel before the table word.  Through the text below the same loads cost the allocator 6 - 10 VGPRs more.
+        const float* in = a.in;
+        const int* ys = a.ys; const int* xs = a.xs;
+        const unsigned* lut = a.lut;
+        const int C = a.C, h = a.h, w = a.w, H = a.H, W = a.W, ow = a.ow;
+        float best[4] = {0.f, 0.f, 0.f, 0.f};
+        int bi[4] = {0, 0, 0, 0};
+        td_up_classes(in, C, h, w, H, W, ys[y], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+        unsigned s[4];
+        td_src_px4<SRC>(src, l, y, xa, ow, q > 0 && xb - xa == 4, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
+        return;
+    }
+    // One cell reads its source in front of the label map, as the fused block above does: the label map over an NV12 view into a 3-byte view.  Behind
+    // it the allocator takes 33 VGPRs where the kernel this body replaced (k_picture_packed<1, true, true, 1>) took 32; the loads are independent, the
+    // bytes read and written the same.
+    constexpr bool SRC_FIRST = LABELS && SRC == TD_SRC_NV12 && DST == TD_DST_P24;
+    unsigned s[4];
+    if (SRC_FIRST) td_src_px4<SRC>(src, l, y, xa, a.ow, xa + 4 <= a.ow, s);
+    if (LABELS) {
+        const unsigned char* lrow = a.labels + (size_t)a.ys[y] * a.W;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = a.lut[lrow[a.xs[td_run_px(xa, e, a.ow)]]];
+    } else {
+        float best[4] = {0.f, 0.f, 0.f, 0.f};
+        int bi[4] = {0, 0, 0, 0};
+        td_up_classes(a.in, a.C, a.h, a.w, a.H, a.W, a.ys[y], [&](int e) { return a.xs[td_run_px(xa, e, a.ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = a.lut[bi[e] & 255];
+    }
+    if (SRC != TD_SRC_NONE) {
+        if (!SRC_FIRST) td_src_px4<SRC>(src, l, y, xa, a.ow, DST == TD_DST_RGB ? q > 0 && xb - xa == 4 : xa + 4 <= a.ow, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
+    }
+}
+
+// Where a picture goes.  TD_DST_RGB: the contiguous block [oh][ow][3] at `base` -- nothing else of this is read; the packed views: the rectangle at
+// (oy, ox) of a frame of rows `pitch` bytes apart; 4:2:0: td_ingest.h's layout table, by the form's choice from these fields or as its constants.
+struct PicDst {
+    unsigned char* base;           // the block, or the destination frame's base; any byte address
+    int pitch, cpitch;             // bytes per luma (or packed) row / per chroma row
+    unsigned u_off, v_off;         // 4:2:0: < 2^31 (one chroma plane: equal)
+    int oy, ox;                    // the rectangle's origin: picture pixel (y, x) is frame pixel (oy + y, ox + x); 4:2:0: both even
+    int swap;                      // packed: the destination's colour order is not the picture word's -- bytes 0 and 2 are exchanged at the store
+    int cstep, uo, vo;             // 4:2:0: bytes between the chroma pairs of a plane's row; where U and V lie in a pair
+    int yoff, ky[3], ku[3], kv[3]; // 4:2:0: rint(c 2^20) of the forward matrix, in the order of the picture word's bytes (the host exchanges r and b behind a b g r source)
+};
+// A row of 3-byte pixels is 3 ow bytes and starts at any byte address; 4 pixels = 12 bytes = three 4-byte words where row + 3 x is 4-byte aligned, i.e. from
 // x = row (mod 4) on (3 x = -row  <=>  x = row (mod 4), 3 being its own inverse).  Lane 0 of a row: the row & 3 pixels in front of the first such
 // group; lane q >= 1: the group behind it: [xa, xb)
 TD_DEV void td_rgb_run(const unsigned char* row, long q, long ow, long* xa, long* xb) {
@@ -222,204 +373,6 @@ TD_DEV void td_rgb_store(unsigned char* row, long q, long xa, long xb, const uns
             const unsigned p = px[X - xa];
             row[3 * X] = (unsigned char)p; row[3 * X + 1] = (unsigned char)(p >> 8); row[3 * X + 2] = (unsigned char)(p >> 16);
         }
-    }
-}
-// The frame's last launch when a picture is asked for: the x8 bilinear upsample evaluated ONLY at the sampled pixels (Y, X) = (ys[oy], xs[ox]),
-// and the colour looked up.  grid = (ceil((ow / 4 + 2) / 256), oh): row from the block index, Y and the vertical coefficients wave-uniform.
-TD_KERNEL void k_upsample_argmax_rgb(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                                     unsigned char* __restrict__ rgb, int C, int h, int w, int H, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = rgb + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    float best[4] = {0.f, 0.f, 0.f, 0.f};
-    int bi[4] = {0, 0, 0, 0};
-    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
-    unsigned px[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = lut[bi[e] & 255];
-    td_rgb_store(orow, q, xa, xb, px);
-}
-// The same picture from a uint8 label map [H][W] the caller already holds (same store layout)
-TD_KERNEL void k_labels_rgb(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                            unsigned char* __restrict__ rgb, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = rgb + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
-    unsigned px[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = lut[lrow[xs[td_run_px(xa, e, ow)]]];
-    td_rgb_store(orow, q, xa, xb, px);
-}
-
-// ---- overlay out -------------------------------------------------------------------------------------------------------------------
-// The picture people look at (include/tdnet.h "overlay out"): the class colours blended over the SOURCE frame, at the source's size.  The colour-map
-// kernels' geometry with oh x ow = Hs x Ws (ys / xs = nearest_index(H, Hs) / (W, Ws); lane split and store: td_rgb_run / td_rgb_store), and per
-// pixel the source bytes s and the table word r | g << 8 | b << 16 | a << 24 (0 for a label >= n_colours):
-//   A = a + (a >> 7)  (0..255 -> 0..256),   out_c = (c A + s_c (256 - A) + 128) >> 8   per channel, int32: A = 0 gives s, A = 256 gives c, no clamp.
-// The source is read at its own resolution, directly from the caller's buffer -- no LDS, no barrier, the early returns of the siblings stay: the
-// lane of an aligned group copies its 12 source bytes (packed RGB: a row starts at any byte, 3 Ws is odd at 1537) or its 4 Y bytes and its 2 - 3
-// chroma pairs (NV12) with byte-aligned loads the compiler is free to merge; head and tail lanes read pixel by pixel.  Only bytes of pixels
-// (y, x < Ws) and of chroma pairs (y >> 1, x >> 1) are addressed: nothing outside the source extent, none of the pitch padding or of the gap between
-// the planes.  (Why not ingest_stage_row: DESIGN.md 5.10.)  NV12 pixels are converted by ingest_nv12_rgb, the rule of "NV12 frames in".
-struct OverlaySrc {
-    const unsigned char* src;      // the frame's base (packed pixels, or the NV12 surface); any byte address
-    int pitch;                     // bytes per frame row (NV12: of both planes)
-    unsigned uv_offset;            // NV12: < 2^31
-    int yoff, cy, cub, cug, cvg, cvr;   // NV12: td_handle.h nv12_coeffs
-    int oy, ox;                    // a source view's origin: picture pixel (y, x) is frame pixel (oy + y, ox + x)
-};
-// The source forms: packed 3-byte pixels, an NV12 surface, packed 4-byte pixels (the 4th byte read with its pixel, never used).  A b g r source
-// needs no form of its own: the blend is per channel, so the host exchanges r and b in the colour table and the picture comes out b g r too.
-enum { TD_SRC_P24 = 0, TD_SRC_NV12 = 1, TD_SRC_P32 = 2 };
-// R and B share one multiply: the fields (c A + s (256 - A) + 128) <= 65408 of bits 0..15 and 16..31 do not carry into each other
-TD_DEV unsigned td_overlay_blend(unsigned lutw, unsigned s) {         // s = sR | sG << 8 | sB << 16
-    const unsigned a = lutw >> 24, A = a + (a >> 7), B = 256u - A;
-    const unsigned rb = (((lutw & 0x00FF00FFu) * A + (s & 0x00FF00FFu) * B + 0x00800080u) >> 8) & 0x00FF00FFu;
-    const unsigned g = (((lutw >> 8) & 0xFFu) * A + ((s >> 8) & 0xFFu) * B + 128u) & 0xFF00u;
-    return rb | g;
-}
-// s[e] = the source pixel (y, xa + e) as sR | sG << 8 | sB << 16 (a partial run repeats its last pixel, td_run_px); quad: the run is a whole group
-// VIEW = false: the whole frame, packed pixels tight -- the origin and the pitch are constants of the form, not arguments: what the entries that
-// predate the views reach compiles to what it was (measured: DESIGN.md 5.11)
-template <int SRC, bool VIEW>
-TD_DEV void td_overlay_src(const OverlaySrc& o, int y, long xa, long ow, bool quad, unsigned* s) {
-    const int oy = VIEW ? o.oy : 0, ox = VIEW ? o.ox : 0;
-    if (SRC == TD_SRC_NV12) {
-        const int gy = oy + y;
-        const unsigned char* yr = o.src + (size_t)gy * o.pitch + ox;
-        const unsigned char* cr = o.src + o.uv_offset + (size_t)(gy >> 1) * o.pitch;   // the chroma row: wave-uniform like y
-        IngestNv12Args k = IngestNv12Args();                           // ingest_nv12_rgb reads the six constants only
-        k.yoff = o.yoff; k.cy = o.cy; k.cub = o.cub; k.cug = o.cug; k.cvg = o.cvg; k.cvr = o.cvr;
-        unsigned yw = 0;
-        if (quad) __builtin_memcpy(&yw, yr + xa, 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const long x = td_run_px(xa, e, ow), cx = (ox + x) & ~1L;
-            const int Y = quad ? (int)((yw >> (8 * e)) & 255u) : (int)yr[x];
-            int p[3];
-            ingest_nv12_rgb(k, Y, cr[cx], cr[cx + 1], p);
-            s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
-        }
-    } else if (SRC == TD_SRC_P32) {
-        const unsigned char* r = o.src + (size_t)(oy + y) * o.pitch + (size_t)ox * 4;
-        if (quad) {
-            unsigned v[4];
-            __builtin_memcpy(v, r + 4 * xa, 16);                       // ONE 16-byte read: four whole pixels of the rectangle
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[e] = v[e] & 0xFFFFFFu;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned char* p = r + 4 * td_run_px(xa, e, ow);
-                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
-            }
-        }
-    } else {
-        const unsigned char* r = VIEW ? o.src + (size_t)(oy + y) * o.pitch + (size_t)ox * 3 : o.src + (size_t)y * ow * 3;   // tight: pitch = 3 ow
-        if (quad) {
-            unsigned v[3];
-            __builtin_memcpy(v, r + 3 * xa, 12);
-            s[0] = v[0] & 0xFFFFFFu;
-            s[1] = ((v[0] >> 24) | (v[1] << 8)) & 0xFFFFFFu;
-            s[2] = ((v[1] >> 16) | (v[2] << 16)) & 0xFFFFFFu;
-            s[3] = v[2] >> 8;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned char* p = r + 3 * td_run_px(xa, e, ow);
-                s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
-            }
-        }
-    }
-}
-// The frame's last launch when the overlay is asked for: k_upsample_argmax_rgb's body (grid, lane split, class loop, argmax rule, store) + the
-// source pixel and the blend.  No branch on A: the blend with A = 0 returns the source.  The launch bound asks for the sibling's 5 waves per SIMD: without
-// it the allocator settles at 98 / 100 VGPRs and 4 waves, with it at 84 / 86 (k_upsample_argmax_rgb: 84), no spill either way.
-template <int SRC, bool VIEW>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                                         OverlaySrc o, unsigned char* __restrict__ out, int C, int h, int w, int H, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = out + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    float best[4] = {0.f, 0.f, 0.f, 0.f};
-    int bi[4] = {0, 0, 0, 0};
-    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
-    unsigned s[4], px[4];
-    td_overlay_src<SRC, VIEW>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
-    td_rgb_store(orow, q, xa, xb, px);
-}
-// The same picture from a uint8 label map [H][W] the caller already holds (k_labels_rgb's body + the same)
-template <int SRC, bool VIEW>
-TD_KERNEL void k_labels_overlay(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                                OverlaySrc o, unsigned char* __restrict__ out, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = out + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
-    unsigned s[4], px[4];
-    td_overlay_src<SRC, VIEW>(o, oy, xa, ow, q > 0 && xb - xa == 4, s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
-    td_rgb_store(orow, q, xa, xb, px);
-}
-
-// ---- destination views -------------------------------------------------------------------------------------------------------------
-// The picture (colour map or overlay) written into a rectangle of a pitched frame instead of a contiguous [h][w][3] block (include/tdnet.h
-// "destination views"): packed 3-byte pixels, packed 4-byte pixels (x = 255), or an NV12 surface.  The kernels above stay what they are -- the
-// contiguous destination is their constant; these forms take the rectangle's origin, the pitch and the colour order as arguments and always read an
-// overlay's source through the VIEW = true readers.  One per-lane body (td_picture_px4) for the four pictures: the class loop, the argmax rule, the
-// colour table, the source readers and the blend are the ones above.
-enum { TD_DST_P24 = 1, TD_DST_P32 = 2, TD_DST_NV12 = 3 };
-struct PicArgs {
-    const float* in;               // low-resolution logits [C][h][w] (the fused forms)
-    const unsigned char* labels;   // uint8 label map [H][W] (the label-map forms)
-    const int* ys; const int* xs;  // [oh], [ow]: the sampled network pixel of a picture row / column
-    const unsigned* lut;           // [256]: the colour-map or the overlay table
-    int C, h, w, H, W, oh, ow;
-};
-struct DstView {
-    unsigned char* base;           // the destination frame's base; any byte address
-    int pitch;                     // bytes per frame row (NV12: of both planes)
-    unsigned uv_offset;            // NV12: < 2^31
-    int oy, ox;                    // the rectangle's origin: picture pixel (y, x) is frame pixel (oy + y, ox + x); NV12: both even
-    int swap;                      // packed: the destination's colour order is not the picture word's -- bytes 0 and 2 are exchanged at the store
-    int yoff, ky[3], ku[3], kv[3]; // NV12: rint(c 2^20) of the forward matrix, in the order of the picture word's bytes (the host exchanges r and b behind a b g r source)
-};
-// The 4 pixels xa .. xa + 3 of picture row y as words c0 | c1 << 8 | c2 << 16 (a partial run repeats its last pixel): the colour table's word of
-// the label -- the first-maximum argmax at the sampled pixel, or the label map's byte -- blended over the source pixel for the overlay.
-template <bool LABELS, bool OVERLAY, int SRC>
-TD_DEV void td_picture_px4(const PicArgs& a, const OverlaySrc& o, int y, long xa, unsigned* px) {
-    if (LABELS) {
-        const unsigned char* lrow = a.labels + (size_t)a.ys[y] * a.W;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) px[e] = a.lut[lrow[a.xs[td_run_px(xa, e, a.ow)]]];
-    } else {
-        float best[4] = {0.f, 0.f, 0.f, 0.f};
-        int bi[4] = {0, 0, 0, 0};
-        td_up_classes(a.in, a.C, a.h, a.w, a.H, a.W, a.ys[y], [&](int e) { return a.xs[td_run_px(xa, e, a.ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
-#pragma unroll
-        for (int e = 0; e < 4; ++e) px[e] = a.lut[bi[e] & 255];
-    }
-    if (OVERLAY) {
-        unsigned s[4];
-        td_overlay_src<SRC, true>(o, y, xa, a.ow, xa + 4 <= a.ow, s);   // a whole run is read at once: four pixels of the rectangle
-#pragma unroll
-        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
     }
 }
 TD_DEV unsigned td_swap_rb(unsigned p) { return (p & 0xFF00u) | ((p >> 16) & 0xFFu) | ((p & 0xFFu) << 16); }
@@ -447,145 +400,48 @@ TD_DEV void td_p32_store(unsigned char* row, long xa, long xb, const unsigned* p
         }
     }
 }
-// Packed destinations: k_upsample_argmax_rgb's geometry (a grid row per picture row, the lane split by the row's address) on the rectangle's rows.
-template <int DST, bool LABELS, bool OVERLAY, int SRC>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_picture_packed(PicArgs a, OverlaySrc o, DstView d) {
+// The row geometry: grid = (ceil((ow / 4 + 2) / 256), oh), the row from the block index, Y and the vertical coefficients wave-uniform, the lane split by
+// the row's address (td_rgb_run / td_p32_run).  The frame's last launch when a picture into a contiguous block or a packed view is asked for.
+// The contiguous destination's row address is a constant of the form: no origin, pitch or swap is read; a lane of it reads its source group at once
+// where its run is an aligned group (q > 0), a lane of a view where the run is whole (xa + 4 <= ow): which bytes a lane reads is part of the memory
+// contract (include/tdnet.h).
+// The launch bound asks for 5 waves per SIMD: without it the allocator settles the fused overlay forms at 98 / 100 VGPRs and 4 waves, with it at 84 / 86
+// (the colour map: 84), no spill either way.  The kernels the label-map forms into a contiguous block replace had no bound, and these
+// keep none: (1024, 1) is the compiler's default for a kernel without the attribute, spelled out because a template cannot leave the attribute away
+// per instantiation.  It promises nothing about the launch, which is 256 threads like every form's (at most 38 VGPRs, 8 waves).
+constexpr int td_rows_threads(bool labels, int dst) { return labels && dst == TD_DST_RGB ? 1024 : 256; }
+constexpr int td_rows_waves(bool labels, int dst) { return labels && dst == TD_DST_RGB ? 1 : 5; }
+template <bool LABELS, int SRC, int DST>
+TD_KERNEL void TD_LAUNCH_BOUNDS(td_rows_threads(LABELS, DST), td_rows_waves(LABELS, DST)) k_picture_rows(PicArgs a, const unsigned char* src, SrcLayout l, PicDst d) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= a.oh) return;
-    unsigned char* row = d.base + (size_t)(d.oy + y) * d.pitch + (size_t)d.ox * (DST == TD_DST_P32 ? 4 : 3);
+    unsigned char* row = DST == TD_DST_RGB ? d.base + (size_t)y * a.ow * 3 : d.base + (size_t)(d.oy + y) * d.pitch + (size_t)d.ox * (DST == TD_DST_P32 ? 4 : 3);
     long xa, xb;
     if (DST == TD_DST_P32) td_p32_run(row, q, a.ow, &xa, &xb);
     else td_rgb_run(row, q, a.ow, &xa, &xb);
     if (xa >= xb) return;
     unsigned px[4];
-    td_picture_px4<LABELS, OVERLAY, SRC>(a, o, y, xa, px);
-    if (d.swap) {                                                      // wave-uniform
+    td_picture_px4<LABELS, SRC, DST>(a, src, l, y, q, xa, xb, px);
+    if (DST != TD_DST_RGB && d.swap) {                                 // wave-uniform
 #pragma unroll
         for (int e = 0; e < 4; ++e) px[e] = td_swap_rb(px[e]);
     }
     if (DST == TD_DST_P32) td_p32_store(row, xa, xb, px);
     else td_rgb_store(row, q, xa, xb, px);
 }
-// NV12 destination.  A lane owns the 2-row x 4-column block (j, q) of the rectangle, which the even origin aligns to the frame's chroma grid: rows
-// 2 j and 2 j + 1, columns 4 q .. 4 q + 3, the chroma pairs (oy / 2 + j, ox / 2 + 2 q) and the one behind it.  Row by row: the picture's four pixels,
-// their luma bytes stored, their colours added to the two pairs' sums; then the pairs.  At the rectangle's odd last row / column a pair covers n = 2
-// or 1 pixels and its sum is scaled by m = 4 / n.  All in int32 (|m S K| <= 1020 * 0.5 * 2^20, + 2^29 + 2^21 < 2^31), arithmetic shifts.  No LDS, no
-// barrier, no cross-lane traffic; grid = (ceil(ceil(ow / 4) / 256), ceil(oh / 2)).
-TD_DEV int td_chroma8(const int* k, const int* s, int m) { return ingest_clamp8((m * (k[0] * s[0] + k[1] * s[1] + k[2] * s[2]) + (128 << 22) + (1 << 21)) >> 22); }
-// The launch bound asks for 4 waves per SIMD, not the siblings' 5: two rows' worth of state (the pairs' six sums beside the class loop's accumulators and
-// coefficients) does not fit 96 VGPRs -- the fused overlay forms spilled 2 - 21 registers there (DESIGN.md 5.12) -- and a lane does two rows' work anyway.
-template <bool LABELS, bool OVERLAY, int SRC>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_nv12(PicArgs a, OverlaySrc o, DstView d) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-    const long xa = 4L * q;
-    if (2 * j >= a.oh || xa >= a.ow) return;
-    const int nx = a.ow - xa < 4 ? (int)(a.ow - xa) : 4, ny = a.oh - 2 * j < 2 ? 1 : 2;
-    int s0[3] = {0, 0, 0}, s1[3] = {0, 0, 0};                          // the colour sums of the pair of columns 0, 1 and of columns 2, 3
-    for (int r = 0; r < ny; ++r) {
-        unsigned px[4];
-        td_picture_px4<LABELS, OVERLAY, SRC>(a, o, 2 * j + r, xa, px);
-        int yb[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c0 = (int)(px[e] & 255u), c1 = (int)((px[e] >> 8) & 255u), c2 = (int)((px[e] >> 16) & 255u);
-            yb[e] = ingest_clamp8((d.ky[0] * c0 + d.ky[1] * c1 + d.ky[2] * c2 + (d.yoff << 20) + (1 << 19)) >> 20);
-            if (e < nx) {
-                int* s = e < 2 ? s0 : s1;
-                s[0] += c0; s[1] += c1; s[2] += c2;
-            }
-        }
-        td_u8_store(d.base + (size_t)(d.oy + 2 * j + r) * d.pitch + d.ox, xa, xa + nx, yb);
-    }
-    const int m0 = 4 / (ny * (nx < 2 ? nx : 2)), m1 = nx > 2 ? 4 / (ny * (nx - 2)) : 0;
-    int cb[4];
-    cb[0] = td_chroma8(d.ku, s0, m0); cb[1] = td_chroma8(d.kv, s0, m0);
-    cb[2] = td_chroma8(d.ku, s1, m1); cb[3] = td_chroma8(d.kv, s1, m1);
-    td_u8_store(d.base + d.uv_offset + (size_t)((d.oy >> 1) + j) * d.pitch + d.ox, xa, xa + (nx > 2 ? 4 : 2), cb);
-}
 
-// ---- overlay out over a YUV surface ------------------------------------------------------------------------------------------------
-// The overlay kernels above with the source read from a surface (include/tdnet.h "surfaces"; td_ingest.h SurfLayout): per pixel of the rectangle its
-// luma sample and the U and V samples covering it, with byte-aligned loads, converted by ingest_surf_rgb.  No LDS, no barrier, the early returns of the
-// siblings; only sample bytes that cover the rectangle are addressed.  Kernels of their own: OverlaySrc and the kernels that take it stay what they are.
-template <bool WIDE>
-TD_DEV void td_overlay_src_surf(const unsigned char* src, const SurfLayout& l, int y, long xa, long ow, unsigned* s) {
-    const int gy = l.oy + y;
-    const unsigned char* lr = src + (size_t)gy * l.pitch + l.loff;                 // wave-uniform like y
-    const size_t crow = (size_t)(gy >> l.cshift) * l.cpitch;
-    const unsigned char* ur = src + l.u_off + crow + l.uo;
-    const unsigned char* vr = src + l.v_off + crow + l.vo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const long gx = l.ox + td_run_px(xa, e, ow), c = (long)l.cstep * (gx >> 1);
-        int p[3];
-        ingest_surf_rgb(l, surf_sample<WIDE>(lr + (long)l.lstride * gx), surf_sample<WIDE>(ur + c), surf_sample<WIDE>(vr + c), p);
-        s[e] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
-    }
-}
-template <bool WIDE>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_upsample_argmax_overlay_surf(const float* __restrict__ in, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                                         const unsigned char* __restrict__ src, SurfLayout l, unsigned char* __restrict__ out, int C, int h, int w, int H, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = out + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    float best[4] = {0.f, 0.f, 0.f, 0.f};
-    int bi[4] = {0, 0, 0, 0};
-    td_up_classes(in, C, h, w, H, W, ys[oy], [&](int e) { return xs[td_run_px(xa, e, ow)]; }, [&](int c, int e, float v) { td_first_max(c, v, best[e], bi[e]); });
-    unsigned s[4], px[4];
-    td_overlay_src_surf<WIDE>(src, l, oy, xa, ow, s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[bi[e] & 255], s[e]);
-    td_rgb_store(orow, q, xa, xb, px);
-}
-template <bool WIDE>
-TD_KERNEL void k_labels_overlay_surf(const unsigned char* __restrict__ labels, const int* __restrict__ ys, const int* __restrict__ xs, const unsigned* __restrict__ lut,
-                                     const unsigned char* __restrict__ src, SurfLayout l, unsigned char* __restrict__ out, int W, int oh, int ow) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (oy >= oh) return;
-    unsigned char* orow = out + (size_t)oy * ow * 3;
-    long xa, xb;
-    td_rgb_run(orow, q, ow, &xa, &xb);
-    if (xa >= xb) return;
-    const unsigned char* lrow = labels + (size_t)ys[oy] * W;
-    unsigned s[4], px[4];
-    td_overlay_src_surf<WIDE>(src, l, oy, xa, ow, s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(lut[lrow[xs[td_run_px(xa, e, ow)]]], s[e]);
-    td_rgb_store(orow, q, xa, xb, px);
-}
-
-// ---- surface destinations ------------------------------------------------------------------------------------------------------------
-// The picture written into a rectangle of a 4:2:0 surface -- NV12 with a chroma pitch of its own, NV21, I420 / YV12, P010 (include/tdnet.h "surfaces") --
-// and the overlay over a surface SOURCE into any destination.  k_picture_nv12's lane block (2 rows x 4 columns, the even origin aligns it to the chroma
-// grid), sums and scaling m = 4 / n; the layout is wave-uniform arguments, the destination's sample width the instantiation:
+// The block geometry: a 4:2:0 destination -- NV12, NV12 with a chroma pitch of its own, NV21, I420 / YV12, P010.  A lane owns the 2-row x 4-column block
+// (j, q) of the rectangle, which the even origin aligns to the frame's chroma grid: rows 2 j and 2 j + 1, columns 4 q .. 4 q + 3, the chroma pairs
+// (oy / 2 + j, ox / 2 + 2 q) and the one behind it.  Row by row: the picture's four pixels, their luma samples stored, their colours added to the two
+// pairs' sums; then the pairs.  At the rectangle's odd last row / column a pair covers n = 2 or 1 pixels and its sum is scaled by m = 4 / n.  All in
+// int32 (|m S K| <= 1020 * 0.5 * 2^20, + 2^29 + 2^21 < 2^31), arithmetic shifts.  No LDS, no barrier, no cross-lane traffic;
+// grid = (ceil(ceil(ow / 4) / 256), ceil(oh / 2)).  The destination's sample width is the instantiation, its layout the form F's:
 //   8 bit   Y = clamp8((K . c + (yoff << 20) + (1 << 19)) >> 20),   U = clamp8((m K . S + (128 << 22) + (1 << 21)) >> 22)     (td_chroma8)
 //   P010    Y10 = clamp10((K . c + (yoff << 20) + (1 << 17)) >> 18), U10 = clamp10((m K . S + (128 << 22) + (1 << 19)) >> 20), stored as value << 6,
 //           little-endian, bytewise unless the run is 8-byte aligned (the base may be an odd address).
-// The sources: the three forms of "overlay out" above through td_overlay_src<SRC, true>, and a surface through td_overlay_src_surf.
-enum { TD_SRC_SURF8 = 3, TD_SRC_SURF16 = 4 };
-struct DstSurf {
-    unsigned char* base;           // the destination surface's base; any byte address
-    int pitch, cpitch;             // bytes per luma row / per chroma row
-    unsigned u_off, v_off;         // < 2^31 (one chroma plane: equal)
-    int oy, ox;                    // the rectangle's origin, both even
-    int cstep, uo, vo;             // bytes between the chroma pairs of a plane's row; where U and V lie in a pair
-    int yoff, ky[3], ku[3], kv[3]; // rint(c 2^20) of the forward matrix, in the order of the picture word's bytes
-};
-template <bool LABELS, bool OVERLAY, int SRC>
-TD_DEV void td_picture_px4s(const PicArgs& a, const OverlaySrc& o, const SurfLayout& sl, int y, long xa, unsigned* px) {
-    if (OVERLAY && SRC >= TD_SRC_SURF8) {
-        td_picture_px4<LABELS, false, TD_SRC_P24>(a, o, y, xa, px);
-        unsigned s[4];
-        td_overlay_src_surf<SRC == TD_SRC_SURF16>(o.src, sl, y, xa, a.ow, s);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
-    } else {
-        td_picture_px4<LABELS, OVERLAY, (SRC >= TD_SRC_SURF8 ? TD_SRC_P24 : SRC)>(a, o, y, xa, px);
-    }
-}
+// YuvFormNv12: the NV12 view, and an NV12 surface whose planes share one pitch; YuvFormArgs: every other surface, and any 4:2:0 destination behind a
+// surface source.
+TD_DEV int td_chroma8(const int* k, const int* s, int m) { return ingest_clamp8((m * (k[0] * s[0] + k[1] * s[1] + k[2] * s[2]) + (128 << 22) + (1 << 21)) >> 22); }
 TD_DEV int td_clamp10(int v) { return v < 0 ? 0 : v > 1023 ? 1023 : v; }
 TD_DEV int td_chroma10(const int* k, const int* s, int m) { return td_clamp10((m * (k[0] * s[0] + k[1] * s[1] + k[2] * s[2]) + (128 << 22) + (1 << 19)) >> 20); }
 // n (1..4) 10-bit values as words value << 6 at p: ONE 8-byte store where all four are there and p is 8-byte aligned, bytes otherwise
@@ -600,8 +456,10 @@ TD_DEV void td_w16_store(unsigned char* p, int n, const int* b) {
         for (int i = 0; i < n; ++i) { const unsigned w = (unsigned)b[i] << 6; p[2 * i] = (unsigned char)w; p[2 * i + 1] = (unsigned char)(w >> 8); }
     }
 }
-template <bool LABELS, bool OVERLAY, int SRC, bool WIDE>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_surface(PicArgs a, OverlaySrc o, SurfLayout sl, DstSurf d) {
+// The launch bound asks for 4 waves per SIMD, not the row kernel's 5: two rows' worth of state (the pairs' six sums beside the class loop's accumulators and
+// coefficients) does not fit 96 VGPRs -- the fused overlay forms spilled 2 - 21 registers there (DESIGN.md 5.12) -- and a lane does two rows' work anyway.
+template <bool LABELS, int SRC, bool WIDE, class F>
+TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_420(PicArgs a, const unsigned char* src, SrcLayout l, PicDst d) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
     const long xa = 4L * q;
     if (2 * j >= a.oh || xa >= a.ow) return;
@@ -609,7 +467,7 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_surface(PicArgs a, OverlaySrc 
     int s0[3] = {0, 0, 0}, s1[3] = {0, 0, 0};                          // the colour sums of the pair of columns 0, 1 and of columns 2, 3
     for (int r = 0; r < ny; ++r) {
         unsigned px[4];
-        td_picture_px4s<LABELS, OVERLAY, SRC>(a, o, sl, 2 * j + r, xa, px);
+        td_picture_px4<LABELS, SRC, TD_DST_YUV420>(a, src, l, 2 * j + r, q, xa, xa + nx, px);
         int yb[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -629,40 +487,18 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 4) k_picture_surface(PicArgs a, OverlaySrc 
     const int np = nx > 2 ? 2 : 1;                                     // chroma pairs of this block
     const int u0 = WIDE ? td_chroma10(d.ku, s0, m0) : td_chroma8(d.ku, s0, m0), v0 = WIDE ? td_chroma10(d.kv, s0, m0) : td_chroma8(d.kv, s0, m0);
     const int u1 = WIDE ? td_chroma10(d.ku, s1, m1) : td_chroma8(d.ku, s1, m1), v1 = WIDE ? td_chroma10(d.kv, s1, m1) : td_chroma8(d.kv, s1, m1);
-    const size_t crow = (size_t)((d.oy >> 1) + j) * d.cpitch, pair = (size_t)(d.ox >> 1) + 2 * (size_t)q;   // the chroma row, the block's first pair
+    const size_t crow = (size_t)((d.oy >> 1) + j) * F::cpitch(d), pair = (size_t)(d.ox >> 1) + 2 * (size_t)q;   // the chroma row, the block's first pair
     if (WIDE) {                                                        // U, V word pairs: 8 bytes per two pairs
         const int cb[4] = {u0, v0, u1, v1};
-        td_w16_store(d.base + d.u_off + crow + 4 * pair, 2 * np, cb);
-    } else if (d.cstep == 2) {                                         // interleaved byte pairs, U first or (NV21) V first: wave-uniform
-        const bool vu = d.uo != 0;
+        td_w16_store(d.base + F::u_off(d) + crow + 4 * pair, 2 * np, cb);
+    } else if (F::cstep(d) == 2) {                                     // interleaved byte pairs, U first or (NV21) V first: wave-uniform
+        const bool vu = F::uo(d) != 0;
         const int cb[4] = {vu ? v0 : u0, vu ? u0 : v0, vu ? v1 : u1, vu ? u1 : v1};
-        td_u8_store(d.base + d.u_off + crow + d.ox, xa, xa + 2 * np, cb);
+        td_u8_store(d.base + F::u_off(d) + crow + d.ox, xa, xa + 2 * np, cb);
     } else {                                                           // I420: a row of the U plane and a row of the V plane
-        unsigned char* up = d.base + d.u_off + crow + pair;
-        unsigned char* vp = d.base + d.v_off + crow + pair;
+        unsigned char* up = d.base + F::u_off(d) + crow + pair;
+        unsigned char* vp = d.base + F::v_off(d) + crow + pair;
         up[0] = (unsigned char)u0; vp[0] = (unsigned char)v0;
         if (np == 2) { up[1] = (unsigned char)u1; vp[1] = (unsigned char)v1; }
     }
-}
-// Packed destinations of the overlay over a surface source: k_picture_packed with the source read by td_overlay_src_surf
-template <int DST, bool LABELS, bool WIDE>
-TD_KERNEL void TD_LAUNCH_BOUNDS(256, 5) k_picture_packed_surf(PicArgs a, const unsigned char* __restrict__ src, SurfLayout sl, DstView d) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (y >= a.oh) return;
-    unsigned char* row = d.base + (size_t)(d.oy + y) * d.pitch + (size_t)d.ox * (DST == TD_DST_P32 ? 4 : 3);
-    long xa, xb;
-    if (DST == TD_DST_P32) td_p32_run(row, q, a.ow, &xa, &xb);
-    else td_rgb_run(row, q, a.ow, &xa, &xb);
-    if (xa >= xb) return;
-    unsigned px[4], s[4];
-    td_picture_px4<LABELS, false, TD_SRC_P24>(a, OverlaySrc(), y, xa, px);
-    td_overlay_src_surf<WIDE>(src, sl, y, xa, a.ow, s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) px[e] = td_overlay_blend(px[e], s[e]);
-    if (d.swap) {                                                      // wave-uniform
-#pragma unroll
-        for (int e = 0; e < 4; ++e) px[e] = td_swap_rb(px[e]);
-    }
-    if (DST == TD_DST_P32) td_p32_store(row, xa, xb, px);
-    else td_rgb_store(row, q, xa, xb, px);
 }

@@ -98,7 +98,7 @@ def test_pictures_into_surfaces(lib, case, layout, variant):
 @pytest.mark.parametrize("standard", [0, 3])
 def test_pictures_into_surfaces_other_standards(lib, standard):
     for layout in (SURF_I420, SURF_P010):
-        cases.run_dest_case(lib, MEM, layout, "padded", "corner_odd", standard=standard, sources=("nv12_view", "uyvy"), offsets=(3,))
+        cases.run_dest_case(lib, MEM, layout, "padded", "corner_odd", standard=standard, sources=("nv12_view", "uyvy", "rgb24_whole"), offsets=(3,))
 
 
 def test_destination_views_behind_a_surface_source(lib):

@@ -104,7 +104,7 @@ def test_pictures_into_surfaces(lib, layout, variant):
 def test_pictures_into_surfaces_other_standards_and_views_behind_surface_sources(lib):
     for standard in (0, 3):
         for layout in (SURF_I420, SURF_P010):
-            cases.run_dest_case(lib, MEM, layout, "padded", "corner_odd", standard=standard, sources=("nv12_view", "uyvy"), offsets=(3,))
+            cases.run_dest_case(lib, MEM, layout, "padded", "corner_odd", standard=standard, sources=("nv12_view", "uyvy", "rgb24_whole"), offsets=(3,))
     cases.run_view_dest_behind_surface_source(lib, MEM)
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU-box probe for destination views (csrc/td_out.h k_picture_packed / k_picture_nv12; include/tdnet.h "destination views").
+"""GPU-box probe for destination views (csrc/td_out.h k_picture_rows into TD_DST_P24 / TD_DST_P32, k_picture_420; before the byte ends were unified: k_picture_packed / k_picture_nv12; include/tdnet.h "destination views").
 
 Device milliseconds per steady-state td4-psp18 frame over an NV12 source, the variants interleaved in one process (one handle each, --rounds rounds of
 --frames frames, the order rotating, HIP events around each round):

@@ -2,7 +2,7 @@
 """GPU-box probe for the byte ends of a frame (csrc/td_ingest.h in, csrc/td_out.h out), to be run under `rocprofv3 --kernel-trace --stats` for the per-kernel times
 (the ops themselves allocate and synchronise):
 
-  ingest    k_ingest_u8 at HxW same-size and from --src-size, beside k_nchw3_to_rgbpad / k_nchw3_to_nhwc4 on an fp32 image of the same
+  ingest    the packed ingest (k_ingest<IngestPacked<3, false>>; before the byte ends were unified: k_ingest_u8) at HxW same-size and from --src-size, beside k_nchw3_to_rgbpad / k_nchw3_to_nhwc4 on an fp32 image of the same
             network size (tdnet_op_stem_image, both layouts)
   labels    k_upsample_argmax_u8 beside k_upsample_argmax on the same low-resolution logits (tdnet_op_upsample_argmax)
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""GPU-box probe for NV12 frames in (csrc/td_ingest.h k_ingest_nv12; include/tdnet.h "NV12 frames in").
+"""GPU-box probe for NV12 frames in (csrc/td_ingest.h k_ingest<IngestYuv<false, YuvFormNv12>>, in a build from before the byte ends were unified k_ingest_nv12; include/tdnet.h "NV12 frames in").
 
-  --mode ingest   k_ingest_nv12 beside k_ingest_u8 on the same picture (tdnet_op_stem_image_nv12 / tdnet_op_stem_image, both layouts), and a
+  --mode ingest   the NV12 ingest beside the packed one (k_ingest<IngestPacked<3, false>>; before: k_ingest_u8) on the same picture (tdnet_op_stem_image_nv12 / tdnet_op_stem_image, both layouts), and a
                   check that the two buffers are identical.  The ops allocate and synchronise: run it under
                   `rocprofv3 --kernel-trace --stats` for the per-kernel times.  --lib PATH loads another build's test library (e.g. the
-                  parent commit's, for its k_ingest_u8; the NV12 half is skipped when that library lacks the entry).
+                  parent commit's, for its packed ingest; the NV12 half is skipped when that library lacks the entry).
   --mode frames   whole td4-psp18 frames per second with NV12 surfaces against RGB bytes, interleaved in one process: two handles on one
                   weight block, --rounds rounds of --frames frames each, alternating; per-round rates, medians and the spread.
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU-box probe for overlay out (csrc/td_out.h k_upsample_argmax_overlay; include/tdnet.h "overlay out").
+"""GPU-box probe for overlay out (csrc/td_out.h k_picture_rows<false, SRC, TD_DST_RGB>, before the byte ends were unified k_upsample_argmax_overlay<SRC, VIEW>; include/tdnet.h "overlay out").
 
 Device milliseconds per steady-state td4-psp18 frame with three last launches on the same frames, interleaved in one process (three handles on
 one weight block, --rounds rounds of --frames frames each, the order rotating, HIP events around each round):

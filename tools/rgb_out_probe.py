@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""GPU-box probe for the colour-map output (csrc/td_out.h k_upsample_argmax_rgb; include/tdnet.h "colour map out"): what does asking a frame
+"""GPU-box probe for the colour-map output (csrc/td_out.h k_picture_rows<false, TD_SRC_NONE, TD_DST_RGB>, before the byte ends were unified k_upsample_argmax_rgb; include/tdnet.h "colour map out"): what does asking a frame
 for its quarter-size picture instead of its uint8 label map change, on the device and in the frame loop?
 
   frame    device ms per steady-state frame (HIP events around `--frames` frames, no host work between them) of forward_labels_u8 against
            forward_rgb_u8: every launch but the last is the same, so the difference is the last kernel's (k_upsample_argmax_u8 against
-           k_upsample_argmax_rgb).  For the two kernels' own times run the probe under `rocprofv3 --kernel-trace --stats`.
+           the fused colour-map kernel).  For the two kernels' own times run the probe under `rocprofv3 --kernel-trace --stats`.
   loop     frames/s of the `tdnet_amd.test --prefetch --u8` loop -- prefetched uint8 upload, forward_labels_u8, asynchronous label download,
            nearest resize + decode_segmap on the host -- against the `--rgb` loop (forward_rgb_u8, picture download, nothing on the host),
            both without and with the PNG encoder (PIL, into memory) behind them.

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """GPU-box probe for source views (include/tdnet.h "source views"): do the existing byte paths pay for the new ones?
 
-Runs, through the test library's operator entries, the kernels an existing caller reaches -- k_ingest_u8 at 1024x2048 same-size, k_ingest_nv12
-at 1080x1920 -> 769x1537, k_upsample_argmax_overlay over a 1080x1920 packed-RGB source (network 769x1537, 19 classes) -- --iters times each (--forms existing), or
+Runs, through the test library's operator entries, the kernels an existing caller reaches -- the packed ingest (k_ingest<IngestPacked<3, false>>; a
+build from before the byte ends were unified: k_ingest_u8) at 1024x2048 same-size, the NV12 ingest (k_ingest<IngestYuv<false, YuvFormNv12>>; k_ingest_nv12)
+at 1080x1920 -> 769x1537, the fused overlay (k_picture_rows<false, TD_SRC_P24T, TD_DST_RGB>; k_upsample_argmax_overlay) over a 1080x1920 packed-RGB source (network 769x1537, 19 classes) -- --iters times each (--forms existing), or
 the new forms for the record (--forms new, a run of its own so that their launches do not land in the same kernel's statistics): a BGRA32 crop (60, 0, 960, 1920) and an NV12 crop at the odd origin
 (61, 1, 958, 1916) of a 1080x1920 frame -> 769x1537.  The ops allocate and synchronise: the times come from
 `rocprofv3 --kernel-trace --stats`, in runs of their own.  --lib PATH loads another build's test library (the parent commit's).
@@ -101,9 +102,14 @@ def kernel_means(run_dir):
         return {r["Name"]: (int(r["Calls"]), float(r["AverageNs"]) / 1000.0) for r in csv.DictReader(f)}
 
 
+# a family's kernels since the byte ends became k_ingest<Reader> / k_picture_rows<LABELS, SRC, DST>: a run of a parent build still shows the names on the left
+RENAMED = {"k_ingest_u8": "k_ingest<IngestPacked<", "k_ingest_nv12": "k_ingest<IngestYuv<false, YuvFormNv12>", "k_upsample_argmax_overlay": "k_picture_rows<false, 1, 0>"}   # TD_SRC_P24T into TD_DST_RGB: the one overlay form the probe times
+
+
 def family(stats, key):
-    """The one kernel of a family (the name up to its template list or argument list) a run launched."""
-    hits = [(k, v) for k, v in stats.items() if k.replace("void ", "").split("<")[0].split("(")[0] == key]
+    """The one kernel of a family (the name up to its template list or argument list, or the family's present name) a run launched."""
+    hits = [(k, v) for k, v in stats.items()
+            if k.replace("void ", "").split("<")[0].split("(")[0] == key or k.replace("void ", "").replace("> >", ">>").startswith(RENAMED[key])]
     assert len(hits) == 1, (key, [k for k, _ in hits])
     return hits[0]
 

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""GPU-box probe for surfaces (csrc/td_ingest.h k_ingest_surface, csrc/td_out.h k_picture_surface; include/tdnet.h "surfaces").
+"""GPU-box probe for surfaces (csrc/td_ingest.h k_ingest<IngestYuv<WIDE, YuvFormArgs>>, csrc/td_out.h k_picture_420<.., YuvFormArgs>; include/tdnet.h "surfaces";
+DESIGN.md 3.5 has the table of the names these kernels had before: k_ingest_surface, k_ingest_nv12, k_picture_surface, k_picture_nv12).
 
-  --mode ingest    per input layout, --iters launches of k_ingest_surface through tdnet_op_stem_image_surface (the packed-row stem image), and a check
+  --mode ingest    per input layout, --iters launches of the YUV ingest through tdnet_op_stem_image_surface (the packed-row stem image), and a check
                    that the buffer is the RGB-byte path's on the oracle's bytes.  The ops allocate and synchronise: run it under
                    `rocprofv3 --kernel-trace --stats`; the dispatches come in the order the probe prints, `--mode summarize` splits them per layout.
-                   --lib PATH loads another build's test library (the parent commit's): its k_ingest_nv12 on the NV12 surface only.
-  --mode picture   the same for the four destination layouts: the fused colour map of 19 classes into a whole surface (k_picture_surface; an NV12
-                   surface with one pitch is k_picture_nv12).  --lib PATH: the parent's k_picture_nv12 through tdnet_op_picture_view.
+                   --lib PATH loads another build's test library (the parent commit's): its NV12 ingest on the NV12 surface only.
+  --mode picture   the same for the four destination layouts: the fused colour map of 19 classes into a whole surface (k_picture_420 with YuvFormArgs; an NV12
+                   surface with one pitch takes YuvFormNv12).  --lib PATH: the parent's NV12 picture kernel through tdnet_op_picture_view.
   --mode frames    whole td4-psp18 frames per second, forward_labels_u8(surface=...) per layout against forward_labels_nv12, alternating on two
                    handles of one weight block: --rounds rounds of --frames frames each; median (min .. max).
   --mode summarize --trace kernel_trace.csv [--plan FILE]: average / minimum per group of --iters consecutive dispatches of the probed kernels.
@@ -66,7 +67,7 @@ def ingest(a, H, W, Hs, Ws):
         out = torch.empty(n, device="cuda")
         for _ in range(a.iters):
             lib.check(lib.tdnet_op_stem_image_nv12(d.data_ptr(), Hs, Ws, surf.row_pitch, surf.u_off, 1, H, W, None, None, 1, out.data_ptr(), n, s))
-        print("plan: k_ingest_nv12 x %d (%s), %dx%d -> %dx%d" % (a.iters, a.lib, Hs, Ws, H, W))
+        print("plan: NV12 ingest x %d (%s), %dx%d -> %dx%d" % (a.iters, a.lib, Hs, Ws, H, W))
         return
     lib = _capi.test_lib()
     n = lib.check(lib.tdnet_op_stem_image(None, None, 0, 0, H, W, None, None, 1, None, 0, None))
@@ -80,7 +81,7 @@ def ingest(a, H, W, Hs, Ws):
         for _ in range(a.iters):
             lib.check(lib.tdnet_op_stem_image_surface(d.data_ptr(), ctypes.byref(t), H, W, None, None, 1, on.data_ptr(), n, s))
         same = torch.equal(o8.view(torch.int32), on.view(torch.int32))
-        print("plan: k_ingest_surface x %d %s, %dx%d -> %dx%d: surface path == RGB-byte path: %s" % (a.iters, layout, Hs, Ws, H, W, same))
+        print("plan: YUV ingest x %d %s, %dx%d -> %dx%d: surface path == RGB-byte path: %s" % (a.iters, layout, Hs, Ws, H, W, same))
         assert same
 
 
@@ -102,7 +103,7 @@ def picture(a, H, W, Hs, Ws):
         dst = torch.zeros(Hs * Ws * 3 // 2, dtype=torch.uint8, device="cuda")
         for _ in range(a.iters):
             lib.check(lib.tdnet_op_picture_view(x.data_ptr(), C, h, w, H, W, None, pal.ctypes.data, 19, None, None, Hs, Ws, dst.data_ptr(), ctypes.byref(tv), s))
-        print("plan: k_picture_nv12 x %d (%s), colour map %dx%d" % (a.iters, a.lib, Hs, Ws))
+        print("plan: k_picture_420 (NV12 form) x %d (%s), colour map %dx%d" % (a.iters, a.lib, Hs, Ws))
         return
     lib = _capi.test_lib()
     for layout in DST_LAYOUTS:
@@ -111,7 +112,7 @@ def picture(a, H, W, Hs, Ws):
         dst = torch.zeros(surface_extent(surf), dtype=torch.uint8, device="cuda")
         for _ in range(a.iters):
             lib.check(lib.tdnet_op_picture_surface(x.data_ptr(), C, h, w, H, W, None, pal.ctypes.data, 19, None, None, None, Hs, Ws, dst.data_ptr(), ctypes.byref(t), None, s))
-        print("plan: %s x %d %s, colour map %dx%d" % ("k_picture_nv12" if layout == "nv12" else "k_picture_surface", a.iters, layout, Hs, Ws))
+        print("plan: %s x %d %s, colour map %dx%d" % ("k_picture_420 (NV12 form)" if layout == "nv12" else "k_picture_420", a.iters, layout, Hs, Ws))
 
 
 def frames(a, H, W, Hs, Ws):
@@ -159,7 +160,8 @@ def summarize(a):
     with open(a.trace) as f:
         for r in csv.DictReader(f):
             name = r.get("Kernel_Name", "")
-            if name.startswith(("k_ingest_surface", "k_ingest_nv12", "k_picture_surface", "k_picture_nv12", "void k_ingest_surface", "void k_picture_surface", "void k_picture_nv12")):
+            # the YUV ingest and the 4:2:0 picture kernels, under their present names and those of a build from before the byte ends were unified
+            if name.replace("void ", "").startswith(("k_ingest<IngestYuv<", "k_picture_420<", "k_ingest_surface", "k_ingest_nv12", "k_picture_surface", "k_picture_nv12")):
                 rows.append((int(r["Start_Timestamp"]), name, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0))
     rows.sort()
     plan = [l.strip()[6:] for l in open(a.plan) if l.startswith("plan: ")] if a.plan else []
