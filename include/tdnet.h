@@ -488,6 +488,65 @@ int  tdnet_forward_labels_conf(tdnet_t* h, const float* img_nchw_dev, int pos_id
 int  tdnet_forward_u8_labels_conf(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);
 /* the unfused form: labels and confidence of full-resolution NCHW logits [nclass,H,W] the caller already holds (v_c = those logits)      */
 int  tdnet_logits_conf(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);
+/* ---- matte out -----------------------------------------------------------------------------------------------------
+ * A SOFT mask of a class set -- "everything that moves" (Cityscapes train ids 11..18) in front of a mapping stage, "person + rider" for a
+ * background replacement, "road + sidewalk" as a drivable-area prior -- from the frame's LAST kernel, instead of 4 * nclass bytes of fp32
+ * logits per pixel and a softmax, a class sum and a rounding of the caller's.  For a pixel let v_c be the upsampled fp32 logit of class c (the
+ * label entries' expression, as in "confidence out"), l the first-maximum argmax and S the configured class set:
+ *   matte       den = sum_c exp(v_c - v_l),  num = sum_{c in S} exp(v_c - v_l), in fp32 with the maximum subtracted (logits of +-300 do not
+ *               overflow);  matte = (uint8) floor(255 num / den + 0.5).
+ *   exact       S = every class gives 255 at every pixel, S = the empty set gives 0 at every pixel, nclass = 1 with S = {0} gives 255: num and
+ *               den are accumulated by the same operations in the same order, so with every class a member they are the same float.
+ *   labels      the labels written beside the matte are the label entries' labels byte for byte, whatever the logits hold: there is no
+ *               rejection here.  For non-finite logits the matte byte is unspecified; the labels are not.
+ *   one byte    a pixel's byte does not depend on which lane or which geometry computed it.
+ *   layout      uint8 [H][W] at the network size, at any byte address, like the confidence map.
+ * tdnet_set_matte: plain host state of the handle -- no allocation, no synchronisation, no finalized weights needed (only cfg.nclass); per handle
+ * (a tdnet_create_shared handle has its own, unset at creation).  classes: n class ids on the HOST, duplicates are legal, n = 0 is the empty
+ * set.  Fails, changing nothing, on an id >= nclass, on n outside 0..256 and on NULL with n > 0.  The set travels to the kernels as ARGUMENTS
+ * (256 membership bits in eight 32-bit words) read when an entry enqueues: a captured hipGraph replays the set of capture time, as it does
+ * min_conf.  Nothing of it lives in device memory.                                                                                          */
+int  tdnet_set_matte(tdnet_t* h, const uint8_t* classes /* [n], host: class ids */, int n /* 0..256 */);
+/* tdnet_forward_labels / tdnet_forward_u8_labels with the other last launch: the matte is written, and the uint8 label map [H,W] too unless
+ * labels_dev is NULL.  The same frame, the same FIFO step, the same tdnet_last_launch_count.  They only enqueue and work inside a hipGraph
+ * capture.  Without a prior tdnet_set_matte they fail naming it and change nothing (a pending encoded frame stays pending).  Only
+ * [matte_dev, matte_dev + H W) is written, and [labels_dev, labels_dev + H W) when labels are given.                                         */
+int  tdnet_forward_matte(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* labels_dev /* | NULL */, uint8_t* matte_dev, void* stream);
+int  tdnet_forward_u8_matte(tdnet_t* h, const uint8_t* img_hwc_dev, int pos_id, uint8_t* labels_dev /* | NULL */, uint8_t* matte_dev, void* stream);
+/* the unfused form: labels and matte of full-resolution NCHW logits [nclass,H,W] the caller already holds (v_c = those logits)            */
+int  tdnet_logits_matte(tdnet_t* h, const float* logits_nchw_dev, uint8_t* labels_dev /* | NULL */, uint8_t* matte_dev, void* stream);
+/* The COMPOSITE: the source frame seen through the matte, at the SOURCE's size, written by the frame's last launch.
+ *   geometry   that of "overlay out": Hs x Ws = the source (rectangle's) size of the byte-input configuration in force (any of tdnet_set_input_u8 / _nv12 /
+ *              _view / _surface); source pixel (y, x) takes the matte byte M of network pixel (ys[y], xs[x]), ys = nearest_index(H, Hs),
+ *              xs = nearest_index(W, Ws) -- the very byte the matte entries write for that network pixel; s = the source pixel as "overlay out" /
+ *              "source views" / "surfaces" define it.
+ *   blend      per channel, in int32, A = M + (M >> 7) (0..255 -> 0..256).
+ *   mode 0     TDNET_COMPOSITE_COLOUR: out_c = (s_c A + bg_c (256 - A) + 128) >> 8 -- the overlay's blend with the source as the colour, M as its alpha
+ *              and bg underneath.  M = 255 gives s exactly, M = 0 gives bg exactly, nothing needs a clamp.  Into the contiguous [Hs][Ws][3] block, or
+ *              with a destination VIEW in force into a rectangle of a pitched RGB / BGR / RGBA / BGRA frame with the x byte 255.
+ *   mode 1     TDNET_COMPOSITE_ALPHA: the source pixel's colour bytes UNCHANGED and the x byte of a 32-bit destination view = M; a compositor then
+ *              blends over whatever it likes.  Requires an RGBA32 / BGRA32 destination view: the frame entry checks that and fails without
+ *              enqueueing, naming the destination it found.
+ *   colour     the rules of "overlay out" and "destination views", unchanged: the source's byte order into the contiguous block, the destination's
+ *              into a view.  bg_rgb is always true r, g, b.
+ *   4:2:0      destinations (tdnet_set_output_surface, or an NV12 view, in force) are refused by name: composite into 4:2:0 is not built.
+ *   memory     the overlay's contract: nothing outside the source extent is read, the result does not depend on padding or gaps, only the rectangle's
+ *              pixel bytes are written; out (or the destination frame's extent) must not overlap the source extent -- checked on the host before
+ *              anything is enqueued.
+ * tdnet_set_output_composite: configuration like tdnet_set_output_overlay (it may synchronise; idempotent for equal arguments; per handle; independent of
+ * the order of the other tdnet_set_* calls and of tdnet_set_output_overlay: a handle may have both).  It shares the overlay's index tables for the pair
+ * network size / source size: rebuilt when either changes, counted once in tdnet_memory_bytes.  Fails, leaving the previous configuration in force, on a
+ * handle that is not finalized, a mode outside 0..1, a NULL bg_rgb in mode 0 and a bg_rgb in mode 1.
+ * The frame entries are tdnet_forward_u8_labels with the other last launch: the same frame, FIFO step and tdnet_last_launch_count; they only enqueue and
+ * work inside a hipGraph capture.  They fail -- changing nothing, a pending encoded frame stays pending, the message naming the missing call or the
+ * field -- without tdnet_set_matte, tdnet_set_output_composite or a byte input, on a rectangle that is not the source's size, on the alpha mode without a
+ * 32-bit view, on a 4:2:0 destination and on overlap.  There is no fp32-image entry: an fp32 tensor has no source bytes.                       */
+#define TDNET_COMPOSITE_COLOUR 0
+#define TDNET_COMPOSITE_ALPHA  1
+int  tdnet_set_output_composite(tdnet_t* h, int mode, const uint8_t* bg_rgb /* [3], host; mode 0: required, mode 1: must be NULL */);
+int  tdnet_forward_u8_composite(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* out_dev, void* stream);
+/* the unfused form: from a matte map [H][W] the caller already holds (any byte address); needs no tdnet_set_matte */
+int  tdnet_matte_composite(tdnet_t* h, const uint8_t* matte_u8_dev, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -512,6 +571,9 @@ int  tdnet_propagate_rgb(tdnet_t* h, uint8_t* rgb_dev, void* stream);   /* see "
 int  tdnet_propagate_overlay(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 int  tdnet_propagate_score(tdnet_t* h, const uint8_t* gt_u8_dev, uint8_t* labels_u8_dev /* | NULL */, void* stream);   /* see "score out" */
 int  tdnet_propagate_labels_conf(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t* conf_dev, void* stream);   /* see "confidence out" */
+int  tdnet_propagate_matte(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t* matte_dev, void* stream);   /* see "matte out" */
+/* the split frame's composite: the caller passes the source again, as for tdnet_propagate_overlay; see "matte out" */
+int  tdnet_propagate_composite(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

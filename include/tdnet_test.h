@@ -186,6 +186,20 @@ int tdnet_op_upsample_argmax_score(const float* in_dev, int C, int h, int w, int
  * (tools/conf_probe.py); unset: the form the library's own entries launch.                                                               */
 int tdnet_op_upsample_argmax_conf(const float* in_dev, int C, int h, int w, int H, int W, uint8_t* labels_u8_dev, uint8_t* conf_u8_dev, int min_conf,
                                   int reject_label, const float* logits_full_dev, void* stream);
+/* labels_u8_dev [H,W] (or NULL) and matte_u8_dev [H,W] (include/tdnet.h "matte out"; any byte addresses) of low-resolution logits [C,h,w]
+ * upsampled to [H,W], through the last kernel of the matte frame entries (logits_full_dev == NULL), or of full-resolution logits [C,H,W] through
+ * the kernel of the unfused entry (logits_full_dev != NULL; in_dev, h, w are then ignored).  classes: n class ids below C on the HOST (n in
+ * 0..256, duplicates legal, NULL with n = 0); C in 1..256.                                                                                   */
+int tdnet_op_upsample_argmax_matte(const float* in_dev, int C, int h, int w, int H, int W, uint8_t* labels_u8_dev, uint8_t* matte_u8_dev, const uint8_t* classes,
+                                   int n, const float* logits_full_dev, void* stream);
+/* The composite of include/tdnet.h "matte out" through the kernels the composite entries launch: of low-resolution logits [C,h,w] and the class set
+ * classes[0 .. n) (matte_u8_dev == NULL) or of a matte map [H,W] (matte_u8_dev != NULL; in_dev, C, h, w, classes, n are then ignored), over the source at
+ * src_base read through src_surface (if not NULL) or src_view, into the contiguous block [Hs,Ws,3] at dst_base (dst_view == NULL) or into dst_view's
+ * rectangle of the pitched frame at dst_base.  mode: TDNET_COMPOSITE_COLOUR with bg_rgb [3] (host), or TDNET_COMPOSITE_ALPHA with bg_rgb NULL and a
+ * 32-bit dst_view.  Any byte addresses.                                                                                                       */
+int tdnet_op_composite(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8_dev, const uint8_t* src_base,
+                       const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* dst_base, const tdnet_view* dst_view, int mode, const uint8_t* bg_rgb,
+                       void* stream);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

@@ -117,6 +117,15 @@ SYMBOLS = {
     "tdnet_forward_u8_labels_conf": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "tdnet_propagate_labels_conf": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_logits_conf": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_matte": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int]),
+    "tdnet_forward_matte": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_forward_u8_matte": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_matte": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_logits_matte": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_output_composite": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
+    "tdnet_forward_u8_composite": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_propagate_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_matte_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -186,6 +195,8 @@ TEST_SYMBOLS = {
                                         c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_score": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
     "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_upsample_argmax_matte": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_composite": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, ctypes.c_int] + [c_void_p] * 6 + [ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_enc_first": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 4 + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 5),
     "tdnet_op_conv1x1_src2_null": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,

@@ -13,6 +13,7 @@
 //                  host side of its tables is at the end of this file), and the one class loop td_score.h and td_conf.h share with them
 //   td_score.h     (kernels) score out: the confusion matrix against ground truth; its host side is at the end of this file too
 //   td_conf.h      (kernels) confidence out: the softmax probability of the label as a byte, rejection of low-confidence labels
+//   td_matte.h     (kernels) matte out: the softmax mass of a class set as a byte
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -36,6 +37,7 @@
 #include "td_out.h"
 #include "td_score.h"
 #include "td_conf.h"
+#include "td_matte.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -302,6 +304,13 @@ struct DstOutput {
     int layout = 0, cpitch = 0;                                        // TDNET_SURF_* (NV12, NV21, I420, P010); bytes per chroma row
     size_t u_off = 0, v_off = 0;
 };
+// The composite output of a handle (tdnet_set_output_composite): the mode and the background.  Plain host state -- both travel as kernel arguments; the
+// index tables of the pair (network size, source size) are the overlay's (OverlayOutput ys / xs: overlay_tables builds them for either configuration).
+struct CompositeOutput {
+    bool set = false;
+    int mode = 0;                                                      // TDNET_COMPOSITE_COLOUR / TDNET_COMPOSITE_ALPHA
+    unsigned char bg[3] = {0, 0, 0};                                   // colour mode: true r, g, b
+};
 // The score output of a handle (tdnet_set_score): the device confusion matrix the score kernels add into and the 256-byte ground-truth map they
 // read.  Per handle, like U8Input.
 struct ScoreOutput {
@@ -404,6 +413,9 @@ struct tdnet {
     DstOutput dst;                                                     // tdnet_set_output_view
     ScoreOutput score;                                                // tdnet_set_score
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
+    CompositeOutput comp;                                              // tdnet_set_output_composite
+    bool matte_set = false;                                            // tdnet_set_matte: plain host state like min_conf; the *_matte entries pass the words as kernel arguments
+    MatteSet matte = {{0, 0, 0, 0, 0, 0, 0, 0}};                       // 256 membership bits: bit c & 31 of word c >> 5
     int launches = 0;                                                  // kernel launches + device copies enqueued by the current frame (td_launch.h TD_COUNTED)
 
     explicit tdnet(TdWeights* w)

@@ -416,7 +416,7 @@ static int run_classifier(tdnet* n, const float* x, int HW, int C, int NC, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// the output stage (td_out.h, td_score.h, td_conf.h): one launch function per output form on the raw sizes -- the tests' operator entries have no
+// the output stage (td_out.h, td_score.h, td_conf.h, td_matte.h): one launch function per output form on the raw sizes -- the tests' operator entries have no
 // handle -- and emit_output, the last launch of a frame, on top of them
 // ---------------------------------------------------------------------------------------------------------------
 static void launch_upsample(const float* in, int C, int h, int w, int H, int W, float* out, hipStream_t s) {
@@ -464,7 +464,7 @@ static int launch_argmax_u8(const float* logits, int C, long HW, unsigned char* 
     B(SURF8, YUV420, false, YuvFormArgs) B(SURF16, YUV420, false, YuvFormArgs) \
     B(NONE, YUV420, true, YuvFormArgs) B(P24, YUV420, true, YuvFormArgs) B(P32, YUV420, true, YuvFormArgs) B(NV12, YUV420, true, YuvFormArgs) \
     B(SURF8, YUV420, true, YuvFormArgs) B(SURF16, YUV420, true, YuvFormArgs)
-#define TD_PICTURE_KEY(src, dst, wide) (((src) * 8 + (dst)) * 2 + ((wide) ? 1 : 0))
+#define TD_PICTURE_KEY(src, dst, wide) (((src) * 8 + (dst)) * 2 + ((wide) ? 1 : 0))   // (launch_composite's own switch reuses the key with its third argument = the alpha mode)
 // a.labels != NULL: the label-map form.  src, l: the overlay's source (TD_SRC_NONE: unused).  wide: a 4:2:0 destination of 16-bit samples.
 static int launch_picture(const PicArgs& a, int src_form, const unsigned char* src, const SrcLayout& l, int dst_form, bool wide, const PicDst& d, hipStream_t s) {
     const bool labels = a.labels != nullptr;
@@ -601,28 +601,95 @@ static int launch_logits_conf_u8(const float* logits, int C, long HW, unsigned c
     else TD_LAUNCH((k_logits_conf_u8<false>), out_grid_run(HW), dim3(256), 0, s, logits, labels, conf, C, HW, min_conf, reject);
     return 0;
 }
+// matte out (td_matte.h): the label entries' last launch that also writes the softmax mass of the class set `set` as a byte per pixel (labels may
+// be NULL: matte only), and the unfused form on full-resolution logits the caller holds.  The set is a kernel argument: eight words by value.
+static int launch_upsample_argmax_matte_u8(const float* in, int C, int h, int w, int H, int W, unsigned char* labels, unsigned char* matte, const MatteSet& set,
+                                           hipStream_t s) {
+    TD_TRY(out_check("matte", "H", H, C));
+    TD_LAUNCH(k_upsample_argmax_matte_u8, out_grid(W, H), dim3(256), 0, s, in, labels, matte, C, h, w, H, W, set);
+    return 0;
+}
+static int launch_logits_matte_u8(const float* logits, int C, long HW, unsigned char* labels, unsigned char* matte, const MatteSet& set, hipStream_t s) {
+    TD_TRY(out_check("matte", "H", 1, C));
+    TD_LAUNCH(k_logits_matte_u8, out_grid_run(HW), dim3(256), 0, s, logits, labels, matte, C, HW, set);
+    return 0;
+}
+// The composite (td_matte.h k_composite_rows): the source frame through the matte at the source's size, from the low-resolution logits and the class
+// set (map == NULL) or from a matte map [H][W] the caller holds.  `o`: the index tables of the pair (network size, source size); `u`: the byte input `src`
+// is read by; `d`: the destination view in force, or one that is not set: the contiguous block [Hs][Ws][3] at `base`.
+// 40 instantiations: 5 source forms (a view of 3- / 4-byte pixels, an NV12 view, a surface of 8- / 16-bit samples: a tight whole frame is a view with
+// origin 0) x 4 destinations (the block, a 3-byte view, a 4-byte view, a 4-byte view with the matte as its x byte) x fused / from a map.
+#define TD_COMPOSITE_SRCS(X, DST, ALPHA) X(P24, DST, ALPHA) X(P32, DST, ALPHA) X(NV12, DST, ALPHA) X(SURF8, DST, ALPHA) X(SURF16, DST, ALPHA)
+#define TD_COMPOSITE_CELLS(X) TD_COMPOSITE_SRCS(X, RGB, false) TD_COMPOSITE_SRCS(X, P24, false) TD_COMPOSITE_SRCS(X, P32, false) TD_COMPOSITE_SRCS(X, P32, true)
+// What the destination in force must be for the composite of byte input `u` in mode c.mode: ONE set of checks and messages, for the frame entries (on the
+// host, before anything is enqueued: td_model.hip composite_args) and for the launch itself (the tests' operator entry has no handle).
+static int composite_dst_check(const U8Input& u, const CompositeOutput& c, const DstOutput& d, const char* who) {
+    static const char* const fmt[] = {"RGB24", "BGR24", "RGBA32", "BGRA32", "NV12"};
+    if (d.set && d.format == TDNET_PIX_NV12)
+        return td_fail("%s: the destination in force is %s: composite into 4:2:0 is not built (tdnet_set_output_view with a packed format, or NULL)", who,
+                       d.surf ? "a 4:2:0 surface (tdnet_set_output_surface)" : "an NV12 view");
+    if (c.mode == TDNET_COMPOSITE_ALPHA && !(d.set && d.bpp == 4))
+        return td_fail("%s: TDNET_COMPOSITE_ALPHA writes the matte as the x byte of an RGBA32 / BGRA32 destination view, but the destination in force is %s", who,
+                       d.set ? fmt[d.format] : "the contiguous [Hs][Ws][3] block (no tdnet_set_output_view)");
+    if (d.set && (u.Hs != d.h || u.Ws != d.w))
+        return td_fail("%s: the composite is %d x %d but the destination view's rectangle is %d x %d (tdnet_set_output_view: nothing is resized)", who, u.Hs, u.Ws, d.h, d.w);
+    return 0;
+}
+static int launch_composite(const float* in, int C, int h, int w, const unsigned char* map, const MatteSet& set, const OverlayOutput& o, const U8Input& u,
+                            const unsigned char* src, const CompositeOutput& c, const DstOutput& d, unsigned char* base, hipStream_t s) {
+    if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("composite: the index tables of this source size are missing (their allocation failed)");
+    TD_TRY(out_check("composite", "src_height", o.Hs, map ? 1 : C));
+    TD_TRY(composite_dst_check(u, c, d, "composite"));
+    const bool alpha = c.mode == TDNET_COMPOSITE_ALPHA;
+    CompArgs a = CompArgs();
+    a.in = in; a.map = map; a.ys = o.ys; a.xs = o.xs;
+    a.C = C; a.h = h; a.w = w; a.H = o.H; a.W = o.W; a.oh = o.Hs; a.ow = o.Ws;
+    a.bg = u.swap ? (unsigned)c.bg[2] | ((unsigned)c.bg[1] << 8) | ((unsigned)c.bg[0] << 16)      // the picture word's bytes are the source's: b g r
+                  : (unsigned)c.bg[0] | ((unsigned)c.bg[1] << 8) | ((unsigned)c.bg[2] << 16);
+    a.set = set;
+    PicDst pd = PicDst();
+    pd.base = base;
+    if (d.set) { pd.pitch = d.pitch; pd.oy = d.oy; pd.ox = d.ox; pd.swap = d.swap != u.swap; }
+    const int dst_form = !d.set ? TD_DST_RGB : d.bpp == 4 ? TD_DST_P32 : TD_DST_P24;
+    const int src_form = picture_src_form(u, false);
+    const SrcLayout l = src_layout(u);
+    const dim3 rows = out_grid(a.ow, a.oh);
+    switch (TD_PICTURE_KEY(src_form, dst_form, alpha)) {
+#define TD_C(SRC, DST, ALPHA) case TD_PICTURE_KEY(TD_SRC_##SRC, TD_DST_##DST, ALPHA): \
+        if (map) TD_LAUNCH((k_composite_rows<true, TD_SRC_##SRC, TD_DST_##DST, ALPHA>), rows, dim3(256), 0, s, a, src, l, pd); \
+        else TD_LAUNCH((k_composite_rows<false, TD_SRC_##SRC, TD_DST_##DST, ALPHA>), rows, dim3(256), 0, s, a, src, l, pd); \
+        return 0;
+    TD_COMPOSITE_CELLS(TD_C)
+#undef TD_C
+    }
+    return td_fail("internal: no composite kernel for source form %d into destination form %d", src_form, dst_form);
+}
 
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE };
 struct FrameOutput {
     OutKind kind;
-    void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF: may be NULL) | rgb [oh][ow][3] | overlay [Hs][Ws][3]
+    void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF, OUT_MATTE: may be NULL) | rgb [oh][ow][3] | overlay, composite [Hs][Ws][3]
                                    // (the two pictures with a destination view in force: the destination frame's base)
     const unsigned char* gt;       // OUT_SCORE: ground truth [H][W]
-    unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]
-    const unsigned char* src;      // OUT_OVERLAY: the source frame, read by the handle's byte-input configuration
+    unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]; OUT_MATTE: matte bytes [H][W]
+    const unsigned char* src;      // OUT_OVERLAY, OUT_COMPOSITE: the source frame, read by the handle's byte-input configuration
 };
 // the handle-side precondition of a form: its tables exist
 static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
     if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
+    if ((kind == OUT_MATTE || kind == OUT_COMPOSITE) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
+    if (kind == OUT_COMPOSITE && !n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
+    if (kind == OUT_COMPOSITE && !n->u8.set)
+        return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or one of its siblings first): the composite is written at its source size", who);
     if (kind == OUT_OVERLAY && !n->overlay.set) return td_fail("%s: the overlay output is not configured (call tdnet_set_output_overlay first)", who);
     if (kind == OUT_OVERLAY && !n->u8.set)
         return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or tdnet_set_input_nv12 first): the overlay is written at its source size", who);
     return 0;
 }
-// The last launch of a frame: the handle's low-resolution logits leave in the form `o`.  Confidence takes the threshold in force NOW (kernel
-// arguments: a captured graph replays the ones it was captured with).
+// The last launch of a frame: the handle's low-resolution logits leave in the form `o`.  Confidence takes the threshold, the matte the class set
+// in force NOW (kernel arguments: a captured graph replays the ones it was captured with).
 static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char* who) {
     TD_TRY(output_configured(n, o.kind, who));
     const float* in = n->lowres;
@@ -636,6 +703,8 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
         return launch_upsample_argmax_rgb(in, C, h, w, n->rgb, (unsigned char*)o.dst, s);
     case OUT_SCORE: return launch_upsample_argmax_score(in, C, h, w, H, W, o.gt, n->score.dmap, (unsigned char*)o.dst, n->score.cm, s);
     case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
+    case OUT_MATTE: return launch_upsample_argmax_matte_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->matte, s);
+    case OUT_COMPOSITE: return launch_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, (unsigned char*)o.dst, s);
     case OUT_OVERLAY:
         if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, nullptr, &n->overlay, &n->u8, o.src, n->dst, (unsigned char*)o.dst, s);
         return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);

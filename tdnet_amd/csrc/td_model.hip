@@ -288,7 +288,7 @@ extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_i
 // The overlay's index tables belong to the pair (network size, source size): a byte-input configuration that changed the source size rebuilds them
 // (the caller has synchronised: the previous tables existed only beside a previous input configuration).  Nothing to do without an overlay.
 static int overlay_follow_input(tdnet* n, const char* who) {
-    if (!n->overlay.set) return 0;
+    if (!n->overlay.set && !n->comp.set) return 0;                    // the composite samples through the same tables
     const size_t before = n->overlay.bytes;
     int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
     n->ws_bytes += n->overlay.bytes - before;
@@ -524,6 +524,96 @@ extern "C" int tdnet_logits_conf(tdnet_t* n, const float* logits, uint8_t* label
     TD_HIP(hipGetLastError());
     return 0;
 }
+// ---- matte out -------------------------------------------------------------------------------------------------------------------------
+// Plain host state of the handle (no allocation, no synchronisation, no weights needed: only cfg.nclass): the class set as 256 membership bits.  A
+// *_matte entry passes the words in force when it ENQUEUES its last launch (kernel arguments: a captured graph replays the set it was captured with).
+extern "C" int tdnet_set_matte(tdnet_t* n, const uint8_t* classes, int count) {
+    if (!n) return td_fail("tdnet_set_matte: null handle");
+    if (count < 0 || count > 256) return td_fail("tdnet_set_matte: n = %d must be in 0..256", count);
+    if (count > 0 && !classes) return td_fail("tdnet_set_matte: classes is NULL with n = %d", count);
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < count; ++i) {
+        if (classes[i] >= n->cfg.nclass) return td_fail("tdnet_set_matte: classes[%d] = %d is not a class id (nclass = %d)", i, (int)classes[i], n->cfg.nclass);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);              // duplicates are legal
+    }
+    n->matte = set;
+    n->matte_set = true;
+    return 0;
+}
+// The labels entries with another last launch: the matte beside (or, labels == NULL, instead of) the label map.  Same frame, same FIFO step, same
+// number of launches.
+extern "C" int tdnet_forward_matte(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, uint8_t* matte, void* stream) {
+    if (!n || !img || !matte) return td_fail("tdnet_forward_matte: null argument");
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_MATTE, labels, nullptr, matte}, stream, "tdnet_forward_matte");
+}
+extern "C" int tdnet_forward_u8_matte(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, uint8_t* matte, void* stream) {
+    if (!n || !img || !matte) return td_fail("tdnet_forward_u8_matte: null argument");
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_MATTE, labels, nullptr, matte}, stream, "tdnet_forward_u8_matte");
+}
+extern "C" int tdnet_logits_matte(tdnet_t* n, const float* logits, uint8_t* labels, uint8_t* matte, void* stream) {
+    if (!n || !logits || !matte) return td_fail("tdnet_logits_matte: null argument");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_logits_matte: weights not finalized");
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(output_configured(n, OUT_MATTE, "tdnet_logits_matte"));
+    TD_TRY(launch_logits_matte_u8(logits, n->cfg.nclass, (long)n->H * n->W, labels, matte, n->matte, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// Configuration of the composite output (not a frame call: it may synchronise; idempotent for equal arguments).  Mode and background are plain host state
+// (kernel arguments); the index tables are the overlay's, built here if the handle has a byte input, by the byte-input configuration otherwise.
+extern "C" int tdnet_set_output_composite(tdnet_t* n, int mode, const uint8_t* bg_rgb) {
+    const char* who = "tdnet_set_output_composite";
+    if (!n) return td_fail("%s: null handle", who);
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    if (mode != TDNET_COMPOSITE_COLOUR && mode != TDNET_COMPOSITE_ALPHA) return td_fail("%s: mode = %d must be 0 (TDNET_COMPOSITE_COLOUR) or 1 (TDNET_COMPOSITE_ALPHA)", who, mode);
+    if (mode == TDNET_COMPOSITE_COLOUR && !bg_rgb) return td_fail("%s: bg_rgb is NULL (the colour mode blends over a background)", who);
+    if (mode == TDNET_COMPOSITE_ALPHA && bg_rgb) return td_fail("%s: bg_rgb must be NULL in the alpha mode (nothing is blended)", who);
+    TD_ON_DEVICE(n, -1);
+    CompositeOutput c;
+    c.set = true; c.mode = mode;
+    if (bg_rgb) memcpy(c.bg, bg_rgb, 3);
+    if (n->u8.set) {
+        const size_t before = n->overlay.bytes;
+        const int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
+        n->ws_bytes += n->overlay.bytes - before;
+        TD_TRY(rc);
+    }
+    n->comp = c;
+    return 0;
+}
+// What every composite entry checks on the host before anything is enqueued: the configurations exist, the destination in force can take this mode, and
+// `out` (or the destination frame's extent) does not overlap the source extent -- the kernel reads the source while it writes the picture.
+static int composite_args(const tdnet* n, bool fused, const uint8_t* src, const uint8_t* out, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    if (fused) TD_TRY(output_configured(n, OUT_COMPOSITE, who));
+    else {
+        if (!n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
+        if (!n->u8.set) return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or one of its siblings first): the composite is written at its source size", who);
+    }
+    const U8Input& u = n->u8;
+    const DstOutput& d = n->dst;
+    TD_TRY(composite_dst_check(u, n->comp, d, who));
+    const size_t nout = d.set ? d.extent : (size_t)3 * u.Hs * u.Ws, nsrc = u.extent;
+    const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+    if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
+    return 0;
+}
+// The labels entries with another last launch: the composite instead of the label map; the image pointer is the frame's image (first launch) AND the
+// composite's source (last launch).  Same frame, same FIFO step, same number of launches.
+extern "C" int tdnet_forward_u8_composite(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_forward_u8_composite: null argument");
+    TD_TRY(composite_args(n, true, img, out, "tdnet_forward_u8_composite"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_COMPOSITE, out, nullptr, nullptr, img}, stream, "tdnet_forward_u8_composite");
+}
+// the unfused form: from a matte map [H][W] the caller holds; needs no class set
+extern "C" int tdnet_matte_composite(tdnet_t* n, const uint8_t* matte, const uint8_t* img, uint8_t* out, void* stream) {
+    if (!n || !matte || !img || !out) return td_fail("tdnet_matte_composite: null argument");
+    TD_TRY(composite_args(n, false, img, out, "tdnet_matte_composite"));
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(launch_composite(nullptr, 0, 0, 0, matte, n->matte, n->overlay, n->u8, img, n->comp, n->dst, out, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
 // ---- split frame + cache transport (path-parallel single stream) ------------------------------------
 // Rank g of a path-parallel group serves the frames t = g (mod W): it encodes its frame as soon as the image is there, publishes
 // the resulting cache entry, receives the entries of the frames in between from its peers (in frame order) and only then
@@ -591,6 +681,16 @@ extern "C" int tdnet_propagate_labels_conf(tdnet_t* n, uint8_t* labels, uint8_t*
     if (!n || !conf) return td_fail("tdnet_propagate_labels_conf: null argument");
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_labels_conf: weights not finalized");   // (its siblings leave this to "no encoded frame")
     return frame_out(n, pending_frame, FrameOutput{OUT_CONF, labels, nullptr, conf}, stream, "tdnet_propagate_labels_conf");
+}
+extern "C" int tdnet_propagate_matte(tdnet_t* n, uint8_t* labels, uint8_t* matte, void* stream) {
+    if (!n || !matte) return td_fail("tdnet_propagate_matte: null argument");
+    if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_matte: weights not finalized");
+    return frame_out(n, pending_frame, FrameOutput{OUT_MATTE, labels, nullptr, matte}, stream, "tdnet_propagate_matte");
+}
+extern "C" int tdnet_propagate_composite(tdnet_t* n, const uint8_t* img, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_propagate_composite: null argument");
+    TD_TRY(composite_args(n, true, img, out, "tdnet_propagate_composite"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_COMPOSITE, out, nullptr, nullptr, img}, stream, "tdnet_propagate_composite");
 }
 extern "C" int tdnet_cache_dims(const tdnet_t* n, int* Lk, int* dk, int* dv) {
     if (!n) return td_fail("tdnet_cache_dims: null handle");

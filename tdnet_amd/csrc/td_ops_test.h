@@ -718,6 +718,63 @@ extern "C" int tdnet_op_upsample_argmax_conf(const float* in, int C, int h, int 
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_conf: device error");
     return rc;
 }
+// Labels (labels_u8 != NULL) and matte bytes [H][W] of low-resolution logits [C][h][w] (logits_full == NULL: k_upsample_argmax_matte_u8) or of
+// full-resolution logits [C][H][W] (logits_full != NULL: k_logits_matte_u8; in, h, w are ignored), for the class set classes[0 .. n) (host).
+extern "C" int tdnet_op_upsample_argmax_matte(const float* in, int C, int h, int w, int H, int W, uint8_t* labels_u8, uint8_t* matte_u8, const uint8_t* classes, int n,
+                                              const float* logits_full, void* stream) {
+    if (!matte_u8) return td_fail("tdnet_op_upsample_argmax_matte: a matte map expected");
+    if (C < 1 || C > 256 || H < 1 || W < 1) return td_fail("tdnet_op_upsample_argmax_matte: C in 1..256 and a size >= 1 x 1 expected");
+    if (n < 0 || n > 256 || (n > 0 && !classes)) return td_fail("tdnet_op_upsample_argmax_matte: n in 0..256 class ids expected");
+    if (!logits_full && (!in || h < 1 || w < 1)) return td_fail("tdnet_op_upsample_argmax_matte: logits [C,h,w] expected");
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < n; ++i) {
+        if (classes[i] >= C) return td_fail("tdnet_op_upsample_argmax_matte: classes[%d] = %d is not a class id (C = %d)", i, (int)classes[i], C);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc = logits_full ? launch_logits_matte_u8(logits_full, C, (long)H * W, labels_u8, matte_u8, set, s)
+                         : launch_upsample_argmax_matte_u8(in, C, h, w, H, W, labels_u8, matte_u8, set, s);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("tdnet_op_upsample_argmax_matte: device error");
+    return rc;
+}
+// The composite (include/tdnet.h "matte out") through exactly the kernels the composite entries launch: of low-resolution logits [C][h][w] and the class
+// set classes[0 .. n) (matte_u8 == NULL) or of a matte map [H][W] (in, C, h, w, classes, n are then ignored), over the source src_base read through
+// src_surface or src_view, into the contiguous block [Hs][Ws][3] at dst_base (dst_view == NULL) or into dst_view's rectangle of the frame at dst_base.
+extern "C" int tdnet_op_composite(const float* in, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8, const uint8_t* src_base,
+                                  const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* dst_base, const tdnet_view* dst_view, int mode,
+                                  const uint8_t* bg_rgb, void* stream) {
+    const char* who = "tdnet_op_composite";
+    if (!src_base || !dst_base || (!src_view && !src_surface)) return td_fail("%s: src_base, dst_base and src_view or src_surface expected", who);
+    if (H < 1 || W < 1) return td_fail("%s: a network size >= 1 x 1 expected", who);
+    if (!matte_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    if (!matte_u8 && (n < 0 || n > 256 || (n > 0 && !classes))) return td_fail("%s: n in 0..256 class ids expected", who);
+    if (mode != TDNET_COMPOSITE_COLOUR && mode != TDNET_COMPOSITE_ALPHA) return td_fail("%s: mode = %d must be 0 or 1", who, mode);
+    if ((mode == TDNET_COMPOSITE_COLOUR) != (bg_rgb != nullptr)) return td_fail("%s: bg_rgb expected in mode 0 and only there", who);
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; !matte_u8 && i < n; ++i) {
+        if (classes[i] >= C) return td_fail("%s: classes[%d] = %d is not a class id (C = %d)", who, i, (int)classes[i], C);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DstOutput d;
+    if (dst_view) TD_TRY(dst_build(d, dst_view, who));
+    CompositeOutput c;
+    c.set = true; c.mode = mode;
+    if (bg_rgb) memcpy(c.bg, bg_rgb, 3);
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(src_surface ? surface_resolve(src_surface, sv, Hs, Ws, who) : view_resolve(src_view, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    int rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) rc = launch_composite(in, C, h, w, matte_u8, set, o, u, src_base, c, d, dst_base, s);
+    if (rc) { const std::string msg = g_err; rc = td_fail("%s: %s", who, msg.c_str()); }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
 // The index table the colour-map kernels sample through (rgb_build's: dataloader.nearest_index restated in C) -> out_host [n_dst] int32.  Host only.
 extern "C" int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host) {
     if (n_src < 1 || n_dst < 1 || !out_host) return td_fail("tdnet_op_nearest_index: sizes >= 1 and a host buffer expected");

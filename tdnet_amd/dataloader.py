@@ -526,6 +526,44 @@ def overlay_u8(src_rgb_u8, labels, palette_rgba):
     return out.astype(np.uint8)
 
 
+def matte_u8(full_logits, classes):
+    """The oracle of the library's matte output (include/tdnet.h "matte out"): uint8 [H, W].  full_logits [C, H, W] are the full-resolution
+    logits, classes the ids of the set (duplicates are legal, an empty list is the empty set).  In float64, the maximum subtracted:
+        matte = floor(255 * sum_{c in S} exp(v_c - max) / sum_c exp(v_c - max) + 0.5)
+    Every class gives 255 and the empty set 0, exactly.  The library evaluates the same in fp32: it may differ by 1 where 255 num / den is within
+    rounding of a half (tests/matte_cases.py has the gate)."""
+    v = np.asarray(full_logits, dtype=np.float64)
+    assert v.ndim == 3
+    member = np.zeros(v.shape[0], bool)
+    ids = np.asarray(list(classes), dtype=np.int64)
+    assert ids.size == 0 or (ids.min() >= 0 and ids.max() < v.shape[0]), "class ids must be below %d" % v.shape[0]
+    member[ids] = True
+    e = np.exp(v - v.max(axis=0, keepdims=True))
+    t = 255.0 * (e[member].sum(axis=0) / e.sum(axis=0))
+    return np.floor(t + 0.5).astype(np.uint8)
+
+
+def composite_u8(src_rgb, matte, H, W, bg=None):
+    """The oracle of the library's composite (include/tdnet.h "matte out"): src_rgb [Hs, Ws, 3] is the frame at its own size, matte [H, W] the
+    matte bytes at the network size.  Source pixel (y, x) takes M = matte[nearest_index(H, Hs)[y], nearest_index(W, Ws)[x]].
+    bg = (r, g, b): uint8 [Hs, Ws, 3], per channel in int32
+        A = M + (M >> 7);  out = (s * A + bg * (256 - A) + 128) >> 8
+    so M = 255 returns the source byte and M = 0 the background's, exactly.  bg = None (the alpha mode): uint8 [Hs, Ws, 4], the source's three
+    bytes unchanged and M as the fourth."""
+    src, m = np.asarray(src_rgb), np.asarray(matte)
+    assert src.dtype == np.uint8 and src.ndim == 3 and src.shape[2] == 3 and m.dtype == np.uint8 and m.shape == (H, W)
+    Hs, Ws = src.shape[:2]
+    M = m[nearest_index(H, Hs)][:, nearest_index(W, Ws)].astype(np.int32)
+    if bg is None:
+        return np.concatenate([src, M.astype(np.uint8)[..., None]], axis=2)
+    b = np.asarray(bg, dtype=np.int32)
+    assert b.shape == (3,) and b.min() >= 0 and b.max() <= 255
+    A = (M + (M >> 7))[..., None]
+    out = (src.astype(np.int32) * A + b * (256 - A) + 128) >> 8
+    assert out.min() >= 0 and out.max() <= 255
+    return out.astype(np.uint8)
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],

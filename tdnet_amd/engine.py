@@ -316,6 +316,49 @@ class Engine:
     def logits_conf(self, logits_ptr, labels_ptr, conf_ptr, stream=None):
         self.lib.check(self.lib.tdnet_logits_conf(self.h, _ptr(logits_ptr), _ptr(labels_ptr), _ptr(conf_ptr), stream))
 
+    # ---- matte out (include/tdnet.h) ----
+    def set_matte(self, classes):
+        """The *_matte entries will write the softmax mass of this class set (ids below nclass; duplicates are legal, an empty list is the empty
+        set) as a byte per pixel.  Plain host state of this handle: no allocation, no synchronisation."""
+        ids = [int(c) for c in classes]
+        if len(ids) > 256 or any(c < 0 or c > 255 for c in ids):
+            raise _capi.TdnetError("set_matte: at most 256 class ids in 0..255")
+        buf = (ctypes.c_uint8 * max(1, len(ids)))(*ids)
+        self.lib.check(self.lib.tdnet_set_matte(self.h, buf if ids else None, len(ids)))
+
+    def forward_matte(self, img_ptr, pos_id, labels_ptr, matte_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_matte(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(matte_ptr), stream))
+
+    def forward_u8_matte(self, img_ptr, pos_id, labels_ptr, matte_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_matte(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(matte_ptr), stream))
+
+    def propagate_matte(self, labels_ptr, matte_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_matte(self.h, _ptr(labels_ptr), _ptr(matte_ptr), stream))
+
+    def logits_matte(self, logits_ptr, labels_ptr, matte_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_logits_matte(self.h, _ptr(logits_ptr), _ptr(labels_ptr), _ptr(matte_ptr), stream))
+
+    def set_output_composite(self, background=None):
+        """Frames may be asked for as the composite (include/tdnet.h "matte out"): the source frame through the matte at the source's size.
+        background (r, g, b): the colour mode, blended over it; None: the alpha mode -- the source's colour bytes and the matte as the x byte of a
+        32-bit destination view (set_output_view).  A configuration call; before or after the byte-input configuration."""
+        if background is None:
+            self.lib.check(self.lib.tdnet_set_output_composite(self.h, 1, None))
+            return
+        bg = [int(v) for v in background]
+        if len(bg) != 3 or any(v < 0 or v > 255 for v in bg):
+            raise _capi.TdnetError("set_output_composite: the background is three byte values r, g, b")
+        self.lib.check(self.lib.tdnet_set_output_composite(self.h, 0, (ctypes.c_uint8 * 3)(*bg)))
+
+    def forward_u8_composite(self, img_ptr, pos_id, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_composite(self.h, _ptr(img_ptr), int(pos_id), _ptr(out_ptr), stream))
+
+    def propagate_composite(self, img_ptr, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_composite(self.h, _ptr(img_ptr), _ptr(out_ptr), stream))
+
+    def matte_composite(self, matte_ptr, img_ptr, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_matte_composite(self.h, _ptr(matte_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

@@ -933,6 +933,121 @@ class _TDNetBase(nn.Module):
             self._engine.logits_conf(logits[i].data_ptr(), out[i].data_ptr(), conf[i].data_ptr(), s)
         return out, conf
 
+    # ---- matte out (not in the reference's model; a caller of the reference runs softmax, a class sum, a resize and a blend over the logits) ----
+    # The frame's last kernel writes, per pixel, the softmax mass of a class set as a byte (255 = certainly one of them; include/tdnet.h
+    # "matte out"), or the source frame composited by it at the source's size.
+    _matte = None
+
+    def set_matte(self, classes):
+        """The class set of the *_matte / *_composite methods: an iterable of class ids below nclass (duplicates are legal, empty = the empty
+        set).  Applies to every handle of a batch, the ones created later included.  Returns the sorted ids."""
+        try:
+            ids = [c for c in classes]
+        except TypeError:
+            raise RuntimeError("set_matte(): classes must be an iterable of class ids, got %r" % (classes,))
+        for c in ids:
+            try:
+                ok = not isinstance(c, bool) and int(c) == c and 0 <= int(c) < self.nclass
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise RuntimeError("set_matte(): %r is not a class id (0..%d)" % (c, self.nclass - 1))
+        self._matte = tuple(sorted(set(int(c) for c in ids)))
+        return self._matte
+
+    def _need_matte(self, who):
+        if self._matte is None:
+            raise RuntimeError("%s(): no class set (call set_matte(classes) first)" % who)
+        return self._matte
+
+    def forward_matte(self, img, pos_id=0):
+        """forward_labels() with the matte: (labels uint8 [N, H, W], matte uint8 [N, H, W])."""
+        ids = self._need_matte("forward_matte")
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        shape = (img.shape[0], img.shape[2], img.shape[3])
+        out, matte = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_matte(ids)
+            eng.forward_matte(img[i].data_ptr(), pos_id, out[i].data_ptr(), matte[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out, matte
+
+    def forward_matte_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
+        """forward_labels_u8() with the matte: bytes in, (labels uint8 [N, H, W], matte uint8 [N, H, W]) out."""
+        ids = self._need_matte("forward_matte_u8")
+        view = self._one_of(view, surface, "view", "surface")
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        img = img_u8.contiguous()
+        shape = (img.shape[0], H, W)
+        out, matte = torch.empty(shape, device=img.device, dtype=torch.uint8), torch.empty(shape, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_matte(ids)
+            eng.forward_u8_matte(img[i].data_ptr(), pos_id, out[i].data_ptr(), matte[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out, matte
+
+    def logits_matte(self, logits):
+        """The unfused form: logits [N, nclass, H, W] (fp32, CUDA) of this model -> (labels uint8 [N, H, W], matte uint8 [N, H, W])."""
+        ids = self._need_matte("logits_matte")
+        if self._engine is None:
+            raise RuntimeError("logits_matte(): no handle yet")
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(logits) or logits.dim() != 4 or tuple(logits.shape[1:]) != (self.nclass, H, W):
+            raise RuntimeError("logits_matte(): expected logits [N, %d, %d, %d]" % (self.nclass, H, W))
+        logits = logits.contiguous().float()
+        shape = (logits.shape[0], H, W)
+        out, matte = torch.empty(shape, device=logits.device, dtype=torch.uint8), torch.empty(shape, device=logits.device, dtype=torch.uint8)
+        s = torch.cuda.current_stream(logits.device).cuda_stream
+        self._engine.set_matte(ids)
+        for i in range(logits.shape[0]):
+            self._engine.logits_matte(logits[i].data_ptr(), out[i].data_ptr(), matte[i].data_ptr(), s)
+        return out, matte
+
+    @staticmethod
+    def _background(background):
+        if background is None:
+            return None
+        try:
+            bg = tuple(int(v) for v in background)
+        except (TypeError, ValueError):
+            bg = ()
+        if len(bg) != 3 or any(v < 0 or v > 255 for v in bg) or any(int(v) != v for v in background):
+            raise RuntimeError("background must be three byte values (r, g, b) or None (the alpha mode), got %r" % (background,))
+        return bg
+
+    def forward_composite_u8(self, img_u8, pos_id, in_size, background=(0, 0, 0), mean=None, std=None, view=None, out_view=None, out=None, surface=None):
+        """forward_labels_u8() with the composite in place of the label map: the frame's bytes in, the frame through the matte of set_matte()'s
+        class set out -- blended over background (r, g, b) -> uint8 [N, Hs, Ws, 3] (out_view: see _dst_out), or with background=None the source's
+        colour bytes and the matte as the x byte of a 32-bit out_view (required then)."""
+        ids = self._need_matte("forward_composite_u8")
+        bg = self._background(background)
+        view = self._one_of(view, surface, "view", "surface")
+        if bg is None and (out_view is None or getattr(out_view, "bpp", 0) != 4):
+            raise RuntimeError("forward_composite_u8(background=None): the alpha mode needs a 32-bit out_view (RGBA32 / BGRA32)")
+        if out_view is not None and getattr(out_view, "nv12", True):
+            raise RuntimeError("forward_composite_u8(): composite into 4:2:0 is not built; out_view must be a packed dataloader.SourceView")
+        if view is not None:
+            self._check_frame_view(img_u8, view)
+        if out_view is not None and torch.is_tensor(img_u8) and (view is not None or img_u8.dim() == 4):
+            self._dst_check(out_view, out, tuple(view.size) if view is not None else tuple(img_u8.shape[1:3]), img_u8.shape[0])
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        img = img_u8.contiguous()
+        if out_view is not None:
+            out = self._dst_out(out_view, out, tuple(view.size) if view is not None else (int(img.shape[1]), int(img.shape[2])), img.shape[0], img.device)
+        else:
+            out = torch.empty(tuple(img.shape) if view is None else (img.shape[0],) + tuple(view.size) + (3,), device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_matte(ids)
+            eng.set_output_composite(bg)
+            self._set_out(eng, out_view)
+            eng.forward_u8_composite(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out
+
     # ---- split frame + cache transport (path-parallel single stream: parallel.PathParallelStream) ------------------
     def encode(self, img, pos_id=0):
         """First half of forward(): backbone + pyramid slice + Encoding; the frame's cache entry is left pending."""
@@ -945,16 +1060,48 @@ class _TDNetBase(nn.Module):
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
     def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None, conf=False, src=None, alpha=0.5, src_size=None,
-                  uv_offset=None, standard=0):
+                  uv_offset=None, standard=0, matte=False, composite=False, background=(0, 0, 0)):
         """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
         uint8 labels (labels="u8"), the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb) or, with
         labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score).
         conf=True: (uint8 labels, uint8 confidence), both [1, H, W], as forward_labels_conf gives them (labels must be left False, True or "u8").
         labels="overlay" with src = the frame that was encoded (uint8 [1, Hs, Ws, 3], or with src_size=(Hs, Ws) the NV12 surface [1, rows, pitch]):
         the overlay [1, Hs, Ws, 3] as forward_overlay_u8 / forward_overlay_nv12 give it (palette, alpha as there); the source is passed again
-        because the library does not remember pointers across calls."""
+        because the library does not remember pointers across calls.
+        matte=True: (uint8 labels, uint8 matte), both [1, H, W], as forward_matte gives them.  composite=True with src = the packed RGB frame that
+        was encoded (uint8 [1, Hs, Ws, 3]): the composite [1, Hs, Ws, 3] over `background` as forward_composite_u8 gives it -- into the contiguous block: like
+        every picture method called without out_view it sets the handle's destination view to none (the model classes name the destination per call; a
+        view set on the engine by hand does not survive it)."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
+        if matte or composite:
+            who = "propagate(matte=True)" if matte else "propagate(composite=True)"
+            if (matte and composite) or conf or labels in ("rgb", "score", "overlay"):
+                raise RuntimeError("%s: asks for one last kernel; conf, another of matte / composite or labels=%r ask for another" % (who, labels))
+            ids = self._need_matte("propagate")
+            H, W, dev = self._pending_shape
+            s = torch.cuda.current_stream(dev).cuda_stream
+            if matte:
+                out, mm = torch.empty((1, H, W), device=dev, dtype=torch.uint8), torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+                self._engine.set_matte(ids)
+                self._pending_shape = None
+                self._engine.propagate_matte(out.data_ptr(), mm.data_ptr(), s)
+                return out, mm
+            bg = self._background(background)
+            if bg is None:
+                raise RuntimeError("propagate(composite=True): the alpha mode needs a destination view; use forward_composite_u8(out_view=...)")
+            key = getattr(self._engine, "_u8_key", None)
+            if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() != 4 or src.shape[0] != 1 or src.shape[3] != 3 or key is None or \
+                    tuple(src.shape[1:3]) != tuple(key[:2]) or src.device != dev:
+                raise RuntimeError("propagate(composite=True): src must be the packed RGB frame that was encoded with encode_u8, uint8 [1, Hs, Ws, 3] on %s" % (dev,))
+            img = src.contiguous()
+            out = torch.empty(tuple(img.shape), device=dev, dtype=torch.uint8)
+            self._engine.set_matte(ids)
+            self._engine.set_output_composite(bg)
+            self._engine.set_output_view(None)
+            self._pending_shape = None
+            self._engine.propagate_composite(img.data_ptr(), out.data_ptr(), s)
+            return out
         if conf:
             if labels in ("rgb", "score", "overlay"):
                 raise RuntimeError("propagate(conf=True): gives uint8 labels and confidence; labels=%r asks for another last kernel" % (labels,))

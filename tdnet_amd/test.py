@@ -29,6 +29,10 @@ SOURCE-size picture instead of the quarter-size colour map (include/tdnet.h "ove
 `--nv12_standard` 0..3) and feeds the surfaces (include/tdnet.h "surfaces"); it combines with what `--nv12` combines with, `--crop` included.
 `--out_yuv LAYOUT:FILE` is `--out_nv12`'s sibling for the destination layouts nv12, nv21, i420 and p010: the device writes every frame's picture through a
 destination surface, appended to the raw file.
+`--matte IDS` (a comma list of class ids, e.g. 11,12,13,14,15,16,17,18) with `--matte_out DIR` has the frame's last kernel also write the matte -- the
+softmax mass of that class set as a byte, 255 = certainly one of them (include/tdnet.h "matte out") -- and saves it at the network size as an 8-bit
+grey PNG DIR/folder/name beside the usual picture.  `--matte IDS --composite R,G,B` (with `--u8`, `--nv12` or `--yuv`) writes, where the overlay's
+picture would go, the frame seen through the matte over that background, at the frame's own (`--crop`: the rectangle's) size.
 """
 import argparse
 import os
@@ -105,6 +109,32 @@ def test(args):
             raise SystemExit("--overlay, --rgb and --gt_path ask for different last kernels: choose one")
         if not 0.0 <= overlay <= 1.0:
             raise SystemExit("--overlay: an opacity in 0..1 expected, got %r" % (overlay,))
+    matte_ids, matte_dir, composite = getattr(args, "matte", None), getattr(args, "matte_out", None), getattr(args, "composite", None)
+    if matte_ids is not None or matte_dir is not None or composite is not None:   # checked before anything is loaded
+        if matte_ids is None:
+            raise SystemExit("--matte_out and --composite need the class set: give --matte IDS (a comma list of class ids) with them")
+        try:
+            matte_ids = tuple(int(v) for v in str(matte_ids).split(",") if v.strip() != "")
+        except ValueError:
+            matte_ids = (-1,)
+        if any(c < 0 or c >= 19 for c in matte_ids):
+            raise SystemExit("--matte: a comma list of class ids in 0..18 expected, got %r" % (args.matte,))
+        if (matte_dir is None) == (composite is None):
+            raise SystemExit("--matte selects the frame's last kernel: give --matte_out DIR (the matte as a PNG) or --composite R,G,B (the frame through it), one of them")
+        if rgb or overlay is not None or getattr(args, "gt_path", None) or getattr(args, "prefetch", False) or getattr(args, "conf", None) is not None or \
+                getattr(args, "min_conf", None) is not None or getattr(args, "out_nv12", None) is not None or getattr(args, "out_yuv", None) is not None:
+            raise SystemExit("--matte asks for a last kernel of its own in the frame-by-frame loop: not with --rgb, --overlay, --gt_path, --prefetch, --conf, --min_conf, "
+                             "--out_nv12 or --out_yuv")
+        if composite is not None:
+            if not bytes_in:
+                raise SystemExit("--composite cuts the frame's own bytes out: give --u8, --nv12 or --yuv with it (an fp32 tensor has no source bytes)")
+            try:
+                composite = tuple(int(v) for v in str(composite).split(","))
+            except ValueError:
+                composite = ()
+            if len(composite) != 3 or any(v < 0 or v > 255 for v in composite):
+                raise SystemExit("--composite: R,G,B expected (the background, three byte values), got %r" % (args.composite,))
+    with_matte = matte_ids is not None
     out_nv12, out_yuv = getattr(args, "out_nv12", None), getattr(args, "out_yuv", None)
     out_layout = None
     if out_yuv is not None:                                            # LAYOUT:FILE; checked before anything is loaded
@@ -165,6 +195,9 @@ def test(args):
             raise SystemExit("--min_conf: a probability in 0..1 expected, got %r" % (min_conf,))
         model.set_confidence(min_conf or 0.0, 255)
 
+    if with_matte:
+        model.set_matte(matte_ids)
+
     def print_scores():                                                # Training/validate.py:91-97
         if gts is None:
             return
@@ -195,6 +228,12 @@ def test(args):
             from PIL import Image
             Image.fromarray(np.squeeze(conf, axis=0)).save(os.path.join(conf_dir, folder, img_name))
 
+    def save_matte(pred, matte, img_name, folder, ori_size):           # --matte_out: the usual picture of the uint8 labels, and the matte at the network size
+        save(pred, img_name, folder, ori_size)
+        os.makedirs(os.path.join(matte_dir, folder), exist_ok=True)
+        from PIL import Image
+        Image.fromarray(np.squeeze(matte, axis=0)).save(os.path.join(matte_dir, folder, img_name))
+
     def save_rgb(picture, img_name, folder, ori_size):                 # --rgb: the device wrote the picture
         write_png(np.squeeze(picture, axis=0), img_name, folder)
 
@@ -210,8 +249,9 @@ def test(args):
             v = SourceView(PIX_RGB24, int(image.shape[1]), int(image.shape[2]), crop=crop)
         return image.reshape(1, -1), v
 
-    nvp, byte = nv12 and crop is None, u8 or crop is not None or yuv is not None   # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
-    described = crop is not None or yuv is not None                    # the frame goes up WHOLE with a description: a source view, or (--yuv) a surface
+    as_view = crop is not None or (nv12 and with_matte)                # --matte: an NV12 surface goes through the byte methods as the whole NV12 view (through_view with no crop)
+    nvp, byte = nv12 and not as_view, u8 or as_view or yuv is not None   # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
+    described = as_view or yuv is not None                             # the frame goes up WHOLE with a description: a source view, or (--yuv) a surface
 
     def vk(v):
         return {"surface": v} if yuv is not None else {"view": v}
@@ -316,6 +356,10 @@ def test(args):
                 l8 = model.forward_labels_nv12(image, i % path_num, src_size, (H, W), standard=nv12_std) if nvp else \
                     model.forward_labels_u8(image, i % path_num, (H, W), **vk(view))
                 output = pictures_nv12(l8, image, ori_size, src_size, view, folder)
+            elif composite is not None:
+                output = model.forward_composite_u8(image, i % path_num, (H, W), background=composite, **vk(view))
+            elif with_matte:
+                output, matte = model.forward_matte_u8(image, i % path_num, (H, W), **vk(view)) if byte else model.forward_matte(image, i % path_num)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size, view)
             elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
@@ -340,7 +384,9 @@ def test(args):
                 timer += elapsed_time
             if gt is not None:
                 save(output.cpu().numpy(), img_name, folder, ori_size)
-            elif rgb or overlay is not None:
+            elif with_matte and composite is None:
+                save_matte(output.cpu().numpy(), matte.cpu().numpy(), img_name, folder, ori_size)
+            elif rgb or overlay is not None or composite is not None:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
                 if overlay is not None and conf_dir is not None:
                     os.makedirs(os.path.join(conf_dir, folder), exist_ok=True)
@@ -379,6 +425,9 @@ if __name__ == "__main__":
     parser.add_argument("--gt_map", nargs="?", type=str, default=None, help="text file of 256 integers: ground-truth byte -> class id (>= 19: ignored); default identity")
     parser.add_argument("--conf", nargs="?", type=str, default=None, help="directory for each frame's confidence map (grey PNG at the network size; 255 = certain)")
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
+    parser.add_argument("--matte", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13,14,15,16,17,18): the class set of --matte_out / --composite")
+    parser.add_argument("--matte_out", nargs="?", type=str, default=None, help="with --matte: directory for each frame's matte (8-bit grey PNG at the network size; 255 = certainly a member of the set)")
+    parser.add_argument("--composite", nargs="?", type=str, default=None, help="with --matte and --u8, --nv12 or --yuv: R,G,B -- write the frame seen through the matte over this background, at the frame's own size, where the overlay's picture would go")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
     parser.add_argument("--yuv", nargs="?", type=str, default=None, help="frames go to the device as tight surfaces of this layout (nv12, nv21, i420, p010, yuy2, uyvy; --nv12_standard): conversion, resize and normalisation in the frame's first launch; combines with what --nv12 combines with, --crop included")
