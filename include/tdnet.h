@@ -183,7 +183,10 @@ int  tdnet_memory_bytes(const tdnet_t* h, size_t* weights_bytes, size_t* handle_
 /* img_nchw_dev [1,3,H,W] -> logits_nchw_dev [1,nclass,H,W].  Mutates the K/Q/V FIFO exactly like
  * buffer_contral (td4_psp18.py:123-134): frames must arrive in order with pos_id = t mod path_num.              */
 int  tdnet_forward(tdnet_t* h, const float* img_nchw_dev, int pos_id, float* logits_nchw_dev, void* stream);
-/* argmax over classes with first-max tie-break = output.max(1)[1] (test.py:61); labels int32 [H,W].             */
+/* argmax over classes with first-max tie-break = output.max(1)[1] (test.py:61); labels int32 [H,W].  +/-inf logits included.  Where a
+ * pixel's logits hold a NaN the label is NOT the reference's (which names the first NaN): class 0 starts the running maximum and a NaN
+ * never replaces it, nor is a NaN in class 0 replaced.  The same rule holds for every label entry below (uint8, colour map, overlay,
+ * score, confidence, matte, views, surfaces): they share one comparison.                                                          */
 int  tdnet_argmax(tdnet_t* h, const float* logits_nchw_dev, int32_t* labels_dev, void* stream);
 /* forward + argmax without materialising the full-resolution logits (labels identical to the two calls above).  */
 int  tdnet_forward_labels(tdnet_t* h, const float* img_nchw_dev, int pos_id, int32_t* labels_dev, void* stream);

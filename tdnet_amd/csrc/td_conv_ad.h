@@ -66,6 +66,9 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 3) k_conv_adirect(ConvArgs p) {
 #pragma unroll
             for (int g = 0; g < NG; ++g)                             // kernel row la_step: floats 4 (2 g + half) .. + 3 of its 24
                 ra[g] = td_buf_ld4(in_buf, ok ? a_off + (unsigned)(la_step * p.W * 3 + (2 * g + half) * 4) * 4u : TD_BUF_OOB, 0u);
+            // floats 21 .. 23 are the next pixel, under the three zero-weight columns: 0 * NaN and 0 * inf are NaNs, and would carry a non-finite
+            // pixel into an output column the reference keeps finite.  Zeros instead: the same sums for every finite image.
+            if (half) { ra[2][1] = 0.f; ra[2][2] = 0.f; ra[2][3] = 0.f; }
         } else if (STEM) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {

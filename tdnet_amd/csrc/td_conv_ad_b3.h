@@ -117,11 +117,17 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, TD_ADB3_OCC) k_conv_adirect_b3(ConvArgs p) 
             else f[j] = *reinterpret_cast<const u32x4*>(smem + buf * BUF_BYTES + frag_off + ((part * 2 + b) * 2) * (BN * 16) + j * 512);
         }
     };
-    auto pair = [&](const f32x4& x0, const f32x4& x1, int i, u32x4& h, u32x4& mdl, u32x4& l) {   // values 2 i, 2 i + 1 of a lane's 8 -> dword i of each part
-        const float a = i < 2 ? x0[2 * i] : x1[2 * i - 4], b = i < 2 ? x0[2 * i + 1] : x1[2 * i - 3];
+    // blk1 (STEM = 2 only): the lane's 8 values are floats 16 + 8 half .. + 7 of the kernel row's 32, and floats 21 .. 31 are the pixels beside the window, under
+    // zero weights: 0 * NaN and 0 * inf are NaNs and would carry a non-finite pixel into output columns the reference keeps finite.  Zeros instead.
+    auto pair = [&](const f32x4& x0, const f32x4& x1, int i, u32x4& h, u32x4& mdl, u32x4& l, bool blk1 = false) {   // values 2 i, 2 i + 1 of a lane's 8 -> dword i of each part
+        float a = i < 2 ? x0[2 * i] : x1[2 * i - 4], b = i < 2 ? x0[2 * i + 1] : x1[2 * i - 3];
+        if (STEM == 2 && blk1) {
+            if (half || 2 * i >= 5) a = 0.f;
+            if (half || 2 * i + 1 >= 5) b = 0.f;
+        }
         unsigned h_, m_, l_;
         if (TD_ADB3_SKIP & 1) { h_ = __builtin_bit_cast(unsigned, a); m_ = __builtin_bit_cast(unsigned, b); l_ = h_; }
-        else td_split3_pair(a, b, h_, m_, l_);
+        else td_split3a_pair(a, b, h_, m_, l_);                   // td_gemm_b3.h: an infinite activation is carried, not turned into NaNs
         h[i] = h_; mdl[i] = m_; l[i] = l_;
     };                                                     // B fragment (high part, k block 0) of the coming step, read at the end of the one before
 
@@ -136,13 +142,13 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, TD_ADB3_OCC) k_conv_adirect_b3(ConvArgs p) 
         const int nb = cb == 2 ? 0 : cb + 1;
         u32x4 bh[NT] = {pf[0], pf[1]}, bm[NT], bl[NT], ch[NT], cm[NT], cl[NT], h1, m1, l1;
         TD_SCHED_FENCE();
-        mm(C.h0, bh); load_a(N); issue_w(); frag(cb, 1, 0, bm); pair(C.raw[2], C.raw[3], 0, h1, m1, l1);
+        mm(C.h0, bh); load_a(N); issue_w(); frag(cb, 1, 0, bm); pair(C.raw[2], C.raw[3], 0, h1, m1, l1, true);
         TD_SCHED_FENCE();
-        mm(C.m0, bh); pair(C.raw[2], C.raw[3], 1, h1, m1, l1);
+        mm(C.m0, bh); pair(C.raw[2], C.raw[3], 1, h1, m1, l1, true);
         TD_SCHED_FENCE();
-        mm(C.l0, bh); frag(cb, 2, 0, bl); pair(C.raw[2], C.raw[3], 2, h1, m1, l1);
+        mm(C.l0, bh); frag(cb, 2, 0, bl); pair(C.raw[2], C.raw[3], 2, h1, m1, l1, true);
         TD_SCHED_FENCE();
-        mm(C.h0, bm); pair(C.raw[2], C.raw[3], 3, h1, m1, l1);
+        mm(C.h0, bm); pair(C.raw[2], C.raw[3], 3, h1, m1, l1, true);
         TD_SCHED_FENCE();
         mm(C.m0, bm); frag(cb, 0, 1, ch);
         TD_SCHED_FENCE();

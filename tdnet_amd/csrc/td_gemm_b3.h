@@ -71,6 +71,32 @@ TD_DEV void td_split3_pair(float a, float b, unsigned& h, unsigned& m, unsigned&
     l = td_pk_bf16(sa, sb);
 }
 
+// The A operand of a conv / GEMM -- the activations -- split so that an INFINITE value survives: h = bf16(inf) = inf leaves inf - inf = NaN in m and l, and every
+// product with the element is a NaN, where the reference has inf x w = an infinity with w's sign (ReLU then makes 0 of -inf: a NaN there is a finite value
+// of the reference turned non-finite).  The six products pair A's low part with B's HIGH part only (h h, m h, l h, h m, m m, h l), and the high part of a
+// weight has the weight's sign and is 0 only for a weight that is 0: an infinity carried as (0, 0, inf) gives inf x w_h once, and 0 x the rest.  A NaN stays
+// a NaN in all three parts.  td_split3_pair runs first; one unordered compare of the pair's low parts tells whether a value was a NaN or an infinity, and only
+// then a branch redoes the pair with the infinity set aside: finite values split exactly as td_split3_pair splits them (selects on every value instead cost
+// 2.9 % of a bf16x3 frame, this 1.4 %: DESIGN.md 5.16).
+TD_DEV void td_split3a_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
+    td_split3_pair(a, b, h, m, l);
+    const float la = __builtin_bit_cast(float, l << 16), lb = __builtin_bit_cast(float, l & 0xffff0000u);
+    if (__builtin_expect(__builtin_isunordered(la, lb), 0)) {          // a NaN in a low part: the value was a NaN or an infinity -- never in a sound frame
+        const bool ia = __builtin_isinf(a), ib = __builtin_isinf(b);
+        const float a0 = ia ? 0.f : a, b0 = ib ? 0.f : b;
+        td_split3_pair(a0, b0, h, m, l);
+        l = (l & (ia ? 0xffff0000u : 0xffffffffu) & (ib ? 0x0000ffffu : 0xffffffffu)) | (ia ? __builtin_bit_cast(unsigned, a) >> 16 : 0u) | (ib ? __builtin_bit_cast(unsigned, b) & 0xffff0000u : 0u);
+    }
+}
+TD_DEV void td_split3a(const f32x4& x0, const f32x4& x1, u32x4& h, u32x4& m, u32x4& l) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned h_, m_, l_;
+        td_split3a_pair(i < 2 ? x0[2 * i] : x1[2 * i - 4], i < 2 ? x0[2 * i + 1] : x1[2 * i - 3], h_, m_, l_);
+        h[i] = h_; m[i] = m_; l[i] = l_;
+    }
+}
+
 #ifdef TD_B3_TRACE      // tools/gemm_b3_trace.hip only: s_memtime stamps of workgroups 0..7, every wave, the first 48 K steps:
 // [0] step start, [1] all MFMAs issued, [2] after the vmcnt wait, [3] after the barrier
 #define TD_B3_STAMP(gs_, slot) do { if (blockIdx.x < 8 && (gs_) < 48 && lane == 0) \
@@ -207,7 +233,7 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_b3(GemmArgs p) {
         f32x4 x[2][2];
         load_a(0, x);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) td_split3(x[i][0], x[i][1], ah[i], am[i], al[i]);
+        for (int i = 0; i < 2; ++i) td_split3a(x[i][0], x[i][1], ah[i], am[i], al[i]);
         TD_BARRIER_RAW();                                              // every wave has read A(0): its buffer may be refilled (A(2), step 0)
     }
     int cb = 0;                                                        // buffer of B(g); A(g + 1) sits in buffer cb ^ 1
@@ -233,7 +259,7 @@ TD_KERNEL void TD_LAUNCH_BOUNDS(256, 2) k_gemm_b3(GemmArgs p) {
                 const int i = c >> 2, qq = c & 3;
                 const float a = qq < 2 ? nx[i][0][2 * qq] : nx[i][1][2 * qq - 4], b = qq < 2 ? nx[i][0][2 * qq + 1] : nx[i][1][2 * qq - 3];
                 unsigned h_, m_, l_;
-                td_split3_pair(a, b, h_, m_, l_);
+                td_split3a_pair(a, b, h_, m_, l_);
                 nh[i][qq] = h_; nm[i][qq] = m_; nl[i][qq] = l_;
             };
             TD_SCHED_FENCE();

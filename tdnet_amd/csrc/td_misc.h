@@ -45,10 +45,15 @@ TD_KERNEL void k_nchw3_to_rgbpad(const float* __restrict__ img, float* __restric
 }
 
 // ---- MaxPool2d(3, stride 2, pad 1), padding = -inf, floor mode (resnet.py:137) -----------------------------------
+// F.max_pool2d bit for bit, non-finite values included: the padding taps are -inf (an all -inf window stays -inf, nothing is clipped), and the
+// running maximum is the NaN-propagating one (td_wino.h td_w_relu's builtin, v_maximum3_f32 on gfx950): a NaN in a window is a NaN in the
+// result, as in the reference -- `t > m ? t : m` dropped it and so hid a corrupted stem output.
+TD_DEV float td_pool_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+#define TD_POOL_PAD (-__builtin_inff())
 TD_KERNEL void k_maxpool3s2(const float* __restrict__ in, float* __restrict__ out, int H, int W, int C, int Ho, int Wo) {
     const int CV = C >> 2;
     const long total = (long)Ho * Wo * CV;
-    // nine UNCONDITIONAL range-checked loads, all in flight, padding taps replaced by -3e38 with a select: `if (inside) load; max`
+    // nine UNCONDITIONAL range-checked loads, all in flight, padding taps replaced by -inf with a select: `if (inside) load; max`
     // is nine dependent memory round trips per output (59 us for 168 MB at 1024x2048)
     const TdBuf in_buf = td_make_buf(in, (unsigned)H * (unsigned)W * (unsigned)C * 4u);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -65,15 +70,15 @@ TD_KERNEL void k_maxpool3s2(const float* __restrict__ in, float* __restrict__ ou
                 ok[ky][kx] = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
                 v[ky][kx] = td_buf_ld4(in_buf, ok[ky][kx] ? (((unsigned)iy * (unsigned)W + (unsigned)ix) * (unsigned)C + (unsigned)cv * 4u) * 4u : TD_BUF_OOB, 0u);
             }
-        f32x4 m = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        f32x4 m = {TD_POOL_PAD, TD_POOL_PAD, TD_POOL_PAD, TD_POOL_PAD};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float t = ok[ky][kx] ? v[ky][kx][e] : -3.0e38f;
-                    m[e] = t > m[e] ? t : m[e];
+                    const float t = ok[ky][kx] ? v[ky][kx][e] : TD_POOL_PAD;
+                    m[e] = td_pool_max(t, m[e]);
                 }
         td_st4(out + (size_t)pix * C + cv * 4, m);
     }
@@ -105,15 +110,15 @@ TD_KERNEL void k_maxpool3s2_h(const void* __restrict__ inv, _Float16* __restrict
                     v[ky][kx] = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
                 } else v[ky][kx] = td_buf_ld4(in_buf, ok[ky][kx] ? el * 4u : TD_BUF_OOB, 0u);
             }
-        f32x4 m = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        f32x4 m = {TD_POOL_PAD, TD_POOL_PAD, TD_POOL_PAD, TD_POOL_PAD};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float t = ok[ky][kx] ? v[ky][kx][e] : -3.0e38f;
-                    m[e] = t > m[e] ? t : m[e];
+                    const float t = ok[ky][kx] ? v[ky][kx][e] : TD_POOL_PAD;
+                    m[e] = td_pool_max(t, m[e]);
                 }
         td_f16x4 oh = {(_Float16)m[0], (_Float16)m[1], (_Float16)m[2], (_Float16)m[3]};
         *reinterpret_cast<td_f16x4*>(out + (size_t)pix * C + cv * 4) = oh;

@@ -88,8 +88,12 @@ TD_KERNEL void k_upsample_x4(const float* __restrict__ in, float* __restrict__ o
     td_st4(out + ((size_t)c * H + Y) * W + X4 * 4, o);
 }
 
-// ---- argmax: the first maximum wins (== output.max(1)[1], test.py:61) ---------------------------------------------------------------
+// ---- argmax: the first maximum wins (== output.max(1)[1], test.py:61, wherever no logit of the pixel is a NaN) ----------------------
 // Class c's value v joins the running maximum `best` (class `bi`) of the classes 0 .. c - 1; true if it took its place.
+// +/-inf compare like any value, so those labels are the reference's too.  A NaN is where the two part: torch's max names the first NaN,
+// here class 0 starts the running maximum and `v > best` is false with a NaN on either side -- a NaN never replaces it, and a NaN in
+// class 0 is never replaced.  A label under a NaN means nothing in the reference either, so the class loop carries no isnan for it; the
+// rule is pinned as it is by tests/nonfinite_cases.py.
 TD_DEV bool td_first_max(int c, float v, float& best, int& bi) {
     const bool up = c == 0 || v > best;
     if (up) { best = v; bi = c; }

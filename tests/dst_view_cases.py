@@ -12,6 +12,8 @@ import ctypes
 
 import numpy as np
 
+import opcheck
+
 import ingest_u8_cases as u8cases
 import view_cases as vc
 from tdnet_amd import _capi
@@ -91,7 +93,14 @@ def guarded(prefill, off):
 
 def op_picture(lib, mem, dview, prefill, off, pal, x=None, labels_u8=None, src=None, size=None):
     """tdnet_op_picture_view into a guarded copy of `prefill`; the whole buffer back.  src: (view, bytes) of the overlay's source, or None: the colour
-    map of `size`.  x: logits [C, h, w] (the fused kernel) or labels_u8 [H, W] (the label-map kernel)."""
+    map of `size`.  x: logits [C, h, w] (the fused kernel) or labels_u8 [H, W] (the label-map kernel).
+    The logits go in between guard bands, once per band fill (opcheck.each_poison): the same bytes both times."""
+    if x is None:
+        return _op_picture(lib, mem, dview, prefill, off, pal, x, labels_u8, src, size, None)
+    return opcheck.each_poison(x, mem.stream is not None, lambda px: _op_picture(lib, mem, dview, prefill, off, pal, x, labels_u8, src, size, px))
+
+
+def _op_picture(lib, mem, dview, prefill, off, pal, x, labels_u8, src, size, px):
     H, W = NET
     host, base = guarded(prefill, off)
     kd, pd = mem.up(host)
@@ -99,7 +108,6 @@ def op_picture(lib, mem, dview, prefill, off, pal, x=None, labels_u8=None, src=N
     pal = np.ascontiguousarray(pal)
     if x is not None:
         C, lh, lw = x.shape
-        kx, px = mem.up(x)
         pl = None
     else:
         C = lh = lw = 0

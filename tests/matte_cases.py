@@ -16,6 +16,8 @@ import ctypes
 
 import numpy as np
 
+import opcheck
+
 from conf_cases import ALL_OFFSETS, ALL_OFFSET_CASES, FEW_OFFSETS, NEAR, NEAR_CAP, SCALES, gate, logits, offsets_of  # noqa: F401  (re-exported)
 from ingest_u8_cases import ARGMAX_CASES
 from score_cases import WIDE_CASES  # noqa: F401  (re-exported: rows wider than one workgroup's strip, and the real geometry)
@@ -71,9 +73,19 @@ def expected(full, ids, who=""):
 # ---- the operator on any memory ----------------------------------------------------------------------------------------------------------
 # `mem` stands for the memory a scenario runs in, as in view_cases.py: mem.up(array, off=0) -> (holder, address); mem.get(buffer) -> numpy
 # (synchronises); mem.stream.
+def _is_array(a):
+    return a is not None and not isinstance(a, int)
+
+
 def matte_op(lib, mem, C, H, W, ids, x=None, h=0, w=0, full=None, lab_off=0, mat_off=0, want_labels=True):
-    """One call of tdnet_op_upsample_argmax_matte: (labels written or None, matte written) as numpy.  x / full: ADDRESSES of the low-resolution
-    / full-resolution logits in `mem`.  Either map sits at its byte offset inside a 0xEE holder whose 16 guard bytes must survive."""
+    """One call of tdnet_op_upsample_argmax_matte: (labels written or None, matte written) as numpy.  x / full: the low-resolution / full-resolution
+    logits -- an ADDRESS in `mem`, or the ARRAY itself: it then goes in between guard bands, once per band fill, and both runs must give the same
+    bytes (opcheck.each_poison).  Either map sits at its byte offset inside a 0xEE holder whose 16 guard bytes must survive."""
+    dev = mem.stream is not None
+    if _is_array(x):
+        return opcheck.each_poison(x, dev, lambda px: matte_op(lib, mem, C, H, W, ids, px, h, w, full, lab_off, mat_off, want_labels))
+    if _is_array(full):
+        return opcheck.each_poison(full, dev, lambda pf: matte_op(lib, mem, C, H, W, ids, x, h, w, pf, lab_off, mat_off, want_labels))
     n = H * W
     mh, mp = mem.up(np.full(n + 16, 0xEE, np.uint8))
     lh, lp = mem.up(np.full(n + 16, 0xEE, np.uint8)) if want_labels else (None, None)
@@ -140,7 +152,10 @@ def expected_dest(prefill, dview, picture_rgb, alpha=None):
 
 def op_composite(lib, mem, src, src_off, dview, prefill, dst_off, bg, x=None, ids=(), matte=None):
     """tdnet_op_composite into a guarded copy of `prefill` (dview None: the contiguous block of prefill.size bytes): the whole buffer back, and the
-    offset of the destination's base in it.  x: ADDRESS of logits [19, 5, 9] in `mem`; or matte: a map [H, W] (uploaded at an odd address)."""
+    offset of the destination's base in it.  x: logits [19, 5, 9] -- an ADDRESS in `mem`, or the ARRAY: between guard bands, once per band fill, the
+    same bytes both times (opcheck.each_poison); or matte: a map [H, W] (uploaded at an odd address)."""
+    if _is_array(x):
+        return opcheck.each_poison(x, mem.stream is not None, lambda px: op_composite(lib, mem, src, src_off, dview, prefill, dst_off, bg, px, ids, matte))
     H, W = NET
     desc, sbytes = src[0], src[1]
     host = np.full(GUARD + dst_off + prefill.size + GUARD, GUARD_BYTE, np.uint8)

@@ -49,13 +49,19 @@ class _Guarded:
     """Guard bands around every tensor a mem hands out: the tensor is the interior of a larger allocation with GUARD bytes in front and
     behind (a multiple of 256, so the interior keeps a fresh allocation's 256-byte alignment).  The bands of an input (put) hold quiet
     NaNs -- an out-of-range read that reaches a result poisons it; one that is discarded is allowed -- and those of an output (empty) a
-    fixed pattern, itself a NaN.  verify() asserts that every band of every tensor handed out since the last verify() still holds its
-    fill bit for bit, and that every output interior is finite and free of the 7e7 fill; then the mem forgets those tensors.  The mem
-    owns the allocations until then: mem.ptr(mem.put(x)) on a temporary stays valid through the kernel call.
+    fixed pattern, itself a NaN.  A NaN cannot poison a MAXIMUM written as a comparison (`v > best`, td_out.h td_first_max: false with a
+    NaN on either side), so put(a, poison=BIG_BITS) fills the bands with 2^127 instead: finite -- a tap read with weight exactly 0 is still
+    discarded (0 * 2^127 = 0, where 0 * inf would be a NaN) -- and larger than any logit, so a maximum that takes it in names another
+    class.  What feeds a maximum runs once per fill of POISONS and must give the same bytes both times.
+    verify() asserts that every band of every tensor handed out since the last verify() still holds its fill bit for bit, and that every
+    output interior is finite and free of the 7e7 fill; then the mem forgets those tensors.  The mem owns the allocations until then:
+    mem.ptr(mem.put(x)) on a temporary stays valid through the kernel call.
     empty(shape, unwritten_rows=mask): an output of which the call writes only some rows (a boolean per index of the first axis, True = must
     NOT be written): verify() holds those rows to the 7e7 fill bit for bit and every other row to "finite and fully written" as usual."""
     GUARD = 4096                     # bytes per band
     IN_BITS = 0x7FC00000             # quiet NaN
+    BIG_BITS = 0x7F000000            # 2^127: the input fill a comparison cannot swallow
+    POISONS = (IN_BITS, BIG_BITS)
     OUT_BITS = 0x7FC5A5A5            # a quiet NaN with a payload: a fixed pattern no kernel produces
     FILL = 7e7
 
@@ -74,9 +80,10 @@ class _Guarded:
         self._live.append((buf, n, bits, is_out, shape, keep))
         return inner
 
-    def put(self, a):
+    def put(self, a, poison=None):
         a = np.ascontiguousarray(a, dtype=np.float32)
-        t = self._new(a.shape, self.IN_BITS, False)
+        assert poison is None or poison in self.POISONS, poison
+        t = self._new(a.shape, self.IN_BITS if poison is None else poison, False)
         self._store(t, a)
         return t
 
@@ -85,8 +92,10 @@ class _Guarded:
         self._store(t, np.float32(self.FILL))
         return t
 
-    def verify(self, untouched=False):
-        """untouched: the calls since the last verify() were refused -- every output interior must still hold its fill instead."""
+    def verify(self, untouched=False, finite=True):
+        """untouched: the calls since the last verify() were refused -- every output interior must still hold its fill instead.
+        finite = False: the inputs held non-finite values on purpose (tests/nonfinite_cases.py), so the outputs may; the bands and "fully
+        written" are checked as always."""
         live, self._live = self._live, []
         g = self.GUARD // 4
         for i, (buf, n, bits, is_out, shape, keep) in enumerate(live):
@@ -105,7 +114,7 @@ class _Guarded:
                     kept = f[keep].view(np.int32) != np.float32(self.FILL).view(np.int32)
                     assert not kept.any(), "%s: %d elements in %d rows that must stay unwritten were written" % (what, int(kept.sum()), int(kept.any(1).sum()))
                     f = f[~keep]
-                assert np.isfinite(f).all(), "%s: %d non-finite values (a read outside an input reached the result)" % (what, int((~np.isfinite(f)).sum()))
+                assert not finite or np.isfinite(f).all(), "%s: %d non-finite values (a read outside an input reached the result)" % (what, int((~np.isfinite(f)).sum()))
                 assert not (f == np.float32(self.FILL)).any(), "%s: %d elements were never written" % (what, int((f == np.float32(self.FILL)).sum()))
 
 
@@ -696,3 +705,79 @@ def upsample(lib, mem, C, h, w, H, W, seed=0, tol=1e-5):
     err = float(np.abs(mem.get(out) - ref).max())
     assert err <= tol, ("upsample", C, h, w, H, W, err)
     return err
+
+
+def _same_bytes(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same_bytes(p, q) for p, q in zip(a, b))
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def each_poison(x, device, run):
+    """fp32 logits x through an output entry inside guard bands, once per fill of _Guarded.POISONS (the quiet NaN a comparison swallows, the 2^127
+    it cannot): run(address) -> an array, or a tuple of arrays and Nones.  The two results must be the same bytes -- an out-of-range read of
+    logits shows under one of the fills -- and the bands intact; returns the first.  device: torch-ROCm memory, else numpy (the emulator)."""
+    if torch.is_tensor(x):
+        x = x.cpu().numpy()
+    first = None
+    for poison in _Guarded.POISONS:
+        mem = GuardedTorchMem() if device else GuardedNumpyMem()
+        got = run(mem.ptr(mem.put(x, poison=poison)))
+        mem.verify()
+        if first is None:
+            first = got
+        else:
+            assert _same_bytes(first, got), "the output depends on what lies around the logits: band fill 0x%08x against 0x%08x" % (poison, _Guarded.POISONS[0])
+    return first
+
+
+class At:
+    """The address of a guarded copy where a helper expects the array (x.ctypes.data) or the tensor (x.data_ptr()) itself."""
+    def __init__(self, addr):
+        self._addr = addr
+        self.ctypes = self
+
+    @property
+    def data(self):
+        return self._addr
+
+    def data_ptr(self):
+        return self._addr
+
+
+GUARDED_ARG_CAP = 8 << 20                                              # bytes: larger logits (the 90 MB of a 769x1537 frame) stay where they are
+
+
+def guarded_arg(name, device, accumulates=None):
+    """Decorator for a test's operator helper: its argument `name` -- fp32 logits as an array or a tensor, or None -- goes through each_poison: the
+    helper runs once per band fill on a guarded copy (it sees an At) and must return the same bytes.  accumulates: an argument the entry adds
+    into (the score entry's matrix), put back to its state at the call before each run."""
+    import functools
+    import inspect
+
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def wrapper(*a, **kw):
+            b = sig.bind(*a, **kw)
+            b.apply_defaults()
+            x = b.arguments[name]
+            nbytes = 0 if x is None or isinstance(x, At) else (x.numel() * x.element_size() if torch.is_tensor(x) else np.asarray(x).nbytes)
+            addr = 0 if nbytes == 0 else (x.data_ptr() if torch.is_tensor(x) else np.asarray(x).ctypes.data)
+            if nbytes == 0 or nbytes > GUARDED_ARG_CAP or addr % 16:     # (a deliberately misaligned map keeps its address: that is what its test is about)
+                return fn(*a, **kw)
+            acc = b.arguments.get(accumulates) if accumulates else None
+            start = None if acc is None else (acc.clone() if torch.is_tensor(acc) else np.array(acc))
+
+            def run(addr):
+                if acc is not None:
+                    acc.copy_(start) if torch.is_tensor(acc) else np.copyto(acc, start)
+                b.arguments[name] = At(addr)
+                return fn(*b.args, **b.kwargs)
+            return each_poison(x, device, run)
+        return wrapper
+    return deco

@@ -4,9 +4,15 @@ labels, uint8 labels, the score entry's labels and matrix, the confidence entry'
 labels -- and every form must name the same label under every pixel.  All comparisons are exact: the forms share one bilinear expression,
 one first-maximum rule and one class loop, there is nothing to tolerate.
 
+The logits sit between guard bands (opcheck._Guarded) and the whole check runs once per band fill of opcheck._Guarded.POISONS -- the quiet NaN, which
+td_first_max's comparison swallows, and 2^127, which it cannot: an out-of-range read of logits names another class under one of the two, and
+the labels of the two runs must be the same bytes.
+
 The byte maps start at byte offsets 0..3 inside their holders.  The int32 map is moved by 0..3 ELEMENTS instead: an int32_t* that is not
 4-byte aligned is outside the C ABI of the entry."""
 import numpy as np
+
+import opcheck
 
 # (C, (h, w), (H, W)): 3 and 19 classes; 5x9 -> 33x65, and 4x7 -> 25x49 (W odd: the rows of a map start at every alignment)
 CASES = [(C, lo, hi) for C in (3, 19) for lo, hi in (((5, 9), (33, 65)), ((4, 7), (25, 49)))]
@@ -51,17 +57,23 @@ def ground_truth(C, H, W):
 
 
 def check(lib, mem, setenv, case, field):
-    """mem: the memory the entries work on -- mem.put(array) -> (keepalive, pointer), mem.holder(nbytes, off) -> (pointer, read) with read()
-    the nbytes written behind `off` (it asserts the 0xEE guard bytes around them), mem.stream.  setenv: monkeypatch.setenv."""
+    """mem: the memory the entries work on -- mem.put(array) -> (keepalive, pointer), mem.put_logits(array, poison) -> the same between guard bands
+    of that fill, mem.holder(nbytes, off) -> (pointer, read) with read() the nbytes written behind `off` (it asserts the 0xEE guard bytes around
+    them), mem.stream.  setenv: monkeypatch.setenv."""
+    ref = None
+    for poison in opcheck._Guarded.POISONS:
+        ref = _check(lib, mem, setenv, case, field, poison, ref)
+
+
+def _check(lib, mem, setenv, case, field, poison, ref):
     C, (h, w), (H, W) = case
     n = H * W
-    x_keep, x = mem.put(logits(field, C, h, w))
+    x_keep, x = mem.put_logits(logits(field, C, h, w), poison)
     gt_keep, gt = mem.put(ground_truth(C, H, W))
     pal = grey_palette()
     s = mem.stream
-    ref = None
     for off in OFFSETS:
-        who = (case_id(case), field, off)
+        who = (case_id(case), field, off, hex(poison))
         # int32 and uint8 labels, one call
         p32, read32 = mem.holder(4 * n, 4 * off)
         p8, read8 = mem.holder(n, off)
@@ -100,4 +112,6 @@ def check(lib, mem, setenv, case, field):
         assert np.array_equal(pic, np.repeat(l8[:, :, None], 3, axis=2)), who
     if field == "ties":
         assert (ref == 0).any() and (ref == C - 1).sum() == 0, case_id(case)   # the first of two equal planes wins everywhere
+    x_keep.verify()                                                    # the bands around the logits are intact
     del x_keep, gt_keep
+    return ref

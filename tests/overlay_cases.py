@@ -11,6 +11,8 @@ import functools
 
 import numpy as np
 
+import opcheck
+
 from ingest_u8_cases import ARGMAX_CASES, lowres_logits  # noqa: F401  (re-exported: the logits of the operator cases)
 from rgb_out_cases import expected_picture, logits40, out_sizes, palette19  # noqa: F401
 from tdnet_amd.dataloader import nv12_extent, nv12_to_rgb_u8, overlay_u8, rgb_to_nv12
@@ -90,14 +92,20 @@ def labels_of(lib, mem, x, C, h, w, H, W):
 
 def op_overlay(lib, mem, H, W, Hs, Ws, pal, src_bytes, src_off, out_off, nv=None, x=None, labels_u8=None):
     """tdnet_op_overlay: the picture written `out_off` bytes into a holder of 0xEE (the guard bytes around it must survive), the source `src_off`
-    bytes into a holder of 0xA5.  nv: None (packed RGB) or (pitch, uv_offset, standard).  x: logits [C, h, w] (fused kernel) or labels_u8 [H, W]."""
+    bytes into a holder of 0xA5.  nv: None (packed RGB) or (pitch, uv_offset, standard).  x: logits [C, h, w] (fused kernel) or labels_u8 [H, W].
+    The logits go in between guard bands, once per band fill (opcheck.each_poison): the same bytes both times."""
+    if x is None:
+        return _op_overlay(lib, mem, H, W, Hs, Ws, pal, src_bytes, src_off, out_off, nv, x, labels_u8, None)
+    return opcheck.each_poison(x, mem.stream is not None, lambda px: _op_overlay(lib, mem, H, W, Hs, Ws, pal, src_bytes, src_off, out_off, nv, x, labels_u8, px))
+
+
+def _op_overlay(lib, mem, H, W, Hs, Ws, pal, src_bytes, src_off, out_off, nv, x, labels_u8, px):
     n = Hs * Ws * 3
     ks, ps = mem.up(src_bytes, src_off)
     holder = mem.out(n + 16)
     pal = np.ascontiguousarray(pal)
     if x is not None:
         C, h, w = x.shape
-        kx, px = mem.up(x)
         pl = None
     else:
         C = h = w = 0

@@ -11,6 +11,8 @@ import functools
 
 import numpy as np
 
+import opcheck
+
 import dst_view_cases as dvc
 import ingest_u8_cases as u8cases
 import view_cases as vc
@@ -139,7 +141,14 @@ OVERLAY_RECTS = ((2, 5, 41, 83), (3, 4, 41, 83))
 
 def op_overlay_surface(lib, mem, surf, src_bytes, src_off, out_off, pal, x=None, labels_u8=None):
     """tdnet_op_overlay_surface: the picture `out_off` bytes into a holder of 0xEE whose other bytes must survive; the frame `src_off` bytes into a
-    holder of 0xA5."""
+    holder of 0xA5.
+    The logits go in between guard bands, once per band fill (opcheck.each_poison): the same bytes both times."""
+    if x is None:
+        return _op_overlay_surface(lib, mem, surf, src_bytes, src_off, out_off, pal, x, labels_u8, None)
+    return opcheck.each_poison(x, mem.stream is not None, lambda px: _op_overlay_surface(lib, mem, surf, src_bytes, src_off, out_off, pal, x, labels_u8, px))
+
+
+def _op_overlay_surface(lib, mem, surf, src_bytes, src_off, out_off, pal, x, labels_u8, px):
     H, W = vc.OVERLAY_NET
     h, w = surf.size
     n = h * w * 3
@@ -149,7 +158,6 @@ def op_overlay_surface(lib, mem, surf, src_bytes, src_off, out_off, pal, x=None,
     t, pt = csurf(surf)
     if x is not None:
         C, lh, lw = x.shape
-        kx, px = mem.up(x)
         pl = None
     else:
         C = lh = lw = 0
@@ -196,7 +204,14 @@ DST_CASES = ("even_41x83", "corner_odd")
 
 def op_picture(lib, mem, dsurf, prefill, off, pal, x=None, labels_u8=None, src=None, size=None):
     """tdnet_op_picture_surface into a guarded copy of `prefill`; the whole buffer back.  src: (Surface or SourceView, bytes) of the overlay's source, or
-    None: the colour map of `size`.  dsurf: a Surface, or a SourceView (a destination view behind a surface source)."""
+    None: the colour map of `size`.  dsurf: a Surface, or a SourceView (a destination view behind a surface source).
+    The logits go in between guard bands, once per band fill (opcheck.each_poison): the same bytes both times."""
+    if x is None:
+        return _op_picture(lib, mem, dsurf, prefill, off, pal, x, labels_u8, src, size, None)
+    return opcheck.each_poison(x, mem.stream is not None, lambda px: _op_picture(lib, mem, dsurf, prefill, off, pal, x, labels_u8, src, size, px))
+
+
+def _op_picture(lib, mem, dsurf, prefill, off, pal, x, labels_u8, src, size, px):
     H, W = NET
     host, base = dvc.guarded(prefill, off)
     kd, pd = mem.up(host)
@@ -207,7 +222,6 @@ def op_picture(lib, mem, dsurf, prefill, off, pal, x=None, labels_u8=None, src=N
     pal = np.ascontiguousarray(pal)
     if x is not None:
         C, lh, lw = x.shape
-        kx, px = mem.up(x)
         pl = None
     else:
         C = lh = lw = 0

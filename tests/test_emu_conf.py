@@ -5,6 +5,7 @@ frames against the label entries and tdnet_forward; the composition with the sco
 import numpy as np
 import pytest
 
+import opcheck
 import conf_cases as cases
 import emu_util
 import score_cases
@@ -44,6 +45,8 @@ def holder(n, off):
     return hold, hold[off:off + n]
 
 
+@opcheck.guarded_arg("x", False)
+@opcheck.guarded_arg("full", False)
 def conf_op(lib, C, H, W, x=None, h=0, w=0, full=None, lab_off=0, conf_off=0, min_conf=0, reject=255, want_labels=True):
     """One call of the operator entry: (labels written or None, confidence written).  Either map sits at its byte offset inside a 0xEE holder
     whose guard bytes must survive."""

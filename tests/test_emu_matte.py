@@ -7,6 +7,7 @@ import pytest
 
 import emu_util
 import matte_cases as cases
+import opcheck
 from tdnet_amd import _capi, arch, weights
 from tdnet_amd.engine import Engine
 
@@ -48,9 +49,11 @@ def holder(n, off):
     return hold, hold[off:off + n]
 
 
+@opcheck.guarded_arg("x", False)
+@opcheck.guarded_arg("full", False)
 def matte_op(lib, C, H, W, ids, x=None, h=0, w=0, full=None, lab_off=0, mat_off=0, want_labels=True):
     """One call of the operator entry: (labels written or None, matte written).  Either map sits at its byte offset inside a 0xEE holder whose
-    guard bytes must survive."""
+    guard bytes must survive.  The logits go in between guard bands, once per band fill (opcheck.guarded_arg): the same bytes both times."""
     mh, mv = holder(H * W, mat_off)
     lh = lv = None
     if want_labels:
@@ -391,7 +394,7 @@ def comp_inputs(lib):
             m.setflags(write=False)
             sets[sname] = (ids, m)
         assert (sets["every"][1] == 255).all() and (sets["empty"][1] == 0).all() and len(np.unique(sets["moving"][1])) > 100
-        _mattes["v"] = (keep, px, sets)
+        _mattes["v"] = (keep, x, sets)                                # the ARRAY: op_composite puts it between guard bands, once per band fill
     return _mattes["v"]
 
 

@@ -21,7 +21,8 @@ def mem():
     return opcheck.GuardedNumpyMem()
 
 
-def test_guarded_mem_catches_what_it_is_for():
+def test_guarded_mem_catches_what_it_is_for(lib):
+    _second_fill_shows_what_a_maximum_swallows(lib)
     mem = opcheck.GuardedNumpyMem()
     x = mem.put(np.arange(6, dtype=np.float32).reshape(2, 3))
     out = mem.empty((2, 3))
@@ -55,6 +56,34 @@ def test_guarded_mem_catches_what_it_is_for():
     out[0, 0] = 1.0
     with pytest.raises(AssertionError, match="launched nothing"):
         mem.verify(untouched=True)
+
+
+def _second_fill_shows_what_a_maximum_swallows(lib):
+    """What the 2^127 fill is for.  tdnet_op_upsample_argmax is told C classes and handed C - 1 planes, so it reads the last plane from the band
+    behind them ((C - 1) h w 4 = 1440 bytes in, inside the 4096-byte band: emulator only, no device test reads out of range on purpose).
+    With the NaN band `v > best` is false for every value read there: the labels are exactly those of the C - 1 planes, and the out-of-range
+    read goes unseen.  With the 2^127 band the out-of-range plane wins and the labels change."""
+    C, h, w, H, W = 19, 4, 5, 25, 33
+    x = np.random.default_rng(5).standard_normal((C - 1, h, w)).astype(np.float32)
+    assert (C - 1) * h * w * 4 + h * w * 4 <= opcheck.GuardedNumpyMem.GUARD
+
+    def labels(planes, classes, poison):
+        mem = opcheck.GuardedNumpyMem()
+        l32 = np.full((H, W), -1, np.int32)
+        lib.check(lib.tdnet_op_upsample_argmax(mem.ptr(mem.put(planes, poison=poison)), classes, h, w, H, W, l32.ctypes.data, None, None))
+        mem.verify()                                                   # the bands themselves are intact: only a poisoned RESULT can tell
+        return l32
+
+    nan_bits, big_bits = opcheck.GuardedNumpyMem.POISONS
+    honest = labels(x, C - 1, nan_bits)
+    assert np.array_equal(labels(x, C - 1, big_bits), honest)          # in range, the fill is never seen
+    assert np.array_equal(labels(x, C, nan_bits), honest)              # out of range into NaNs: nothing changes, nothing is detected
+    lied = labels(x, C, big_bits)
+    assert (lied == C - 1).mean() > 0.4 and not np.array_equal(lied, honest)   # out of range into 2^127: the labels give it away
+    mem = opcheck.GuardedNumpyMem()
+    band = mem.put(np.zeros(3, np.float32), poison=big_bits)
+    assert np.ctypeslib.as_array((ctypes.c_float * 1).from_address(band.ctypes.data + 12))[0] == 2.0 ** 127   # finite: 0 * fill is 0, a zero-weight tap stays discarded
+    mem.verify()
 
 
 @pytest.mark.parametrize("tile", cases.DIRECT_TILES)

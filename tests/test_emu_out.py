@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import emu_util
+import opcheck
 import out_cases as cases
 
 
@@ -19,6 +20,13 @@ class HostMem:
     def put(a):
         a = np.array(a)                                                # a writable, contiguous copy
         return a, a.ctypes.data
+
+    @staticmethod
+    def put_logits(a, poison):
+        """(the guarded mem that owns it -- verify() checks the bands --, address) of fp32 logits between guard bands of the fill `poison`"""
+        mem = opcheck.GuardedNumpyMem()
+        t = mem.put(a, poison=poison)
+        return mem, t.ctypes.data
 
     @staticmethod
     def get(keep):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import emu_util
+import opcheck
 import rgb_out_cases as cases
 from tdnet_amd import _capi, arch, weights
 from tdnet_amd.dataloader import nearest_index
@@ -48,6 +49,7 @@ def labels_of(lib, x, C, h, w, H, W):
     return l32
 
 
+@opcheck.guarded_arg("x", False)
 def picture(lib, H, W, oh, ow, palette, off, x=None, C=0, h=0, w=0, labels_u8=None):
     """The picture written `off` bytes into a holder of 0xEE; the guard bytes around it must survive."""
     n = oh * ow * 3

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import emu_util
+import opcheck
 import score_cases as cases
 from tdnet_amd import _capi, arch, weights
 from tdnet_amd.engine import Engine
@@ -38,6 +39,7 @@ def held(a, off, fill):
     return holder, holder[off:off + a.size].reshape(a.shape)
 
 
+@opcheck.guarded_arg("x", False, accumulates="cm")
 def score(lib, C, H, W, gt, x=None, h=0, w=0, gt_off=0, lab_off=None, gt_map=None, labels_in=None, cm=None):
     """One call of the operator entry: (cm, labels written or None).  gt sits gt_off bytes into a 0xEE holder, the label map (lab_off != None) lab_off
     bytes into another whose guard bytes must survive; cm is accumulated into (a fresh zero matrix by default)."""

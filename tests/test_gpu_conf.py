@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import opcheck
 import conf_cases as cases
 import score_cases
 from tdnet_amd import _capi
@@ -46,6 +47,8 @@ def reference(lib, key, x, C, h, w, H, W):
     return _ref[key]
 
 
+@opcheck.guarded_arg("x", True)
+@opcheck.guarded_arg("full", True)
 def conf_op(lib, C, H, W, x=None, h=0, w=0, full=None, lab_off=0, conf_off=0, min_conf=0, reject=255, want_labels=True):
     """One call of the operator entry on device memory: (labels written or None, confidence written) as numpy.  Either map sits at its byte
     offset inside a 0xEE holder whose 16 guard bytes must survive."""

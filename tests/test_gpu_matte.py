@@ -49,21 +49,23 @@ def check_case(lib, key, x, C, h, w, H, W, offsets, set_names=None):
     labels, fullh = l32.cpu().numpy(), full.cpu().numpy()
     assert labels.min() >= 0 and labels.max() < C
     kf, pf = MEM.up(fullh, 4)                                          # the unfused kernel's logits at a non-16-byte-aligned address
+    # the logits as ARRAYS: matte_op puts them between guard bands, once per band fill (the 90 MB of the real geometry stay where they are)
+    guarded_full = fullh if fullh.nbytes <= (8 << 20) else full.data_ptr()
     got = {}
     sets = {k: v for k, v in cases.class_sets(C).items() if set_names is None or k in set_names}
     for i, (sname, ids) in enumerate(sets.items()):
         want, near = cases.expected(fullh, ids, (key, sname))
         first = None
         for lab_off, mat_off in (offsets if i == 0 else cases.FEW_OFFSETS[i % 4:i % 4 + 1]):
-            lab, mat = cases.matte_op(lib, MEM, C, H, W, ids, px, h, w, lab_off=lab_off, mat_off=mat_off)
+            lab, mat = cases.matte_op(lib, MEM, C, H, W, ids, x, h, w, lab_off=lab_off, mat_off=mat_off)
             assert np.array_equal(lab, labels), (key, sname, lab_off, mat_off)
             cases.gate(mat, want, near, (key, sname, lab_off, mat_off))
             first = mat if first is None else first
             assert np.array_equal(mat, first), (key, sname, lab_off, mat_off)   # one byte per pixel whatever the offsets
-        _, only = cases.matte_op(lib, MEM, C, H, W, ids, px, h, w, mat_off=3, want_labels=False)
+        _, only = cases.matte_op(lib, MEM, C, H, W, ids, x, h, w, mat_off=3, want_labels=False)
         assert np.array_equal(only, first), (key, sname)
         got[sname] = first
-        lab, umat = cases.matte_op(lib, MEM, C, H, W, ids, full=full.data_ptr(), lab_off=(i + 1) & 3, mat_off=i & 3)
+        lab, umat = cases.matte_op(lib, MEM, C, H, W, ids, full=guarded_full, lab_off=(i + 1) & 3, mat_off=i & 3)
         assert np.array_equal(lab, labels), (key, sname)
         cases.gate(umat, want, near, (key, sname, "unfused"))
         d = np.abs(umat.astype(np.int64) - first)
@@ -111,7 +113,7 @@ _mattes = {}
 
 def comp_inputs(lib):
     if not _mattes:
-        keep, px = MEM.up(cases.logits("odd_w", 19, 5, 9, 6))
+        keep, px = None, cases.logits("odd_w", 19, 5, 9, 6)          # the array: matte_op / op_composite put it between guard bands, once per band fill
         sets = {}
         for sname, ids in (("moving", cases.MOVING), ("every", tuple(range(19))), ("empty", ())):
             sets[sname] = (ids, cases.matte_op(lib, MEM, 19, 33, 65, ids, px, 5, 9, want_labels=False)[1])

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import opcheck
 import out_cases as cases
 from tdnet_amd import _capi
 
@@ -26,6 +27,13 @@ class DeviceMem:
         a = np.array(a)
         t = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
         return t, t.data_ptr()
+
+    @staticmethod
+    def put_logits(a, poison):
+        """(the guarded mem that owns it -- verify() checks the bands --, address) of fp32 logits between guard bands of the fill `poison`"""
+        mem = opcheck.GuardedTorchMem()
+        t = mem.put(a, poison=poison)
+        return mem, t.data_ptr()
 
     @staticmethod
     def get(keep):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import opcheck
 import score_cases as cases
 from tdnet_amd import _capi
 from tdnet_amd.metrics import SCORE_KEYS, runningScore
@@ -39,6 +40,7 @@ def held(a, off):
     return holder, holder.data_ptr() + off
 
 
+@opcheck.guarded_arg("x", True, accumulates="cm")
 def score(lib, C, H, W, gt, x=None, h=0, w=0, gt_off=0, lab_off=None, gt_map=None, labels_in=None, lin_off=0, cm=None):
     """One call of the operator entry on device memory: (cm as numpy uint64, labels written or None)."""
     gh, gp = held(gt, gt_off)

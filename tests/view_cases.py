@@ -12,6 +12,8 @@ import functools
 
 import numpy as np
 
+import opcheck
+
 import ingest_u8_cases as u8cases
 from tdnet_amd import _capi
 from tdnet_amd.dataloader import (PIX_BGR, PIX_BGR24, PIX_BGRA32, PIX_NV12, PIX_RGB24, PIX_RGBA32, SourceView, nearest_index, nv12_extent, overlay_u8, pack_view,
@@ -192,7 +194,14 @@ def expected_overlay(view, src_bytes, labels, pal):
 
 def op_overlay_view(lib, mem, view, src_bytes, src_off, out_off, pal, x=None, labels_u8=None):
     """tdnet_op_overlay_view: the picture `out_off` bytes into a holder of 0xEE whose other bytes must survive; the frame `src_off` bytes into a
-    holder of 0xA5.  x: logits [C, h, w] (the fused kernel) or labels_u8 [H, W] (the label-map kernel)."""
+    holder of 0xA5.  x: logits [C, h, w] (the fused kernel) or labels_u8 [H, W] (the label-map kernel).
+    The logits go in between guard bands, once per band fill (opcheck.each_poison): the same bytes both times."""
+    if x is None:
+        return _op_overlay_view(lib, mem, view, src_bytes, src_off, out_off, pal, x, labels_u8, None)
+    return opcheck.each_poison(x, mem.stream is not None, lambda px: _op_overlay_view(lib, mem, view, src_bytes, src_off, out_off, pal, x, labels_u8, px))
+
+
+def _op_overlay_view(lib, mem, view, src_bytes, src_off, out_off, pal, x, labels_u8, px):
     H, W = OVERLAY_NET
     h, w = view.size
     n = h * w * 3
@@ -202,7 +211,6 @@ def op_overlay_view(lib, mem, view, src_bytes, src_off, out_off, pal, x=None, la
     t, pt = cview(view)
     if x is not None:
         C, lh, lw = x.shape
-        kx, px = mem.up(x)
         pl = None
     else:
         C = lh = lw = 0
