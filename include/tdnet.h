@@ -550,6 +550,47 @@ int  tdnet_set_output_composite(tdnet_t* h, int mode, const uint8_t* bg_rgb /* [
 int  tdnet_forward_u8_composite(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* out_dev, void* stream);
 /* the unfused form: from a matte map [H][W] the caller already holds (any byte address); needs no tdnet_set_matte */
 int  tdnet_matte_composite(tdnet_t* h, const uint8_t* matte_u8_dev, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
+/* ---- regions out ---------------------------------------------------------------------------------------------------
+ * What a video pipeline does next with a semantic map is not per pixel: the "thing" classes become objects -- a box, an area and a centroid per blob
+ * for a tracker, a counter or an alert.  These entries label the connected components of a class set on the device, behind the frame's labels, instead
+ * of a download of the label map and a connected-components pass on a host core.  Let L[Y][X] be the label the label entries give (first-maximum argmax
+ * of the upsampled logits, H x W, the network size), S the configured class set, connectivity 4 or 8:
+ *   region      a maximal set of pixels with L in S that are pairwise connected through neighbours carrying the SAME label: two adjacent member
+ *               classes are two regions.  A label outside S, or >= nclass (a reject_label written by the confidence entries and handed to the unfused
+ *               entry), is background.
+ *   numbering   a region's key is the raster index Y W + X of its first pixel (its smallest raster index).  Regions with area < min_area are dropped;
+ *               the survivors are numbered 1, 2, ... by growing key (the order scipy.ndimage.label gives for one class).  count = the survivors.
+ *   id map      optional: int32 [H][W], the region's number, 0 for background and for dropped regions.  Ids run up to count, also beyond max_regions.
+ *   table       a device buffer of tdnet_regions_bytes bytes, 8-byte aligned (any other alignment is refused, the message naming regions_dev): a 16-byte
+ *               header tdnet_regions_header, then max_regions records tdnet_region of 48 bytes.  stored = min(count, max_regions); record i describes
+ *               region i + 1; records from index stored on are zero.  The box is inclusive; first_y / first_x is the first pixel; the centroid is
+ *               sum / area (64 bits: 2 Mpx x 2047 does not fit 2^32).  status bit TDNET_REGIONS_OVERFLOW: count > max_regions.  Bit TDNET_REGIONS_BOUND: a
+ *               bounded loop of the kernels ran out -- never on a correct build; the table is then not to be trusted.
+ *   exact       everything is an integer: the result does not depend on the launch geometry or on the order in which the atomics land.
+ * tdnet_set_regions: configuration (it may synchronise; idempotent for equal arguments; per handle).  It allocates the handle's workspace -- three int32
+ * [H][W] maps, a byte map and a few words, counted in tdnet_memory_bytes -- once.  classes: n class ids on the HOST (duplicates legal, n = 0: the empty
+ * set).  Fails, changing nothing, on a handle that is not finalized, an id >= nclass, n outside 0..256, NULL classes with n > 0, a connectivity other than
+ * 4 or 8, max_regions outside 1..65536 and min_area < 1.  The set (256 membership bits), the connectivity and the two limits travel as kernel
+ * ARGUMENTS read when an entry enqueues: a captured hipGraph replays those of capture time.
+ * The frame entries and the unfused entry only enqueue -- no host synchronisation, no memset or copy calls: every buffer is zeroed by a kernel -- and work
+ * inside a hipGraph capture.  The frame entries keep tdnet_forward_u8_labels' FIFO step, and the labels they write (labels_dev may be NULL, ids_dev too)
+ * are the label entries' labels byte for byte.  Without a prior tdnet_set_regions they fail naming it and change nothing (a pending encoded frame stays
+ * pending).  tdnet_labels_regions, the unfused form on a uint8 label map [H][W] at any byte address, needs no frame state beyond the configuration and
+ * enqueues TDNET_REGIONS_LAUNCHES launches; a frame entry's tdnet_last_launch_count is tdnet_forward_u8_labels' - 1 + TDNET_REGIONS_LAUNCHES: the
+ * frame's label launch IS the first region launch.  One handle's entries share one workspace: enqueue them on one stream, or order them.             */
+#define TDNET_REGIONS_LAUNCHES 7
+#define TDNET_REGIONS_OVERFLOW 1u
+#define TDNET_REGIONS_BOUND    2u
+typedef struct tdnet_regions_header { uint32_t count, stored, status, reserved; } tdnet_regions_header;
+typedef struct tdnet_region { int32_t label, area, x0, y0, x1, y1, first_y, first_x; uint64_t sum_x, sum_y; } tdnet_region;
+int  tdnet_set_regions(tdnet_t* h, const uint8_t* classes /* [n], host: class ids */, int n /* 0..256 */, int connectivity /* 4 | 8 */,
+                       int max_regions /* 1..65536 */, int min_area /* >= 1 */);
+size_t tdnet_regions_bytes(const tdnet_t* h);   /* 16 + 48 max_regions; 0 before tdnet_set_regions */
+int  tdnet_forward_regions(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev,
+                           void* stream);
+int  tdnet_forward_u8_regions(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev,
+                              void* stream);
+int  tdnet_labels_regions(tdnet_t* h, const uint8_t* labels_u8_dev, int32_t* ids_dev /* | NULL */, void* regions_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -577,6 +618,7 @@ int  tdnet_propagate_labels_conf(tdnet_t* h, uint8_t* labels_dev /* | NULL */, u
 int  tdnet_propagate_matte(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t* matte_dev, void* stream);   /* see "matte out" */
 /* the split frame's composite: the caller passes the source again, as for tdnet_propagate_overlay; see "matte out" */
 int  tdnet_propagate_composite(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
+int  tdnet_propagate_regions(tdnet_t* h, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev, void* stream);   /* see "regions out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

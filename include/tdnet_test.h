@@ -200,6 +200,14 @@ int tdnet_op_upsample_argmax_matte(const float* in_dev, int C, int h, int w, int
 int tdnet_op_composite(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8_dev, const uint8_t* src_base,
                        const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* dst_base, const tdnet_view* dst_view, int mode, const uint8_t* bg_rgb,
                        void* stream);
+/* Regions out (include/tdnet.h) through exactly the launches the regions entries enqueue, on maps the caller holds: from low-resolution logits [C,h,w]
+ * (labels_in_u8_dev == NULL; the uint8 labels go to labels_u8_dev [H,W] if given) or from a uint8 label map [H,W] at any byte address (in_dev, h, w and
+ * labels_u8_dev are then ignored).  classes: n class ids below C on the HOST; connectivity 4 | 8; ids_dev: int32 [H,W] or NULL; regions_dev: 16 + 48
+ * max_regions bytes, 8-byte aligned.  The workspace is allocated for the call.                                                                 */
+int tdnet_op_regions(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* labels_in_u8_dev, uint8_t* labels_u8_dev, const uint8_t* classes, int n,
+                     int connectivity, int max_regions, int min_area, int32_t* ids_dev, void* regions_dev, void* stream);
+/* the tile (rows, columns) of the first launch: the tests size their cases from it */
+int tdnet_op_regions_tile(int* th, int* tw);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

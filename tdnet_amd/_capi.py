@@ -126,6 +126,12 @@ SYMBOLS = {
     "tdnet_forward_u8_composite": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_propagate_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_matte_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_regions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "tdnet_regions_bytes": (ctypes.c_size_t, [c_void_p]),
+    "tdnet_forward_regions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_forward_u8_regions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_regions": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_labels_regions": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -197,6 +203,8 @@ TEST_SYMBOLS = {
     "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_matte": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_composite": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, ctypes.c_int] + [c_void_p] * 6 + [ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_regions": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p] + [ctypes.c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_regions_tile": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_enc_first": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 4 + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 5),
     "tdnet_op_conv1x1_src2_null": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,

@@ -14,6 +14,7 @@
 //   td_score.h     (kernels) score out: the confusion matrix against ground truth; its host side is at the end of this file too
 //   td_conf.h      (kernels) confidence out: the softmax probability of the label as a byte, rejection of low-confidence labels
 //   td_matte.h     (kernels) matte out: the softmax mass of a class set as a byte
+//   td_regions.h   (kernels) regions out: connected components of a class set with boxes; its workspace's host side is at the end of this file
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -38,6 +39,7 @@
 #include "td_score.h"
 #include "td_conf.h"
 #include "td_matte.h"
+#include "td_regions.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -321,6 +323,18 @@ struct ScoreOutput {
     unsigned char* dmap = nullptr;                                     // [256]
     size_t bytes = 0;
 };
+// The regions output of a handle (tdnet_set_regions): the configuration -- plain host state, read when an entry enqueues -- and the workspace the seven
+// launches of td_regions.h pass their maps through.  Per handle, like U8Input.
+struct RegionsOutput {
+    bool set = false;
+    MatteSet classes = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    int conn = 8, max_regions = 0, min_area = 1;
+    int H = 0, W = 0;
+    int *parent = nullptr, *root = nullptr, *area = nullptr, *blk = nullptr;   // three int32 [H][W]; the block counts
+    unsigned* flag = nullptr;                                          // one word, zero between runs
+    unsigned char* lab = nullptr;                                      // [H][W]: where a frame's labels go when the caller asks for none
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -412,6 +426,7 @@ struct tdnet {
     OverlayOutput overlay;                                             // tdnet_set_output_overlay
     DstOutput dst;                                                     // tdnet_set_output_view
     ScoreOutput score;                                                // tdnet_set_score
+    RegionsOutput regions;                                            // tdnet_set_regions
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     CompositeOutput comp;                                              // tdnet_set_output_composite
     bool matte_set = false;                                            // tdnet_set_matte: plain host state like min_conf; the *_matte entries pass the words as kernel arguments
@@ -917,5 +932,38 @@ static int score_build(ScoreOutput& c, int nclass, const unsigned char* gt_map, 
     v.set = true;
     score_free(c);
     c = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// regions output: the host side of td_regions.h's workspace
+// ---------------------------------------------------------------------------------------------------------------
+static void regions_free(RegionsOutput& r) {
+    for (int* q : {r.parent, r.root, r.area, r.blk}) if (q) hipFree(q);
+    if (r.flag) hipFree(r.flag);
+    if (r.lab) hipFree(r.lab);
+    r = RegionsOutput();
+}
+static long regions_blocks(int H, int W) { return ((long)H * W + TD_RG_BLOCK - 1) / TD_RG_BLOCK; }
+static size_t regions_table_bytes(int max_regions) { return sizeof(TdRegionsHeader) + (size_t)max_regions * sizeof(TdRegion); }
+// What the kernels can address: a raster index is an int, a wave's coordinate sum 32 bits
+static int regions_size_check(int H, int W, const char* who) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535 || (long)H * W > TD_RG_MAX_PIXELS) return td_fail("%s: a map of %d x %d is outside 1..65535 per side and 2^30 - 16 pixels", who, H, W);
+    return 0;
+}
+// Allocate the workspace of an H x W map (the flag word zeroed) into memory `r` owns; the configuration fields are the caller's.  On failure `r` is left as it was.
+static int regions_alloc(RegionsOutput& r, int H, int W, const char* who) {
+    TD_TRY(regions_size_check(H, W, who));
+    RegionsOutput v;
+    const size_t HW = (size_t)H * W, nblk = (size_t)regions_blocks(H, W);
+    if (dev_alloc(&v.parent, HW) || dev_alloc(&v.root, HW) || dev_alloc(&v.area, HW) || dev_alloc(&v.blk, nblk) || dev_alloc(&v.flag, 1) || dev_alloc(&v.lab, HW)) {
+        regions_free(v);
+        return -1;
+    }
+    if (hipMemset(v.flag, 0, sizeof(unsigned)) != hipSuccess) { regions_free(v); return td_fail("%s: clearing the workspace failed", who); }
+    v.H = H; v.W = W;
+    v.bytes = 3 * HW * sizeof(int) + nblk * sizeof(int) + sizeof(unsigned) + HW;
+    regions_free(r);
+    r = v;
     return 0;
 }

@@ -664,9 +664,50 @@ static int launch_composite(const float* in, int C, int h, int w, const unsigned
     }
     return td_fail("internal: no composite kernel for source form %d into destination form %d", src_form, dst_form);
 }
+// regions out (td_regions.h): the seven launches, from the low-resolution logits (in != NULL: the first launch is the frame's label launch too and writes the
+// label bytes to labels_out, or to the workspace's map where the caller asks for none) or from a uint8 label map [H][W] the caller holds (labels_in, at any
+// byte address).  ids: int32 [H][W] or NULL.  table: regions_table_bytes(r.max_regions) bytes, 8-byte aligned.  `r`: the workspace of this H x W and the
+// configuration, read NOW (kernel arguments: a captured graph replays the ones it was captured with).  Only enqueues: every buffer is zeroed by a kernel.
+static_assert(TD_REGIONS_LAUNCHES == TDNET_REGIONS_LAUNCHES && TD_RG_OVERFLOW == TDNET_REGIONS_OVERFLOW && TD_RG_BOUND == TDNET_REGIONS_BOUND &&
+              sizeof(TdRegion) == sizeof(tdnet_region) && sizeof(TdRegionsHeader) == sizeof(tdnet_regions_header), "td_regions.h and include/tdnet.h disagree");
+static int regions_table_check(const void* table, const char* who) {
+    if (!table) return td_fail("%s: regions_dev is NULL", who);
+    if ((size_t)table & 7u) return td_fail("%s: regions_dev = %p is not 8-byte aligned", who, table);
+    return 0;
+}
+static int run_regions(const float* in, int C, int h, int w, int H, int W, const unsigned char* labels_in, unsigned char* labels_out, int32_t* ids, void* table,
+                       const RegionsOutput& r, hipStream_t s, const char* who) {
+    TD_TRY(regions_table_check(table, who));
+    TD_TRY(regions_size_check(H, W, who));
+    if (C < 1 || C > 256) return td_fail("%s: nclass = %d must be in 1..256", who, C);
+    if (!r.parent || r.H != H || r.W != W) return td_fail("%s: internal: the regions workspace is not that of a %d x %d map", who, H, W);
+    if (r.conn != 4 && r.conn != 8) return td_fail("%s: connectivity = %d must be 4 or 8", who, r.conn);
+    if (r.max_regions < 1 || r.max_regions > 65536 || r.min_area < 1) return td_fail("%s: max_regions = %d must be in 1..65536 and min_area = %d at least 1", who, r.max_regions, r.min_area);
+    RegionsArgs a = RegionsArgs();
+    a.in = in; a.labels = in ? (labels_out ? labels_out : r.lab) : labels_in;
+    a.ids = ids; a.table = (unsigned long long*)table;
+    a.parent = r.parent; a.root = r.root; a.area = r.area; a.blk = r.blk; a.flag = r.flag;
+    a.C = C; a.h = h; a.w = w; a.H = H; a.W = W;
+    a.conn = r.conn; a.max_regions = r.max_regions; a.min_area = r.min_area;
+    a.set = r.classes;
+    a.zero = 0;                                                        // K2's read operand (td_regions.h td_rg_read): a zero the compiler cannot see
+    const dim3 tiles((W + TD_RG_TW - 1) / TD_RG_TW, (H + TD_RG_TH - 1) / TD_RG_TH);
+    const long words = (long)(regions_table_bytes(r.max_regions) / 8), nblk = regions_blocks(H, W);
+    const long row_lanes = (long)((H - 1) / TD_RG_TH) * W, col_lanes = (long)((W - 1) / TD_RG_TW) * H, lanes = row_lanes + (r.conn == 8 ? 2 : 1) * col_lanes;
+    const size_t tile_lds = 2 * TD_RG_TW * TD_RG_TH * sizeof(int);
+    if (in) TD_LAUNCH((k_regions_tile<true>), tiles, dim3(256), tile_lds, s, a, words);
+    else TD_LAUNCH((k_regions_tile<false>), tiles, dim3(256), tile_lds, s, a, words);
+    TD_LAUNCH(k_regions_merge, dim3((unsigned)std::max<long>(1, (lanes + 255) / 256)), dim3(256), 0, s, a, row_lanes, col_lanes);
+    TD_LAUNCH(k_regions_flatten, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    TD_LAUNCH(k_regions_count, dim3((unsigned)nblk), dim3(256), 4 * sizeof(int), s, a);
+    TD_LAUNCH(k_regions_scan, dim3(1), dim3(256), 256 * sizeof(int), s, a, (int)nblk);
+    TD_LAUNCH(k_regions_number, dim3((unsigned)nblk), dim3(256), 260 * sizeof(int), s, a);
+    TD_LAUNCH(k_regions_stats, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    return 0;
+}
 
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS };
 struct FrameOutput {
     OutKind kind;
     void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF, OUT_MATTE: may be NULL) | rgb [oh][ow][3] | overlay, composite [Hs][Ws][3]
@@ -674,11 +715,14 @@ struct FrameOutput {
     const unsigned char* gt;       // OUT_SCORE: ground truth [H][W]
     unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]; OUT_MATTE: matte bytes [H][W]
     const unsigned char* src;      // OUT_OVERLAY, OUT_COMPOSITE: the source frame, read by the handle's byte-input configuration
+    int32_t* ids;                  // OUT_REGIONS: the id map [H][W] (may be NULL; dst: the uint8 labels, may be NULL too)
+    void* table;                   // OUT_REGIONS: the header and the records
 };
 // the handle-side precondition of a form: its tables exist
 static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
     if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
+    if (kind == OUT_REGIONS && !n->regions.set) return td_fail("%s: the regions output is not configured (call tdnet_set_regions first)", who);
     if ((kind == OUT_MATTE || kind == OUT_COMPOSITE) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
     if (kind == OUT_COMPOSITE && !n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
     if (kind == OUT_COMPOSITE && !n->u8.set)
@@ -705,6 +749,7 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
     case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
     case OUT_MATTE: return launch_upsample_argmax_matte_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->matte, s);
     case OUT_COMPOSITE: return launch_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, (unsigned char*)o.dst, s);
+    case OUT_REGIONS: return run_regions(in, C, h, w, H, W, nullptr, (unsigned char*)o.dst, o.ids, o.table, n->regions, s, who);
     case OUT_OVERLAY:
         if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, nullptr, &n->overlay, &n->u8, o.src, n->dst, (unsigned char*)o.dst, s);
         return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);

@@ -145,6 +145,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     rgb_free(n->rgb);
     overlay_free(n->overlay);
     score_free(n->score);
+    regions_free(n->regions);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -691,6 +692,68 @@ extern "C" int tdnet_propagate_composite(tdnet_t* n, const uint8_t* img, uint8_t
     if (!n || !img || !out) return td_fail("tdnet_propagate_composite: null argument");
     TD_TRY(composite_args(n, true, img, out, "tdnet_propagate_composite"));
     return frame_out(n, pending_frame, FrameOutput{OUT_COMPOSITE, out, nullptr, nullptr, img}, stream, "tdnet_propagate_composite");
+}
+// ---- regions out -----------------------------------------------------------------------------------------------------------------------
+// Configuration of the regions output (not a frame call: it may synchronise; idempotent for equal arguments; per handle).  The class set, the connectivity
+// and the two limits are plain host state, passed as kernel arguments when an entry ENQUEUES; the workspace (three int32 maps, a byte map, the block
+// counts) lives in memory this handle owns.  A failed call changes nothing.
+extern "C" int tdnet_set_regions(tdnet_t* n, const uint8_t* classes, int count, int connectivity, int max_regions, int min_area) {
+    const char* who = "tdnet_set_regions";
+    if (!n) return td_fail("%s: null handle", who);
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    if (count < 0 || count > 256) return td_fail("%s: n = %d must be in 0..256", who, count);
+    if (count > 0 && !classes) return td_fail("%s: classes is NULL with n = %d", who, count);
+    if (connectivity != 4 && connectivity != 8) return td_fail("%s: connectivity = %d must be 4 or 8", who, connectivity);
+    if (max_regions < 1 || max_regions > 65536) return td_fail("%s: max_regions = %d must be in 1..65536", who, max_regions);
+    if (min_area < 1) return td_fail("%s: min_area = %d must be at least 1", who, min_area);
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < count; ++i) {
+        if (classes[i] >= n->cfg.nclass) return td_fail("%s: classes[%d] = %d is not a class id (nclass = %d)", who, i, (int)classes[i], n->cfg.nclass);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);              // duplicates are legal
+    }
+    TD_ON_DEVICE(n, -1);
+    if (!n->regions.parent) {                                          // the workspace depends on the handle's size alone: allocated once
+        const size_t before = n->regions.bytes;
+        TD_TRY(regions_alloc(n->regions, n->H, n->W, who));
+        n->ws_bytes += n->regions.bytes - before;
+    }
+    RegionsOutput& r = n->regions;
+    r.classes = set; r.conn = connectivity; r.max_regions = max_regions; r.min_area = min_area;
+    r.set = true;
+    return 0;
+}
+extern "C" size_t tdnet_regions_bytes(const tdnet_t* n) { return n && n->regions.set ? regions_table_bytes(n->regions.max_regions) : 0; }
+// What every regions entry checks on the host before anything is enqueued: the configuration exists and the table can be addressed
+static int regions_args(const tdnet* n, const void* table, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(output_configured(n, OUT_REGIONS, who));
+    return regions_table_check(table, who);
+}
+// The labels entries with another tail: the frame's label launch is the first of the TDNET_REGIONS_LAUNCHES region launches.  Same frame, same FIFO step;
+// labels and ids may each be NULL.
+extern "C" int tdnet_forward_regions(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, int32_t* ids, void* regions_dev, void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_regions: null argument");
+    TD_TRY(regions_args(n, regions_dev, "tdnet_forward_regions"));
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_REGIONS, labels, nullptr, nullptr, nullptr, ids, regions_dev}, stream, "tdnet_forward_regions");
+}
+extern "C" int tdnet_forward_u8_regions(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, int32_t* ids, void* regions_dev, void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_u8_regions: null argument");
+    TD_TRY(regions_args(n, regions_dev, "tdnet_forward_u8_regions"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_REGIONS, labels, nullptr, nullptr, nullptr, ids, regions_dev}, stream, "tdnet_forward_u8_regions");
+}
+extern "C" int tdnet_propagate_regions(tdnet_t* n, uint8_t* labels, int32_t* ids, void* regions_dev, void* stream) {
+    if (!n) return td_fail("tdnet_propagate_regions: null argument");
+    TD_TRY(regions_args(n, regions_dev, "tdnet_propagate_regions"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_REGIONS, labels, nullptr, nullptr, nullptr, ids, regions_dev}, stream, "tdnet_propagate_regions");
+}
+// the unfused form: from a uint8 label map [H][W] the caller holds (at any byte address); needs no frame state beyond the configuration
+extern "C" int tdnet_labels_regions(tdnet_t* n, const uint8_t* labels, int32_t* ids, void* regions_dev, void* stream) {
+    if (!n || !labels) return td_fail("tdnet_labels_regions: null argument");
+    TD_TRY(regions_args(n, regions_dev, "tdnet_labels_regions"));
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(run_regions(nullptr, n->cfg.nclass, 0, 0, n->H, n->W, labels, nullptr, ids, regions_dev, n->regions, (hipStream_t)stream, "tdnet_labels_regions"));
+    TD_HIP(hipGetLastError());
+    return 0;
 }
 extern "C" int tdnet_cache_dims(const tdnet_t* n, int* Lk, int* dk, int* dv) {
     if (!n) return td_fail("tdnet_cache_dims: null handle");

@@ -870,3 +870,34 @@ extern "C" double tdnet_bench_conv(int H, int W, int Cin, int Cout, int KS, int 
     free_conv_layer(L);
     return ms / iters;
 }
+// Regions out (include/tdnet.h) through exactly the seven launches the entries enqueue, on maps the caller holds: from low-resolution logits [C][h][w]
+// (labels_in == NULL: the labels go to labels_out [H][W] if given) or from a uint8 label map [H][W] at any byte address (in, h, w, labels_out are then
+// ignored).  classes: n class ids below C on the host.  ids: int32 [H][W] or NULL; regions: 16 + 48 * max_regions bytes, 8-byte aligned.  The workspace is
+// allocated here and released before the call returns.
+extern "C" int tdnet_op_regions(const float* in, int C, int h, int w, int H, int W, const uint8_t* labels_in, uint8_t* labels_out, const uint8_t* classes, int n,
+                                int connectivity, int max_regions, int min_area, int32_t* ids, void* regions, void* stream) {
+    const char* who = "tdnet_op_regions";
+    if (C < 1 || C > 256 || H < 1 || W < 1) return td_fail("%s: C in 1..256 and a size >= 1 x 1 expected", who);
+    if (!labels_in && (!in || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] or a label map expected", who);
+    if (n < 0 || n > 256 || (n > 0 && !classes)) return td_fail("%s: n in 0..256 class ids expected", who);
+    RegionsOutput r;
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < n; ++i) {
+        if (classes[i] >= C) return td_fail("%s: classes[%d] = %d is not a class id (C = %d)", who, i, (int)classes[i], C);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);
+    }
+    TD_TRY(regions_table_check(regions, who));
+    TD_TRY(regions_alloc(r, H, W, who));
+    r.classes = set; r.conn = connectivity; r.max_regions = max_regions; r.min_area = min_area; r.set = true;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_regions(labels_in ? nullptr : in, C, h, w, H, W, labels_in, labels_out, ids, regions, r, s, who);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    regions_free(r);
+    return rc;
+}
+// the tile of the first launch: the tests size their cases from it
+extern "C" int tdnet_op_regions_tile(int* th, int* tw) {
+    if (th) *th = TD_RG_TH;
+    if (tw) *tw = TD_RG_TW;
+    return 0;
+}

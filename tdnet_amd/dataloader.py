@@ -564,6 +564,81 @@ def composite_u8(src_rgb, matte, H, W, bg=None):
     return out.astype(np.uint8)
 
 
+# One record of the library's regions table (include/tdnet.h tdnet_region, 48 bytes): the box is inclusive, the centroid is sum / area
+REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("first_y", "<i4"), ("first_x", "<i4"),
+                         ("sum_x", "<u8"), ("sum_y", "<u8")])
+REGIONS_HEADER_DTYPE = np.dtype([("count", "<u4"), ("stored", "<u4"), ("status", "<u4"), ("reserved", "<u4")])
+REGIONS_OVERFLOW, REGIONS_BOUND = 1, 2                               # header status bits
+
+
+def regions_u8(labels, classes, connectivity=8, min_area=1, max_regions=256):
+    """The oracle of the library's regions output (include/tdnet.h "regions out"): (ids int32 [H, W], count, table).  labels [H, W] uint8; classes the
+    ids of the set.  A region is a maximal set of pixels whose label is in the set, connected (4 or 8 neighbours) through pixels of the SAME label.
+    A plain flood fill started at every unvisited member pixel in raster order: the start is the region's first pixel, so the regions come out
+    by growing key.  Regions below min_area are dropped, the others numbered from 1; ids holds the number (0: background or dropped), also beyond
+    max_regions; table is a REGION_DTYPE array of min(count, max_regions) records, record i for region i + 1."""
+    lab = np.asarray(labels)
+    assert lab.ndim == 2 and lab.dtype == np.uint8 and connectivity in (4, 8) and min_area >= 1 and max_regions >= 1
+    H, W = lab.shape
+    member = set(int(c) for c in classes)
+    flat = lab.reshape(-1).tolist()
+    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (-1, 1), (1, -1), (1, 1)] if connectivity == 8 else [])
+    seen = [False] * (H * W)
+    found = []                                                         # (pixels, record) by growing first pixel
+    for start in range(H * W):
+        l = flat[start]
+        if seen[start] or l not in member:
+            continue
+        seen[start] = True
+        stack, pixels = [start], []
+        while stack:
+            p = stack.pop()
+            pixels.append(p)
+            y, x = divmod(p, W)
+            for dy, dx in steps:
+                yy, xx = y + dy, x + dx
+                if 0 <= yy < H and 0 <= xx < W:
+                    q = yy * W + xx
+                    if not seen[q] and flat[q] == l:
+                        seen[q] = True
+                        stack.append(q)
+        if len(pixels) < min_area:
+            continue
+        ys, xs = [p // W for p in pixels], [p % W for p in pixels]
+        found.append((pixels, (l, len(pixels), min(xs), min(ys), max(xs), max(ys), start // W, start % W, sum(xs), sum(ys))))
+    ids = np.zeros(H * W, np.int32)
+    for k, (pixels, _) in enumerate(found):
+        ids[pixels] = k + 1
+    table = np.array([rec for _, rec in found[:max_regions]], dtype=REGION_DTYPE) if found else np.zeros(0, REGION_DTYPE)
+    return ids.reshape(H, W), len(found), table
+
+
+class RegionTable(np.ndarray):
+    """REGION_DTYPE records of the regions a frame's table holds (record i: region i + 1), with the header's .count (all regions found, which may
+    exceed len()) and .status (REGIONS_OVERFLOW: count > max_regions) as attributes."""
+    count = 0
+    status = 0
+
+    def __array_finalize__(self, obj):
+        self.count = getattr(obj, "count", 0)
+        self.status = getattr(obj, "status", 0)
+
+
+def region_table(buf, max_regions):
+    """The table the library wrote (16 + 48 * max_regions bytes) as a RegionTable of its `stored` records (a copy)."""
+    hdr, recs = regions_unpack(buf, max_regions)
+    t = recs[:int(hdr["stored"])].copy().view(RegionTable)
+    t.count, t.status = int(hdr["count"]), int(hdr["status"])
+    return t
+
+
+def regions_unpack(buf, max_regions):
+    """A regions table as the library writes it (bytes, or a uint8 array of 16 + 48 * max_regions) -> (header record, REGION_DTYPE [max_regions])."""
+    raw = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    assert raw.size == 16 + 48 * max_regions, (raw.size, max_regions)
+    return raw[:16].view(REGIONS_HEADER_DTYPE)[0], raw[16:].view(REGION_DTYPE)
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],

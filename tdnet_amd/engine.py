@@ -359,6 +359,32 @@ class Engine:
     def matte_composite(self, matte_ptr, img_ptr, out_ptr, stream=None):
         self.lib.check(self.lib.tdnet_matte_composite(self.h, _ptr(matte_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
 
+    # ---- regions out (include/tdnet.h) ----
+    def set_regions(self, classes, connectivity=8, max_regions=256, min_area=1):
+        """The *_regions entries will label the connected components (4 or 8 neighbours, same label) of this class set, drop those below min_area and
+        describe the first max_regions in their table.  A configuration call: allocates this handle's workspace once."""
+        ids = [int(c) for c in classes]
+        if len(ids) > 256 or any(c < 0 or c > 255 for c in ids):
+            raise _capi.TdnetError("set_regions: at most 256 class ids in 0..255")
+        buf = (ctypes.c_uint8 * max(1, len(ids)))(*ids)
+        self.lib.check(self.lib.tdnet_set_regions(self.h, buf if ids else None, len(ids), int(connectivity), int(max_regions), int(min_area)))
+
+    def regions_bytes(self):
+        """bytes of the table the regions entries write (16 + 48 * max_regions; 8-byte aligned device memory of the caller's); 0 before set_regions"""
+        return int(self.lib.tdnet_regions_bytes(self.h))
+
+    def forward_regions(self, img_ptr, pos_id, labels_ptr, ids_ptr, regions_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_regions(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), stream))
+
+    def forward_u8_regions(self, img_ptr, pos_id, labels_ptr, ids_ptr, regions_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_regions(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), stream))
+
+    def propagate_regions(self, labels_ptr, ids_ptr, regions_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_regions(self.h, _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), stream))
+
+    def labels_regions(self, labels_ptr, ids_ptr, regions_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_labels_regions(self.h, _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

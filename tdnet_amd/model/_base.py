@@ -1006,6 +1006,106 @@ class _TDNetBase(nn.Module):
             self._engine.logits_matte(logits[i].data_ptr(), out[i].data_ptr(), matte[i].data_ptr(), s)
         return out, matte
 
+    # ---- regions out (not in the reference's model; a caller of the reference downloads the labels and runs a connected-components pass on the host) ----
+    # The connected components of a class set of the frame's labels, numbered by their first pixel, with area, box and coordinate sums (include/tdnet.h
+    # "regions out").  Every method returns (labels uint8 [N, H, W], ids int32 [N, H, W] or None, [dataloader.RegionTable per sample]); reading the tables
+    # synchronises with the device.
+    _regions = None
+
+    def set_regions(self, classes, connectivity=8, max_regions=256, min_area=1):
+        """The configuration of the *_regions methods: an iterable of class ids below nclass (duplicates are legal, empty = no region at all), 4 or 8
+        neighbours, the number of records of the table (1..65536; more regions than that are still counted and numbered in the id map) and the area below
+        which a region is dropped.  Host state of the model; every handle is told when it runs."""
+        try:
+            ids = list(classes)
+        except TypeError:
+            raise RuntimeError("set_regions(): classes must be an iterable of class ids, got %r" % (classes,))
+        for c in ids:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < self.nclass:
+                raise RuntimeError("set_regions(): %r is not a class id (0..%d)" % (c, self.nclass - 1))
+        if connectivity not in (4, 8):
+            raise RuntimeError("set_regions(): connectivity must be 4 or 8, got %r" % (connectivity,))
+        if not 1 <= int(max_regions) <= 65536 or int(min_area) < 1:
+            raise RuntimeError("set_regions(): max_regions must be in 1..65536 and min_area at least 1, got %r and %r" % (max_regions, min_area))
+        self._regions = (tuple(sorted(set(int(c) for c in ids))), int(connectivity), int(max_regions), int(min_area))
+        return self._regions
+
+    def _need_regions(self, who):
+        if self._regions is None:
+            raise RuntimeError("%s(): no configuration (call set_regions(classes) first)" % who)
+        return self._regions
+
+    def _regions_out(self, n, H, W, device, return_ids):
+        max_regions = self._regions[2]
+        out = torch.empty((n, H, W), device=device, dtype=torch.uint8)
+        ids = torch.empty((n, H, W), device=device, dtype=torch.int32) if return_ids else None
+        table = torch.empty((n, 2 + 6 * max_regions), device=device, dtype=torch.int64)   # 16 + 48 * max_regions bytes per sample, 8-byte aligned
+        return out, ids, table
+
+    def _regions_tables(self, table):
+        from ..dataloader import region_table
+        host = table.cpu().numpy()
+        return [region_table(host[i], self._regions[2]) for i in range(host.shape[0])]
+
+    def forward_regions(self, img, pos_id=0, return_ids=True):
+        """forward_labels() with the regions of set_regions()'s class set behind the labels."""
+        cfg = self._need_regions("forward_regions")
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        out, ids, table = self._regions_out(img.shape[0], img.shape[2], img.shape[3], img.device, return_ids)
+
+        def one(i, eng, s):
+            eng.set_regions(*cfg)
+            eng.forward_regions(img[i].data_ptr(), pos_id, out[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out, ids, self._regions_tables(table)
+
+    def forward_regions_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None, return_ids=True):
+        """forward_labels_u8() with the regions behind the labels: bytes in (any byte-input configuration: view= / surface= as there)."""
+        cfg = self._need_regions("forward_regions_u8")
+        view = self._one_of(view, surface, "view", "surface")
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        img = img_u8.contiguous()
+        out, ids, table = self._regions_out(img.shape[0], H, W, img.device, return_ids)
+
+        def one(i, eng, s):
+            eng.set_regions(*cfg)
+            eng.forward_u8_regions(img[i].data_ptr(), pos_id, out[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out, ids, self._regions_tables(table)
+
+    def regions_labels(self, labels_u8, return_ids=True):
+        """The unfused form: uint8 labels [N, H, W] (CUDA) of this model's size -- the label entries', or the confidence entries' with rejected pixels,
+        which are background -- sample i on handle i.  Returns the labels as given."""
+        cfg = self._need_regions("regions_labels")
+        if self._engine is None:
+            raise RuntimeError("regions_labels(): no handle yet")
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != (H, W):
+            raise RuntimeError("regions_labels(): expected uint8 labels [N, %d, %d]" % (H, W))
+        labels = labels_u8.contiguous()
+        engines = [self._engine] + list(self._extra_engines)
+        if labels.shape[0] > len(engines):
+            raise RuntimeError("regions_labels(): %d label maps but %d handle(s)" % (labels.shape[0], len(engines)))
+        _, ids, table = self._regions_out(labels.shape[0], H, W, labels.device, return_ids)
+        s = torch.cuda.current_stream(labels.device).cuda_stream
+        for i in range(labels.shape[0]):
+            engines[i].set_regions(*cfg)
+            engines[i].labels_regions(labels[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(), s)
+        return labels, ids, self._regions_tables(table)
+
+    def propagate_regions(self, return_ids=True):
+        """propagate() with the regions behind the labels, for the frame encode() / encode_u8() left pending."""
+        cfg = self._need_regions("propagate_regions")
+        if self._engine is None or self._pending_shape is None:
+            raise RuntimeError("propagate_regions(): no encoded frame is pending (call encode(img, pos_id) first)")
+        H, W, dev = self._pending_shape
+        out, ids, table = self._regions_out(1, H, W, dev, return_ids)
+        self._engine.set_regions(*cfg)
+        self._pending_shape = None
+        self._engine.propagate_regions(out.data_ptr(), None if ids is None else ids.data_ptr(), table.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out, ids, self._regions_tables(table)
+
     @staticmethod
     def _background(background):
         if background is None:

@@ -33,6 +33,9 @@ destination surface, appended to the raw file.
 softmax mass of that class set as a byte, 255 = certainly one of them (include/tdnet.h "matte out") -- and saves it at the network size as an 8-bit
 grey PNG DIR/folder/name beside the usual picture.  `--matte IDS --composite R,G,B` (with `--u8`, `--nv12` or `--yuv`) writes, where the overlay's
 picture would go, the frame seen through the matte over that background, at the frame's own (`--crop`: the rectangle's) size.
+`--regions IDS` (a comma list of class ids; `--regions_conn 4|8`, `--regions_min_area N`) labels the connected components of those classes on the device
+behind every frame's labels (include/tdnet.h "regions out") and prints the count per frame; `--regions_out DIR` writes one CSV per frame,
+DIR/folder/name.csv: id,label,area,x0,y0,x1,y1,cx,cy in network-size pixels.
 """
 import argparse
 import os
@@ -62,6 +65,19 @@ def load_ground_truth(gt_path, items, size, nearest_index, pin):
         t = torch.from_numpy(np.ascontiguousarray(g)[np.newaxis])
         out.append([t.pin_memory() if pin else t])
     return out
+
+
+REGIONS_CLI_MAX = 4096                                                 # records of --regions' table: regions beyond are counted, not written
+
+
+def regions_csv(table):
+    """The text --regions_out writes for one frame's records (REGION_DTYPE; record i is region i + 1): id,label,area,x0,y0,x1,y1,cx,cy with the
+    centroid sum / area to three decimals."""
+    lines = ["id,label,area,x0,y0,x1,y1,cx,cy"]
+    for i, r in enumerate(table):
+        lines.append("%d,%d,%d,%d,%d,%d,%d,%.3f,%.3f" % (i + 1, r["label"], r["area"], r["x0"], r["y0"], r["x1"], r["y1"],
+                                                         int(r["sum_x"]) / int(r["area"]), int(r["sum_y"]) / int(r["area"])))
+    return "\n".join(lines) + "\n"
 
 
 def yuv_surface(layout, height, width, standard, crop=None):
@@ -135,6 +151,26 @@ def test(args):
             if len(composite) != 3 or any(v < 0 or v > 255 for v in composite):
                 raise SystemExit("--composite: R,G,B expected (the background, three byte values), got %r" % (args.composite,))
     with_matte = matte_ids is not None
+    region_ids, regions_dir = getattr(args, "regions", None), getattr(args, "regions_out", None)
+    regions_conn, regions_min_area = getattr(args, "regions_conn", None), getattr(args, "regions_min_area", None)
+    if region_ids is not None or regions_dir is not None or regions_conn is not None or regions_min_area is not None:   # checked before anything is loaded
+        if region_ids is None:
+            raise SystemExit("--regions_conn, --regions_min_area and --regions_out need the class set: give --regions IDS (a comma list of class ids) with them")
+        try:
+            region_ids = tuple(int(v) for v in str(region_ids).split(",") if v.strip() != "")
+        except ValueError:
+            region_ids = (-1,)
+        if any(c < 0 or c >= 19 for c in region_ids):
+            raise SystemExit("--regions: a comma list of class ids in 0..18 expected, got %r" % (args.regions,))
+        regions_conn = 8 if regions_conn is None else regions_conn
+        regions_min_area = 1 if regions_min_area is None else regions_min_area
+        if regions_conn not in (4, 8) or regions_min_area < 1:
+            raise SystemExit("--regions_conn: 4 or 8 expected, --regions_min_area: at least 1; got %r and %r" % (regions_conn, regions_min_area))
+        if rgb or overlay is not None or with_matte or getattr(args, "gt_path", None) or getattr(args, "prefetch", False) or getattr(args, "conf", None) is not None or \
+                getattr(args, "min_conf", None) is not None or getattr(args, "out_nv12", None) is not None or getattr(args, "out_yuv", None) is not None:
+            raise SystemExit("--regions asks for a tail of its own in the frame-by-frame loop: not with --rgb, --overlay, --matte, --gt_path, --prefetch, --conf, --min_conf, "
+                             "--out_nv12 or --out_yuv")
+    with_regions = region_ids is not None
     out_nv12, out_yuv = getattr(args, "out_nv12", None), getattr(args, "out_yuv", None)
     out_layout = None
     if out_yuv is not None:                                            # LAYOUT:FILE; checked before anything is loaded
@@ -197,6 +233,13 @@ def test(args):
 
     if with_matte:
         model.set_matte(matte_ids)
+    if with_regions:
+        model.set_regions(region_ids, regions_conn, REGIONS_CLI_MAX, regions_min_area)
+
+    def save_regions(table, img_name, folder):                         # --regions_out: one CSV per frame; the centroid is sum / area
+        os.makedirs(os.path.join(regions_dir, folder), exist_ok=True)
+        with open(os.path.join(regions_dir, folder, os.path.splitext(img_name)[0] + ".csv"), "w") as f:
+            f.write(regions_csv(table))
 
     def print_scores():                                                # Training/validate.py:91-97
         if gts is None:
@@ -249,7 +292,7 @@ def test(args):
             v = SourceView(PIX_RGB24, int(image.shape[1]), int(image.shape[2]), crop=crop)
         return image.reshape(1, -1), v
 
-    as_view = crop is not None or (nv12 and with_matte)                # --matte: an NV12 surface goes through the byte methods as the whole NV12 view (through_view with no crop)
+    as_view = crop is not None or (nv12 and (with_matte or with_regions))   # --matte, --regions: an NV12 surface goes through the byte methods as the whole NV12 view (through_view with no crop)
     nvp, byte = nv12 and not as_view, u8 or as_view or yuv is not None   # with --crop an NV12 surface goes through the byte methods too, as an NV12 view
     described = as_view or yuv is not None                             # the frame goes up WHOLE with a description: a source view, or (--yuv) a surface
 
@@ -360,6 +403,9 @@ def test(args):
                 output = model.forward_composite_u8(image, i % path_num, (H, W), background=composite, **vk(view))
             elif with_matte:
                 output, matte = model.forward_matte_u8(image, i % path_num, (H, W), **vk(view)) if byte else model.forward_matte(image, i % path_num)
+            elif with_regions:
+                output, _, tables = model.forward_regions_u8(image, i % path_num, (H, W), return_ids=False, **vk(view)) if byte else \
+                    model.forward_regions(image, i % path_num, return_ids=False)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size, view)
             elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
@@ -386,6 +432,11 @@ def test(args):
                 save(output.cpu().numpy(), img_name, folder, ori_size)
             elif with_matte and composite is None:
                 save_matte(output.cpu().numpy(), matte.cpu().numpy(), img_name, folder, ori_size)
+            elif with_regions:                                         # the usual picture of the uint8 labels, and the frame's regions
+                save(output.cpu().numpy(), img_name, folder, ori_size)
+                print(" Frame {0:2d}   {1:d} regions{2:s}".format(i + 1, tables[0].count, "" if tables[0].count == len(tables[0]) else " (%d in the table)" % len(tables[0])))
+                if regions_dir is not None:
+                    save_regions(tables[0], img_name, folder)
             elif rgb or overlay is not None or composite is not None:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
                 if overlay is not None and conf_dir is not None:
@@ -428,6 +479,10 @@ if __name__ == "__main__":
     parser.add_argument("--matte", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13,14,15,16,17,18): the class set of --matte_out / --composite")
     parser.add_argument("--matte_out", nargs="?", type=str, default=None, help="with --matte: directory for each frame's matte (8-bit grey PNG at the network size; 255 = certainly a member of the set)")
     parser.add_argument("--composite", nargs="?", type=str, default=None, help="with --matte and --u8, --nv12 or --yuv: R,G,B -- write the frame seen through the matte over this background, at the frame's own size, where the overlay's picture would go")
+    parser.add_argument("--regions", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13): label the connected components of these classes on the device behind every frame's labels")
+    parser.add_argument("--regions_conn", nargs="?", type=int, default=None, help="with --regions: 4 or 8 neighbours (default 8)")
+    parser.add_argument("--regions_min_area", nargs="?", type=int, default=None, help="with --regions: drop regions of fewer pixels (default 1)")
+    parser.add_argument("--regions_out", nargs="?", type=str, default=None, help="with --regions: directory for one CSV per frame: id,label,area,x0,y0,x1,y1,cx,cy (network-size pixels, inclusive box)")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
     parser.add_argument("--yuv", nargs="?", type=str, default=None, help="frames go to the device as tight surfaces of this layout (nv12, nv21, i420, p010, yuy2, uyvy; --nv12_standard): conversion, resize and normalisation in the frame's first launch; combines with what --nv12 combines with, --crop included")
