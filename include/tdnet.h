@@ -591,7 +591,61 @@ int  tdnet_forward_regions(tdnet_t* h, const float* img_nchw_dev, int pos_id, ui
 int  tdnet_forward_u8_regions(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev,
                               void* stream);
 int  tdnet_labels_regions(tdnet_t* h, const uint8_t* labels_u8_dev, int32_t* ids_dev /* | NULL */, void* regions_dev, void* stream);
-/* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).                     */
+/* ---- tracks out ----------------------------------------------------------------------------------------------------
+ * A region's number is the raster rank of its first pixel: it changes whenever anything appears above the object.  A tracker, a counter or an alert
+ * needs to know that region 3 of this frame is region 5 of the last one.  These entries are the regions entries plus a match of this frame's regions
+ * against those of the previous tracked frame of the handle, by pixel overlap, on the device -- instead of a download of two id maps per frame and a
+ * count of their overlaps on a host core.  ids, count, stored and the records are those of "regions out" for the current frame under the regions
+ * configuration in force; ids', stored', label'[p], track'[p], age'[p] are those of the previous tracked frame, kept in device memory the handle owns.
+ * Only regions that have a record take part: a pixel whose id is 0 or greater than stored is background here, likewise with stored' on the other side.
+ *   overlap     n(p, c) = the pixels with ids'[i] == p and ids[i] == c, for 1 <= p <= stored', 1 <= c <= stored and label'[p] == label[c]: a track
+ *               keeps its class; pairs of different labels have n = 0.
+ *   partners    bp(c) = the p with the largest n(p, c) > 0, ties to the smallest p, 0 if there is none; bc(p) = the c with the largest n(p, c) > 0,
+ *               ties to the smallest c, 0 if there is none.
+ *   match       c continues p iff bp(c) == p, bc(p) == c and n(p, c) >= min_overlap: track[c] = track'[p], age[c] = age'[p] + 1, prev_region = p,
+ *               overlap = n(p, c), origin_track = track[c].
+ *   birth       every other c is born: age = 1, prev_region = 0, overlap = 0, origin_track = track'[bp(c)] if bp(c) != 0 (the track it split from or
+ *               re-formed out of), else 0.  Born regions take the ids next, next + 1, ... in growing c; next starts at 1 and advances by the number of
+ *               births.  A track id is never 0; behaviour after 2^32 - 1 births is unspecified.
+ *   first frame after tdnet_set_tracks on a fresh handle, and after tdnet_tracks_reset, stored' = 0: every region is born and next = 1.
+ *   memory      ONE frame: a track with no mutual partner ends and is not found again later.  Re-identification (appearance, motion models, occlusion
+ *               handling) is out of scope: a caller who needs it builds it on origin_track, the boxes and the centroids.
+ *   table       a device buffer of tdnet_tracks_bytes = 16 + 24 max_regions bytes, 8-byte aligned (any other alignment is refused, the message naming
+ *               tracks_dev): a header tdnet_tracks_header {count = stored, matched, ended = the previous regions 1..stored' without a match, status},
+ *               then max_regions records tdnet_track; record i belongs to region i + 1 of the regions table written by the same call; records from
+ *               index stored on are zero.  status bit TDNET_TRACKS_BOUND: a bounded loop of the kernels ran out -- never on a correct build.  There is
+ *               no overflow bit: the internal pair table is sized for every pixel carrying a pair of its own.
+ *   track map   optional: int32 [H][W], the track id of the pixel's region; 0 for background, for dropped regions and for regions beyond the table.
+ *   exact       everything is an integer: the result does not depend on the launch geometry, on where a pair lands in any internal table or on the
+ *               order in which atomics arrive.
+ * tdnet_set_tracks: configuration, like tdnet_set_regions (it may synchronise; idempotent: a second call changes min_overlap and keeps the tracks; per
+ * handle; independent of the order of the other tdnet_set_* calls).  It allocates the state once, sized from the handle alone (H, W and the ceiling of
+ * 65536 regions: two int32 [H][W] maps, a pair table of 8-byte slots, the power of two >= 2 H W of them, and 28 bytes per possible region), counted in
+ * tdnet_memory_bytes.  A later tdnet_set_regions with other arguments needs no reallocation: it changes what the next frame's ids are, and the match is
+ * defined on the two id maps as they are.  min_overlap travels as a kernel ARGUMENT read when an entry enqueues.  Fails, changing nothing, on
+ * min_overlap < 1 and on a handle that is not finalized.
+ * The frame entries and the unfused entry are the regions entries plus TDNET_TRACKS_LAUNCHES launches: labels, id map and regions table are the same
+ * byte for byte, the FIFO step is the same, tdnet_last_launch_count is the regions entry's + TDNET_TRACKS_LAUNCHES.  They only enqueue -- no host
+ * synchronisation, no memset or copy calls -- and ALL state between frames (previous ids, labels, tracks, ages, stored', next) lives at fixed device
+ * addresses; nothing on the host changes per frame, so a captured hipGraph replays as the eager loop does, and successive replays continue the tracks.
+ * They fail -- changing nothing, naming the call and the field, a pending encoded frame stays pending -- without tdnet_set_regions or tdnet_set_tracks
+ * (the message names the missing call) and on a NULL or misaligned table.  A regions entry or a label entry between two tracked frames does not touch
+ * the track state: the "previous frame" is the previous TRACKED frame.  tdnet_tracks_reset is enqueued on the stream (one launch) and ordered like a
+ * frame entry.  tdnet_reset does NOT touch the track state: it has no stream to order the change against.                                       */
+#define TDNET_TRACKS_LAUNCHES 4
+#define TDNET_TRACKS_BOUND    1u
+typedef struct tdnet_tracks_header { uint32_t count, matched, ended, status; } tdnet_tracks_header;
+typedef struct tdnet_track { uint32_t track, age, prev_region, overlap, origin_track, reserved; } tdnet_track;
+int  tdnet_set_tracks(tdnet_t* h, int min_overlap /* >= 1 */);
+size_t tdnet_tracks_bytes(const tdnet_t* h);   /* 16 + 24 max_regions; 0 until both tdnet_set_regions and tdnet_set_tracks */
+int  tdnet_forward_tracks(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev,
+                          int32_t* track_ids_dev /* | NULL */, void* tracks_dev, void* stream);
+int  tdnet_forward_u8_tracks(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev,
+                             int32_t* track_ids_dev /* | NULL */, void* tracks_dev, void* stream);
+int  tdnet_labels_tracks(tdnet_t* h, const uint8_t* labels_u8_dev, int32_t* ids_dev /* | NULL */, void* regions_dev, int32_t* track_ids_dev /* | NULL */,
+                         void* tracks_dev, void* stream);
+int  tdnet_tracks_reset(tdnet_t* h, void* stream);   /* enqueued */
+/* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).  The track state of "tracks out" stays: tdnet_tracks_reset. */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
 
@@ -619,6 +673,8 @@ int  tdnet_propagate_matte(tdnet_t* h, uint8_t* labels_dev /* | NULL */, uint8_t
 /* the split frame's composite: the caller passes the source again, as for tdnet_propagate_overlay; see "matte out" */
 int  tdnet_propagate_composite(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
 int  tdnet_propagate_regions(tdnet_t* h, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev, void* stream);   /* see "regions out" */
+int  tdnet_propagate_tracks(tdnet_t* h, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev, int32_t* track_ids_dev /* | NULL */,
+                            void* tracks_dev, void* stream);   /* see "tracks out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

@@ -208,6 +208,15 @@ int tdnet_op_regions(const float* in_dev, int C, int h, int w, int H, int W, con
                      int connectivity, int max_regions, int min_area, int32_t* ids_dev, void* regions_dev, void* stream);
 /* the tile (rows, columns) of the first launch: the tests size their cases from it */
 int tdnet_op_regions_tile(int* th, int* tw);
+/* Tracks out (include/tdnet.h) through exactly the launches the tracks entries enqueue, one frame per call, from a uint8 label map [H,W] at any byte
+ * address.  state_dev: tdnet_op_tracks_state_bytes(H, W) bytes the CALLER owns, 16-byte aligned; all zero is the reset state, and the blob carries the
+ * tracks from call to call.  ids_dev, track_ids_dev: int32 [H,W] or NULL; regions_dev: 16 + 48 max_regions bytes, tracks_dev: 16 + 24 max_regions bytes,
+ * both 8-byte aligned.  The regions workspace is allocated for the call.                                                                       */
+size_t tdnet_op_tracks_state_bytes(int H, int W);
+int tdnet_op_tracks(const uint8_t* labels_u8_dev, int C, int H, int W, const uint8_t* classes, int n, int connectivity, int max_regions, int min_area, int min_overlap,
+                    void* state_dev, int32_t* ids_dev, void* regions_dev, int32_t* track_ids_dev, void* tracks_dev, void* stream);
+/* the slots of the internal pair table for an H x W map (a power of two >= 2 H W): the tests size the worst case from it */
+long tdnet_op_tracks_capacity(int H, int W);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

@@ -15,6 +15,7 @@
 //   td_conf.h      (kernels) confidence out: the softmax probability of the label as a byte, rejection of low-confidence labels
 //   td_matte.h     (kernels) matte out: the softmax mass of a class set as a byte
 //   td_regions.h   (kernels) regions out: connected components of a class set with boxes; its workspace's host side is at the end of this file
+//   td_tracks.h    (kernels) tracks out: region identity across frames by pixel overlap; its state's host side is at the end of this file
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -40,6 +41,7 @@
 #include "td_conf.h"
 #include "td_matte.h"
 #include "td_regions.h"
+#include "td_tracks.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -335,6 +337,15 @@ struct RegionsOutput {
     unsigned char* lab = nullptr;                                      // [H][W]: where a frame's labels go when the caller asks for none
     size_t bytes = 0;
 };
+// The tracks output of a handle (tdnet_set_tracks): min_overlap -- plain host state, a kernel argument read when an entry enqueues -- and ONE device
+// blob that holds everything that lives between frames (td_tracks.h TracksState) at fixed addresses: nothing on the host changes per frame.
+struct TracksOutput {
+    bool set = false;
+    int min_overlap = 1;
+    void* blob = nullptr;
+    TracksState st = TracksState();
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -427,6 +438,7 @@ struct tdnet {
     DstOutput dst;                                                     // tdnet_set_output_view
     ScoreOutput score;                                                // tdnet_set_score
     RegionsOutput regions;                                            // tdnet_set_regions
+    TracksOutput tracks;                                              // tdnet_set_tracks
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     CompositeOutput comp;                                              // tdnet_set_output_composite
     bool matte_set = false;                                            // tdnet_set_matte: plain host state like min_conf; the *_matte entries pass the words as kernel arguments
@@ -965,5 +977,56 @@ static int regions_alloc(RegionsOutput& r, int H, int W, const char* who) {
     v.bytes = 3 * HW * sizeof(int) + nblk * sizeof(int) + sizeof(unsigned) + HW;
     regions_free(r);
     r = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// tracks output: the host side of td_tracks.h's state
+// ---------------------------------------------------------------------------------------------------------------
+// The pair table's size: the power of two >= 2 H W slots (at least 2), so that the H W distinct pairs a frame can have never fill it beyond half
+static int tracks_hash_lg(int H, int W) {
+    int lg = 1;
+    while ((1l << lg) < 2 * (long)H * W) ++lg;
+    return lg;
+}
+static size_t tracks_table_bytes(int max_regions) { return sizeof(TdTracksHeader) + (size_t)max_regions * sizeof(TdTrack); }
+// Where the parts of an H x W state lie inside a blob at `base` (16-byte aligned; NULL: only the size is wanted); every part starts on a 16-byte boundary.
+// The layout depends on H and W alone: the ceiling of 65536 regions, not the max_regions in force.
+static size_t tracks_layout(void* base, int H, int W, TracksState* st) {
+    const size_t HW = (size_t)H * W, R = TD_TK_MAX_REGIONS;
+    const int lg = tracks_hash_lg(H, W);
+    size_t off = 0;
+    char* b = (char*)base;
+    auto take = [&](size_t bytes) { char* q = b ? b + off : nullptr; off += (bytes + 15) & ~(size_t)15; return q; };
+    TracksState v = TracksState();
+    v.words = (unsigned*)take(4 * sizeof(unsigned));
+    v.prev = (int*)take(HW * sizeof(int));
+    v.cur = (int*)take(HW * sizeof(int));
+    v.hash = (td_u64*)take(((size_t)1 << lg) * sizeof(td_u64));
+    v.best_prev = (td_u64*)take(R * sizeof(td_u64));
+    v.best_cur = (td_u64*)take(R * sizeof(td_u64));
+    v.lab = (int*)take(R * sizeof(int));
+    v.track = (unsigned*)take(R * sizeof(unsigned));
+    v.age = (unsigned*)take(R * sizeof(unsigned));
+    v.lg = lg;
+    if (st) *st = v;
+    return off;
+}
+static void tracks_free(TracksOutput& t) {
+    if (t.blob) hipFree(t.blob);
+    t = TracksOutput();
+}
+// Allocate and zero (the reset state) the state of an H x W map into memory `t` owns.  On failure `t` is left as it was.
+static int tracks_alloc(TracksOutput& t, int H, int W, const char* who) {
+    TD_TRY(regions_size_check(H, W, who));
+    TracksOutput v;
+    v.bytes = tracks_layout(nullptr, H, W, nullptr);
+    unsigned char* blob = nullptr;
+    if (dev_alloc(&blob, v.bytes)) return -1;
+    v.blob = blob;
+    if (hipMemset(v.blob, 0, v.bytes) != hipSuccess) { tracks_free(v); return td_fail("%s: clearing the track state failed", who); }
+    tracks_layout(v.blob, H, W, &v.st);
+    tracks_free(t);
+    t = v;
     return 0;
 }

@@ -705,9 +705,36 @@ static int run_regions(const float* in, int C, int h, int w, int H, int W, const
     TD_LAUNCH(k_regions_stats, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return 0;
 }
+// tracks out (td_tracks.h): the four launches behind run_regions, on the id map and the regions table the same call wrote.  ids: the current id map (the
+// caller's, or the state's own map where the caller asked for none).  table: tracks_table_bytes(max_regions) bytes, 8-byte aligned.  min_overlap is read
+// NOW (a kernel argument).  Only enqueues: the state is zeroed by the kernels themselves.
+static_assert(TD_TRACKS_LAUNCHES == TDNET_TRACKS_LAUNCHES && TD_TK_BOUND == TDNET_TRACKS_BOUND && sizeof(TdTrack) == sizeof(tdnet_track) &&
+              sizeof(TdTracksHeader) == sizeof(tdnet_tracks_header), "td_tracks.h and include/tdnet.h disagree");
+static int tracks_table_check(const void* table, const char* who) {
+    if (!table) return td_fail("%s: tracks_dev is NULL", who);
+    if ((size_t)table & 7u) return td_fail("%s: tracks_dev = %p is not 8-byte aligned", who, table);
+    return 0;
+}
+static int run_tracks(int H, int W, const int32_t* ids, const void* rtable, int32_t* track_ids, void* table, const TracksState& st, int max_regions, int min_overlap,
+                      hipStream_t s, const char* who) {
+    TD_TRY(tracks_table_check(table, who));
+    TD_TRY(regions_size_check(H, W, who));
+    if (!st.words || !ids || !rtable) return td_fail("%s: internal: the track state is not allocated", who);
+    if (min_overlap < 1) return td_fail("%s: min_overlap = %d must be at least 1", who, min_overlap);
+    TracksArgs a = TracksArgs();
+    a.st = st; a.ids = ids; a.rtable = (const td_u64*)rtable; a.table = (td_u64*)table; a.track_ids = track_ids;
+    a.H = H; a.W = W; a.max_regions = max_regions; a.min_overlap = min_overlap;
+    const long nblk = regions_blocks(H, W), cap = 1l << st.lg, words = (long)(tracks_table_bytes(max_regions) / 8);
+    const long HW = (long)H * W;
+    TD_LAUNCH(k_tracks_pairs, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    TD_LAUNCH(k_tracks_best, dim3((unsigned)std::max<long>(1, (cap + 255) / 256)), dim3(256), 0, s, a, words);
+    TD_LAUNCH(k_tracks_resolve, dim3(1), dim3(TD_TK_WG), (TD_TK_WG + TD_TK_WG / 64) * sizeof(int), s, a);
+    TD_LAUNCH(k_tracks_commit, dim3((unsigned)nblk), dim3(256), 0, s, a, (int)std::min<long>(TD_TK_MAX_REGIONS, HW));
+    return 0;
+}
 
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS, OUT_TRACKS };
 struct FrameOutput {
     OutKind kind;
     void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF, OUT_MATTE: may be NULL) | rgb [oh][ow][3] | overlay, composite [Hs][Ws][3]
@@ -717,12 +744,15 @@ struct FrameOutput {
     const unsigned char* src;      // OUT_OVERLAY, OUT_COMPOSITE: the source frame, read by the handle's byte-input configuration
     int32_t* ids;                  // OUT_REGIONS: the id map [H][W] (may be NULL; dst: the uint8 labels, may be NULL too)
     void* table;                   // OUT_REGIONS: the header and the records
+    int32_t* track_ids;            // OUT_TRACKS (OUT_REGIONS' fields plus): the track map [H][W] (may be NULL)
+    void* tracks;                  // OUT_TRACKS: the tracks table
 };
 // the handle-side precondition of a form: its tables exist
 static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
     if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
-    if (kind == OUT_REGIONS && !n->regions.set) return td_fail("%s: the regions output is not configured (call tdnet_set_regions first)", who);
+    if ((kind == OUT_REGIONS || kind == OUT_TRACKS) && !n->regions.set) return td_fail("%s: the regions output is not configured (call tdnet_set_regions first)", who);
+    if (kind == OUT_TRACKS && !n->tracks.set) return td_fail("%s: the tracks output is not configured (call tdnet_set_tracks first)", who);
     if ((kind == OUT_MATTE || kind == OUT_COMPOSITE) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
     if (kind == OUT_COMPOSITE && !n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
     if (kind == OUT_COMPOSITE && !n->u8.set)
@@ -750,6 +780,12 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
     case OUT_MATTE: return launch_upsample_argmax_matte_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->matte, s);
     case OUT_COMPOSITE: return launch_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, (unsigned char*)o.dst, s);
     case OUT_REGIONS: return run_regions(in, C, h, w, H, W, nullptr, (unsigned char*)o.dst, o.ids, o.table, n->regions, s, who);
+    case OUT_TRACKS: {
+        int32_t* ids = o.ids ? o.ids : n->tracks.st.cur;
+        TD_TRY(tracks_table_check(o.tracks, who));
+        TD_TRY(run_regions(in, C, h, w, H, W, nullptr, (unsigned char*)o.dst, ids, o.table, n->regions, s, who));
+        return run_tracks(H, W, ids, o.table, o.track_ids, o.tracks, n->tracks.st, n->regions.max_regions, n->tracks.min_overlap, s, who);
+    }
     case OUT_OVERLAY:
         if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, nullptr, &n->overlay, &n->u8, o.src, n->dst, (unsigned char*)o.dst, s);
         return launch_upsample_argmax_overlay(in, C, h, w, n->overlay, n->u8, o.src, (unsigned char*)o.dst, s);

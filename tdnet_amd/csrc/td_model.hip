@@ -146,6 +146,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     overlay_free(n->overlay);
     score_free(n->score);
     regions_free(n->regions);
+    tracks_free(n->tracks);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -752,6 +753,75 @@ extern "C" int tdnet_labels_regions(tdnet_t* n, const uint8_t* labels, int32_t* 
     TD_TRY(regions_args(n, regions_dev, "tdnet_labels_regions"));
     TD_ON_DEVICE(n, -1);
     TD_TRY(run_regions(nullptr, n->cfg.nclass, 0, 0, n->H, n->W, labels, nullptr, ids, regions_dev, n->regions, (hipStream_t)stream, "tdnet_labels_regions"));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// ---- tracks out --------------------------------------------------------------------------------------------------------------------------
+// Configuration of the tracks output (not a frame call: it may synchronise; idempotent; per handle; independent of the order of the other tdnet_set_*
+// calls).  The state blob is sized from the handle alone (H, W and the ceiling of 65536 regions) and allocated, zeroed, ONCE: a second call only
+// changes min_overlap and leaves the tracks as they are.  A failed call changes nothing.
+extern "C" int tdnet_set_tracks(tdnet_t* n, int min_overlap) {
+    const char* who = "tdnet_set_tracks";
+    if (!n) return td_fail("%s: null handle", who);
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    if (min_overlap < 1) return td_fail("%s: min_overlap = %d must be at least 1", who, min_overlap);
+    TD_ON_DEVICE(n, -1);
+    if (!n->tracks.blob) {
+        const size_t before = n->tracks.bytes;
+        TD_TRY(tracks_alloc(n->tracks, n->H, n->W, who));
+        n->ws_bytes += n->tracks.bytes - before;
+    }
+    n->tracks.min_overlap = min_overlap;
+    n->tracks.set = true;
+    return 0;
+}
+extern "C" size_t tdnet_tracks_bytes(const tdnet_t* n) { return n && n->regions.set && n->tracks.set ? tracks_table_bytes(n->regions.max_regions) : 0; }
+// What every tracks entry checks on the host before anything is enqueued: both configurations exist and both tables can be addressed
+static int tracks_args(const tdnet* n, const void* regions_dev, const void* tracks_dev, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(output_configured(n, OUT_TRACKS, who));
+    TD_TRY(regions_table_check(regions_dev, who));
+    return tracks_table_check(tracks_dev, who);
+}
+// The regions entries with the tracking launches behind them.  Same frame, same FIFO step, same labels, ids and regions table; labels, ids and track_ids
+// may each be NULL.
+extern "C" int tdnet_forward_tracks(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, int32_t* ids, void* regions_dev, int32_t* track_ids, void* tracks_dev,
+                                    void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_tracks: null argument");
+    TD_TRY(tracks_args(n, regions_dev, tracks_dev, "tdnet_forward_tracks"));
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_TRACKS, labels, nullptr, nullptr, nullptr, ids, regions_dev, track_ids, tracks_dev}, stream,
+                     "tdnet_forward_tracks");
+}
+extern "C" int tdnet_forward_u8_tracks(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, int32_t* ids, void* regions_dev, int32_t* track_ids, void* tracks_dev,
+                                       void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_u8_tracks: null argument");
+    TD_TRY(tracks_args(n, regions_dev, tracks_dev, "tdnet_forward_u8_tracks"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_TRACKS, labels, nullptr, nullptr, nullptr, ids, regions_dev, track_ids, tracks_dev}, stream,
+                     "tdnet_forward_u8_tracks");
+}
+extern "C" int tdnet_propagate_tracks(tdnet_t* n, uint8_t* labels, int32_t* ids, void* regions_dev, int32_t* track_ids, void* tracks_dev, void* stream) {
+    if (!n) return td_fail("tdnet_propagate_tracks: null argument");
+    TD_TRY(tracks_args(n, regions_dev, tracks_dev, "tdnet_propagate_tracks"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_TRACKS, labels, nullptr, nullptr, nullptr, ids, regions_dev, track_ids, tracks_dev}, stream, "tdnet_propagate_tracks");
+}
+// the unfused form: from a uint8 label map [H][W] the caller holds (at any byte address)
+extern "C" int tdnet_labels_tracks(tdnet_t* n, const uint8_t* labels, int32_t* ids, void* regions_dev, int32_t* track_ids, void* tracks_dev, void* stream) {
+    const char* who = "tdnet_labels_tracks";
+    if (!n || !labels) return td_fail("%s: null argument", who);
+    TD_TRY(tracks_args(n, regions_dev, tracks_dev, who));
+    TD_ON_DEVICE(n, -1);
+    int32_t* cur = ids ? ids : n->tracks.st.cur;
+    TD_TRY(run_regions(nullptr, n->cfg.nclass, 0, 0, n->H, n->W, labels, nullptr, cur, regions_dev, n->regions, (hipStream_t)stream, who));
+    TD_TRY(run_tracks(n->H, n->W, cur, regions_dev, track_ids, tracks_dev, n->tracks.st, n->regions.max_regions, n->tracks.min_overlap, (hipStream_t)stream, who));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// Forget every track: enqueued on `stream` (one launch), ordered like a frame entry.  The next tracked frame's regions are all born, from track 1.
+extern "C" int tdnet_tracks_reset(tdnet_t* n, void* stream) {
+    if (!n) return td_fail("tdnet_tracks_reset: null handle");
+    if (!n->tracks.set) return td_fail("tdnet_tracks_reset: the tracks output is not configured (call tdnet_set_tracks first)");
+    TD_ON_DEVICE(n, -1);
+    TD_LAUNCH(k_tracks_reset, dim3(1), dim3(64), 0, (hipStream_t)stream, n->tracks.st);
     TD_HIP(hipGetLastError());
     return 0;
 }

@@ -901,3 +901,38 @@ extern "C" int tdnet_op_regions_tile(int* th, int* tw) {
     if (tw) *tw = TD_RG_TW;
     return 0;
 }
+// Tracks out (include/tdnet.h) through exactly the launches the tracks entries enqueue (TDNET_REGIONS_LAUNCHES + TDNET_TRACKS_LAUNCHES), one frame per call,
+// from a uint8 label map [H][W] at any byte address.  state: tdnet_op_tracks_state_bytes(H, W) bytes the CALLER owns, 16-byte aligned, all zero = the reset
+// state; it carries the tracks from call to call.  ids, track_ids: int32 [H][W] or NULL; regions: 16 + 48 * max_regions bytes, tracks: 16 + 24 * max_regions
+// bytes, both 8-byte aligned.  The regions workspace is allocated here and released before the call returns.
+extern "C" size_t tdnet_op_tracks_state_bytes(int H, int W) { return H < 1 || W < 1 || regions_size_check(H, W, "tdnet_op_tracks_state_bytes") ? 0 : tracks_layout(nullptr, H, W, nullptr); }
+// the pair table's slots for an H x W map: the tests size the worst case (H W distinct pairs) from it
+extern "C" long tdnet_op_tracks_capacity(int H, int W) { return H < 1 || W < 1 ? 0 : 1l << tracks_hash_lg(H, W); }
+extern "C" int tdnet_op_tracks(const uint8_t* labels, int C, int H, int W, const uint8_t* classes, int n, int connectivity, int max_regions, int min_area, int min_overlap,
+                               void* state, int32_t* ids, void* regions, int32_t* track_ids, void* tracks, void* stream) {
+    const char* who = "tdnet_op_tracks";
+    if (C < 1 || C > 256 || H < 1 || W < 1 || !labels) return td_fail("%s: a label map, C in 1..256 and a size >= 1 x 1 expected", who);
+    if (n < 0 || n > 256 || (n > 0 && !classes)) return td_fail("%s: n in 0..256 class ids expected", who);
+    if (min_overlap < 1) return td_fail("%s: min_overlap = %d must be at least 1", who, min_overlap);
+    if (!state) return td_fail("%s: state_dev is NULL", who);
+    if ((size_t)state & 15u) return td_fail("%s: state_dev = %p is not 16-byte aligned", who, state);
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < n; ++i) {
+        if (classes[i] >= C) return td_fail("%s: classes[%d] = %d is not a class id (C = %d)", who, i, (int)classes[i], C);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);
+    }
+    TD_TRY(regions_table_check(regions, who));
+    TD_TRY(tracks_table_check(tracks, who));
+    RegionsOutput r;
+    TD_TRY(regions_alloc(r, H, W, who));
+    r.classes = set; r.conn = connectivity; r.max_regions = max_regions; r.min_area = min_area; r.set = true;
+    TracksState st;
+    tracks_layout(state, H, W, &st);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* cur = ids ? ids : st.cur;
+    int rc = run_regions(nullptr, C, 0, 0, H, W, labels, nullptr, cur, regions, r, s, who);
+    if (!rc) rc = run_tracks(H, W, cur, regions, track_ids, tracks, st, max_regions, min_overlap, s, who);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    regions_free(r);
+    return rc;
+}

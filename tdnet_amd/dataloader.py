@@ -639,6 +639,96 @@ def regions_unpack(buf, max_regions):
     return raw[:16].view(REGIONS_HEADER_DTYPE)[0], raw[16:].view(REGION_DTYPE)
 
 
+# One record of the library's tracks table (include/tdnet.h tdnet_track, 24 bytes; record i belongs to region i + 1 of the regions table of the same call)
+TRACK_DTYPE = np.dtype([("track", "<u4"), ("age", "<u4"), ("prev_region", "<u4"), ("overlap", "<u4"), ("origin_track", "<u4"), ("reserved", "<u4")])
+TRACKS_HEADER_DTYPE = np.dtype([("count", "<u4"), ("matched", "<u4"), ("ended", "<u4"), ("status", "<u4")])
+TRACKS_BOUND = 1                                                     # header status bit
+
+
+class TrackOracle:
+    """The oracle of the library's tracks output (include/tdnet.h "tracks out"): a small stateful matcher.  .step(labels) labels the frame with
+    regions_u8, counts the overlaps n(p, c) of regions that have a record on both sides with np.unique over the pixel pairs, applies the contract --
+    best partners with ties to the smallest number, mutual choice and n >= min_overlap continue a track, every other region is born with the next id --
+    and returns (ids, region table, track map, header, records): ids and table as regions_u8 gives them, track map int32 [H, W], header a
+    TRACKS_HEADER_DTYPE record, records TRACK_DTYPE [stored].  It remembers ONE frame.  .reset() forgets every track: ids restart at 1."""
+
+    def __init__(self, classes, connectivity=8, min_area=1, max_regions=256, min_overlap=1):
+        assert min_overlap >= 1
+        self.classes, self.connectivity, self.min_area, self.max_regions, self.min_overlap = list(classes), connectivity, min_area, max_regions, min_overlap
+        self.reset()
+
+    def reset(self):
+        self.prev_ids = None                                           # ids' with everything beyond stored' zeroed
+        self.prev_label = np.zeros(0, np.int64)
+        self.prev_track = np.zeros(0, np.int64)
+        self.prev_age = np.zeros(0, np.int64)
+        self.next = 1
+
+    def step(self, labels):
+        ids, count, table = regions_u8(labels, self.classes, self.connectivity, self.min_area, self.max_regions)
+        stored, storedp = len(table), len(self.prev_track)
+        cur = np.where(ids <= stored, ids, 0).astype(np.int64)
+        label = table["label"].astype(np.int64)
+        n = {}                                                         # (p, c) -> overlap, equal labels only
+        if storedp and stored:
+            assert self.prev_ids.shape == cur.shape, "a tracker is for frames of one size"
+            both = (self.prev_ids > 0) & (cur > 0)
+            pairs, counts = np.unique(np.stack([self.prev_ids[both], cur[both]], 1), axis=0, return_counts=True)
+            for (p, c), k in zip(pairs.tolist(), counts.tolist()):
+                if self.prev_label[p - 1] == label[c - 1]:
+                    n[(p, c)] = k
+        bp, bc = {}, {}                                                # best partner: largest n, then the smallest number
+        for (p, c), k in sorted(n.items()):
+            if c not in bp or k > n[(bp[c], c)]:
+                bp[c] = p
+        for (p, c), k in sorted(n.items(), key=lambda it: (it[0][1], it[0][0])):
+            if p not in bc or k > n[(p, bc[p])]:
+                bc[p] = c
+        recs = np.zeros(stored, TRACK_DTYPE)
+        matched = 0
+        for c in range(1, stored + 1):
+            p = bp.get(c, 0)
+            if p and bc[p] == c and n[(p, c)] >= self.min_overlap:
+                t = int(self.prev_track[p - 1])
+                recs[c - 1] = (t, int(self.prev_age[p - 1]) + 1, p, n[(p, c)], t, 0)
+                matched += 1
+            else:
+                recs[c - 1] = (self.next, 1, 0, 0, int(self.prev_track[p - 1]) if p else 0, 0)
+                self.next += 1
+        header = np.zeros(1, TRACKS_HEADER_DTYPE)[0]
+        header["count"], header["matched"], header["ended"], header["status"] = stored, matched, storedp - matched, 0
+        track_map = np.concatenate([[0], recs["track"].astype(np.int64)])[cur].astype(np.int32)
+        self.prev_ids, self.prev_label = cur, label
+        self.prev_track, self.prev_age = recs["track"].astype(np.int64), recs["age"].astype(np.int64)
+        return ids, table, track_map, header, recs
+
+
+class TrackTable(np.ndarray):
+    """TRACK_DTYPE records of the regions a frame's regions table holds (record i: region i + 1), with the header's .matched, .ended and .status as
+    attributes; born = len() - matched."""
+    matched = 0
+    ended = 0
+    status = 0
+
+    def __array_finalize__(self, obj):
+        self.matched, self.ended, self.status = getattr(obj, "matched", 0), getattr(obj, "ended", 0), getattr(obj, "status", 0)
+
+
+def tracks_unpack(buf, max_regions):
+    """A tracks table as the library writes it (bytes, or a uint8 array of 16 + 24 * max_regions) -> (header record, TRACK_DTYPE [max_regions])."""
+    raw = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    assert raw.size == 16 + 24 * max_regions, (raw.size, max_regions)
+    return raw[:16].view(TRACKS_HEADER_DTYPE)[0], raw[16:].view(TRACK_DTYPE)
+
+
+def track_table(buf, max_regions):
+    """The table the library wrote (16 + 24 * max_regions bytes) as a TrackTable of its `count` records (a copy)."""
+    hdr, recs = tracks_unpack(buf, max_regions)
+    t = recs[:int(hdr["count"])].copy().view(TrackTable)
+    t.matched, t.ended, t.status = int(hdr["matched"]), int(hdr["ended"]), int(hdr["status"])
+    return t
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],

@@ -385,6 +385,34 @@ class Engine:
     def labels_regions(self, labels_ptr, ids_ptr, regions_ptr, stream=None):
         self.lib.check(self.lib.tdnet_labels_regions(self.h, _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), stream))
 
+    # ---- tracks out (include/tdnet.h) ----
+    def set_tracks(self, min_overlap=1):
+        """The *_tracks entries will match each frame's regions against those of the previous tracked frame by pixel overlap (a match needs at least
+        min_overlap pixels).  A configuration call: allocates this handle's track state once; a second call keeps the tracks."""
+        self.lib.check(self.lib.tdnet_set_tracks(self.h, int(min_overlap)))
+
+    def tracks_bytes(self):
+        """bytes of the table the tracks entries write (16 + 24 * max_regions; 8-byte aligned device memory of the caller's); 0 until both set_regions and set_tracks"""
+        return int(self.lib.tdnet_tracks_bytes(self.h))
+
+    def forward_tracks(self, img_ptr, pos_id, labels_ptr, ids_ptr, regions_ptr, track_ids_ptr, tracks_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_tracks(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), _ptr(track_ids_ptr),
+                                                     _ptr(tracks_ptr), stream))
+
+    def forward_u8_tracks(self, img_ptr, pos_id, labels_ptr, ids_ptr, regions_ptr, track_ids_ptr, tracks_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_tracks(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), _ptr(track_ids_ptr),
+                                                        _ptr(tracks_ptr), stream))
+
+    def propagate_tracks(self, labels_ptr, ids_ptr, regions_ptr, track_ids_ptr, tracks_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_tracks(self.h, _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), _ptr(track_ids_ptr), _ptr(tracks_ptr), stream))
+
+    def labels_tracks(self, labels_ptr, ids_ptr, regions_ptr, track_ids_ptr, tracks_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_labels_tracks(self.h, _ptr(labels_ptr), _ptr(ids_ptr), _ptr(regions_ptr), _ptr(track_ids_ptr), _ptr(tracks_ptr), stream))
+
+    def tracks_reset(self, stream=None):
+        """forget every track (enqueued on the stream): the next tracked frame's regions are all born, from track 1"""
+        self.lib.check(self.lib.tdnet_tracks_reset(self.h, stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

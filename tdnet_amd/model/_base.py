@@ -1106,6 +1106,112 @@ class _TDNetBase(nn.Module):
         self._engine.propagate_regions(out.data_ptr(), None if ids is None else ids.data_ptr(), table.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         return out, ids, self._regions_tables(table)
 
+    # ---- tracks out (not in the reference's model; a caller of the reference downloads two id maps per frame and counts their overlaps on the host) ----
+    # The regions methods plus region identity across frames (include/tdnet.h "tracks out"): every method returns what its regions method returns plus
+    # (track map int32 [N, H, W] or None, [dataloader.TrackTable per sample]).  The track state lives on the device, per handle (sample i of a batch is a
+    # stream of its own); it remembers ONE frame, and only the tracked methods advance it.
+    _tracks = None
+
+    def set_tracks(self, min_overlap=1):
+        """The configuration of the *_tracks methods: a region continues a track only if the two overlap in at least min_overlap pixels."""
+        if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, np.integer)) or int(min_overlap) < 1:
+            raise RuntimeError("set_tracks(): min_overlap must be an integer >= 1, got %r" % (min_overlap,))
+        self._tracks = int(min_overlap)
+        return self._tracks
+
+    def _need_tracks(self, who):
+        cfg = self._need_regions(who)
+        if self._tracks is None:
+            raise RuntimeError("%s(): no configuration (call set_tracks() first)" % who)
+        return cfg
+
+    def _tracks_out(self, n, H, W, device, return_track_ids):
+        tmap = torch.empty((n, H, W), device=device, dtype=torch.int32) if return_track_ids else None
+        return tmap, torch.empty((n, 2 + 3 * self._regions[2]), device=device, dtype=torch.int64)   # 16 + 24 * max_regions bytes per sample, 8-byte aligned
+
+    def _tracks_tables(self, table):
+        from ..dataloader import track_table
+        host = table.cpu().numpy()
+        return [track_table(host[i], self._regions[2]) for i in range(host.shape[0])]
+
+    def _tracks_config(self, eng, cfg):
+        eng.set_regions(*cfg)
+        eng.set_tracks(self._tracks)
+
+    def forward_tracks(self, img, pos_id=0, return_ids=True, return_track_ids=True):
+        """forward_regions() with the tracks behind the regions."""
+        cfg = self._need_tracks("forward_tracks")
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        out, ids, table = self._regions_out(img.shape[0], img.shape[2], img.shape[3], img.device, return_ids)
+        tmap, ttable = self._tracks_out(img.shape[0], img.shape[2], img.shape[3], img.device, return_track_ids)
+
+        def one(i, eng, s):
+            self._tracks_config(eng, cfg)
+            eng.forward_tracks(img[i].data_ptr(), pos_id, out[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(),
+                               None if tmap is None else tmap[i].data_ptr(), ttable[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out, ids, self._regions_tables(table), tmap, self._tracks_tables(ttable)
+
+    def forward_tracks_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None, return_ids=True, return_track_ids=True):
+        """forward_regions_u8() with the tracks behind the regions: bytes in (any byte-input configuration: view= / surface= as there)."""
+        cfg = self._need_tracks("forward_tracks_u8")
+        view = self._one_of(view, surface, "view", "surface")
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        img = img_u8.contiguous()
+        out, ids, table = self._regions_out(img.shape[0], H, W, img.device, return_ids)
+        tmap, ttable = self._tracks_out(img.shape[0], H, W, img.device, return_track_ids)
+
+        def one(i, eng, s):
+            self._tracks_config(eng, cfg)
+            eng.forward_u8_tracks(img[i].data_ptr(), pos_id, out[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(),
+                                  None if tmap is None else tmap[i].data_ptr(), ttable[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out, ids, self._regions_tables(table), tmap, self._tracks_tables(ttable)
+
+    def labels_tracks(self, labels_u8, return_ids=True, return_track_ids=True):
+        """The unfused form: uint8 labels [N, H, W] (CUDA) of this model's size, sample i on handle i (and on handle i's tracks).  Returns the labels as given."""
+        cfg = self._need_tracks("labels_tracks")
+        if self._engine is None:
+            raise RuntimeError("labels_tracks(): no handle yet")
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or tuple(labels_u8.shape[1:]) != (H, W):
+            raise RuntimeError("labels_tracks(): expected uint8 labels [N, %d, %d]" % (H, W))
+        labels = labels_u8.contiguous()
+        engines = [self._engine] + list(self._extra_engines)
+        if labels.shape[0] > len(engines):
+            raise RuntimeError("labels_tracks(): %d label maps but %d handle(s)" % (labels.shape[0], len(engines)))
+        _, ids, table = self._regions_out(labels.shape[0], H, W, labels.device, return_ids)
+        tmap, ttable = self._tracks_out(labels.shape[0], H, W, labels.device, return_track_ids)
+        s = torch.cuda.current_stream(labels.device).cuda_stream
+        for i in range(labels.shape[0]):
+            self._tracks_config(engines[i], cfg)
+            engines[i].labels_tracks(labels[i].data_ptr(), None if ids is None else ids[i].data_ptr(), table[i].data_ptr(),
+                                     None if tmap is None else tmap[i].data_ptr(), ttable[i].data_ptr(), s)
+        return labels, ids, self._regions_tables(table), tmap, self._tracks_tables(ttable)
+
+    def propagate_tracks(self, return_ids=True, return_track_ids=True):
+        """propagate_regions() with the tracks behind the regions, for the frame encode() / encode_u8() left pending."""
+        cfg = self._need_tracks("propagate_tracks")
+        if self._engine is None or self._pending_shape is None:
+            raise RuntimeError("propagate_tracks(): no encoded frame is pending (call encode(img, pos_id) first)")
+        H, W, dev = self._pending_shape
+        out, ids, table = self._regions_out(1, H, W, dev, return_ids)
+        tmap, ttable = self._tracks_out(1, H, W, dev, return_track_ids)
+        self._tracks_config(self._engine, cfg)
+        self._pending_shape = None
+        self._engine.propagate_tracks(out.data_ptr(), None if ids is None else ids.data_ptr(), table.data_ptr(), None if tmap is None else tmap.data_ptr(),
+                                      ttable.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out, ids, self._regions_tables(table), tmap, self._tracks_tables(ttable)
+
+    def reset_tracks(self):
+        """Forget every track on every handle that has tracks (enqueued on the current stream): the next tracked frame's regions are all born, from id 1."""
+        if self._engine is None or self._tracks is None:
+            return
+        for eng in [self._engine] + list(self._extra_engines):
+            eng.set_tracks(self._tracks)                               # idempotent; a handle that never ran a tracked frame gets its (zeroed) state here
+            eng.tracks_reset(torch.cuda.current_stream().cuda_stream)
+
     @staticmethod
     def _background(background):
         if background is None:

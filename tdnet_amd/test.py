@@ -34,7 +34,8 @@ softmax mass of that class set as a byte, 255 = certainly one of them (include/t
 grey PNG DIR/folder/name beside the usual picture.  `--matte IDS --composite R,G,B` (with `--u8`, `--nv12` or `--yuv`) writes, where the overlay's
 picture would go, the frame seen through the matte over that background, at the frame's own (`--crop`: the rectangle's) size.
 `--regions IDS` (a comma list of class ids; `--regions_conn 4|8`, `--regions_min_area N`) labels the connected components of those classes on the device
-behind every frame's labels (include/tdnet.h "regions out") and prints the count per frame; `--regions_out DIR` writes one CSV per frame,
+behind every frame's labels (include/tdnet.h "regions out") and prints the count per frame (`--tracks [MIN_OVERLAP]` follows them across frames, "tracks out":
+matched / born / ended per frame, and the columns track,age,origin in the CSVs); `--regions_out DIR` writes one CSV per frame,
 DIR/folder/name.csv: id,label,area,x0,y0,x1,y1,cx,cy in network-size pixels.
 """
 import argparse
@@ -70,13 +71,15 @@ def load_ground_truth(gt_path, items, size, nearest_index, pin):
 REGIONS_CLI_MAX = 4096                                                 # records of --regions' table: regions beyond are counted, not written
 
 
-def regions_csv(table):
+def regions_csv(table, tracks=None):
     """The text --regions_out writes for one frame's records (REGION_DTYPE; record i is region i + 1): id,label,area,x0,y0,x1,y1,cx,cy with the
-    centroid sum / area to three decimals."""
-    lines = ["id,label,area,x0,y0,x1,y1,cx,cy"]
+    centroid sum / area to three decimals.  tracks (--tracks: TRACK_DTYPE, record i for region i + 1) adds the columns track,age,origin."""
+    lines = ["id,label,area,x0,y0,x1,y1,cx,cy" + ("" if tracks is None else ",track,age,origin")]
     for i, r in enumerate(table):
         lines.append("%d,%d,%d,%d,%d,%d,%d,%.3f,%.3f" % (i + 1, r["label"], r["area"], r["x0"], r["y0"], r["x1"], r["y1"],
                                                          int(r["sum_x"]) / int(r["area"]), int(r["sum_y"]) / int(r["area"])))
+        if tracks is not None:
+            lines[-1] += ",%d,%d,%d" % (tracks[i]["track"], tracks[i]["age"], tracks[i]["origin_track"])
     return "\n".join(lines) + "\n"
 
 
@@ -171,6 +174,12 @@ def test(args):
             raise SystemExit("--regions asks for a tail of its own in the frame-by-frame loop: not with --rgb, --overlay, --matte, --gt_path, --prefetch, --conf, --min_conf, "
                              "--out_nv12 or --out_yuv")
     with_regions = region_ids is not None
+    min_overlap = getattr(args, "tracks", None)                        # --tracks [MIN_OVERLAP]: checked before anything is loaded
+    if min_overlap is not None and not with_regions:
+        raise SystemExit("--tracks follows the regions of --regions across frames: give --regions IDS (a comma list of class ids) with it")
+    if min_overlap is not None and min_overlap < 1:
+        raise SystemExit("--tracks: a minimum overlap of at least 1 pixel expected, got %r" % (min_overlap,))
+    with_tracks = min_overlap is not None
     out_nv12, out_yuv = getattr(args, "out_nv12", None), getattr(args, "out_yuv", None)
     out_layout = None
     if out_yuv is not None:                                            # LAYOUT:FILE; checked before anything is loaded
@@ -235,11 +244,13 @@ def test(args):
         model.set_matte(matte_ids)
     if with_regions:
         model.set_regions(region_ids, regions_conn, REGIONS_CLI_MAX, regions_min_area)
+    if with_tracks:
+        model.set_tracks(min_overlap)
 
-    def save_regions(table, img_name, folder):                         # --regions_out: one CSV per frame; the centroid is sum / area
+    def save_regions(table, img_name, folder, tracks=None):            # --regions_out: one CSV per frame; the centroid is sum / area
         os.makedirs(os.path.join(regions_dir, folder), exist_ok=True)
         with open(os.path.join(regions_dir, folder, os.path.splitext(img_name)[0] + ".csv"), "w") as f:
-            f.write(regions_csv(table))
+            f.write(regions_csv(table, tracks))
 
     def print_scores():                                                # Training/validate.py:91-97
         if gts is None:
@@ -403,6 +414,9 @@ def test(args):
                 output = model.forward_composite_u8(image, i % path_num, (H, W), background=composite, **vk(view))
             elif with_matte:
                 output, matte = model.forward_matte_u8(image, i % path_num, (H, W), **vk(view)) if byte else model.forward_matte(image, i % path_num)
+            elif with_tracks:
+                output, _, tables, _, tracks = model.forward_tracks_u8(image, i % path_num, (H, W), return_ids=False, return_track_ids=False, **vk(view)) if byte else \
+                    model.forward_tracks(image, i % path_num, return_ids=False, return_track_ids=False)
             elif with_regions:
                 output, _, tables = model.forward_regions_u8(image, i % path_num, (H, W), return_ids=False, **vk(view)) if byte else \
                     model.forward_regions(image, i % path_num, return_ids=False)
@@ -434,9 +448,11 @@ def test(args):
                 save_matte(output.cpu().numpy(), matte.cpu().numpy(), img_name, folder, ori_size)
             elif with_regions:                                         # the usual picture of the uint8 labels, and the frame's regions
                 save(output.cpu().numpy(), img_name, folder, ori_size)
-                print(" Frame {0:2d}   {1:d} regions{2:s}".format(i + 1, tables[0].count, "" if tables[0].count == len(tables[0]) else " (%d in the table)" % len(tables[0])))
+                print(" Frame {0:2d}   {1:d} regions{2:s}{3:s}".format(
+                    i + 1, tables[0].count, "" if tables[0].count == len(tables[0]) else " (%d in the table)" % len(tables[0]),
+                    "" if not with_tracks else "   matched / born / ended {0:d} / {1:d} / {2:d}".format(tracks[0].matched, len(tracks[0]) - tracks[0].matched, tracks[0].ended)))
                 if regions_dir is not None:
-                    save_regions(tables[0], img_name, folder)
+                    save_regions(tables[0], img_name, folder, tracks[0] if with_tracks else None)
             elif rgb or overlay is not None or composite is not None:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
                 if overlay is not None and conf_dir is not None:
@@ -482,6 +498,7 @@ if __name__ == "__main__":
     parser.add_argument("--regions", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13): label the connected components of these classes on the device behind every frame's labels")
     parser.add_argument("--regions_conn", nargs="?", type=int, default=None, help="with --regions: 4 or 8 neighbours (default 8)")
     parser.add_argument("--regions_min_area", nargs="?", type=int, default=None, help="with --regions: drop regions of fewer pixels (default 1)")
+    parser.add_argument("--tracks", nargs="?", type=int, const=1, default=None, help="with --regions: follow the regions across frames on the device (optional value: the minimum overlap in pixels of a match, default 1); prints matched / born / ended per frame, --regions_out CSVs gain track,age,origin")
     parser.add_argument("--regions_out", nargs="?", type=str, default=None, help="with --regions: directory for one CSV per frame: id,label,area,x0,y0,x1,y1,cx,cy (network-size pixels, inclusive box)")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
