@@ -645,6 +645,49 @@ int  tdnet_forward_u8_tracks(tdnet_t* h, const uint8_t* img_dev, int pos_id, uin
 int  tdnet_labels_tracks(tdnet_t* h, const uint8_t* labels_u8_dev, int32_t* ids_dev /* | NULL */, void* regions_dev, int32_t* track_ids_dev /* | NULL */,
                          void* tracks_dev, void* stream);
 int  tdnet_tracks_reset(tdnet_t* h, void* stream);   /* enqueued */
+/* ---- runs out ------------------------------------------------------------------------------------------------------
+ * A semantic map is long horizontal runs of one value, and masks travel between tools as run-length codes.  These entries code a map as a table of runs on
+ * the device -- behind the frame's label launch, or from a map the caller holds -- so that a recorder, a sender or a host-side rule engine downloads the
+ * table instead of the [H][W] map; tdnet_runs_labels / tdnet_runs_ids turn a table back into a map on a receiving handle.  Let V[Y][X] be a map of the
+ * network size H x W -- the uint8 labels the label entries give, or an int32 map: the id map or the track map of the regions / tracks entries -- and
+ * i = Y W + X the flat index:
+ *   run         a maximal horizontal segment of equal value: pixel i starts a run iff X == 0 or V[i] != V[i - 1].  Runs never cross a row start, also where
+ *               the value goes on into the next row.  The runs partition the map; none is filtered.  They are numbered 1, 2, ... by growing start;
+ *               count is their number, H <= count <= H W.
+ *   table       a device buffer of tdnet_runs_bytes = 16 + 8 (max_runs + 1) bytes, 8-byte aligned (any other alignment is refused, the message naming
+ *               runs_dev): a header tdnet_runs_header with stored = min(count, max_runs), then records tdnet_run; record j < stored is run j + 1; record
+ *               `stored`, the closing record, is {the start of run stored + 1 if stored < count, else H W; 0}: every stored run ends where the next record
+ *               starts.  Records behind the closing one are NOT written: the bytes there stay what they were (a table sized for the worst case costs
+ *               no 8 max_runs bytes of stores per frame).  status bit TDNET_RUNS_OVERFLOW: count > max_runs; count is the true count either way.
+ *   exact       integers only; the result does not depend on the launch geometry.  The coder uses no atomics: every rank is a prefix sum.
+ * tdnet_set_runs: configuration (it may synchronise; idempotent for equal arguments; per handle).  It allocates the workspace -- a byte map for the calls
+ * that ask for no labels, and the block counts -- once, counted in tdnet_memory_bytes.  max_runs must be in 1 .. H W; the map may have up to 2^30 - 16
+ * pixels (the regions' limit: a flat index fits its word).  It fails, changing nothing, on a handle that is not finalized and on a max_runs out of range.
+ * max_runs travels as a kernel ARGUMENT read when an entry enqueues: a captured hipGraph replays capture time's.  tdnet_runs_bytes is 0 before it.
+ * The frame entries follow the label entries' rules: the same FIFO step, labels (labels_dev may be NULL) byte for byte those of tdnet_forward_u8_labels.
+ * All coding entries only enqueue -- no host synchronisation, no memset or copy calls -- and work inside a hipGraph capture; a pending encoded frame stays
+ * pending on any refusal.  A frame entry's tdnet_last_launch_count is the label entry's - 1 + TDNET_RUNS_LAUNCHES: the frame's label launch (unchanged; it
+ * does not count starts) is the first runs launch, and count, scan and emit follow it.  tdnet_labels_runs takes a uint8 map at any byte address,
+ * tdnet_ids_runs an int32 map, 4-byte aligned, of arbitrary values, negative ones included -- called behind a regions or tracks entry on the same stream;
+ * both enqueue TDNET_RUNS_LAUNCHES - 1 launches.  Without a prior tdnet_set_runs every entry fails naming it.
+ * Decoding, TDNET_RUNS_DECODE_LAUNCHES launch: the kernel reads `stored` from the device header, clamped to the handle's max_runs.  Pixel i below the
+ * closing record's start gets the value of the run that holds it (the uint8 form: its low byte), every other pixel `fill` -- which covers an overflowed
+ * table.  The output may sit at any byte address (uint8) or any 4-byte aligned address (int32).  A table the coder did not write gives unspecified values;
+ * the kernel still reads nothing outside tdnet_runs_bytes and writes nothing outside the map: its searches are bounded by max_runs, not by the records.
+ * One handle's entries share one workspace: enqueue them on one stream, or order them.                                                          */
+#define TDNET_RUNS_LAUNCHES 4
+#define TDNET_RUNS_DECODE_LAUNCHES 1
+#define TDNET_RUNS_OVERFLOW 1u
+typedef struct tdnet_runs_header { uint32_t count, stored, status, reserved; } tdnet_runs_header;
+typedef struct tdnet_run { uint32_t start; int32_t value; } tdnet_run;
+int  tdnet_set_runs(tdnet_t* h, int max_runs /* 1 .. H W */);
+size_t tdnet_runs_bytes(const tdnet_t* h);   /* 16 + 8 (max_runs + 1); 0 before tdnet_set_runs */
+int  tdnet_forward_runs(tdnet_t* h, const float* img_nchw_dev, int pos_id, uint8_t* labels_dev /* | NULL */, void* runs_dev, void* stream);
+int  tdnet_forward_u8_runs(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* labels_dev /* | NULL */, void* runs_dev, void* stream);
+int  tdnet_labels_runs(tdnet_t* h, const uint8_t* labels_u8_dev, void* runs_dev, void* stream);
+int  tdnet_ids_runs(tdnet_t* h, const int32_t* ids_i32_dev, void* runs_dev, void* stream);
+int  tdnet_runs_labels(tdnet_t* h, const void* runs_dev, int fill, uint8_t* labels_u8_dev, void* stream);
+int  tdnet_runs_ids(tdnet_t* h, const void* runs_dev, int fill, int32_t* ids_i32_dev, void* stream);
 /* Empties the FIFO (the reference never resets between clips; needed to feed a second clip).  The track state of "tracks out" stays: tdnet_tracks_reset. */
 int  tdnet_reset(tdnet_t* h);
 int  tdnet_fifo_len(const tdnet_t* h);
@@ -675,6 +718,7 @@ int  tdnet_propagate_composite(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_
 int  tdnet_propagate_regions(tdnet_t* h, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev, void* stream);   /* see "regions out" */
 int  tdnet_propagate_tracks(tdnet_t* h, uint8_t* labels_dev /* | NULL */, int32_t* ids_dev /* | NULL */, void* regions_dev, int32_t* track_ids_dev /* | NULL */,
                             void* tracks_dev, void* stream);   /* see "tracks out" */
+int  tdnet_propagate_runs(tdnet_t* h, uint8_t* labels_dev /* | NULL */, void* runs_dev, void* stream);   /* see "runs out" */
 /* cache entry geometry: q,k are [Lk,dk], v is [Lk,dv] fp32                                                         */
 int  tdnet_cache_dims(const tdnet_t* h, int* Lk, int* dk, int* dv);
 /* copy the pending frame's entry into caller-owned device buffers                                                  */

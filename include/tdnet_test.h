@@ -217,6 +217,15 @@ int tdnet_op_tracks(const uint8_t* labels_u8_dev, int C, int H, int W, const uin
                     void* state_dev, int32_t* ids_dev, void* regions_dev, int32_t* track_ids_dev, void* tracks_dev, void* stream);
 /* the slots of the internal pair table for an H x W map (a power of two >= 2 H W): the tests size the worst case from it */
 long tdnet_op_tracks_capacity(int H, int W);
+/* Runs out (include/tdnet.h) through exactly the launches the runs entries enqueue, on maps the caller holds.  Exactly one source: low-resolution logits
+ * [C,h,w] (in_dev; the label launch writes labels_u8_dev [H,W], which is then required), a uint8 map [H,W] at any byte address (map_u8_dev) or an int32 map
+ * [H,W], 4-byte aligned (map_i32_dev).  runs_dev: 16 + 8 (max_runs + 1) bytes, 8-byte aligned.  The workspace is allocated for the call.            */
+int tdnet_op_runs(const float* in_dev, int C, int h, int w, int H, int W, uint8_t* labels_u8_dev, const uint8_t* map_u8_dev, const int32_t* map_i32_dev, int max_runs,
+                  void* runs_dev, void* stream);
+/* the way back, one launch: exactly one of out_u8_dev (any byte address) and out_i32_dev (4-byte aligned) */
+int tdnet_op_runs_decode(const void* runs_dev, int max_runs, int fill, int H, int W, uint8_t* out_u8_dev, int32_t* out_i32_dev, void* stream);
+/* the pixels a workgroup of the flat launches covers: the tests size their cases from it */
+int tdnet_op_runs_block(void);
 /* that host function's index table for one axis (tdnet_amd/dataloader.py nearest_index): out_host [n_dst] int32.  No device work.             */
 int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host);
 

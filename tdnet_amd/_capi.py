@@ -139,6 +139,15 @@ SYMBOLS = {
     "tdnet_propagate_tracks": (ctypes.c_int, [c_void_p] * 7),
     "tdnet_labels_tracks": (ctypes.c_int, [c_void_p] * 7),
     "tdnet_tracks_reset": (ctypes.c_int, [c_void_p, c_void_p]),
+    "tdnet_set_runs": (ctypes.c_int, [c_void_p, ctypes.c_int]),
+    "tdnet_runs_bytes": (ctypes.c_size_t, [c_void_p]),
+    "tdnet_forward_runs": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_forward_u8_runs": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "tdnet_propagate_runs": (ctypes.c_int, [c_void_p] * 4),
+    "tdnet_labels_runs": (ctypes.c_int, [c_void_p] * 4),
+    "tdnet_ids_runs": (ctypes.c_int, [c_void_p] * 4),
+    "tdnet_runs_labels": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_runs_ids": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_reset": (ctypes.c_int, [c_void_p]),
     "tdnet_fifo_len": (ctypes.c_int, [c_void_p]),
     "tdnet_encode": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
@@ -215,6 +224,9 @@ TEST_SYMBOLS = {
     "tdnet_op_tracks_state_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "tdnet_op_tracks": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 3 + [c_void_p] + [ctypes.c_int] * 5 + [c_void_p] * 6),
     "tdnet_op_tracks_capacity": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
+    "tdnet_op_runs": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_runs_decode": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_runs_block": (ctypes.c_int, []),
     "tdnet_op_nearest_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p]),
     "tdnet_op_enc_first": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 4 + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 5),
     "tdnet_op_conv1x1_src2_null": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,

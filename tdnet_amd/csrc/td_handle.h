@@ -16,6 +16,7 @@
 //   td_matte.h     (kernels) matte out: the softmax mass of a class set as a byte
 //   td_regions.h   (kernels) regions out: connected components of a class set with boxes; its workspace's host side is at the end of this file
 //   td_tracks.h    (kernels) tracks out: region identity across frames by pixel overlap; its state's host side is at the end of this file
+//   td_runs.h      (kernels) runs out: a label or id map as a run-length table, and back; its workspace's host side is at the end of this file
 //   td_ops_test.h  single-operator entry points for the tests + roofline / tuning probes (not on the product path)
 //   td_model.hip   the translation unit: the C ABI of include/tdnet.h
 #pragma once
@@ -41,6 +42,7 @@
 #include "td_conf.h"
 #include "td_matte.h"
 #include "td_regions.h"
+#include "td_runs.h"
 #include "td_tracks.h"
 
 #include <cmath>
@@ -346,6 +348,16 @@ struct TracksOutput {
     TracksState st = TracksState();
     size_t bytes = 0;
 };
+// The runs output of a handle (tdnet_set_runs): max_runs -- plain host state, a kernel argument read when an entry enqueues -- and the workspace of
+// td_runs.h: the block counts, and a byte map for the frame entries that are asked for no labels.
+struct RunsState {
+    bool set = false;
+    int max_runs = 0;
+    int H = 0, W = 0;
+    int* blk = nullptr;                                                // [runs_blocks(H, W)]
+    unsigned char* lab = nullptr;                                      // [H][W]
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -439,6 +451,7 @@ struct tdnet {
     ScoreOutput score;                                                // tdnet_set_score
     RegionsOutput regions;                                            // tdnet_set_regions
     TracksOutput tracks;                                              // tdnet_set_tracks
+    RunsState runs;                                                   // tdnet_set_runs
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     CompositeOutput comp;                                              // tdnet_set_output_composite
     bool matte_set = false;                                            // tdnet_set_matte: plain host state like min_conf; the *_matte entries pass the words as kernel arguments
@@ -1028,5 +1041,29 @@ static int tracks_alloc(TracksOutput& t, int H, int W, const char* who) {
     tracks_layout(v.blob, H, W, &v.st);
     tracks_free(t);
     t = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// runs output: the host side of td_runs.h's workspace
+// ---------------------------------------------------------------------------------------------------------------
+static void runs_free(RunsState& r) {
+    if (r.blk) hipFree(r.blk);
+    if (r.lab) hipFree(r.lab);
+    r = RunsState();
+}
+// the flat launches' grid: H W / 4 aligned groups, the head lane and a tail lane (td_out.h out_grid_run's count)
+static long runs_blocks(int H, int W) { return ((long)H * W / 4 + 2 + TD_RN_LANES - 1) / TD_RN_LANES; }
+static size_t runs_table_bytes(int max_runs) { return sizeof(TdRunsHeader) + ((size_t)max_runs + 1) * sizeof(TdRun); }
+// Allocate the workspace of an H x W map into memory `r` owns (with_map: the byte map too); max_runs is the caller's.  On failure `r` is left as it was.
+static int runs_alloc(RunsState& r, int H, int W, bool with_map, const char* who) {
+    TD_TRY(regions_size_check(H, W, who));
+    RunsState v;
+    const size_t HW = (size_t)H * W, nblk = (size_t)runs_blocks(H, W);
+    if (dev_alloc(&v.blk, nblk) || (with_map && dev_alloc(&v.lab, HW))) { runs_free(v); return -1; }
+    v.H = H; v.W = W;
+    v.bytes = nblk * sizeof(int) + (with_map ? HW : 0);
+    runs_free(r);
+    r = v;
     return 0;
 }

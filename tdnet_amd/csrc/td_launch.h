@@ -732,9 +732,53 @@ static int run_tracks(int H, int W, const int32_t* ids, const void* rtable, int3
     TD_LAUNCH(k_tracks_commit, dim3((unsigned)nblk), dim3(256), 0, s, a, (int)std::min<long>(TD_TK_MAX_REGIONS, HW));
     return 0;
 }
+// runs out (td_runs.h): the three launches behind a map the caller or the frame's label launch wrote -- uint8 [H][W] at any byte address (i32 false) or
+// int32 [H][W], 4-byte aligned -- into a table of runs_table_bytes(max_runs) bytes, 8-byte aligned.  `r`: the workspace of this H x W; max_runs is read NOW
+// (a kernel argument: a captured graph replays the one it was captured with).  Only enqueues: every word the table's contract names is stored by a kernel.
+static_assert(TD_RUNS_LAUNCHES == TDNET_RUNS_LAUNCHES && TD_RUNS_DECODE_LAUNCHES == TDNET_RUNS_DECODE_LAUNCHES && TD_RN_OVERFLOW == TDNET_RUNS_OVERFLOW &&
+              sizeof(TdRun) == sizeof(tdnet_run) && sizeof(TdRunsHeader) == sizeof(tdnet_runs_header), "td_runs.h and include/tdnet.h disagree");
+static int runs_table_check(const void* table, const char* who) {
+    if (!table) return td_fail("%s: runs_dev is NULL", who);
+    if ((size_t)table & 7u) return td_fail("%s: runs_dev = %p is not 8-byte aligned", who, table);
+    return 0;
+}
+static int runs_args_check(int H, int W, const void* map, bool i32, const void* table, const RunsState& r, int max_runs, const char* who) {
+    TD_TRY(runs_table_check(table, who));
+    TD_TRY(regions_size_check(H, W, who));
+    if (!map) return td_fail("%s: the map is NULL", who);
+    if (i32 && ((size_t)map & 3u)) return td_fail("%s: ids_dev = %p is not 4-byte aligned", who, map);
+    if (!r.blk || r.H != H || r.W != W) return td_fail("%s: internal: the runs workspace is not that of a %d x %d map", who, H, W);
+    if (max_runs < 1 || (long)max_runs > (long)H * W) return td_fail("%s: max_runs = %d must be in 1..%ld (H W)", who, max_runs, (long)H * W);
+    return 0;
+}
+static int run_runs(int H, int W, const void* map, bool i32, void* table, const RunsState& r, int max_runs, hipStream_t s, const char* who) {
+    TD_TRY(runs_args_check(H, W, map, i32, table, r, max_runs, who));
+    RunsArgs a = RunsArgs();
+    a.map = map; a.table = (unsigned long long*)table; a.blk = r.blk;
+    a.H = H; a.W = W; a.max_runs = max_runs;
+    const long nblk = runs_blocks(H, W);
+    if (i32) TD_LAUNCH(k_runs_count<int>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 4 * sizeof(int), s, a);
+    else TD_LAUNCH(k_runs_count<unsigned char>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 4 * sizeof(int), s, a);
+    TD_LAUNCH(k_runs_scan, dim3(1), dim3(TD_RN_LANES), 4 * sizeof(int), s, a, (int)nblk);
+    if (i32) TD_LAUNCH(k_runs_emit<int>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 4 * sizeof(int), s, a);
+    else TD_LAUNCH(k_runs_emit<unsigned char>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 4 * sizeof(int), s, a);
+    return 0;
+}
+// the way back: one launch; `out` uint8 [H][W] at any byte address or int32 [H][W], 4-byte aligned.  The kernel reads the table's stored from the device,
+// clamped to max_runs.
+static int run_runs_decode(int H, int W, const void* table, int fill, void* out, bool i32, const RunsState& r, int max_runs, hipStream_t s, const char* who) {
+    TD_TRY(runs_args_check(H, W, out, i32, table, r, max_runs, who));
+    RunsArgs a = RunsArgs();
+    a.map = out; a.table = (unsigned long long*)const_cast<void*>(table); a.blk = nullptr;
+    a.H = H; a.W = W; a.max_runs = max_runs;
+    const long nblk = runs_blocks(H, W);
+    if (i32) TD_LAUNCH(k_runs_decode<int>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 0, s, a, fill);
+    else TD_LAUNCH(k_runs_decode<unsigned char>, dim3((unsigned)nblk), dim3(TD_RN_LANES), 0, s, a, fill);
+    return 0;
+}
 
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS, OUT_TRACKS };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS, OUT_TRACKS, OUT_RUNS };
 struct FrameOutput {
     OutKind kind;
     void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF, OUT_MATTE: may be NULL) | rgb [oh][ow][3] | overlay, composite [Hs][Ws][3]
@@ -743,7 +787,7 @@ struct FrameOutput {
     unsigned char* conf;           // OUT_CONF: confidence bytes [H][W]; OUT_MATTE: matte bytes [H][W]
     const unsigned char* src;      // OUT_OVERLAY, OUT_COMPOSITE: the source frame, read by the handle's byte-input configuration
     int32_t* ids;                  // OUT_REGIONS: the id map [H][W] (may be NULL; dst: the uint8 labels, may be NULL too)
-    void* table;                   // OUT_REGIONS: the header and the records
+    void* table;                   // OUT_REGIONS: the header and the records; OUT_RUNS: the runs table (dst: the uint8 labels, may be NULL)
     int32_t* track_ids;            // OUT_TRACKS (OUT_REGIONS' fields plus): the track map [H][W] (may be NULL)
     void* tracks;                  // OUT_TRACKS: the tracks table
 };
@@ -752,6 +796,7 @@ static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if (kind == OUT_RGB && !n->rgb.set) return td_fail("%s: the colour-map output is not configured (call tdnet_set_output_rgb first)", who);
     if (kind == OUT_SCORE && !n->score.set) return td_fail("%s: the score output is not configured (call tdnet_set_score first)", who);
     if ((kind == OUT_REGIONS || kind == OUT_TRACKS) && !n->regions.set) return td_fail("%s: the regions output is not configured (call tdnet_set_regions first)", who);
+    if (kind == OUT_RUNS && !n->runs.set) return td_fail("%s: the runs output is not configured (call tdnet_set_runs first)", who);
     if (kind == OUT_TRACKS && !n->tracks.set) return td_fail("%s: the tracks output is not configured (call tdnet_set_tracks first)", who);
     if ((kind == OUT_MATTE || kind == OUT_COMPOSITE) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
     if (kind == OUT_COMPOSITE && !n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
@@ -785,6 +830,12 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
         TD_TRY(tracks_table_check(o.tracks, who));
         TD_TRY(run_regions(in, C, h, w, H, W, nullptr, (unsigned char*)o.dst, ids, o.table, n->regions, s, who));
         return run_tracks(H, W, ids, o.table, o.track_ids, o.tracks, n->tracks.st, n->regions.max_regions, n->tracks.min_overlap, s, who);
+    }
+    case OUT_RUNS: {                                                   // the label launch as the label entries enqueue it, then the map it wrote
+        unsigned char* lab = o.dst ? (unsigned char*)o.dst : n->runs.lab;
+        TD_TRY(runs_args_check(H, W, lab, false, o.table, n->runs, n->runs.max_runs, who));
+        TD_TRY(launch_upsample_argmax_u8(in, C, h, w, H, W, lab, s));
+        return run_runs(H, W, lab, false, o.table, n->runs, n->runs.max_runs, s, who);
     }
     case OUT_OVERLAY:
         if (n->dst.set) return launch_picture_dst(in, C, h, w, nullptr, nullptr, &n->overlay, &n->u8, o.src, n->dst, (unsigned char*)o.dst, s);

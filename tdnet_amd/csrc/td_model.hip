@@ -147,6 +147,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     score_free(n->score);
     regions_free(n->regions);
     tracks_free(n->tracks);
+    runs_free(n->runs);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -825,6 +826,71 @@ extern "C" int tdnet_tracks_reset(tdnet_t* n, void* stream) {
     TD_HIP(hipGetLastError());
     return 0;
 }
+// ---- runs out ----------------------------------------------------------------------------------------------------------------------------
+// Configuration of the runs output (not a frame call: it may synchronise; idempotent for equal arguments; per handle).  max_runs is plain host state, passed
+// as a kernel argument when an entry ENQUEUES; the workspace (a byte map, the block counts) depends on the handle's size alone and is allocated once.  A
+// failed call changes nothing.
+extern "C" int tdnet_set_runs(tdnet_t* n, int max_runs) {
+    const char* who = "tdnet_set_runs";
+    if (!n) return td_fail("%s: null handle", who);
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(regions_size_check(n->H, n->W, who));
+    if (max_runs < 1 || (long)max_runs > (long)n->H * n->W) return td_fail("%s: max_runs = %d must be in 1..%ld (H W)", who, max_runs, (long)n->H * n->W);
+    TD_ON_DEVICE(n, -1);
+    if (!n->runs.blk) {
+        const size_t before = n->runs.bytes;
+        TD_TRY(runs_alloc(n->runs, n->H, n->W, true, who));
+        n->ws_bytes += n->runs.bytes - before;
+    }
+    n->runs.max_runs = max_runs;
+    n->runs.set = true;
+    return 0;
+}
+extern "C" size_t tdnet_runs_bytes(const tdnet_t* n) { return n && n->runs.set ? runs_table_bytes(n->runs.max_runs) : 0; }
+// What every runs entry checks on the host before anything is enqueued: the configuration exists and the table can be addressed
+static int runs_args(const tdnet* n, const void* table, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(output_configured(n, OUT_RUNS, who));
+    return runs_table_check(table, who);
+}
+// The labels entries with the coding launches behind the label launch.  Same frame, same FIFO step, same labels; labels may be NULL.
+extern "C" int tdnet_forward_runs(tdnet_t* n, const float* img, int pos_id, uint8_t* labels, void* runs_dev, void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_runs: null argument");
+    TD_TRY(runs_args(n, runs_dev, "tdnet_forward_runs"));
+    return frame_out(n, frame_input_f32(img), pos_id, FrameOutput{OUT_RUNS, labels, nullptr, nullptr, nullptr, nullptr, runs_dev}, stream, "tdnet_forward_runs");
+}
+extern "C" int tdnet_forward_u8_runs(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* labels, void* runs_dev, void* stream) {
+    if (!n || !img) return td_fail("tdnet_forward_u8_runs: null argument");
+    TD_TRY(runs_args(n, runs_dev, "tdnet_forward_u8_runs"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_RUNS, labels, nullptr, nullptr, nullptr, nullptr, runs_dev}, stream, "tdnet_forward_u8_runs");
+}
+extern "C" int tdnet_propagate_runs(tdnet_t* n, uint8_t* labels, void* runs_dev, void* stream) {
+    if (!n) return td_fail("tdnet_propagate_runs: null argument");
+    TD_TRY(runs_args(n, runs_dev, "tdnet_propagate_runs"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_RUNS, labels, nullptr, nullptr, nullptr, nullptr, runs_dev}, stream, "tdnet_propagate_runs");
+}
+// the unfused forms: from a uint8 map at any byte address, or an int32 map (the id map or the track map a regions / tracks entry wrote on the same stream)
+static int runs_unfused(tdnet* n, const void* map, bool i32, void* runs_dev, void* stream, const char* who) {
+    if (!n || !map) return td_fail("%s: null argument", who);
+    TD_TRY(runs_args(n, runs_dev, who));
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(run_runs(n->H, n->W, map, i32, runs_dev, n->runs, n->runs.max_runs, (hipStream_t)stream, who));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_labels_runs(tdnet_t* n, const uint8_t* labels, void* runs_dev, void* stream) { return runs_unfused(n, labels, false, runs_dev, stream, "tdnet_labels_runs"); }
+extern "C" int tdnet_ids_runs(tdnet_t* n, const int32_t* ids, void* runs_dev, void* stream) { return runs_unfused(n, ids, true, runs_dev, stream, "tdnet_ids_runs"); }
+// the way back: one launch
+static int runs_decode(tdnet* n, const void* runs_dev, int fill, void* out, bool i32, void* stream, const char* who) {
+    if (!n || !out) return td_fail("%s: null argument", who);
+    TD_TRY(runs_args(n, runs_dev, who));
+    TD_ON_DEVICE(n, -1);
+    TD_TRY(run_runs_decode(n->H, n->W, runs_dev, fill, out, i32, n->runs, n->runs.max_runs, (hipStream_t)stream, who));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int tdnet_runs_labels(tdnet_t* n, const void* runs_dev, int fill, uint8_t* labels, void* stream) { return runs_decode(n, runs_dev, fill, labels, false, stream, "tdnet_runs_labels"); }
+extern "C" int tdnet_runs_ids(tdnet_t* n, const void* runs_dev, int fill, int32_t* ids, void* stream) { return runs_decode(n, runs_dev, fill, ids, true, stream, "tdnet_runs_ids"); }
 extern "C" int tdnet_cache_dims(const tdnet_t* n, int* Lk, int* dk, int* dv) {
     if (!n) return td_fail("tdnet_cache_dims: null handle");
     if (n->cfg.model == 1) return td_fail("tdnet_cache_dims: pspnet has no cache");

@@ -936,3 +936,38 @@ extern "C" int tdnet_op_tracks(const uint8_t* labels, int C, int H, int W, const
     regions_free(r);
     return rc;
 }
+// Runs out (include/tdnet.h) through exactly the launches the runs entries enqueue, on maps the caller holds: from low-resolution logits [C][h][w] (the label
+// launch writes labels [H][W], required then), from a uint8 map at any byte address or from an int32 map, 4-byte aligned.  runs: 16 + 8 (max_runs + 1) bytes,
+// 8-byte aligned.  The workspace is allocated here and released before the call returns.
+extern "C" int tdnet_op_runs(const float* in, int C, int h, int w, int H, int W, uint8_t* labels, const uint8_t* map_u8, const int32_t* map_i32, int max_runs, void* runs,
+                             void* stream) {
+    const char* who = "tdnet_op_runs";
+    if (H < 1 || W < 1) return td_fail("%s: a size >= 1 x 1 expected", who);
+    if ((in != nullptr) + (map_u8 != nullptr) + (map_i32 != nullptr) != 1) return td_fail("%s: exactly one of logits, a uint8 map and an int32 map expected", who);
+    if (in && (!labels || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 and a label map to write expected", who);
+    TD_TRY(runs_table_check(runs, who));
+    RunsState r;
+    TD_TRY(runs_alloc(r, H, W, false, who));
+    hipStream_t s = (hipStream_t)stream;
+    const void* map = in ? (const void*)labels : map_u8 ? (const void*)map_u8 : (const void*)map_i32;
+    int rc = runs_args_check(H, W, map, map_i32 != nullptr, runs, r, max_runs, who);
+    if (!rc && in) rc = launch_upsample_argmax_u8(in, C, h, w, H, W, labels, s);
+    if (!rc) rc = run_runs(H, W, map, map_i32 != nullptr, runs, r, max_runs, s, who);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    runs_free(r);
+    return rc;
+}
+extern "C" int tdnet_op_runs_decode(const void* runs, int max_runs, int fill, int H, int W, uint8_t* out_u8, int32_t* out_i32, void* stream) {
+    const char* who = "tdnet_op_runs_decode";
+    if (H < 1 || W < 1) return td_fail("%s: a size >= 1 x 1 expected", who);
+    if ((out_u8 != nullptr) + (out_i32 != nullptr) != 1) return td_fail("%s: exactly one of a uint8 and an int32 output expected", who);
+    RunsState r;
+    TD_TRY(runs_alloc(r, H, W, false, who));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_runs_decode(H, W, runs, fill, out_u8 ? (void*)out_u8 : (void*)out_i32, out_i32 != nullptr, r, max_runs, s, who);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    runs_free(r);
+    return rc;
+}
+// the pixels a workgroup of the flat launches covers: the tests size their cases from it
+extern "C" int tdnet_op_runs_block(void) { return TD_RN_BLOCK; }

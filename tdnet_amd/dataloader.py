@@ -729,6 +729,52 @@ def track_table(buf, max_regions):
     return t
 
 
+# The library's runs table (include/tdnet.h "runs out"): a 16-byte header, then 8-byte records; record `stored` is the closing record
+RUN_DTYPE = np.dtype([("start", "<u4"), ("value", "<i4")])
+RUNS_HEADER_DTYPE = np.dtype([("count", "<u4"), ("stored", "<u4"), ("status", "<u4"), ("reserved", "<u4")])
+RUNS_OVERFLOW = 1                                                      # header status bit
+
+
+def runs_of(m, max_runs=None):
+    """The run-length table of a map [H, W] (uint8 labels or int32 ids) as the library defines it: pixel i = Y W + X starts a run iff X == 0 or
+    m[i] != m[i - 1].  Returns (RUNS_HEADER_DTYPE record, RUN_DTYPE [stored + 1]): the first min(count, max_runs) runs and the closing record
+    {start of the next run, or H W; 0}.  max_runs None: H W, every run."""
+    m = np.asarray(m)
+    H, W = m.shape
+    flag = np.ones((H, W), bool)
+    flag[:, 1:] = m[:, 1:] != m[:, :-1]
+    starts = np.flatnonzero(flag.reshape(-1))
+    count = int(starts.size)
+    max_runs = H * W if max_runs is None else int(max_runs)
+    stored = min(count, max_runs)
+    recs = np.zeros(stored + 1, RUN_DTYPE)
+    recs["start"][:stored] = starts[:stored]
+    recs["value"][:stored] = m.reshape(-1)[starts[:stored]].astype(np.int64)
+    recs["start"][stored] = starts[stored] if stored < count else H * W
+    hdr = np.zeros(1, RUNS_HEADER_DTYPE)[0]
+    hdr["count"], hdr["stored"], hdr["status"] = count, stored, RUNS_OVERFLOW if count > max_runs else 0
+    return hdr, recs
+
+
+def runs_decode(header, records, H, W, fill, dtype=np.int32):
+    """The map a table stands for: every pixel below the closing record's start takes the value of its run (dtype uint8: the low byte), the rest `fill`."""
+    stored = int(header["stored"])
+    starts = records["start"][:stored + 1].astype(np.int64)
+    out = np.full(H * W, fill, np.int64)
+    out[:starts[stored]] = np.repeat(records["value"][:stored].astype(np.int64), np.diff(starts))
+    return (out & 255).astype(np.uint8).reshape(H, W) if np.dtype(dtype) == np.uint8 else out.astype(np.int32).reshape(H, W)
+
+
+def run_table(buf):
+    """A runs table as the library wrote it (bytes, or an array of 16 + 8 (max_runs + 1) bytes) -> (header record, RUN_DTYPE [stored + 1], copies): the
+    stored runs and the closing record.  What lies behind the closing record was never written and is not looked at."""
+    raw = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    hdr = raw[:16].view(RUNS_HEADER_DTYPE)[0].copy()
+    n = int(hdr["stored"]) + 1
+    assert raw.size >= 16 + 8 * n, (raw.size, n)
+    return hdr, raw[16:16 + 8 * n].view(RUN_DTYPE).copy()
+
+
 class cityscapesLoader():
     colors = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 153, 153], [153, 153, 153],
               [250, 170, 30], [220, 220, 0], [107, 142, 35], [152, 251, 152], [0, 130, 180], [220, 20, 60],
@@ -897,6 +943,68 @@ class LabelDownloader:
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self._inflight.append((ev, buf, tag))
+        return done
+
+    def drain(self):
+        return self._collect(block=True)
+
+
+class RunsDownloader:
+    """Device runs tables (include/tdnet.h "runs out": a uint8 tensor of runs_bytes) -> host records through pinned memory, asynchronously, beside
+    LabelDownloader: submit(table, tag) enqueues ONE copy on a side stream -- the header and a prefix of the records, sized from the count of the latest
+    frame that has arrived plus a quarter (before any has: the whole table) -- and returns what has ARRIVED meanwhile as [(tag, header,
+    records[:stored + 1])], in order; drain() waits for the rest.  Where the header says the prefix was short, the remainder is fetched with a second
+    copy before the frame is handed out.  The downloader keeps the table tensor until then: do not let a later frame overwrite it earlier (rotate
+    depth + 1 tables).  The records are VIEWS of the pinned buffers, valid until the next submit() / drain() call.  .short counts the second copies."""
+
+    def __init__(self, device, depth=3):
+        self.device, self.depth = torch.device(device), max(2, int(depth))
+        self.stream = torch.cuda.Stream(self.device)
+        self._slots, self._inflight, self._handed = [], [], []
+        self._last_count = None
+        self.short = 0
+
+    def _collect(self, block):
+        self._slots.extend(self._handed)
+        self._handed = []
+        out = []
+        while self._inflight and (block or self._inflight[0][0].query()):
+            ev, buf, table, nbytes, tag = self._inflight.pop(0)
+            ev.synchronize()
+            raw = buf.numpy()
+            hdr = raw[:16].view(RUNS_HEADER_DTYPE)[0].copy()
+            need = 16 + 8 * (int(hdr["stored"]) + 1)
+            if need > nbytes:                                          # the prefix was short: the remainder, now
+                self.short += 1
+                with torch.cuda.stream(self.stream):
+                    buf[nbytes:need].copy_(table[nbytes:need], non_blocking=True)
+                self.stream.synchronize()
+            self._last_count = int(hdr["count"])
+            out.append((tag, hdr, raw[16:need].view(RUN_DTYPE)))
+            self._handed.append(buf)
+        return out
+
+    def submit(self, table, tag=None):
+        done = self._collect(block=len(self._inflight) >= self.depth)
+        table = table.view(torch.uint8).reshape(-1)
+        total = int(table.numel())
+        buf = None
+        for j, b in enumerate(self._slots):
+            if b.numel() == total:
+                buf = self._slots.pop(j)
+                break
+        if buf is None:
+            buf = torch.empty(total, dtype=torch.uint8).pin_memory()
+        nbytes = total if self._last_count is None else min(total, 16 + 8 * (self._last_count + self._last_count // 4 + 1))
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(ready)
+            buf[:nbytes].copy_(table[:nbytes], non_blocking=True)
+            table.record_stream(self.stream)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._inflight.append((ev, buf, table, nbytes, tag))
         return done
 
     def drain(self):

@@ -413,6 +413,41 @@ class Engine:
         """forget every track (enqueued on the stream): the next tracked frame's regions are all born, from track 1"""
         self.lib.check(self.lib.tdnet_tracks_reset(self.h, stream))
 
+    # ---- runs out (include/tdnet.h) ----
+    def set_runs(self, max_runs):
+        """The *_runs entries will code a map as a table of at most max_runs (1 .. H W) horizontal runs.  A configuration call: allocates this handle's
+        workspace once."""
+        self.lib.check(self.lib.tdnet_set_runs(self.h, int(max_runs)))
+
+    def runs_bytes(self):
+        """bytes of the table the runs entries write (16 + 8 * (max_runs + 1); 8-byte aligned device memory of the caller's); 0 before set_runs"""
+        return int(self.lib.tdnet_runs_bytes(self.h))
+
+    def forward_runs(self, img_ptr, pos_id, labels_ptr, runs_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_runs(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(runs_ptr), stream))
+
+    def forward_u8_runs(self, img_ptr, pos_id, labels_ptr, runs_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_runs(self.h, _ptr(img_ptr), int(pos_id), _ptr(labels_ptr), _ptr(runs_ptr), stream))
+
+    def propagate_runs(self, labels_ptr, runs_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_runs(self.h, _ptr(labels_ptr), _ptr(runs_ptr), stream))
+
+    def labels_runs(self, labels_ptr, runs_ptr, stream=None):
+        """the unfused form on a uint8 map [H, W] at any byte address"""
+        self.lib.check(self.lib.tdnet_labels_runs(self.h, _ptr(labels_ptr), _ptr(runs_ptr), stream))
+
+    def ids_runs(self, ids_ptr, runs_ptr, stream=None):
+        """the unfused form on an int32 map [H, W] (an id map or a track map), 4-byte aligned"""
+        self.lib.check(self.lib.tdnet_ids_runs(self.h, _ptr(ids_ptr), _ptr(runs_ptr), stream))
+
+    def runs_labels(self, runs_ptr, fill, labels_ptr, stream=None):
+        """a table back into a uint8 map [H, W]; pixels the table does not cover get `fill`"""
+        self.lib.check(self.lib.tdnet_runs_labels(self.h, _ptr(runs_ptr), int(fill), _ptr(labels_ptr), stream))
+
+    def runs_ids(self, runs_ptr, fill, ids_ptr, stream=None):
+        """a table back into an int32 map [H, W]; pixels the table does not cover get `fill`"""
+        self.lib.check(self.lib.tdnet_runs_ids(self.h, _ptr(runs_ptr), int(fill), _ptr(ids_ptr), stream))
+
     # ---- split frame + cache transport (path-parallel single stream; include/tdnet.h) ----
     def encode(self, img_ptr, pos_id, stream=None):
         self.lib.check(self.lib.tdnet_encode(self.h, _ptr(img_ptr), int(pos_id), stream))

@@ -1212,6 +1212,136 @@ class _TDNetBase(nn.Module):
             eng.set_tracks(self._tracks)                               # idempotent; a handle that never ran a tracked frame gets its (zeroed) state here
             eng.tracks_reset(torch.cuda.current_stream().cuda_stream)
 
+    # ---- runs out (not in the reference's model; a caller of the reference downloads the map itself) ----
+    # A label map or an id / track map as a run-length table (include/tdnet.h "runs out").  The coding methods return (..., table int64 [N, 2 + max_runs + 1]
+    # on the device, [(header, records[:stored + 1]) per sample]); reading the records synchronises with the device and copies the header and the stored
+    # prefix only.  dataloader.RunsDownloader takes table[i] for a loop that must not wait.
+    _runs = None
+
+    def set_runs(self, max_runs=None):
+        """The configuration of the *_runs methods: the number of runs a table holds (1 .. H W; None: H W, every map fits).  Host state of the model; every
+        handle is told when it runs."""
+        if max_runs is not None and (isinstance(max_runs, bool) or not isinstance(max_runs, (int, np.integer)) or int(max_runs) < 1):
+            raise RuntimeError("set_runs(): max_runs must be an integer >= 1 or None, got %r" % (max_runs,))
+        self._runs = (None if max_runs is None else int(max_runs),)
+        return self._runs
+
+    def _need_runs(self, who, H, W):
+        if self._runs is None:
+            raise RuntimeError("%s(): no configuration (call set_runs() first)" % who)
+        max_runs = H * W if self._runs[0] is None else self._runs[0]
+        if max_runs > H * W:
+            raise RuntimeError("%s(): max_runs = %d is more than the %d pixels of a %d x %d map" % (who, max_runs, H * W, H, W))
+        return max_runs
+
+    @staticmethod
+    def _runs_tables(table):
+        from ..dataloader import RUN_DTYPE, RUNS_HEADER_DTYPE
+        out = []
+        for i in range(table.shape[0]):
+            hdr = table[i, :2].cpu().numpy().view(RUNS_HEADER_DTYPE)[0]
+            out.append((hdr, table[i, 2:2 + int(hdr["stored"]) + 1].cpu().numpy().view(RUN_DTYPE)))
+        return out
+
+    def forward_runs(self, img, pos_id=0):
+        """forward_labels() with the run-length table of the labels behind them: (labels uint8 [N, H, W], table, [(header, records)])."""
+        self._check_frame(img, pos_id)
+        img = img.contiguous().float()
+        n, H, W = img.shape[0], img.shape[2], img.shape[3]
+        max_runs = self._need_runs("forward_runs", H, W)
+        out = torch.empty((n, H, W), device=img.device, dtype=torch.uint8)
+        table = torch.empty((n, 2 + max_runs + 1), device=img.device, dtype=torch.int64)
+
+        def one(i, eng, s):
+            eng.set_runs(max_runs)
+            eng.forward_runs(img[i].data_ptr(), pos_id, out[i].data_ptr(), table[i].data_ptr(), s)
+        self._for_each_sample(img, one)
+        return out, table, self._runs_tables(table)
+
+    def forward_u8_runs(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
+        """forward_labels_u8() with the run-length table behind the labels: bytes in (any byte-input configuration: view= / surface= as there)."""
+        view = self._one_of(view, surface, "view", "surface")
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        max_runs = self._need_runs("forward_u8_runs", H, W)
+        img = img_u8.contiguous()
+        out = torch.empty((img.shape[0], H, W), device=img.device, dtype=torch.uint8)
+        table = torch.empty((img.shape[0], 2 + max_runs + 1), device=img.device, dtype=torch.int64)
+
+        def one(i, eng, s):
+            eng.set_runs(max_runs)
+            eng.forward_u8_runs(img[i].data_ptr(), pos_id, out[i].data_ptr(), table[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out, table, self._runs_tables(table)
+
+    def propagate_runs(self):
+        """propagate() with the run-length table behind the labels, for the frame encode() / encode_u8() left pending."""
+        if self._engine is None or self._pending_shape is None:
+            raise RuntimeError("propagate_runs(): no encoded frame is pending (call encode(img, pos_id) first)")
+        H, W, dev = self._pending_shape
+        max_runs = self._need_runs("propagate_runs", H, W)
+        out = torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+        table = torch.empty((1, 2 + max_runs + 1), device=dev, dtype=torch.int64)
+        self._engine.set_runs(max_runs)
+        self._pending_shape = None
+        self._engine.propagate_runs(out.data_ptr(), table.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out, table, self._runs_tables(table)
+
+    def _runs_maps(self, who, maps, dtype):
+        if self._engine is None:
+            raise RuntimeError("%s(): no handle yet" % who)
+        H, W = self._engine_key[:2]
+        if not torch.is_tensor(maps) or maps.dtype != dtype or maps.dim() != 3 or tuple(maps.shape[1:]) != (H, W) or not maps.is_cuda:
+            raise RuntimeError("%s(): expected %s maps [N, %d, %d] on the device" % (who, str(dtype).replace("torch.", ""), H, W))
+        engines = [self._engine] + list(self._extra_engines)
+        if maps.shape[0] > len(engines):
+            raise RuntimeError("%s(): %d maps but %d handle(s)" % (who, maps.shape[0], len(engines)))
+        return H, W, engines
+
+    def _runs_code(self, who, maps, dtype):
+        H, W, engines = self._runs_maps(who, maps, dtype)
+        max_runs = self._need_runs(who, H, W)
+        maps = maps.contiguous()
+        table = torch.empty((maps.shape[0], 2 + max_runs + 1), device=maps.device, dtype=torch.int64)
+        s = torch.cuda.current_stream(maps.device).cuda_stream
+        for i in range(maps.shape[0]):
+            engines[i].set_runs(max_runs)
+            (engines[i].labels_runs if dtype == torch.uint8 else engines[i].ids_runs)(maps[i].data_ptr(), table[i].data_ptr(), s)
+        return table, self._runs_tables(table)
+
+    def labels_runs(self, labels_u8):
+        """The unfused form: uint8 maps [N, H, W] (CUDA) of this model's size, sample i on handle i.  Returns (table, [(header, records)])."""
+        return self._runs_code("labels_runs", labels_u8, torch.uint8)
+
+    def ids_runs(self, ids_i32):
+        """The unfused form on int32 maps [N, H, W] (CUDA): the id maps or track maps of the regions / tracks methods, or any int32 values."""
+        return self._runs_code("ids_runs", ids_i32, torch.int32)
+
+    def _runs_decode(self, who, table, fill, dtype):
+        if self._engine is None:
+            raise RuntimeError("%s(): no handle yet" % who)
+        H, W = self._engine_key[:2]
+        max_runs = self._need_runs(who, H, W)
+        if not torch.is_tensor(table) or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2 + max_runs + 1 or not table.is_cuda:
+            raise RuntimeError("%s(): expected int64 tables [N, %d] on the device (max_runs = %d)" % (who, 2 + max_runs + 1, max_runs))
+        engines = [self._engine] + list(self._extra_engines)
+        if table.shape[0] > len(engines):
+            raise RuntimeError("%s(): %d tables but %d handle(s)" % (who, table.shape[0], len(engines)))
+        table = table.contiguous()
+        out = torch.empty((table.shape[0], H, W), device=table.device, dtype=dtype)
+        s = torch.cuda.current_stream(table.device).cuda_stream
+        for i in range(table.shape[0]):
+            engines[i].set_runs(max_runs)
+            (engines[i].runs_labels if dtype == torch.uint8 else engines[i].runs_ids)(table[i].data_ptr(), int(fill), out[i].data_ptr(), s)
+        return out
+
+    def runs_labels(self, table, fill=0):
+        """Tables back into uint8 maps [N, H, W] on the device; pixels a table does not cover (an overflowed one) get `fill`."""
+        return self._runs_decode("runs_labels", table, fill, torch.uint8)
+
+    def runs_ids(self, table, fill=0):
+        """Tables back into int32 maps [N, H, W] on the device; pixels a table does not cover get `fill`."""
+        return self._runs_decode("runs_ids", table, fill, torch.int32)
+
     @staticmethod
     def _background(background):
         if background is None:

@@ -37,6 +37,9 @@ picture would go, the frame seen through the matte over that background, at the 
 behind every frame's labels (include/tdnet.h "regions out") and prints the count per frame (`--tracks [MIN_OVERLAP]` follows them across frames, "tracks out":
 matched / born / ended per frame, and the columns track,age,origin in the CSVs); `--regions_out DIR` writes one CSV per frame,
 DIR/folder/name.csv: id,label,area,x0,y0,x1,y1,cx,cy in network-size pixels.
+`--runs [MAX_RUNS]` (fp32 or `--u8` frames) codes every frame's labels as a run-length table on the device behind the label launch (include/tdnet.h
+"runs out"); the PNGs are those of the plain loop.  `--runs_out DIR` downloads the tables asynchronously (dataloader.RunsDownloader: the header and the
+stored records only) and writes DIR/folder/name.npy: the records (start, value), the closing record last.
 """
 import argparse
 import os
@@ -180,6 +183,18 @@ def test(args):
     if min_overlap is not None and min_overlap < 1:
         raise SystemExit("--tracks: a minimum overlap of at least 1 pixel expected, got %r" % (min_overlap,))
     with_tracks = min_overlap is not None
+    max_runs, runs_dir = getattr(args, "runs", None), getattr(args, "runs_out", None)   # --runs [MAX_RUNS]: checked before anything is loaded
+    if runs_dir is not None and max_runs is None:
+        raise SystemExit("--runs_out writes the tables of --runs: give --runs [MAX_RUNS] with it")
+    if max_runs is not None:
+        if max_runs != 0 and not 1 <= max_runs <= H * W:
+            raise SystemExit("--runs: a table of 1 .. %d runs (H W) expected, got %r" % (H * W, max_runs))
+        if rgb or overlay is not None or with_matte or with_regions or getattr(args, "gt_path", None) or getattr(args, "prefetch", False) or \
+                getattr(args, "conf", None) is not None or getattr(args, "min_conf", None) is not None or nv12 or crop is not None or yuv is not None or \
+                getattr(args, "out_nv12", None) is not None or getattr(args, "out_yuv", None) is not None:
+            raise SystemExit("--runs asks for a tail of its own in the frame-by-frame loop: with --u8 or fp32 frames only, not with --rgb, --overlay, --matte, --regions, "
+                             "--gt_path, --prefetch, --conf, --min_conf, --nv12, --yuv, --crop, --out_nv12 or --out_yuv")
+    with_runs = max_runs is not None
     out_nv12, out_yuv = getattr(args, "out_nv12", None), getattr(args, "out_yuv", None)
     out_layout = None
     if out_yuv is not None:                                            # LAYOUT:FILE; checked before anything is loaded
@@ -246,6 +261,17 @@ def test(args):
         model.set_regions(region_ids, regions_conn, REGIONS_CLI_MAX, regions_min_area)
     if with_tracks:
         model.set_tracks(min_overlap)
+    runs_down = None
+    if with_runs:
+        from tdnet_amd.dataloader import RunsDownloader
+        model.set_runs(max_runs or None)                               # --runs without a value: H W, every map fits
+        runs_down = RunsDownloader(device)
+
+    def save_runs(arrived):                                            # --runs_out: one .npy of records (start, value; the closing record last) per frame
+        for (img_name, folder), hdr, recs in arrived:
+            if runs_dir is not None:
+                os.makedirs(os.path.join(runs_dir, folder), exist_ok=True)
+                np.save(os.path.join(runs_dir, folder, os.path.splitext(img_name)[0] + ".npy"), recs)
 
     def save_regions(table, img_name, folder, tracks=None):            # --regions_out: one CSV per frame; the centroid is sum / area
         os.makedirs(os.path.join(regions_dir, folder), exist_ok=True)
@@ -420,6 +446,8 @@ def test(args):
             elif with_regions:
                 output, _, tables = model.forward_regions_u8(image, i % path_num, (H, W), return_ids=False, **vk(view)) if byte else \
                     model.forward_regions(image, i % path_num, return_ids=False)
+            elif with_runs:
+                output, rtable, _ = model.forward_u8_runs(image, i % path_num, (H, W)) if byte else model.forward_runs(image, i % path_num)
             elif rgb:
                 output = colour_map(image, i % path_num, ori_size, src_size, view)
             elif overlay is not None and with_conf:                    # the accepted pixels tinted, the rejected ones (label 255) the bare frame
@@ -453,6 +481,9 @@ def test(args):
                     "" if not with_tracks else "   matched / born / ended {0:d} / {1:d} / {2:d}".format(tracks[0].matched, len(tracks[0]) - tracks[0].matched, tracks[0].ended)))
                 if regions_dir is not None:
                     save_regions(tables[0], img_name, folder, tracks[0] if with_tracks else None)
+            elif with_runs:                                            # the usual picture of the uint8 labels; the table travels beside it
+                save(output.cpu().numpy(), img_name, folder, ori_size)
+                save_runs(runs_down.submit(rtable[0], (img_name, folder)))
             elif rgb or overlay is not None or composite is not None:
                 save_rgb(output.cpu().numpy(), img_name, folder, ori_size)
                 if overlay is not None and conf_dir is not None:
@@ -464,6 +495,8 @@ def test(args):
             else:
                 save(output.data.max(1)[1].cpu().numpy(), img_name, folder, ori_size)
             print(" Frame {0:2d}   RunningTime/Latency={1:3.5f} s".format(i + 1, elapsed_time))
+    if runs_down is not None:
+        save_runs(runs_down.drain())
     print("---------------------")
     print(" Model: {0:s}".format(args.model))
     if i > 5:
@@ -500,6 +533,8 @@ if __name__ == "__main__":
     parser.add_argument("--regions_min_area", nargs="?", type=int, default=None, help="with --regions: drop regions of fewer pixels (default 1)")
     parser.add_argument("--tracks", nargs="?", type=int, const=1, default=None, help="with --regions: follow the regions across frames on the device (optional value: the minimum overlap in pixels of a match, default 1); prints matched / born / ended per frame, --regions_out CSVs gain track,age,origin")
     parser.add_argument("--regions_out", nargs="?", type=str, default=None, help="with --regions: directory for one CSV per frame: id,label,area,x0,y0,x1,y1,cx,cy (network-size pixels, inclusive box)")
+    parser.add_argument("--runs", nargs="?", type=int, const=0, default=None, help="code every frame's labels as a run-length table on the device behind the label launch (optional value: the runs a table holds, default H W: every map fits); the PNGs are those of the plain loop")
+    parser.add_argument("--runs_out", nargs="?", type=str, default=None, help="with --runs: directory for one .npy per frame: the records (start, value) of the frame's runs and the closing record, downloaded asynchronously")
     parser.add_argument("--overlay", nargs="?", type=float, default=None, help="with --u8 or --nv12: write the class colours blended over the frame at this opacity (0..1), at the frame's own size")
     parser.add_argument("--out_nv12", nargs="?", type=str, default=None, help="with --rgb or --overlay (and --u8 or --nv12): append every frame's picture as a tight NV12 surface (--nv12_standard) to this raw file, written by the device through a destination view; a further clip's surfaces go to FILE with the clip's folder name in front of the extension")
     parser.add_argument("--yuv", nargs="?", type=str, default=None, help="frames go to the device as tight surfaces of this layout (nv12, nv21, i420, p010, yuy2, uyvy; --nv12_standard): conversion, resize and normalisation in the frame's first launch; combines with what --nv12 combines with, --crop included")
