@@ -550,6 +550,54 @@ int  tdnet_set_output_composite(tdnet_t* h, int mode, const uint8_t* bg_rgb /* [
 int  tdnet_forward_u8_composite(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* out_dev, void* stream);
 /* the unfused form: from a matte map [H][W] the caller already holds (any byte address); needs no tdnet_set_matte */
 int  tdnet_matte_composite(tdnet_t* h, const uint8_t* matte_u8_dev, const uint8_t* img_dev, uint8_t* out_dev, void* stream);
+/* ---- refined matte -------------------------------------------------------------------------------------------------
+ * A matte byte is a x8 bilinear upsample of 1/8-resolution logits: its outline is soft and ignores the real edge, which the frame shows.  The standard
+ * remedy is He et al.'s guided filter of the matte with the frame's luma as the guide.  It is defined here so that EVERY STEP IS AN INTEGER OPERATION OR ONE
+ * CORRECTLY ROUNDED fp32 OPERATION: box sums of integers do not depend on the order of the additions, so the device result does not depend on how the
+ * kernels tile the map, and the oracle (tdnet_amd/dataloader.py refine_matte_u8) is matched byte for byte.
+ *   inputs      G (guide) and M (matte): uint8 [rows][cols]; radius r in 1..16; eps in 4..65025, an integer in SQUARED BYTE units (65 ~ 1e-3 * 255^2)
+ *   window      of pixel (y, x): rows max(0, y - r) .. min(rows - 1, y + r), columns likewise -- the box clipped to the map; N its pixel count, S_x the sum
+ *               of x over it
+ *   stage 1     cov = N S_GM - S_G S_M;   den = N S_GG - S_G^2 + eps N^2 (> 0);   a = f32(cov) / f32(den);
+ *               a_q = clamp(rint(a * 1024.f), -32767, 32767);   b_q = rint(f32(1024 S_M - a_q S_G) / f32(16 N))      -- the slope in Q10, the offset in Q6
+ *   stage 2     A = sum a_q, B = sum b_q over the window;   out = clamp8(rint(f32(A G + 16 B) / f32(1024 N)))
+ *   arithmetic  f32 is the round-to-nearest-even conversion of the integer, / the IEEE fp32 division, rint rounds halves to even (rintf); the library is
+ *               built with -ffp-contract=off
+ *   bounds      the box sums fit 32 bits (S_GG, S_GM <= 1089 * 65025); cov, den, 1024 S_M - a_q S_G and A G + 16 B need 64 (N S_GM reaches 7.7e10);
+ *               |a_q| <= 32767 fits 16 bits; |b_q| <= 33791 * 255 / 16; |A| <= 3.6e7 and |B| <= 5.9e8 fit 32.  With eps >= 4, |a| <= sigma_M / (2 sqrt(eps)) < 32:
+ *               the clamp on a_q is a guard that never binds
+ *   exact       a constant matte comes back unchanged for any guide, r and eps (cov = 0, and 1024 N c is representable); an all-255 guide and matte give
+ *               255; the result does not depend on the byte address or the pitch of any of the three maps
+ *   guide       of a frame: Y = (77 R + 150 G + 29 B + 128) >> 8 of the converted, clamped r g b pixel (dataloader.py luma_u8)
+ * tdnet_refine_matte is the operator on maps the caller holds: any size up to 65535 per side and 2^30 - 16 pixels, any byte addresses, rows guide_pitch /
+ * matte_pitch / out_pitch >= cols bytes apart (only the pixels' bytes are read or written, never the padding).  It needs no configuration, only enqueues
+ * its TDNET_REFINE_OP_LAUNCHES launches (the coefficient planes, then the bytes) and works inside a hipGraph capture; radius and eps travel as kernel
+ * arguments read at enqueue, so a captured graph replays those of capture time.  scratch_dev: tdnet_refine_scratch_bytes bytes (6 per pixel), 4-byte aligned,
+ * the caller's; its contents afterwards are unspecified.  Checked on the host before anything is enqueued, the message naming the argument: the ranges of
+ * radius and eps, the size, pitch >= cols, the scratch's alignment, and that out overlaps neither input nor the scratch and the scratch neither input.
+ * THE FRAME ENTRIES refine the frame's matte at the SOURCE's size: the guide is the luma of the source pixel as "overlay out" / "source views" / "surfaces" define it,
+ * the matte M_src[y][x] = matte[ys[y]][xs[x]] with the composite's nearest_index tables -- the very byte the composite uses.  The frame's last launch writes both
+ * planes into the handle's workspace (in place of the label launch), the operator's two launches follow: TDNET_REFINE_LAUNCHES = 3, and tdnet_last_launch_count
+ * = the label entry's + 2.  out_dev: [Hs][Ws] bytes, tight, any byte address, not overlapping the source extent.
+ * tdnet_set_matte_refine: radius 0 = off (the default), else radius 1..16 and eps 4..65025.  Configuration: it may allocate and synchronise, is idempotent for
+ * equal arguments, per handle, and accepted before or after the byte-input configuration; the workspace follows the source size -- 2 + 6 + 1 bytes per source
+ * pixel and two index tables -- and is counted in tdnet_memory_bytes.  A failed call leaves the previous state in force.
+ * tdnet_forward_u8_matte_refined / tdnet_propagate_matte_refined (the split frame: the caller passes the source again) need tdnet_set_matte, a byte input and a
+ * non-zero radius; otherwise they fail naming the missing call and change nothing (a pending encoded frame stays pending).  They only enqueue.
+ * WITH A NON-ZERO RADIUS IN FORCE tdnet_forward_u8_composite, tdnet_propagate_composite and tdnet_matte_composite composite through the refined matte: the three
+ * launches, then the existing composite kernel from the refined map -- the label entry's launch count + 3; every rule of "matte out" holds (4:2:0 destinations
+ * stay refused).  With radius 0 they are byte for byte and launch for launch what they are without this section.                                     */
+#define TDNET_REFINE_MAX_RADIUS 16
+#define TDNET_REFINE_MIN_EPS 4
+#define TDNET_REFINE_MAX_EPS 65025
+#define TDNET_REFINE_OP_LAUNCHES 2
+#define TDNET_REFINE_LAUNCHES 3
+int  tdnet_set_matte_refine(tdnet_t* h, int radius /* 0: off */, int eps);
+int  tdnet_forward_u8_matte_refined(tdnet_t* h, const uint8_t* img_dev, int pos_id, uint8_t* out_dev /* [Hs][Ws] */, void* stream);
+int  tdnet_propagate_matte_refined(tdnet_t* h, const uint8_t* img_dev, uint8_t* out_dev /* [Hs][Ws] */, void* stream);
+size_t tdnet_refine_scratch_bytes(int rows, int cols);      /* 0 for a size below 1 x 1 */
+int  tdnet_refine_matte(tdnet_t* h, const uint8_t* guide_dev, size_t guide_pitch, const uint8_t* matte_dev, size_t matte_pitch, uint8_t* out_dev, size_t out_pitch,
+                        int rows, int cols, int radius, int eps, void* scratch_dev, void* stream);
 /* ---- regions out ---------------------------------------------------------------------------------------------------
  * What a video pipeline does next with a semantic map is not per pixel: the "thing" classes become objects -- a box, an area and a centroid per blob
  * for a tracker, a counter or an alert.  These entries label the connected components of a class set on the device, behind the frame's labels, instead

@@ -200,6 +200,16 @@ int tdnet_op_upsample_argmax_matte(const float* in_dev, int C, int h, int w, int
 int tdnet_op_composite(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8_dev, const uint8_t* src_base,
                        const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* dst_base, const tdnet_view* dst_view, int mode, const uint8_t* bg_rgb,
                        void* stream);
+/* Stage 1 of the refined matte (include/tdnet.h "refined matte") alone, through the launch the operator entry enqueues first: the coefficient planes a_q
+ * (aq_dev, int16 [rows,cols]) and b_q (bq_dev, int32 [rows,cols]) of a guide and a matte at any byte addresses.  The scratch is allocated for the call. */
+int tdnet_op_refine_coeff(const uint8_t* guide_dev, size_t guide_pitch, const uint8_t* matte_dev, size_t matte_pitch, int rows, int cols, int radius, int eps,
+                          int16_t* aq_dev, int32_t* bq_dev, void* stream);
+/* The gather launch of the refined frame entries alone: luma and M_src [Hs,Ws] (tight, 4-byte aligned) of the source at src_base read through src_surface (if not
+ * NULL) or src_view; the matte from logits [C,h,w] and the class set classes[0 .. n) (matte_u8_dev == NULL) or from a matte map [H,W].                 */
+int tdnet_op_refine_gather(const float* in_dev, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8_dev, const uint8_t* src_base,
+                           const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* luma_dev, uint8_t* msrc_dev, void* stream);
+/* the tiles of the operator's two launches (columns; rows of the first; rows of the second): the tests size their cases from them */
+int tdnet_op_refine_tile(int* tx, int* ty_coeff, int* ty_apply);
 /* Regions out (include/tdnet.h) through exactly the launches the regions entries enqueue, on maps the caller holds: from low-resolution logits [C,h,w]
  * (labels_in_u8_dev == NULL; the uint8 labels go to labels_u8_dev [H,W] if given) or from a uint8 label map [H,W] at any byte address (in_dev, h, w and
  * labels_u8_dev are then ignored).  classes: n class ids below C on the HOST; connectivity 4 | 8; ids_dev: int32 [H,W] or NULL; regions_dev: 16 + 48

@@ -126,6 +126,11 @@ SYMBOLS = {
     "tdnet_forward_u8_composite": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_propagate_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdnet_matte_composite": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_set_matte_refine": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tdnet_forward_u8_matte_refined": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_propagate_matte_refined": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdnet_refine_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "tdnet_refine_matte": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 4 + [c_void_p, c_void_p]),
     "tdnet_set_regions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "tdnet_regions_bytes": (ctypes.c_size_t, [c_void_p]),
     "tdnet_forward_regions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -219,6 +224,9 @@ TEST_SYMBOLS = {
     "tdnet_op_upsample_argmax_conf": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_upsample_argmax_matte": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "tdnet_op_composite": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, ctypes.c_int] + [c_void_p] * 6 + [ctypes.c_int, c_void_p, c_void_p]),
+    "tdnet_op_refine_coeff": (ctypes.c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "tdnet_op_refine_gather": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, ctypes.c_int] + [c_void_p] * 7),
+    "tdnet_op_refine_tile": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
     "tdnet_op_regions": (ctypes.c_int, [c_void_p] + [ctypes.c_int] * 5 + [c_void_p, c_void_p, c_void_p] + [ctypes.c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
     "tdnet_op_regions_tile": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tdnet_op_tracks_state_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

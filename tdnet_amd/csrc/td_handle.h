@@ -44,6 +44,7 @@
 #include "td_regions.h"
 #include "td_runs.h"
 #include "td_tracks.h"
+#include "td_refine.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -358,6 +359,17 @@ struct RunsState {
     unsigned char* lab = nullptr;                                      // [H][W]
     size_t bytes = 0;
 };
+// The refined matte of a handle (tdnet_set_matte_refine): radius (0 = off) and eps -- plain host state, kernel arguments read when an entry enqueues -- and the
+// workspace at the SOURCE's size (it follows the byte input like the overlay's tables): luma and M_src (2 bytes per source pixel), the coefficient planes (6), the
+// refined map (1), and the identity index tables the existing composite kernel reads the refined map through.
+struct RefineState {
+    int radius = 0, eps = 0;
+    int Hs = 0, Ws = 0;                                                // the source size the workspace was allocated for (0: none yet)
+    unsigned char *luma = nullptr, *msrc = nullptr, *refined = nullptr;   // [Hs][Ws] each
+    int* scratch = nullptr;                                            // 6 Hs Ws bytes: b_q int32, then a_q int16
+    int *idy = nullptr, *idx = nullptr;                                // [Hs], [Ws]: 0, 1, 2, ...
+    size_t bytes = 0;
+};
 struct ProfRec { int family; int dominant; hipEvent_t e0, e1; double flops; };   // dominant: 0 no, 1 direct 3x3 128x128, 2 Winograd batched GEMM
 
 // Everything a model owns that does NOT change from frame to frame: the host state_dict until it is finalized, then the BN-folded,
@@ -452,6 +464,7 @@ struct tdnet {
     RegionsOutput regions;                                            // tdnet_set_regions
     TracksOutput tracks;                                              // tdnet_set_tracks
     RunsState runs;                                                   // tdnet_set_runs
+    RefineState refine;                                                // tdnet_set_matte_refine
     int min_conf = 0, reject_label = 255;                              // tdnet_set_confidence: plain host state, read when a *_conf entry enqueues its last launch
     CompositeOutput comp;                                              // tdnet_set_output_composite
     bool matte_set = false;                                            // tdnet_set_matte: plain host state like min_conf; the *_matte entries pass the words as kernel arguments
@@ -1051,6 +1064,39 @@ static void runs_free(RunsState& r) {
     if (r.blk) hipFree(r.blk);
     if (r.lab) hipFree(r.lab);
     r = RunsState();
+}
+// refined matte: the workspace of RefineState for a source of Hs x Ws.  On failure `r` is left as it was; radius and eps are the caller's.
+static void refine_free(RefineState& r) {
+    if (r.luma) hipFree(r.luma);
+    if (r.msrc) hipFree(r.msrc);
+    if (r.refined) hipFree(r.refined);
+    if (r.scratch) hipFree(r.scratch);
+    if (r.idy) hipFree(r.idy);
+    if (r.idx) hipFree(r.idx);
+    const int radius = r.radius, eps = r.eps;
+    r = RefineState();
+    r.radius = radius; r.eps = eps;
+}
+static int refine_alloc(RefineState& r, int Hs, int Ws, const char* who) {
+    if (r.luma && r.Hs == Hs && r.Ws == Ws) return 0;
+    if (Hs < 1 || Ws < 1 || Hs > 65535 || Ws > 65535 || (long)Hs * Ws > TD_RG_MAX_PIXELS)
+        return td_fail("%s: a source of %d x %d is outside 1..65535 per side and 2^30 - 16 pixels", who, Hs, Ws);
+    RefineState v;
+    const size_t n = (size_t)Hs * Ws;
+    std::vector<int> id((size_t)(Hs > Ws ? Hs : Ws));
+    for (size_t i = 0; i < id.size(); ++i) id[i] = (int)i;
+    if (dev_alloc(&v.luma, n) || dev_alloc(&v.msrc, n) || dev_alloc(&v.refined, n) || dev_alloc(&v.scratch, (6 * n + 3) / 4) || dev_alloc(&v.idy, (size_t)Hs) ||
+        dev_alloc(&v.idx, (size_t)Ws) || hipMemcpy(v.idy, id.data(), (size_t)Hs * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v.idx, id.data(), (size_t)Ws * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        refine_free(v);
+        return td_fail("%s: allocating the refined matte's workspace for a %d x %d source failed", who, Hs, Ws);
+    }
+    v.Hs = Hs; v.Ws = Ws;
+    v.bytes = 9 * n + ((size_t)Hs + Ws) * sizeof(int);
+    v.radius = r.radius; v.eps = r.eps;
+    refine_free(r);
+    r = v;
+    return 0;
 }
 // the flat launches' grid: H W / 4 aligned groups, the head lane and a tail lane (td_out.h out_grid_run's count)
 static long runs_blocks(int H, int W) { return ((long)H * W / 4 + 2 + TD_RN_LANES - 1) / TD_RN_LANES; }

@@ -635,8 +635,9 @@ static int composite_dst_check(const U8Input& u, const CompositeOutput& c, const
         return td_fail("%s: the composite is %d x %d but the destination view's rectangle is %d x %d (tdnet_set_output_view: nothing is resized)", who, u.Hs, u.Ws, d.h, d.w);
     return 0;
 }
+// rf != NULL: `map` is a map at the SOURCE's size (the refined matte in rf's workspace), read through rf's identity tables with W = Ws: the same kernels.
 static int launch_composite(const float* in, int C, int h, int w, const unsigned char* map, const MatteSet& set, const OverlayOutput& o, const U8Input& u,
-                            const unsigned char* src, const CompositeOutput& c, const DstOutput& d, unsigned char* base, hipStream_t s) {
+                            const unsigned char* src, const CompositeOutput& c, const DstOutput& d, unsigned char* base, hipStream_t s, const RefineState* rf = nullptr) {
     if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("composite: the index tables of this source size are missing (their allocation failed)");
     TD_TRY(out_check("composite", "src_height", o.Hs, map ? 1 : C));
     TD_TRY(composite_dst_check(u, c, d, "composite"));
@@ -644,6 +645,7 @@ static int launch_composite(const float* in, int C, int h, int w, const unsigned
     CompArgs a = CompArgs();
     a.in = in; a.map = map; a.ys = o.ys; a.xs = o.xs;
     a.C = C; a.h = h; a.w = w; a.H = o.H; a.W = o.W; a.oh = o.Hs; a.ow = o.Ws;
+    if (rf) { a.ys = rf->idy; a.xs = rf->idx; a.H = rf->Hs; a.W = rf->Ws; }
     a.bg = u.swap ? (unsigned)c.bg[2] | ((unsigned)c.bg[1] << 8) | ((unsigned)c.bg[0] << 16)      // the picture word's bytes are the source's: b g r
                   : (unsigned)c.bg[0] | ((unsigned)c.bg[1] << 8) | ((unsigned)c.bg[2] << 16);
     a.set = set;
@@ -663,6 +665,59 @@ static int launch_composite(const float* in, int C, int h, int w, const unsigned
 #undef TD_C
     }
     return td_fail("internal: no composite kernel for source form %d into destination form %d", src_form, dst_form);
+}
+// refined matte (td_refine.h): the guided filter of a matte byte map with a guide byte map of the same size, two launches.  The scratch holds the
+// coefficient planes: b_q int32 [rows][cols], then a_q int16 [rows][cols] -- 6 bytes per pixel, 4-byte aligned.
+static_assert(TD_RF_MAX_RADIUS == TDNET_REFINE_MAX_RADIUS && TD_RF_MIN_EPS == TDNET_REFINE_MIN_EPS && TD_RF_MAX_EPS == TDNET_REFINE_MAX_EPS && TDNET_REFINE_OP_LAUNCHES == 2 && TDNET_REFINE_LAUNCHES == 3,
+              "td_refine.h and include/tdnet.h disagree");
+static size_t refine_scratch_bytes(int rows, int cols) { return rows < 1 || cols < 1 ? 0 : (size_t)6 * (size_t)rows * (size_t)cols; }
+static int refine_range_check(int radius, int eps, const char* who) {
+    if (radius < 1 || radius > TD_RF_MAX_RADIUS) return td_fail("%s: radius = %d must be in 1..%d", who, radius, TD_RF_MAX_RADIUS);
+    if (eps < TD_RF_MIN_EPS || eps > TD_RF_MAX_EPS) return td_fail("%s: eps = %d must be in %d..%d (squared byte units)", who, eps, TD_RF_MIN_EPS, TD_RF_MAX_EPS);
+    return 0;
+}
+static int refine_size_check(int rows, int cols, const char* who) {
+    if (rows < 1 || cols < 1 || rows > 65535 || cols > 65535 || (long)rows * cols > TD_RG_MAX_PIXELS)
+        return td_fail("%s: a map of %d x %d is outside 1..65535 per side and 2^30 - 16 pixels", who, rows, cols);
+    return 0;
+}
+static bool refine_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+static size_t refine_extent(size_t pitch, int rows, int cols) { return (size_t)(rows - 1) * pitch + (size_t)cols; }
+// every check of the operator, before anything is enqueued; want_out false: the coefficient launch alone (the tests' entry): no output, and the scratch may be NULL
+static int refine_args_check(const unsigned char* guide, size_t gpitch, const unsigned char* matte, size_t mpitch, const unsigned char* out, size_t opitch, bool want_out,
+                             int rows, int cols, int radius, int eps, const void* scratch, const char* who) {
+    if (!guide || !matte || (want_out && (!out || !scratch))) return td_fail("%s: null argument", who);
+    TD_TRY(refine_size_check(rows, cols, who));
+    TD_TRY(refine_range_check(radius, eps, who));
+    if (gpitch < (size_t)cols) return td_fail("%s: guide_pitch = %zu is below cols = %d", who, gpitch, cols);
+    if (mpitch < (size_t)cols) return td_fail("%s: matte_pitch = %zu is below cols = %d", who, mpitch, cols);
+    if (want_out && opitch < (size_t)cols) return td_fail("%s: out_pitch = %zu is below cols = %d", who, opitch, cols);
+    if (!scratch) return 0;                                            // the tests' coefficient entry allocates its own behind these checks
+    if ((size_t)scratch & 3u) return td_fail("%s: scratch_dev = %p is not 4-byte aligned", who, scratch);
+    const size_t ng = refine_extent(gpitch, rows, cols), nm = refine_extent(mpitch, rows, cols), ns = refine_scratch_bytes(rows, cols);
+    if (refine_overlap(scratch, ns, guide, ng)) return td_fail("%s: the scratch overlaps the guide (%zu bytes at %p against %zu bytes at %p)", who, ns, scratch, ng, (const void*)guide);
+    if (refine_overlap(scratch, ns, matte, nm)) return td_fail("%s: the scratch overlaps the matte (%zu bytes at %p against %zu bytes at %p)", who, ns, scratch, nm, (const void*)matte);
+    if (!want_out) return 0;
+    const size_t no = refine_extent(opitch, rows, cols);
+    if (refine_overlap(out, no, guide, ng)) return td_fail("%s: out overlaps the guide (%zu bytes at %p against %zu bytes at %p)", who, no, (const void*)out, ng, (const void*)guide);
+    if (refine_overlap(out, no, matte, nm)) return td_fail("%s: out overlaps the matte (%zu bytes at %p against %zu bytes at %p)", who, no, (const void*)out, nm, (const void*)matte);
+    if (refine_overlap(out, no, scratch, ns)) return td_fail("%s: out overlaps the scratch (%zu bytes at %p against %zu bytes at %p)", who, no, (const void*)out, ns, scratch);
+    return 0;
+}
+static int* refine_bq(void* scratch) { return (int*)scratch; }
+static short* refine_aq(void* scratch, int rows, int cols) { return (short*)((char*)scratch + (size_t)4 * rows * cols); }
+// the arguments are checked (refine_args_check); radius and eps travel as kernel arguments: a captured graph replays those of capture time
+static void launch_refine_coeff(const unsigned char* guide, size_t gpitch, const unsigned char* matte, size_t mpitch, int rows, int cols, int radius, int eps, void* scratch,
+                                hipStream_t s) {
+    TD_LAUNCH(k_refine_coeff, dim3((cols + TD_RF_TX - 1) / TD_RF_TX, (rows + TD_RF_CY - 1) / TD_RF_CY), dim3(256), td_rf_coeff_lds(radius), s, guide, gpitch, matte, mpitch,
+              refine_aq(scratch, rows, cols), refine_bq(scratch), rows, cols, radius, eps);
+}
+static void launch_refine_apply(const unsigned char* guide, size_t gpitch, unsigned char* out, size_t opitch, int rows, int cols, int radius, void* scratch, hipStream_t s) {
+    TD_LAUNCH(k_refine_apply, dim3((cols + TD_RF_TX - 1) / TD_RF_TX, (rows + TD_RF_AY - 1) / TD_RF_AY), dim3(256), td_rf_apply_lds(radius), s, guide, gpitch,
+              (const short*)refine_aq(scratch, rows, cols), (const int*)refine_bq(scratch), out, opitch, rows, cols, radius);
 }
 // regions out (td_regions.h): the seven launches, from the low-resolution logits (in != NULL: the first launch is the frame's label launch too and writes the
 // label bytes to labels_out, or to the workspace's map where the caller asks for none) or from a uint8 label map [H][W] the caller holds (labels_in, at any
@@ -777,8 +832,53 @@ static int run_runs_decode(int H, int W, const void* table, int fill, void* out,
     return 0;
 }
 
+// The refined matte of a frame at the source's size (td_refine.h k_refine_gather, then the operator's two launches): from the low-resolution logits and the class
+// set (map == NULL: the gather IS the frame's last launch) or from a matte map [H][W] the caller holds.  out: [Hs][Ws] bytes, rows opitch apart -- the caller's,
+// or rf.refined for the composite.  radius and eps are read NOW.  10 instantiations: the composite's 5 source forms x fused / from a map.
+#define TD_GATHER_SRCS(X) X(P24) X(P32) X(NV12) X(SURF8) X(SURF16)
+static int refine_ready(const RefineState& rf, const U8Input& u, const char* who) {
+    if (rf.radius < 1) return td_fail("%s: the matte refinement is not configured (call tdnet_set_matte_refine with a radius of 1..%d first)", who, TD_RF_MAX_RADIUS);
+    if (!rf.luma || rf.Hs != u.Hs || rf.Ws != u.Ws) return td_fail("%s: the refined matte's workspace for this source size is missing (its allocation failed)", who);
+    return 0;
+}
+static int launch_refine_gather(const GatherArgs& a, const U8Input& u, const unsigned char* src, hipStream_t s) {
+    const int src_form = picture_src_form(u, false);
+    const SrcLayout l = src_layout(u);
+    const dim3 rows = out_grid(a.ow, a.oh);
+    switch (src_form) {
+#define TD_G(SRC) case TD_SRC_##SRC: \
+        if (a.map) TD_LAUNCH((k_refine_gather<true, TD_SRC_##SRC>), rows, dim3(256), 0, s, a, src, l); \
+        else TD_LAUNCH((k_refine_gather<false, TD_SRC_##SRC>), rows, dim3(256), 0, s, a, src, l); \
+        return 0;
+    TD_GATHER_SRCS(TD_G)
+#undef TD_G
+    }
+    return td_fail("internal: no gather kernel for source form %d", src_form);
+}
+static int run_refine_frame(const float* in, int C, int h, int w, const unsigned char* map, const MatteSet& set, const OverlayOutput& o, const U8Input& u,
+                            const unsigned char* src, const RefineState& rf, unsigned char* out, size_t opitch, hipStream_t s, const char* who) {
+    if (!o.Hs || o.Hs != u.Hs || o.Ws != u.Ws || o.H != u.H || o.W != u.W) return td_fail("%s: the index tables of this source size are missing (their allocation failed)", who);
+    TD_TRY(refine_ready(rf, u, who));
+    TD_TRY(out_check("refined matte", "src_height", o.Hs, map ? 1 : C));
+    GatherArgs a = GatherArgs();
+    a.in = in; a.map = map; a.ys = o.ys; a.xs = o.xs;
+    a.C = C; a.h = h; a.w = w; a.H = o.H; a.W = o.W; a.oh = o.Hs; a.ow = o.Ws;
+    a.swap = u.swap ? 1 : 0; a.luma = rf.luma; a.msrc = rf.msrc; a.set = set;
+    TD_TRY(launch_refine_gather(a, u, src, s));
+    launch_refine_coeff(rf.luma, (size_t)rf.Ws, rf.msrc, (size_t)rf.Ws, rf.Hs, rf.Ws, rf.radius, rf.eps, rf.scratch, s);
+    launch_refine_apply(rf.luma, (size_t)rf.Ws, out, opitch, rf.Hs, rf.Ws, rf.radius, rf.scratch, s);
+    return 0;
+}
+// the composite through the refined matte: the three launches into the workspace's map, then the EXISTING composite kernel from that map
+static int run_refined_composite(const float* in, int C, int h, int w, const unsigned char* map, const MatteSet& set, const OverlayOutput& o, const U8Input& u,
+                                 const unsigned char* src, const CompositeOutput& c, const DstOutput& d, const RefineState& rf, unsigned char* base, hipStream_t s, const char* who) {
+    TD_TRY(composite_dst_check(u, c, d, who));                         // before the first launch
+    TD_TRY(run_refine_frame(in, C, h, w, map, set, o, u, src, rf, rf.refined, (size_t)rf.Ws, s, who));
+    return launch_composite(nullptr, 0, 0, 0, rf.refined, set, o, u, src, c, d, base, s, &rf);
+}
+
 // What leaves a frame: the form and the pointers that form needs (device memory of the caller's)
-enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS, OUT_TRACKS, OUT_RUNS };
+enum OutKind { OUT_LOGITS, OUT_LABELS_I32, OUT_LABELS_U8, OUT_RGB, OUT_SCORE, OUT_CONF, OUT_OVERLAY, OUT_MATTE, OUT_COMPOSITE, OUT_REGIONS, OUT_TRACKS, OUT_RUNS, OUT_MATTE_REFINED };
 struct FrameOutput {
     OutKind kind;
     void* dst;                     // fp32 logits [C][H][W] | int32 labels [H][W] | uint8 labels [H][W] (OUT_SCORE, OUT_CONF, OUT_MATTE: may be NULL) | rgb [oh][ow][3] | overlay, composite [Hs][Ws][3]
@@ -798,10 +898,13 @@ static int output_configured(const tdnet* n, OutKind kind, const char* who) {
     if ((kind == OUT_REGIONS || kind == OUT_TRACKS) && !n->regions.set) return td_fail("%s: the regions output is not configured (call tdnet_set_regions first)", who);
     if (kind == OUT_RUNS && !n->runs.set) return td_fail("%s: the runs output is not configured (call tdnet_set_runs first)", who);
     if (kind == OUT_TRACKS && !n->tracks.set) return td_fail("%s: the tracks output is not configured (call tdnet_set_tracks first)", who);
-    if ((kind == OUT_MATTE || kind == OUT_COMPOSITE) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
+    if ((kind == OUT_MATTE || kind == OUT_COMPOSITE || kind == OUT_MATTE_REFINED) && !n->matte_set) return td_fail("%s: the class set of the matte is not configured (call tdnet_set_matte first)", who);
     if (kind == OUT_COMPOSITE && !n->comp.set) return td_fail("%s: the composite output is not configured (call tdnet_set_output_composite first)", who);
     if (kind == OUT_COMPOSITE && !n->u8.set)
         return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or one of its siblings first): the composite is written at its source size", who);
+    if (kind == OUT_MATTE_REFINED && !n->u8.set)
+        return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or one of its siblings first): the refined matte is written at its source size", who);
+    if (kind == OUT_MATTE_REFINED) TD_TRY(refine_ready(n->refine, n->u8, who));
     if (kind == OUT_OVERLAY && !n->overlay.set) return td_fail("%s: the overlay output is not configured (call tdnet_set_output_overlay first)", who);
     if (kind == OUT_OVERLAY && !n->u8.set)
         return td_fail("%s: the byte input is not configured (call tdnet_set_input_u8 or tdnet_set_input_nv12 first): the overlay is written at its source size", who);
@@ -823,7 +926,11 @@ static int emit_output(tdnet* n, const FrameOutput& o, hipStream_t s, const char
     case OUT_SCORE: return launch_upsample_argmax_score(in, C, h, w, H, W, o.gt, n->score.dmap, (unsigned char*)o.dst, n->score.cm, s);
     case OUT_CONF: return launch_upsample_argmax_conf_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->min_conf, n->reject_label, s);
     case OUT_MATTE: return launch_upsample_argmax_matte_u8(in, C, h, w, H, W, (unsigned char*)o.dst, o.conf, n->matte, s);
-    case OUT_COMPOSITE: return launch_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, (unsigned char*)o.dst, s);
+    case OUT_COMPOSITE:
+        if (n->refine.radius) return run_refined_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, n->refine, (unsigned char*)o.dst, s, who);
+        return launch_composite(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->comp, n->dst, (unsigned char*)o.dst, s);
+    case OUT_MATTE_REFINED:
+        return run_refine_frame(in, C, h, w, nullptr, n->matte, n->overlay, n->u8, o.src, n->refine, (unsigned char*)o.dst, (size_t)n->u8.Ws, s, who);
     case OUT_REGIONS: return run_regions(in, C, h, w, H, W, nullptr, (unsigned char*)o.dst, o.ids, o.table, n->regions, s, who);
     case OUT_TRACKS: {
         int32_t* ids = o.ids ? o.ids : n->tracks.st.cur;

@@ -148,6 +148,7 @@ extern "C" void tdnet_destroy(tdnet_t* n) {
     regions_free(n->regions);
     tracks_free(n->tracks);
     runs_free(n->runs);
+    refine_free(n->refine);
     for (float* q : {n->wino_v2, n->wino_m2}) if (q) hipFree(q);
     for (auto* v : {&n->seg_t, &n->seg_r, &n->seg_x}) for (float* q : *v) if (q) hipFree(q);
     if (n->chain2) hipStreamDestroy(n->chain2);
@@ -291,11 +292,16 @@ extern "C" int tdnet_forward_u8_labels(tdnet_t* n, const uint8_t* img, int pos_i
 // The overlay's index tables belong to the pair (network size, source size): a byte-input configuration that changed the source size rebuilds them
 // (the caller has synchronised: the previous tables existed only beside a previous input configuration).  Nothing to do without an overlay.
 static int overlay_follow_input(tdnet* n, const char* who) {
-    if (!n->overlay.set && !n->comp.set) return 0;                    // the composite samples through the same tables
+    if (!n->overlay.set && !n->comp.set && !n->refine.radius) return 0;   // the composite and the refined matte sample through the same tables
     const size_t before = n->overlay.bytes;
     int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
     n->ws_bytes += n->overlay.bytes - before;
     if (!rc) rc = overlay_set_swap(n->overlay, n->u8.swap, who);       // the picture's colour order is the source's
+    if (!rc && n->refine.radius) {                                     // the refined matte's workspace is the source's size
+        const size_t rb = n->refine.bytes;
+        rc = refine_alloc(n->refine, n->u8.Hs, n->u8.Ws, who);
+        n->ws_bytes += n->refine.bytes - rb;
+    }
     return rc;
 }
 // The handle's ONE byte-input configuration, whichever entry describes it (not a frame call: it may synchronise; idempotent for equal arguments).  The
@@ -596,6 +602,7 @@ static int composite_args(const tdnet* n, bool fused, const uint8_t* src, const 
     const U8Input& u = n->u8;
     const DstOutput& d = n->dst;
     TD_TRY(composite_dst_check(u, n->comp, d, who));
+    if (n->refine.radius) TD_TRY(refine_ready(n->refine, u, who));
     const size_t nout = d.set ? d.extent : (size_t)3 * u.Hs * u.Ws, nsrc = u.extent;
     const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
     if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
@@ -613,7 +620,68 @@ extern "C" int tdnet_matte_composite(tdnet_t* n, const uint8_t* matte, const uin
     if (!n || !matte || !img || !out) return td_fail("tdnet_matte_composite: null argument");
     TD_TRY(composite_args(n, false, img, out, "tdnet_matte_composite"));
     TD_ON_DEVICE(n, -1);
+    if (n->refine.radius) TD_TRY(run_refined_composite(nullptr, 0, 0, 0, matte, n->matte, n->overlay, n->u8, img, n->comp, n->dst, n->refine, out, (hipStream_t)stream, "tdnet_matte_composite"));
+    else
     TD_TRY(launch_composite(nullptr, 0, 0, 0, matte, n->matte, n->overlay, n->u8, img, n->comp, n->dst, out, (hipStream_t)stream));
+    TD_HIP(hipGetLastError());
+    return 0;
+}
+// ---- refined matte ---------------------------------------------------------------------------------------------------------------------
+// Configuration (not a frame call: it may allocate and synchronise; idempotent for equal arguments; per handle; either order with the byte-input
+// configuration: the workspace follows the source size and is allocated here if the handle has a byte input, by that configuration otherwise).  radius 0 = off,
+// the default: the composite entries are then what they are without this call.  A failed call leaves the previous state in force.
+extern "C" int tdnet_set_matte_refine(tdnet_t* n, int radius, int eps) {
+    const char* who = "tdnet_set_matte_refine";
+    if (!n) return td_fail("%s: null handle", who);
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    if (radius != 0) TD_TRY(refine_range_check(radius, eps, who));
+    TD_ON_DEVICE(n, -1);
+    if (radius == 0) {
+        if (n->refine.luma) { TD_HIP(hipDeviceSynchronize()); n->ws_bytes -= n->refine.bytes; refine_free(n->refine); }
+        n->refine.radius = n->refine.eps = 0;
+        return 0;
+    }
+    if (n->u8.set) {
+        RefineState& r = n->refine;
+        if (r.luma && (r.Hs != n->u8.Hs || r.Ws != n->u8.Ws)) TD_HIP(hipDeviceSynchronize());
+        const size_t ob = n->overlay.bytes, rb = r.bytes;
+        int rc = overlay_tables(n->overlay, n->H, n->W, n->u8.Hs, n->u8.Ws, who);
+        n->ws_bytes += n->overlay.bytes - ob;
+        if (!rc) rc = overlay_set_swap(n->overlay, n->u8.swap, who);
+        if (!rc) rc = refine_alloc(r, n->u8.Hs, n->u8.Ws, who);
+        n->ws_bytes += r.bytes - rb;
+        TD_TRY(rc);
+    }
+    n->refine.radius = radius;
+    n->refine.eps = eps;
+    return 0;
+}
+// What the two refined-matte frame entries check on the host before anything is enqueued
+static int refined_args(const tdnet* n, const uint8_t* src, const uint8_t* out, const char* who) {
+    if (!n->finalized || !n->ws_ready) return td_fail("%s: weights not finalized", who);
+    TD_TRY(output_configured(n, OUT_MATTE_REFINED, who));
+    const size_t nout = (size_t)n->u8.Hs * n->u8.Ws, nsrc = n->u8.extent;
+    const uintptr_t s0 = (uintptr_t)src, o0 = (uintptr_t)out;
+    if (s0 < o0 + nout && o0 < s0 + nsrc) return td_fail("%s: out overlaps the source frame (%zu bytes at %p against %zu bytes at %p)", who, nout, (const void*)out, nsrc, (const void*)src);
+    return 0;
+}
+// The labels entries with the other end: the refined matte [Hs][Ws] at the source's size; tdnet_last_launch_count = the label entry's + 2
+extern "C" int tdnet_forward_u8_matte_refined(tdnet_t* n, const uint8_t* img, int pos_id, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_forward_u8_matte_refined: null argument");
+    TD_TRY(refined_args(n, img, out, "tdnet_forward_u8_matte_refined"));
+    return frame_out(n, frame_input_u8(n, img), pos_id, FrameOutput{OUT_MATTE_REFINED, out, nullptr, nullptr, img}, stream, "tdnet_forward_u8_matte_refined");
+}
+// The operator on maps the caller holds (td_refine.h): the handle gives the device, nothing else -- no configuration, no weights.  Every check is made
+// before the first launch; the two launches only enqueue.
+extern "C" size_t tdnet_refine_scratch_bytes(int rows, int cols) { return refine_scratch_bytes(rows, cols); }
+extern "C" int tdnet_refine_matte(tdnet_t* n, const uint8_t* guide, size_t guide_pitch, const uint8_t* matte, size_t matte_pitch, uint8_t* out, size_t out_pitch,
+                                  int rows, int cols, int radius, int eps, void* scratch, void* stream) {
+    const char* who = "tdnet_refine_matte";
+    if (!n) return td_fail("%s: null handle", who);
+    TD_TRY(refine_args_check(guide, guide_pitch, matte, matte_pitch, out, out_pitch, true, rows, cols, radius, eps, scratch, who));
+    TD_ON_DEVICE(n, -1);
+    launch_refine_coeff(guide, guide_pitch, matte, matte_pitch, rows, cols, radius, eps, scratch, (hipStream_t)stream);
+    launch_refine_apply(guide, guide_pitch, out, out_pitch, rows, cols, radius, scratch, (hipStream_t)stream);
     TD_HIP(hipGetLastError());
     return 0;
 }
@@ -689,6 +757,11 @@ extern "C" int tdnet_propagate_matte(tdnet_t* n, uint8_t* labels, uint8_t* matte
     if (!n || !matte) return td_fail("tdnet_propagate_matte: null argument");
     if (!n->finalized || !n->ws_ready) return td_fail("tdnet_propagate_matte: weights not finalized");
     return frame_out(n, pending_frame, FrameOutput{OUT_MATTE, labels, nullptr, matte}, stream, "tdnet_propagate_matte");
+}
+extern "C" int tdnet_propagate_matte_refined(tdnet_t* n, const uint8_t* img, uint8_t* out, void* stream) {
+    if (!n || !img || !out) return td_fail("tdnet_propagate_matte_refined: null argument");
+    TD_TRY(refined_args(n, img, out, "tdnet_propagate_matte_refined"));
+    return frame_out(n, pending_frame, FrameOutput{OUT_MATTE_REFINED, out, nullptr, nullptr, img}, stream, "tdnet_propagate_matte_refined");
 }
 extern "C" int tdnet_propagate_composite(tdnet_t* n, const uint8_t* img, uint8_t* out, void* stream) {
     if (!n || !img || !out) return td_fail("tdnet_propagate_composite: null argument");

@@ -775,6 +775,67 @@ extern "C" int tdnet_op_composite(const float* in, int C, int h, int w, int H, i
     u8_free(u);
     return rc;
 }
+// Stage 1 of the refined matte (include/tdnet.h "refined matte") alone, through the launch tdnet_refine_matte enqueues first: the coefficient planes a_q
+// (int16 [rows][cols]) and b_q (int32 [rows][cols]) of a guide and a matte at any byte addresses.  The scratch is allocated for the call.
+extern "C" int tdnet_op_refine_coeff(const uint8_t* guide, size_t guide_pitch, const uint8_t* matte, size_t matte_pitch, int rows, int cols, int radius, int eps,
+                                     int16_t* aq_dev, int32_t* bq_dev, void* stream) {
+    const char* who = "tdnet_op_refine_coeff";
+    if (!aq_dev || !bq_dev) return td_fail("%s: null argument", who);
+    TD_TRY(refine_args_check(guide, guide_pitch, matte, matte_pitch, nullptr, 0, false, rows, cols, radius, eps, nullptr, who));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)rows * cols;
+    void* scratch = nullptr;
+    if (hipMalloc(&scratch, refine_scratch_bytes(rows, cols)) != hipSuccess) return td_fail("%s: hipMalloc failed", who);
+    int rc = 0;
+    launch_refine_coeff(guide, guide_pitch, matte, matte_pitch, rows, cols, radius, eps, scratch, s);
+    if (hipMemcpyAsync(aq_dev, refine_aq(scratch, rows, cols), 2 * n, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(bq_dev, refine_bq(scratch), 4 * n, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = td_fail("%s: copy failed", who);
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    hipFree(scratch);
+    return rc;
+}
+// The gather launch of the refined frame entries (td_refine.h k_refine_gather) alone: luma and M_src [Hs][Ws] (tight, device, 4-byte aligned) of the source at
+// src_base read through src_surface or src_view, the matte from low-resolution logits [C][h][w] and the class set (matte_u8 == NULL) or from a map [H][W].
+extern "C" int tdnet_op_refine_gather(const float* in, int C, int h, int w, int H, int W, const uint8_t* classes, int n, const uint8_t* matte_u8, const uint8_t* src_base,
+                                      const tdnet_view* src_view, const tdnet_surface* src_surface, uint8_t* luma_dev, uint8_t* msrc_dev, void* stream) {
+    const char* who = "tdnet_op_refine_gather";
+    if (!src_base || !luma_dev || !msrc_dev || (!src_view && !src_surface)) return td_fail("%s: src_base, the two planes and src_view or src_surface expected", who);
+    if (((size_t)luma_dev | (size_t)msrc_dev) & 3u) return td_fail("%s: the planes must be 4-byte aligned", who);
+    if (H < 1 || W < 1) return td_fail("%s: a network size >= 1 x 1 expected", who);
+    if (!matte_u8 && (!in || C < 1 || C > 256 || h < 1 || w < 1)) return td_fail("%s: logits [C,h,w] with C in 1..256 expected", who);
+    if (!matte_u8 && (n < 0 || n > 256 || (n > 0 && !classes))) return td_fail("%s: n in 0..256 class ids expected", who);
+    MatteSet set = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; !matte_u8 && i < n; ++i) {
+        if (classes[i] >= C) return td_fail("%s: classes[%d] = %d is not a class id (C = %d)", who, i, (int)classes[i], C);
+        set.w[classes[i] >> 5] |= 1u << (classes[i] & 31);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    U8Input u;
+    OverlayOutput o;
+    SrcView sv;
+    int Hs = 0, Ws = 0;
+    TD_TRY(src_surface ? surface_resolve(src_surface, sv, Hs, Ws, who) : view_resolve(src_view, sv, Hs, Ws, who));
+    TD_TRY(u8_build(u, sv, Hs, Ws, H, W, nullptr, nullptr, who));
+    int rc = overlay_tables(o, H, W, Hs, Ws, who);
+    if (!rc) {
+        GatherArgs a = GatherArgs();
+        a.in = in; a.map = matte_u8; a.ys = o.ys; a.xs = o.xs;
+        a.C = C; a.h = h; a.w = w; a.H = H; a.W = W; a.oh = Hs; a.ow = Ws;
+        a.swap = u.swap ? 1 : 0; a.luma = luma_dev; a.msrc = msrc_dev; a.set = set;
+        rc = launch_refine_gather(a, u, src_base, s);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) rc = td_fail("%s: device error", who);
+    overlay_free(o);
+    u8_free(u);
+    return rc;
+}
+// the tiles of the two launches (columns, rows of the coefficient launch's, rows of the apply launch's): the tests size their cases from them
+extern "C" int tdnet_op_refine_tile(int* tx, int* ty_coeff, int* ty_apply) {
+    if (tx) *tx = TD_RF_TX;
+    if (ty_coeff) *ty_coeff = TD_RF_CY;
+    if (ty_apply) *ty_apply = TD_RF_AY;
+    return 0;
+}
 // The index table the colour-map kernels sample through (rgb_build's: dataloader.nearest_index restated in C) -> out_host [n_dst] int32.  Host only.
 extern "C" int tdnet_op_nearest_index(int n_src, int n_dst, int32_t* out_host) {
     if (n_src < 1 || n_dst < 1 || !out_host) return td_fail("tdnet_op_nearest_index: sizes >= 1 and a host buffer expected");

@@ -564,6 +564,58 @@ def composite_u8(src_rgb, matte, H, W, bg=None):
     return out.astype(np.uint8)
 
 
+def luma_u8(rgb):
+    """The guide of a frame (include/tdnet.h "refined matte"): uint8 [..., 3] r g b -> uint8 [...], Y = (77 R + 150 G + 29 B + 128) >> 8.
+    The weights add up to 256, so grey (v, v, v) gives v and nothing needs a clamp."""
+    p = np.asarray(rgb)
+    assert p.dtype == np.uint8 and p.shape[-1] == 3
+    p = p.astype(np.int32)
+    return ((77 * p[..., 0] + 150 * p[..., 1] + 29 * p[..., 2] + 128) >> 8).astype(np.uint8)
+
+
+REFINE_MAX_RADIUS = 16
+REFINE_MIN_EPS, REFINE_MAX_EPS = 4, 65025
+
+
+def _box_sum(a, r):
+    """int64 [h, w]: the sum of `a` over the box of radius r around every pixel, clipped to the map (an integral image: exact)."""
+    h, w = a.shape
+    ii = np.zeros((h + 1, w + 1), np.int64)
+    ii[1:, 1:] = a.astype(np.int64).cumsum(0).cumsum(1)
+    y0, y1 = np.maximum(np.arange(h) - r, 0), np.minimum(np.arange(h) + r, h - 1) + 1
+    x0, x1 = np.maximum(np.arange(w) - r, 0), np.minimum(np.arange(w) + r, w - 1) + 1
+    return ii[y1][:, x1] - ii[y0][:, x1] - ii[y1][:, x0] + ii[y0][:, x0]
+
+
+def refine_matte_u8(guide, matte, radius, eps, want_coeff=False):
+    """The oracle of the library's refined matte (include/tdnet.h "refined matte"): He et al.'s guided filter of the matte bytes [h, w] with
+    the guide bytes [h, w], restated so that every step is an integer operation or ONE correctly rounded fp32 operation.  The window of a pixel
+    is the box of radius `radius` (1..16) clipped to the map, N its pixel count, S_x the sums over it; eps (4..65025) is in squared byte units.
+        cov = N S_GM - S_G S_M;   den = N S_GG - S_G^2 + eps N^2 (> 0);   a = f32(cov) / f32(den)
+        a_q = clamp(rint(a * 1024), -32767, 32767)                        the slope in Q10
+        b_q = rint(f32(1024 S_M - a_q S_G) / f32(16 N))                   the offset in Q6
+        A = sum a_q, B = sum b_q over the window;   out = clamp8(rint(f32(A G + 16 B) / f32(1024 N)))
+    The integers are int64 here; f32() is the round-to-nearest-even conversion, / the IEEE fp32 division, rint rounds halves to even.
+    want_coeff: (out, a_q int16 [h, w], b_q int32 [h, w])."""
+    G, M = np.asarray(guide), np.asarray(matte)
+    assert G.dtype == np.uint8 and M.dtype == np.uint8 and G.ndim == 2 and G.shape == M.shape and G.size > 0
+    r, eps = int(radius), int(eps)
+    assert 1 <= r <= REFINE_MAX_RADIUS and REFINE_MIN_EPS <= eps <= REFINE_MAX_EPS, (radius, eps)
+    g, m = G.astype(np.int64), M.astype(np.int64)
+    N = _box_sum(np.ones_like(g), r)
+    SG, SM, SGG, SGM = _box_sum(g, r), _box_sum(m, r), _box_sum(g * g, r), _box_sum(g * m, r)
+    cov = N * SGM - SG * SM
+    den = N * SGG - SG * SG + eps * N * N
+    assert den.min() > 0
+    f32 = lambda v: v.astype(np.float32)
+    a = f32(cov) / f32(den)
+    aq = np.clip(np.rint(a * np.float32(1024.0)), -32767, 32767).astype(np.int64)
+    bq = np.rint(f32(1024 * SM - aq * SG) / f32(16 * N)).astype(np.int64)
+    A, B = _box_sum(aq, r), _box_sum(bq, r)
+    out = np.clip(np.rint(f32(A * g + 16 * B) / f32(1024 * N)), 0, 255).astype(np.uint8)
+    return (out, aq.astype(np.int16), bq.astype(np.int32)) if want_coeff else out
+
+
 # One record of the library's regions table (include/tdnet.h tdnet_region, 48 bytes): the box is inclusive, the centroid is sum / area
 REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("first_y", "<i4"), ("first_x", "<i4"),
                          ("sum_x", "<u8"), ("sum_y", "<u8")])

@@ -359,6 +359,28 @@ class Engine:
     def matte_composite(self, matte_ptr, img_ptr, out_ptr, stream=None):
         self.lib.check(self.lib.tdnet_matte_composite(self.h, _ptr(matte_ptr), _ptr(img_ptr), _ptr(out_ptr), stream))
 
+    # ---- refined matte (include/tdnet.h) ----
+    def set_matte_refine(self, radius, eps=65):
+        """radius 1..16 and eps 4..65025 (squared byte units): the composite entries composite through the guided-filtered matte, and the *_matte_refined
+        entries write it at the source's size.  radius 0: off (the default).  A configuration call; before or after the byte-input configuration."""
+        self.lib.check(self.lib.tdnet_set_matte_refine(self.h, int(radius), int(eps)))
+
+    def forward_u8_matte_refined(self, img_ptr, pos_id, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_forward_u8_matte_refined(self.h, _ptr(img_ptr), int(pos_id), _ptr(out_ptr), stream))
+
+    def propagate_matte_refined(self, img_ptr, out_ptr, stream=None):
+        self.lib.check(self.lib.tdnet_propagate_matte_refined(self.h, _ptr(img_ptr), _ptr(out_ptr), stream))
+
+    def refine_scratch_bytes(self, rows, cols):
+        """bytes of the scratch refine_matte needs for a map of rows x cols (6 per pixel; 4-byte aligned device memory of the caller's)"""
+        return int(self.lib.tdnet_refine_scratch_bytes(int(rows), int(cols)))
+
+    def refine_matte(self, guide_ptr, guide_pitch, matte_ptr, matte_pitch, out_ptr, out_pitch, rows, cols, radius, eps, scratch_ptr, stream=None):
+        """The guided filter of the matte bytes [rows, cols] with the guide bytes, rows `pitch` bytes apart at any byte addresses -> out.  Needs no
+        configuration; only enqueues (two launches)."""
+        self.lib.check(self.lib.tdnet_refine_matte(self.h, _ptr(guide_ptr), int(guide_pitch), _ptr(matte_ptr), int(matte_pitch), _ptr(out_ptr), int(out_pitch),
+                                                   int(rows), int(cols), int(radius), int(eps), _ptr(scratch_ptr), stream))
+
     # ---- regions out (include/tdnet.h) ----
     def set_regions(self, classes, connectivity=8, max_regions=256, min_area=1):
         """The *_regions entries will label the connected components (4 or 8 neighbours, same label) of this class set, drop those below min_area and

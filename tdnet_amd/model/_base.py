@@ -989,6 +989,40 @@ class _TDNetBase(nn.Module):
         self._u8_call(img, (H, W), one, mean, std, view=view)
         return out, matte
 
+    _refine = (0, 65)
+
+    def set_matte_refine(self, radius, eps=65):
+        """The refined matte (include/tdnet.h "refined matte"): radius 1..16 and eps 4..65025 (squared byte units; 65 ~ 1e-3 * 255^2) -- the composite methods
+        then composite through the matte guided-filtered by the frame's luma at the frame's own size, and forward_matte_refined_u8 / propagate(matte_refined=True)
+        return that matte.  radius 0: off, the default.  Host state of the model; every handle is told when it runs.  Returns (radius, eps)."""
+        if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= 16:
+            raise RuntimeError("set_matte_refine(): radius must be 0 (off) or in 1..16, got %r" % (radius,))
+        if int(radius) and (isinstance(eps, bool) or int(eps) != eps or not 4 <= int(eps) <= 65025):
+            raise RuntimeError("set_matte_refine(): eps must be in 4..65025 (squared byte units), got %r" % (eps,))
+        self._refine = (int(radius), int(eps) if int(radius) else 0)
+        return self._refine
+
+    def forward_matte_refined_u8(self, img_u8, pos_id=0, in_size=None, mean=None, std=None, view=None, surface=None):
+        """forward_labels_u8() with the refined matte in place of the label map: bytes in, uint8 [N, Hs, Ws] out -- the matte of set_matte()'s class set at the
+        frame's own (a view's rectangle's) size, guided-filtered by the frame's luma with set_matte_refine()'s radius and eps."""
+        ids = self._need_matte("forward_matte_refined_u8")
+        if not self._refine[0]:
+            raise RuntimeError("forward_matte_refined_u8(): no refinement (call set_matte_refine(radius, eps) with a radius of 1..16 first)")
+        view = self._one_of(view, surface, "view", "surface")
+        if view is not None:
+            self._check_frame_view(img_u8, view)
+        H, W = self._check_frame_u8(img_u8, pos_id, in_size, view)
+        img = img_u8.contiguous()
+        size = tuple(view.size) if view is not None else (int(img.shape[1]), int(img.shape[2]))
+        out = torch.empty((img.shape[0],) + size, device=img.device, dtype=torch.uint8)
+
+        def one(i, eng, s):
+            eng.set_matte(ids)
+            eng.set_matte_refine(*self._refine)
+            eng.forward_u8_matte_refined(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
+        self._u8_call(img, (H, W), one, mean, std, view=view)
+        return out
+
     def logits_matte(self, logits):
         """The unfused form: logits [N, nclass, H, W] (fp32, CUDA) of this model -> (labels uint8 [N, H, W], matte uint8 [N, H, W])."""
         ids = self._need_matte("logits_matte")
@@ -1005,6 +1039,28 @@ class _TDNetBase(nn.Module):
         for i in range(logits.shape[0]):
             self._engine.logits_matte(logits[i].data_ptr(), out[i].data_ptr(), matte[i].data_ptr(), s)
         return out, matte
+
+    def refine_matte(self, guide, matte, radius, eps=65):
+        """The refined matte (include/tdnet.h "refined matte"): the guided filter of matte uint8 [N, h, w] (or [h, w]) with guide uint8 of the same shape,
+        both CUDA, any size -> uint8 of that shape.  radius 1..16; eps 4..65025 in squared byte units (65 ~ 1e-3 * 255^2).  The rows of either input may
+        be a strided view (stride(-1) == 1); needs no configuration, only a handle for its device.  dataloader.luma_u8 is the guide of a frame."""
+        if self._engine is None:
+            raise RuntimeError("refine_matte(): no handle yet")
+        for name, t in (("guide", guide), ("matte", matte)):
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (2, 3) or t.numel() == 0:
+                raise RuntimeError("refine_matte(): %s must be a non-empty uint8 CUDA tensor [N, h, w] or [h, w]" % name)
+        if guide.shape != matte.shape:
+            raise RuntimeError("refine_matte(): guide %s and matte %s differ in shape" % (tuple(guide.shape), tuple(matte.shape)))
+        g3, m3 = (guide, matte) if guide.dim() == 3 else (guide[None], matte[None])
+        rows = lambda t: t if t.stride(-1) == 1 and t.stride(-2) >= t.shape[-1] else t.contiguous()
+        g3, m3 = rows(g3), rows(m3)
+        n, h, w = g3.shape
+        out = torch.empty((n, h, w), device=g3.device, dtype=torch.uint8)
+        scratch = torch.empty(((self._engine.refine_scratch_bytes(h, w) + 3) // 4,), device=g3.device, dtype=torch.int32)
+        s = torch.cuda.current_stream(g3.device).cuda_stream
+        for i in range(n):
+            self._engine.refine_matte(g3[i].data_ptr(), g3.stride(1), m3[i].data_ptr(), m3.stride(1), out[i].data_ptr(), w, h, w, radius, eps, scratch.data_ptr(), s)
+        return out if guide.dim() == 3 else out[0]
 
     # ---- regions out (not in the reference's model; a caller of the reference downloads the labels and runs a connected-components pass on the host) ----
     # The connected components of a class set of the frame's labels, numbered by their first pixel, with area, box and coordinate sums (include/tdnet.h
@@ -1379,6 +1435,7 @@ class _TDNetBase(nn.Module):
         def one(i, eng, s):
             eng.set_matte(ids)
             eng.set_output_composite(bg)
+            eng.set_matte_refine(*self._refine)
             self._set_out(eng, out_view)
             eng.forward_u8_composite(img[i].data_ptr(), pos_id, out[i].data_ptr(), s)
         self._u8_call(img, (H, W), one, mean, std, view=view)
@@ -1396,7 +1453,7 @@ class _TDNetBase(nn.Module):
         eng.encode(img.data_ptr(), pos_id, torch.cuda.current_stream(img.device).cuda_stream)
 
     def propagate(self, labels=False, out_size=None, palette=None, gt=None, gt_map=None, conf=False, src=None, alpha=0.5, src_size=None,
-                  uv_offset=None, standard=0, matte=False, composite=False, background=(0, 0, 0)):
+                  uv_offset=None, standard=0, matte=False, composite=False, background=(0, 0, 0), matte_refined=False):
         """Second half of forward() for the pending frame, against the FIFO as it stands; returns logits, int32 labels (labels=True),
         uint8 labels (labels="u8"), the colour map [1, oh, ow, 3] (labels="rgb", with out_size=(oh, ow) and a palette as forward_rgb) or, with
         labels="score" and gt=uint8 [1, H, W], the uint8 labels of a frame whose counts were added to the handle's matrix (forward_score).
@@ -1407,9 +1464,29 @@ class _TDNetBase(nn.Module):
         matte=True: (uint8 labels, uint8 matte), both [1, H, W], as forward_matte gives them.  composite=True with src = the packed RGB frame that
         was encoded (uint8 [1, Hs, Ws, 3]): the composite [1, Hs, Ws, 3] over `background` as forward_composite_u8 gives it -- into the contiguous block: like
         every picture method called without out_view it sets the handle's destination view to none (the model classes name the destination per call; a
-        view set on the engine by hand does not survive it)."""
+        view set on the engine by hand does not survive it).  matte_refined=True with the same src: the refined matte [1, Hs, Ws] as
+        forward_matte_refined_u8 gives it."""
         if self._engine is None or self._pending_shape is None:
             raise RuntimeError("propagate(): no encoded frame is pending (call encode(img, pos_id) first)")
+        if matte_refined:
+            who = "propagate(matte_refined=True)"
+            if matte or composite or conf or labels:
+                raise RuntimeError("%s: asks for one last kernel; conf, matte, composite or labels=%r ask for another" % (who, labels))
+            ids = self._need_matte("propagate")
+            if not self._refine[0]:
+                raise RuntimeError("%s: no refinement (call set_matte_refine(radius, eps) with a radius of 1..16 first)" % who)
+            H, W, dev = self._pending_shape
+            key = getattr(self._engine, "_u8_key", None)
+            if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() != 4 or src.shape[0] != 1 or src.shape[3] != 3 or key is None or \
+                    tuple(src.shape[1:3]) != tuple(key[:2]) or src.device != dev:
+                raise RuntimeError("%s: src must be the packed RGB frame that was encoded with encode_u8, uint8 [1, Hs, Ws, 3] on %s" % (who, dev))
+            img = src.contiguous()
+            out = torch.empty(tuple(img.shape[:3]), device=dev, dtype=torch.uint8)
+            self._engine.set_matte(ids)
+            self._engine.set_matte_refine(*self._refine)
+            self._pending_shape = None
+            self._engine.propagate_matte_refined(img.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
         if matte or composite:
             who = "propagate(matte=True)" if matte else "propagate(composite=True)"
             if (matte and composite) or conf or labels in ("rgb", "score", "overlay"):
@@ -1434,6 +1511,7 @@ class _TDNetBase(nn.Module):
             out = torch.empty(tuple(img.shape), device=dev, dtype=torch.uint8)
             self._engine.set_matte(ids)
             self._engine.set_output_composite(bg)
+            self._engine.set_matte_refine(*self._refine)
             self._engine.set_output_view(None)
             self._pending_shape = None
             self._engine.propagate_composite(img.data_ptr(), out.data_ptr(), s)

@@ -33,6 +33,8 @@ destination surface, appended to the raw file.
 softmax mass of that class set as a byte, 255 = certainly one of them (include/tdnet.h "matte out") -- and saves it at the network size as an 8-bit
 grey PNG DIR/folder/name beside the usual picture.  `--matte IDS --composite R,G,B` (with `--u8`, `--nv12` or `--yuv`) writes, where the overlay's
 picture would go, the frame seen through the matte over that background, at the frame's own (`--crop`: the rectangle's) size.
+`--refine R[,EPS]` with them (and a byte input) guided-filters the matte by the frame's luma (include/tdnet.h "refined matte"): `--matte_out` then writes the
+refined matte at the frame's own size (and no label picture), `--composite` composites through it.
 `--regions IDS` (a comma list of class ids; `--regions_conn 4|8`, `--regions_min_area N`) labels the connected components of those classes on the device
 behind every frame's labels (include/tdnet.h "regions out") and prints the count per frame (`--tracks [MIN_OVERLAP]` follows them across frames, "tracks out":
 matched / born / ended per frame, and the columns track,age,origin in the CSVs); `--regions_out DIR` writes one CSV per frame,
@@ -157,6 +159,20 @@ def test(args):
             if len(composite) != 3 or any(v < 0 or v > 255 for v in composite):
                 raise SystemExit("--composite: R,G,B expected (the background, three byte values), got %r" % (args.composite,))
     with_matte = matte_ids is not None
+    refine = getattr(args, "refine", None)
+    if refine is not None:                                             # checked before anything is loaded
+        if not with_matte:
+            raise SystemExit("--refine filters the matte: give --matte IDS with --matte_out DIR or --composite R,G,B with it")
+        if not bytes_in:
+            raise SystemExit("--refine takes the frame's own luma as its guide: give --u8, --nv12 or --yuv with it (an fp32 tensor has no source bytes)")
+        try:
+            refine = tuple(int(v) for v in str(refine).split(","))
+        except ValueError:
+            refine = ()
+        if len(refine) == 1:
+            refine = refine + (65,)
+        if len(refine) != 2 or not 1 <= refine[0] <= 16 or not 4 <= refine[1] <= 65025:
+            raise SystemExit("--refine: R[,EPS] expected, a radius in 1..16 and eps in 4..65025 (squared byte units, default 65), got %r" % (args.refine,))
     region_ids, regions_dir = getattr(args, "regions", None), getattr(args, "regions_out", None)
     regions_conn, regions_min_area = getattr(args, "regions_conn", None), getattr(args, "regions_min_area", None)
     if region_ids is not None or regions_dir is not None or regions_conn is not None or regions_min_area is not None:   # checked before anything is loaded
@@ -257,6 +273,8 @@ def test(args):
 
     if with_matte:
         model.set_matte(matte_ids)
+    if refine is not None:
+        model.set_matte_refine(*refine)
     if with_regions:
         model.set_regions(region_ids, regions_conn, REGIONS_CLI_MAX, regions_min_area)
     if with_tracks:
@@ -438,6 +456,9 @@ def test(args):
                 output = pictures_nv12(l8, image, ori_size, src_size, view, folder)
             elif composite is not None:
                 output = model.forward_composite_u8(image, i % path_num, (H, W), background=composite, **vk(view))
+            elif with_matte and refine is not None:                    # --matte_out with --refine: the refined matte at the frame's own size, no label picture
+                matte = model.forward_matte_refined_u8(image, i % path_num, (H, W), **vk(view))
+                output = None
             elif with_matte:
                 output, matte = model.forward_matte_u8(image, i % path_num, (H, W), **vk(view)) if byte else model.forward_matte(image, i % path_num)
             elif with_tracks:
@@ -472,6 +493,10 @@ def test(args):
                 timer += elapsed_time
             if gt is not None:
                 save(output.cpu().numpy(), img_name, folder, ori_size)
+            elif with_matte and composite is None and refine is not None:
+                os.makedirs(os.path.join(matte_dir, folder), exist_ok=True)
+                from PIL import Image
+                Image.fromarray(np.squeeze(matte.cpu().numpy(), axis=0)).save(os.path.join(matte_dir, folder, img_name))
             elif with_matte and composite is None:
                 save_matte(output.cpu().numpy(), matte.cpu().numpy(), img_name, folder, ori_size)
             elif with_regions:                                         # the usual picture of the uint8 labels, and the frame's regions
@@ -527,6 +552,7 @@ if __name__ == "__main__":
     parser.add_argument("--min_conf", nargs="?", type=float, default=None, help="reject labels whose softmax probability is below this (0..1): label 255, grey in the picture")
     parser.add_argument("--matte", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13,14,15,16,17,18): the class set of --matte_out / --composite")
     parser.add_argument("--matte_out", nargs="?", type=str, default=None, help="with --matte: directory for each frame's matte (8-bit grey PNG at the network size; 255 = certainly a member of the set)")
+    parser.add_argument("--refine", nargs="?", type=str, default=None, help="with --matte and --u8, --nv12 or --yuv: R[,EPS] -- guided-filter the matte by the frame's luma (radius 1..16, eps 4..65025 in squared byte units, default 65): --matte_out then writes the refined matte at the frame's own size, --composite uses it")
     parser.add_argument("--composite", nargs="?", type=str, default=None, help="with --matte and --u8, --nv12 or --yuv: R,G,B -- write the frame seen through the matte over this background, at the frame's own size, where the overlay's picture would go")
     parser.add_argument("--regions", nargs="?", type=str, default=None, help="comma list of class ids (e.g. 11,12,13): label the connected components of these classes on the device behind every frame's labels")
     parser.add_argument("--regions_conn", nargs="?", type=int, default=None, help="with --regions: 4 or 8 neighbours (default 8)")
